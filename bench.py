@@ -16,6 +16,7 @@ with its own value / ms_per_step / roofline / cpu_baseline):
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29511 bench.py --gpus 8 --steps 10 --warmup 2
     python bench.py --workload schnet4096      # one workload alone as the printed line
+    python bench.py --steps 10 --dump-outputs DIR  # + what the last timed pass of the headline computed, as DIR/<name>.npy
 """
 import argparse
 import json
@@ -310,10 +311,38 @@ def _ordered_config(cfg):
     return out
 
 
-def run_lj108(args, rank, world, dev, mdist, with_cpu=True, form="lj", dt=None, steps=None, warmup=None):
+DUMP_BUDGET_BYTES = 48 << 20        # --dump-outputs: the sampled trajectories stay well inside 64 MB in all
+DUMP_SEED = 20240601
+
+
+def dump_lj108_outputs(out_dir, last, params):
+    """What the caller of one timed lj108 pass receives, written as <out_dir>/<name>.npy (float32; float64 for the indices):
+    the loss, the RDF g(r), the parameters after the optimizer step and the gradient that step applied, and v_t / q_t / pv_t
+    of a fixed, seeded sample of the replicas (all of them when they fit the budget), `replicas` the sampled indices."""
+    v_t, q_t, pv_t, g, loss = last
+    R = q_t.shape[0]
+    per_replica = 4 * (v_t[0].numel() + q_t[0].numel() + pv_t[0].numel())
+    k = min(R, DUMP_BUDGET_BYTES // per_replica)
+    if k < 1:
+        raise SystemExit("--dump-outputs: one replica's trajectory (%d bytes) exceeds the dump budget" % per_replica)
+    idx = np.arange(R) if k == R else np.sort(np.random.default_rng(DUMP_SEED).choice(R, size=k, replace=False))
+    sel = torch.from_numpy(idx).to(q_t.device)
+    arrays = {"loss": loss.detach().reshape(()), "g": g.detach(),
+              "theta": torch.cat([p.detach().reshape(-1) for p in params]),
+              "theta_grad": torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1) for p in params]),
+              "v_t": v_t.detach().index_select(0, sel), "q_t": q_t.detach().index_select(0, sel),
+              "pv_t": pv_t.detach().index_select(0, sel)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, x in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), x.float().cpu().numpy())
+    np.save(os.path.join(out_dir, "replicas.npy"), idx.astype(np.float64))
+
+
+def run_lj108(args, rank, world, dev, mdist, with_cpu=True, form="lj", dt=None, steps=None, warmup=None, dump=None):
     """form "lj": LennardJones(1, 1), the headline.  form "exvol": the reference README's own demo model,
     ExcludedVolume(sigma 1, epsilon 1, power 12) at its dt = 0.01 (README.md:70-85): the same ring kernels -- the even-power
-    polynomial with the attractive coefficient 0."""
+    polynomial with the attractive coefficient 0.  dump: a directory that receives what the last timed pass computed
+    (rank 0, `dump_lj108_outputs`)."""
     import copy
     args = copy.copy(args)
     if dt is not None:
@@ -367,6 +396,8 @@ def run_lj108(args, rank, world, dev, mdist, with_cpu=True, form="lj", dt=None, 
         mdist.all_reduce_grads(params)           # the one collective per outer step
         opt.step()
         step.last_q = q_t
+        if dump:
+            step.last = (v_t, q_t, pv_t, g, loss)
         return loss
 
     for _ in range(args.warmup):
@@ -382,6 +413,8 @@ def run_lj108(args, rank, world, dev, mdist, with_cpu=True, form="lj", dt=None, 
     el = mdist.max_over_ranks(el_rank, dev)
     if not (_finite(step.last_q) and all(_finite(p) for p in params)):
         raise SystemExit("bench: non-finite trajectory or parameters -- the measurement would be invalid")
+    if dump and rank == 0:
+        dump_lj108_outputs(dump, step.last, params)
     md_steps = R * (T - 1) * world * args.steps
     label = "LJ(1,1)" if form == "lj" else "ExcludedVolume(sigma 1, eps 1, power 12)"
     out = {"metric": "MD steps/sec (fwd+adjoint), 108-atom %s NHC" % ("LJ" if form == "lj" else "ExcludedVolume"), "value": md_steps / el,
@@ -1500,7 +1533,14 @@ def main():
                                                              "there: headline + lj4096 + schnet4096 only)")
     ap.add_argument("--full-line", action="store_true", help="print the un-compacted record as the last line (default: compact "
                                                               "line; the full record goes to gpurun_out/bench_full.json)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed pass computed as DIR/<name>.npy (lj108 / exvol108 "
+                         "and the headline of --workload all; inputs are seeded, so two builds can be compared output for output)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload not in ("all", "lj108", "exvol108"):
+        ap.error("--dump-outputs covers the 108-atom workloads (all, lj108, exvol108)")
     if args.bf16_rows:
         args.bf16 = True
 
@@ -1527,12 +1567,12 @@ def main():
     elif args.workload == "water192x64":
         out = run_water192_stacked(args, rank, world, dev, mdist, R=args.replicas or 64, steps=args.steps, warmup=args.warmup)
     elif args.workload == "exvol108":
-        out = run_lj108(args, rank, world, dev, mdist, cpu, form="exvol", dt=0.01)
+        out = run_lj108(args, rank, world, dev, mdist, cpu, form="exvol", dt=0.01, dump=args.dump_outputs)
     else:
         global _DEFERRED
         if args.workload == "all" and not args.no_secondary:
             _DEFERRED = []                      # (every timed GPU leg first, the CPU legs afterwards: see _DEFERRED)
-        out = run_lj108(args, rank, world, dev, mdist, cpu)
+        out = run_lj108(args, rank, world, dev, mdist, cpu, dump=args.dump_outputs)
         if args.workload == "all" and not args.no_secondary:
             sec = {}
             import copy

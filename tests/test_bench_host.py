@@ -115,3 +115,31 @@ def test_compulsory_bytes_of_the_fused_adjoint_launch():
     b = bench._lj108_compulsory_bytes(108, 16384, 50, 2)
     per_step_replica = b / (16384 * 49.0)
     assert 2500 < per_step_replica < 2800, "one (v, q, pv) frame of 108 atoms per step-replica: ~2.6 KB"
+
+
+def test_dump_outputs_writes_a_seeded_float_sample_within_budget(tmp_path):
+    """--dump-outputs (bench.dump_lj108_outputs): every array float32 / float64, the replicas a fixed seeded sample when the
+    trajectories exceed the budget, the same sample on every call, and the whole dump under 64 MB."""
+    import numpy as np
+    import torch
+    bench = importlib.import_module("bench")
+    R, T = 1000, 50
+    g = torch.Generator().manual_seed(0)
+    v_t, q_t = torch.randn(R, T, 108, 3, generator=g), torch.randn(R, T, 108, 3, generator=g)
+    pv_t, rdf = torch.randn(R, T, 5, generator=g), torch.rand(100, generator=g)
+    params = [torch.nn.Parameter(torch.tensor([1.0])), torch.nn.Parameter(torch.tensor([1.0]))]
+    params[0].grad = torch.tensor([0.5])
+    last = (v_t, q_t, pv_t, rdf, rdf.sum())
+    outs = []
+    for sub in ("a", "b"):
+        bench.dump_lj108_outputs(str(tmp_path / sub), last, params)
+        outs.append({f[:-4]: np.load(tmp_path / sub / f) for f in sorted(os.listdir(tmp_path / sub))})
+    a, b = outs
+    assert sorted(a) == ["g", "loss", "pv_t", "q_t", "replicas", "theta", "theta_grad", "v_t"]
+    assert all(x.dtype in (np.float32, np.float64) for x in a.values())
+    assert sum(os.path.getsize(tmp_path / "a" / (k + ".npy")) for k in a) < 64 << 20
+    idx = a["replicas"].astype(np.int64)
+    assert 0 < len(idx) < R and len(set(idx)) == len(idx) and np.all(np.diff(idx) > 0)
+    assert np.array_equal(a["q_t"], q_t.numpy()[idx]) and np.array_equal(a["pv_t"], pv_t.numpy()[idx])
+    assert np.array_equal(a["theta_grad"], [0.5, 0.0]) and a["loss"].shape == ()
+    assert all(np.array_equal(a[k], b[k]) for k in a)

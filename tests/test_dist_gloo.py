@@ -1,6 +1,8 @@
 """Multi-process (world_size 2, gloo, CPU) coverage of the replica-sharding layer that bench.py
 and the training loop use on N GPUs with RCCL: shard partition, flat-gradient all-reduce, the
-max/sum helpers.  The HIP kernels are not involved (no GPU here); the collective pattern is."""
+max/sum helpers.  The HIP kernels are not involved; the collective pattern is.  The ranks compute on the CPU even
+where a GPU is visible (the suite also runs whole on a GPU machine): they report torch.cuda as unavailable, so
+mdist.init picks the CPU device."""
 import os
 import socket
 import sys
@@ -26,6 +28,7 @@ def _worker(rank, world, port, q):
                       MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     import torch.distributed as dist
     from mdgrad_amd import dist as mdist
+    torch.cuda.is_available = lambda: False           # CPU ranks on any machine (module docstring)
     r, w, dev = mdist.init(backend="gloo")
     assert (r, w) == (rank, world) and dev.type == "cpu"
     # replica shard: 7 replicas over 2 ranks -> [0,4) and [4,7)
@@ -119,6 +122,7 @@ _SELF_LAUNCH_SCRIPT = '''
 import argparse, os, sys
 sys.path.insert(0, %r)
 import torch
+torch.cuda.is_available = lambda: False
 from mdgrad_amd import dist as mdist
 ap = argparse.ArgumentParser(); ap.add_argument("--gpus", type=int, default=1); args = ap.parse_args()
 if args.gpus > 1 and "WORLD_SIZE" not in os.environ:

@@ -218,6 +218,24 @@ int mdg_traj_adj_small(const MdgTrajParams* prm /*host*/, const MdgCell* cell /*
                        const float* g_v, const float* g_q, const float* g_pv,
                        float* adj_v0, float* adj_q0, float* adj_pv0, float* adj_theta,
                        void* stream);
+/* The same two launches keeping the force of every saved frame: f_t is AoS [n_rep][n_frames][n_atoms][3] f32 like q_t
+ * (frames 1..n_frames-1 written, frame 0 untouched).  The forward writes it, the adjoint reads it for its first
+ * evaluation of each interval instead of rebuilding that force (same bits as f_t = NULL).  Only where the
+ * wave-per-replica kernels run, mdg_traj_ring_taken() != 0; elsewhere f_t is ignored.  4 n_rep n_frames n_atoms 3 bytes:
+ * 1.06 GB at 16 384 x 50 x 108. */
+int mdg_traj_ring_taken(const MdgTrajParams* prm /*host*/, const MdgCell* cell /*host*/, const MdgTerms* terms /*host*/);
+int mdg_traj_fwd_small_ft(const MdgTrajParams* prm /*host*/, const MdgCell* cell /*host*/,
+                          const MdgTerms* terms /*host*/, const float* theta,
+                          const float* mass, const float* t_grid,
+                          const float* v0, const float* q0, const float* pv0,
+                          float* v_t, float* q_t, float* pv_t, float* f_t, int32_t* nonfinite, void* stream);
+int mdg_traj_adj_small_ft(const MdgTrajParams* prm /*host*/, const MdgCell* cell /*host*/,
+                          const MdgTerms* terms /*host*/, const float* theta,
+                          const float* mass, const float* t_grid,
+                          const float* v_t, const float* q_t, const float* pv_t, const float* f_t,
+                          const float* g_v, const float* g_q, const float* g_pv,
+                          float* adj_v0, float* adj_q0, float* adj_pv0, float* adj_theta,
+                          void* stream);
 /* The same two launches for integrators with topology_update_freq > 1 (torchmd/md.py:200-204: the lists are rebuilt only
  * at the calls whose running count is a multiple of the frequency -- the counter advances on EVERY right-hand-side call,
  * the adjoint's included -- and are stale in between: pair set and image flags frozen at the rebuild positions, no cutoff
@@ -272,6 +290,20 @@ int mdg_traj_adj_small_rdf(const MdgTrajParams* prm /*host*/, const MdgCell* cel
                            const float* g_v, const float* g_q, const float* g_pv,
                            float* adj_v0, float* adj_q0, float* adj_pv0, float* adj_theta,
                            const MdgRdfFuse* rdf /*host*/, const float* g_raw /*[nbins]*/, void* stream);
+/* the fused-observable launches with the per-frame forces of mdg_traj_fwd_small_ft / mdg_traj_adj_small_ft */
+int mdg_traj_fwd_small_rdf_ft(const MdgTrajParams* prm /*host*/, const MdgCell* cell /*host*/,
+                              const MdgTerms* terms /*host*/, const float* theta,
+                              const float* mass, const float* t_grid,
+                              const float* v0, const float* q0, const float* pv0,
+                              float* v_t, float* q_t, float* pv_t, float* f_t, int32_t* nonfinite,
+                              const MdgRdfFuse* rdf /*host*/, float* raw /*[nbins]*/, void* stream);
+int mdg_traj_adj_small_rdf_ft(const MdgTrajParams* prm /*host*/, const MdgCell* cell /*host*/,
+                              const MdgTerms* terms /*host*/, const float* theta,
+                              const float* mass, const float* t_grid,
+                              const float* v_t, const float* q_t, const float* pv_t, const float* f_t,
+                              const float* g_v, const float* g_q, const float* g_pv,
+                              float* adj_v0, float* adj_q0, float* adj_pv0, float* adj_theta,
+                              const MdgRdfFuse* rdf /*host*/, const float* g_raw /*[nbins]*/, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * K5-K7 for systems beyond one workgroup (N <= 32768, NoseHooverChain or NVE): same contract as

@@ -120,6 +120,15 @@ _SIGNATURES = {
                                      P, P, P, P, P, P, P, P, P, P, P]),
     "mdg_traj_adj_small": (C.c_int, [C.POINTER(MdgTrajParams), C.POINTER(MdgCell), C.POINTER(MdgTerms),
                                      P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "mdg_traj_ring_taken": (C.c_int, [C.POINTER(MdgTrajParams), C.POINTER(MdgCell), C.POINTER(MdgTerms)]),
+    "mdg_traj_fwd_small_ft": (C.c_int, [C.POINTER(MdgTrajParams), C.POINTER(MdgCell), C.POINTER(MdgTerms),
+                                        P, P, P, P, P, P, P, P, P, P, P, P]),
+    "mdg_traj_adj_small_ft": (C.c_int, [C.POINTER(MdgTrajParams), C.POINTER(MdgCell), C.POINTER(MdgTerms),
+                                        P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "mdg_traj_fwd_small_rdf_ft": (C.c_int, [C.POINTER(MdgTrajParams), C.POINTER(MdgCell), C.POINTER(MdgTerms),
+                                            P, P, P, P, P, P, P, P, P, P, P, C.POINTER(MdgRdfFuse), P, P]),
+    "mdg_traj_adj_small_rdf_ft": (C.c_int, [C.POINTER(MdgTrajParams), C.POINTER(MdgCell), C.POINTER(MdgTerms),
+                                            P, P, P, P, P, P, P, P, P, P, P, P, P, P, C.POINTER(MdgRdfFuse), P, P]),
     "mdg_traj_rdf_supported": (C.c_int, [C.POINTER(MdgTrajParams), C.POINTER(MdgCell), C.POINTER(MdgTerms),
                                          C.POINTER(MdgRdfFuse)]),
     "mdg_traj_fwd_small_rdf": (C.c_int, [C.POINTER(MdgTrajParams), C.POINTER(MdgCell), C.POINTER(MdgTerms),

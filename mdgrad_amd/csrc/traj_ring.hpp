@@ -100,7 +100,11 @@ __device__ __forceinline__ void ring_table_scatter2(const RingRdf& X, int idx, f
 // One packed pair operation: lane atoms (i0, i1) against visitors (j0, j1) [CROSS: (j1, j0)].
 // v0 / v1: both atoms of the pair in .x / .y exist.  JSIDE: also update the visitors' accumulators.
 // LEVEL 0: geometry only (RDF gradient of a frame the adjoint does not evaluate forces at).
+// LEVEL 1: force.  LEVEL 2: force, H.w and the parameter sums.  LEVEL 3: LEVEL 2 without the force (the adjoint's
+// first evaluation of an interval when the forward pass stored the force of that frame: TrajArgs::f_t).
 // r0 / r1: the pair in .x / .y feeds the RDF (exists and, for RDF = 1, is the one copy of a pair met twice).
+constexpr bool ring_level_force(int level) { return level == 1 || level == 2; }
+
 template <int LEVEL, bool NEAR, bool CROSS, bool JSIDE, int RDF, int KIND>
 __device__ __forceinline__ void ring_pair(const RingLJ& K, const RingRdf& X, const Vec3x2& qi, const Vec3x2& wi,
                                           const Vec3x2& qj, const Vec3x2& wj, bool v0, bool v1, bool r0, bool r1,
@@ -188,8 +192,9 @@ __device__ __forceinline__ void ring_pair(const RingLJ& K, const RingRdf& X, con
             // branch-free: a rejected pair is evaluated at the cutoff and multiplied by zero
             PairOut o0, o1;
             float r0, ir0, r1, ir1;
-            pair_eval<LEVEL, KIND>(K.t0, ok0 ? d2.x : K.rc2, r0, ir0, o0);
-            pair_eval<LEVEL, KIND>(K.t0, ok1 ? d2.y : K.rc2, r1, ir1, o1);
+            constexpr int PL = LEVEL >= 2 ? 2 : LEVEL;
+            pair_eval<PL, KIND>(K.t0, ok0 ? d2.x : K.rc2, r0, ir0, o0);
+            pair_eval<PL, KIND>(K.t0, ok1 ? d2.y : K.rc2, r1, ir1, o1);
             c1 = f32x2{ok0 ? o0.du * ir0 : 0.f, ok1 ? o1.du * ir1 : 0.f};
             if constexpr (LEVEL >= 2) {
                 kk = f32x2{ok0 ? (o0.d2u - o0.du * ir0) * (ir0 * ir0) : 0.f, ok1 ? (o1.d2u - o1.du * ir1) * (ir1 * ir1) : 0.f};
@@ -198,13 +203,15 @@ __device__ __forceinline__ void ring_pair(const RingLJ& K, const RingRdf& X, con
                     tk[k] = f32x2{ok0 ? 0.5f * o0.ddu_dth[k] * ir0 : 0.f, ok1 ? 0.5f * o1.ddu_dth[k] * ir1 : 0.f};
             }
         }
-        fi.x += c1 * dx; fi.y += c1 * dy; fi.z += c1 * dz;                            // F_i += (phi'/r) D
-        if constexpr (JSIDE) {
-            if constexpr (CROSS) {
-                fj.x = __builtin_elementwise_fma(-c1.yx, dx.yx, fj.x); fj.y = __builtin_elementwise_fma(-c1.yx, dy.yx, fj.y);
-                fj.z = __builtin_elementwise_fma(-c1.yx, dz.yx, fj.z);
-            } else {
-                fj.x -= c1 * dx; fj.y -= c1 * dy; fj.z -= c1 * dz;
+        if constexpr (ring_level_force(LEVEL)) {
+            fi.x += c1 * dx; fi.y += c1 * dy; fi.z += c1 * dz;                        // F_i += (phi'/r) D
+            if constexpr (JSIDE) {
+                if constexpr (CROSS) {
+                    fj.x = __builtin_elementwise_fma(-c1.yx, dx.yx, fj.x); fj.y = __builtin_elementwise_fma(-c1.yx, dy.yx, fj.y);
+                    fj.z = __builtin_elementwise_fma(-c1.yx, dz.yx, fj.z);
+                } else {
+                    fj.x -= c1 * dx; fj.y -= c1 * dy; fj.z -= c1 * dz;
+                }
             }
         }
         if constexpr (LEVEL >= 2) {
@@ -246,7 +253,7 @@ __device__ __forceinline__ void ring_lds_fence() {
     __builtin_amdgcn_wave_barrier();
 }
 
-// All pair terms of one replica.  Outputs: f (force), g (= dq of the augmented dynamics, already negated),
+// All pair terms of one replica.  Outputs: f (force; LEVEL 3 leaves it untouched), g (= dq of the augmented dynamics, already negated),
 // th[k] = this lane's part of the parameter sums over DIRECTED pairs (LEVEL 2; LJ 12-6: of s6 (w.D)/d2 and
 // s12 (w.D)/d2, other forms: of 1/2 d2phi/(dr dtheta_k) (w.D)/r), rq = dL/dq of the fused RDF for this frame (RDF = 2).
 // The ring has nl = ceil(N/2) lanes (the lanes that own atoms).  The visitors' positions and w do not move at all:
@@ -310,7 +317,7 @@ __device__ __forceinline__ void ring_sweep(const RingLJ& K, const RingRdf& X, co
     for (int k = 1; k <= nsteps; ++k) {
         idx -= 1; idx = idx < 0 ? idx + nl : idx;
         qj.x = sqx[idx]; qj.y = sqy[idx]; qj.z = sqz[idx];
-        if constexpr (LEVEL >= 1) fj = ring_move(fj, prev);
+        if constexpr (ring_level_force(LEVEL)) fj = ring_move(fj, prev);
         if constexpr (LEVEL >= 2) { wj.x = swx[idx]; wj.y = swy[idx]; wj.z = swz[idx]; gj = ring_move(gj, prev); }
         if constexpr (RDF == 2) rj = ring_move(rj, prev);
         const bool vj0 = 2 * idx < N, vj1 = 2 * idx + 1 < N;
@@ -344,7 +351,7 @@ __device__ __forceinline__ void ring_sweep(const RingLJ& K, const RingRdf& X, co
     // the travelling accumulators are nsteps lanes ahead of their owners
     int home = lane + nsteps; home = home >= nl ? home - nl : home;
     home = (lane < nl ? home : lane) * 4;
-    if constexpr (LEVEL >= 1) {
+    if constexpr (ring_level_force(LEVEL)) {
         fj = ring_move(fj, home);
         f.x = fi.x + fj.x; f.y = fi.y + fj.y; f.z = fi.z + fj.z;
     }
@@ -423,13 +430,15 @@ __device__ __forceinline__ void ring_pair_lj_multi(const RingLJ (&K)[NT], const 
             t6[m] = s6 * i2; t12[m] = s12 * i2;
         }
     }
-    fi.x += c1 * dx; fi.y += c1 * dy; fi.z += c1 * dz;                                // F_i += (phi'/r) D
-    if constexpr (JSIDE) {
-        if constexpr (CROSS) {
-            fj.x = __builtin_elementwise_fma(-c1.yx, dx.yx, fj.x); fj.y = __builtin_elementwise_fma(-c1.yx, dy.yx, fj.y);
-            fj.z = __builtin_elementwise_fma(-c1.yx, dz.yx, fj.z);
-        } else {
-            fj.x -= c1 * dx; fj.y -= c1 * dy; fj.z -= c1 * dz;
+    if constexpr (ring_level_force(LEVEL)) {
+        fi.x += c1 * dx; fi.y += c1 * dy; fi.z += c1 * dz;                            // F_i += (phi'/r) D
+        if constexpr (JSIDE) {
+            if constexpr (CROSS) {
+                fj.x = __builtin_elementwise_fma(-c1.yx, dx.yx, fj.x); fj.y = __builtin_elementwise_fma(-c1.yx, dy.yx, fj.y);
+                fj.z = __builtin_elementwise_fma(-c1.yx, dz.yx, fj.z);
+            } else {
+                fj.x -= c1 * dx; fj.y -= c1 * dy; fj.z -= c1 * dz;
+            }
         }
     }
     if constexpr (LEVEL >= 2) {
@@ -485,7 +494,7 @@ __device__ __forceinline__ void ring_sweep_lj_multi(const RingLJ (&K)[NT], const
     for (int k = 1; k <= nsteps; ++k) {
         idx -= 1; idx = idx < 0 ? idx + nl : idx;
         qj.x = sqx[idx]; qj.y = sqy[idx]; qj.z = sqz[idx];
-        fj = ring_move(fj, prev);
+        if constexpr (ring_level_force(LEVEL)) fj = ring_move(fj, prev);
         if constexpr (LEVEL >= 2) { wj.x = swx[idx]; wj.y = swy[idx]; wj.z = swz[idx]; gj = ring_move(gj, prev); }
         const bool vj0 = 2 * idx < N, vj1 = 2 * idx + 1 < N;
         const bool s0 = vi0 && vj0, s1 = vi1 && vj1, c0 = vi0 && vj1, c1 = vi1 && vj0;
@@ -516,8 +525,10 @@ __device__ __forceinline__ void ring_sweep_lj_multi(const RingLJ (&K)[NT], const
     }
     int home = lane + nsteps; home = home >= nl ? home - nl : home;
     home = (lane < nl ? home : lane) * 4;
-    fj = ring_move(fj, home);
-    f.x = fi.x + fj.x; f.y = fi.y + fj.y; f.z = fi.z + fj.z;
+    if constexpr (ring_level_force(LEVEL)) {
+        fj = ring_move(fj, home);
+        f.x = fi.x + fj.x; f.y = fi.y + fj.y; f.z = fi.z + fj.z;
+    }
     if constexpr (LEVEL >= 2) {
         gj = ring_move(gj, home);
         g.x = -(gi.x + gj.x); g.y = -(gi.y + gj.y); g.z = -(gi.z + gj.z);
@@ -550,7 +561,7 @@ __device__ __forceinline__ void ring_force_terms(const RingLJ (&K)[NT], const Ri
         for (int m = 1; m < NT; ++m) {
             Vec3x2 f2 = vzero(), g2 = vzero(), r2 = vzero();
             ring_force<LEVEL, 0, KIND, MASK>(K[m], X, M[m], false, N, lane, q, w, f2, g2, th[m], r2, lds);
-            f.x += f2.x; f.y += f2.y; f.z += f2.z;
+            if constexpr (ring_level_force(LEVEL)) { f.x += f2.x; f.y += f2.y; f.z += f2.z; }
             if constexpr (LEVEL >= 2) { g.x += g2.x; g.y += g2.y; g.z += g2.z; }
         }
     }
@@ -724,6 +735,7 @@ __global__ __launch_bounds__(RDF ? 1024 : 64) void traj_fwd_ring_kernel(const Tr
             }
             ring_store(A.q_t + (fr + k + 1) * N3, q, N, lane);
             ring_store(A.v_t + (fr + k + 1) * N3, v, N, lane);
+            if (A.f_t) ring_store(A.f_t + (fr + k + 1) * N3, f, N, lane);   // the force at q_t[k + 1]: the adjoint's first evaluation
             if (nhc && lane < C) A.pv_t[(fr + k + 1) * C + lane] = pv;
         }
         if (A.nonfinite) {
@@ -778,9 +790,17 @@ __device__ __forceinline__ void ring_theta(const RingLJ& K, const float (&th)[MD
 // table gradient goes to the adj_theta row of its first replica, the rows of its other replicas are zero: only the sum over
 // replicas of a tabulated kind's rows is defined (what the caller forms, ops.FusedTrajFn.backward).
 constexpr int RING_TABLE_WAVES = 8;
-
-template <bool RDF, int KIND, bool MASK = false, int NT = 1>
-__global__ __launch_bounds__(KIND == KIND_TABLE ? 64 * RING_TABLE_WAVES : 64) void traj_adj_ring_kernel(const TrajArgs A, const RingRdfArgs F) {
+// FT: the forward pass stored the force of every frame (TrajArgs::f_t).  The first augmented evaluation of interval i sits at
+// frame i and needs the force there; it reads it instead of rebuilding it, and its sweep (LEVEL 3) carries no force
+// accumulators and no travelling force (6 ds_bpermute per ring step fewer).  The forward's LEVEL 1 sweep sums the force in
+// the order of the LEVEL 2 sweep, so the result is the same bits.
+#ifndef MDG_RING_ADJ_WAVES
+#define MDG_RING_ADJ_WAVES 1
+#endif
+template <bool RDF, int KIND, bool MASK = false, int NT = 1, bool FT = false>
+__global__ __launch_bounds__(KIND == KIND_TABLE ? 64 * RING_TABLE_WAVES : 64)
+__attribute__((amdgpu_waves_per_eu(KIND == KIND_LJ126 && NT == 1 && !MASK ? MDG_RING_ADJ_WAVES : 1)))
+void traj_adj_ring_kernel(const TrajArgs A, const RingRdfArgs F) {
     static_assert(NT == 1 || (MASK && KIND != KIND_TABLE), "several terms: masked built-in forms");
     extern __shared__ __attribute__((aligned(16))) float smr[];
     const int N = A.prm.n_atoms, T = A.prm.n_frames, C = A.prm.n_chains;
@@ -857,7 +877,12 @@ __global__ __launch_bounds__(KIND == KIND_TABLE ? 64 * RING_TABLE_WAVES : 64) vo
         // (table kind: the parameter term of an interval comes from the midpoint evaluation for NHC, sovlers.py:160, and
         //  from this first one for NVE, :82,101 -- both with total weight h)
         if constexpr (KIND == KIND_TABLE) X.tgw = (nhc || !live) ? 0.f : 0.5f * h * A.terms.t[0].c;
-        ring_force_terms<2, RDF ? 2 : 0, KIND, MASK, NT>(K, X, M, with_rdf, N, lane, q, w, f, dq, th, rq, lds);
+        if constexpr (FT) {
+            ring_force_terms<3, RDF ? 2 : 0, KIND, MASK, NT>(K, X, M, with_rdf, N, lane, q, w, f, dq, th, rq, lds);
+            f = ring_load(A.f_t + (fr + i) * N3, N, lane);
+        } else {
+            ring_force_terms<2, RDF ? 2 : 0, KIND, MASK, NT>(K, X, M, with_rdf, N, lane, q, w, f, dq, th, rq, lds);
+        }
         if (with_rdf) { lq.x += rq.x; lq.y += rq.y; lq.z += rq.z; }       // dL/dq_t[i] of the fused observable
         Vec3x2 lvh, lqh;
         if (nhc) {

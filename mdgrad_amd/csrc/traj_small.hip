@@ -34,6 +34,9 @@ struct TrajArgs {
     uint16_t* code;
     int freq;
     long long count0;       // value of the integrator's update_count at the first force call of this launch
+    // ring kernels only: the force at every saved frame, AoS [R, T, N, 3] like q_t (frames 1..T-1; null: not kept).  The
+    // forward writes it, the adjoint reads it for its first evaluation of each interval (traj_adj_ring_kernel<..., FT>).
+    float* f_t;
 };
 
 constexpr int KMAX_ALL = MDG_MAX_TERMS * MDG_MAX_THETA;
@@ -910,28 +913,30 @@ size_t ring_table_lds(const MdgTerms& terms, bool adjoint) {
     if (terms.t[0].kind != MDG_PAIR_TABLE) return 0;
     return sizeof(float) * (size_t)(adjoint ? 6 : 2) * terms.t[0].p + 16;
 }
-// launch of a ring kernel specialised on the pair form
-#define MDG_RING_LAUNCH(KERNEL, RDF_, grid, block, lds, st, ...)                                              \
+// launch of a ring kernel specialised on the pair form; TAIL: further template arguments after <RDF, KIND, MASK, NT>
+// (empty, or MDG_RING_FT for the adjoint that reads the forward's forces)
+#define MDG_RING_FT , true
+#define MDG_RING_LAUNCH(KERNEL, RDF_, TAIL, grid, block, lds, st, ...)                                        \
     do {                                                                                                      \
         const bool masked_ = terms->t[0].mask != nullptr;                                                     \
         const int nt_ = terms->n_terms;              /* (ring_form: > 1 only for the LJ family, unfused observable) */ \
         switch (ring_kind(terms->t[0])) {                                                                     \
         case KIND_LJ126:                                                                                      \
-            if (nt_ == 2) hipLaunchKernelGGL((KERNEL<false, KIND_LJ126, true, 2>), grid, block, lds, st, __VA_ARGS__);    \
-            else if (nt_ == 3) hipLaunchKernelGGL((KERNEL<false, KIND_LJ126, true, 3>), grid, block, lds, st, __VA_ARGS__); \
-            else if (masked_) hipLaunchKernelGGL((KERNEL<RDF_, KIND_LJ126, true>), grid, block, lds, st, __VA_ARGS__);    \
-            else hipLaunchKernelGGL((KERNEL<RDF_, KIND_LJ126>), grid, block, lds, st, __VA_ARGS__);                       \
+            if (nt_ == 2) hipLaunchKernelGGL((KERNEL<false, KIND_LJ126, true, 2 TAIL>), grid, block, lds, st, __VA_ARGS__);    \
+            else if (nt_ == 3) hipLaunchKernelGGL((KERNEL<false, KIND_LJ126, true, 3 TAIL>), grid, block, lds, st, __VA_ARGS__); \
+            else if (masked_) hipLaunchKernelGGL((KERNEL<RDF_, KIND_LJ126, true, 1 TAIL>), grid, block, lds, st, __VA_ARGS__);    \
+            else hipLaunchKernelGGL((KERNEL<RDF_, KIND_LJ126, false, 1 TAIL>), grid, block, lds, st, __VA_ARGS__);               \
             break;                                                                                            \
         case MDG_PAIR_LJ:                                                                                     \
-            if (nt_ == 2) hipLaunchKernelGGL((KERNEL<false, MDG_PAIR_LJ, true, 2>), grid, block, lds, st, __VA_ARGS__);   \
-            else if (nt_ == 3) hipLaunchKernelGGL((KERNEL<false, MDG_PAIR_LJ, true, 3>), grid, block, lds, st, __VA_ARGS__);  \
-            else if (masked_) hipLaunchKernelGGL((KERNEL<RDF_, MDG_PAIR_LJ, true>), grid, block, lds, st, __VA_ARGS__);   \
-            else hipLaunchKernelGGL((KERNEL<RDF_, MDG_PAIR_LJ>), grid, block, lds, st, __VA_ARGS__);                      \
+            if (nt_ == 2) hipLaunchKernelGGL((KERNEL<false, MDG_PAIR_LJ, true, 2 TAIL>), grid, block, lds, st, __VA_ARGS__);   \
+            else if (nt_ == 3) hipLaunchKernelGGL((KERNEL<false, MDG_PAIR_LJ, true, 3 TAIL>), grid, block, lds, st, __VA_ARGS__);  \
+            else if (masked_) hipLaunchKernelGGL((KERNEL<RDF_, MDG_PAIR_LJ, true, 1 TAIL>), grid, block, lds, st, __VA_ARGS__);   \
+            else hipLaunchKernelGGL((KERNEL<RDF_, MDG_PAIR_LJ, false, 1 TAIL>), grid, block, lds, st, __VA_ARGS__);              \
             break;                                                                                            \
-        case KIND_TABLE: hipLaunchKernelGGL((KERNEL<false, KIND_TABLE>), grid, block, lds, st, __VA_ARGS__); break;     \
-        case MDG_PAIR_MORSE: hipLaunchKernelGGL((KERNEL<RDF_, MDG_PAIR_MORSE>), grid, block, lds, st, __VA_ARGS__); break; \
-        case MDG_PAIR_BUCK: hipLaunchKernelGGL((KERNEL<RDF_, MDG_PAIR_BUCK>), grid, block, lds, st, __VA_ARGS__); break;  \
-        default: hipLaunchKernelGGL((KERNEL<RDF_, MDG_PAIR_YUKAWA>), grid, block, lds, st, __VA_ARGS__); break;          \
+        case KIND_TABLE: hipLaunchKernelGGL((KERNEL<false, KIND_TABLE, false, 1 TAIL>), grid, block, lds, st, __VA_ARGS__); break; \
+        case MDG_PAIR_MORSE: hipLaunchKernelGGL((KERNEL<RDF_, MDG_PAIR_MORSE, false, 1 TAIL>), grid, block, lds, st, __VA_ARGS__); break; \
+        case MDG_PAIR_BUCK: hipLaunchKernelGGL((KERNEL<RDF_, MDG_PAIR_BUCK, false, 1 TAIL>), grid, block, lds, st, __VA_ARGS__); break;  \
+        default: hipLaunchKernelGGL((KERNEL<RDF_, MDG_PAIR_YUKAWA, false, 1 TAIL>), grid, block, lds, st, __VA_ARGS__); break;          \
         }                                                                                                     \
     } while (0)
 
@@ -1031,10 +1036,21 @@ int validate(const MdgTrajParams* p, const MdgCell* cell, const MdgTerms* terms)
 
 }  // namespace
 
+extern "C" int mdg_traj_ring_taken(const MdgTrajParams* prm, const MdgCell* cell, const MdgTerms* terms) {
+    return prm && cell && terms && validate(prm, cell, terms) == MDG_OK && use_ring(*prm, *cell, *terms);
+}
+
 extern "C" int mdg_traj_fwd_small(const MdgTrajParams* prm, const MdgCell* cell, const MdgTerms* terms,
                                   const float* theta, const float* mass, const float* t_grid,
                                   const float* v0, const float* q0, const float* pv0,
                                   float* v_t, float* q_t, float* pv_t, int32_t* nonfinite, void* stream) {
+    return mdg_traj_fwd_small_ft(prm, cell, terms, theta, mass, t_grid, v0, q0, pv0, v_t, q_t, pv_t, nullptr, nonfinite, stream);
+}
+
+extern "C" int mdg_traj_fwd_small_ft(const MdgTrajParams* prm, const MdgCell* cell, const MdgTerms* terms,
+                                     const float* theta, const float* mass, const float* t_grid,
+                                     const float* v0, const float* q0, const float* pv0,
+                                     float* v_t, float* q_t, float* pv_t, float* f_t, int32_t* nonfinite, void* stream) {
     int rc = validate(prm, cell, terms);
     if (rc) return rc;
     MDG_CHECK_ARG(mass && t_grid && v0 && q0 && v_t && q_t, "traj_fwd: null buffer");
@@ -1045,7 +1061,8 @@ extern "C" int mdg_traj_fwd_small(const MdgTrajParams* prm, const MdgCell* cell,
     const int N = prm->n_atoms;
     if (use_ring(*prm, *cell, *terms)) {
         MDG_CHECK_ARG(theta || terms->n_theta_total == 0, "traj_fwd: null theta");
-        MDG_RING_LAUNCH(traj_fwd_ring_kernel, false, dim3(prm->n_rep), dim3(64), RING_LDS_FWD + ring_table_lds(*terms, false),
+        a.f_t = f_t;
+        MDG_RING_LAUNCH(traj_fwd_ring_kernel, false, , dim3(prm->n_rep), dim3(64), RING_LDS_FWD + ring_table_lds(*terms, false),
                         (hipStream_t)stream, a, RingRdfArgs{});
         MDG_CHECK_LAUNCH("traj_fwd_ring_kernel");
         return MDG_OK;
@@ -1071,6 +1088,16 @@ extern "C" int mdg_traj_adj_small(const MdgTrajParams* prm, const MdgCell* cell,
                                   const float* g_v, const float* g_q, const float* g_pv,
                                   float* adj_v0, float* adj_q0, float* adj_pv0, float* adj_theta,
                                   void* stream) {
+    return mdg_traj_adj_small_ft(prm, cell, terms, theta, mass, t_grid, v_t, q_t, pv_t, nullptr, g_v, g_q, g_pv, adj_v0,
+                                 adj_q0, adj_pv0, adj_theta, stream);
+}
+
+extern "C" int mdg_traj_adj_small_ft(const MdgTrajParams* prm, const MdgCell* cell, const MdgTerms* terms,
+                                     const float* theta, const float* mass, const float* t_grid,
+                                     const float* v_t, const float* q_t, const float* pv_t, const float* f_t,
+                                     const float* g_v, const float* g_q, const float* g_pv,
+                                     float* adj_v0, float* adj_q0, float* adj_pv0, float* adj_theta,
+                                     void* stream) {
     int rc = validate(prm, cell, terms);
     if (rc) return rc;
     MDG_CHECK_ARG(mass && t_grid && v_t && q_t && adj_v0 && adj_q0, "traj_adj: null buffer");
@@ -1086,8 +1113,14 @@ extern "C" int mdg_traj_adj_small(const MdgTrajParams* prm, const MdgCell* cell,
         // (tabulated kind: RING_TABLE_WAVES replicas per workgroup share the nodes and one pair of gradient planes)
         const bool rt = terms->t[0].kind == MDG_PAIR_TABLE;
         const int wpw = rt ? RING_TABLE_WAVES : 1;
-        MDG_RING_LAUNCH(traj_adj_ring_kernel, false, dim3((prm->n_rep + wpw - 1) / wpw), dim3(64 * wpw),
-                        wpw * RING_LDS_ADJ + ring_table_lds(*terms, true), (hipStream_t)stream, a, RingRdfArgs{});
+        const size_t lds = wpw * RING_LDS_ADJ + ring_table_lds(*terms, true);
+        a.f_t = const_cast<float*>(f_t);
+        if (f_t)
+            MDG_RING_LAUNCH(traj_adj_ring_kernel, false, MDG_RING_FT, dim3((prm->n_rep + wpw - 1) / wpw), dim3(64 * wpw), lds,
+                            (hipStream_t)stream, a, RingRdfArgs{});
+        else
+            MDG_RING_LAUNCH(traj_adj_ring_kernel, false, , dim3((prm->n_rep + wpw - 1) / wpw), dim3(64 * wpw), lds,
+                            (hipStream_t)stream, a, RingRdfArgs{});
         MDG_CHECK_LAUNCH("traj_adj_ring_kernel");
         return MDG_OK;
     }
@@ -1185,6 +1218,15 @@ extern "C" int mdg_traj_fwd_small_rdf(const MdgTrajParams* prm, const MdgCell* c
                                       const float* v0, const float* q0, const float* pv0,
                                       float* v_t, float* q_t, float* pv_t, int32_t* nonfinite,
                                       const MdgRdfFuse* rdf, float* raw, void* stream) {
+    return mdg_traj_fwd_small_rdf_ft(prm, cell, terms, theta, mass, t_grid, v0, q0, pv0, v_t, q_t, pv_t, nullptr, nonfinite,
+                                     rdf, raw, stream);
+}
+
+extern "C" int mdg_traj_fwd_small_rdf_ft(const MdgTrajParams* prm, const MdgCell* cell, const MdgTerms* terms,
+                                         const float* theta, const float* mass, const float* t_grid,
+                                         const float* v0, const float* q0, const float* pv0,
+                                         float* v_t, float* q_t, float* pv_t, float* f_t, int32_t* nonfinite,
+                                         const MdgRdfFuse* rdf, float* raw, void* stream) {
     int rc = validate(prm, cell, terms);
     if (rc) return rc;
     MDG_CHECK_ARG((theta || terms->n_theta_total == 0) && mass && t_grid && v0 && q0 && v_t && q_t && raw, "traj_fwd_rdf: null buffer");
@@ -1194,7 +1236,7 @@ extern "C" int mdg_traj_fwd_small_rdf(const MdgTrajParams* prm, const MdgCell* c
                   "(see mdg_traj_rdf_supported)");
     TrajArgs a{};
     a.prm = *prm; a.cell = *cell; a.terms = *terms; a.theta = theta; a.mass = mass; a.t = t_grid;
-    a.v0 = v0; a.q0 = q0; a.pv0 = pv0; a.v_t = v_t; a.q_t = q_t; a.pv_t = pv_t; a.nonfinite = nonfinite;
+    a.v0 = v0; a.q0 = q0; a.pv0 = pv0; a.v_t = v_t; a.q_t = q_t; a.pv_t = pv_t; a.nonfinite = nonfinite; a.f_t = f_t;
     hipStream_t st = (hipStream_t)stream;
     uint32_t* ghist = nullptr;
     MDG_HIP(hipMallocAsync((void**)&ghist, sizeof(uint32_t) * (size_t)P.nfine, st));
@@ -1204,7 +1246,7 @@ extern "C" int mdg_traj_fwd_small_rdf(const MdgTrajParams* prm, const MdgCell* c
     int grid = (prm->n_rep + RING_RDF_WAVES - 1) / RING_RDF_WAVES;
     if (grid > 256) grid = 256;                                   // one resident workgroup (16 waves) per CU
     const size_t lds = sizeof(float) * (size_t)((P.nfine + 1) & ~1LL) + RING_RDF_WAVES * RING_LDS_FWD;
-    MDG_RING_LAUNCH(traj_fwd_ring_kernel, true, dim3(grid), dim3(64 * RING_RDF_WAVES), lds, st, a, F);
+    MDG_RING_LAUNCH(traj_fwd_ring_kernel, true, , dim3(grid), dim3(64 * RING_RDF_WAVES), lds, st, a, F);
     rc = mdg_rdf_fine_finish(ghist, P, rdf->mu, rdf->nbins, raw, st);
     (void)hipFreeAsync(ghist, st);
     if (rc) return rc;
@@ -1218,6 +1260,16 @@ extern "C" int mdg_traj_adj_small_rdf(const MdgTrajParams* prm, const MdgCell* c
                                       const float* g_v, const float* g_q, const float* g_pv,
                                       float* adj_v0, float* adj_q0, float* adj_pv0, float* adj_theta,
                                       const MdgRdfFuse* rdf, const float* g_raw, void* stream) {
+    return mdg_traj_adj_small_rdf_ft(prm, cell, terms, theta, mass, t_grid, v_t, q_t, pv_t, nullptr, g_v, g_q, g_pv, adj_v0,
+                                     adj_q0, adj_pv0, adj_theta, rdf, g_raw, stream);
+}
+
+extern "C" int mdg_traj_adj_small_rdf_ft(const MdgTrajParams* prm, const MdgCell* cell, const MdgTerms* terms,
+                                         const float* theta, const float* mass, const float* t_grid,
+                                         const float* v_t, const float* q_t, const float* pv_t, const float* f_t,
+                                         const float* g_v, const float* g_q, const float* g_pv,
+                                         float* adj_v0, float* adj_q0, float* adj_pv0, float* adj_theta,
+                                         const MdgRdfFuse* rdf, const float* g_raw, void* stream) {
     int rc = validate(prm, cell, terms);
     if (rc) return rc;
     MDG_CHECK_ARG((theta || terms->n_theta_total == 0) && mass && t_grid && v_t && q_t && adj_v0 && adj_q0 && g_raw, "traj_adj_rdf: null buffer");
@@ -1237,7 +1289,10 @@ extern "C" int mdg_traj_adj_small_rdf(const MdgTrajParams* prm, const MdgCell* c
     if (rc == MDG_OK) {
         RingRdfArgs F = ring_rdf_args(*rdf, P);
         F.tab = tab;
-        MDG_RING_LAUNCH(traj_adj_ring_kernel, true, dim3(prm->n_rep), dim3(64), sizeof(float4) * (size_t)P.ncell + RING_LDS_ADJ, st, a, F);
+        const size_t lds = sizeof(float4) * (size_t)P.ncell + RING_LDS_ADJ;
+        a.f_t = const_cast<float*>(f_t);
+        if (f_t) MDG_RING_LAUNCH(traj_adj_ring_kernel, true, MDG_RING_FT, dim3(prm->n_rep), dim3(64), lds, st, a, F);
+        else MDG_RING_LAUNCH(traj_adj_ring_kernel, true, , dim3(prm->n_rep), dim3(64), lds, st, a, F);
     }
     (void)hipFreeAsync(tab, st);
     if (rc) return rc;

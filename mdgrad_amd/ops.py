@@ -472,14 +472,21 @@ class FusedTrajFn(torch.autograd.Function):
             fuse = None
         ctx.fuse = fuse
         raw = None
+        # the wave-per-replica kernels keep the force of every saved frame for the adjoint's first evaluation of each
+        # interval (mdg_traj_*_ft: 4 R T N 3 bytes, written once and read once; 1.06 GB at 16 384 x 50 x 108 atoms)
+        f_t = None
+        if not spec.large and not getattr(spec, "stale_freq", 0) and lib.mdg_traj_ring_taken(
+                C.byref(prm), C.byref(spec.cell_struct), C.byref(spec.terms)):
+            f_t = torch.empty(R, T, N, 3, device=dev)
+        ctx.f_t = f_t
         if fuse is not None:
             # the observable rides along: raw soft histogram of the selected frames of all replicas
             raw = torch.empty(fuse.nbins, device=dev)
             bad = torch.zeros(R, dtype=torch.int32, device=dev)
-            check(lib.mdg_traj_fwd_small_rdf(C.byref(prm), C.byref(spec.cell_struct), C.byref(spec.terms), ptr(thc),
-                                             ptr(spec.mass), ptr(tc), ptr(v0c), ptr(q0c), ptr(pv0c), ptr(v_t),
-                                             ptr(q_t), ptr(pv_t), ptr(bad), C.byref(fuse.struct()), ptr(raw),
-                                             stream_ptr(dev)), "mdg_traj_fwd_small_rdf")
+            check(lib.mdg_traj_fwd_small_rdf_ft(C.byref(prm), C.byref(spec.cell_struct), C.byref(spec.terms), ptr(thc),
+                                                ptr(spec.mass), ptr(tc), ptr(v0c), ptr(q0c), ptr(pv0c), ptr(v_t),
+                                                ptr(q_t), ptr(pv_t), ptr(f_t), ptr(bad), C.byref(fuse.struct()), ptr(raw),
+                                                stream_ptr(dev)), "mdg_traj_fwd_small_rdf_ft")
         elif spec.large:
             ws = torch.empty(int(lib.mdg_traj_large_workspace(R, N, T, spec.n_theta_total)), device=dev)
             flags = torch.zeros(8, dtype=torch.int32, device=dev)
@@ -527,9 +534,9 @@ class FusedTrajFn(torch.autograd.Function):
             ctx.stale_code = code                  # (the lists this pass ended with: what its backward continues from)
         else:
             bad = torch.zeros(R, dtype=torch.int32, device=dev)
-            check(lib.mdg_traj_fwd_small(C.byref(prm), C.byref(spec.cell_struct), C.byref(spec.terms), ptr(thc),
-                                         ptr(spec.mass), ptr(tc), ptr(v0c), ptr(q0c), ptr(pv0c), ptr(v_t),
-                                         ptr(q_t), ptr(pv_t), ptr(bad), stream_ptr(dev)), "mdg_traj_fwd_small")
+            check(lib.mdg_traj_fwd_small_ft(C.byref(prm), C.byref(spec.cell_struct), C.byref(spec.terms), ptr(thc),
+                                            ptr(spec.mass), ptr(tc), ptr(v0c), ptr(q0c), ptr(pv0c), ptr(v_t),
+                                            ptr(q_t), ptr(pv_t), ptr(f_t), ptr(bad), stream_ptr(dev)), "mdg_traj_fwd_small_ft")
         if getattr(spec, "table", False) and not spec.large:
             # tabulated user pair module: a live pair closer than the first table node has no valid entry
             # (one host sync per trajectory, table mode only)
@@ -598,15 +605,16 @@ class FusedTrajFn(torch.autograd.Function):
         table = getattr(spec, "table", False)
 
         ws, lists_ok = getattr(ctx, "ws", None), getattr(ctx, "lists_ok", False)
+        f_t = getattr(ctx, "f_t", None)
 
         def launch(terms, search=False):
             if g_raw is not None:
                 gr = g_raw.detach().to(torch.float32).contiguous()
-                check(lib.mdg_traj_adj_small_rdf(C.byref(prm), C.byref(spec.cell_struct), C.byref(terms), ptr(thc),
-                                                 ptr(spec.mass), ptr(tc), ptr(v_t), ptr(q_t), ptr(pv_t), ptr(gv),
-                                                 ptr(gq), ptr(gp), ptr(adj_v), ptr(adj_q), ptr(adj_p), ptr(adj_th),
-                                                 C.byref(fuse.struct()), ptr(gr), stream_ptr(dev)),
-                      "mdg_traj_adj_small_rdf")
+                check(lib.mdg_traj_adj_small_rdf_ft(C.byref(prm), C.byref(spec.cell_struct), C.byref(terms), ptr(thc),
+                                                    ptr(spec.mass), ptr(tc), ptr(v_t), ptr(q_t), ptr(pv_t), ptr(f_t), ptr(gv),
+                                                    ptr(gq), ptr(gp), ptr(adj_v), ptr(adj_q), ptr(adj_p), ptr(adj_th),
+                                                    C.byref(fuse.struct()), ptr(gr), stream_ptr(dev)),
+                      "mdg_traj_adj_small_rdf_ft")
                 return None
             if spec.large and getattr(spec, "stale_freq", 0):
                 # stale rows; 3 calls per interval (the dL/dt evaluation and two augmented ones, sovlers.py:258-266)
@@ -658,10 +666,10 @@ class FusedTrajFn(torch.autograd.Function):
                 integ.update_count += 3 * (T - 1)
                 integ._stale_fused_dirty = True
                 return None
-            check(lib.mdg_traj_adj_small(C.byref(prm), C.byref(spec.cell_struct), C.byref(terms), ptr(thc),
-                                         ptr(spec.mass), ptr(tc), ptr(v_t), ptr(q_t), ptr(pv_t), ptr(gv), ptr(gq),
-                                         ptr(gp), ptr(adj_v), ptr(adj_q), ptr(adj_p), ptr(adj_th),
-                                         stream_ptr(dev)), "mdg_traj_adj_small")
+            check(lib.mdg_traj_adj_small_ft(C.byref(prm), C.byref(spec.cell_struct), C.byref(terms), ptr(thc),
+                                            ptr(spec.mass), ptr(tc), ptr(v_t), ptr(q_t), ptr(pv_t), ptr(f_t), ptr(gv), ptr(gq),
+                                            ptr(gp), ptr(adj_v), ptr(adj_q), ptr(adj_p), ptr(adj_th),
+                                            stream_ptr(dev)), "mdg_traj_adj_small_ft")
             return None
 
         def check_large(flags):

@@ -156,7 +156,7 @@ def test_bench_two_ranks_on_one_device():
         s.close()
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3",
-               "--warmup", "2", "--replicas", "1024", "--no-secondary", "--no-cpu-baseline"]
+               "--warmup", "2", "--replicas", "1024", "--full", "--no-secondary", "--no-cpu-baseline"]
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
         if r.returncode == 0 or "address already in use" not in (r.stderr + r.stdout).lower():
             break
@@ -177,7 +177,7 @@ def test_bench_plain_command_spawns_two_ranks_on_one_device():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(MDG_DIST_BACKEND="gloo", MDG_SINGLE_DEVICE="1")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--replicas", "1024",
-           "--no-secondary", "--no-cpu-baseline"]
+           "--full", "--no-secondary", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -200,7 +200,7 @@ def test_bench_plain_command_with_four_ranks_on_one_device():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(MDG_DIST_BACKEND="gloo", MDG_SINGLE_DEVICE="1")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--workload", "lj108", "--steps", "3", "--warmup", "2",
-           "--replicas", "2048", "--no-cpu-baseline"]
+           "--replicas", "2048", "--full", "--no-cpu-baseline"]
     t0 = time.time()
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     wall = time.time() - t0
@@ -217,13 +217,13 @@ def test_bench_plain_command_with_four_ranks_on_one_device():
 
 
 def test_bench_default_leg_set_for_more_than_one_rank_is_lean():
-    """... and the default leg set of an N > 1 run: headline + lj4096 + schnet4096, no precision variants (two ranks on one
-    device; small pass counts so the test stays short)."""
+    """... and the default leg set of an N > 1 --full run: headline + lj4096 + schnet4096, no precision variants (two ranks on
+    one device; small pass counts so the test stays short)."""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(MDG_DIST_BACKEND="gloo", MDG_SINGLE_DEVICE="1")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--replicas", "1024",
-           "--no-cpu-baseline"]
+           "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -16,5 +16,5 @@ done
 bash tools/prof_gnn_single.sh $TAG > /dev/null 2>&1
 (python tools/kbench_cfconv.py --rows16 2>&1 | grep -v amdgpu.ids) > gpurun_out/prof/${TAG}_cfconv_kbench_stash.txt
 (python tools/kbench_ring_mask.py 2>&1 | grep -v amdgpu.ids) > gpurun_out/prof/${TAG}_ring_mask_kbench.txt
-(timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/f_bench.json 2> gpurun_out/f_bench.err); tail -c 200 gpurun_out/f_bench.err
-tail -c 600 gpurun_out/f_bench.json
+(timeout 1200 python bench.py --full --gpus 1 --steps 20 --warmup 5 > profiles/${TAG}_bench.json 2> /tmp/${TAG}_bench.err); tail -c 200 /tmp/${TAG}_bench.err
+tail -c 600 profiles/${TAG}_bench.json

@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/prof
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-python $R/bench.py > $O/${TAG}_bench.json 2> /tmp/bench.err; tail -c 300 $O/${TAG}_bench.json
+python $R/bench.py --full > $O/${TAG}_bench.json 2> /tmp/bench.err; tail -c 300 $O/${TAG}_bench.json
 # kernel-time tables (rocprofv3 --kernel-trace --stats) of the three workloads
 for W in lj108 schnet4096 lj4096; do LINES_SHOWN=3 bash $R/tools/prof_workload.sh $W ${TAG} > /dev/null 2>&1; done
 LINES_SHOWN=3 bash $R/tools/prof_workload.sh schnet4096 ${TAG}bf16 --bf16 > /dev/null 2>&1      # (the bench line's secondary runs bf16 operands)

@@ -826,6 +826,27 @@ int mdg_nhv_adj_end(const float* vh, const float* pm, const float* lvh, const fl
                     float* lp, float* scratch, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * K14  bond-angle distribution  (replaces angle_distribution.forward and its autograd backward:
+ *      torchmd/observable.py:120-151, compute_angle :166-179, generate_angle_list torchmd/topology.py:83-122;
+ *      csrc/adf.hip)
+ *   pos [n_frames * n_atoms, 3]; col / cnt: the ELL list of K1 over those rows (frames = groups of n_atoms, col holds row
+ *   indices); the cell must be diagonal.  Every ordered triplet (i, j, k) of one frame with (i, j) and (j, k) listed pairs and
+ *   k != i is counted: theta at centre j between u = x_i - x_j and v = x_k - x_j, both re-imaged with topology.get_offsets.
+ *   raw[b] = sum exp(coeff (theta - mu_b)^2), mu_b = mu[0] + b * spacing, b < nbins <= 4096; centres farther than
+ *   5.3 / sqrt(-coeff log2 e) from theta are dropped (<= 2^-28 of a peak term each).
+ *   fwd: raw[nbins] (NaN if an angle is not finite); scratch: int64 words of mdg_adf_partial_size(), bitwise reproducible.
+ *   bwd: given g_raw[nbins] = dL/draw, writes g_xyz [n_frames * n_atoms, 3]; triplets with |u x v| <= 2^-20 |u| |v|
+ *   contribute zero (the symmetric subgradient at theta = 0, pi).  Bitwise reproducible, no atomics.
+ */
+int64_t mdg_adf_partial_size(int n_frames, int n_atoms, int max_nbr, int nbins);
+int mdg_adf_fwd(const float* pos, int n_frames, int n_atoms, const MdgCell* cell /*host*/, float cutoff, const int32_t* col,
+                const int32_t* cnt, int max_nbr, const float* mu, float spacing, float coeff, int nbins, float* raw,
+                int64_t* scratch, void* stream);
+int mdg_adf_bwd(const float* pos, int n_frames, int n_atoms, const MdgCell* cell /*host*/, float cutoff, const int32_t* col,
+                const int32_t* cnt, int max_nbr, const float* mu, float spacing, float coeff, int nbins,
+                const float* g_raw, float* g_xyz, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * f4  bonded terms over a static topology table (csrc/bonded.hip).
  * Replaces torchmd/interface.py:447-455 (BondPotentials.forward: harmonic in the SQUARED bond length,
  * 1/2 k (|b|^2 - ro)^2) and :496-508 (AnglePotentials.forward: 1/2 k (theta - theta0)^2 over triples (i, j, k) centred on

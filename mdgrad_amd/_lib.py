@@ -226,6 +226,11 @@ _SIGNATURES = {
     "mdg_schnet_workspace": (C.c_int64, [C.POINTER(MdgSchnetPlan), C.c_int, C.c_int]),
     "mdg_schnet_force": (C.c_int, [C.POINTER(MdgSchnetPlan), P, P, P, P]),
     "mdg_schnet_force_vjp": (C.c_int, [C.POINTER(MdgSchnetPlan), P, P, P, P, P, C.c_float, P, P, P, P]),
+    "mdg_adf_partial_size": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mdg_adf_fwd": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), C.c_float, P, P, C.c_int, P, C.c_float, C.c_float,
+                              C.c_int, P, P, P]),
+    "mdg_adf_bwd": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), C.c_float, P, P, C.c_int, P, C.c_float, C.c_float,
+                              C.c_int, P, P, P]),
     "mdg_bonded_eval": (C.c_int, [P, C.c_int, C.POINTER(C.c_float), C.c_int, P, C.c_int, C.c_float, C.c_float, P, P, P, P, P, P,
                                   C.c_float, C.c_int, P]),
 }

@@ -11,6 +11,7 @@
 //   nhc_vv_forward   K5/6 sovlers.py:106-127 / :21-40       -> mdg_traj_fwd_small
 //   nhc_vv_adjoint   K7   sovlers.py:211-293                -> mdg_traj_adj_small
 //   rdf_fwd/rdf_bwd  K8   observable.py:62-76               -> mdg_rdf_fwd_uniform / mdg_rdf_bwd_uniform
+//   adf_fwd/adf_bwd  K14  observable.py:120-151             -> mdg_adf_fwd / mdg_adf_bwd
 //   edge_geom(+_bwd) schnet.py:142                          -> mdg_edge_geom / mdg_edge_geom_bwd
 //   cfconv_fwd/_bwd  K9+K10 modules.py:531-571              -> mdg_cfconv_fwd(_bf16) / mdg_cfconv_bwd(_bf16)
 //   dense_ssp        K11/12 layers.py:86-134                -> mdg_dense
@@ -254,6 +255,40 @@ Tensor rdf_bwd(const Tensor& xyz, at::ArrayRef<double> cell, double cutoff, cons
     return g;
 }
 
+// ------------------------------------------------------------------------------------------------ K14
+void adf_check(const Tensor& pos, int64_t n_frames, int64_t n_atoms, const Tensor& col, const Tensor& cnt, const Tensor& mu) {
+    check_f32(pos, "pos"); check_f32(mu, "mu"); check_i32(col, "col"); check_i32(cnt, "cnt");
+    same_device(pos, col, "col"); same_device(pos, cnt, "cnt"); same_device(pos, mu, "mu");
+    TORCH_CHECK(n_frames > 0 && n_atoms > 0 && n_frames * n_atoms < (int64_t(1) << 31),
+                "mdgrad: n_frames and n_atoms must be positive with n_frames * n_atoms < 2^31 (chunk the frames)");
+    TORCH_CHECK(pos.numel() == n_frames * n_atoms * 3, "mdgrad: pos must hold n_frames * n_atoms rows of 3");
+    TORCH_CHECK(col.dim() == 2 && col.size(0) == n_frames * n_atoms && cnt.numel() == col.size(0),
+                "mdgrad: col must be [n_frames * n_atoms, max_nbr] and cnt [n_frames * n_atoms]");
+}
+Tensor adf_fwd(const Tensor& pos, int64_t n_frames, int64_t n_atoms, at::ArrayRef<double> cell, double cutoff, const Tensor& col,
+               const Tensor& cnt, const Tensor& mu, double spacing, double coeff) {
+    adf_check(pos, n_frames, n_atoms, col, cnt, mu);
+    const MdgCell c = make_cell(cell);
+    const int B = (int)mu.numel(), M = (int)col.size(1);
+    Tensor raw = at::empty({B}, pos.options());
+    Tensor scratch = at::empty({mdg_adf_partial_size((int)n_frames, (int)n_atoms, M, B)}, pos.options().dtype(at::kLong));
+    ok(mdg_adf_fwd(fptr(pos), (int)n_frames, (int)n_atoms, &c, (float)cutoff, col.data_ptr<int32_t>(), cnt.data_ptr<int32_t>(), M,
+                   fptr(mu), (float)spacing, (float)coeff, B, mptr(raw), scratch.data_ptr<int64_t>(), stream_of(pos)));
+    return raw;
+}
+Tensor adf_bwd(const Tensor& pos, int64_t n_frames, int64_t n_atoms, at::ArrayRef<double> cell, double cutoff, const Tensor& col,
+               const Tensor& cnt, const Tensor& mu, double spacing, double coeff, const Tensor& g_raw) {
+    adf_check(pos, n_frames, n_atoms, col, cnt, mu);
+    check_f32(g_raw, "g_raw"); same_device(pos, g_raw, "g_raw");
+    const MdgCell c = make_cell(cell);
+    const int B = (int)mu.numel(), M = (int)col.size(1);
+    TORCH_CHECK(g_raw.numel() == B, "mdgrad: g_raw must have one entry per centre");
+    Tensor g = at::empty_like(pos);
+    ok(mdg_adf_bwd(fptr(pos), (int)n_frames, (int)n_atoms, &c, (float)cutoff, col.data_ptr<int32_t>(), cnt.data_ptr<int32_t>(), M,
+                   fptr(mu), (float)spacing, (float)coeff, B, fptr(g_raw), mptr(g), stream_of(pos)));
+    return g;
+}
+
 // ------------------------------------------------------------------------------------------------ SchNet block
 MdgFilterNet filter_net(const Tensor& mu, const Tensor& coef, const Tensor& W1, const Tensor& b1, const Tensor& W2,
                         const Tensor& b2) {
@@ -411,6 +446,10 @@ TORCH_LIBRARY(mdgrad, m) {
           "(Tensor, Tensor, Tensor, Tensor)");
     m.def("rdf_fwd(Tensor xyz, float[] cell, float cutoff, Tensor? mask, Tensor mu, float spacing, float coeff) -> Tensor");
     m.def("rdf_bwd(Tensor xyz, float[] cell, float cutoff, Tensor? mask, Tensor mu, float spacing, float coeff, Tensor g_raw) -> Tensor");
+    m.def("adf_fwd(Tensor pos, int n_frames, int n_atoms, float[] cell, float cutoff, Tensor col, Tensor cnt, Tensor mu, "
+          "float spacing, float coeff) -> Tensor");
+    m.def("adf_bwd(Tensor pos, int n_frames, int n_atoms, float[] cell, float cutoff, Tensor col, Tensor cnt, Tensor mu, "
+          "float spacing, float coeff, Tensor g_raw) -> Tensor");
     m.def("edge_geom(Tensor x, Tensor? w, Tensor nbr, Tensor offsets) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("edge_geom_bwd(Tensor? d_b, Tensor dd_b, Tensor? d, Tensor? dd, Tensor uhat, Tensor? ddel, Tensor col, Tensor eid, "
           "Tensor cnt) -> (Tensor, Tensor)");
@@ -433,6 +472,8 @@ TORCH_LIBRARY_IMPL(mdgrad, CUDA, m) {      // (the HIP backend registers under t
     m.impl("nhc_vv_adjoint", nhc_vv_adjoint);
     m.impl("rdf_fwd", rdf_fwd);
     m.impl("rdf_bwd", rdf_bwd);
+    m.impl("adf_fwd", adf_fwd);
+    m.impl("adf_bwd", adf_bwd);
     m.impl("edge_geom", edge_geom);
     m.impl("edge_geom_bwd", edge_geom_bwd);
     m.impl("cfconv_fwd", cfconv_fwd);

@@ -1,14 +1,19 @@
 """Observables with the reference's interface (torchmd/observable.py): generate_vol_bins
 :10-21, Observable :24-31, rdf :33-76, vacf :153-163.  The pair search + Gaussian smearing +
 histogram of rdf.forward is one HIP op (ops.RdfRawFn, csrc/rdf.hip); vacf is one fused reduction over the
-velocity trajectory (ops.VacfFn, csrc/observe.hip)."""
+velocity trajectory (ops.VacfFn, csrc/observe.hip).  angle_distribution :120-151 (with Angles :89-118 and
+compute_angle :166-179): the triplet search + Gaussian smearing + histogram and its gradient are one HIP op
+(ops.AdfRawFn, csrc/adf.hip); the per-triplet angles are torch ops over the device-built angle list."""
+import math
 import warnings
 
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, topology
+from .nn.layers import GaussianSmearing
 from .system import check_system
+from .topology import generate_angle_list, get_offsets
 
 
 def generate_vol_bins(start, end, nbins, dim):
@@ -112,6 +117,90 @@ class rdf(Observable):
         count = count / norm
         rdf = count / (self.vol_bins / self.V)
         return count, self.bins, rdf
+
+
+def compute_angle(xyz, angle_list, cell, N):
+    """torchmd/observable.py:166-179: cos of the angle at atom j between x_i - x_j and x_k - x_j for rows (frame, i, j, k),
+    each bond vector re-imaged with topology.get_offsets on the diagonal `cell`."""
+    frames = xyz.reshape(-1, N, 3)
+    f, i, j, k = angle_list.to(frames.device).unbind(1)
+    centre = frames[f, j]
+    u = frames[f, i] - centre
+    v = frames[f, k] - centre
+    u = u + get_offsets(u, cell, frames.device) * cell
+    v = v + get_offsets(v, cell, frames.device) * cell
+    return (u * v).sum(-1) / (u.pow(2).sum(-1) * v.pow(2).sum(-1)).sqrt()
+
+
+class Angles(Observable):
+    """torchmd/observable.py:89-118: forward(xyz) -> cos of every triplet angle, in the reference's list order."""
+
+    def __init__(self, system, nbins, angle_range, cutoff=3.0, index_tuple=None, width=None):
+        super().__init__(system)
+        start, end = angle_range[0], angle_range[1]
+        self.bins = torch.linspace(start, end, nbins + 1).to(self.device)
+        self.smear = GaussianSmearing(start=start, stop=self.bins[-1], n_gaussians=nbins, width=width,
+                                      trainable=False).to(self.device)
+        self.width = self.smear.width[0].item()
+        self.cutoff = cutoff
+        self.index_tuple = index_tuple
+        self.nbins = nbins
+        self._cell_struct = _lib.make_cell(self.cell)      # diagonal of the cell, as the reference
+        self._mask = ops.build_mask(self.natoms, index_tuple, None, self.device)
+
+    def _angle_cos(self, frames):
+        """cos of every triplet angle of `frames` [F, N, 3] in the reference's order (compute_angle over the angle list).  The
+        half lists are built in the frame chunks of ops.AdfRawFn, the size of the triplet list is checked before it is
+        built, and an allocation failure anywhere on the way is the same ValueError, naming keep_angles=False."""
+        F, N = frames.shape[0], self.natoms
+        fc = ops._adf_chunk_frames(F, N, self._cell_struct, self.cutoff)
+        x = frames.detach()
+        try:
+            halves, n_cand = [], 0
+            for f0 in range(0, F, fc):
+                ell = ops.build_ell(x[f0:f0 + fc].reshape(-1, 3), self._cell_struct, self.cutoff, self._mask, group=N)
+                c = ell.cnt.to(torch.int64)
+                n_cand += int((c * c).sum())          # the candidate rows of generate_angle_list: sum over centres cnt^2
+                if 4 * n_cand > topology.ANGLE_LIST_MAX:
+                    raise ValueError("%s: more than %d candidate triplets exceed the list limit of %d entries; use "
+                                     "angle_distribution(..., keep_angles=False) for the histogram alone"
+                                     % (type(self).__name__, n_cand, topology.ANGLE_LIST_MAX))
+                nbr = ell.half_list()[0]
+                del ell
+                f = torch.div(nbr[:, :1], N, rounding_mode="floor")
+                halves.append(torch.cat([f + f0, nbr - f * N], 1))
+            return compute_angle(frames, generate_angle_list(torch.cat(halves, 0)), self.cell, N=N)
+        except torch.cuda.OutOfMemoryError as e:
+            raise ValueError("%s: the triplet list does not fit in device memory (%s); use angle_distribution(..., "
+                             "keep_angles=False) for the histogram alone" % (type(self).__name__, e)) from None
+
+    def forward(self, xyz):
+        return self._angle_cos(xyz.reshape(-1, self.natoms, 3))
+
+
+class angle_distribution(Angles):
+    """torchmd/observable.py:120-151: forward(xyz) -> (bins, count, angles).  count is the normalised Gaussian-smeared
+    histogram of every ordered triplet angle (ops.AdfRawFn: HIP histogram and gradient).  angles are the per-triplet angles in
+    the reference's order (torch ops, differentiable); keep_angles=False returns None there and never builds the list."""
+
+    def __init__(self, system, nbins, angle_range, cutoff=3.0, index_tuple=None, width=None, keep_angles=True):
+        super().__init__(system, nbins, angle_range, cutoff=cutoff, index_tuple=index_tuple, width=width)
+        offsets = self.smear.offsets
+        self.spacing = float(offsets[1] - offsets[0]) if nbins > 1 else 0.0      # linspace: equally spaced
+        self.coeff = float(-0.5 / torch.pow(self.smear.width[0].detach().cpu().to(torch.float32), 2))
+        if not (self.width != 0 and math.isfinite(self.coeff)):        # (a descending range gives a negative width)
+            raise ValueError("angle_distribution: width must be nonzero, got %r" % self.width)
+        self.keep_angles = keep_angles
+
+    def forward(self, xyz):
+        frames = xyz.reshape(-1, self.natoms, 3)
+        count = ops.AdfRawFn.apply(frames, self.smear.offsets, self.coeff, self.cutoff, self._cell_struct, self._mask,
+                                   self.spacing)
+        count = count / count.sum()
+        angles = None
+        if self.keep_angles:
+            angles = self._angle_cos(frames).acos()
+        return self.bins, count, angles
 
 
 class vacf(Observable):

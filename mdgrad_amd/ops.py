@@ -4,6 +4,7 @@ torch.autograd.Function wrappers that own the differentiation contract
     PairEnergyFn -> PairGradFn -> (Hessian-vector product)     pair potentials, any order <= 2
     FusedTrajFn                                                 whole NH-Verlet/Verlet trajectory + adjoint
     RdfRawFn                                                    soft histogram
+    AdfRawFn                                                    soft histogram of bond angles
 
 Everything here requires HIP tensors; there is no CPU path.
 """
@@ -861,6 +862,73 @@ class RdfRawFn(torch.autograd.Function):
         check(lib.mdg_rdf_bwd_uniform(ptr(x3), F, N, C.byref(cell_struct), cutoff, ptr(mask), ptr(muc), spacing,
                                       coeff, B, ptr(gr), ptr(gx), stream_ptr(x3.device)), "mdg_rdf_bwd")
         return gx.reshape(shape), None, None, None, None, None, None, None
+
+
+# ----------------------------------------------------------------------------- angle distribution
+ADF_CHUNK_BYTES = 1 << 30    # neighbour-list memory (col + shift + cnt) per chunk of frames in AdfRawFn
+ADF_CHUNK_FRAMES = None      # when set: frames per chunk (tests force several chunks with it)
+
+
+def _adf_chunk_frames(F, N, cell_struct, cutoff):
+    if ADF_CHUNK_FRAMES is not None:
+        return max(1, min(F, int(ADF_CHUNK_FRAMES)))
+    per_frame = N * (8 * estimate_max_nbr(N, cell_struct, cutoff) + 4)
+    return max(1, min(F, ADF_CHUNK_BYTES // per_frame, (2 ** 31 - 1) // N))
+
+
+class AdfRawFn(torch.autograd.Function):
+    """raw[b] = sum over frames and ordered triplets (i, j, k) of the neighbour list (j the centre, k != i) of
+    exp(coeff (theta_ijk - mu_b)^2) -- the GaussianSmearing(angles).sum(0) of torchmd/observable.py:148 (csrc/adf.hip, K14).
+    xyz: [F, N, 3] frames.  The lists are built in chunks of frames so that their memory stays near ADF_CHUNK_BYTES; the
+    backward pass reuses the forward's list when there was one chunk and rebuilds the chunks one at a time otherwise, so one
+    chunk's list is alive at any time."""
+
+    @staticmethod
+    def forward(ctx, xyz, mu, coeff, cutoff, cell_struct, mask, spacing):
+        lib = _lib.load()
+        require_gpu(xyz, "xyz")
+        x3 = xyz.detach()
+        x3 = x3 if x3.is_contiguous() else x3.contiguous()
+        F, N, B = x3.shape[0], x3.shape[1], mu.shape[0]
+        dev = x3.device
+        muc = mu.detach().to(device=dev, dtype=torch.float32).contiguous()
+        fc = _adf_chunk_frames(F, N, cell_struct, cutoff)
+        scratch = torch.empty(int(lib.mdg_adf_partial_size(fc, N, 1, B)), dtype=torch.int64, device=dev)
+        raw, keep = None, None
+        for f0 in range(0, F, fc):
+            f1 = min(F, f0 + fc)
+            flat = x3[f0:f1].reshape(-1, 3)
+            ell = build_ell(flat, cell_struct, cutoff, mask, group=N)
+            part = torch.empty(B, device=dev)
+            check(lib.mdg_adf_fwd(ptr(flat), f1 - f0, N, C.byref(cell_struct), float(cutoff), ptr(ell.col), ptr(ell.cnt),
+                                  ell.max_nbr, ptr(muc), float(spacing), float(coeff), B, ptr(part), ptr(scratch),
+                                  stream_ptr(dev)), "mdg_adf_fwd")
+            raw = part if raw is None else raw + part
+            # only a single chunk's list is kept for the backward pass: with several chunks each list is released here
+            # (stream order makes the caching allocator's reuse safe), so at most one chunk's list is alive at a time
+            keep = ell if (f0 == 0 and f1 == F) else None
+            del ell
+        ctx.ell = keep
+        ctx.args = (float(coeff), float(cutoff), cell_struct, mask, float(spacing), fc, xyz.shape)
+        ctx.save_for_backward(x3, muc)
+        return raw
+
+    @staticmethod
+    def backward(ctx, g_raw):
+        lib = _lib.load()
+        x3, muc = ctx.saved_tensors
+        coeff, cutoff, cell_struct, mask, spacing, fc, shape = ctx.args
+        F, N, B = x3.shape[0], x3.shape[1], muc.shape[0]
+        gr = g_raw.detach().to(torch.float32).contiguous()
+        gx = torch.empty_like(x3)
+        for f0 in range(0, F, fc):
+            f1 = min(F, f0 + fc)
+            flat = x3[f0:f1].reshape(-1, 3)
+            ell = ctx.ell if ctx.ell is not None else build_ell(flat, cell_struct, cutoff, mask, group=N)
+            check(lib.mdg_adf_bwd(ptr(flat), f1 - f0, N, C.byref(cell_struct), float(cutoff), ptr(ell.col), ptr(ell.cnt),
+                                  ell.max_nbr, ptr(muc), float(spacing), float(coeff), B, ptr(gr), ptr(gx[f0:f1]),
+                                  stream_ptr(x3.device)), "mdg_adf_bwd")
+        return gx.reshape(shape), None, None, None, None, None, None
 
 
 # ----------------------------------------------------------------------------- velocity observables

@@ -1,5 +1,7 @@
 """Topology helpers with the reference's names (torchmd/topology.py).  The neighbour search
-runs in the HIP builders (csrc/nbr.hip); results come back in the reference's format."""
+runs in the HIP builders (csrc/nbr.hip); results come back in the reference's format.  The angle list
+(generate_angle_list) is built from sorted index tensors on the list's own device, without the reference's
+[M, M] mask over all directed pairs."""
 import itertools
 
 import torch
@@ -53,3 +55,45 @@ def generate_nbr_list(xyz, cutoff, cell, index_tuple=None, ex_pairs=None, get_di
 def get_offsets(vecs, cell, device):
     """torchmd/topology.py:75-80 (non-strict >= on the + side, unlike generate_nbr_list)."""
     return -vecs.ge(0.5 * cell).to(torch.float).to(device) + vecs.lt(-0.5 * cell).to(torch.float).to(device)
+
+
+def make_directed(nbr_list):
+    """torchmd/topology.py:101-122: the list followed by the same rows with the two atom columns swapped."""
+    return torch.cat([nbr_list, nbr_list[:, [0, 2, 1]]], 0)
+
+
+ANGLE_LIST_MAX = 2 ** 31     # entries (rows x 4) beyond which generate_angle_list refuses
+
+
+def generate_angle_list(nbr_list):
+    """torchmd/topology.py:83-98: rows (frame, i, j, k) for every directed row (frame, i, j) of make_directed(nbr_list),
+    in that row order, followed by its thirds k: the third atoms of the directed rows (frame, j, k), k != i, in directed-row
+    order.  Same rows in the same order as the reference, from a stable sort of the directed rows by (frame, first atom)
+    instead of the reference's [M, M] mask; runs on the list's device.  Raises ValueError when the list would exceed
+    ANGLE_LIST_MAX entries or does not fit in memory."""
+    assert nbr_list.shape[1] == 3
+    d = make_directed(nbr_list.to(torch.long))
+    M, dev = d.shape[0], d.device
+    if M == 0:
+        return torch.zeros(0, 4, dtype=torch.long, device=dev)
+    span = int(d[:, 1:].max()) + 1
+    key = d[:, 0] * span + d[:, 1]                          # group of directed rows that leave atom d[:, 1] of frame d[:, 0]
+    order = torch.sort(key, stable=True)[1]                 # stable: each group keeps the directed-row order
+    skey = key[order]
+    want = d[:, 0] * span + d[:, 2]                         # row (f, i, j) takes the group of (f, j)
+    lo = torch.searchsorted(skey, want)
+    n = torch.searchsorted(skey, want, right=True) - lo
+    total = int(n.sum())
+    if 4 * total > ANGLE_LIST_MAX:
+        raise ValueError("generate_angle_list: %d candidate triplets exceed the list limit of %d entries; "
+                         "use angle_distribution(..., keep_angles=False) for the histogram alone" % (total, ANGLE_LIST_MAX))
+    try:
+        row = torch.repeat_interleave(torch.arange(M, device=dev), n)
+        start = torch.cumsum(n, 0) - n
+        cand = order[lo[row] + torch.arange(total, device=dev) - start[row]]
+        third = d[cand, 2]
+        keep = third != d[row, 1]
+        return torch.cat([d[row[keep]], third[keep, None]], 1)
+    except torch.cuda.OutOfMemoryError as e:
+        raise ValueError("generate_angle_list: the triplet list does not fit in device memory (%s); "
+                         "use angle_distribution(..., keep_angles=False) for the histogram alone" % e) from None

@@ -224,6 +224,10 @@ int mdg_traj_adj_small(const MdgTrajParams* prm /*host*/, const MdgCell* cell /*
  * wave-per-replica kernels run, mdg_traj_ring_taken() != 0; elsewhere f_t is ignored.  4 n_rep n_frames n_atoms 3 bytes:
  * 1.06 GB at 16 384 x 50 x 108. */
 int mdg_traj_ring_taken(const MdgTrajParams* prm /*host*/, const MdgCell* cell /*host*/, const MdgTerms* terms /*host*/);
+/* 1 when the one-workgroup-per-replica kernels hold a replica of n_atoms atoms -- with an MDG_PAIR_TABLE term of
+ * table_nodes nodes (0: a built-in form) -- in LDS for both the forward and the adjoint launch, else 0: the size rule
+ * mdg_traj_fwd_small* / mdg_traj_adj_small* check (the adjoint's state and the table's gradient words are the larger). */
+int mdg_traj_small_fits(int n_atoms, int table_nodes);
 int mdg_traj_fwd_small_ft(const MdgTrajParams* prm /*host*/, const MdgCell* cell /*host*/,
                           const MdgTerms* terms /*host*/, const float* theta,
                           const float* mass, const float* t_grid,

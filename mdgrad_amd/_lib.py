@@ -121,6 +121,7 @@ _SIGNATURES = {
     "mdg_traj_adj_small": (C.c_int, [C.POINTER(MdgTrajParams), C.POINTER(MdgCell), C.POINTER(MdgTerms),
                                      P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "mdg_traj_ring_taken": (C.c_int, [C.POINTER(MdgTrajParams), C.POINTER(MdgCell), C.POINTER(MdgTerms)]),
+    "mdg_traj_small_fits": (C.c_int, [C.c_int, C.c_int]),
     "mdg_traj_fwd_small_ft": (C.c_int, [C.POINTER(MdgTrajParams), C.POINTER(MdgCell), C.POINTER(MdgTerms),
                                         P, P, P, P, P, P, P, P, P, P, P, P]),
     "mdg_traj_adj_small_ft": (C.c_int, [C.POINTER(MdgTrajParams), C.POINTER(MdgCell), C.POINTER(MdgTerms),

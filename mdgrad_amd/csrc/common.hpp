@@ -165,7 +165,7 @@ struct TermConst {
     int kind, p, q;
     float c, rc2;
     float k0, k1, k2, k3, k4;   // LJ: sig, eps, 1/sig | Morse: a, phi, A, 1/(1+A) | Buck: A,B,C | Yukawa: eps,kappa
-                                // Table: k0 = u0, k1 = 1/du, k2 = nodes - 1 - eps
+                                // Table: k0 = u0, k1 = 1/du, k2 = nodes - 1
     const float* tab;           // Table: [2 p] nodes (c1_g, du * dc1/du_g) in global memory (L1/L2 resident)
 };
 
@@ -177,7 +177,7 @@ __device__ __forceinline__ TermConst term_prepare(const MdgPairTerm& t, const fl
     const float* th = theta + t.theta_off;
     switch (t.kind) {
     case MDG_PAIR_TABLE:
-        c.k0 = t.a; c.k1 = 1.f / t.phi; c.k2 = (float)(t.p - 1) - 1e-3f; c.tab = th;
+        c.k0 = t.a; c.k1 = 1.f / t.phi; c.k2 = (float)(t.p - 1); c.tab = th;
         break;
     case MDG_PAIR_LJ: c.k0 = th[0]; c.k1 = th[1]; c.k2 = 1.0f / th[0]; break;
     case MDG_PAIR_MORSE: {
@@ -264,8 +264,9 @@ __device__ __forceinline__ void pair_eval(const TermConst& tc, float d2, float& 
     case MDG_PAIR_TABLE: {
         // c1(u) = phi'(r)/r and its u-derivative from the cubic-Hermite table (see traj_small.hip,
         // force_table_packed): phi' = c1 r, phi'' = 2 u dc1/du + c1
+        // (grid coordinate clamped to the nodes [0, p - 1], cell index to the last cell: the last node is fr = 1 of it)
         const float tt = fminf(fmaxf((d2 - tc.k0) * tc.k1, 0.f), tc.k2);
-        const int g = (int)tt;
+        const int g = min((int)tt, tc.p - 2);
         const float fr = tt - (float)g;
         const float2 n0 = *reinterpret_cast<const float2*>(tc.tab + 2 * g);
         const float2 n1 = *reinterpret_cast<const float2*>(tc.tab + 2 * g + 2);

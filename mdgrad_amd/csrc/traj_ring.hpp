@@ -86,7 +86,8 @@ struct RingRdf {
     // order-independent) and the weight of the current evaluation's contributions (0: the evaluation does not accumulate,
     // sovlers.py:160 / :82,101); tlim: the largest single contribution the words can take without any sum leaving int64;
     // tflag: LDS word, bit 1 = a live pair below the first node (forward), bit 2 = a contribution at or beyond tlim (adjoint)
-    const float2* ttab; unsigned long long* tg64; int32_t* tflag; float tgw, tu0, tinv_du, ttmax, tlim;
+    // ttmax = p - 1 clamps the grid coordinate, tgmax = p - 2 the cell index (the last node is fraction 1 of the last cell)
+    const float2* ttab; unsigned long long* tg64; int32_t* tflag; float tgw, tu0, tinv_du, ttmax, tlim; int tgmax;
 };
 
 // A node's value and slope entries (idx even, idx + 1): one 64-bit LDS atomic each -- as many atomic instructions as the
@@ -166,7 +167,7 @@ __device__ __forceinline__ void ring_pair(const RingLJ& K, const RingRdf& X, con
             }
             f32x2 tt = (d2 - X.tu0) * X.tinv_du;
             tt.x = fminf(fmaxf(ok0 ? tt.x : 0.f, 0.f), X.ttmax); tt.y = fminf(fmaxf(ok1 ? tt.y : 0.f, 0.f), X.ttmax);
-            g0 = (int)tt.x; g1 = (int)tt.y;
+            g0 = min((int)tt.x, X.tgmax); g1 = min((int)tt.y, X.tgmax);
             const f32x2 fr = {tt.x - (float)g0, tt.y - (float)g1};
             const float2 a0 = X.ttab[g0], b0 = X.ttab[g0 + 1], a1 = X.ttab[g1], b1 = X.ttab[g1 + 1];
             const f32x2 v0 = {a0.x, a1.x}, s0 = {a0.y, a1.y}, v1 = {b0.x, b1.x}, s1 = {b0.y, b1.y};
@@ -670,7 +671,7 @@ __global__ __launch_bounds__(RDF ? 1024 : 64) void traj_fwd_ring_kernel(const Tr
         const float* thp = A.theta + t0.theta_off;
         for (int g = threadIdx.x; g < t0.p; g += blockDim.x) ttab[g] = make_float2(thp[2 * g], thp[2 * g + 1]);
         if (threadIdx.x == 0) *tflag = 0;
-        X.ttab = ttab; X.tflag = tflag; X.tu0 = t0.a; X.tinv_du = 1.f / t0.phi; X.ttmax = (float)(t0.p - 1) - 1e-3f;
+        X.ttab = ttab; X.tflag = tflag; X.tu0 = t0.a; X.tinv_du = 1.f / t0.phi; X.ttmax = (float)(t0.p - 1); X.tgmax = t0.p - 2;
         __syncthreads();
     }
     if constexpr (RDF) {
@@ -846,7 +847,7 @@ void traj_adj_ring_kernel(const TrajArgs A, const RingRdfArgs F) {
         // one word can receive a contribution from every pair evaluation of the workgroup's replicas: one accumulating
         // evaluation per interval, N (N - 1) / 2 pairs, two ends each
         X.tlim = fx64_limit((double)NWV * (double)(T > 1 ? T - 1 : 1) * (double)N * (double)N);
-        X.tu0 = t0.a; X.tinv_du = 1.f / t0.phi; X.ttmax = (float)(t0.p - 1) - 1e-3f;
+        X.tu0 = t0.a; X.tinv_du = 1.f / t0.phi; X.ttmax = (float)(t0.p - 1); X.tgmax = t0.p - 2;
         __syncthreads();
     }
     const size_t fr = (size_t)rep * T;

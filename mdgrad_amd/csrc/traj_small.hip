@@ -171,7 +171,8 @@ __device__ __forceinline__ void force_table_packed(const TrajArgs& A, int tpa_lo
     const int slot = threadIdx.x >> tpa_log2, sub = threadIdx.x & (TPA - 1);
     const MdgPairTerm& t0 = A.terms.t[0];
     const float rc2 = t0.cutoff * t0.cutoff, u0 = t0.a, inv_du = 1.f / t0.phi;
-    const float tmax = (float)(t0.p - 1) - 1e-3f;
+    const float tmax = (float)(t0.p - 1);
+    const int gmax = t0.p - 2;
     const float ivx = A.cell.inv[0], ivy = A.cell.inv[4], ivz = A.cell.inv[8];
     const float hx = A.cell.h[0], hy = A.cell.h[4], hz = A.cell.h[8];
     const bool acc = LEVEL >= 2 && T.g64 != nullptr;
@@ -204,10 +205,11 @@ __device__ __forceinline__ void force_table_packed(const TrajArgs& A, int tpa_lo
             // a live pair below the first node: the table does not cover it (the forward kernel reports it through
             // the per-replica flag, bit 1, and the host raises instead of returning clamped forces)
             if (LEVEL == 1 && ((ok0 && d2.x < u0) || (ok1 && d2.y < u0))) vmax = 1.f;
-            // grid coordinate (clamped: below the first node the first cell is extrapolated with fr = 0)
+            // grid coordinate clamped to the nodes [0, p - 1] (below the first node: the first node, fr = 0), cell index to
+            // the last cell (the last node is fr = 1 of it)
             f32x2 tt = (d2 - u0) * inv_du;
             tt.x = fminf(fmaxf(ok0 ? tt.x : 0.f, 0.f), tmax); tt.y = fminf(fmaxf(ok1 ? tt.y : 0.f, 0.f), tmax);
-            const int g0 = (int)tt.x, g1 = (int)tt.y;
+            const int g0 = min((int)tt.x, gmax), g1 = min((int)tt.y, gmax);
             const f32x2 fr = {tt.x - (float)g0, tt.y - (float)g1};
             const float2 a0 = T.tab[g0], b0 = T.tab[g0 + 1], a1 = T.tab[g1], b1 = T.tab[g1 + 1];
             const f32x2 v0 = {a0.x, a1.x}, s0 = {a0.y, a1.y}, v1 = {b0.x, b1.x}, s1 = {b0.y, b1.y};
@@ -988,6 +990,23 @@ int pick_block(const MdgTrajParams& p, bool table) {
     return 1024;
 }
 
+// LDS of the one-workgroup-per-replica kernels (the single source of the size rule: the launches below check it, and
+// mdg_traj_small_fits reports it to the host, which routes what does not fit to the multi-launch kernels): the
+// replica's state in columns of ld floats (13 forward, 28 adjoint), the thermostat chain, the reduction scratch and, for
+// a table of `nodes` nodes, the nodes (forward) or the nodes plus their int64 gradient words (adjoint).  The kernels hold
+// static LDS of their own beside it (256 bytes: the workgroup reductions behind __syncthreads_or; the code object's
+// group_segment_fixed_size, checked in tests/test_gpu_pair_table.py): what a launch asks for must fit the workgroup's
+// 160 KiB together with that -- a tabulated adjoint at N = 1 011 .. 1 012 with 2 048 nodes once asked for 160 KiB - 64 B
+// and faulted.
+constexpr size_t SMALL_STATIC_LDS = 256;
+constexpr size_t SMALL_LDS_MAX = 160 * 1024 - SMALL_STATIC_LDS;
+int small_ld(int n_atoms) { return n_atoms <= 128 ? 128 : (n_atoms + 1) & ~1; }
+size_t small_lds(int n_atoms, int nodes, bool adjoint) {
+    const size_t ld = small_ld(n_atoms);
+    return sizeof(float) * (adjoint ? 28 * ld + 6 * MDG_MAX_CHAINS + RED_FLOATS + 6 * (size_t)nodes
+                                    : 13 * ld + 5 * MDG_MAX_CHAINS + RED_FLOATS + 2 * (size_t)nodes);
+}
+
 // specialisation table: single-term kernels with the functional form fixed at compile time
 // (orthorhombic cell), everything else through the generic <NT = MDG_MAX_TERMS> kernel.
 #define MDG_TRAJ_DISPATCH(KERNEL)                                                                      \
@@ -1036,6 +1055,11 @@ int validate(const MdgTrajParams* p, const MdgCell* cell, const MdgTerms* terms)
 
 }  // namespace
 
+extern "C" int mdg_traj_small_fits(int n_atoms, int table_nodes) {
+    return n_atoms > 0 && table_nodes >= 0 && small_lds(n_atoms, table_nodes, false) <= SMALL_LDS_MAX &&
+           small_lds(n_atoms, table_nodes, true) <= SMALL_LDS_MAX;
+}
+
 extern "C" int mdg_traj_ring_taken(const MdgTrajParams* prm, const MdgCell* cell, const MdgTerms* terms) {
     return prm && cell && terms && validate(prm, cell, terms) == MDG_OK && use_ring(*prm, *cell, *terms);
 }
@@ -1068,11 +1092,11 @@ extern "C" int mdg_traj_fwd_small_ft(const MdgTrajParams* prm, const MdgCell* ce
         return MDG_OK;
     }
     const int block = pick_block(*prm, terms->t[0].kind == MDG_PAIR_TABLE);
-    const size_t tab = terms->t[0].kind == MDG_PAIR_TABLE ? 2 * (size_t)terms->t[0].p : 0;
-    MDG_CHECK_ARG(!tab || theta, "traj_fwd: the table is passed through theta");
-    a.ld = N <= 128 ? 128 : (N + 1) & ~1;
-    const size_t lds = sizeof(float) * (13 * (size_t)a.ld + 5 * MDG_MAX_CHAINS + RED_FLOATS + tab);
-    MDG_CHECK_ARG(lds <= 160 * 1024, "traj_fwd: N=%d does not fit the LDS-resident kernel", N);
+    const int nodes = terms->t[0].kind == MDG_PAIR_TABLE ? terms->t[0].p : 0;
+    MDG_CHECK_ARG(!nodes || theta, "traj_fwd: the table is passed through theta");
+    a.ld = small_ld(N);
+    const size_t lds = small_lds(N, nodes, false);
+    MDG_CHECK_ARG(lds <= SMALL_LDS_MAX, "traj_fwd: N=%d does not fit the LDS-resident kernel", N);
     const int tl = pick_tpa_log2(N, block);
     const bool diag = cell->diag != 0;
     dim3 grid(prm->n_rep);
@@ -1125,11 +1149,11 @@ extern "C" int mdg_traj_adj_small_ft(const MdgTrajParams* prm, const MdgCell* ce
         return MDG_OK;
     }
     const int block = pick_block(*prm, terms->t[0].kind == MDG_PAIR_TABLE);
-    const size_t tab = terms->t[0].kind == MDG_PAIR_TABLE ? 6 * (size_t)terms->t[0].p : 0;   // nodes + the int64 gradient words
-    MDG_CHECK_ARG(!tab || theta, "traj_adj: the table is passed through theta");
-    a.ld = N <= 128 ? 128 : (N + 1) & ~1;
-    const size_t lds = sizeof(float) * (28 * (size_t)a.ld + 6 * MDG_MAX_CHAINS + RED_FLOATS + tab);
-    MDG_CHECK_ARG(lds <= 160 * 1024, "traj_adj: N=%d does not fit the LDS-resident kernel", N);
+    const int nodes = terms->t[0].kind == MDG_PAIR_TABLE ? terms->t[0].p : 0;
+    MDG_CHECK_ARG(!nodes || theta, "traj_adj: the table is passed through theta");
+    a.ld = small_ld(N);
+    const size_t lds = small_lds(N, nodes, true);
+    MDG_CHECK_ARG(lds <= SMALL_LDS_MAX, "traj_adj: N=%d does not fit the LDS-resident kernel", N);
     const int tl = pick_tpa_log2(N, block);
     const bool diag = cell->diag != 0;
     dim3 grid(prm->n_rep);
@@ -1162,9 +1186,9 @@ extern "C" int mdg_traj_fwd_small_stale(const MdgTrajParams* prm, const MdgCell*
     a.code = code; a.freq = freq; a.count0 = count0;
     const int N = prm->n_atoms;
     const int block = pick_block(*prm, false);
-    a.ld = N <= 128 ? 128 : (N + 1) & ~1;
-    const size_t lds = sizeof(float) * (13 * (size_t)a.ld + 5 * MDG_MAX_CHAINS + RED_FLOATS);
-    MDG_CHECK_ARG(lds <= 160 * 1024, "traj_fwd_stale: N=%d does not fit the LDS-resident kernel", N);
+    a.ld = small_ld(N);
+    const size_t lds = small_lds(N, 0, false);
+    MDG_CHECK_ARG(lds <= SMALL_LDS_MAX, "traj_fwd_stale: N=%d does not fit the LDS-resident kernel", N);
     const int tl = pick_tpa_log2(N, block);
     dim3 grid(prm->n_rep);
     hipStream_t st = (hipStream_t)stream;
@@ -1194,9 +1218,9 @@ extern "C" int mdg_traj_adj_small_stale(const MdgTrajParams* prm, const MdgCell*
     a.code = code; a.freq = freq; a.count0 = count0;
     const int N = prm->n_atoms;
     const int block = pick_block(*prm, false);
-    a.ld = N <= 128 ? 128 : (N + 1) & ~1;
-    const size_t lds = sizeof(float) * (28 * (size_t)a.ld + 6 * MDG_MAX_CHAINS + RED_FLOATS);
-    MDG_CHECK_ARG(lds <= 160 * 1024, "traj_adj_stale: N=%d does not fit the LDS-resident kernel", N);
+    a.ld = small_ld(N);
+    const size_t lds = small_lds(N, 0, true);
+    MDG_CHECK_ARG(lds <= SMALL_LDS_MAX, "traj_adj_stale: N=%d does not fit the LDS-resident kernel", N);
     const int tl = pick_tpa_log2(N, block);
     dim3 grid(prm->n_rep);
     hipStream_t st = (hipStream_t)stream;

@@ -10,7 +10,7 @@ import weakref
 
 import torch
 
-from . import units, ops
+from . import units, ops, _lib
 from .interface import PairPotentials, Stack
 from .sovlers import odeint_adjoint, odeint
 from .system import wrap_positions
@@ -159,7 +159,7 @@ class _EOM(torch.nn.Module):
     _ensemble = None
     _method = None
     fused_large = None      # None = by size; True/False forces the multi-launch / one-workgroup kernels
-    fused_table = True      # tabulate user pair modules for the fused kernels (N <= 1024); False: generic path
+    fused_table = True      # tabulate user pair modules for the fused kernels (N <= 32 768); False: generic path
     fuse_observables = False   # True (or attach_observable): an rdf called on a fused trajectory is evaluated INSIDE the next
     #                            trajectory launches (its histogram is then an output of the launch, not a function of q_t in
     #                            the autograd graph: autograd.grad(loss, q_t) / hooks on q_t do not see the RDF term).  Off by
@@ -248,13 +248,16 @@ class _EOM(torch.nn.Module):
                      else (getattr(self.system, "n_replicas", 1), N, N))
             if self.update_count % freq != 0 and (code is None or tuple(code.shape) != shape):
                 return None                 # (between two rebuilds without the lists of this geometry: the generic path)
-        table_large = N > FUSED_MAX_ATOMS if self.fused_large is None else bool(self.fused_large)
-        if (mods is None and self.adjoint and self.fused_table
-                and (N <= FUSED_MAX_ATOMS_LARGE if table_large else N <= FUSED_MAX_ATOMS)):
-            members = _table_members(self.model)
-            if members is not None and (self._ensemble == 1 or 2 <= self.num_chains <= 16):
+        members = _table_members(self.model) if mods is None and self.adjoint and self.fused_table else None
+        if members is not None and (self._ensemble == 1 or 2 <= self.num_chains <= 16):
+            # the one-workgroup kernels only where the adjoint's state, nodes and gradient words fit in LDS (at 2 048 nodes
+            # N <= 1 010, at 4 096 N <= 570: the library's size rule, mdg_traj_small_fits), else the multi-launch kernels;
+            # a caller who forces the one-workgroup kernels on a system they cannot hold gets the generic path
+            nodes = int(self.table_nodes)
+            fits_small = N <= FUSED_MAX_ATOMS and bool(_lib.load().mdg_traj_small_fits(N, nodes))
+            table_large = not fits_small if self.fused_large is None else bool(self.fused_large)
+            if (N <= FUSED_MAX_ATOMS_LARGE) if table_large else fits_small:
                 kw = {} if self._ensemble != 0 else dict(T=self.T, n_dof=self.N_dof, Q=[float(x) for x in self.Q.tolist()])
-                nodes = int(self.table_nodes)
                 spec = _TableSpec(self, members, nodes, self.table_rmin * float(members[0].cutoff), self._ensemble, N,
                                   self.mass[:N].contiguous(), members[0]._cell_struct, None, 2 * nodes, [None],
                                   large=table_large, **kw)

@@ -13,6 +13,7 @@ import torch
 
 __all__ = [
     "cell_matrix", "nbr_list", "compute_dis", "pair_phi", "PairTerm", "ModelOracle", "BondTerm", "AngleTerm",
+    "table_c1", "TableTerm",
     "get_offsets_oracle",
     "NHCOracle", "NVEOracle", "odeint_oracle", "adjoint_oracle", "rdf_oracle", "rdf_raw_oracle",
     "rdf_normalise_oracle", "vacf_oracle", "temperature_oracle",
@@ -264,6 +265,60 @@ class AngleTerm(_BondedTerm):
         b2 = b2 + get_offsets_oracle(b2, L) * L
         cos = (b1 * b2).sum(-1) / (b1.pow(2).sum(-1) * b2.pow(2).sum(-1)).sqrt()   # :500-503
         return 0.5 * self.k * (torch.acos(cos) - self.x0).pow(2).sum(-1)           # :505-507
+
+
+def table_c1(table, u0, du, u):
+    """The tabulated pair model's c1(u) = phi'(r)/r (MDG_PAIR_TABLE): cubic Hermite over the nodes
+    (c1_g, du dc1/du_g) of `table` [2 p] on the uniform grid u_g = u0 + g du, g = 0 .. p-1.  The cell is
+    g = min(floor(t), p - 2) for t = (u - u0) / du clamped to [0, p - 1] (below the first node: the first
+    node's value and slope; the last node itself lies in the last cell, at fraction 1).  Differentiable in
+    u and in the table."""
+    nodes = table.reshape(-1, 2)
+    p = nodes.shape[0]
+    t = ((u - u0) / du).clamp(0.0, p - 1.0)
+    g = t.detach().floor().long().clamp(max=p - 2)
+    f = t - g.to(t)
+    v0, s0, v1, s1 = nodes[g, 0], nodes[g, 1], nodes[g + 1, 0], nodes[g + 1, 1]
+    om = 1.0 - f
+    return (1.0 + 2.0 * f) * om * om * v0 + f * om * om * s0 + f * f * (3.0 - 2.0 * f) * v1 + f * f * (f - 1.0) * s1
+
+
+class TableTerm:
+    """The tabulated pair model of the fused kernels (MDG_PAIR_TABLE) as an oracle term: F_i = sum_j c1(u_ij) D_ij,
+    D_ij = x_j - x_i (minimum image), u = |D|^2 < cutoff^2, c1 from `table_c1`.  `table` is the term's theta, so
+    force_vjp's third output is d(w.F)/d(table) [2 p]; it and d(w.F)/dq come from autograd on w.F."""
+
+    def __init__(self, table, u0, du, cutoff, cell):
+        self.theta = torch.as_tensor(table).reshape(-1)
+        self.u0, self.du, self.cutoff = float(u0), float(du), float(cutoff)
+        self.cell = cell_matrix(cell)
+        self.nbr = self.off = None
+
+    @property
+    def n_theta(self):
+        return self.theta.numel()
+
+    def reset(self, q):
+        self.nbr, self.off = nbr_list(q.detach(), self.cutoff, self.cell.to(q))
+
+    def _force(self, q, table):
+        D = -compute_dis(q, self.nbr, self.off.to(q), self.cell.to(q))[0]       # x_j - x_i
+        t = table_c1(table, self.u0, self.du, D.pow(2).sum(1))[:, None] * D
+        F = torch.zeros_like(q)
+        F.index_add_(0, self.nbr[:, 0], t)
+        F.index_add_(0, self.nbr[:, 1], -t)
+        return F
+
+    def force(self, q):
+        return self._force(q, self.theta.to(q))
+
+    def force_vjp(self, q, w):
+        with torch.enable_grad():
+            x = q.detach().requires_grad_(True)
+            tab = self.theta.to(q).detach().requires_grad_(True)
+            F = self._force(x, tab)
+            dq, dth = torch.autograd.grad((w.detach() * F).sum(), (x, tab))
+        return F.detach(), dq, dth
 
 
 class ModelOracle:

@@ -1009,10 +1009,16 @@ size_t small_lds(int n_atoms, int nodes, bool adjoint) {
 
 // specialisation table: single-term kernels with the functional form fixed at compile time
 // (orthorhombic cell), everything else through the generic <NT = MDG_MAX_TERMS> kernel.
-#define MDG_TRAJ_DISPATCH(KERNEL)                                                                      \
+// GENERIC: the generic kernel whatever the terms (stale lists: only it reads TrajArgs::code; never a tabulated term).
+// Reads the caller's `prm`, `cell`, `terms`, `a`, `st` and its launch geometry `g` (SmallGeom, below).
+#define MDG_TRAJ_DISPATCH(KERNEL, GENERIC)                                                             \
     do {                                                                                               \
-        const bool single = terms->n_terms == 1 && diag && !terms->t[0].mask;                          \
+        const bool diag = cell->diag != 0;                                                             \
+        const bool single = !(GENERIC) && terms->n_terms == 1 && diag && !terms->t[0].mask;            \
         const int kind = terms->t[0].kind;                                                             \
+        const dim3 grid(prm->n_rep), block(g.block);                                                   \
+        const size_t lds = g.lds;                                                                      \
+        const int tl = g.tl;                                                                           \
         if (kind == MDG_PAIR_TABLE)                                                                    \
             hipLaunchKernelGGL((KERNEL<true, 1, KIND_TABLE>), grid, dim3(block), lds, st, a, tl);      \
         else if (single && kind == MDG_PAIR_LJ && terms->t[0].p == 12 && (terms->t[0].q == 6 || terms->t[0].c == 0.f)) \
@@ -1053,6 +1059,176 @@ int validate(const MdgTrajParams* p, const MdgCell* cell, const MdgTerms* terms)
     return MDG_OK;
 }
 
+// What an entry point asks for beyond the plain trajectory (the counterpart of StaleOpt in traj_large.hip): which extra
+// travels with the launch, and that extra's arguments.  Members an entry point does not use stay zero.
+struct SmallOpt {
+    enum Extra { PLAIN, STALE, RDF } extra;
+    float* f_t;                     // ring kernels: TrajArgs::f_t (null: not kept / not read)
+    const MdgRdfFuse* rdf;          // RDF: the observable ...
+    float* raw;                     //      ... its raw histogram (forward, out)
+    const float* g_raw;             //      ... dL/d(raw) (adjoint, in)
+    int freq;                       // STALE: TrajArgs::freq / count0 / code
+    int64_t count0;
+    uint16_t* code;
+};
+
+// the entry-point family a refusal names
+const char* small_who(bool adjoint, const SmallOpt& o) {
+    static const char* const who[2][3] = {{"traj_fwd", "traj_fwd_stale", "traj_fwd_rdf"},
+                                          {"traj_adj", "traj_adj_stale", "traj_adj_rdf"}};
+    return who[adjoint][o.extra];
+}
+
+// the refusals an extra adds, after the common ones and before any launch geometry
+int validate_small_opt(const char* who, const MdgTrajParams* prm, const MdgCell* cell, const MdgTerms* terms, const SmallOpt& o,
+                       RdfFinePlan* P) {
+    if (o.extra == SmallOpt::RDF)
+        MDG_CHECK_ARG(ring_rdf_plan(*prm, *cell, *terms, o.rdf, P), "%s: not available for this system / observable "
+                      "(see mdg_traj_rdf_supported)", who);
+    if (o.extra == SmallOpt::STALE) {
+        MDG_CHECK_ARG(o.freq >= 1 && o.count0 >= 0 && o.code, "%s: bad frequency / counter / list buffer", who);
+        MDG_CHECK_ARG(terms->t[0].kind != MDG_PAIR_TABLE, "%s: a tabulated pair model is not supported", who);
+    }
+    return MDG_OK;
+}
+
+// Launch geometry of the one-workgroup-per-replica kernels (what MDG_TRAJ_DISPATCH launches with); refuses what does not
+// fit SMALL_LDS_MAX.
+struct SmallGeom { int block; int ld; size_t lds; int tl; };
+int small_geometry(const char* who, const MdgTrajParams* prm, const MdgTerms* terms, const float* theta, bool adjoint,
+                   SmallGeom* g) {
+    const int N = prm->n_atoms;
+    const bool table = terms->t[0].kind == MDG_PAIR_TABLE;
+    const int nodes = table ? terms->t[0].p : 0;
+    MDG_CHECK_ARG(!nodes || theta, "%s: the table is passed through theta", who);
+    g->block = pick_block(*prm, table);
+    g->ld = small_ld(N);
+    g->lds = small_lds(N, nodes, adjoint);
+    MDG_CHECK_ARG(g->lds <= SMALL_LDS_MAX, "%s: N=%d does not fit the LDS-resident kernel", who, N);
+    g->tl = pick_tpa_log2(N, g->block);
+    return MDG_OK;
+}
+
+// The forward launch behind every mdg_traj_fwd_small* entry point.  The route is decided here, once: the fused RDF runs on
+// the ring kernels only (ring_rdf_plan asks use_ring itself), stale lists on the generic workgroup kernels only (nothing
+// else reads TrajArgs::code), everything else on the ring where use_ring takes it and on the workgroup kernels otherwise.
+int traj_fwd_small_run(const MdgTrajParams* prm, const MdgCell* cell, const MdgTerms* terms,
+                       const float* theta, const float* mass, const float* t_grid,
+                       const float* v0, const float* q0, const float* pv0,
+                       float* v_t, float* q_t, float* pv_t, int32_t* nonfinite, void* stream, const SmallOpt& o) {
+    int rc = validate(prm, cell, terms);
+    if (rc) return rc;
+    const char* who = small_who(false, o);
+    const bool stale = o.extra == SmallOpt::STALE, rdf = o.extra == SmallOpt::RDF;
+    // (every entry point keeps the answers it gave when it had a launch sequence of its own: the fused-RDF ones count theta
+    //  and the histogram among the required buffers, the plain ones ask for theta only once the ring is taken or a table is
+    //  read -- below --, the stale ones not at all)
+    MDG_CHECK_ARG(mass && t_grid && v0 && q0 && v_t && q_t && (!rdf || ((theta || terms->n_theta_total == 0) && o.raw)),
+                  "%s: null buffer", who);
+    MDG_CHECK_ARG(prm->ensemble == 1 || (pv0 && pv_t), "%s: NHC needs pv0/pv_t", who);
+    RdfFinePlan P;
+    if ((rc = validate_small_opt(who, prm, cell, terms, o, &P)) != MDG_OK) return rc;
+    TrajArgs a{};
+    a.prm = *prm; a.cell = *cell; a.terms = *terms; a.theta = theta; a.mass = mass; a.t = t_grid;
+    a.v0 = v0; a.q0 = q0; a.pv0 = pv0; a.v_t = v_t; a.q_t = q_t; a.pv_t = pv_t; a.nonfinite = nonfinite;
+    hipStream_t st = (hipStream_t)stream;
+    if (rdf || (!stale && use_ring(*prm, *cell, *terms))) {
+        MDG_CHECK_ARG(theta || terms->n_theta_total == 0, "%s: null theta", who);
+        a.f_t = o.f_t;
+        if (!rdf) {
+            MDG_RING_LAUNCH(traj_fwd_ring_kernel, false, , dim3(prm->n_rep), dim3(64), RING_LDS_FWD + ring_table_lds(*terms, false),
+                            st, a, RingRdfArgs{});
+            MDG_CHECK_LAUNCH("traj_fwd_ring_kernel");
+            return MDG_OK;
+        }
+        uint32_t* ghist = nullptr;
+        MDG_HIP(hipMallocAsync((void**)&ghist, sizeof(uint32_t) * (size_t)P.nfine, st));
+        MDG_HIP(hipMemsetAsync(ghist, 0, sizeof(uint32_t) * (size_t)P.nfine, st));
+        RingRdfArgs F = ring_rdf_args(*o.rdf, P);
+        F.ghist = ghist;
+        int grid = (prm->n_rep + RING_RDF_WAVES - 1) / RING_RDF_WAVES;
+        if (grid > 256) grid = 256;                                   // one resident workgroup (16 waves) per CU
+        const size_t lds = sizeof(float) * (size_t)((P.nfine + 1) & ~1LL) + RING_RDF_WAVES * RING_LDS_FWD;
+        MDG_RING_LAUNCH(traj_fwd_ring_kernel, true, , dim3(grid), dim3(64 * RING_RDF_WAVES), lds, st, a, F);
+        rc = mdg_rdf_fine_finish(ghist, P, o.rdf->mu, o.rdf->nbins, o.raw, st);
+        (void)hipFreeAsync(ghist, st);
+        if (rc) return rc;
+        MDG_CHECK_LAUNCH("traj_fwd_ring_kernel<rdf>");
+        return MDG_OK;
+    }
+    SmallGeom g;
+    if ((rc = small_geometry(who, prm, terms, theta, false, &g)) != MDG_OK) return rc;
+    a.ld = g.ld;
+    if (stale) { a.code = o.code; a.freq = o.freq; a.count0 = o.count0; }
+    MDG_TRAJ_DISPATCH(traj_fwd_kernel, stale);
+    MDG_CHECK_LAUNCH(stale ? "traj_fwd_kernel (stale lists)" : "traj_fwd_kernel");
+    return MDG_OK;
+}
+
+// The adjoint launch behind every mdg_traj_adj_small* entry point; routes as traj_fwd_small_run.  (adj_pv0 is not among the
+// required buffers: no entry point of this file ever asked for it.)
+int traj_adj_small_run(const MdgTrajParams* prm, const MdgCell* cell, const MdgTerms* terms,
+                       const float* theta, const float* mass, const float* t_grid,
+                       const float* v_t, const float* q_t, const float* pv_t,
+                       const float* g_v, const float* g_q, const float* g_pv,
+                       float* adj_v0, float* adj_q0, float* adj_pv0, float* adj_theta, void* stream, const SmallOpt& o) {
+    int rc = validate(prm, cell, terms);
+    if (rc) return rc;
+    const char* who = small_who(true, o);
+    const bool stale = o.extra == SmallOpt::STALE, rdf = o.extra == SmallOpt::RDF;
+    // (theta / dL/d(raw): per entry point, as in traj_fwd_small_run)
+    MDG_CHECK_ARG(mass && t_grid && v_t && q_t && adj_v0 && adj_q0 &&
+                  (!rdf || ((theta || terms->n_theta_total == 0) && o.g_raw)), "%s: null buffer", who);
+    MDG_CHECK_ARG(prm->ensemble == 1 || pv_t, "%s: NHC needs pv_t", who);
+    RdfFinePlan P;
+    if ((rc = validate_small_opt(who, prm, cell, terms, o, &P)) != MDG_OK) return rc;
+    TrajArgs a{};
+    a.prm = *prm; a.cell = *cell; a.terms = *terms; a.theta = theta; a.mass = mass; a.t = t_grid;
+    a.v_t = const_cast<float*>(v_t); a.q_t = const_cast<float*>(q_t); a.pv_t = const_cast<float*>(pv_t);
+    a.g_v = g_v; a.g_q = g_q; a.g_pv = g_pv;
+    a.adj_v0 = adj_v0; a.adj_q0 = adj_q0; a.adj_pv0 = adj_pv0; a.adj_theta = adj_theta;
+    hipStream_t st = (hipStream_t)stream;
+    if (rdf || (!stale && use_ring(*prm, *cell, *terms))) {
+        MDG_CHECK_ARG(theta || terms->n_theta_total == 0, "%s: null theta", who);
+        a.f_t = o.f_t;
+        if (!rdf) {
+            // (tabulated kind: RING_TABLE_WAVES replicas per workgroup share the nodes and one pair of gradient planes)
+            const bool rt = terms->t[0].kind == MDG_PAIR_TABLE;
+            const int wpw = rt ? RING_TABLE_WAVES : 1;
+            const size_t lds = wpw * RING_LDS_ADJ + ring_table_lds(*terms, true);
+            if (o.f_t)
+                MDG_RING_LAUNCH(traj_adj_ring_kernel, false, MDG_RING_FT, dim3((prm->n_rep + wpw - 1) / wpw), dim3(64 * wpw), lds,
+                                st, a, RingRdfArgs{});
+            else
+                MDG_RING_LAUNCH(traj_adj_ring_kernel, false, , dim3((prm->n_rep + wpw - 1) / wpw), dim3(64 * wpw), lds,
+                                st, a, RingRdfArgs{});
+            MDG_CHECK_LAUNCH("traj_adj_ring_kernel");
+            return MDG_OK;
+        }
+        float4* tab = nullptr;                                        // (stream-ordered scratch: no state, re-entrant)
+        MDG_HIP(hipMallocAsync((void**)&tab, sizeof(float4) * (size_t)P.ncell, st));
+        rc = mdg_rdf_bwd_table_u(o.rdf->mu, o.rdf->coeff, o.rdf->nbins, o.g_raw, P, tab, st);
+        if (rc == MDG_OK) {
+            RingRdfArgs F = ring_rdf_args(*o.rdf, P);
+            F.tab = tab;
+            const size_t lds = sizeof(float4) * (size_t)P.ncell + RING_LDS_ADJ;
+            if (o.f_t) MDG_RING_LAUNCH(traj_adj_ring_kernel, true, MDG_RING_FT, dim3(prm->n_rep), dim3(64), lds, st, a, F);
+            else MDG_RING_LAUNCH(traj_adj_ring_kernel, true, , dim3(prm->n_rep), dim3(64), lds, st, a, F);
+        }
+        (void)hipFreeAsync(tab, st);
+        if (rc) return rc;
+        MDG_CHECK_LAUNCH("traj_adj_ring_kernel<rdf>");
+        return MDG_OK;
+    }
+    SmallGeom g;
+    if ((rc = small_geometry(who, prm, terms, theta, true, &g)) != MDG_OK) return rc;
+    a.ld = g.ld;
+    if (stale) { a.code = o.code; a.freq = o.freq; a.count0 = o.count0; }
+    MDG_TRAJ_DISPATCH(traj_adj_kernel, stale);
+    MDG_CHECK_LAUNCH(stale ? "traj_adj_kernel (stale lists)" : "traj_adj_kernel");
+    return MDG_OK;
+}
+
 }  // namespace
 
 extern "C" int mdg_traj_small_fits(int n_atoms, int table_nodes) {
@@ -1068,42 +1244,16 @@ extern "C" int mdg_traj_fwd_small(const MdgTrajParams* prm, const MdgCell* cell,
                                   const float* theta, const float* mass, const float* t_grid,
                                   const float* v0, const float* q0, const float* pv0,
                                   float* v_t, float* q_t, float* pv_t, int32_t* nonfinite, void* stream) {
-    return mdg_traj_fwd_small_ft(prm, cell, terms, theta, mass, t_grid, v0, q0, pv0, v_t, q_t, pv_t, nullptr, nonfinite, stream);
+    return traj_fwd_small_run(prm, cell, terms, theta, mass, t_grid, v0, q0, pv0, v_t, q_t, pv_t, nonfinite, stream,
+                              SmallOpt{SmallOpt::PLAIN});
 }
 
 extern "C" int mdg_traj_fwd_small_ft(const MdgTrajParams* prm, const MdgCell* cell, const MdgTerms* terms,
                                      const float* theta, const float* mass, const float* t_grid,
                                      const float* v0, const float* q0, const float* pv0,
                                      float* v_t, float* q_t, float* pv_t, float* f_t, int32_t* nonfinite, void* stream) {
-    int rc = validate(prm, cell, terms);
-    if (rc) return rc;
-    MDG_CHECK_ARG(mass && t_grid && v0 && q0 && v_t && q_t, "traj_fwd: null buffer");
-    MDG_CHECK_ARG(prm->ensemble == 1 || (pv0 && pv_t), "traj_fwd: NHC needs pv0/pv_t");
-    TrajArgs a{};
-    a.prm = *prm; a.cell = *cell; a.terms = *terms; a.theta = theta; a.mass = mass; a.t = t_grid;
-    a.v0 = v0; a.q0 = q0; a.pv0 = pv0; a.v_t = v_t; a.q_t = q_t; a.pv_t = pv_t; a.nonfinite = nonfinite;
-    const int N = prm->n_atoms;
-    if (use_ring(*prm, *cell, *terms)) {
-        MDG_CHECK_ARG(theta || terms->n_theta_total == 0, "traj_fwd: null theta");
-        a.f_t = f_t;
-        MDG_RING_LAUNCH(traj_fwd_ring_kernel, false, , dim3(prm->n_rep), dim3(64), RING_LDS_FWD + ring_table_lds(*terms, false),
-                        (hipStream_t)stream, a, RingRdfArgs{});
-        MDG_CHECK_LAUNCH("traj_fwd_ring_kernel");
-        return MDG_OK;
-    }
-    const int block = pick_block(*prm, terms->t[0].kind == MDG_PAIR_TABLE);
-    const int nodes = terms->t[0].kind == MDG_PAIR_TABLE ? terms->t[0].p : 0;
-    MDG_CHECK_ARG(!nodes || theta, "traj_fwd: the table is passed through theta");
-    a.ld = small_ld(N);
-    const size_t lds = small_lds(N, nodes, false);
-    MDG_CHECK_ARG(lds <= SMALL_LDS_MAX, "traj_fwd: N=%d does not fit the LDS-resident kernel", N);
-    const int tl = pick_tpa_log2(N, block);
-    const bool diag = cell->diag != 0;
-    dim3 grid(prm->n_rep);
-    hipStream_t st = (hipStream_t)stream;
-    MDG_TRAJ_DISPATCH(traj_fwd_kernel);
-    MDG_CHECK_LAUNCH("traj_fwd_kernel");
-    return MDG_OK;
+    return traj_fwd_small_run(prm, cell, terms, theta, mass, t_grid, v0, q0, pv0, v_t, q_t, pv_t, nonfinite, stream,
+                              SmallOpt{SmallOpt::PLAIN, f_t});
 }
 
 extern "C" int mdg_traj_adj_small(const MdgTrajParams* prm, const MdgCell* cell, const MdgTerms* terms,
@@ -1112,8 +1262,8 @@ extern "C" int mdg_traj_adj_small(const MdgTrajParams* prm, const MdgCell* cell,
                                   const float* g_v, const float* g_q, const float* g_pv,
                                   float* adj_v0, float* adj_q0, float* adj_pv0, float* adj_theta,
                                   void* stream) {
-    return mdg_traj_adj_small_ft(prm, cell, terms, theta, mass, t_grid, v_t, q_t, pv_t, nullptr, g_v, g_q, g_pv, adj_v0,
-                                 adj_q0, adj_pv0, adj_theta, stream);
+    return traj_adj_small_run(prm, cell, terms, theta, mass, t_grid, v_t, q_t, pv_t, g_v, g_q, g_pv, adj_v0, adj_q0, adj_pv0,
+                              adj_theta, stream, SmallOpt{SmallOpt::PLAIN});
 }
 
 extern "C" int mdg_traj_adj_small_ft(const MdgTrajParams* prm, const MdgCell* cell, const MdgTerms* terms,
@@ -1122,45 +1272,8 @@ extern "C" int mdg_traj_adj_small_ft(const MdgTrajParams* prm, const MdgCell* ce
                                      const float* g_v, const float* g_q, const float* g_pv,
                                      float* adj_v0, float* adj_q0, float* adj_pv0, float* adj_theta,
                                      void* stream) {
-    int rc = validate(prm, cell, terms);
-    if (rc) return rc;
-    MDG_CHECK_ARG(mass && t_grid && v_t && q_t && adj_v0 && adj_q0, "traj_adj: null buffer");
-    MDG_CHECK_ARG(prm->ensemble == 1 || pv_t, "traj_adj: NHC needs pv_t");
-    TrajArgs a{};
-    a.prm = *prm; a.cell = *cell; a.terms = *terms; a.theta = theta; a.mass = mass; a.t = t_grid;
-    a.v_t = const_cast<float*>(v_t); a.q_t = const_cast<float*>(q_t); a.pv_t = const_cast<float*>(pv_t);
-    a.g_v = g_v; a.g_q = g_q; a.g_pv = g_pv;
-    a.adj_v0 = adj_v0; a.adj_q0 = adj_q0; a.adj_pv0 = adj_pv0; a.adj_theta = adj_theta;
-    const int N = prm->n_atoms;
-    if (use_ring(*prm, *cell, *terms)) {
-        MDG_CHECK_ARG(theta || terms->n_theta_total == 0, "traj_adj: null theta");
-        // (tabulated kind: RING_TABLE_WAVES replicas per workgroup share the nodes and one pair of gradient planes)
-        const bool rt = terms->t[0].kind == MDG_PAIR_TABLE;
-        const int wpw = rt ? RING_TABLE_WAVES : 1;
-        const size_t lds = wpw * RING_LDS_ADJ + ring_table_lds(*terms, true);
-        a.f_t = const_cast<float*>(f_t);
-        if (f_t)
-            MDG_RING_LAUNCH(traj_adj_ring_kernel, false, MDG_RING_FT, dim3((prm->n_rep + wpw - 1) / wpw), dim3(64 * wpw), lds,
-                            (hipStream_t)stream, a, RingRdfArgs{});
-        else
-            MDG_RING_LAUNCH(traj_adj_ring_kernel, false, , dim3((prm->n_rep + wpw - 1) / wpw), dim3(64 * wpw), lds,
-                            (hipStream_t)stream, a, RingRdfArgs{});
-        MDG_CHECK_LAUNCH("traj_adj_ring_kernel");
-        return MDG_OK;
-    }
-    const int block = pick_block(*prm, terms->t[0].kind == MDG_PAIR_TABLE);
-    const int nodes = terms->t[0].kind == MDG_PAIR_TABLE ? terms->t[0].p : 0;
-    MDG_CHECK_ARG(!nodes || theta, "traj_adj: the table is passed through theta");
-    a.ld = small_ld(N);
-    const size_t lds = small_lds(N, nodes, true);
-    MDG_CHECK_ARG(lds <= SMALL_LDS_MAX, "traj_adj: N=%d does not fit the LDS-resident kernel", N);
-    const int tl = pick_tpa_log2(N, block);
-    const bool diag = cell->diag != 0;
-    dim3 grid(prm->n_rep);
-    hipStream_t st = (hipStream_t)stream;
-    MDG_TRAJ_DISPATCH(traj_adj_kernel);
-    MDG_CHECK_LAUNCH("traj_adj_kernel");
-    return MDG_OK;
+    return traj_adj_small_run(prm, cell, terms, theta, mass, t_grid, v_t, q_t, pv_t, g_v, g_q, g_pv, adj_v0, adj_q0, adj_pv0,
+                              adj_theta, stream, SmallOpt{SmallOpt::PLAIN, const_cast<float*>(f_t)});
 }
 
 // ------------------------------------------------------------------------------------ stale neighbour lists
@@ -1174,28 +1287,8 @@ extern "C" int mdg_traj_fwd_small_stale(const MdgTrajParams* prm, const MdgCell*
                                         const float* v0, const float* q0, const float* pv0,
                                         float* v_t, float* q_t, float* pv_t, int32_t* nonfinite,
                                         int freq, int64_t count0, uint16_t* code, void* stream) {
-    int rc = validate(prm, cell, terms);
-    if (rc) return rc;
-    MDG_CHECK_ARG(mass && t_grid && v0 && q0 && v_t && q_t, "traj_fwd_stale: null buffer");
-    MDG_CHECK_ARG(prm->ensemble == 1 || (pv0 && pv_t), "traj_fwd_stale: NHC needs pv0/pv_t");
-    MDG_CHECK_ARG(freq >= 1 && count0 >= 0 && code, "traj_fwd_stale: bad frequency / counter / list buffer");
-    MDG_CHECK_ARG(terms->t[0].kind != MDG_PAIR_TABLE, "traj_fwd_stale: a tabulated pair model is not supported");
-    TrajArgs a{};
-    a.prm = *prm; a.cell = *cell; a.terms = *terms; a.theta = theta; a.mass = mass; a.t = t_grid;
-    a.v0 = v0; a.q0 = q0; a.pv0 = pv0; a.v_t = v_t; a.q_t = q_t; a.pv_t = pv_t; a.nonfinite = nonfinite;
-    a.code = code; a.freq = freq; a.count0 = count0;
-    const int N = prm->n_atoms;
-    const int block = pick_block(*prm, false);
-    a.ld = small_ld(N);
-    const size_t lds = small_lds(N, 0, false);
-    MDG_CHECK_ARG(lds <= SMALL_LDS_MAX, "traj_fwd_stale: N=%d does not fit the LDS-resident kernel", N);
-    const int tl = pick_tpa_log2(N, block);
-    dim3 grid(prm->n_rep);
-    hipStream_t st = (hipStream_t)stream;
-    if (cell->diag) hipLaunchKernelGGL((traj_fwd_kernel<true, MDG_MAX_TERMS, -1>), grid, dim3(block), lds, st, a, tl);
-    else hipLaunchKernelGGL((traj_fwd_kernel<false, MDG_MAX_TERMS, -1>), grid, dim3(block), lds, st, a, tl);
-    MDG_CHECK_LAUNCH("traj_fwd_kernel (stale lists)");
-    return MDG_OK;
+    return traj_fwd_small_run(prm, cell, terms, theta, mass, t_grid, v0, q0, pv0, v_t, q_t, pv_t, nonfinite, stream,
+                              SmallOpt{SmallOpt::STALE, nullptr, nullptr, nullptr, nullptr, freq, count0, code});
 }
 
 extern "C" int mdg_traj_adj_small_stale(const MdgTrajParams* prm, const MdgCell* cell, const MdgTerms* terms,
@@ -1204,30 +1297,8 @@ extern "C" int mdg_traj_adj_small_stale(const MdgTrajParams* prm, const MdgCell*
                                         const float* g_v, const float* g_q, const float* g_pv,
                                         float* adj_v0, float* adj_q0, float* adj_pv0, float* adj_theta,
                                         int freq, int64_t count0, uint16_t* code, void* stream) {
-    int rc = validate(prm, cell, terms);
-    if (rc) return rc;
-    MDG_CHECK_ARG(mass && t_grid && v_t && q_t && adj_v0 && adj_q0, "traj_adj_stale: null buffer");
-    MDG_CHECK_ARG(prm->ensemble == 1 || pv_t, "traj_adj_stale: NHC needs pv_t");
-    MDG_CHECK_ARG(freq >= 1 && count0 >= 0 && code, "traj_adj_stale: bad frequency / counter / list buffer");
-    MDG_CHECK_ARG(terms->t[0].kind != MDG_PAIR_TABLE, "traj_adj_stale: a tabulated pair model is not supported");
-    TrajArgs a{};
-    a.prm = *prm; a.cell = *cell; a.terms = *terms; a.theta = theta; a.mass = mass; a.t = t_grid;
-    a.v_t = const_cast<float*>(v_t); a.q_t = const_cast<float*>(q_t); a.pv_t = const_cast<float*>(pv_t);
-    a.g_v = g_v; a.g_q = g_q; a.g_pv = g_pv;
-    a.adj_v0 = adj_v0; a.adj_q0 = adj_q0; a.adj_pv0 = adj_pv0; a.adj_theta = adj_theta;
-    a.code = code; a.freq = freq; a.count0 = count0;
-    const int N = prm->n_atoms;
-    const int block = pick_block(*prm, false);
-    a.ld = small_ld(N);
-    const size_t lds = small_lds(N, 0, true);
-    MDG_CHECK_ARG(lds <= SMALL_LDS_MAX, "traj_adj_stale: N=%d does not fit the LDS-resident kernel", N);
-    const int tl = pick_tpa_log2(N, block);
-    dim3 grid(prm->n_rep);
-    hipStream_t st = (hipStream_t)stream;
-    if (cell->diag) hipLaunchKernelGGL((traj_adj_kernel<true, MDG_MAX_TERMS, -1>), grid, dim3(block), lds, st, a, tl);
-    else hipLaunchKernelGGL((traj_adj_kernel<false, MDG_MAX_TERMS, -1>), grid, dim3(block), lds, st, a, tl);
-    MDG_CHECK_LAUNCH("traj_adj_kernel (stale lists)");
-    return MDG_OK;
+    return traj_adj_small_run(prm, cell, terms, theta, mass, t_grid, v_t, q_t, pv_t, g_v, g_q, g_pv, adj_v0, adj_q0, adj_pv0,
+                              adj_theta, stream, SmallOpt{SmallOpt::STALE, nullptr, nullptr, nullptr, nullptr, freq, count0, code});
 }
 
 // ------------------------------------------------------------------------------------ fused RDF observable
@@ -1242,8 +1313,8 @@ extern "C" int mdg_traj_fwd_small_rdf(const MdgTrajParams* prm, const MdgCell* c
                                       const float* v0, const float* q0, const float* pv0,
                                       float* v_t, float* q_t, float* pv_t, int32_t* nonfinite,
                                       const MdgRdfFuse* rdf, float* raw, void* stream) {
-    return mdg_traj_fwd_small_rdf_ft(prm, cell, terms, theta, mass, t_grid, v0, q0, pv0, v_t, q_t, pv_t, nullptr, nonfinite,
-                                     rdf, raw, stream);
+    return traj_fwd_small_run(prm, cell, terms, theta, mass, t_grid, v0, q0, pv0, v_t, q_t, pv_t, nonfinite, stream,
+                              SmallOpt{SmallOpt::RDF, nullptr, rdf, raw});
 }
 
 extern "C" int mdg_traj_fwd_small_rdf_ft(const MdgTrajParams* prm, const MdgCell* cell, const MdgTerms* terms,
@@ -1251,31 +1322,8 @@ extern "C" int mdg_traj_fwd_small_rdf_ft(const MdgTrajParams* prm, const MdgCell
                                          const float* v0, const float* q0, const float* pv0,
                                          float* v_t, float* q_t, float* pv_t, float* f_t, int32_t* nonfinite,
                                          const MdgRdfFuse* rdf, float* raw, void* stream) {
-    int rc = validate(prm, cell, terms);
-    if (rc) return rc;
-    MDG_CHECK_ARG((theta || terms->n_theta_total == 0) && mass && t_grid && v0 && q0 && v_t && q_t && raw, "traj_fwd_rdf: null buffer");
-    MDG_CHECK_ARG(prm->ensemble == 1 || (pv0 && pv_t), "traj_fwd_rdf: NHC needs pv0/pv_t");
-    RdfFinePlan P;
-    MDG_CHECK_ARG(ring_rdf_plan(*prm, *cell, *terms, rdf, &P), "traj_fwd_rdf: not available for this system / observable "
-                  "(see mdg_traj_rdf_supported)");
-    TrajArgs a{};
-    a.prm = *prm; a.cell = *cell; a.terms = *terms; a.theta = theta; a.mass = mass; a.t = t_grid;
-    a.v0 = v0; a.q0 = q0; a.pv0 = pv0; a.v_t = v_t; a.q_t = q_t; a.pv_t = pv_t; a.nonfinite = nonfinite; a.f_t = f_t;
-    hipStream_t st = (hipStream_t)stream;
-    uint32_t* ghist = nullptr;
-    MDG_HIP(hipMallocAsync((void**)&ghist, sizeof(uint32_t) * (size_t)P.nfine, st));
-    MDG_HIP(hipMemsetAsync(ghist, 0, sizeof(uint32_t) * (size_t)P.nfine, st));
-    RingRdfArgs F = ring_rdf_args(*rdf, P);
-    F.ghist = ghist;
-    int grid = (prm->n_rep + RING_RDF_WAVES - 1) / RING_RDF_WAVES;
-    if (grid > 256) grid = 256;                                   // one resident workgroup (16 waves) per CU
-    const size_t lds = sizeof(float) * (size_t)((P.nfine + 1) & ~1LL) + RING_RDF_WAVES * RING_LDS_FWD;
-    MDG_RING_LAUNCH(traj_fwd_ring_kernel, true, , dim3(grid), dim3(64 * RING_RDF_WAVES), lds, st, a, F);
-    rc = mdg_rdf_fine_finish(ghist, P, rdf->mu, rdf->nbins, raw, st);
-    (void)hipFreeAsync(ghist, st);
-    if (rc) return rc;
-    MDG_CHECK_LAUNCH("traj_fwd_ring_kernel<rdf>");
-    return MDG_OK;
+    return traj_fwd_small_run(prm, cell, terms, theta, mass, t_grid, v0, q0, pv0, v_t, q_t, pv_t, nonfinite, stream,
+                              SmallOpt{SmallOpt::RDF, f_t, rdf, raw});
 }
 
 extern "C" int mdg_traj_adj_small_rdf(const MdgTrajParams* prm, const MdgCell* cell, const MdgTerms* terms,
@@ -1284,8 +1332,8 @@ extern "C" int mdg_traj_adj_small_rdf(const MdgTrajParams* prm, const MdgCell* c
                                       const float* g_v, const float* g_q, const float* g_pv,
                                       float* adj_v0, float* adj_q0, float* adj_pv0, float* adj_theta,
                                       const MdgRdfFuse* rdf, const float* g_raw, void* stream) {
-    return mdg_traj_adj_small_rdf_ft(prm, cell, terms, theta, mass, t_grid, v_t, q_t, pv_t, nullptr, g_v, g_q, g_pv, adj_v0,
-                                     adj_q0, adj_pv0, adj_theta, rdf, g_raw, stream);
+    return traj_adj_small_run(prm, cell, terms, theta, mass, t_grid, v_t, q_t, pv_t, g_v, g_q, g_pv, adj_v0, adj_q0, adj_pv0,
+                              adj_theta, stream, SmallOpt{SmallOpt::RDF, nullptr, rdf, nullptr, g_raw});
 }
 
 extern "C" int mdg_traj_adj_small_rdf_ft(const MdgTrajParams* prm, const MdgCell* cell, const MdgTerms* terms,
@@ -1294,32 +1342,6 @@ extern "C" int mdg_traj_adj_small_rdf_ft(const MdgTrajParams* prm, const MdgCell
                                          const float* g_v, const float* g_q, const float* g_pv,
                                          float* adj_v0, float* adj_q0, float* adj_pv0, float* adj_theta,
                                          const MdgRdfFuse* rdf, const float* g_raw, void* stream) {
-    int rc = validate(prm, cell, terms);
-    if (rc) return rc;
-    MDG_CHECK_ARG((theta || terms->n_theta_total == 0) && mass && t_grid && v_t && q_t && adj_v0 && adj_q0 && g_raw, "traj_adj_rdf: null buffer");
-    MDG_CHECK_ARG(prm->ensemble == 1 || pv_t, "traj_adj_rdf: NHC needs pv_t");
-    RdfFinePlan P;
-    MDG_CHECK_ARG(ring_rdf_plan(*prm, *cell, *terms, rdf, &P), "traj_adj_rdf: not available for this system / observable "
-                  "(see mdg_traj_rdf_supported)");
-    TrajArgs a{};
-    a.prm = *prm; a.cell = *cell; a.terms = *terms; a.theta = theta; a.mass = mass; a.t = t_grid;
-    a.v_t = const_cast<float*>(v_t); a.q_t = const_cast<float*>(q_t); a.pv_t = const_cast<float*>(pv_t);
-    a.g_v = g_v; a.g_q = g_q; a.g_pv = g_pv;
-    a.adj_v0 = adj_v0; a.adj_q0 = adj_q0; a.adj_pv0 = adj_pv0; a.adj_theta = adj_theta;
-    hipStream_t st = (hipStream_t)stream;
-    float4* tab = nullptr;                                        // (stream-ordered scratch: no state, re-entrant)
-    MDG_HIP(hipMallocAsync((void**)&tab, sizeof(float4) * (size_t)P.ncell, st));
-    rc = mdg_rdf_bwd_table_u(rdf->mu, rdf->coeff, rdf->nbins, g_raw, P, tab, st);
-    if (rc == MDG_OK) {
-        RingRdfArgs F = ring_rdf_args(*rdf, P);
-        F.tab = tab;
-        const size_t lds = sizeof(float4) * (size_t)P.ncell + RING_LDS_ADJ;
-        a.f_t = const_cast<float*>(f_t);
-        if (f_t) MDG_RING_LAUNCH(traj_adj_ring_kernel, true, MDG_RING_FT, dim3(prm->n_rep), dim3(64), lds, st, a, F);
-        else MDG_RING_LAUNCH(traj_adj_ring_kernel, true, , dim3(prm->n_rep), dim3(64), lds, st, a, F);
-    }
-    (void)hipFreeAsync(tab, st);
-    if (rc) return rc;
-    MDG_CHECK_LAUNCH("traj_adj_ring_kernel<rdf>");
-    return MDG_OK;
+    return traj_adj_small_run(prm, cell, terms, theta, mass, t_grid, v_t, q_t, pv_t, g_v, g_q, g_pv, adj_v0, adj_q0, adj_pv0,
+                              adj_theta, stream, SmallOpt{SmallOpt::RDF, const_cast<float*>(f_t), rdf, nullptr, g_raw});
 }

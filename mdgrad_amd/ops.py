@@ -347,6 +347,10 @@ class FusedSpec:
         self.ensemble, self.n_atoms, self.mass = ensemble, n_atoms, mass
         self.cell_struct, self.terms, self.n_theta_total, self.masks = cell_struct, terms, n_theta_total, masks
         self.T, self.n_dof, self.Q, self.block = float(T), float(n_dof), list(Q), block
+        # what the trajectory code reads beyond the constructor's arguments (assigned by md.fused_spec, the observable
+        # and FusedTrajFn): tabulated pair model, topology_update_freq > 1, the fused observable, stacked replicas
+        self.table, self.stale_freq, self.rdf_hint, self.n_rep = False, 0, None, 1
+        self._integrator, self._last_large = None, None
 
     def params(self, n_rep, n_frames):
         p = MdgTrajParams()
@@ -378,7 +382,7 @@ def large_list_builds(spec):
     backward pass): int32 [R, T], entry (r, f) = the frame whose neighbour search produced the candidate list that
     served frame f (Verlet reuse, csrc/traj_large.hip); None when the lists were not kept.  Diagnostics:
     `len(set(row))` searches ran for that replica."""
-    last = getattr(spec, "_last_large", None)
+    last = spec._last_large
     if last is None:
         raise RuntimeError("mdgrad_amd: no trajectory of the multi-launch (large-N) kernels has run on this spec")
     ref, (R, N, T, KT) = last
@@ -427,11 +431,7 @@ def fused_traj(v0, q0, pv0, t, theta, spec, time_dim=None):
     """FusedTrajFn.apply plus the bookkeeping of the fused observable: returns (v_t, q_t[, pv_t]) with q_t tagged so
     that an `rdf` called on it (or on a slice of it along time) finds the histogram the launch already made, or
     registers itself for the next launch."""
-    spec._fuse_now = True                  # (direct callers of FusedTrajFn.apply keep its plain output tuple)
-    try:
-        outs = FusedTrajFn.apply(v0, q0, pv0, t, theta, spec)
-    finally:
-        spec._fuse_now = False
+    outs = FusedTrajFn.apply(v0, q0, pv0, t, theta, spec, True)   # (direct six-argument callers keep the plain output tuple)
     n = 3 if spec.ensemble == 0 else 2
     tag_trajectory(outs[1], spec, outs[n] if len(outs) > n else None,
                    (1 if v0.dim() == 3 else 0) if time_dim is None else time_dim)
@@ -439,7 +439,27 @@ def fused_traj(v0, q0, pv0, t, theta, spec, time_dim=None):
 
 
 def tag_trajectory(q_t, spec, raw, time_dim):
-    q_t._mdg_traj = (spec, time_dim, getattr(spec, "rdf_hint", None) if raw is not None else None, raw)
+    q_t._mdg_traj = (spec, time_dim, spec.rdf_hint if raw is not None else None, raw)
+
+
+def _stale_launch(ctx, spec, R, T, dev, calls, launch):
+    """One launch of the stale-list kernels (topology_update_freq > 1: lists rebuilt at the calls whose running count is a
+    multiple of the frequency, md.py:200-204; on the large path the host loop of the library decides per call whether it
+    rebuilds, round 6).  `launch(freq, count0, lists)` runs with the integrator's persistent lists and call counter, which
+    then advances by the right-hand-side calls the reference makes: `calls` = 2 per interval in the forward pass, 3 in the
+    adjoint (the dL/dt evaluation and two augmented ones, sovlers.py:258-266).  Returns the lists."""
+    integ = spec._integrator
+    if getattr(integ, "_stale_code", None) is None and ctx.stale_code is not None:
+        # a generic force / odeint call on this integrator between the fused forward and this backward (logging,
+        # an observable) dropped the fused lists (md.update_topology): the forward's own lists -- held on ctx --
+        # are the ones its saved frames were integrated with; the call counter keeps what the calls in between
+        # made of it, as the reference's would
+        integ._stale_code = ctx.stale_code
+    code = integ.stale_lists(R, spec.n_atoms, dev, large=ctx.large)
+    launch(int(ctx.stale_freq), int(integ.update_count), ptr(code))
+    integ.update_count += calls * (T - 1)
+    integ._stale_fused_dirty = True        # (the generic path's own lists are older than these now: md.update_topology)
+    return code
 
 
 class FusedTrajFn(torch.autograd.Function):
@@ -448,7 +468,7 @@ class FusedTrajFn(torch.autograd.Function):
     States may carry a leading replica dimension [R,N,3]."""
 
     @staticmethod
-    def forward(ctx, v0, q0, pv0, t, theta, spec):
+    def forward(ctx, v0, q0, pv0, t, theta, spec, fuse=False):
         lib = _lib.load()
         require_gpu(v0, "v0"), require_gpu(q0, "q0"), require_gpu(t, "t")
         batched = v0.dim() == 3
@@ -465,9 +485,12 @@ class FusedTrajFn(torch.autograd.Function):
         q_t = torch.empty(R, T, N, 3, device=dev)
         pv_t = torch.empty(R, T, Cn, device=dev) if nhc else None
         prm = spec.params(R, T)
-        ctx.ws = None
-        fuse = getattr(spec, "rdf_hint", None) if getattr(spec, "_fuse_now", False) else None
-        if fuse is not None and (spec.large or getattr(spec, "table", False) or thc is None or not fuse.fits(spec, dev)
+        # the route is decided here, once, and kept on ctx for backward: multi-launch (large) or one-workgroup / ring
+        # kernels, stale lists or not, the RDF fused in or not (`fuse`: only fused_traj / odeint_adjoint ask), forces kept or not
+        ctx.large, ctx.stale_freq, ctx.table = bool(spec.large), int(spec.stale_freq), bool(spec.table)
+        ctx.ws, ctx.lists_ok, ctx.stale_code = None, False, None
+        fuse = spec.rdf_hint if fuse else None
+        if fuse is not None and (spec.large or spec.table or thc is None or not fuse.fits(spec, dev)
                                  or not lib.mdg_traj_rdf_supported(C.byref(prm), C.byref(spec.cell_struct),
                                                                    C.byref(spec.terms), C.byref(fuse.struct()))):
             fuse = None
@@ -476,39 +499,38 @@ class FusedTrajFn(torch.autograd.Function):
         # the wave-per-replica kernels keep the force of every saved frame for the adjoint's first evaluation of each
         # interval (mdg_traj_*_ft: 4 R T N 3 bytes, written once and read once; 1.06 GB at 16 384 x 50 x 108 atoms)
         f_t = None
-        if not spec.large and not getattr(spec, "stale_freq", 0) and lib.mdg_traj_ring_taken(
+        if not ctx.large and not ctx.stale_freq and lib.mdg_traj_ring_taken(
                 C.byref(prm), C.byref(spec.cell_struct), C.byref(spec.terms)):
             f_t = torch.empty(R, T, N, 3, device=dev)
         ctx.f_t = f_t
+        args = (C.byref(prm), C.byref(spec.cell_struct), C.byref(spec.terms), ptr(thc), ptr(spec.mass), ptr(tc),
+                ptr(v0c), ptr(q0c), ptr(pv0c), ptr(v_t), ptr(q_t), ptr(pv_t))
+
+        def run(fn, *extras):                      # the forward launch: the common arguments, then the route's own
+            check(fn(*args, *extras, stream_ptr(dev)), fn.__name__)
+
+        if ctx.large:
+            ws = torch.empty(int(lib.mdg_traj_large_workspace(R, N, T, spec.n_theta_total)), device=dev)
+            flags = torch.zeros(8, dtype=torch.int32, device=dev)
+            out = (ptr(ws), ptr(flags))
+        else:
+            bad = torch.zeros(R, dtype=torch.int32, device=dev)
+            out = (ptr(bad),)
         if fuse is not None:
             # the observable rides along: raw soft histogram of the selected frames of all replicas
             raw = torch.empty(fuse.nbins, device=dev)
-            bad = torch.zeros(R, dtype=torch.int32, device=dev)
-            check(lib.mdg_traj_fwd_small_rdf_ft(C.byref(prm), C.byref(spec.cell_struct), C.byref(spec.terms), ptr(thc),
-                                                ptr(spec.mass), ptr(tc), ptr(v0c), ptr(q0c), ptr(pv0c), ptr(v_t),
-                                                ptr(q_t), ptr(pv_t), ptr(f_t), ptr(bad), C.byref(fuse.struct()), ptr(raw),
-                                                stream_ptr(dev)), "mdg_traj_fwd_small_rdf_ft")
-        elif spec.large:
-            ws = torch.empty(int(lib.mdg_traj_large_workspace(R, N, T, spec.n_theta_total)), device=dev)
-            flags = torch.zeros(8, dtype=torch.int32, device=dev)
-            if getattr(spec, "stale_freq", 0):
-                # topology_update_freq > 1 beyond one workgroup per replica (round 6): stale rows, the host loop of the library
-                # decides per call whether it rebuilds (md.py:200-204); 2 (T - 1) calls
-                integ = spec._integrator
+            run(lib.mdg_traj_fwd_small_rdf_ft, ptr(f_t), *out, C.byref(fuse.struct()), ptr(raw))
+        elif ctx.stale_freq:
+            if ctx.large:
                 assert int(lib.mdg_traj_large_stale_words(R, N)) == R * N * 257
-                rows = integ.stale_lists(R, N, dev, large=True)
-                check(lib.mdg_traj_fwd_large_stale(C.byref(prm), C.byref(spec.cell_struct), C.byref(spec.terms), ptr(thc),
-                                                   ptr(spec.mass), ptr(tc), ptr(v0c), ptr(q0c), ptr(pv0c), ptr(v_t), ptr(q_t),
-                                                   ptr(pv_t), ptr(ws), ptr(flags), int(spec.stale_freq), int(integ.update_count),
-                                                   ptr(rows), stream_ptr(dev)), "mdg_traj_fwd_large_stale")
-                integ.update_count += 2 * (T - 1)
-                integ._stale_fused_dirty = True
-                ctx.stale_code = rows
-            else:
-                check(lib.mdg_traj_fwd_large(C.byref(prm), C.byref(spec.cell_struct), C.byref(spec.terms), ptr(thc),
-                                             ptr(spec.mass), ptr(tc), ptr(v0c), ptr(q0c), ptr(pv0c), ptr(v_t),
-                                             ptr(q_t), ptr(pv_t), ptr(ws), ptr(flags), stream_ptr(dev)),
-                      "mdg_traj_fwd_large")
+            fn = lib.mdg_traj_fwd_large_stale if ctx.large else lib.mdg_traj_fwd_small_stale
+            # (the lists this pass ended with: what its backward continues from)
+            ctx.stale_code = _stale_launch(ctx, spec, R, T, dev, 2, lambda *tail: run(fn, *out, *tail))
+        elif ctx.large:
+            run(lib.mdg_traj_fwd_large, *out)
+        else:
+            run(lib.mdg_traj_fwd_small_ft, ptr(f_t), *out)
+        if ctx.large:
             fl = flags.tolist()                    # one sync per trajectory (neighbour buffer / table range check)
             if fl[0]:
                 raise RuntimeError("mdgrad_amd: an atom has %d neighbours within the cutoff; the fused large-N "
@@ -520,25 +542,7 @@ class FusedTrajFn(torch.autograd.Function):
             spec._last_large = (weakref.ref(ws), (R, N, T, spec.n_theta_total))    # (ops.large_list_builds)
             ctx.lists_ok = not fl[4]               # every frame's candidate list was stored: the adjoint re-tests them
             LARGE_STATS["lists_incomplete"] += int(bool(fl[4]))
-        elif getattr(spec, "stale_freq", 0):
-            # topology_update_freq > 1: stale lists, rebuilt at the calls whose running count is a multiple of the frequency
-            # (md.py:200-204); the forward pass makes 2 (T - 1) calls
-            integ = spec._integrator
-            code = integ.stale_lists(R, N, dev)
-            bad = torch.zeros(R, dtype=torch.int32, device=dev)
-            check(lib.mdg_traj_fwd_small_stale(C.byref(prm), C.byref(spec.cell_struct), C.byref(spec.terms), ptr(thc),
-                                               ptr(spec.mass), ptr(tc), ptr(v0c), ptr(q0c), ptr(pv0c), ptr(v_t), ptr(q_t),
-                                               ptr(pv_t), ptr(bad), int(spec.stale_freq), int(integ.update_count), ptr(code),
-                                               stream_ptr(dev)), "mdg_traj_fwd_small_stale")
-            integ.update_count += 2 * (T - 1)
-            integ._stale_fused_dirty = True        # (the generic path's own lists are older than these now: md.update_topology)
-            ctx.stale_code = code                  # (the lists this pass ended with: what its backward continues from)
-        else:
-            bad = torch.zeros(R, dtype=torch.int32, device=dev)
-            check(lib.mdg_traj_fwd_small_ft(C.byref(prm), C.byref(spec.cell_struct), C.byref(spec.terms), ptr(thc),
-                                            ptr(spec.mass), ptr(tc), ptr(v0c), ptr(q0c), ptr(pv0c), ptr(v_t),
-                                            ptr(q_t), ptr(pv_t), ptr(f_t), ptr(bad), stream_ptr(dev)), "mdg_traj_fwd_small_ft")
-        if getattr(spec, "table", False) and not spec.large:
+        if ctx.table and not ctx.large:
             # tabulated user pair module: a live pair closer than the first table node has no valid entry
             # (one host sync per trajectory, table mode only)
             if bool((bad & 2).any()):
@@ -603,36 +607,29 @@ class FusedTrajFn(torch.autograd.Function):
         KT = spec.n_theta_total
         adj_th = torch.zeros(R, KT, device=dev) if KT else None
         prm = spec.params(R, T)
-        table = getattr(spec, "table", False)
+        table, ws, lists_ok = ctx.table, ctx.ws, ctx.lists_ok
+        frames = (ptr(thc), ptr(spec.mass), ptr(tc), ptr(v_t), ptr(q_t), ptr(pv_t))
+        grads_ = (ptr(gv), ptr(gq), ptr(gp), ptr(adj_v), ptr(adj_q), ptr(adj_p), ptr(adj_th))
 
-        ws, lists_ok = getattr(ctx, "ws", None), getattr(ctx, "lists_ok", False)
-        f_t = getattr(ctx, "f_t", None)
+        def run(fn, terms, *extras, prm=prm, f_t=()):
+            # the adjoint launch: the common arguments (the _ft entry points take the forward's forces after the frames),
+            # then the route's own
+            check(fn(C.byref(prm), C.byref(spec.cell_struct), C.byref(terms), *frames, *f_t, *grads_, *extras,
+                     stream_ptr(dev)), fn.__name__)
 
         def launch(terms, search=False):
+            # the route the forward took (ctx); the fused RDF only while its gradient has not been folded into gq above
             if g_raw is not None:
                 gr = g_raw.detach().to(torch.float32).contiguous()
-                check(lib.mdg_traj_adj_small_rdf_ft(C.byref(prm), C.byref(spec.cell_struct), C.byref(terms), ptr(thc),
-                                                    ptr(spec.mass), ptr(tc), ptr(v_t), ptr(q_t), ptr(pv_t), ptr(f_t), ptr(gv),
-                                                    ptr(gq), ptr(gp), ptr(adj_v), ptr(adj_q), ptr(adj_p), ptr(adj_th),
-                                                    C.byref(fuse.struct()), ptr(gr), stream_ptr(dev)),
-                      "mdg_traj_adj_small_rdf_ft")
+                run(lib.mdg_traj_adj_small_rdf_ft, terms, C.byref(fuse.struct()), ptr(gr), f_t=(ptr(ctx.f_t),))
                 return None
-            if spec.large and getattr(spec, "stale_freq", 0):
-                # stale rows; 3 calls per interval (the dL/dt evaluation and two augmented ones, sovlers.py:258-266)
-                integ = spec._integrator
-                if getattr(integ, "_stale_code", None) is None and getattr(ctx, "stale_code", None) is not None:
-                    integ._stale_code = ctx.stale_code      # (a generic call in between dropped them: see the small path below)
-                rows = integ.stale_lists(R, N, dev, large=True)
-                flags = torch.zeros(8, dtype=torch.int32, device=dev)
-                check(lib.mdg_traj_adj_large_stale(C.byref(prm), C.byref(spec.cell_struct), C.byref(terms), ptr(thc),
-                                                   ptr(spec.mass), ptr(tc), ptr(v_t), ptr(q_t), ptr(pv_t), ptr(gv), ptr(gq),
-                                                   ptr(gp), ptr(adj_v), ptr(adj_q), ptr(adj_p), ptr(adj_th), ptr(ws), ptr(flags),
-                                                   int(spec.stale_freq), int(integ.update_count), ptr(rows), stream_ptr(dev)),
-                      "mdg_traj_adj_large_stale")
-                integ.update_count += 3 * (T - 1)
-                integ._stale_fused_dirty = True
+            if ctx.stale_freq:
+                flags = torch.zeros(8, dtype=torch.int32, device=dev) if ctx.large else None
+                fn = lib.mdg_traj_adj_large_stale if ctx.large else lib.mdg_traj_adj_small_stale
+                out = (ptr(ws), ptr(flags)) if ctx.large else ()
+                _stale_launch(ctx, spec, R, T, dev, 3, lambda *tail: run(fn, terms, *out, *tail))
                 return flags
-            if spec.large:
+            if ctx.large:
                 # the stored candidate lists of the forward pass serve the adjoint unless one overflowed there (or, flag
                 # 5 below, a midpoint moved past their skin): block = -1 asks for fresh searches
                 # (a loop, not a recursive call: a closure that names itself is a reference cycle, and this one would
@@ -641,36 +638,12 @@ class FusedTrajFn(torch.autograd.Function):
                 for search in ((search,) if (search or not lists_ok or spec.block == -1) else (False, True)):
                     pl.block = -1 if (search or not lists_ok or spec.block == -1) else 0
                     flags = torch.zeros(8, dtype=torch.int32, device=dev)
-                    check(lib.mdg_traj_adj_large(C.byref(pl), C.byref(spec.cell_struct), C.byref(terms), ptr(thc),
-                                                 ptr(spec.mass), ptr(tc), ptr(v_t), ptr(q_t), ptr(pv_t), ptr(gv), ptr(gq),
-                                                 ptr(gp), ptr(adj_v), ptr(adj_q), ptr(adj_p), ptr(adj_th), ptr(ws),
-                                                 ptr(flags), stream_ptr(dev)), "mdg_traj_adj_large")
+                    run(lib.mdg_traj_adj_large, terms, ptr(ws), ptr(flags), prm=pl)
                     if pl.block == -1 or not int(flags[5]):
                         break
                     LARGE_STATS["adjoint_redone_with_searches"] += 1
                 return flags
-            if getattr(spec, "stale_freq", 0):
-                # the adjoint makes 3 calls per interval (the dL/dt evaluation and two augmented ones, sovlers.py:258-266)
-                integ = spec._integrator
-                if getattr(integ, "_stale_code", None) is None and getattr(ctx, "stale_code", None) is not None:
-                    # a generic force / odeint call on this integrator between the fused forward and this backward (logging,
-                    # an observable) dropped the fused lists (md.update_topology): the forward's own lists -- held on ctx --
-                    # are the ones its saved frames were integrated with; the call counter keeps what the calls in between
-                    # made of it, as the reference's would
-                    integ._stale_code = ctx.stale_code
-                code = integ.stale_lists(R, N, dev)
-                check(lib.mdg_traj_adj_small_stale(C.byref(prm), C.byref(spec.cell_struct), C.byref(terms), ptr(thc),
-                                                   ptr(spec.mass), ptr(tc), ptr(v_t), ptr(q_t), ptr(pv_t), ptr(gv), ptr(gq),
-                                                   ptr(gp), ptr(adj_v), ptr(adj_q), ptr(adj_p), ptr(adj_th),
-                                                   int(spec.stale_freq), int(integ.update_count), ptr(code),
-                                                   stream_ptr(dev)), "mdg_traj_adj_small_stale")
-                integ.update_count += 3 * (T - 1)
-                integ._stale_fused_dirty = True
-                return None
-            check(lib.mdg_traj_adj_small_ft(C.byref(prm), C.byref(spec.cell_struct), C.byref(terms), ptr(thc),
-                                            ptr(spec.mass), ptr(tc), ptr(v_t), ptr(q_t), ptr(pv_t), ptr(f_t), ptr(gv), ptr(gq),
-                                            ptr(gp), ptr(adj_v), ptr(adj_q), ptr(adj_p), ptr(adj_th),
-                                            stream_ptr(dev)), "mdg_traj_adj_small_ft")
+            run(lib.mdg_traj_adj_small_ft, terms, f_t=(ptr(ctx.f_t),))
             return None
 
         def check_large(flags):
@@ -715,7 +688,7 @@ class FusedTrajFn(torch.autograd.Function):
         g_t = None
         if ctx.needs_input_grad[3]:
             g_t = _time_vjps(spec, tc, v_t, q_t, pv_t, gv, gq, gp)
-        return adj_v, adj_q, adj_p, g_t, gth, None
+        return adj_v, adj_q, adj_p, g_t, gth, None, None
 
 
 def _time_vjps(spec, t, v_t, q_t, pv_t, gv, gq, gp):
@@ -723,12 +696,12 @@ def _time_vjps(spec, t, v_t, q_t, pv_t, gv, gq, gp):
     k >= 1 and dL/dt_0 = -(their sum); the right-hand side does not depend on t, so the adjoint of time is not
     changed by the augmented integration.  Nobody on the hot path consumes it (the reference's drivers do not
     either), so it is computed on request only -- one force evaluation per saved frame on the generic HIP ops."""
-    integ = getattr(spec, "_integrator", None)
+    integ = spec._integrator
     if integ is None:
         raise NotImplementedError("mdgrad_amd: dL/dt needs the integrator behind the fused spec")
     R, T = v_t.shape[0], v_t.shape[1]
     nhc = pv_t is not None
-    stacked = getattr(spec, "n_rep", 1) > 1
+    stacked = spec.n_rep > 1
     zero = lambda like: torch.zeros_like(like)
     out = torch.zeros(T, device=v_t.device, dtype=t.dtype)
     with torch.no_grad():

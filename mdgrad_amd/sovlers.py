@@ -409,15 +409,11 @@ def odeint_adjoint(func, y0, t, rtol=1e-6, atol=1e-12, method=None, options=None
         flat_params = spec.flat_params()
         y0 = tuple(y0)
         pv0 = y0[2] if spec.ensemble == 0 else None
-        R, N = getattr(spec, "n_rep", 1), spec.n_atoms
+        R, N = spec.n_rep, spec.n_atoms
         if R > 1 and y0[0].dim() == 2:
             # replica-stacked system ([R*N, 3] states): one workgroup (or grid row) per replica
-            spec._fuse_now = True
-            try:
-                outs = ops.FusedTrajFn.apply(y0[0].reshape(R, N, 3), y0[1].reshape(R, N, 3),
-                                             pv0.reshape(R, -1) if pv0 is not None else None, t, flat_params, spec)
-            finally:
-                spec._fuse_now = False
+            outs = ops.FusedTrajFn.apply(y0[0].reshape(R, N, 3), y0[1].reshape(R, N, 3),
+                                         pv0.reshape(R, -1) if pv0 is not None else None, t, flat_params, spec, True)
             T_ = t.shape[0]
             res = [outs[0].transpose(0, 1).reshape(T_, R * N, 3), outs[1].transpose(0, 1).reshape(T_, R * N, 3)]
             if pv0 is not None:

@@ -279,6 +279,71 @@ def test_host_side_of_the_stale_list_entry_points_of_the_large_path():
     assert fwd(lj, 3, 0, fake) == -1                       # (beyond the large path's 32 768 atoms)
 
 
+def test_refusals_of_the_ten_small_trajectory_entry_points():
+    """mdg_traj_{fwd,adj}_small[_ft|_stale|_rdf|_rdf_ft] without a GPU: what each entry point refuses before any launch and
+    in which words.  The expected column was recorded by running this table against the library of commit b315187, where
+    six of the ten had a launch sequence of their own; the one launcher per direction behind them since keeps every
+    entry point's answer.  Every tuple is refused during validation (fake pointers, nothing is launched)."""
+    from mdgrad_amd import _lib, ops
+    lib = _lib.load()
+    fake, B = ctypes.c_void_p(0x1000), ctypes.byref
+    cell = _lib.make_cell([4.8] * 3)
+    lj = ops.make_terms([ops.make_term(dict(kind=0,      # MDG_PAIR_LJ
+                                             p=12, q=6, c=1.0), 2.5, 0, 2, None)], 2)
+    tab = ops.make_terms([ops.make_term(dict(kind=ops.MDG_PAIR_TABLE, p=64, a=0.25, phi=0.1, c=1.0), 2.5, 0, 128, None)], 128)
+
+    def params(n_rep=1, n_atoms=108, n_chains=3):
+        prm = _lib.MdgTrajParams()
+        prm.n_rep, prm.n_atoms, prm.n_frames, prm.n_chains, prm.ensemble = n_rep, n_atoms, 5, n_chains, 0
+        return prm
+
+    def fuse(stride=1):
+        return _lib.MdgRdfFuse(0x1000, 100, -1632.0, 0.75, 0.0175, 2.5, 0, stride)
+
+    def call(name, prm=None, terms=lj, null=(), freq=3, count0=0, rdf=None):
+        prm = params() if prm is None else prm
+        adj = "_adj_" in name
+        names = ["theta", "mass", "t"] + (["v_t", "q_t", "pv_t"] if adj else ["v0", "q0", "pv0", "v_t", "q_t", "pv_t"])
+        names += ["f_t"] if name.endswith("_ft") else []
+        names += ["g_v", "g_q", "g_pv", "adj_v0", "adj_q0", "adj_pv0", "adj_theta"] if adj else ["nonfinite"]
+        args = [None if n in null else fake for n in names]
+        if "stale" in name:
+            args += [freq, count0, None if "code" in null else fake]
+        elif "rdf" in name:
+            args += [None if "rdf" in null else B(fuse() if rdf is None else rdf), None if "raw" in null else fake]
+        rc = getattr(lib, name)(None if "prm" in null else B(prm), B(cell), B(terms), *args, None)
+        return rc, lib.mdg_last_error()
+
+    plain = ["mdg_traj_%s_small%s" % (d, s) for d in ("fwd", "adj") for s in ("", "_ft")]
+    stale = ["mdg_traj_%s_small_stale" % d for d in ("fwd", "adj")]
+    fused = ["mdg_traj_%s_small_rdf%s" % (d, s) for d in ("fwd", "adj") for s in ("", "_ft")]
+    ring = dict(prm=params(n_rep=1024))                  # (many replicas of one LJ 12-6 term: the wave-per-replica kernels)
+    table = [                                            # (entry points, arguments, expected substring of mdg_last_error)
+        (plain + stale + fused, dict(null=("prm",)), b"null descriptor"),
+        (plain + stale + fused, dict(prm=params(n_rep=0)), b"bad sizes"),
+        (plain + stale + fused, dict(prm=params(n_chains=1)), b"num_chains"),
+        (plain + stale + fused, dict(null=("pv_t",)), b"NHC needs"),
+        (plain + stale + fused, dict(null=("mass",)), b"null buffer"),
+        (plain + stale, dict(prm=params(n_atoms=4096)), b"does not fit the LDS"),
+        (fused, dict(prm=params(n_atoms=4096)), b"not available"),
+        (plain, dict(prm=params(n_atoms=200), terms=tab, null=("theta",)), b"table is passed through theta"),
+        (plain, dict(null=("theta",), **ring), b"null theta"),
+        (fused, dict(null=("theta",), **ring), b"null buffer"),
+        (stale, dict(freq=0), b"frequency"),
+        (stale, dict(count0=-1), b"counter"),
+        (stale, dict(null=("code",)), b"list buffer"),
+        (stale, dict(prm=params(n_atoms=200), terms=tab), b"tabulated"),
+        (fused, dict(null=("rdf",), **ring), b"not available"),
+        (fused, dict(null=("raw",), **ring), b"null buffer"),
+        (fused, dict(rdf=fuse(stride=0), **ring), b"not available"),
+        (fused, dict(), b"not available"),               # (one replica: not where the ring kernels run)
+    ]
+    for names, kw, want in table:
+        for name in names:
+            rc, msg = call(name, **kw)
+            assert rc == -1 and want in msg, (name, kw, rc, msg)
+
+
 def test_host_side_of_the_row_chain_and_the_nh_half_step_scratch():
     """mdg_row_chain / mdg_nhv_scratch_floats without a GPU: struct layout, argument validation (every refusal happens before
     a launch), the empty call, and the size of the cross-workgroup scratch (partials of 1 024-element chunks, a ticket per

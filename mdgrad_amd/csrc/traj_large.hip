@@ -1959,12 +1959,12 @@ __global__ void large_adj_init(const float* __restrict__ g_v, const float* __res
 }
 
 struct WsLayout {
-    size_t q, v, vh, f, lv, lq, lvh, lqh, dq, qm, vm, wl, pv, ph, pvh, lp, lph, pvm, partA, partB, partN, gth, ghi, glo, flags,
+    size_t q, v, vh, f, lv, lq, lvh, lqh, dq, qm, vm, wl, pv, ph, pvh, lp, lph, pvm, partA, partB, partN, gth, ghi, flags,
         spos, bstart, binslot, nl_idx, nl_cnt, nl_bad, nl_build, nl_state, nl_perm, nl_bst, total;
     bool keep_lists;
 };
 
-WsLayout ws_layout(int R, int N, int nb, int KT, int T) {
+WsLayout ws_layout(int R, int N, int KT, int T) {
     WsLayout w{};
     size_t o = 0;
     auto take = [&](size_t n) { size_t r = o; o += (n + 63) / 64 * 64; return r; };
@@ -1972,12 +1972,12 @@ WsLayout ws_layout(int R, int N, int nb, int KT, int T) {
     w.q = take(s3); w.v = take(s3); w.vh = take(s3); w.f = take(s3);
     w.lv = take(s3); w.lq = take(s3); w.lvh = take(s3); w.lqh = take(s3); w.dq = take(s3); w.qm = take(s3); w.vm = take(s3); w.wl = take(s3);
     w.pv = take(sc); w.ph = take(sc); w.pvh = take(sc); w.lp = take(sc); w.lph = take(sc); w.pvm = take(sc);
+    const int nb = (N + LG_WAVES_CELL - 1) / LG_WAVES_CELL;            // partial rows: the larger of the two workgroup shapes
     const int nbmax = nb > (3 * N + 255) / 256 ? nb : (3 * N + 255) / 256;
     w.partA = take((size_t)R * nbmax); w.partB = take((size_t)R * nbmax);
     w.partN = take((size_t)R * nbmax * LG_NV);
     w.gth = take((size_t)R * (KT > 0 ? KT : 1));
     w.ghi = take((size_t)2 * R * (KT > 0 ? KT : 1));    // (int64 words of the table kind -- offsets are multiples of 256 B --; a few words otherwise)
-    w.glo = w.ghi;
     w.flags = take(16);
     w.spos = take((size_t)R * N * 4);
     w.bstart = take((size_t)R * (LG_MAX_CELLS + 1));
@@ -2038,6 +2038,48 @@ LgStreams* lg_streams() {
     return &P;
 }
 
+// The replica groups of one trajectory: how many, their streams (the caller's when there is one group), the fork before the
+// launch loops and the join after them.  Whoever leaves the scope between fork() and join() -- an error return included --
+// still joins: the caller's stream is ordered after everything queued on the side streams, which work on the same workspace.
+struct RepGroup { int r0, n; hipStream_t stream; };       // first replica, replicas, the stream of their launches
+class LgGroups {
+    const int R_;
+    const hipStream_t st_;
+    int G_ = 1;
+    LgStreams* LS_ = nullptr;
+    bool forked_ = false;                                   // side streams wait on the caller's and have not been joined yet
+    hipError_t join_streams() {                             // every side stream, also after one failed; the first error
+        hipError_t first = hipSuccess;
+        for (int g = 0; forked_ && g < G_; ++g) {
+            hipError_t e = hipEventRecord(LS_->join[g], LS_->s[g]);
+            if (e == hipSuccess) e = hipStreamWaitEvent(st_, LS_->join[g], 0);
+            if (first == hipSuccess) first = e;
+        }
+        forked_ = false;
+        return first;
+    }
+public:
+    LgGroups(int R, hipStream_t st) : R_(R), st_(st) {}
+    ~LgGroups() { (void)join_streams(); }                   // (an error on this path is not reported: the first one wins)
+    int fork() {
+        G_ = lg_group_count(R_, st_);
+        LS_ = G_ > 1 ? lg_streams() : nullptr;
+        if (!LS_) G_ = 1;
+        if (G_ > 1) {
+            MDG_HIP(hipEventRecord(LS_->fork, st_));
+            forked_ = true;
+            for (int g = 0; g < G_; ++g) MDG_HIP(hipStreamWaitEvent(LS_->s[g], LS_->fork, 0));
+        }
+        return MDG_OK;
+    }
+    int join() { MDG_HIP(join_streams()); return MDG_OK; }
+    int count() const { return G_; }
+    RepGroup group(int g) const {
+        const int r0 = (int)((long long)R_ * g / G_);
+        return {r0, (int)((long long)R_ * (g + 1) / G_) - r0, G_ > 1 ? LS_->s[g] : st_};
+    }
+};
+
 // MDG_LARGE_TILES=0: the listed launches gather by atom index from L2 (A/B measurements; the pre-round-5 kernels)
 bool large_tiles_enabled() {
     const char* e = getenv("MDG_LARGE_TILES");
@@ -2062,235 +2104,323 @@ int validate_large(const MdgTrajParams* p, const MdgCell* cell, const MdgTerms* 
     return MDG_OK;
 }
 
-}  // namespace
-
-extern "C" int64_t mdg_traj_large_workspace(int n_rep, int n_atoms, int n_frames, int n_theta_total) {
-    if (n_rep <= 0 || n_atoms <= 0 || n_frames <= 0) return -1;
-    const int nb = (n_atoms + LG_WAVES_CELL - 1) / LG_WAVES_CELL;       // (the larger of the two workgroup shapes)
-    return (int64_t)ws_layout(n_rep, n_atoms, nb, n_theta_total, n_frames).total;
-}
-
-extern "C" int mdg_traj_large_list_builds(const float* ws, int n_rep, int n_atoms, int n_frames, int n_theta_total,
-                                          int32_t* build_of_frame, void* stream) {
-    MDG_CHECK_ARG(ws && build_of_frame && n_rep > 0 && n_atoms > 0 && n_frames > 0, "traj_large_list_builds: bad arguments");
-    const WsLayout L = ws_layout(n_rep, n_atoms, (n_atoms + LG_WAVES_CELL - 1) / LG_WAVES_CELL, n_theta_total, n_frames);
-    if (!L.keep_lists) return 1;
-    MDG_HIP(hipMemcpyAsync(build_of_frame, ws + L.nl_build, sizeof(int32_t) * (size_t)n_rep * n_frames,
-                           hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return MDG_OK;
-}
-
-// (phases that bin need the replica in ONE workgroup; the adjoint over stored lists does not: one atom per thread)
-#define LG_PREP_LAUNCH(PH_)                                                                          \
-    do {                                                                                             \
-        if ((PH_) >= 2 && a.nl_idx)                                                                  \
-            hipLaunchKernelGGL((large_prep<PH_, 1>), dim3((N + LG_PREP_SMALL - 1) / LG_PREP_SMALL, Rg), dim3(LG_PREP_SMALL), 0, sg, a); \
-        else if (N <= 4 * LG_PREP) hipLaunchKernelGGL((large_prep<PH_, 4>), dim3(1, Rg), dim3(LG_PREP), 0, sg, a); \
-        else if (N <= LG_PREP_ATOMS * LG_PREP) hipLaunchKernelGGL((large_prep<PH_, LG_PREP_ATOMS>), dim3(1, Rg), dim3(LG_PREP), 0, sg, a); \
-        else hipLaunchKernelGGL((large_prep<PH_, LG_PREP_ATOMS_MAX>), dim3(1, Rg), dim3(LG_PREP), 0, sg, a); \
-    } while (0)
-
-// the replica groups of a trajectory: G, their streams (the caller's when G == 1), fork / join around the launch loops
-#define LG_GROUPS_BEGIN()                                                                            \
-    int G = lg_group_count(R, st);                                                                   \
-    LgStreams* LS = G > 1 ? lg_streams() : nullptr;                                                  \
-    if (!LS) G = 1;                                                                                  \
-    if (G > 1) {                                                                                     \
-        MDG_HIP(hipEventRecord(LS->fork, st));                                                       \
-        for (int g = 0; g < G; ++g) MDG_HIP(hipStreamWaitEvent(LS->s[g], LS->fork, 0));              \
-    }                                                                                                \
-    (void)0
-#define LG_GROUP(g_)                                                                                 \
-    const int r0_ = (int)((long long)R * (g_) / G), Rg = (int)((long long)R * ((g_) + 1) / G) - r0_; \
-    hipStream_t sg = G > 1 ? LS->s[g_] : st;                                                         \
-    a.rep0 = r0_;                                                                                    \
-    (void)0
-#define LG_GROUPS_END()                                                                              \
-    if (G > 1) {                                                                                     \
-        for (int g = 0; g < G; ++g) {                                                                \
-            MDG_HIP(hipEventRecord(LS->join[g], LS->s[g]));                                          \
-            MDG_HIP(hipStreamWaitEvent(st, LS->join[g], 0));                                         \
-        }                                                                                            \
-    }                                                                                                \
-    a.rep0 = 0;                                                                                      \
-    (void)0
-
-#define LG_SETUP()                                                                                   \
-    const int R = prm->n_rep, N = prm->n_atoms;                                                      \
-    const int nbE = 1;              /* the element-wise work of a replica runs in one workgroup (large_prep) */ \
-    const WsLayout L = ws_layout(R, N, (N + LG_WAVES_CELL - 1) / LG_WAVES_CELL, terms->n_theta_total, prm->n_frames); \
-    LargeArgs a{};                                                                                   \
-    a.prm = *prm; a.cell = *cell; a.terms = *terms; a.theta = theta; a.mass = mass; a.t = t_grid;   \
-    a.q = ws + L.q; a.v = ws + L.v; a.vh = ws + L.vh; a.f = ws + L.f;                                \
-    a.lv = ws + L.lv; a.lq = ws + L.lq; a.lvh = ws + L.lvh; a.lqh = ws + L.lqh; a.dq = ws + L.dq;    \
-    a.qm = ws + L.qm; a.vm = ws + L.vm; a.wl = ws + L.wl;                                            \
-    a.pv = ws + L.pv; a.ph = ws + L.ph; a.pvh = ws + L.pvh; a.lp = ws + L.lp; a.lph = ws + L.lph;    \
-    a.pvm = ws + L.pvm; a.partA = ws + L.partA; a.partB = ws + L.partB; a.partN = ws + L.partN;      \
-    a.gth = ws + L.gth; a.flags = flags; a.nbE = nbE;                                                \
-    const bool table = terms->t[0].kind == MDG_PAIR_TABLE;                                           \
-    a.g64 = table ? reinterpret_cast<unsigned long long*>(ws + L.ghi) : nullptr;                     \
-    a.glim = fx64_limit((double)(prm->n_frames > 1 ? prm->n_frames - 1 : 1) * (double)prm->n_atoms * (double)LG_CAP); \
-    hipStream_t st = (hipStream_t)stream;                                                            \
-    const bool diag = cell->diag != 0;                                                               \
-    a.spos = reinterpret_cast<float4*>(ws + L.spos);                                                 \
-    a.bstart = reinterpret_cast<int32_t*>(ws + L.bstart);                                            \
-    a.binslot = reinterpret_cast<int32_t*>(ws + L.binslot);                                          \
-    a.ncell = 0;                                                                                     \
-    if (L.keep_lists && prm->block != -1) {          /* (block = -1: search at every evaluation) */       \
-        a.nl_idx = reinterpret_cast<uint16_t*>(ws + L.nl_idx); a.nl_cnt = reinterpret_cast<int32_t*>(ws + L.nl_cnt); \
-        a.nl_bad = reinterpret_cast<int32_t*>(ws + L.nl_bad);                                        \
-        a.nl_build = reinterpret_cast<int32_t*>(ws + L.nl_build);                                    \
-        a.nl_state = reinterpret_cast<int32_t*>(ws + L.nl_state);                                    \
-        float rcm = 0.f;                                                                             \
-        for (int m = 0; m < terms->n_terms; ++m) rcm = terms->t[m].cutoff > rcm ? terms->t[m].cutoff : rcm; \
-        a.skin = LG_SKIN * rcm;                                                                      \
-    }                                                                                                \
-    if (diag) {                                                                                      \
-        float rcmax = 0.f;                                                                           \
-        for (int m = 0; m < terms->n_terms; ++m) rcmax = terms->t[m].cutoff > rcmax ? terms->t[m].cutoff : rcmax; \
-        int nbx[3];                                                                                  \
-        bool ok = rcmax > 0.f;                                                                       \
-        for (int d = 0; d < 3 && ok; ++d) { nbx[d] = (int)floorf(cell->h[4 * d] / (rcmax + a.skin)); ok = nbx[d] >= 3; } \
-        if (ok && (long long)nbx[0] * nbx[1] * nbx[2] <= LG_MAX_CELLS) {                             \
-            a.nb[0] = nbx[0]; a.nb[1] = nbx[1]; a.nb[2] = nbx[2]; a.ncell = nbx[0] * nbx[1] * nbx[2]; \
-        }                                                                                            \
-    }                                                                                                \
-    if (a.ncell && a.nl_idx) {                                                                       \
-        /* column tiles: staged capacity = 1.35 x the nine columns of a uniform box (+ slack); a box whose tiles cannot */ \
-        /* be staged keeps the L2-gather launches */                                                 \
-        a.ncol = a.nb[0] * a.nb[1];                                                                  \
-        long long cap = (long long)(9.0 * 1.35 * N / (double)a.ncol) + 64;                           \
-        if (cap > N) cap = N;                                                                        \
-        cap = (cap + 63) / 64 * 64;                                                                  \
-        if (large_tiles_enabled() && cap <= LG_TILE_MAX && a.ncol <= LG_MAX_COLS && a.ncol <= (N + LG_WAVES_CELL - 1) / LG_WAVES_CELL) { \
-            a.tile_cap = (int)cap;                                                                   \
-            a.nl_perm = reinterpret_cast<int32_t*>(ws + L.nl_perm);                                  \
-            a.nl_bst = reinterpret_cast<int32_t*>(ws + L.nl_bst);                                    \
-        }          /* (otherwise the rows hold atom indices and the listed launches gather from L2, as in unbinned boxes) */ \
-    }                                                                                                \
-    const int wpb = a.ncell ? LG_WAVES_CELL : LG_WAVES;                                              \
-    const int nbF = (N + wpb - 1) / wpb;                                                             \
-    a.nbF = nbF;                                                                                     \
-    const dim3 gL((N + LG_ROW_ATOMS - 1) / LG_ROW_ATOMS, R);       /* the listed kernels: 16 atoms per workgroup */ \
-    a.nbL = (int)gL.x > a.ncol || !a.tile_cap ? (int)gL.x : a.ncol;   /* partA rows of the listed / searching launches */ \
-    const size_t tile_lds = sizeof(float4) * (size_t)wpb * LG_CAP + (a.ncell ? 0 : sizeof(float) * 3 * LG_TILE); \
-    const bool lj126 = terms->n_terms == 1 && diag && !terms->t[0].mask && terms->t[0].kind == MDG_PAIR_LJ && \
-                       terms->t[0].p == 12 && (terms->t[0].q == 6 || terms->t[0].c == 0.f);          \
-    (void)0;
-
 // stale lists (topology_update_freq > 1): frequency, the integrator's call count at the launch's first call, the persistent rows
 struct StaleOpt { int freq; long long count0; uint32_t* rows; };
-static inline bool stale_due(const StaleOpt* so, long long e) { return (so->count0 + e) % (long long)so->freq == 0; }
-static int validate_stale(const MdgTrajParams* prm, const MdgTerms* terms, const StaleOpt* so) {
+inline bool stale_due(const StaleOpt* so, long long e) { return (so->count0 + e) % (long long)so->freq == 0; }
+int validate_stale(const MdgTrajParams* prm, const MdgTerms* terms, const StaleOpt* so) {
     MDG_CHECK_ARG(so->freq >= 1 && so->count0 >= 0 && so->rows, "traj_large_stale: bad frequency / counter / list buffer");
     MDG_CHECK_ARG(prm->n_atoms <= 32768, "traj_large_stale: at most 32 768 atoms (15-bit row entries)");
     for (int m = 0; m < terms->n_terms; ++m)
         MDG_CHECK_ARG(terms->t[m].kind != MDG_PAIR_TABLE, "traj_large_stale: a tabulated pair model is not supported");
     return MDG_OK;
 }
-#define LG_STALE_SETUP()                                                                             \
-    if (so) {                                                                                        \
-        a.st_row = so->rows;                                                                         \
-        a.st_cnt = reinterpret_cast<int32_t*>(so->rows + (size_t)R * N * LG_CAP);                    \
-    }                                                                                                \
-    (void)0
 
-static int traj_fwd_large_run(const MdgTrajParams* prm, const MdgCell* cell, const MdgTerms* terms,
-                              const float* theta, const float* mass, const float* t_grid,
-                              const float* v0, const float* q0, const float* pv0,
-                              float* v_t, float* q_t, float* pv_t, float* ws, int32_t* flags, void* stream,
-                              const StaleOpt* so) {
-    int rc = validate_large(prm, cell, terms);
-    if (rc) return rc;
+// THE LAUNCH PLAN of one trajectory in one direction: the route (lists kept or not, binned or not, column tiles or L2 gathers,
+// the kernel variant) is decided here, once; traj_{fwd,adj}_large_run only sequence the launch functions below over it.
+struct LargePlan {
+    LargeArgs a;                 // the kernel argument: the run loops set step / st_bin, the launch functions rep0 / st_rebuild
+    int R, N;
+    hipStream_t st;              // the caller's stream
+    bool diag, lj126, table;     // orthorhombic cell; one unmasked LJ 12-6 term in such a cell (kernels of its own); tabulated model
+    int wpb, grid_search;        // the searching launches (large_force_step / large_adj_force): waves per workgroup, workgroups per replica
+    size_t tile_lds;             // ... their dynamic LDS
+    int grid_rows;               // workgroups per replica of large_search_rows: 16 atoms each
+    int grid_listed;             // ... of this direction's L2-gather launch over the stored rows (large_fwd_listed / large_adj_listed)
+};
+enum class Direction { forward, adjoint };
+
+int large_plan(LargePlan& p, Direction dir, const MdgTrajParams* prm, const MdgCell* cell, const MdgTerms* terms,
+               const float* theta, const float* mass, const float* t_grid, float* ws, int32_t* flags, void* stream,
+               const StaleOpt* so) {
+    if (so)
+        if (const int rc = validate_stale(prm, terms, so)) return rc;
+    p = LargePlan{};
+    LargeArgs& a = p.a;
+    const int R = p.R = prm->n_rep, N = p.N = prm->n_atoms;
+    const WsLayout L = ws_layout(R, N, terms->n_theta_total, prm->n_frames);
+    a.prm = *prm; a.cell = *cell; a.terms = *terms; a.theta = theta; a.mass = mass; a.t = t_grid;
+    a.q = ws + L.q; a.v = ws + L.v; a.vh = ws + L.vh; a.f = ws + L.f; a.qm = ws + L.qm; a.vm = ws + L.vm; a.wl = ws + L.wl;
+    a.lv = ws + L.lv; a.lq = ws + L.lq; a.lvh = ws + L.lvh; a.lqh = ws + L.lqh; a.dq = ws + L.dq;
+    a.pv = ws + L.pv; a.ph = ws + L.ph; a.pvh = ws + L.pvh; a.lp = ws + L.lp; a.lph = ws + L.lph;
+    a.pvm = ws + L.pvm; a.partA = ws + L.partA; a.partB = ws + L.partB; a.partN = ws + L.partN;
+    a.gth = ws + L.gth; a.flags = flags; a.nbE = 1;     // (nbE: the element-wise work of a replica runs in one workgroup, large_prep)
+    p.table = terms->t[0].kind == MDG_PAIR_TABLE;
+    a.g64 = p.table ? reinterpret_cast<unsigned long long*>(ws + L.ghi) : nullptr;
+    a.glim = fx64_limit((double)(prm->n_frames > 1 ? prm->n_frames - 1 : 1) * (double)prm->n_atoms * (double)LG_CAP);
+    p.st = (hipStream_t)stream;
+    p.diag = cell->diag != 0;
+    a.spos = reinterpret_cast<float4*>(ws + L.spos);
+    a.bstart = reinterpret_cast<int32_t*>(ws + L.bstart); a.binslot = reinterpret_cast<int32_t*>(ws + L.binslot);
+    if (so) {                       // stale lists: no candidate lists of the Verlet-reuse kind -- block = -1 --, the persistent rows
+        a.prm.block = -1;
+        a.st_row = so->rows;
+        a.st_cnt = reinterpret_cast<int32_t*>(so->rows + (size_t)R * N * LG_CAP);
+    }
+    float rcmax = 0.f;
+    for (int m = 0; m < terms->n_terms; ++m) rcmax = terms->t[m].cutoff > rcmax ? terms->t[m].cutoff : rcmax;
+    if (L.keep_lists && a.prm.block != -1) {          // (block = -1: search at every evaluation)
+        a.nl_idx = reinterpret_cast<uint16_t*>(ws + L.nl_idx); a.nl_cnt = reinterpret_cast<int32_t*>(ws + L.nl_cnt);
+        a.nl_bad = reinterpret_cast<int32_t*>(ws + L.nl_bad); a.nl_build = reinterpret_cast<int32_t*>(ws + L.nl_build);
+        a.nl_state = reinterpret_cast<int32_t*>(ws + L.nl_state);
+        a.skin = LG_SKIN * rcmax;
+    }
+    if (p.diag) {
+        int nbx[3];
+        bool ok = rcmax > 0.f;
+        for (int d = 0; d < 3 && ok; ++d) { nbx[d] = (int)floorf(cell->h[4 * d] / (rcmax + a.skin)); ok = nbx[d] >= 3; }
+        if (ok && (long long)nbx[0] * nbx[1] * nbx[2] <= LG_MAX_CELLS) {
+            a.nb[0] = nbx[0]; a.nb[1] = nbx[1]; a.nb[2] = nbx[2]; a.ncell = nbx[0] * nbx[1] * nbx[2];
+        }
+    }
+    if (a.ncell && a.nl_idx) {
+        // column tiles: staged capacity = 1.35 x the nine columns of a uniform box (+ slack); a box whose tiles cannot
+        // be staged keeps the L2-gather launches
+        a.ncol = a.nb[0] * a.nb[1];
+        long long cap = (long long)(9.0 * 1.35 * N / (double)a.ncol) + 64;
+        if (cap > N) cap = N;
+        cap = (cap + 63) / 64 * 64;
+        if (large_tiles_enabled() && cap <= LG_TILE_MAX && a.ncol <= LG_MAX_COLS && a.ncol <= (N + LG_WAVES_CELL - 1) / LG_WAVES_CELL) {
+            a.tile_cap = (int)cap;
+            a.nl_perm = reinterpret_cast<int32_t*>(ws + L.nl_perm);
+            a.nl_bst = reinterpret_cast<int32_t*>(ws + L.nl_bst);
+        }          // (otherwise the rows hold atom indices and the listed launches gather from L2, as in unbinned boxes)
+    }
+    p.wpb = a.ncell ? LG_WAVES_CELL : LG_WAVES;
+    p.grid_search = (N + p.wpb - 1) / p.wpb;
+    p.grid_rows = (N + LG_ROW_ATOMS - 1) / LG_ROW_ATOMS;              // the listed kernels: 16 atoms per workgroup
+    const int groups = dir == Direction::adjoint ? LG_ADJ_GROUPS : LG_FWD_GROUPS;
+    p.grid_listed = (N + LG_ROW_ATOMS * groups - 1) / (LG_ROW_ATOMS * groups);
+    // rows of partN this direction's force launches write and its prep launches sum: the forward launches all write
+    // grid_search rows, the adjoint over stored lists one per bin column or per workgroup of large_adj_listed
+    a.nbF = dir == Direction::adjoint && a.nl_idx ? (a.tile_cap ? a.ncol : p.grid_listed) : p.grid_search;
+    a.nbL = p.grid_rows > a.ncol || !a.tile_cap ? p.grid_rows : a.ncol;   // partA rows of the listed / searching launches
+    p.tile_lds = sizeof(float4) * (size_t)p.wpb * LG_CAP + (a.ncell ? 0 : sizeof(float) * 3 * LG_TILE);
+    p.lj126 = terms->n_terms == 1 && p.diag && !terms->t[0].mask && terms->t[0].kind == MDG_PAIR_LJ &&
+              terms->t[0].p == 12 && (terms->t[0].q == 6 || terms->t[0].c == 0.f);
+    return MDG_OK;
+}
+
+// one launch for the replicas of a group, on the group's stream
+template <class Kernel, class... Extra>
+void launch_group(Kernel kernel, LargePlan& p, const RepGroup& g, dim3 grid, dim3 block, size_t lds, Extra... extra) {
+    p.a.rep0 = g.r0;
+    hipLaunchKernelGGL(kernel, grid, block, lds, g.stream, p.a, extra...);
+}
+
+// The kernel variant of a plan, chosen in this one place: f(Variant<DIAG, KIND>{}) names the kernel of its launch family
+// (the stale-row kernels exist in the generic kind only; families without a DIAG parameter read KIND alone).
+template <bool DIAG_, int KIND_> struct Variant { static constexpr bool DIAG = DIAG_; static constexpr int KIND = KIND_; };
+template <bool GENERIC_ONLY = false, class F>
+void with_variant(const LargePlan& p, F f) {
+    if constexpr (!GENERIC_ONLY) { if (p.lj126) return f(Variant<true, KIND_LJ126>{}); }
+    return p.diag ? f(Variant<true, -1>{}) : f(Variant<false, -1>{});
+}
+
+// (phases that bin need the replica in ONE workgroup; the adjoint over stored lists does not: one atom per thread)
+template <int PH>
+void launch_prep(LargePlan& p, const RepGroup& g) {
+    const int N = p.N;
+    if (PH >= 2 && p.a.nl_idx) launch_group(large_prep<PH, 1>, p, g, dim3((N + LG_PREP_SMALL - 1) / LG_PREP_SMALL, g.n), dim3(LG_PREP_SMALL), 0);
+    else if (N <= 4 * LG_PREP) launch_group(large_prep<PH, 4>, p, g, dim3(1, g.n), dim3(LG_PREP), 0);
+    else if (N <= LG_PREP_ATOMS * LG_PREP) launch_group(large_prep<PH, LG_PREP_ATOMS>, p, g, dim3(1, g.n), dim3(LG_PREP), 0);
+    else launch_group(large_prep<PH, LG_PREP_ATOMS_MAX>, p, g, dim3(1, g.n), dim3(LG_PREP), 0);
+}
+
+// the force launch of a forward call that may search: binned box with lists kept -- the row-based search (one sweep) --, else
+// search + evaluate in one kernel
+template <int MODE>
+void launch_force_step(LargePlan& p, const RepGroup& g) {
+    with_variant(p, [&](auto v) {
+        using V = decltype(v);
+        if (p.a.nl_idx && p.a.ncell) launch_group(large_search_rows<MODE, V::KIND>, p, g, dim3(p.grid_rows, g.n), dim3(256), 0);
+        else launch_group(large_force_step<V::DIAG, MODE, V::KIND>, p, g, dim3(p.grid_search, g.n), dim3(64 * p.wpb), p.tile_lds);
+    });
+}
+
+// ... over the stored candidates of the current list (returns at once when the step searched): column tiles, else L2 gathers
+void launch_fwd_listed(LargePlan& p, const RepGroup& g) {
+    with_variant(p, [&](auto v) {
+        using V = decltype(v);
+        if (p.a.tile_cap)
+            launch_group(large_fwd_tiled<V::KIND>, p, g, dim3(g.n, p.a.ncol), dim3(LG_TILE_THREADS), sizeof(float) * 4 * (size_t)p.a.tile_cap);
+        else if (p.a.nl_idx) launch_group(large_fwd_listed<V::DIAG, V::KIND>, p, g, dim3(p.grid_listed, g.n), dim3(256), 0);
+    });
+}
+
+// ... with stale rows: rebuild them at this call, or evaluate the stored ones
+template <int MODE>
+void launch_stale_step(LargePlan& p, const RepGroup& g, bool rebuild) {
+    p.a.st_rebuild = rebuild ? 1 : 0;
+    with_variant<true>(p, [&](auto v) {
+        launch_group(large_force_step<decltype(v)::DIAG, MODE, -1, true>, p, g, dim3(p.grid_search, g.n), dim3(64 * p.wpb), p.tile_lds);
+    });
+}
+
+// one of the two evaluations (force + Hessian.w + parameter vjp) of an adjoint interval: over column tiles, over stored rows
+// from L2, or with a search of its own
+void launch_adj_force(LargePlan& p, const RepGroup& g, int second) {
+    with_variant(p, [&](auto v) {
+        using V = decltype(v);
+        if (p.a.tile_cap)
+            launch_group(large_adj_tiled<V::KIND>, p, g, dim3(g.n, p.a.ncol), dim3(LG_TILE_THREADS), sizeof(float) * 7 * (size_t)p.a.tile_cap, second);
+        else if (p.a.nl_idx) launch_group(large_adj_listed<V::DIAG, V::KIND>, p, g, dim3(p.grid_listed, g.n), dim3(256), 0, second);
+        else launch_group(large_adj_force<V::DIAG, V::KIND>, p, g, dim3(p.grid_search, g.n), dim3(64 * p.wpb), p.tile_lds, second);
+    });
+}
+
+void launch_stale_adj(LargePlan& p, const RepGroup& g, int second, bool rebuild) {
+    p.a.st_rebuild = rebuild ? 1 : 0;
+    with_variant<true>(p, [&](auto v) {
+        launch_group(large_adj_force<decltype(v)::DIAG, -1, true>, p, g, dim3(p.grid_search, g.n), dim3(64 * p.wpb), p.tile_lds, second);
+    });
+}
+
+int traj_fwd_large_run(const MdgTrajParams* prm, const MdgCell* cell, const MdgTerms* terms,
+                       const float* theta, const float* mass, const float* t_grid, const float* v0, const float* q0, const float* pv0,
+                       float* v_t, float* q_t, float* pv_t, float* ws, int32_t* flags, void* stream, const StaleOpt* so) {
+    if (const int rc = validate_large(prm, cell, terms)) return rc;
     MDG_CHECK_ARG(mass && t_grid && v0 && q0 && v_t && q_t && ws && flags, "traj_fwd_large: null buffer");
     MDG_CHECK_ARG(prm->ensemble == 1 || (pv0 && pv_t), "traj_fwd_large: NHC needs pv0/pv_t");
-    MdgTrajParams pstale;
-    if (so) {                                   // (stale lists: no candidate lists of the Verlet-reuse kind -- block = -1)
-        rc = validate_stale(prm, terms, so);
-        if (rc) return rc;
-        pstale = *prm; pstale.block = -1; prm = &pstale;
-    }
-    LG_SETUP();
-    LG_STALE_SETUP();
+    LargePlan p;
+    if (const int rc = large_plan(p, Direction::forward, prm, cell, terms, theta, mass, t_grid, ws, flags, stream, so)) return rc;
+    LargeArgs& a = p.a;
     a.v_t = v_t; a.q_t = q_t; a.pv_t = pv_t;
-    const int C = prm->n_chains, T = prm->n_frames;
-    MDG_HIP(hipMemcpyAsync(a.q, q0, sizeof(float) * (size_t)R * N * 3, hipMemcpyDeviceToDevice, st));
-    MDG_HIP(hipMemcpyAsync(a.v, v0, sizeof(float) * (size_t)R * N * 3, hipMemcpyDeviceToDevice, st));
+    const int R = p.R, N = p.N, C = prm->n_chains, T = prm->n_frames;
+    MDG_HIP(hipMemcpyAsync(a.q, q0, sizeof(float) * (size_t)R * N * 3, hipMemcpyDeviceToDevice, p.st));
+    MDG_HIP(hipMemcpyAsync(a.v, v0, sizeof(float) * (size_t)R * N * 3, hipMemcpyDeviceToDevice, p.st));
     if (prm->ensemble == 0)
         MDG_HIP(hipMemcpy2DAsync(a.pv, sizeof(float) * MDG_MAX_CHAINS, pv0, sizeof(float) * C, sizeof(float) * C, R,
-                                 hipMemcpyDeviceToDevice, st));
+                                 hipMemcpyDeviceToDevice, p.st));
     a.step = 0;
-    if (a.nl_idx) MDG_HIP(hipMemsetAsync(a.nl_bad, 0, sizeof(int32_t) * (size_t)R * T, st));
-#define LG_FORCE_STEP(MODE_)                                                                                    \
-    do {                                                                                                        \
-        const dim3 gF(nbF, Rg), gLg(gL.x, Rg);                                                                  \
-        if (a.nl_idx && a.ncell) {         /* binned box, lists kept: the row-based search (one sweep) */      \
-            if (lj126) hipLaunchKernelGGL((large_search_rows<MODE_, KIND_LJ126>), gLg, dim3(256), 0, sg, a);  \
-            else hipLaunchKernelGGL((large_search_rows<MODE_, -1>), gLg, dim3(256), 0, sg, a);                 \
-        } else                                                                                                  \
-        if (lj126) hipLaunchKernelGGL((large_force_step<true, MODE_, KIND_LJ126>), gF, dim3(64 * wpb), tile_lds, sg, a); \
-        else if (diag) hipLaunchKernelGGL((large_force_step<true, MODE_, -1>), gF, dim3(64 * wpb), tile_lds, sg, a);    \
-        else hipLaunchKernelGGL((large_force_step<false, MODE_, -1>), gF, dim3(64 * wpb), tile_lds, sg, a);            \
-    } while (0)
-    // stale lists: the first right-hand-side call of step k has the running index 2 k, the second 2 k + 1 (sovlers.py:110-127);
-    // calls 2 k + 1 and 2 k + 2 share their positions, so the force of the former serves the latter unless that one rebuilds
-#define LG_STALE_STEP(MODE_, REBUILD_)                                                                          \
-    do {                                                                                                        \
-        const dim3 gF(nbF, Rg);                                                                                 \
-        a.st_rebuild = (REBUILD_) ? 1 : 0;                                                                      \
-        if (diag) hipLaunchKernelGGL((large_force_step<true, MODE_, -1, true>), gF, dim3(64 * wpb), tile_lds, sg, a);  \
-        else hipLaunchKernelGGL((large_force_step<false, MODE_, -1, true>), gF, dim3(64 * wpb), tile_lds, sg, a);      \
-    } while (0)
-    LG_GROUPS_BEGIN();
+    if (a.nl_idx) MDG_HIP(hipMemsetAsync(a.nl_bad, 0, sizeof(int32_t) * (size_t)R * T, p.st));
+    LgGroups groups(R, p.st);
+    if (const int rc = groups.fork()) return rc;
+    const int G = groups.count();
     if (so) {
+        // stale lists: the first right-hand-side call of step k has the running index 2 k, the second 2 k + 1 (sovlers.py:110-127);
+        // calls 2 k + 1 and 2 k + 2 share their positions, so the force of the former serves the latter unless that one rebuilds
         for (int g = 0; g < G; ++g) {
-            LG_GROUP(g);
+            const RepGroup grp = groups.group(g);
             a.st_bin = stale_due(so, 0);
-            if (a.ncell && a.st_bin) LG_PREP_LAUNCH(0);
-            LG_STALE_STEP(0, stale_due(so, 0));
+            if (a.ncell && a.st_bin) launch_prep<0>(p, grp);
+            launch_stale_step<0>(p, grp, stale_due(so, 0));
         }
         for (int k = 0; k + 1 < T; ++k) {
             a.step = k;
             const bool again = k + 2 < T && stale_due(so, 2ll * k + 2) && !stale_due(so, 2ll * k + 1);
             for (int g = 0; g < G; ++g) {
-                LG_GROUP(g);
+                const RepGroup grp = groups.group(g);
                 a.st_bin = stale_due(so, 2ll * k + 1) || again;     // (the bins serve both calls at these positions)
-                LG_PREP_LAUNCH(1);
-                LG_STALE_STEP(1, stale_due(so, 2ll * k + 1));
-                if (again) LG_STALE_STEP(2, true);
+                launch_prep<1>(p, grp);
+                launch_stale_step<1>(p, grp, stale_due(so, 2ll * k + 1));
+                if (again) launch_stale_step<2>(p, grp, true);
             }
         }
     } else {
-    for (int g = 0; g < G; ++g) {
-        LG_GROUP(g);
-        if (a.ncell) LG_PREP_LAUNCH(0);
-        LG_FORCE_STEP(0);
-    }
-    for (int k = 0; k + 1 < T; ++k) {
-        a.step = k;
         for (int g = 0; g < G; ++g) {
-            LG_GROUP(g);
-            LG_PREP_LAUNCH(1);                                  // kick + drift + bath half step; search needed? then binning
-            LG_FORCE_STEP(1);                                   // (returns at once while the current list serves)
-            if (a.tile_cap) {                                   // (returns at once when the step searched)
-                const dim3 gT(Rg, a.ncol);
-                const size_t lds = sizeof(float) * 4 * (size_t)a.tile_cap;
-                if (lj126) hipLaunchKernelGGL((large_fwd_tiled<KIND_LJ126>), gT, dim3(LG_TILE_THREADS), lds, sg, a);
-                else hipLaunchKernelGGL((large_fwd_tiled<-1>), gT, dim3(LG_TILE_THREADS), lds, sg, a);
-            } else if (a.nl_idx) {
-                const dim3 gLF((N + LG_ROW_ATOMS * LG_FWD_GROUPS - 1) / (LG_ROW_ATOMS * LG_FWD_GROUPS), Rg);
-                if (lj126) hipLaunchKernelGGL((large_fwd_listed<true, KIND_LJ126>), gLF, dim3(256), 0, sg, a);
-                else if (diag) hipLaunchKernelGGL((large_fwd_listed<true, -1>), gLF, dim3(256), 0, sg, a);
-                else hipLaunchKernelGGL((large_fwd_listed<false, -1>), gLF, dim3(256), 0, sg, a);
+            const RepGroup grp = groups.group(g);
+            if (a.ncell) launch_prep<0>(p, grp);
+            launch_force_step<0>(p, grp);
+        }
+        for (int k = 0; k + 1 < T; ++k) {
+            a.step = k;
+            for (int g = 0; g < G; ++g) {
+                const RepGroup grp = groups.group(g);
+                launch_prep<1>(p, grp);                             // kick + drift + bath half step; search needed? then binning
+                launch_force_step<1>(p, grp);                       // (returns at once while the current list serves)
+                launch_fwd_listed(p, grp);                          // (returns at once when the step searched)
             }
         }
     }
-    }
-    LG_GROUPS_END();
-#undef LG_FORCE_STEP
-#undef LG_STALE_STEP
+    if (const int rc = groups.join()) return rc;
+    a.rep0 = 0;
     MDG_CHECK_LAUNCH("traj_fwd_large");
     return MDG_OK;
+}
+
+int traj_adj_large_run(const MdgTrajParams* prm, const MdgCell* cell, const MdgTerms* terms,
+                       const float* theta, const float* mass, const float* t_grid, const float* v_t, const float* q_t, const float* pv_t,
+                       const float* g_v, const float* g_q, const float* g_pv,
+                       float* adj_v0, float* adj_q0, float* adj_pv0, float* adj_theta,
+                       float* ws, int32_t* flags, void* stream, const StaleOpt* so) {
+    if (const int rc = validate_large(prm, cell, terms)) return rc;
+    MDG_CHECK_ARG(mass && t_grid && v_t && q_t && adj_v0 && adj_q0 && ws && flags, "traj_adj_large: null buffer");
+    MDG_CHECK_ARG(prm->ensemble == 1 || (pv_t && adj_pv0), "traj_adj_large: NHC needs pv_t/adj_pv0");
+    LargePlan p;
+    if (const int rc = large_plan(p, Direction::adjoint, prm, cell, terms, theta, mass, t_grid, ws, flags, stream, so)) return rc;
+    LargeArgs& a = p.a;
+    a.v_t = const_cast<float*>(v_t); a.q_t = const_cast<float*>(q_t); a.pv_t = const_cast<float*>(pv_t);
+    a.g_v = g_v; a.g_q = g_q; a.g_pv = g_pv;
+    const int R = p.R, N = p.N, C = prm->n_chains, T = prm->n_frames, KT = terms->n_theta_total;
+    // lam = dL/dy_{T-1}: ONE launch for all replicas (three copies per replica in a host loop were 192 serialised 3-5 us copies
+    // per 64-replica adjoint: 0.5-1 ms of a 20 ms pass)
+    hipLaunchKernelGGL(large_adj_init, dim3((3 * N + 255) / 256, R), dim3(256), 0, p.st, g_v, g_q, g_pv, N, T, C, a.lv, a.lq, a.lp);
+    MDG_HIP(hipMemsetAsync(a.gth, 0, sizeof(float) * (size_t)R * (KT > 0 ? KT : 1), p.st));
+    if (p.table) MDG_HIP(hipMemsetAsync(a.g64, 0, sizeof(unsigned long long) * (size_t)R * KT, p.st));
+    LgGroups groups(R, p.st);
+    if (const int rc = groups.fork()) return rc;
+    const int G = groups.count();
+    for (int i = T - 1; i >= 1; --i) {
+        a.step = i;
+        for (int g = 0; g < G; ++g) {
+            const RepGroup grp = groups.group(g);
+            if (so) {
+                // an interval makes three calls (sovlers.py:258-266): the dL/dt evaluation at y_i (its result is not used,
+                // but it advances the counter and may rebuild), the first augmented evaluation at the same positions, the
+                // midpoint evaluation -- running counts c0, c0 + 1, c0 + 2
+                const long long c0 = 3ll * (T - 1 - i);
+                a.st_bin = stale_due(so, c0) || stale_due(so, c0 + 1);
+                launch_prep<2>(p, grp);
+                launch_stale_adj(p, grp, 0, stale_due(so, c0) || stale_due(so, c0 + 1));
+                a.st_bin = stale_due(so, c0 + 2);
+                launch_prep<3>(p, grp);
+                launch_stale_adj(p, grp, 1, stale_due(so, c0 + 2));
+            } else {
+                launch_prep<2>(p, grp);                                             // finish interval i + 1, bin frame i
+                launch_adj_force(p, grp, 0);
+                launch_prep<3>(p, grp);                                             // midpoint state, bin it
+                launch_adj_force(p, grp, 1);
+            }
+        }
+    }
+    a.step = 0;
+    for (int g = 0; g < G; ++g) launch_prep<4>(p, groups.group(g));                 // finish interval 1
+    if (const int rc = groups.join()) return rc;
+    a.rep0 = 0;
+    MDG_HIP(hipMemcpyAsync(adj_v0, a.lv, sizeof(float) * (size_t)R * N * 3, hipMemcpyDeviceToDevice, p.st));
+    MDG_HIP(hipMemcpyAsync(adj_q0, a.lq, sizeof(float) * (size_t)R * N * 3, hipMemcpyDeviceToDevice, p.st));
+    if (prm->ensemble == 0)
+        MDG_HIP(hipMemcpy2DAsync(adj_pv0, sizeof(float) * C, a.lp, sizeof(float) * MDG_MAX_CHAINS, sizeof(float) * C, R,
+                                 hipMemcpyDeviceToDevice, p.st));
+    if (adj_theta && p.table) {
+        const size_t n = (size_t)R * KT;
+        hipLaunchKernelGGL(large_table_grad, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, p.st, a.g64, n, terms->t[0].c, adj_theta);
+    } else if (adj_theta && KT > 0)
+        MDG_HIP(hipMemcpyAsync(adj_theta, a.gth, sizeof(float) * (size_t)R * KT, hipMemcpyDeviceToDevice, p.st));
+    MDG_CHECK_LAUNCH("traj_adj_large");
+    return MDG_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t mdg_traj_large_workspace(int n_rep, int n_atoms, int n_frames, int n_theta_total) {
+    if (n_rep <= 0 || n_atoms <= 0 || n_frames <= 0) return -1;
+    return (int64_t)ws_layout(n_rep, n_atoms, n_theta_total, n_frames).total;
+}
+
+extern "C" int mdg_traj_large_list_builds(const float* ws, int n_rep, int n_atoms, int n_frames, int n_theta_total,
+                                          int32_t* build_of_frame, void* stream) {
+    MDG_CHECK_ARG(ws && build_of_frame && n_rep > 0 && n_atoms > 0 && n_frames > 0, "traj_large_list_builds: bad arguments");
+    const WsLayout L = ws_layout(n_rep, n_atoms, n_theta_total, n_frames);
+    if (!L.keep_lists) return 1;
+    MDG_HIP(hipMemcpyAsync(build_of_frame, ws + L.nl_build, sizeof(int32_t) * (size_t)n_rep * n_frames,
+                           hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return MDG_OK;
+}
+
+extern "C" int64_t mdg_traj_large_stale_words(int n_rep, int n_atoms) {
+    if (n_rep <= 0 || n_atoms <= 0) return -1;
+    return (int64_t)n_rep * n_atoms * (LG_CAP + 1);
 }
 
 extern "C" int mdg_traj_fwd_large(const MdgTrajParams* prm, const MdgCell* cell, const MdgTerms* terms,
@@ -2300,11 +2430,6 @@ extern "C" int mdg_traj_fwd_large(const MdgTrajParams* prm, const MdgCell* cell,
     return traj_fwd_large_run(prm, cell, terms, theta, mass, t_grid, v0, q0, pv0, v_t, q_t, pv_t, ws, flags, stream, nullptr);
 }
 
-extern "C" int64_t mdg_traj_large_stale_words(int n_rep, int n_atoms) {
-    if (n_rep <= 0 || n_atoms <= 0) return -1;
-    return (int64_t)n_rep * n_atoms * (LG_CAP + 1);
-}
-
 extern "C" int mdg_traj_fwd_large_stale(const MdgTrajParams* prm, const MdgCell* cell, const MdgTerms* terms,
                                         const float* theta, const float* mass, const float* t_grid,
                                         const float* v0, const float* q0, const float* pv0,
@@ -2312,105 +2437,6 @@ extern "C" int mdg_traj_fwd_large_stale(const MdgTrajParams* prm, const MdgCell*
                                         int freq, int64_t count0, uint32_t* rows, void* stream) {
     const StaleOpt so{freq, (long long)count0, rows};
     return traj_fwd_large_run(prm, cell, terms, theta, mass, t_grid, v0, q0, pv0, v_t, q_t, pv_t, ws, flags, stream, &so);
-}
-
-static int traj_adj_large_run(const MdgTrajParams* prm, const MdgCell* cell, const MdgTerms* terms,
-                              const float* theta, const float* mass, const float* t_grid,
-                              const float* v_t, const float* q_t, const float* pv_t,
-                              const float* g_v, const float* g_q, const float* g_pv,
-                              float* adj_v0, float* adj_q0, float* adj_pv0, float* adj_theta,
-                              float* ws, int32_t* flags, void* stream, const StaleOpt* so) {
-    int rc = validate_large(prm, cell, terms);
-    if (rc) return rc;
-    MDG_CHECK_ARG(mass && t_grid && v_t && q_t && adj_v0 && adj_q0 && ws && flags, "traj_adj_large: null buffer");
-    MDG_CHECK_ARG(prm->ensemble == 1 || (pv_t && adj_pv0), "traj_adj_large: NHC needs pv_t/adj_pv0");
-    MdgTrajParams pstale;
-    if (so) {
-        rc = validate_stale(prm, terms, so);
-        if (rc) return rc;
-        pstale = *prm; pstale.block = -1; prm = &pstale;
-    }
-    LG_SETUP();
-    LG_STALE_SETUP();
-    a.v_t = const_cast<float*>(v_t); a.q_t = const_cast<float*>(q_t); a.pv_t = const_cast<float*>(pv_t);
-    a.g_v = g_v; a.g_q = g_q; a.g_pv = g_pv;
-    const int C = prm->n_chains, T = prm->n_frames, KT = terms->n_theta_total;
-    const size_t fr = sizeof(float) * (size_t)N * 3;
-    // lam = dL/dy_{T-1}: ONE launch for all replicas (three copies per replica in a host loop were 192 serialised 3-5 us copies
-    // per 64-replica adjoint: 0.5-1 ms of a 20 ms pass)
-    (void)fr;
-    hipLaunchKernelGGL(large_adj_init, dim3((3 * N + 255) / 256, R), dim3(256), 0, st, g_v, g_q, g_pv, N, T, C, a.lv, a.lq, a.lp);
-    MDG_HIP(hipMemsetAsync(a.gth, 0, sizeof(float) * (size_t)R * (KT > 0 ? KT : 1), st));
-    if (table) {
-        MDG_HIP(hipMemsetAsync(a.g64, 0, sizeof(unsigned long long) * (size_t)R * KT, st));
-    }
-    const int gLAx = (N + LG_ROW_ATOMS * LG_ADJ_GROUPS - 1) / (LG_ROW_ATOMS * LG_ADJ_GROUPS);
-    if (a.nl_idx) a.nbF = a.tile_cap ? a.ncol : gLAx;         // (rows of partN the listed launches write, the prep launches sum)
-#define LG_ADJ_FORCE(SECOND_)                                                                                       \
-    do {                                                                                                            \
-        const dim3 gF(nbF, Rg), gLA(gLAx, Rg);                                                                      \
-        if (a.tile_cap) {                                                                                           \
-            const size_t lds_ = sizeof(float) * 7 * (size_t)a.tile_cap;                                             \
-            if (lj126) hipLaunchKernelGGL((large_adj_tiled<KIND_LJ126>), dim3(Rg, a.ncol), dim3(LG_TILE_THREADS), lds_, sg, a, SECOND_); \
-            else hipLaunchKernelGGL((large_adj_tiled<-1>), dim3(Rg, a.ncol), dim3(LG_TILE_THREADS), lds_, sg, a, SECOND_); \
-        } else if (a.nl_idx) {                                                                                      \
-            if (lj126) hipLaunchKernelGGL((large_adj_listed<true, KIND_LJ126>), gLA, dim3(256), 0, sg, a, SECOND_);      \
-            else if (diag) hipLaunchKernelGGL((large_adj_listed<true, -1>), gLA, dim3(256), 0, sg, a, SECOND_);           \
-            else hipLaunchKernelGGL((large_adj_listed<false, -1>), gLA, dim3(256), 0, sg, a, SECOND_);                    \
-        } else if (lj126) hipLaunchKernelGGL((large_adj_force<true, KIND_LJ126>), gF, dim3(64 * wpb), tile_lds, sg, a, SECOND_); \
-        else if (diag) hipLaunchKernelGGL((large_adj_force<true, -1>), gF, dim3(64 * wpb), tile_lds, sg, a, SECOND_);    \
-        else hipLaunchKernelGGL((large_adj_force<false, -1>), gF, dim3(64 * wpb), tile_lds, sg, a, SECOND_);            \
-    } while (0)
-#define LG_STALE_ADJ(SECOND_, REBUILD_)                                                                             \
-    do {                                                                                                            \
-        const dim3 gF(nbF, Rg);                                                                                     \
-        a.st_rebuild = (REBUILD_) ? 1 : 0;                                                                          \
-        if (diag) hipLaunchKernelGGL((large_adj_force<true, -1, true>), gF, dim3(64 * wpb), tile_lds, sg, a, SECOND_);  \
-        else hipLaunchKernelGGL((large_adj_force<false, -1, true>), gF, dim3(64 * wpb), tile_lds, sg, a, SECOND_);      \
-    } while (0)
-    LG_GROUPS_BEGIN();
-    for (int i = T - 1; i >= 1; --i) {
-        a.step = i;
-        for (int g = 0; g < G; ++g) {
-            LG_GROUP(g);
-            if (so) a.st_bin = stale_due(so, 3ll * (T - 1 - i)) || stale_due(so, 3ll * (T - 1 - i) + 1);
-            LG_PREP_LAUNCH(2);                                                      // finish interval i + 1, bin frame i
-            if (so) {
-                // an interval makes three calls (sovlers.py:258-266): the dL/dt evaluation at y_i (its result is not used,
-                // but it advances the counter and may rebuild), the first augmented evaluation at the same positions, the
-                // midpoint evaluation -- running counts c0, c0 + 1, c0 + 2
-                const long long c0 = 3ll * (T - 1 - i);
-                LG_STALE_ADJ(0, stale_due(so, c0) || stale_due(so, c0 + 1));
-                a.st_bin = stale_due(so, c0 + 2);
-                LG_PREP_LAUNCH(3);
-                LG_STALE_ADJ(1, stale_due(so, c0 + 2));
-                continue;
-            }
-            LG_ADJ_FORCE(0);
-            LG_PREP_LAUNCH(3);                                                      // midpoint state, bin it
-            LG_ADJ_FORCE(1);
-        }
-    }
-#undef LG_ADJ_FORCE
-#undef LG_STALE_ADJ
-    a.step = 0;
-    for (int g = 0; g < G; ++g) {
-        LG_GROUP(g);
-        LG_PREP_LAUNCH(4);                                                          // finish interval 1
-    }
-    LG_GROUPS_END();
-    MDG_HIP(hipMemcpyAsync(adj_v0, a.lv, sizeof(float) * (size_t)R * N * 3, hipMemcpyDeviceToDevice, st));
-    MDG_HIP(hipMemcpyAsync(adj_q0, a.lq, sizeof(float) * (size_t)R * N * 3, hipMemcpyDeviceToDevice, st));
-    if (prm->ensemble == 0)
-        MDG_HIP(hipMemcpy2DAsync(adj_pv0, sizeof(float) * C, a.lp, sizeof(float) * MDG_MAX_CHAINS, sizeof(float) * C, R,
-                                 hipMemcpyDeviceToDevice, st));
-    if (adj_theta && table) {
-        const size_t n = (size_t)R * KT;
-        hipLaunchKernelGGL(large_table_grad, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a.g64, n, terms->t[0].c, adj_theta);
-    } else if (adj_theta && KT > 0)
-        MDG_HIP(hipMemcpyAsync(adj_theta, a.gth, sizeof(float) * (size_t)R * KT, hipMemcpyDeviceToDevice, st));
-    MDG_CHECK_LAUNCH("traj_adj_large");
-    return MDG_OK;
 }
 
 extern "C" int mdg_traj_adj_large(const MdgTrajParams* prm, const MdgCell* cell, const MdgTerms* terms,

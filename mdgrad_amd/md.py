@@ -155,6 +155,15 @@ class _TableSpec(ops.FusedSpec):
             return torch.stack((c1, self.du * dc1), 1).reshape(-1)
 
 
+def _stale_shape(n_rep, n_atoms, large):
+    """Shape of the persistent stale-list buffer, sized by the library: the rows and counts of mdg_traj_*_large_stale as one
+    run of int32 words (`large`), else the [R][N][N] int16 codes of the one-workgroup kernels."""
+    lib = _lib.load()
+    if large:
+        return (int(lib.mdg_traj_large_stale_words(n_rep, n_atoms)),)
+    return (n_rep, n_atoms, int(lib.mdg_traj_stale_words(n_rep, n_atoms)) // (n_rep * n_atoms))
+
+
 class _EOM(torch.nn.Module):
     _ensemble = None
     _method = None
@@ -244,8 +253,7 @@ class _EOM(torch.nn.Module):
                     or N > (min(FUSED_MAX_ATOMS_LARGE, 32768) if stale_large else FUSED_MAX_ATOMS)):
                 return None
             code = getattr(self, "_stale_code", None)
-            shape = ((getattr(self.system, "n_replicas", 1) * N * 257,) if stale_large
-                     else (getattr(self.system, "n_replicas", 1), N, N))
+            shape = _stale_shape(getattr(self.system, "n_replicas", 1), N, stale_large)
             if self.update_count % freq != 0 and (code is None or tuple(code.shape) != shape):
                 return None                 # (between two rebuilds without the lists of this geometry: the generic path)
         members = _table_members(self.model) if mods is None and self.adjoint and self.fused_table else None
@@ -305,7 +313,7 @@ class _EOM(torch.nn.Module):
         every term as of the last rebuild; `large`: the rows of mdg_traj_*_large_stale, [R][N][256] uint32 entries + counts) --
         the fused counterpart of the reference's nbr_list / offsets attributes."""
         code = getattr(self, "_stale_code", None)
-        shape = (n_rep * n_atoms * 257,) if large else (n_rep, n_atoms, n_atoms)
+        shape = _stale_shape(n_rep, n_atoms, large)
         if code is None or tuple(code.shape) != shape or code.device != device:
             if code is not None or self.update_count % int(self.topology_update_freq) != 0:
                 raise RuntimeError("mdgrad_amd: the fused stale-list kernels have no lists for this launch (%s) while the call "

@@ -521,8 +521,6 @@ class FusedTrajFn(torch.autograd.Function):
             raw = torch.empty(fuse.nbins, device=dev)
             run(lib.mdg_traj_fwd_small_rdf_ft, ptr(f_t), *out, C.byref(fuse.struct()), ptr(raw))
         elif ctx.stale_freq:
-            if ctx.large:
-                assert int(lib.mdg_traj_large_stale_words(R, N)) == R * N * 257
             fn = lib.mdg_traj_fwd_large_stale if ctx.large else lib.mdg_traj_fwd_small_stale
             # (the lists this pass ended with: what its backward continues from)
             ctx.stale_code = _stale_launch(ctx, spec, R, T, dev, 2, lambda *tail: run(fn, *out, *tail))

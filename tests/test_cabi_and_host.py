@@ -344,6 +344,86 @@ def test_refusals_of_the_ten_small_trajectory_entry_points():
             assert rc == -1 and want in msg, (name, kw, rc, msg)
 
 
+def test_refusals_of_the_four_large_trajectory_entry_points():
+    """mdg_traj_{fwd,adj}_large[_stale] without a GPU: what each entry point refuses before any launch and in which words.
+    The expected column was recorded by running this table against the library of commit 0560fac, where the host side of
+    the multi-launch path was written in function-like macros; the launch plan and the launch functions behind the same
+    entry points since keep every answer.  Every tuple is refused during validation (fake pointers, nothing is launched).
+    (The stale variants' own 32 768-atom limit coincides with the path's: the common check answers first.)"""
+    from mdgrad_amd import _lib, ops
+    lib = _lib.load()
+    fake, B = ctypes.c_void_p(0x1000), ctypes.byref
+    cell = _lib.make_cell([16.9] * 3)
+    LJ = dict(kind=0,                                    # MDG_PAIR_LJ
+              p=12, q=6, c=1.0)
+
+    def table_term(nodes=64, n_theta=128, mask=False):
+        t = ops.make_term(dict(kind=ops.MDG_PAIR_TABLE, p=nodes, a=0.25, phi=0.1, c=1.0), 2.5, 0, n_theta, None)
+        if mask:
+            t.mask = 0x1000
+        return t
+
+    lj = ops.make_terms([ops.make_term(LJ, 2.5, 0, 2, None)], 2)
+    none = ops.make_terms([], 0)
+    tab = ops.make_terms([table_term()], 128)
+    tab_beside = ops.make_terms([table_term(), ops.make_term(LJ, 2.5, 128, 2, None)], 130)
+    tab_masked = ops.make_terms([table_term(mask=True)], 128)
+    tab_short = ops.make_terms([table_term(nodes=2, n_theta=4)], 4)
+    tab_theta = ops.make_terms([table_term(n_theta=100)], 100)
+
+    def params(n_rep=1, n_atoms=4096, n_chains=3, ensemble=0):
+        prm = _lib.MdgTrajParams()
+        prm.n_rep, prm.n_atoms, prm.n_frames, prm.n_chains, prm.ensemble = n_rep, n_atoms, 5, n_chains, ensemble
+        return prm
+
+    def call(name, prm=None, terms=lj, null=(), freq=3, count0=0):
+        prm = params() if prm is None else prm
+        names = ["theta", "mass", "t"] + (["v_t", "q_t", "pv_t", "g_v", "g_q", "g_pv", "adj_v0", "adj_q0", "adj_pv0", "adj_theta"]
+                                           if "_adj_" in name else ["v0", "q0", "pv0", "v_t", "q_t", "pv_t"])
+        args = [None if n in null else fake for n in names + ["ws", "flags"]]
+        if "stale" in name:
+            args += [freq, count0, None if "rows" in null else fake]
+        rc = getattr(lib, name)(None if "prm" in null else B(prm), None if "cell" in null else B(cell),
+                                None if "terms" in null else B(terms), *args, None)
+        return rc, lib.mdg_last_error()
+
+    plain = ["mdg_traj_%s_large" % d for d in ("fwd", "adj")]
+    stale = ["mdg_traj_%s_large_stale" % d for d in ("fwd", "adj")]
+    table = [                                            # (entry points, arguments, expected substring of mdg_last_error)
+        (plain + stale, dict(null=("prm",)), b"traj_large: null descriptor"),
+        (plain + stale, dict(null=("cell",)), b"traj_large: null descriptor"),
+        (plain + stale, dict(null=("terms",)), b"traj_large: null descriptor"),
+        (plain + stale, dict(prm=params(n_rep=0)), b"traj_large: bad sizes"),
+        (plain + stale, dict(prm=params(n_atoms=1)), b"traj_large: bad sizes"),
+        (plain + stale, dict(prm=params(n_atoms=32769)), b"traj_large: at most 32768 atoms"),
+        (plain + stale, dict(prm=params(n_atoms=40000)), b"traj_large: at most 32768 atoms"),
+        (plain + stale, dict(prm=params(ensemble=2)), b"ensemble must be 0 (NHC) or 1 (NVE)"),
+        (plain + stale, dict(prm=params(n_chains=1)), b"traj_large: 2 <= num_chains <= 16"),
+        (plain + stale, dict(prm=params(n_chains=17)), b"traj_large: 2 <= num_chains <= 16"),
+        (plain + stale, dict(terms=none), b"pair terms"),
+        (plain + stale, dict(terms=tab_beside), b"a tabulated pair model must be the only term, unmasked"),
+        (plain + stale, dict(terms=tab_masked), b"a tabulated pair model must be the only term, unmasked"),
+        (plain + stale, dict(terms=tab_short), b"traj_large: bad table (nodes 2, n_theta 4"),
+        (plain + stale, dict(terms=tab_theta), b"traj_large: bad table (nodes 64, n_theta 100"),
+        (plain + stale, dict(null=("mass",)), b"_large: null buffer"),
+        (plain + stale, dict(null=("ws",)), b"_large: null buffer"),
+        (plain + stale, dict(null=("flags",)), b"_large: null buffer"),
+        (plain + stale, dict(terms=tab, null=("mass",)), b"_large: null buffer"),
+        (plain + stale, dict(null=("pv_t",)), b"_large: NHC needs pv"),
+        (["mdg_traj_fwd_large", "mdg_traj_fwd_large_stale"], dict(null=("pv0",)), b"traj_fwd_large: NHC needs pv0/pv_t"),
+        (["mdg_traj_adj_large", "mdg_traj_adj_large_stale"], dict(null=("adj_pv0",)), b"traj_adj_large: NHC needs pv_t/adj_pv0"),
+        (stale, dict(freq=0), b"traj_large_stale: bad frequency / counter / list buffer"),
+        (stale, dict(count0=-1), b"traj_large_stale: bad frequency / counter / list buffer"),
+        (stale, dict(null=("rows",)), b"traj_large_stale: bad frequency / counter / list buffer"),
+        (stale, dict(terms=tab), b"traj_large_stale: a tabulated pair model is not supported"),
+        (stale, dict(null=("mass",), freq=0), b"_large: null buffer"),      # (the direction's own checks come first)
+    ]
+    for names, kw, want in table:
+        for name in names:
+            rc, msg = call(name, **kw)
+            assert rc == -1 and want in msg, (name, kw, rc, msg)
+
+
 def test_host_side_of_the_row_chain_and_the_nh_half_step_scratch():
     """mdg_row_chain / mdg_nhv_scratch_floats without a GPU: struct layout, argument validation (every refusal happens before
     a launch), the empty call, and the size of the cross-workgroup scratch (partials of 1 024-element chunks, a ticket per

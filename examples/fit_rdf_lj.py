@@ -5,6 +5,7 @@ trajectory -- the inner loop of the reference's scripts/fit_rdf_pair.py / demo/f
 fused forward and one fused adjoint launch, and (on N GPUs) one gradient all-reduce per step.
 
     python examples/fit_rdf_lj.py --replicas 64 --epochs 30
+    python examples/fit_rdf_lj.py --replicas 64 --epochs 30 --pressure-target 1.6    # + (mean P - target)^2 in the loss
 """
 import argparse
 import os
@@ -51,9 +52,12 @@ def main(argv=None):
     ap.add_argument("--epochs", type=int, default=30)
     ap.add_argument("--frames", type=int, default=60)
     ap.add_argument("--lr", type=float, default=0.01)
+    ap.add_argument("--pressure-target", type=float, default=None,
+                    help="adds (mean P - target)^2 over the sampled frames to the loss (thermo.Pressure); off by default")
     args = ap.parse_args(argv)
     from mdgrad_amd import dist as mdist
     from mdgrad_amd.observable import rdf
+    from mdgrad_amd.thermo import Pressure
     rank, world, dev = mdist.init()
     # target: RDF of the "true" liquid (sigma = 1.0, eps = 1.0)
     system, _, integ_true = build(1.0, 1.0, dev)
@@ -63,6 +67,7 @@ def main(argv=None):
         g_target = obs(q_true[:, 20:])[2]
     # start from a wrong potential
     system, model, integ = build(0.92, 0.8, dev)
+    pressure = Pressure(system, integ.model) if args.pressure_target is not None else None
     opt = torch.optim.Adam(integ.parameters(), lr=args.lr)
     hist = []
     for epoch in range(args.epochs):
@@ -70,6 +75,8 @@ def main(argv=None):
         v_t, q_t, pv_t = trajectories(system, integ, args.replicas, args.frames, 0.005, 100 + epoch * world + rank, dev)
         g = obs(q_t[:, 20:])[2]
         loss = (g - g_target).pow(2).mean()
+        if pressure is not None:
+            loss = loss + (pressure(q_t[:, 20:], v_t[:, 20:]).mean() - args.pressure_target).pow(2)
         loss.backward()
         mdist.all_reduce_grads(integ.parameters(), average=True)
         opt.step()

@@ -851,6 +851,28 @@ int mdg_adf_bwd(const float* pos, int n_frames, int n_atoms, const MdgCell* cell
                 const float* g_raw, float* g_xyz, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * K15  pair virial of every frame and its gradient: the configurational part of the pressure
+ *      P = (sum_i m_i |v_i|^2 + W) / (dim V)  (mdgrad_amd/thermo.py Pressure; the reference's sketch, torchmd/thermo.py:17-54,
+ *      uses undefined names and does not run; csrc/virial.hip)
+ *   pos [n_frames, n_atoms, 3]; the cell must be diagonal; terms: 1..MDG_MAX_TERMS built-in forms (MDG_PAIR_LJ .. MDG_PAIR_YUKAWA),
+ *   each with its own cutoff and optional [n_atoms, n_atoms] mask, parameters packed in term order (theta_off = running sum).
+ *   W[f] = - sum_terms sum_pairs r phi'(r) over the pair set PairPotentials sums the energy over: i < j, the strict +-1/2
+ *   minimum image of topology.py:59-64, 0 < d^2 < cutoff^2 (un-contracted d^2 like the list builders), the term's mask.
+ *   W = -dU/ds at s = 1 for x -> s x, L -> s L with the pair set held fixed.
+ *   fwd: W[n_frames].
+ *   bwd: given gW[n_frames] = dL/dW, writes g_pos [n_frames, n_atoms, 3] = gW_f sum_j (phi' + r phi'') (x_j - x_i) / r and
+ *        g_theta[n_theta_total] = - sum_f gW_f sum_pairs r dphi'/dtheta (nullable without parameters).
+ *   List-free all-pairs sweeps (a wave per frame up to 128 atoms, a workgroup per frame up to 1024, 256 x 256 tiles up to
+ *   32 768); n_frames < 2^24.  workspace: mdg_virial_workspace() floats, shared by both calls.  Fixed-order sums, no
+ *   floating-point atomics: bitwise reproducible.
+ */
+int64_t mdg_virial_workspace(int n_frames, int n_atoms, int n_theta_total);
+int mdg_virial_fwd(const float* pos, int n_frames, int n_atoms, const MdgCell* cell /*host*/, const MdgTerms* terms /*host*/,
+                   const float* theta, float* W, float* workspace, void* stream);
+int mdg_virial_bwd(const float* pos, int n_frames, int n_atoms, const MdgCell* cell /*host*/, const MdgTerms* terms /*host*/,
+                   const float* theta, const float* gW, float* g_pos, float* g_theta, float* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * f4  bonded terms over a static topology table (csrc/bonded.hip).
  * Replaces torchmd/interface.py:447-455 (BondPotentials.forward: harmonic in the SQUARED bond length,
  * 1/2 k (|b|^2 - ro)^2) and :496-508 (AnglePotentials.forward: 1/2 k (theta - theta0)^2 over triples (i, j, k) centred on

@@ -8,7 +8,7 @@ import torch
 from . import _lib
 
 PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libmdgrad_torch.so")
-OPS = ("nbr_build", "pair_force", "pair_hvp", "nhc_vv_forward", "nhc_vv_adjoint", "rdf_fwd", "rdf_bwd", "adf_fwd", "adf_bwd", "edge_geom",
+OPS = ("nbr_build", "pair_force", "pair_hvp", "nhc_vv_forward", "nhc_vv_adjoint", "rdf_fwd", "rdf_bwd", "adf_fwd", "adf_bwd", "virial_fwd", "virial_bwd", "edge_geom",
        "edge_geom_bwd", "cfconv_fwd", "cfconv_bwd", "dense_ssp", "ssp_dual_bwd_t", "atb")
 _state = {"tried": False, "ns": None}
 
@@ -26,6 +26,17 @@ def get():
 def cell_args(cs):
     """MdgCell -> the 19 numbers of the ops' `float[] cell` argument."""
     return [float(x) for x in cs.h] + [float(x) for x in cs.inv] + [float(cs.diag)]
+
+
+def terms_args(terms):
+    """MdgTerms -> the `int[] terms_i` (kind, p, q, theta_off, n_theta per term) and `float[] terms_f` (c, a, phi, cutoff)
+    arguments of the ops that take several pair terms."""
+    ti, tf = [], []
+    for k in range(terms.n_terms):
+        t = terms.t[k]
+        ti += [int(t.kind), int(t.p), int(t.q), int(t.theta_off), int(t.n_theta)]
+        tf += [float(t.c), float(t.a), float(t.phi), float(t.cutoff)]
+    return ti, tf
 
 
 def none_if_empty(t):

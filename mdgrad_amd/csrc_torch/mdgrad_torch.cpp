@@ -12,6 +12,7 @@
 //   nhc_vv_adjoint   K7   sovlers.py:211-293                -> mdg_traj_adj_small
 //   rdf_fwd/rdf_bwd  K8   observable.py:62-76               -> mdg_rdf_fwd_uniform / mdg_rdf_bwd_uniform
 //   adf_fwd/adf_bwd  K14  observable.py:120-151             -> mdg_adf_fwd / mdg_adf_bwd
+//   virial_fwd/_bwd  K15  thermo.py Pressure (pair virial)   -> mdg_virial_fwd / mdg_virial_bwd
 //   edge_geom(+_bwd) schnet.py:142                          -> mdg_edge_geom / mdg_edge_geom_bwd
 //   cfconv_fwd/_bwd  K9+K10 modules.py:531-571              -> mdg_cfconv_fwd(_bf16) / mdg_cfconv_bwd(_bf16)
 //   dense_ssp        K11/12 layers.py:86-134                -> mdg_dense
@@ -289,6 +290,56 @@ Tensor adf_bwd(const Tensor& pos, int64_t n_frames, int64_t n_atoms, at::ArrayRe
     return g;
 }
 
+// ------------------------------------------------------------------------------------------------ K15
+// terms_i / terms_f = the terms' 5 ints / 4 floats back to back; masks = one optional [N,N] uint8 selection per term
+MdgTerms virial_terms(const Tensor& pos, at::ArrayRef<int64_t> terms_i, at::ArrayRef<double> terms_f,
+                      const c10::List<c10::optional<Tensor>>& masks, const OptTensor& theta) {
+    check_f32(pos, "pos");
+    TORCH_CHECK(pos.dim() == 3 && pos.size(2) == 3, "mdgrad: pos must be [F,N,3]");
+    const size_t nt = terms_i.size() / 5;
+    TORCH_CHECK(nt >= 1 && nt <= MDG_MAX_TERMS && terms_i.size() == 5 * nt && terms_f.size() == 4 * nt && masks.size() == nt,
+                "mdgrad: 1..", MDG_MAX_TERMS, " pair terms of 5 ints + 4 floats + an optional mask");
+    MdgTerms ts{};
+    ts.n_terms = (int32_t)nt;
+    for (size_t m = 0; m < nt; ++m) {
+        const OptTensor mk = masks.get(m);
+        if (mk.has_value() && mk->defined()) {
+            same_device(pos, *mk, "mask");
+            TORCH_CHECK(mk->numel() == pos.size(1) * pos.size(1), "mdgrad: a mask must be [N,N]");
+        }
+        ts.t[m] = make_term(terms_i.slice(5 * m, 5), terms_f.slice(4 * m, 4), mk);
+        ts.n_theta_total += ts.t[m].n_theta;
+    }
+    const int64_t have = (theta.has_value() && theta->defined()) ? theta->numel() : 0;
+    TORCH_CHECK(have == ts.n_theta_total, "mdgrad: theta must hold the terms' ", ts.n_theta_total, " parameters");
+    if (have) same_device(pos, *theta, "theta");
+    return ts;
+}
+Tensor virial_fwd(const Tensor& pos, at::ArrayRef<double> cell, at::ArrayRef<int64_t> terms_i, at::ArrayRef<double> terms_f,
+                  const c10::List<c10::optional<Tensor>>& masks, const OptTensor& theta) {
+    const MdgTerms ts = virial_terms(pos, terms_i, terms_f, masks, theta);
+    const MdgCell c = make_cell(cell);
+    const int F = (int)pos.size(0), N = (int)pos.size(1);
+    Tensor W = at::empty({F}, pos.options()), ws = at::empty({mdg_virial_workspace(F, N, ts.n_theta_total)}, pos.options());
+    ok(mdg_virial_fwd(fptr(pos), F, N, &c, &ts, fptr(theta, "theta"), mptr(W), mptr(ws), stream_of(pos)));
+    return W;
+}
+// (g_pos [F,N,3], g_theta [K])
+std::tuple<Tensor, Tensor> virial_bwd(const Tensor& pos, at::ArrayRef<double> cell, at::ArrayRef<int64_t> terms_i,
+                                      at::ArrayRef<double> terms_f, const c10::List<c10::optional<Tensor>>& masks,
+                                      const OptTensor& theta, const Tensor& gW) {
+    const MdgTerms ts = virial_terms(pos, terms_i, terms_f, masks, theta);
+    check_f32(gW, "gW"); same_device(pos, gW, "gW");
+    TORCH_CHECK(gW.numel() == pos.size(0), "mdgrad: gW must have one entry per frame");
+    const MdgCell c = make_cell(cell);
+    const int F = (int)pos.size(0), N = (int)pos.size(1), K = ts.n_theta_total;
+    Tensor g = at::empty_like(pos), gth = at::empty({K}, pos.options());
+    Tensor ws = at::empty({mdg_virial_workspace(F, N, K)}, pos.options());
+    ok(mdg_virial_bwd(fptr(pos), F, N, &c, &ts, fptr(theta, "theta"), fptr(gW), mptr(g), K ? mptr(gth) : nullptr, mptr(ws),
+                      stream_of(pos)));
+    return {g, gth};
+}
+
 // ------------------------------------------------------------------------------------------------ SchNet block
 MdgFilterNet filter_net(const Tensor& mu, const Tensor& coef, const Tensor& W1, const Tensor& b1, const Tensor& W2,
                         const Tensor& b2) {
@@ -450,6 +501,9 @@ TORCH_LIBRARY(mdgrad, m) {
           "float spacing, float coeff) -> Tensor");
     m.def("adf_bwd(Tensor pos, int n_frames, int n_atoms, float[] cell, float cutoff, Tensor col, Tensor cnt, Tensor mu, "
           "float spacing, float coeff, Tensor g_raw) -> Tensor");
+    m.def("virial_fwd(Tensor pos, float[] cell, int[] terms_i, float[] terms_f, Tensor?[] masks, Tensor? theta) -> Tensor");
+    m.def("virial_bwd(Tensor pos, float[] cell, int[] terms_i, float[] terms_f, Tensor?[] masks, Tensor? theta, Tensor gW) -> "
+          "(Tensor, Tensor)");
     m.def("edge_geom(Tensor x, Tensor? w, Tensor nbr, Tensor offsets) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("edge_geom_bwd(Tensor? d_b, Tensor dd_b, Tensor? d, Tensor? dd, Tensor uhat, Tensor? ddel, Tensor col, Tensor eid, "
           "Tensor cnt) -> (Tensor, Tensor)");
@@ -474,6 +528,8 @@ TORCH_LIBRARY_IMPL(mdgrad, CUDA, m) {      // (the HIP backend registers under t
     m.impl("rdf_bwd", rdf_bwd);
     m.impl("adf_fwd", adf_fwd);
     m.impl("adf_bwd", adf_bwd);
+    m.impl("virial_fwd", virial_fwd);
+    m.impl("virial_bwd", virial_bwd);
     m.impl("edge_geom", edge_geom);
     m.impl("edge_geom_bwd", edge_geom_bwd);
     m.impl("cfconv_fwd", cfconv_fwd);

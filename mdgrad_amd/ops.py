@@ -5,6 +5,7 @@ torch.autograd.Function wrappers that own the differentiation contract
     FusedTrajFn                                                 whole NH-Verlet/Verlet trajectory + adjoint
     RdfRawFn                                                    soft histogram
     AdfRawFn                                                    soft histogram of bond angles
+    VirialFn                                                    pair virial of every frame (pressure)
 
 Everything here requires HIP tensors; there is no CPU path.
 """
@@ -900,6 +901,46 @@ class AdfRawFn(torch.autograd.Function):
                                   ell.max_nbr, ptr(muc), float(spacing), float(coeff), B, ptr(gr), ptr(gx[f0:f1]),
                                   stream_ptr(x3.device)), "mdg_adf_bwd")
         return gx.reshape(shape), None, None, None, None, None, None
+
+
+# ----------------------------------------------------------------------------- pair virial (pressure)
+class VirialFn(torch.autograd.Function):
+    """W[f] = -sum_terms sum_pairs r phi'(r) of every frame of xyz [F, N, 3] (csrc/virial.hip, K15): the configurational part
+    of thermo.Pressure.  theta = the terms' parameters packed in term order (torch.cat of the modules' parameters, so the
+    gradient flows back into them like PairEnergyFn's); terms = MdgTerms of built-in forms whose theta_off follow that
+    packing; masks keeps the terms' selection masks alive.  Differentiable once."""
+
+    @staticmethod
+    def forward(ctx, xyz, theta, cell_struct, terms, masks):
+        lib = _lib.load()
+        require_gpu(xyz, "xyz")
+        x3 = xyz.detach()
+        x3 = x3 if x3.is_contiguous() else x3.contiguous()
+        F, N = x3.shape[0], x3.shape[1]
+        th = theta.detach().to(device=x3.device, dtype=torch.float32).contiguous()
+        K = th.numel()
+        ws = torch.empty(int(lib.mdg_virial_workspace(F, N, K)), device=x3.device)
+        W = torch.empty(F, device=x3.device)
+        check(lib.mdg_virial_fwd(ptr(x3), F, N, C.byref(cell_struct), C.byref(terms), ptr(th) if K else None, ptr(W), ptr(ws),
+                                 stream_ptr(x3.device)), "mdg_virial_fwd")
+        ctx.args = (cell_struct, terms, masks, xyz.shape, theta.shape)
+        ctx.save_for_backward(x3, th)
+        return W
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gW):
+        lib = _lib.load()
+        x3, th = ctx.saved_tensors
+        cell_struct, terms, masks, xshape, tshape = ctx.args
+        F, N, K = x3.shape[0], x3.shape[1], th.numel()
+        g = gW.detach().to(torch.float32).contiguous()
+        ws = torch.empty(int(lib.mdg_virial_workspace(F, N, K)), device=x3.device)
+        gx = torch.empty_like(x3)
+        gth = torch.empty(K, device=x3.device) if K else None
+        check(lib.mdg_virial_bwd(ptr(x3), F, N, C.byref(cell_struct), C.byref(terms), ptr(th) if K else None, ptr(g), ptr(gx),
+                                 ptr(gth), ptr(ws), stream_ptr(x3.device)), "mdg_virial_bwd")
+        return gx.reshape(xshape), (gth.reshape(tshape) if K else None), None, None, None
 
 
 # ----------------------------------------------------------------------------- velocity observables

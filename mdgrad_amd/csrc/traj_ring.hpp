@@ -104,9 +104,11 @@ __device__ __forceinline__ void ring_table_scatter2(const RingRdf& X, int idx, f
 // LEVEL 1: force.  LEVEL 2: force, H.w and the parameter sums.  LEVEL 3: LEVEL 2 without the force (the adjoint's
 // first evaluation of an interval when the forward pass stored the force of that frame: TrajArgs::f_t).
 // r0 / r1: the pair in .x / .y feeds the RDF (exists and, for RDF = 1, is the one copy of a pair met twice).
+// SUMS = false (LEVEL >= 2): without the parameter sums -- no tk factors, no TH accumulation, no table scatter: the adjoint's
+// first evaluation of an NHC interval, whose sums the midpoint evaluation overwrites before anything reads them (sovlers.py:160).
 constexpr bool ring_level_force(int level) { return level == 1 || level == 2; }
 
-template <int LEVEL, bool NEAR, bool CROSS, bool JSIDE, int RDF, int KIND>
+template <int LEVEL, bool NEAR, bool CROSS, bool JSIDE, int RDF, int KIND, bool SUMS = true>
 __device__ __forceinline__ void ring_pair(const RingLJ& K, const RingRdf& X, const Vec3x2& qi, const Vec3x2& wi,
                                           const Vec3x2& qj, const Vec3x2& wj, bool v0, bool v1, bool r0, bool r1,
                                           Vec3x2& fi, Vec3x2& gi, Vec3x2& fj, Vec3x2& gj, f32x2 (&TH)[MDG_MAX_THETA],
@@ -187,7 +189,7 @@ __device__ __forceinline__ void ring_pair(const RingLJ& K, const RingRdf& X, con
             c1 = (K.m1a * s6 - K.m1b * s12) * i2;
             if constexpr (LEVEL >= 2) {
                 kk = (K.kb * s12 - K.ka * s6) * (i2 * i2);
-                tk[0] = s6 * i2; tk[1] = s12 * i2;       // (S6, S12: both parameter gradients are linear in these sums)
+                if constexpr (SUMS) { tk[0] = s6 * i2; tk[1] = s12 * i2; }   // (S6, S12: both parameter gradients are linear in these sums)
             }
         } else {
             // branch-free: a rejected pair is evaluated at the cutoff and multiplied by zero
@@ -199,9 +201,11 @@ __device__ __forceinline__ void ring_pair(const RingLJ& K, const RingRdf& X, con
             c1 = f32x2{ok0 ? o0.du * ir0 : 0.f, ok1 ? o1.du * ir1 : 0.f};
             if constexpr (LEVEL >= 2) {
                 kk = f32x2{ok0 ? (o0.d2u - o0.du * ir0) * (ir0 * ir0) : 0.f, ok1 ? (o1.d2u - o1.du * ir1) * (ir1 * ir1) : 0.f};
+                if constexpr (SUMS) {
 #pragma unroll
-                for (int k = 0; k < NTH; ++k)
-                    tk[k] = f32x2{ok0 ? 0.5f * o0.ddu_dth[k] * ir0 : 0.f, ok1 ? 0.5f * o1.ddu_dth[k] * ir1 : 0.f};
+                    for (int k = 0; k < NTH; ++k)
+                        tk[k] = f32x2{ok0 ? 0.5f * o0.ddu_dth[k] * ir0 : 0.f, ok1 ? 0.5f * o1.ddu_dth[k] * ir1 : 0.f};
+                }
             }
         }
         if constexpr (ring_level_force(LEVEL)) {
@@ -226,9 +230,11 @@ __device__ __forceinline__ void ring_pair(const RingLJ& K, const RingRdf& X, con
             if constexpr (JSIDE) {
                 gj.x -= CROSS ? tx.yx : tx; gj.y -= CROSS ? ty.yx : ty; gj.z -= CROSS ? tz.yx : tz;
             }
+            if constexpr (SUMS) {
 #pragma unroll
-            for (int k = 0; k < NTH; ++k) TH[k] += tk[k] * b;
-            if constexpr (KIND == KIND_TABLE) {
+                for (int k = 0; k < NTH; ++k) TH[k] += tk[k] * b;
+            }
+            if constexpr (KIND == KIND_TABLE && SUMS) {
                 // table gradient: d(w.F)/dnode += 1/2 (D.w_ij) basis per DIRECTED pair (tgw carries 1/2 h 2^S); a ring step
                 // meets an undirected pair once and stands for both directions
                 if (X.tgw != 0.f) {
@@ -287,7 +293,7 @@ __device__ __forceinline__ RingMask ring_mask_load(const uint8_t* __restrict__ m
     return M;
 }
 
-template <int LEVEL, bool NEAR, int RDF, int KIND, bool MASK>
+template <int LEVEL, bool NEAR, int RDF, int KIND, bool MASK, bool SUMS = true>
 __device__ __forceinline__ void ring_sweep(const RingLJ& K, const RingRdf& X, const RingMask& M, int N, int lane, const Vec3x2& q,
                                            const Vec3x2& w, Vec3x2& f, Vec3x2& g, float (&th)[MDG_MAX_THETA], Vec3x2& rq,
                                            f32x2* __restrict__ lds) {
@@ -308,7 +314,7 @@ __device__ __forceinline__ void ring_sweep(const RingLJ& K, const RingRdf& X, co
         const bool v = vi0 && vi1;
         bool vm = v;
         if constexpr (MASK) vm = v && ((ring_mask_word(M.w, lane >> 4) >> (2 * (lane & 15) + 1)) & 1u);   // (i0, i1)
-        ring_pair<LEVEL, NEAR, true, false, RDF, KIND>(K, X, q, w, q, w, vm, vm, v, RDF == 2 && v, fi, gi, fj, gj, D, ri, rj);
+        ring_pair<LEVEL, NEAR, true, false, RDF, KIND, SUMS>(K, X, q, w, q, w, vm, vm, v, RDF == 2 && v, fi, gi, fj, gj, D, ri, rj);
     }
     const int prev = lane < nl ? ((lane == 0 ? nl : lane) - 1) * 4 : lane * 4;     // bpermute address of lane l-1
     const int nsteps = (nl - 1) >> 1;
@@ -328,8 +334,8 @@ __device__ __forceinline__ void ring_sweep(const RingLJ& K, const RingRdf& X, co
             const uint32_t b0 = ring_mask_word(M.w, idx >> 4) >> (2 * (idx & 15)), b1 = ring_mask_word(M.w + 4, idx >> 4) >> (2 * (idx & 15));
             ms0 = s0 && (b0 & 1u); mc0 = c0 && (b0 & 2u); mc1 = c1 && (b1 & 1u); ms1 = s1 && (b1 & 2u);
         }
-        ring_pair<LEVEL, NEAR, false, true, RDF, KIND>(K, X, q, w, qj, wj, ms0, ms1, s0, s1, fi, gi, fj, gj, S, ri, rj);
-        ring_pair<LEVEL, NEAR, true, true, RDF, KIND>(K, X, q, w, qj, wj, mc0, mc1, c0, c1, fi, gi, fj, gj, S, ri, rj);
+        ring_pair<LEVEL, NEAR, false, true, RDF, KIND, SUMS>(K, X, q, w, qj, wj, ms0, ms1, s0, s1, fi, gi, fj, gj, S, ri, rj);
+        ring_pair<LEVEL, NEAR, true, true, RDF, KIND, SUMS>(K, X, q, w, qj, wj, mc0, mc1, c0, c1, fi, gi, fj, gj, S, ri, rj);
     }
     if (!(nl & 1)) {
         // antipodal lanes (k = nl/2) see each other from both sides -> directed evaluation, visitors not updated
@@ -346,8 +352,8 @@ __device__ __forceinline__ void ring_sweep(const RingLJ& K, const RingRdf& X, co
         }
         const bool once = RDF == 2 || 2 * lane < nl;
         Vec3x2 fu = vzero(), gu = vzero(), ru = vzero();
-        ring_pair<LEVEL, NEAR, false, false, RDF, KIND>(K, X, q, w, qj, wj, ms0, ms1, s0 && once, s1 && once, fi, gi, fu, gu, D, ri, ru);
-        ring_pair<LEVEL, NEAR, true, false, RDF, KIND>(K, X, q, w, qj, wj, mc0, mc1, c0 && once, c1 && once, fi, gi, fu, gu, D, ri, ru);
+        ring_pair<LEVEL, NEAR, false, false, RDF, KIND, SUMS>(K, X, q, w, qj, wj, ms0, ms1, s0 && once, s1 && once, fi, gi, fu, gu, D, ri, ru);
+        ring_pair<LEVEL, NEAR, true, false, RDF, KIND, SUMS>(K, X, q, w, qj, wj, mc0, mc1, c0 && once, c1 && once, fi, gi, fu, gu, D, ri, ru);
     }
     // the travelling accumulators are nsteps lanes ahead of their owners
     int home = lane + nsteps; home = home >= nl ? home - nl : home;
@@ -359,13 +365,19 @@ __device__ __forceinline__ void ring_sweep(const RingLJ& K, const RingRdf& X, co
     if constexpr (LEVEL >= 2) {
         gj = ring_move(gj, home);
         g.x = -(gi.x + gj.x); g.y = -(gi.y + gj.y); g.z = -(gi.z + gj.z);
+        if constexpr (SUMS) {
 #pragma unroll
-        for (int k = 0; k < MDG_MAX_THETA; ++k)
-            th[k] = 2.f * hsum(S[k]) + hsum(D[k]);  // an undirected pair of the ring steps stands for both directions
+            for (int k = 0; k < MDG_MAX_THETA; ++k)
+                th[k] = 2.f * hsum(S[k]) + hsum(D[k]);  // an undirected pair of the ring steps stands for both directions
+        }
     }
     if constexpr (RDF == 2) {
         rj = ring_move(rj, home);
         rq.x = ri.x + rj.x; rq.y = ri.y + rj.y; rq.z = ri.z + rj.z;
+    } else {
+        // (every variant ends in the same stores: where the callers' branches over the variants join, the compiler merges the
+        //  last stores of the arms, and arms that end in stores to DIFFERENT outputs leave it a pointer it keeps in scratch)
+        rq = vzero();
     }
 }
 
@@ -380,21 +392,21 @@ __device__ __forceinline__ bool ring_near(const RingLJ& K, const Vec3x2& q) {
 }
 
 // RDF: compile-time mode of the kernel; with_rdf: this frame is one of the observable's frames (wave-uniform)
-template <int LEVEL, int RDF, int KIND, bool MASK>
+template <int LEVEL, int RDF, int KIND, bool MASK, bool SUMS = true>
 __device__ __forceinline__ void ring_force(const RingLJ& K, const RingRdf& X, const RingMask& M, bool with_rdf, int N, int lane,
                                            const Vec3x2& q, const Vec3x2& w, Vec3x2& f, Vec3x2& g, float (&th)[MDG_MAX_THETA],
                                            Vec3x2& rq, f32x2* __restrict__ lds) {
     const bool near = ring_near(K, q);
     if constexpr (RDF != 0) {
         if (with_rdf) {
-            if (near) ring_sweep<LEVEL, true, RDF, KIND, MASK>(K, X, M, N, lane, q, w, f, g, th, rq, lds);
-            else ring_sweep<LEVEL, false, RDF, KIND, MASK>(K, X, M, N, lane, q, w, f, g, th, rq, lds);
+            if (near) ring_sweep<LEVEL, true, RDF, KIND, MASK, SUMS>(K, X, M, N, lane, q, w, f, g, th, rq, lds);
+            else ring_sweep<LEVEL, false, RDF, KIND, MASK, SUMS>(K, X, M, N, lane, q, w, f, g, th, rq, lds);
             return;
         }
     }
     if constexpr (LEVEL >= 1) {
-        if (near) ring_sweep<LEVEL, true, 0, KIND, MASK>(K, X, M, N, lane, q, w, f, g, th, rq, lds);
-        else ring_sweep<LEVEL, false, 0, KIND, MASK>(K, X, M, N, lane, q, w, f, g, th, rq, lds);
+        if (near) ring_sweep<LEVEL, true, 0, KIND, MASK, SUMS>(K, X, M, N, lane, q, w, f, g, th, rq, lds);
+        else ring_sweep<LEVEL, false, 0, KIND, MASK, SUMS>(K, X, M, N, lane, q, w, f, g, th, rq, lds);
     }
 }
 
@@ -544,7 +556,8 @@ __device__ __forceinline__ void ring_sweep_lj_multi(const RingLJ (&K)[NT], const
 // 228-260): LJ 12-6 terms share ONE sweep (ring_sweep_lj_multi); other LJ-family powers take one ring sweep per term with the
 // term's constants and its 128-bit mask rows, forces and Hessian.w added up, the parameter sums kept per term.  The fused
 // observable rides on the first term's sweep only (its flags are unmasked).
-template <int LEVEL, int RDF, int KIND, bool MASK, int NT>
+// (SUMS = false leaves th untouched; the shared LJ 12-6 sweep of several terms always forms its sums)
+template <int LEVEL, int RDF, int KIND, bool MASK, int NT, bool SUMS = true>
 __device__ __forceinline__ void ring_force_terms(const RingLJ (&K)[NT], const RingRdf& X, const RingMask (&M)[NT], bool with_rdf, int N,
                                                  int lane, const Vec3x2& q, const Vec3x2& w, Vec3x2& f, Vec3x2& g,
                                                  float (&th)[NT][MDG_MAX_THETA], Vec3x2& rq, f32x2* __restrict__ lds) {
@@ -556,12 +569,12 @@ __device__ __forceinline__ void ring_force_terms(const RingLJ (&K)[NT], const Ri
         }
         return;
     }
-    ring_force<LEVEL, RDF, KIND, MASK>(K[0], X, M[0], with_rdf, N, lane, q, w, f, g, th[0], rq, lds);
+    ring_force<LEVEL, RDF, KIND, MASK, SUMS>(K[0], X, M[0], with_rdf, N, lane, q, w, f, g, th[0], rq, lds);
     if constexpr (NT > 1 && LEVEL >= 1) {
 #pragma unroll
         for (int m = 1; m < NT; ++m) {
             Vec3x2 f2 = vzero(), g2 = vzero(), r2 = vzero();
-            ring_force<LEVEL, 0, KIND, MASK>(K[m], X, M[m], false, N, lane, q, w, f2, g2, th[m], r2, lds);
+            ring_force<LEVEL, 0, KIND, MASK, SUMS>(K[m], X, M[m], false, N, lane, q, w, f2, g2, th[m], r2, lds);
             if constexpr (ring_level_force(LEVEL)) { f.x += f2.x; f.y += f2.y; f.z += f2.z; }
             if constexpr (LEVEL >= 2) { g.x += g2.x; g.y += g2.y; g.z += g2.z; }
         }
@@ -791,102 +804,78 @@ __device__ __forceinline__ void ring_theta(const RingLJ& K, const float (&th)[MD
 // table gradient goes to the adj_theta row of its first replica, the rows of its other replicas are zero: only the sum over
 // replicas of a tabulated kind's rows is defined (what the caller forms, ops.FusedTrajFn.backward).
 constexpr int RING_TABLE_WAVES = 8;
+// RDF = true (every other kind): RING_RDF_ADJ_WAVES replicas (one wave each: one per SIMD) share ONE copy of the observable's
+// derivative table (14 KB at the headline's 100 bins, 17 KB at most).  A copy per wave holds the CU's 160 KB to eight waves;
+// one per four leaves room for three workgroups -- twelve waves, three per SIMD.  The waves meet at one barrier, after the
+// co-operative table load, and are independent from there on.
+constexpr int RING_RDF_ADJ_WAVES = 4;
+constexpr int ring_adj_waves(bool rdf, int kind) { return kind == KIND_TABLE ? RING_TABLE_WAVES : (rdf ? RING_RDF_ADJ_WAVES : 1); }
 // FT: the forward pass stored the force of every frame (TrajArgs::f_t).  The first augmented evaluation of interval i sits at
 // frame i and needs the force there; it reads it instead of rebuilding it, and its sweep (LEVEL 3) carries no force
 // accumulators and no travelling force (6 ds_bpermute per ring step fewer).  The forward's LEVEL 1 sweep sums the force in
 // the order of the LEVEL 2 sweep, so the result is the same bits.
-#ifndef MDG_RING_ADJ_WAVES
-#define MDG_RING_ADJ_WAVES 1
-#endif
-template <bool RDF, int KIND, bool MASK = false, int NT = 1, bool FT = false>
-__global__ __launch_bounds__(KIND == KIND_TABLE ? 64 * RING_TABLE_WAVES : 64)
-__attribute__((amdgpu_waves_per_eu(KIND == KIND_LJ126 && NT == 1 && !MASK ? MDG_RING_ADJ_WAVES : 1)))
-void traj_adj_ring_kernel(const TrajArgs A, const RingRdfArgs F) {
-    static_assert(NT == 1 || (MASK && KIND != KIND_TABLE), "several terms: masked built-in forms");
-    extern __shared__ __attribute__((aligned(16))) float smr[];
-    const int N = A.prm.n_atoms, T = A.prm.n_frames, C = A.prm.n_chains;
-    const bool nhc = A.prm.ensemble == 0;
-    constexpr int NWV = KIND == KIND_TABLE ? RING_TABLE_WAVES : 1;
-    const int wid = KIND == KIND_TABLE ? (int)(threadIdx.x >> 6) : 0, lane = threadIdx.x & 63, N3 = 3 * N;
-    // (a wave beyond the last replica of the last workgroup repeats the last replica without accumulating or storing)
-    // (the other kinds launch one wave per replica: `live` is a compile-time true there, the code of round 4)
-    const bool live = KIND != KIND_TABLE || (int)(blockIdx.x * NWV + wid) < A.prm.n_rep;
-    const int rep = KIND != KIND_TABLE ? (int)blockIdx.x : (live ? (int)(blockIdx.x * NWV + wid) : A.prm.n_rep - 1);
-    RingLJ K[NT];
-    RingMask M[NT];
-#pragma unroll
-    for (int m = 0; m < NT; ++m) {
-        K[m] = ring_constants(A, m);
-        M[m] = RingMask{};
-        if constexpr (MASK) M[m] = ring_mask_load(A.terms.t[m].mask, N, lane);
-    }
-    RingRdf X{};
-    int ncell = 0;
-    if constexpr (RDF) {
-        // the cells of rdf_bwd_fine_kernel's table (8 per centre spacing over the same distances), equally spaced in d^2
-        float hu;
-        rdf_u_grid(F.mu, F.nbins, F.reach_bins, X.ulo, hu, ncell);
-        float4* tab = reinterpret_cast<float4*>(smr);
-        for (int n = lane; n < ncell; n += 64) tab[n] = F.tab[n];
-        X.tab = tab; X.inv_hu = 1.0f / hu;
-        X.tmax = fminf((float)ncell, (F.rc * F.rc - X.ulo) * X.inv_hu);
-        __syncthreads();
-    }
-    f32x2* lds = reinterpret_cast<f32x2*>(smr + 4 * ncell) + wid * 6 * 64;
-    if constexpr (KIND == KIND_TABLE) {
-        // the nodes and the workgroup's two gradient planes behind the waves' ring buffers (6 x 64 f32x2 each)
-        const MdgPairTerm& t0 = A.terms.t[0];
-        float2* ttab = reinterpret_cast<float2*>(smr + 4 * ncell + NWV * 6 * 64 * 2);
-        unsigned long long* tg = reinterpret_cast<unsigned long long*>(ttab + t0.p);        // [2 p] int64 words
-        int32_t* tflag = reinterpret_cast<int32_t*>(tg + 2 * t0.p);
-        const float* thp = A.theta + t0.theta_off;
-        for (int g = threadIdx.x; g < t0.p; g += blockDim.x) ttab[g] = make_float2(thp[2 * g], thp[2 * g + 1]);
-        for (int g = threadIdx.x; g < 2 * t0.p; g += blockDim.x) tg[g] = 0ull;
-        if (threadIdx.x == 0) *tflag = 0;
-        X.ttab = ttab; X.tg64 = tg; X.tflag = tflag; X.tgw = 0.f;
-        // one word can receive a contribution from every pair evaluation of the workgroup's replicas: one accumulating
-        // evaluation per interval, N (N - 1) / 2 pairs, two ends each
-        X.tlim = fx64_limit((double)NWV * (double)(T > 1 ? T - 1 : 1) * (double)N * (double)N);
-        X.tu0 = t0.a; X.tinv_du = 1.f / t0.phi; X.ttmax = (float)(t0.p - 1); X.tgmax = t0.p - 2;
-        __syncthreads();
-    }
-    const size_t fr = (size_t)rep * T;
+//
+// Three waves per SIMD (168 VGPRs) for the headline instantiations -- one unmasked LJ 12-6 term reading the forward's forces.
+// A sweep uses about 100 registers; what made the kernel 220 wide is the state that is live ACROSS a sweep and not used IN it:
+// the costates lv, lq and, around the midpoint sweep, their half-step values.  That state is parked by hand in a wave-private
+// LDS slab behind the ring buffers (RING_PARK_VECS x [3][64] f32x2, the ring buffers' conflict-free ds_write_b64 /
+// ds_read_b64 layout; a value comes back as the bits that went in), v is loaded after the first sweep (where f is), and the
+// first evaluation of an NHC interval runs without its dead parameter sums (SUMS = false).  Letting the register allocator
+// reach the same count on its own put 84-92 B of scratch per lane into the ring loop and cost 9 % of the pass.
+constexpr int RING_PARK_VECS = 4;
+constexpr bool ring_adj_parks(int kind, bool mask, int nt, bool ft) { return kind == KIND_LJ126 && !mask && nt == 1 && ft; }
+constexpr int ring_adj_slab(bool parks) { return (6 + (parks ? 3 * RING_PARK_VECS : 0)) * 64; }   // f32x2 per wave
+__device__ __forceinline__ void ring_park(f32x2* __restrict__ park, int slot, int lane, const Vec3x2& a) {
+    f32x2* p = park + slot * 192 + lane;
+    p[0] = a.x; p[64] = a.y; p[128] = a.z;
+}
+__device__ __forceinline__ Vec3x2 ring_unpark(const f32x2* __restrict__ park, int slot, int lane) {
+    const f32x2* p = park + slot * 192 + lane;
+    return Vec3x2{p[0], p[64], p[128]};
+}
+
+// The intervals T-1 .. 1 of one replica's adjoint, specialised on the ensemble (wave-uniform: TrajArgs::prm.ensemble): the two
+// bodies share nothing but the sweeps, and under NHC the first evaluation's parameter sums are dead.
+// lv, lq, lp: the costates, in: dL/dy_{T-1}, out: at frame 0.  gth: the parameter gradient, accumulated.
+template <bool NHC, bool RDF, int KIND, bool MASK, int NT, bool FT>
+__device__ __forceinline__ void ring_adj_intervals(const TrajArgs& A, const RingRdfArgs& F, const RingLJ (&K)[NT], RingRdf& X,
+                                                   const RingMask (&M)[NT], bool live, size_t fr, int lane, f32x2* __restrict__ lds,
+                                                   Vec3x2& lv, Vec3x2& lq, float& lp, float (&gth)[NT][MDG_MAX_THETA]) {
+    constexpr bool PARK = ring_adj_parks(KIND, MASK, NT, FT);
+    const int N = A.prm.n_atoms, T = A.prm.n_frames, C = A.prm.n_chains, N3 = 3 * N;
+    f32x2* park = lds + 6 * 64;
     f32x2 ms = {1.f, 1.f};
     if (2 * lane < N) ms.x = A.mass[2 * lane];
     if (2 * lane + 1 < N) ms.y = A.mass[2 * lane + 1];
     const f32x2 ims = rcp2(ms);
     const float Qk = ring_chain_mass(A, lane);
     const float iQ0 = 1.f / A.prm.Q[0];
-    // lam = dL/dy_{T-1}                                            sovlers.py:249
-    Vec3x2 lv = A.g_v ? ring_load(A.g_v + (fr + T - 1) * N3, N, lane) : vzero();
-    Vec3x2 lq = A.g_q ? ring_load(A.g_q + (fr + T - 1) * N3, N, lane) : vzero();
-    float lp = (nhc && lane < C && A.g_pv) ? A.g_pv[(fr + T - 1) * C + lane] : 0.f;
-    float gth[NT][MDG_MAX_THETA];
-#pragma unroll
-    for (int m = 0; m < NT; ++m)
-#pragma unroll
-        for (int k = 0; k < MDG_MAX_THETA; ++k) gth[m][k] = 0.f;
     for (int i = T - 1; i >= 1; --i) {
         const float h = A.t[i] - A.t[i - 1];
-        Vec3x2 q = ring_load(A.q_t + (fr + i) * N3, N, lane), v = ring_load(A.v_t + (fr + i) * N3, N, lane);
-        float pv = (nhc && lane < C) ? A.pv_t[(fr + i) * C + lane] : 0.f;
+        Vec3x2 q = ring_load(A.q_t + (fr + i) * N3, N, lane);
+        float pv = (NHC && lane < C) ? A.pv_t[(fr + i) * C + lane] : 0.f;
         Vec3x2 w, f, dq, rq = vzero(), ru;
         float th[NT][MDG_MAX_THETA];
         // ---------------- first augmented evaluation at (y_i, lam)
-        if (nhc) { w.x = lv.x * ims; w.y = lv.y * ims; w.z = lv.z * ims; } else w = lv;
+        if constexpr (NHC) { w.x = lv.x * ims; w.y = lv.y * ims; w.z = lv.z * ims; } else w = lv;
         const bool with_rdf = RDF && ring_frame_selected(F, i);
         // (table kind: the parameter term of an interval comes from the midpoint evaluation for NHC, sovlers.py:160, and
         //  from this first one for NVE, :82,101 -- both with total weight h)
-        if constexpr (KIND == KIND_TABLE) X.tgw = (nhc || !live) ? 0.f : 0.5f * h * A.terms.t[0].c;
-        if constexpr (FT) {
-            ring_force_terms<3, RDF ? 2 : 0, KIND, MASK, NT>(K, X, M, with_rdf, N, lane, q, w, f, dq, th, rq, lds);
-            f = ring_load(A.f_t + (fr + i) * N3, N, lane);
-        } else {
-            ring_force_terms<2, RDF ? 2 : 0, KIND, MASK, NT>(K, X, M, with_rdf, N, lane, q, w, f, dq, th, rq, lds);
+        if constexpr (KIND == KIND_TABLE) X.tgw = (NHC || !live) ? 0.f : 0.5f * h * A.terms.t[0].c;
+        if constexpr (PARK) {
+            if constexpr (NHC) ring_park(park, 0, lane, lv);          // (NVE: w IS lv, live through the sweep anyway)
+            ring_park(park, 1, lane, lq);
         }
+        ring_force_terms<FT ? 3 : 2, RDF ? 2 : 0, KIND, MASK, NT, !NHC>(K, X, M, with_rdf, N, lane, q, w, f, dq, th, rq, lds);
+        if constexpr (PARK) {
+            if constexpr (NHC) lv = ring_unpark(park, 0, lane); else lv = w;
+            lq = ring_unpark(park, 1, lane);
+        }
+        if constexpr (FT) f = ring_load(A.f_t + (fr + i) * N3, N, lane);
+        Vec3x2 v = ring_load(A.v_t + (fr + i) * N3, N, lane);
         if (with_rdf) { lq.x += rq.x; lq.y += rq.y; lq.z += rq.z; }       // dL/dq_t[i] of the fused observable
         Vec3x2 lvh, lqh;
-        if (nhc) {
+        if constexpr (NHC) {
             const Vec3x2 p{v.x * ms, v.y * ms, v.z * ms};
             const float ke = 0.5f * wave_sum(ring_dot(p, v)), slv = wave_sum(ring_dot(lv, v));
             const float pv0 = lane0(pv), lp0 = lane0(lp), c0 = pv0 * iQ0;
@@ -909,7 +898,15 @@ void traj_adj_ring_kernel(const TrajArgs A, const RingRdfArgs F) {
             // ---------------- midpoint evaluation                    :147-150
             w.x = lvh.x * ims; w.y = lvh.y * ims; w.z = lvh.z * ims;
             if constexpr (KIND == KIND_TABLE) X.tgw = live ? 0.5f * h * A.terms.t[0].c : 0.f;
+            if constexpr (PARK) {
+                ring_park(park, 0, lane, lv); ring_park(park, 1, lane, lq);
+                ring_park(park, 2, lane, lvh); ring_park(park, 3, lane, lqh);
+            }
             ring_force_terms<2, 0, KIND, MASK, NT>(K, X, M, false, N, lane, q, w, f, dq, th, ru, lds);
+            if constexpr (PARK) {
+                lv = ring_unpark(park, 0, lane); lq = ring_unpark(park, 1, lane);
+                lvh = ring_unpark(park, 2, lane); lqh = ring_unpark(park, 3, lane);
+            }
             const float slm = wave_sum(ring_dot(lvh, v));
             const float cm = lane0(pv) * iQ0, lpm0 = lane0(lph);
             const float gpm = ring_bath_vjp(A, lane, Qk, pv, lph, slm);
@@ -944,7 +941,9 @@ void traj_adj_ring_kernel(const TrajArgs A, const RingRdfArgs F) {
             MDG_RING_NVE(x) MDG_RING_NVE(y) MDG_RING_NVE(z)
 #undef MDG_RING_NVE
             if constexpr (KIND == KIND_TABLE) X.tgw = 0.f;
+            if constexpr (PARK) ring_park(park, 3, lane, lqh);        // (lvh is the sweep's own w)
             ring_force_terms<2, 0, KIND, MASK, NT>(K, X, M, false, N, lane, q, lvh, f, dq, th, ru, lds);
+            if constexpr (PARK) lqh = ring_unpark(park, 3, lane);
             const Vec3x2 gv = A.g_v ? ring_load(A.g_v + (fr + i - 1) * N3, N, lane) : vzero();
             const Vec3x2 gq = A.g_q ? ring_load(A.g_q + (fr + i - 1) * N3, N, lane) : vzero();
             lv.x = lvh.x + gv.x; lv.y = lvh.y + gv.y; lv.z = lvh.z + gv.z;
@@ -953,6 +952,77 @@ void traj_adj_ring_kernel(const TrajArgs A, const RingRdfArgs F) {
             lq.z = (lqh.z + dq.z * h * 0.5f) + gq.z;
         }
     }
+}
+
+template <bool RDF, int KIND, bool MASK = false, int NT = 1, bool FT = false>
+__global__ __launch_bounds__(64 * ring_adj_waves(RDF, KIND))
+// (Morse: the widest single-term form sits at the edge of two waves per SIMD, 250-257 registers; the hint keeps it inside)
+__attribute__((amdgpu_waves_per_eu(ring_adj_parks(KIND, MASK, NT, FT) ? 3 : (KIND == MDG_PAIR_MORSE ? 2 : 1))))
+void traj_adj_ring_kernel(const TrajArgs A, const RingRdfArgs F) {
+    static_assert(NT == 1 || (MASK && KIND != KIND_TABLE), "several terms: masked built-in forms");
+    extern __shared__ __attribute__((aligned(16))) float smr[];
+    const int N = A.prm.n_atoms, T = A.prm.n_frames, C = A.prm.n_chains;
+    const bool nhc = A.prm.ensemble == 0;
+    constexpr int NWV = ring_adj_waves(RDF, KIND);
+    // (wid through readfirstlane: the compiler then knows the replica index -- and every frame address built on it -- to be
+    //  wave-uniform and keeps them in scalar registers)
+    const int wid = NWV > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0, lane = threadIdx.x & 63, N3 = 3 * N;
+    // (a wave beyond the last replica of the last workgroup repeats the last replica without accumulating or storing)
+    // (one wave per workgroup: `live` is a compile-time true, the code of round 4)
+    const bool live = NWV == 1 || (int)(blockIdx.x * NWV + wid) < A.prm.n_rep;
+    const int rep = NWV == 1 ? (int)blockIdx.x : (live ? (int)(blockIdx.x * NWV + wid) : A.prm.n_rep - 1);
+    RingLJ K[NT];
+    RingMask M[NT];
+#pragma unroll
+    for (int m = 0; m < NT; ++m) {
+        K[m] = ring_constants(A, m);
+        M[m] = RingMask{};
+        if constexpr (MASK) M[m] = ring_mask_load(A.terms.t[m].mask, N, lane);
+    }
+    RingRdf X{};
+    int ncell = 0;
+    if constexpr (RDF) {
+        // the cells of rdf_bwd_fine_kernel's table (8 per centre spacing over the same distances), equally spaced in d^2:
+        // one copy for the workgroup, loaded by all its waves
+        float hu;
+        rdf_u_grid(F.mu, F.nbins, F.reach_bins, X.ulo, hu, ncell);
+        float4* tab = reinterpret_cast<float4*>(smr);
+        for (int n = threadIdx.x; n < ncell; n += blockDim.x) tab[n] = F.tab[n];
+        X.tab = tab; X.inv_hu = 1.0f / hu;
+        X.tmax = fminf((float)ncell, (F.rc * F.rc - X.ulo) * X.inv_hu);
+        __syncthreads();
+    }
+    // per wave: the ring buffers (6 x 64 f32x2) and, where the kernel parks state, its slab behind them
+    f32x2* lds = reinterpret_cast<f32x2*>(smr + 4 * ncell) + wid * ring_adj_slab(ring_adj_parks(KIND, MASK, NT, FT));
+    if constexpr (KIND == KIND_TABLE) {
+        // the nodes and the workgroup's two gradient planes behind the waves' ring buffers (6 x 64 f32x2 each)
+        const MdgPairTerm& t0 = A.terms.t[0];
+        float2* ttab = reinterpret_cast<float2*>(smr + 4 * ncell + NWV * 6 * 64 * 2);
+        unsigned long long* tg = reinterpret_cast<unsigned long long*>(ttab + t0.p);        // [2 p] int64 words
+        int32_t* tflag = reinterpret_cast<int32_t*>(tg + 2 * t0.p);
+        const float* thp = A.theta + t0.theta_off;
+        for (int g = threadIdx.x; g < t0.p; g += blockDim.x) ttab[g] = make_float2(thp[2 * g], thp[2 * g + 1]);
+        for (int g = threadIdx.x; g < 2 * t0.p; g += blockDim.x) tg[g] = 0ull;
+        if (threadIdx.x == 0) *tflag = 0;
+        X.ttab = ttab; X.tg64 = tg; X.tflag = tflag; X.tgw = 0.f;
+        // one word can receive a contribution from every pair evaluation of the workgroup's replicas: one accumulating
+        // evaluation per interval, N (N - 1) / 2 pairs, two ends each
+        X.tlim = fx64_limit((double)NWV * (double)(T > 1 ? T - 1 : 1) * (double)N * (double)N);
+        X.tu0 = t0.a; X.tinv_du = 1.f / t0.phi; X.ttmax = (float)(t0.p - 1); X.tgmax = t0.p - 2;
+        __syncthreads();
+    }
+    const size_t fr = (size_t)rep * T;
+    // lam = dL/dy_{T-1}                                            sovlers.py:249
+    Vec3x2 lv = A.g_v ? ring_load(A.g_v + (fr + T - 1) * N3, N, lane) : vzero();
+    Vec3x2 lq = A.g_q ? ring_load(A.g_q + (fr + T - 1) * N3, N, lane) : vzero();
+    float lp = (nhc && lane < C && A.g_pv) ? A.g_pv[(fr + T - 1) * C + lane] : 0.f;
+    float gth[NT][MDG_MAX_THETA];
+#pragma unroll
+    for (int m = 0; m < NT; ++m)
+#pragma unroll
+        for (int k = 0; k < MDG_MAX_THETA; ++k) gth[m][k] = 0.f;
+    if (nhc) ring_adj_intervals<true, RDF, KIND, MASK, NT, FT>(A, F, K, X, M, live, fr, lane, lds, lv, lq, lp, gth);
+    else ring_adj_intervals<false, RDF, KIND, MASK, NT, FT>(A, F, K, X, M, live, fr, lane, lds, lv, lq, lp, gth);
     if constexpr (RDF) {
         if (ring_frame_selected(F, 0)) {                              // frame 0: no force evaluation there
             const Vec3x2 q = ring_load(A.q_t + fr * N3, N, lane), wu = vzero();
@@ -986,7 +1056,7 @@ void traj_adj_ring_kernel(const TrajArgs A, const RingRdfArgs F) {
         }
         return;
     }
-    if (lane == 0 && A.adj_theta) {
+    if (live && lane == 0 && A.adj_theta) {
 #pragma unroll
         for (int m = 0; m < NT; ++m) {
             float* out = A.adj_theta + (size_t)rep * A.terms.n_theta_total + A.terms.t[m].theta_off;

@@ -944,6 +944,12 @@ size_t ring_table_lds(const MdgTerms& terms, bool adjoint) {
 
 constexpr size_t RING_LDS_FWD = sizeof(f32x2) * 3 * 64;      // per wave: the visitors' positions
 constexpr size_t RING_LDS_ADJ = sizeof(f32x2) * 6 * 64;      //           ... and adjoint directions
+// per wave of the adjoint launch of these terms: the ring buffers and, where the kernel parks state across its sweeps
+// (ring_adj_parks: one unmasked LJ 12-6 term reading the forward's forces), the slab behind them
+size_t ring_adj_wave_lds(const MdgTerms& terms, bool ft) {
+    const bool parks = ring_adj_parks(ring_kind(terms.t[0]), terms.t[0].mask != nullptr, terms.n_terms, ft);
+    return sizeof(f32x2) * (size_t)ring_adj_slab(parks);
+}
 size_t ring_table_adj_lds(int nodes) { return RING_TABLE_WAVES * RING_LDS_ADJ + sizeof(float) * 6 * (size_t)nodes + 16; }
 constexpr int RING_RDF_WAVES = 16;                           // waves sharing the fine histogram of the fused RDF
 constexpr int RING_RDF_MAX_CELLS = 1088;                     // derivative table <= 17 KB: eight adjoint waves per CU
@@ -1195,7 +1201,7 @@ int traj_adj_small_run(const MdgTrajParams* prm, const MdgCell* cell, const MdgT
             // (tabulated kind: RING_TABLE_WAVES replicas per workgroup share the nodes and one pair of gradient planes)
             const bool rt = terms->t[0].kind == MDG_PAIR_TABLE;
             const int wpw = rt ? RING_TABLE_WAVES : 1;
-            const size_t lds = wpw * RING_LDS_ADJ + ring_table_lds(*terms, true);
+            const size_t lds = wpw * ring_adj_wave_lds(*terms, o.f_t != nullptr) + ring_table_lds(*terms, true);
             if (o.f_t)
                 MDG_RING_LAUNCH(traj_adj_ring_kernel, false, MDG_RING_FT, dim3((prm->n_rep + wpw - 1) / wpw), dim3(64 * wpw), lds,
                                 st, a, RingRdfArgs{});
@@ -1205,15 +1211,20 @@ int traj_adj_small_run(const MdgTrajParams* prm, const MdgCell* cell, const MdgT
             MDG_CHECK_LAUNCH("traj_adj_ring_kernel");
             return MDG_OK;
         }
+        // RING_RDF_ADJ_WAVES replicas per workgroup share the table: 14 KB + 4 x (3 KB + 6 KB parked state) = 50 KB at the
+        // headline's 100 bins -- three workgroups, twelve waves, in the CU's 160 KB (a table near RING_RDF_MAX_CELLS leaves two)
+        const int wpw = RING_RDF_ADJ_WAVES;
+        const size_t lds = sizeof(float4) * (size_t)P.ncell + wpw * ring_adj_wave_lds(*terms, o.f_t != nullptr);
+        MDG_CHECK_ARG(lds <= device_lds_per_block(), "%s: %zu bytes of LDS per workgroup exceed the device's limit", who, lds);
         float4* tab = nullptr;                                        // (stream-ordered scratch: no state, re-entrant)
         MDG_HIP(hipMallocAsync((void**)&tab, sizeof(float4) * (size_t)P.ncell, st));
         rc = mdg_rdf_bwd_table_u(o.rdf->mu, o.rdf->coeff, o.rdf->nbins, o.g_raw, P, tab, st);
         if (rc == MDG_OK) {
             RingRdfArgs F = ring_rdf_args(*o.rdf, P);
             F.tab = tab;
-            const size_t lds = sizeof(float4) * (size_t)P.ncell + RING_LDS_ADJ;
-            if (o.f_t) MDG_RING_LAUNCH(traj_adj_ring_kernel, true, MDG_RING_FT, dim3(prm->n_rep), dim3(64), lds, st, a, F);
-            else MDG_RING_LAUNCH(traj_adj_ring_kernel, true, , dim3(prm->n_rep), dim3(64), lds, st, a, F);
+            const dim3 grid((prm->n_rep + wpw - 1) / wpw), block(64 * wpw);
+            if (o.f_t) MDG_RING_LAUNCH(traj_adj_ring_kernel, true, MDG_RING_FT, grid, block, lds, st, a, F);
+            else MDG_RING_LAUNCH(traj_adj_ring_kernel, true, , grid, block, lds, st, a, F);
         }
         (void)hipFreeAsync(tab, st);
         if (rc) return rc;

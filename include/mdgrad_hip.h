@@ -873,6 +873,29 @@ int mdg_virial_bwd(const float* pos, int n_frames, int n_atoms, const MdgCell* c
                    const float* theta, const float* gW, float* g_pos, float* g_theta, float* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * K16  static structure factor S(k) of every frame and its gradient (mdgrad_amd/observable.py structure_factor; the
+ *      reference has none, the definition is this project's; csrc/sk.hip)
+ *   pos [n_frames, n_atoms, 3]; the cell must be diagonal, lengths L.  kvec int32 [n_vecs, 3]: integer wave vectors n,
+ *   k(n) = 2 pi (nx / Lx, ny / Ly, nz / Lz), |n_d| <= 1024, sorted by bin; seg int32 [n_bins + 1]: ascending offsets of the bins'
+ *   segments in kvec (seg[0] = 0, seg[n_bins] = n_vecs; an empty bin repeats an offset).  weights: nullable [n_atoms] (null =
+ *   unit weights); norm = sum_i w_i^2 (n_atoms for unit weights), formed by the caller.
+ *     rho_f(k) = sum_i w_i exp(i k.x_fi)     S_f(k) = |rho_f(k)|^2 / norm     S[f, b] = mean of S_f(k) over bin b (0 when empty)
+ *   fwd: S [n_frames, n_bins].
+ *   bwd: given gS [n_frames, n_bins] = dL/dS, writes g_pos [n_frames, n_atoms, 3]
+ *        = sum_k (gS[f, b(k)] / count_b) (2 w_i / norm) (Im rho cos k.x - Re rho sin k.x) k;  rho is recomputed per frame.
+ *   Phases are reduced in turns per axis before sine and cosine (positions many cells outside the box lose nothing).
+ *   List-free phase sums (a wave per frame up to 128 atoms, a workgroup per frame up to 1024, atom-block x vector-chunk tiles up
+ *   to 32 768); n_frames < 2^24, 1 <= n_vecs <= 65 536, 1 <= n_bins <= 1024.  workspace: mdg_sk_workspace() floats, shared by
+ *   both calls.  Fixed-order sums: bitwise reproducible.
+ */
+int64_t mdg_sk_workspace(int n_frames, int n_atoms, int n_vecs);
+int mdg_sk_fwd(const float* pos, int n_frames, int n_atoms, const MdgCell* cell /*host*/, const float* weights, float norm,
+               const int32_t* kvec, int n_vecs, const int32_t* seg, int n_bins, float* S, float* workspace, void* stream);
+int mdg_sk_bwd(const float* pos, int n_frames, int n_atoms, const MdgCell* cell /*host*/, const float* weights, float norm,
+               const int32_t* kvec, int n_vecs, const int32_t* seg, int n_bins, const float* gS, float* g_pos, float* workspace,
+               void* stream);
+
+/* ------------------------------------------------------------------------------------
  * f4  bonded terms over a static topology table (csrc/bonded.hip).
  * Replaces torchmd/interface.py:447-455 (BondPotentials.forward: harmonic in the SQUARED bond length,
  * 1/2 k (|b|^2 - ro)^2) and :496-508 (AnglePotentials.forward: 1/2 k (theta - theta0)^2 over triples (i, j, k) centred on

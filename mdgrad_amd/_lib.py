@@ -235,6 +235,9 @@ _SIGNATURES = {
     "mdg_virial_workspace": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "mdg_virial_fwd": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), C.POINTER(MdgTerms), P, P, P, P]),
     "mdg_virial_bwd": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), C.POINTER(MdgTerms), P, P, P, P, P, P]),
+    "mdg_sk_workspace": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "mdg_sk_fwd": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), P, C.c_float, P, C.c_int, P, C.c_int, P, P, P]),
+    "mdg_sk_bwd": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), P, C.c_float, P, C.c_int, P, C.c_int, P, P, P, P]),
     "mdg_bonded_eval": (C.c_int, [P, C.c_int, C.POINTER(C.c_float), C.c_int, P, C.c_int, C.c_float, C.c_float, P, P, P, P, P, P,
                                   C.c_float, C.c_int, P]),
 }

@@ -13,6 +13,7 @@
 //   rdf_fwd/rdf_bwd  K8   observable.py:62-76               -> mdg_rdf_fwd_uniform / mdg_rdf_bwd_uniform
 //   adf_fwd/adf_bwd  K14  observable.py:120-151             -> mdg_adf_fwd / mdg_adf_bwd
 //   virial_fwd/_bwd  K15  thermo.py Pressure (pair virial)   -> mdg_virial_fwd / mdg_virial_bwd
+//   sk_fwd/sk_bwd    K16  observable.py structure_factor     -> mdg_sk_fwd / mdg_sk_bwd
 //   edge_geom(+_bwd) schnet.py:142                          -> mdg_edge_geom / mdg_edge_geom_bwd
 //   cfconv_fwd/_bwd  K9+K10 modules.py:531-571              -> mdg_cfconv_fwd(_bf16) / mdg_cfconv_bwd(_bf16)
 //   dense_ssp        K11/12 layers.py:86-134                -> mdg_dense
@@ -340,6 +341,48 @@ std::tuple<Tensor, Tensor> virial_bwd(const Tensor& pos, at::ArrayRef<double> ce
     return {g, gth};
 }
 
+// ------------------------------------------------------------------------------------------------ K16
+// pos [F,N,3]; kvec int32 [M,3] sorted by bin, seg int32 [B+1] (its host copy seg_host gives the shapes a check without a
+// device read); weights [N] or none, norm = sum of the squared weights
+void sk_check(const Tensor& pos, const OptTensor& weights, const Tensor& kvec, const Tensor& seg, at::ArrayRef<int64_t> seg_host) {
+    check_f32(pos, "pos");
+    TORCH_CHECK(pos.dim() == 3 && pos.size(2) == 3, "mdgrad: pos must be [F,N,3]");
+    check_i32(kvec, "kvec"); check_i32(seg, "seg");
+    same_device(pos, kvec, "kvec"); same_device(pos, seg, "seg");
+    TORCH_CHECK(kvec.dim() == 2 && kvec.size(1) == 3, "mdgrad: kvec must be [M,3]");
+    TORCH_CHECK(seg_host.size() >= 2 && (int64_t)seg_host.size() == seg.numel(), "mdgrad: seg and seg_host must hold the same "
+                "n_bins + 1 offsets");
+    TORCH_CHECK(seg_host.front() == 0 && seg_host.back() == kvec.size(0), "mdgrad: the vector table kvec must hold seg[-1] = ",
+                seg_host.back(), " rows, got ", kvec.size(0));
+    for (size_t b = 1; b < seg_host.size(); ++b) TORCH_CHECK(seg_host[b] >= seg_host[b - 1], "mdgrad: seg must be ascending");
+    if (weights.has_value() && weights->defined()) {
+        TORCH_CHECK(weights->numel() == pos.size(1), "mdgrad: weights must hold one entry per atom");
+        same_device(pos, *weights, "weights");
+    }
+}
+Tensor sk_fwd(const Tensor& pos, at::ArrayRef<double> cell, const OptTensor& weights, double norm, const Tensor& kvec,
+              const Tensor& seg, at::ArrayRef<int64_t> seg_host) {
+    sk_check(pos, weights, kvec, seg, seg_host);
+    const MdgCell c = make_cell(cell);
+    const int F = (int)pos.size(0), N = (int)pos.size(1), M = (int)kvec.size(0), B = (int)seg.numel() - 1;
+    Tensor S = at::empty({F, B}, pos.options()), ws = at::empty({mdg_sk_workspace(F, N, M)}, pos.options());
+    ok(mdg_sk_fwd(fptr(pos), F, N, &c, fptr(weights, "weights"), (float)norm, kvec.data_ptr<int32_t>(), M, seg.data_ptr<int32_t>(),
+                  B, mptr(S), mptr(ws), stream_of(pos)));
+    return S;
+}
+Tensor sk_bwd(const Tensor& pos, at::ArrayRef<double> cell, const OptTensor& weights, double norm, const Tensor& kvec,
+              const Tensor& seg, at::ArrayRef<int64_t> seg_host, const Tensor& gS) {
+    sk_check(pos, weights, kvec, seg, seg_host);
+    check_f32(gS, "gS"); same_device(pos, gS, "gS");
+    const MdgCell c = make_cell(cell);
+    const int F = (int)pos.size(0), N = (int)pos.size(1), M = (int)kvec.size(0), B = (int)seg.numel() - 1;
+    TORCH_CHECK(gS.numel() == (int64_t)F * B, "mdgrad: gS must be [F,B]");
+    Tensor g = at::empty_like(pos), ws = at::empty({mdg_sk_workspace(F, N, M)}, pos.options());
+    ok(mdg_sk_bwd(fptr(pos), F, N, &c, fptr(weights, "weights"), (float)norm, kvec.data_ptr<int32_t>(), M, seg.data_ptr<int32_t>(),
+                  B, fptr(gS), mptr(g), mptr(ws), stream_of(pos)));
+    return g;
+}
+
 // ------------------------------------------------------------------------------------------------ SchNet block
 MdgFilterNet filter_net(const Tensor& mu, const Tensor& coef, const Tensor& W1, const Tensor& b1, const Tensor& W2,
                         const Tensor& b2) {
@@ -504,6 +547,9 @@ TORCH_LIBRARY(mdgrad, m) {
     m.def("virial_fwd(Tensor pos, float[] cell, int[] terms_i, float[] terms_f, Tensor?[] masks, Tensor? theta) -> Tensor");
     m.def("virial_bwd(Tensor pos, float[] cell, int[] terms_i, float[] terms_f, Tensor?[] masks, Tensor? theta, Tensor gW) -> "
           "(Tensor, Tensor)");
+    m.def("sk_fwd(Tensor pos, float[] cell, Tensor? weights, float norm, Tensor kvec, Tensor seg, int[] seg_host) -> Tensor");
+    m.def("sk_bwd(Tensor pos, float[] cell, Tensor? weights, float norm, Tensor kvec, Tensor seg, int[] seg_host, Tensor gS) -> "
+          "Tensor");
     m.def("edge_geom(Tensor x, Tensor? w, Tensor nbr, Tensor offsets) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("edge_geom_bwd(Tensor? d_b, Tensor dd_b, Tensor? d, Tensor? dd, Tensor uhat, Tensor? ddel, Tensor col, Tensor eid, "
           "Tensor cnt) -> (Tensor, Tensor)");
@@ -530,6 +576,8 @@ TORCH_LIBRARY_IMPL(mdgrad, CUDA, m) {      // (the HIP backend registers under t
     m.impl("adf_bwd", adf_bwd);
     m.impl("virial_fwd", virial_fwd);
     m.impl("virial_bwd", virial_bwd);
+    m.impl("sk_fwd", sk_fwd);
+    m.impl("sk_bwd", sk_bwd);
     m.impl("edge_geom", edge_geom);
     m.impl("edge_geom_bwd", edge_geom_bwd);
     m.impl("cfconv_fwd", cfconv_fwd);

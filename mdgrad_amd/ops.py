@@ -6,6 +6,7 @@ torch.autograd.Function wrappers that own the differentiation contract
     RdfRawFn                                                    soft histogram
     AdfRawFn                                                    soft histogram of bond angles
     VirialFn                                                    pair virial of every frame (pressure)
+    SkFn                                                        static structure factor of every frame
 
 Everything here requires HIP tensors; there is no CPU path.
 """
@@ -941,6 +942,43 @@ class VirialFn(torch.autograd.Function):
         check(lib.mdg_virial_bwd(ptr(x3), F, N, C.byref(cell_struct), C.byref(terms), ptr(th) if K else None, ptr(g), ptr(gx),
                                  ptr(gth), ptr(ws), stream_ptr(x3.device)), "mdg_virial_bwd")
         return gx.reshape(xshape), (gth.reshape(tshape) if K else None), None, None, None
+
+
+# ----------------------------------------------------------------------------- static structure factor
+class SkFn(torch.autograd.Function):
+    """S[f, b] = mean over bin b of |sum_i w_i exp(i k.x_fi)|^2 / norm for every frame of xyz [F, N, 3] (csrc/sk.hip, K16):
+    the kernel side of observable.structure_factor.  kvec int32 [M, 3] (integer wave vectors sorted by bin) and seg int32
+    [B + 1] (the bins' segment offsets) live on the device; weights [N] or None, norm = sum of the squared weights.  The
+    weights and wave vectors are constants; differentiable once with respect to the positions (rho is recomputed)."""
+
+    @staticmethod
+    def forward(ctx, xyz, cell_struct, weights, norm, kvec, seg):
+        lib = _lib.load()
+        require_gpu(xyz, "xyz")
+        x3 = xyz.detach()
+        x3 = x3 if x3.is_contiguous() else x3.contiguous()
+        F, N, M, B = x3.shape[0], x3.shape[1], kvec.shape[0], seg.numel() - 1
+        ws = torch.empty(int(lib.mdg_sk_workspace(F, N, M)), device=x3.device)
+        S = torch.empty(F, B, device=x3.device)
+        check(lib.mdg_sk_fwd(ptr(x3), F, N, C.byref(cell_struct), ptr(weights), float(norm), ptr(kvec), M, ptr(seg), B, ptr(S),
+                             ptr(ws), stream_ptr(x3.device)), "mdg_sk_fwd")
+        ctx.args = (cell_struct, weights, norm, kvec, seg, xyz.shape)
+        ctx.save_for_backward(x3)
+        return S
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gS):
+        lib = _lib.load()
+        (x3,) = ctx.saved_tensors
+        cell_struct, weights, norm, kvec, seg, xshape = ctx.args
+        F, N, M, B = x3.shape[0], x3.shape[1], kvec.shape[0], seg.numel() - 1
+        g = gS.detach().to(torch.float32).contiguous()
+        ws = torch.empty(int(lib.mdg_sk_workspace(F, N, M)), device=x3.device)
+        gx = torch.empty_like(x3)
+        check(lib.mdg_sk_bwd(ptr(x3), F, N, C.byref(cell_struct), ptr(weights), float(norm), ptr(kvec), M, ptr(seg), B, ptr(g),
+                             ptr(gx), ptr(ws), stream_ptr(x3.device)), "mdg_sk_bwd")
+        return gx.reshape(xshape), None, None, None, None, None
 
 
 # ----------------------------------------------------------------------------- velocity observables

@@ -896,6 +896,33 @@ int mdg_sk_bwd(const float* pos, int n_frames, int n_atoms, const MdgCell* cell 
                void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * K17  mean-squared displacement of a trajectory over all lags, its fourth moment and their gradient
+ *      (mdgrad_amd/observable.py msd; the reference has none, the definition is this project's; csrc/msd.hip)
+ *   x [n_batch, n_frames, n_cols, 3], one continuous (unwrapped) trajectory per batch entry; the n_cols columns are
+ *   n_cols / group replicas of `group` atoms each, and replica c / group of batch b owns output row
+ *   b * (n_cols / group) + c / group.  weights: nullable [group], w_i >= 0 and not all zero (null = unit weights).
+ *   With T = n_frames, s = origin_stride and the origins O_tau = {t0 = 0, s, 2 s, ... : t0 + tau < T}, per row
+ *     M_p[tau] = 1 / (|O_tau| sum_i w_i)  sum_{t0 in O_tau} sum_i w_i |x_i(t0 + tau) - x_i(t0)|^p ,  tau = 0 .. n_lags - 1
+ *   All three components, no cell, no re-imaging.  M_p[0] is exactly 0.
+ *   fwd: out2 [rows, n_lags] (p = 2) and, unless null, out4 [rows, n_lags] (p = 4).
+ *   bwd: given g2 [rows, n_lags] = dL/dM_2 and g4 (nullable) = dL/dM_4, writes every element of gx [n_batch, n_frames,
+ *        n_cols, 3] once:  gx_i(t) = w_i sum_tau [ (t - tau in O_tau) f(x_t - x_{t-tau}) - (t in O_tau, t + tau < T)
+ *        f(x_{t+tau} - x_t) ],  f(d) = (2 g2_tau + 4 g4_tau |d|^2) d / (|O_tau| sum w).
+ *   Every position is read from device memory once: a workgroup walks through time with a ring of frames of its atom tile
+ *   in LDS and takes all lags from it.  1 <= n_lags <= min(n_frames, 1024), origin_stride >= 1, n_cols % group == 0.
+ *   workspace: mdg_msd_workspace() floats, enough for either call.  Fixed-order sums, no floating-point atomics: bitwise
+ *   reproducible.  mdg_msd_tile_atoms / _window / _max_lags: the forward's atom tile (16), frame window (16) and the lag limit.
+ */
+int64_t mdg_msd_workspace(int n_batch, int n_cols, int group, int n_lags, int fourth);
+int mdg_msd_fwd(const float* x, int n_batch, int n_frames, int n_cols, int group, const float* weights, int n_lags,
+                int origin_stride, float* out2, float* out4, float* workspace, void* stream);
+int mdg_msd_bwd(const float* x, int n_batch, int n_frames, int n_cols, int group, const float* weights, int n_lags,
+                int origin_stride, const float* g2, const float* g4, float* gx, float* workspace, void* stream);
+int mdg_msd_tile_atoms(void);
+int mdg_msd_window(void);
+int mdg_msd_max_lags(void);
+
+/* ------------------------------------------------------------------------------------
  * f4  bonded terms over a static topology table (csrc/bonded.hip).
  * Replaces torchmd/interface.py:447-455 (BondPotentials.forward: harmonic in the SQUARED bond length,
  * 1/2 k (|b|^2 - ro)^2) and :496-508 (AnglePotentials.forward: 1/2 k (theta - theta0)^2 over triples (i, j, k) centred on

@@ -238,6 +238,12 @@ _SIGNATURES = {
     "mdg_sk_workspace": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "mdg_sk_fwd": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), P, C.c_float, P, C.c_int, P, C.c_int, P, P, P]),
     "mdg_sk_bwd": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), P, C.c_float, P, C.c_int, P, C.c_int, P, P, P, P]),
+    "mdg_msd_workspace": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mdg_msd_fwd": (C.c_int, [P, C.c_int, C.c_int, C.c_int, C.c_int, P, C.c_int, C.c_int, P, P, P, P]),
+    "mdg_msd_bwd": (C.c_int, [P, C.c_int, C.c_int, C.c_int, C.c_int, P, C.c_int, C.c_int, P, P, P, P, P]),
+    "mdg_msd_tile_atoms": (C.c_int, []),
+    "mdg_msd_window": (C.c_int, []),
+    "mdg_msd_max_lags": (C.c_int, []),
     "mdg_bonded_eval": (C.c_int, [P, C.c_int, C.POINTER(C.c_float), C.c_int, P, C.c_int, C.c_float, C.c_float, P, P, P, P, P, P,
                                   C.c_float, C.c_int, P]),
 }

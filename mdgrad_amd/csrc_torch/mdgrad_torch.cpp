@@ -14,6 +14,7 @@
 //   adf_fwd/adf_bwd  K14  observable.py:120-151             -> mdg_adf_fwd / mdg_adf_bwd
 //   virial_fwd/_bwd  K15  thermo.py Pressure (pair virial)   -> mdg_virial_fwd / mdg_virial_bwd
 //   sk_fwd/sk_bwd    K16  observable.py structure_factor     -> mdg_sk_fwd / mdg_sk_bwd
+//   msd_fwd/msd_bwd  K17  observable.py msd                  -> mdg_msd_fwd / mdg_msd_bwd
 //   edge_geom(+_bwd) schnet.py:142                          -> mdg_edge_geom / mdg_edge_geom_bwd
 //   cfconv_fwd/_bwd  K9+K10 modules.py:531-571              -> mdg_cfconv_fwd(_bf16) / mdg_cfconv_bwd(_bf16)
 //   dense_ssp        K11/12 layers.py:86-134                -> mdg_dense
@@ -22,6 +23,7 @@
 #include <c10/hip/HIPStream.h>
 #include <torch/library.h>
 
+#include <algorithm>
 #include <tuple>
 #include <vector>
 
@@ -383,6 +385,51 @@ Tensor sk_bwd(const Tensor& pos, at::ArrayRef<double> cell, const OptTensor& wei
     return g;
 }
 
+// ------------------------------------------------------------------------------------------------ K17
+// x [n_batch,T,n_cols,3]; the columns are n_cols / group replicas of `group` atoms; weights [group] or none
+void msd_check(const Tensor& x, int64_t group, const OptTensor& weights, int64_t n_lags, int64_t origin_stride) {
+    check_f32(x, "x");
+    TORCH_CHECK(x.dim() == 4 && x.size(3) == 3, "mdgrad: x must be [n_batch,T,n_cols,3]");
+    TORCH_CHECK(group >= 1 && x.size(2) % group == 0, "mdgrad: the columns of x (", x.size(2), ") must be a multiple of group (",
+                group, ")");
+    TORCH_CHECK(n_lags >= 1 && n_lags <= x.size(1), "mdgrad: 1 <= n_lags <= T (got ", n_lags, ", ", x.size(1), ")");
+    TORCH_CHECK(origin_stride >= 1 && origin_stride <= INT32_MAX, "mdgrad: origin_stride must be >= 1");
+    TORCH_CHECK(x.size(0) <= INT32_MAX && x.size(1) <= INT32_MAX && x.size(2) <= INT32_MAX, "mdgrad: x is too large");
+    if (weights.has_value() && weights->defined()) {
+        TORCH_CHECK(weights->numel() == group, "mdgrad: weights must hold one entry per atom of a replica (", group, ")");
+        same_device(x, *weights, "weights");
+    }
+}
+std::tuple<Tensor, Tensor> msd_fwd(const Tensor& x, int64_t group, const OptTensor& weights, int64_t n_lags, int64_t origin_stride,
+                                   bool fourth) {
+    msd_check(x, group, weights, n_lags, origin_stride);
+    const int nb = (int)x.size(0), T = (int)x.size(1), nc = (int)x.size(2);
+    const int64_t rows = (int64_t)nb * (nc / group);
+    Tensor m2 = at::empty({rows, n_lags}, x.options()), m4 = at::empty({fourth ? rows : 0, n_lags}, x.options());
+    Tensor ws = at::empty({std::max<int64_t>(mdg_msd_workspace(nb, nc, (int)group, (int)n_lags, fourth), 2)}, x.options());
+    ok(mdg_msd_fwd(fptr(x), nb, T, nc, (int)group, fptr(weights, "weights"), (int)n_lags, (int)origin_stride, mptr(m2),
+                   fourth ? mptr(m4) : nullptr, mptr(ws), stream_of(x)));
+    return {m2, m4};
+}
+Tensor msd_bwd(const Tensor& x, int64_t group, const OptTensor& weights, int64_t n_lags, int64_t origin_stride, const Tensor& g2,
+               const OptTensor& g4) {
+    msd_check(x, group, weights, n_lags, origin_stride);
+    check_f32(g2, "g2"); same_device(x, g2, "g2");
+    const int nb = (int)x.size(0), T = (int)x.size(1), nc = (int)x.size(2);
+    const int64_t rows = (int64_t)nb * (nc / group);
+    TORCH_CHECK(g2.numel() == rows * n_lags, "mdgrad: g2 must be [rows,n_lags]");
+    const bool fourth = g4.has_value() && g4->defined();
+    if (fourth) {
+        TORCH_CHECK(g4->numel() == rows * n_lags, "mdgrad: g4 must be [rows,n_lags]");
+        same_device(x, *g4, "g4");
+    }
+    Tensor gx = at::empty_like(x);
+    Tensor ws = at::empty({std::max<int64_t>(mdg_msd_workspace(nb, nc, (int)group, (int)n_lags, fourth), 2)}, x.options());
+    ok(mdg_msd_bwd(fptr(x), nb, T, nc, (int)group, fptr(weights, "weights"), (int)n_lags, (int)origin_stride, fptr(g2),
+                   fptr(g4, "g4"), mptr(gx), mptr(ws), stream_of(x)));
+    return gx;
+}
+
 // ------------------------------------------------------------------------------------------------ SchNet block
 MdgFilterNet filter_net(const Tensor& mu, const Tensor& coef, const Tensor& W1, const Tensor& b1, const Tensor& W2,
                         const Tensor& b2) {
@@ -550,6 +597,8 @@ TORCH_LIBRARY(mdgrad, m) {
     m.def("sk_fwd(Tensor pos, float[] cell, Tensor? weights, float norm, Tensor kvec, Tensor seg, int[] seg_host) -> Tensor");
     m.def("sk_bwd(Tensor pos, float[] cell, Tensor? weights, float norm, Tensor kvec, Tensor seg, int[] seg_host, Tensor gS) -> "
           "Tensor");
+    m.def("msd_fwd(Tensor x, int group, Tensor? weights, int n_lags, int origin_stride, bool fourth) -> (Tensor, Tensor)");
+    m.def("msd_bwd(Tensor x, int group, Tensor? weights, int n_lags, int origin_stride, Tensor g2, Tensor? g4) -> Tensor");
     m.def("edge_geom(Tensor x, Tensor? w, Tensor nbr, Tensor offsets) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("edge_geom_bwd(Tensor? d_b, Tensor dd_b, Tensor? d, Tensor? dd, Tensor uhat, Tensor? ddel, Tensor col, Tensor eid, "
           "Tensor cnt) -> (Tensor, Tensor)");
@@ -578,6 +627,8 @@ TORCH_LIBRARY_IMPL(mdgrad, CUDA, m) {      // (the HIP backend registers under t
     m.impl("virial_bwd", virial_bwd);
     m.impl("sk_fwd", sk_fwd);
     m.impl("sk_bwd", sk_bwd);
+    m.impl("msd_fwd", msd_fwd);
+    m.impl("msd_bwd", msd_bwd);
     m.impl("edge_geom", edge_geom);
     m.impl("edge_geom_bwd", edge_geom_bwd);
     m.impl("cfconv_fwd", cfconv_fwd);

@@ -4,7 +4,9 @@ histogram of rdf.forward is one HIP op (ops.RdfRawFn, csrc/rdf.hip); vacf is one
 velocity trajectory (ops.VacfFn, csrc/observe.hip).  angle_distribution :120-151 (with Angles :89-118 and
 compute_angle :166-179): the triplet search + Gaussian smearing + histogram and its gradient are one HIP op
 (ops.AdfRawFn, csrc/adf.hip); the per-triplet angles are torch ops over the device-built angle list.  structure_factor has no
-counterpart in the reference: the static structure factor S(k) over the cell's own wave vectors (ops.SkFn, csrc/sk.hip)."""
+counterpart in the reference: the static structure factor S(k) over the cell's own wave vectors (ops.SkFn, csrc/sk.hip).  Nor
+has msd: the mean-squared displacement over all lags and time origins with its fourth moment (ops.MsdFn, csrc/msd.hip), and
+diffusion_coefficient, the Einstein slope of it."""
 import math
 import warnings
 
@@ -320,6 +322,120 @@ class structure_factor(Observable):
 
     def forward(self, xyz):
         return self.k, self.per_frame(xyz).reshape(-1, self.nbins).mean(0)
+
+
+MSD_MAX_LAGS = 1024                                                    # csrc/msd.hip
+
+
+class msd(Observable):
+    """Mean-squared displacement over all lags and time origins, optionally with the fourth moment (no counterpart in the
+    reference).
+
+    For one replica of T frames, real per-atom weights w_i >= 0 (default 1), s = origin_stride and the time origins
+    O_tau = {t0 = 0, s, 2 s, ... : t0 + tau < T}, the moments of order p = 2 and 4 are
+
+        M_p[tau] = 1 / (|O_tau| sum_i w_i)  sum_{t0 in O_tau} sum_i w_i |x_i(t0 + tau) - x_i(t0)|^p ,   tau = 0 .. t_range - 1
+
+    (the lag convention of vacf: t_range lags, the first is 0, and M_p[0] is exactly 0).  The positions are taken as given:
+    all three components are used and nothing is re-imaged, so q_t has to be ONE continuous, unwrapped trajectory -- what a
+    single simulate / odeint_adjoint call returns (the fused trajectories do not wrap inside a call), not frames concatenated
+    across epochs, between which Simulations.simulate wraps the positions into the cell.
+
+    index_tuple selects atoms: a list of atom indices, or the pair form of the other observables (two lists), meaning their
+    union; it is shorthand for 0/1 weights, so a per-species MSD is one call.  weights and index_tuple multiply.  The weights
+    are constants (no gradient).
+
+    forward(q_t) -> M_2 [t_range], the mean over the replicas.  per_replica(q_t) keeps them: [T, N, 3] -> [t_range],
+    [R, T, N, 3] -> [R, t_range] (time is dim -3), replica-stacked [T, k N, 3] -> [k, t_range] and [R, T, k N, 3] ->
+    [R, k, t_range].  With fourth_moment=True: moments(q_t) -> (M_2, M_4), moments_per_replica(q_t) likewise, and
+    non_gaussian(q_t) -> alpha_2 = d M_4 / ((d + 2) M_2^2) - 1 with d = system.dim, 0 where M_2 is 0 (lag 0).
+    diffusion_coefficient(m, dt) turns M_2 into the Einstein estimate of D.
+
+    HIP kernels forward and backward (ops.MsdFn, csrc/msd.hip): every position is read once, whatever t_range is.
+    Differentiable once with respect to the positions; t_range <= 1024."""
+
+    def __init__(self, system, t_range, index_tuple=None, weights=None, origin_stride=1, fourth_moment=False):
+        super().__init__(system)
+        if not (isinstance(t_range, (int, np.integer)) and 1 <= int(t_range) <= MSD_MAX_LAGS):
+            raise ValueError("msd: t_range must be an integer in 1..%d, got %r" % (MSD_MAX_LAGS, t_range))
+        if not (isinstance(origin_stride, (int, np.integer)) and int(origin_stride) >= 1):
+            raise ValueError("msd: origin_stride must be an integer >= 1, got %r" % (origin_stride,))
+        self.t_range, self.origin_stride, self.fourth_moment = int(t_range), int(origin_stride), bool(fourth_moment)
+        self.dim = getattr(system, "dim", 3)
+        self.index_tuple = index_tuple
+        w = None
+        if weights is not None:
+            w = torch.as_tensor(weights, dtype=torch.float32).detach().reshape(-1).cpu()
+            if w.numel() != self.natoms:
+                raise ValueError("msd: weights must hold one entry per atom (%d), got %d" % (self.natoms, w.numel()))
+            if not (bool(torch.isfinite(w).all()) and bool((w >= 0).all())):
+                raise ValueError("msd: weights must be finite and non-negative")
+        if index_tuple is not None:
+            idx = list(index_tuple)
+            if len(idx) and not isinstance(idx[0], (int, np.integer)):            # the pair form: the union of both lists
+                idx = [i for part in idx for i in list(part)]
+            sel = torch.as_tensor(np.asarray(idx, dtype=np.int64)).reshape(-1)
+            if sel.numel() == 0 or int(sel.min()) < 0 or int(sel.max()) >= self.natoms:
+                raise ValueError("msd: index_tuple must name atoms in 0..%d, got %r" % (self.natoms - 1, index_tuple))
+            mask = torch.zeros(self.natoms)
+            mask[sel] = 1.0
+            w = mask if w is None else w * mask
+        if w is not None and not float(w.double().sum()) > 0:
+            raise ValueError("msd: the weights%s must not all be zero" % (" (with index_tuple applied)" if index_tuple is not None else ""))
+        self.weights = None if w is None else w.contiguous().to(self.device)
+
+    def _batch(self, x):
+        if x.dim() not in (3, 4) or x.shape[-1] != 3 or x.shape[-2] == 0 or x.shape[-2] % self.natoms:
+            raise ValueError("msd: q_t must be [T, k * %d, 3] or [R, T, k * %d, 3], got %s" % (self.natoms, self.natoms, tuple(x.shape)))
+        if self.t_range > x.shape[-3]:
+            raise ValueError("msd: t_range = %d exceeds the %d frames of q_t" % (self.t_range, x.shape[-3]))
+        k = x.shape[-2] // self.natoms
+        lead = (tuple(x.shape[:-3]) + ((k,) if k > 1 else ()))
+        return (x if x.dim() == 4 else x.unsqueeze(0)), lead
+
+    def moments_per_replica(self, q_t):
+        """(M_2, M_4) of every replica (M_4 is None without fourth_moment), shaped as per_replica."""
+        x, lead = self._batch(q_t)
+        m2, m4 = ops.MsdFn.apply(x, self.natoms, self.weights, self.t_range, self.origin_stride, self.fourth_moment)
+        return m2.reshape(lead + (self.t_range,)), (m4.reshape(lead + (self.t_range,)) if m4 is not None else None)
+
+    def per_replica(self, q_t):
+        """M_2 of every replica: [t_range], [R, t_range], [k, t_range] or [R, k, t_range]."""
+        return self.moments_per_replica(q_t)[0]
+
+    def moments(self, q_t):
+        """(M_2, M_4), each [t_range], averaged over the replicas; needs fourth_moment=True."""
+        if not self.fourth_moment:
+            raise ValueError("msd: moments / non_gaussian need fourth_moment=True")
+        m2, m4 = self.moments_per_replica(q_t)
+        return m2.reshape(-1, self.t_range).mean(0), m4.reshape(-1, self.t_range).mean(0)
+
+    def non_gaussian(self, q_t):
+        """alpha_2[tau] = d M_4 / ((d + 2) M_2^2) - 1 from the replica-averaged moments; 0 where M_2 = 0 (lag 0)."""
+        m2, m4 = self.moments(q_t)
+        ok = m2 > 0
+        safe = torch.where(ok, m2, torch.ones_like(m2))
+        return torch.where(ok, self.dim * m4 / ((self.dim + 2) * safe * safe) - 1.0, torch.zeros_like(m2))
+
+    def forward(self, q_t):
+        return self.per_replica(q_t).reshape(-1, self.t_range).mean(0)
+
+
+def diffusion_coefficient(m, dt, fit_range=None, dim=3):
+    """Einstein estimate D = slope / (2 dim): the least-squares slope of m[..., a:b] against tau * dt over the lags
+    tau = a .. b - 1 of fit_range = (a, b) (default: every lag), in closed form,
+
+        slope = sum_tau (tau - mean tau) m[tau] / (dt sum_tau (tau - mean tau)^2)
+
+    so it is differentiable in m and works on any leading batch shape.  m [..., L] is what msd returns (lag tau at index tau)."""
+    L = m.shape[-1]
+    a, b, _ = slice(*(fit_range if fit_range is not None else (0, L))).indices(L)
+    if b - a < 2:
+        raise ValueError("diffusion_coefficient: fit_range = %r selects %d of the %d lags; a slope needs two"
+                         % (fit_range, max(b - a, 0), L))
+    tau = torch.arange(a, b, device=m.device, dtype=m.dtype)
+    c = tau - tau.mean()
+    return (m[..., a:b] * (c / (c.pow(2).sum() * dt))).sum(-1) / (2 * dim)
 
 
 class vacf(Observable):

@@ -7,6 +7,7 @@ torch.autograd.Function wrappers that own the differentiation contract
     AdfRawFn                                                    soft histogram of bond angles
     VirialFn                                                    pair virial of every frame (pressure)
     SkFn                                                        static structure factor of every frame
+    MsdFn                                                       mean-squared displacement over all lags (+ fourth moment)
 
 Everything here requires HIP tensors; there is no CPU path.
 """
@@ -1007,6 +1008,56 @@ class VacfFn(torch.autograd.Function):
         check(lib.mdg_vacf_bwd(ptr(v), ptr(gc), v.shape[0], v[0].numel(), ctx.n_lags, ptr(gv), stream_ptr(v.device)),
               "mdg_vacf_bwd")
         return gv, None
+
+
+class MsdFn(torch.autograd.Function):
+    """M_2[row, tau] (and M_4 with fourth=True) of x [n_batch, T, n_cols, 3] over the lags tau = 0 .. n_lags-1 (csrc/msd.hip,
+    K17): the kernel side of observable.msd.  The n_cols columns are n_cols / group replicas of `group` atoms; row =
+    batch * (n_cols / group) + replica.  weights [group] on the device or None; a constant.  Returns (M_2, M_4 or None), each
+    [rows, n_lags].  Differentiable once with respect to the positions.  The torch.ops layer serves it when it is loaded
+    (_torch_ops.get()), the ctypes bindings otherwise: the same kernels either way."""
+
+    @staticmethod
+    def forward(ctx, x, group, weights, n_lags, origin_stride, fourth):
+        require_gpu(x, "x")
+        x4 = x.detach()
+        x4 = x4 if x4.is_contiguous() else x4.contiguous()
+        nb, T, nc = x4.shape[0], x4.shape[1], x4.shape[2]
+        tops = _torch_ops.get()
+        if tops is not None:
+            m2, m4 = tops.msd_fwd(x4, int(group), weights, int(n_lags), int(origin_stride), bool(fourth))
+            m4 = m4 if fourth else None                     # (the op returns an empty tensor there)
+        else:
+            lib = _lib.load()
+            rows = nb * (nc // group if group > 0 and nc % group == 0 else 0)
+            m2 = torch.empty(rows, n_lags, device=x4.device)
+            m4 = torch.empty(rows, n_lags, device=x4.device) if fourth else None
+            ws = torch.empty(max(int(lib.mdg_msd_workspace(nb, nc, group, n_lags, int(fourth))), 2), device=x4.device)
+            check(lib.mdg_msd_fwd(ptr(x4), nb, T, nc, group, ptr(weights), n_lags, origin_stride, ptr(m2), ptr(m4), ptr(ws),
+                                  stream_ptr(x4.device)), "mdg_msd_fwd")
+        ctx.args = (group, weights, n_lags, origin_stride, fourth, x.shape)
+        ctx.save_for_backward(x4)
+        return m2, m4
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g2, g4):
+        (x4,) = ctx.saved_tensors
+        group, weights, n_lags, origin_stride, fourth, xshape = ctx.args
+        nb, T, nc = x4.shape[0], x4.shape[1], x4.shape[2]
+        rows = nb * (nc // group)
+        g2 = (torch.zeros(rows, n_lags, device=x4.device) if g2 is None else g2.detach().to(torch.float32).contiguous())
+        g4 = None if (not fourth or g4 is None) else g4.detach().to(torch.float32).contiguous()
+        tops = _torch_ops.get()
+        if tops is not None:
+            gx = tops.msd_bwd(x4, int(group), weights, int(n_lags), int(origin_stride), g2, g4)
+        else:
+            lib = _lib.load()
+            gx = torch.empty_like(x4)
+            ws = torch.empty(max(int(lib.mdg_msd_workspace(nb, nc, group, n_lags, int(fourth))), 2), device=x4.device)
+            check(lib.mdg_msd_bwd(ptr(x4), nb, T, nc, group, ptr(weights), n_lags, origin_stride, ptr(g2), ptr(g4), ptr(gx),
+                                  ptr(ws), stream_ptr(x4.device)), "mdg_msd_bwd")
+        return gx.reshape(xshape), None, None, None, None, None
 
 
 class TemperatureFn(torch.autograd.Function):

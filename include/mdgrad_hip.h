@@ -923,6 +923,44 @@ int mdg_msd_window(void);
 int mdg_msd_max_lags(void);
 
 /* ------------------------------------------------------------------------------------
+ * K18  intermediate scattering functions of a trajectory over all lags, coherent F(k,t) and self F_s(k,t), and their gradient
+ *      (mdgrad_amd/observable.py intermediate_scattering; the reference has none, the definition is this project's;
+ *      csrc/isf.hip)
+ *   x [n_batch, n_frames, n_cols, 3]; the n_cols columns are n_cols / group replicas of `group` atoms each.  One call takes the
+ *   replicas rep0 .. rep0 + n_reps - 1 of every batch entry (callers chunk the rows that way to bound the workspace); replica r
+ *   of batch b owns output row b * n_reps + (r - rep0).  cell: diagonal, positive lengths L.  weights: nullable [group]
+ *   (null = unit weights), norm = W2 = sum_i w_i^2 > 0.  kvec int32 [n_vecs, 3] and seg int32 [n_bins + 1] as in K16.
+ *   kind: 0 coherent, 1 self.  With T = n_frames, s = origin_stride, O_tau = {t0 = 0, s, 2 s, ... : t0 + tau < T}, per row
+ *     rho(k, t)   = sum_i w_i exp(i k.x_i(t))
+ *     F(k, tau)   = 1 / (|O_tau| W2)  sum_{t0 in O_tau} Re[ rho(k, t0 + tau) conj rho(k, t0) ]
+ *     F_s(k, tau) = 1 / (|O_tau| W2)  sum_{t0 in O_tau} sum_i w_i^2 cos( k.(x_i(t0 + tau) - x_i(t0)) ) ,  tau = 0 .. n_lags - 1
+ *   and F[b, tau] = the mean over the vectors of bin b (0 for an empty bin).
+ *   fwd: F [rows, n_bins, n_lags].
+ *   bwd: given gF [rows, n_bins, n_lags] = dL/dF, writes every element of gx that belongs to the call's replicas once (the
+ *        other columns are not touched); an atom of weight 0 gets exactly 0.
+ *   Coherent: rho of every (frame, vector) goes to the workspace, the origin sums run in double.  Self: one sine / cosine pair
+ *   per (frame, atom, vector); a workgroup walks through time with a ring of phasors in LDS and takes all lags from it.
+ *   1 <= n_lags <= min(n_frames, mdg_isf_max_lags()), origin_stride >= 1, n_cols % group == 0, 1 <= n_vecs <= 65 536,
+ *   1 <= n_bins <= 1024, coherent: group <= 32 768.  workspace: mdg_isf_workspace(kind, n_batch * n_reps, ...) floats (never
+ *   null: pass one float where it returns 0), enough for either call:
+ *     self      rows * n_vecs * n_lags * ceil(group / 16)
+ *     coherent  2 * rows * n_vecs * (n_frames * ceil(group / 1024) + max(n_lags, n_frames))
+ *   Fixed-order sums, no floating-point atomics: bitwise reproducible, and a row's result does not depend on which other rows
+ *   share its call.  mdg_isf_max_lags / _tile_atoms / _window: the lag limit and the self forward's atom tile and frame window.
+ */
+int64_t mdg_isf_workspace(int kind, int64_t n_rows, int n_frames, int group, int n_vecs, int n_lags);
+int mdg_isf_fwd(int kind, const float* x, int n_batch, int n_frames, int n_cols, int group, int rep0, int n_reps,
+                const MdgCell* cell /*host*/, const float* weights, double norm, const int32_t* kvec, int n_vecs,
+                const int32_t* seg, int n_bins, int n_lags, int origin_stride, float* F, float* workspace, void* stream);
+int mdg_isf_bwd(int kind, const float* x, int n_batch, int n_frames, int n_cols, int group, int rep0, int n_reps,
+                const MdgCell* cell /*host*/, const float* weights, double norm, const int32_t* kvec, int n_vecs,
+                const int32_t* seg, int n_bins, int n_lags, int origin_stride, const float* gF, float* gx, float* workspace,
+                void* stream);
+int mdg_isf_max_lags(void);
+int mdg_isf_tile_atoms(void);
+int mdg_isf_window(void);
+
+/* ------------------------------------------------------------------------------------
  * f4  bonded terms over a static topology table (csrc/bonded.hip).
  * Replaces torchmd/interface.py:447-455 (BondPotentials.forward: harmonic in the SQUARED bond length,
  * 1/2 k (|b|^2 - ro)^2) and :496-508 (AnglePotentials.forward: 1/2 k (theta - theta0)^2 over triples (i, j, k) centred on

@@ -244,6 +244,14 @@ _SIGNATURES = {
     "mdg_msd_tile_atoms": (C.c_int, []),
     "mdg_msd_window": (C.c_int, []),
     "mdg_msd_max_lags": (C.c_int, []),
+    "mdg_isf_workspace": (C.c_int64, [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mdg_isf_fwd": (C.c_int, [C.c_int, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(MdgCell), P, C.c_double, P,
+                              C.c_int, P, C.c_int, C.c_int, C.c_int, P, P, P]),
+    "mdg_isf_bwd": (C.c_int, [C.c_int, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(MdgCell), P, C.c_double, P,
+                              C.c_int, P, C.c_int, C.c_int, C.c_int, P, P, P, P]),
+    "mdg_isf_max_lags": (C.c_int, []),
+    "mdg_isf_tile_atoms": (C.c_int, []),
+    "mdg_isf_window": (C.c_int, []),
     "mdg_bonded_eval": (C.c_int, [P, C.c_int, C.POINTER(C.c_float), C.c_int, P, C.c_int, C.c_float, C.c_float, P, P, P, P, P, P,
                                   C.c_float, C.c_int, P]),
 }

@@ -15,6 +15,7 @@
 //   virial_fwd/_bwd  K15  thermo.py Pressure (pair virial)   -> mdg_virial_fwd / mdg_virial_bwd
 //   sk_fwd/sk_bwd    K16  observable.py structure_factor     -> mdg_sk_fwd / mdg_sk_bwd
 //   msd_fwd/msd_bwd  K17  observable.py msd                  -> mdg_msd_fwd / mdg_msd_bwd
+//   isf_fwd/isf_bwd  K18  observable.py intermediate_scattering -> mdg_isf_fwd / mdg_isf_bwd
 //   edge_geom(+_bwd) schnet.py:142                          -> mdg_edge_geom / mdg_edge_geom_bwd
 //   cfconv_fwd/_bwd  K9+K10 modules.py:531-571              -> mdg_cfconv_fwd(_bf16) / mdg_cfconv_bwd(_bf16)
 //   dense_ssp        K11/12 layers.py:86-134                -> mdg_dense
@@ -430,6 +431,67 @@ Tensor msd_bwd(const Tensor& x, int64_t group, const OptTensor& weights, int64_t
     return gx;
 }
 
+// ------------------------------------------------------------------------------------------------ K18
+// x [n_batch,T,n_cols,3]; the replicas rep0 .. rep0 + n_reps - 1 of every batch; kvec / seg / seg_host / weights / norm as K16
+void isf_check(const Tensor& x, int64_t kind, int64_t group, int64_t rep0, int64_t n_reps, const OptTensor& weights,
+               const Tensor& kvec, const Tensor& seg, at::ArrayRef<int64_t> seg_host, int64_t n_lags, int64_t origin_stride) {
+    check_f32(x, "x");
+    TORCH_CHECK(kind == 0 || kind == 1, "mdgrad: kind must be 0 (coherent) or 1 (self)");
+    TORCH_CHECK(x.dim() == 4 && x.size(3) == 3, "mdgrad: x must be [n_batch,T,n_cols,3]");
+    TORCH_CHECK(group >= 1 && x.size(2) % group == 0, "mdgrad: the columns of x (", x.size(2), ") must be a multiple of group (",
+                group, ")");
+    TORCH_CHECK(rep0 >= 0 && n_reps >= 1 && rep0 + n_reps <= x.size(2) / group, "mdgrad: replicas ", rep0, " .. +", n_reps,
+                " are not among the ", x.size(2) / group, " of x");
+    TORCH_CHECK(n_lags >= 1 && n_lags <= x.size(1), "mdgrad: 1 <= n_lags <= T (got ", n_lags, ", ", x.size(1), ")");
+    TORCH_CHECK(origin_stride >= 1 && origin_stride <= INT32_MAX, "mdgrad: origin_stride must be >= 1");
+    TORCH_CHECK(x.size(0) <= INT32_MAX && x.size(1) <= INT32_MAX && x.size(2) <= INT32_MAX, "mdgrad: x is too large");
+    check_i32(kvec, "kvec"); check_i32(seg, "seg");
+    same_device(x, kvec, "kvec"); same_device(x, seg, "seg");
+    TORCH_CHECK(kvec.dim() == 2 && kvec.size(1) == 3, "mdgrad: kvec must be [M,3]");
+    TORCH_CHECK(seg_host.size() >= 2 && (int64_t)seg_host.size() == seg.numel(), "mdgrad: seg and seg_host must hold the same "
+                "n_bins + 1 offsets");
+    TORCH_CHECK(seg_host.front() == 0 && seg_host.back() == kvec.size(0), "mdgrad: the vector table kvec must hold seg[-1] = ",
+                seg_host.back(), " rows, got ", kvec.size(0));
+    for (size_t b = 1; b < seg_host.size(); ++b) TORCH_CHECK(seg_host[b] >= seg_host[b - 1], "mdgrad: seg must be ascending");
+    if (weights.has_value() && weights->defined()) {
+        TORCH_CHECK(weights->numel() == group, "mdgrad: weights must hold one entry per atom of a replica (", group, ")");
+        same_device(x, *weights, "weights");
+    }
+}
+int64_t isf_ws(int64_t kind, int64_t rows, int T, int64_t group, int M, int64_t n_lags) {
+    return std::max<int64_t>(mdg_isf_workspace((int)kind, rows, T, (int)group, M, (int)n_lags), 1);
+}
+Tensor isf_fwd(const Tensor& x, int64_t kind, int64_t group, int64_t rep0, int64_t n_reps, at::ArrayRef<double> cell,
+               const OptTensor& weights, double norm, const Tensor& kvec, const Tensor& seg, at::ArrayRef<int64_t> seg_host,
+               int64_t n_lags, int64_t origin_stride) {
+    isf_check(x, kind, group, rep0, n_reps, weights, kvec, seg, seg_host, n_lags, origin_stride);
+    const MdgCell c = make_cell(cell);
+    const int nb = (int)x.size(0), T = (int)x.size(1), nc = (int)x.size(2), M = (int)kvec.size(0), B = (int)seg.numel() - 1;
+    const int64_t rows = (int64_t)nb * n_reps;
+    Tensor F = at::empty({rows, B, n_lags}, x.options()), ws = at::empty({isf_ws(kind, rows, T, group, M, n_lags)}, x.options());
+    ok(mdg_isf_fwd((int)kind, fptr(x), nb, T, nc, (int)group, (int)rep0, (int)n_reps, &c, fptr(weights, "weights"), norm,
+                   kvec.data_ptr<int32_t>(), M, seg.data_ptr<int32_t>(), B, (int)n_lags, (int)origin_stride, mptr(F), mptr(ws),
+                   stream_of(x)));
+    return F;
+}
+// writes the columns of the call's replicas in gx (the shape of x) and leaves the others alone
+void isf_bwd(const Tensor& x, int64_t kind, int64_t group, int64_t rep0, int64_t n_reps, at::ArrayRef<double> cell,
+             const OptTensor& weights, double norm, const Tensor& kvec, const Tensor& seg, at::ArrayRef<int64_t> seg_host,
+             int64_t n_lags, int64_t origin_stride, const Tensor& gF, Tensor gx) {
+    isf_check(x, kind, group, rep0, n_reps, weights, kvec, seg, seg_host, n_lags, origin_stride);
+    check_f32(gF, "gF"); same_device(x, gF, "gF");
+    check_f32(gx, "gx"); same_device(x, gx, "gx");
+    TORCH_CHECK(gx.sizes() == x.sizes(), "mdgrad: gx must have the shape of x");
+    const MdgCell c = make_cell(cell);
+    const int nb = (int)x.size(0), T = (int)x.size(1), nc = (int)x.size(2), M = (int)kvec.size(0), B = (int)seg.numel() - 1;
+    const int64_t rows = (int64_t)nb * n_reps;
+    TORCH_CHECK(gF.numel() == rows * B * n_lags, "mdgrad: gF must be [rows,n_bins,n_lags]");
+    Tensor ws = at::empty({isf_ws(kind, rows, T, group, M, n_lags)}, x.options());
+    ok(mdg_isf_bwd((int)kind, fptr(x), nb, T, nc, (int)group, (int)rep0, (int)n_reps, &c, fptr(weights, "weights"), norm,
+                   kvec.data_ptr<int32_t>(), M, seg.data_ptr<int32_t>(), B, (int)n_lags, (int)origin_stride, fptr(gF), mptr(gx),
+                   mptr(ws), stream_of(x)));
+}
+
 // ------------------------------------------------------------------------------------------------ SchNet block
 MdgFilterNet filter_net(const Tensor& mu, const Tensor& coef, const Tensor& W1, const Tensor& b1, const Tensor& W2,
                         const Tensor& b2) {
@@ -599,6 +661,10 @@ TORCH_LIBRARY(mdgrad, m) {
           "Tensor");
     m.def("msd_fwd(Tensor x, int group, Tensor? weights, int n_lags, int origin_stride, bool fourth) -> (Tensor, Tensor)");
     m.def("msd_bwd(Tensor x, int group, Tensor? weights, int n_lags, int origin_stride, Tensor g2, Tensor? g4) -> Tensor");
+    m.def("isf_fwd(Tensor x, int kind, int group, int rep0, int n_reps, float[] cell, Tensor? weights, float norm, Tensor kvec, "
+          "Tensor seg, int[] seg_host, int n_lags, int origin_stride) -> Tensor");
+    m.def("isf_bwd(Tensor x, int kind, int group, int rep0, int n_reps, float[] cell, Tensor? weights, float norm, Tensor kvec, "
+          "Tensor seg, int[] seg_host, int n_lags, int origin_stride, Tensor gF, Tensor(a!) gx) -> ()");
     m.def("edge_geom(Tensor x, Tensor? w, Tensor nbr, Tensor offsets) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("edge_geom_bwd(Tensor? d_b, Tensor dd_b, Tensor? d, Tensor? dd, Tensor uhat, Tensor? ddel, Tensor col, Tensor eid, "
           "Tensor cnt) -> (Tensor, Tensor)");
@@ -629,6 +695,8 @@ TORCH_LIBRARY_IMPL(mdgrad, CUDA, m) {      // (the HIP backend registers under t
     m.impl("sk_bwd", sk_bwd);
     m.impl("msd_fwd", msd_fwd);
     m.impl("msd_bwd", msd_bwd);
+    m.impl("isf_fwd", isf_fwd);
+    m.impl("isf_bwd", isf_bwd);
     m.impl("edge_geom", edge_geom);
     m.impl("edge_geom_bwd", edge_geom_bwd);
     m.impl("cfconv_fwd", cfconv_fwd);

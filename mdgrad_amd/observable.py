@@ -6,7 +6,9 @@ compute_angle :166-179): the triplet search + Gaussian smearing + histogram and 
 (ops.AdfRawFn, csrc/adf.hip); the per-triplet angles are torch ops over the device-built angle list.  structure_factor has no
 counterpart in the reference: the static structure factor S(k) over the cell's own wave vectors (ops.SkFn, csrc/sk.hip).  Nor
 has msd: the mean-squared displacement over all lags and time origins with its fourth moment (ops.MsdFn, csrc/msd.hip), and
-diffusion_coefficient, the Einstein slope of it."""
+diffusion_coefficient, the Einstein slope of it; nor intermediate_scattering: the coherent and self intermediate scattering
+functions F(k,t), F_s(k,t) over the wave vectors of structure_factor and the lags of msd (ops.IsfFn, csrc/isf.hip), with
+relaxation and relaxation_time."""
 import math
 import warnings
 
@@ -436,6 +438,159 @@ def diffusion_coefficient(m, dt, fit_range=None, dim=3):
     tau = torch.arange(a, b, device=m.device, dtype=m.dtype)
     c = tau - tau.mean()
     return (m[..., a:b] * (c / (c.pow(2).sum() * dt))).sum(-1) / (2 * dim)
+
+
+def isf_max_lags():
+    """The largest t_range of intermediate_scattering: what the LDS ring of csrc/isf.hip holds (mdg_isf_max_lags)."""
+    return int(_lib.load().mdg_isf_max_lags())
+
+
+class intermediate_scattering(Observable):
+    """Intermediate scattering function over all lags and time origins, coherent or self (no counterpart in the reference).
+
+    The cell is diagonal with lengths L; the wave vectors k(n) = 2 pi (nx / Lx, ny / Ly, nz / Lz) are selected, ordered and
+    binned exactly as structure_factor does (sk_vectors: half space, hard bins on |k| taken in float64, max_per_bin,
+    system.dim == 2 keeping nz = 0).  For one replica of T frames, real per-atom weights w_i (default 1), s = origin_stride,
+    the time origins O_tau = {t0 = 0, s, 2 s, ... : t0 + tau < T} and the lags tau = 0 .. t_range - 1 (the lag convention of
+    vacf and msd)
+
+        rho(k, t)   = sum_i w_i exp(i k.x_i(t))                 W2 = sum_i w_i^2
+        F(k, tau)   = 1 / (|O_tau| W2)  sum_{t0 in O_tau} Re[ rho(k, t0 + tau) conj rho(k, t0) ]                  kind="coherent"
+        F_s(k, tau) = 1 / (|O_tau| W2)  sum_{t0 in O_tau} sum_i w_i^2 cos( k.(x_i(t0 + tau) - x_i(t0)) )          kind="self"
+        F[b, tau], F_s[b, tau] = mean over the selected vectors of bin b      (empty bin: 0, n_vectors[b] = 0: mask it)
+
+    F_s is exactly the i = j part of F, so the distinct part is F - F_s; with 0/1 weights both are the partial functions of
+    the selected atoms.  F[b, 0] with origin_stride = 1 is the frame mean of structure_factor's S[b]; F_s[b, 0] = 1; for one
+    atom F = F_s.  The small-k limit of F_s is exp(-k^2 MSD / 6).  Both are periodic in every coordinate of every frame:
+    positions wrapped into the cell and unwrapped positions give the same value, unlike msd.  The frames still have to be
+    consecutive in time, but wrapping between epochs (Simulations.simulate) does no harm.
+
+    index_tuple selects atoms as in msd: a list of atom indices, or the pair form of the other observables (two lists),
+    meaning their union; it is shorthand for 0/1 weights and multiplies into weights.  Weights and vectors are constants.
+
+    forward(q_t) -> (k [nbins], F [nbins, t_range]): the mean |k| of each bin's vectors (the bin centre for an empty bin) and
+    the mean over the replicas.  per_replica(q_t) keeps them: [T, N, 3] -> [nbins, t_range], [R, T, N, 3] ->
+    [R, nbins, t_range] (time is dim -3), replica-stacked [T, k N, 3] -> [k, nbins, t_range] and [R, T, k N, 3] ->
+    [R, k, nbins, t_range].  Attributes: bins (the edges), n_vectors [nbins], kvecs [M, 3], k [nbins].  relaxation(F)
+    normalises by the lag-0 value, relaxation_time(phi, dt) gives the time at which it has fallen to 1 / e.
+
+    HIP kernels forward and backward (ops.IsfFn, csrc/isf.hip): the self part costs one sine / cosine pair per (frame, atom,
+    vector), not per (origin, lag, atom, vector).  Differentiable once with respect to the positions; t_range <= isf_max_lags()."""
+
+    KINDS = {"coherent": 0, "self": 1}
+
+    def __init__(self, system, nbins, k_range, t_range, kind="coherent", weights=None, index_tuple=None, max_per_bin=None,
+                 origin_stride=1):
+        super().__init__(system)
+        name = "intermediate_scattering"
+        full = np.asarray(system.get_cell(), dtype=np.float64)
+        if full.shape == (3, 3) and np.any(full - np.diag(np.diag(full)) != 0.0):
+            raise ValueError("%s: the cell must be diagonal (triclinic cells are not supported)" % name)
+        if kind not in self.KINDS:
+            raise ValueError("%s: kind must be 'coherent' or 'self', got %r" % (name, kind))
+        if not (isinstance(nbins, (int, np.integer)) and 1 <= int(nbins) <= SK_MAX_BINS):
+            raise ValueError("%s: nbins must be 1..%d, got %r" % (name, SK_MAX_BINS, nbins))
+        if not (len(k_range) == 2 and 0 < float(k_range[0]) < float(k_range[1])):
+            raise ValueError("%s: k_range must be (k_min, k_max) with 0 < k_min < k_max, got %r" % (name, k_range))
+        if max_per_bin is not None and int(max_per_bin) < 1:
+            raise ValueError("%s: max_per_bin must be a positive integer, got %r" % (name, max_per_bin))
+        if not (isinstance(t_range, (int, np.integer)) and 1 <= int(t_range) <= isf_max_lags()):
+            raise ValueError("%s: t_range must be an integer in 1..%d, got %r" % (name, isf_max_lags(), t_range))
+        if not (isinstance(origin_stride, (int, np.integer)) and int(origin_stride) >= 1):
+            raise ValueError("%s: origin_stride must be an integer >= 1, got %r" % (name, origin_stride))
+        self.kind, self.nbins, self.dim = kind, int(nbins), getattr(system, "dim", 3)
+        self.t_range, self.origin_stride, self.index_tuple = int(t_range), int(origin_stride), index_tuple
+        lengths = self.cell.detach().cpu().to(torch.float64).numpy()          # the float32 lengths the kernels see
+        try:
+            n, seg, kabs, edges = sk_vectors(lengths, self.nbins, k_range, self.dim, max_per_bin)
+        except ValueError as e:
+            raise ValueError(str(e).replace("structure_factor", name)) from None
+        if len(n) == 0:
+            raise ValueError("%s: no wave vector of this cell lies in k_range = %r" % (name, tuple(k_range)))
+        if len(n) > SK_MAX_VECTORS:
+            raise ValueError("%s: %d wave vectors exceed the limit of %d; thin them with max_per_bin" % (name, len(n), SK_MAX_VECTORS))
+        self.bins = torch.as_tensor(edges)
+        counts = np.diff(seg)
+        sums = np.bincount(np.repeat(np.arange(self.nbins), counts), weights=kabs, minlength=self.nbins)
+        centre = 0.5 * (edges[1:] + edges[:-1])
+        self.n_vectors = torch.as_tensor(counts)
+        self.kvecs = torch.as_tensor(n)
+        self.k = torch.as_tensor(np.where(counts > 0, sums / np.maximum(counts, 1), centre), dtype=torch.float32).to(self.device)
+        self._seg_host = [int(x) for x in seg]
+        self._kvec = torch.as_tensor(n, dtype=torch.int32).contiguous().to(self.device)
+        self._seg = torch.as_tensor(seg, dtype=torch.int32).to(self.device)
+        w = None
+        if weights is not None:
+            w = torch.as_tensor(weights, dtype=torch.float32).detach().reshape(-1).cpu()
+            if w.numel() != self.natoms:
+                raise ValueError("%s: weights must hold one entry per atom (%d), got %d" % (name, self.natoms, w.numel()))
+            if not bool(torch.isfinite(w).all()):
+                raise ValueError("%s: the weights must be finite and not all zero" % name)
+        if index_tuple is not None:
+            idx = list(index_tuple)
+            if len(idx) and not isinstance(idx[0], (int, np.integer)):            # the pair form: the union of both lists
+                idx = [i for part in idx for i in list(part)]
+            sel = torch.as_tensor(np.asarray(idx, dtype=np.int64)).reshape(-1)
+            if sel.numel() == 0 or int(sel.min()) < 0 or int(sel.max()) >= self.natoms:
+                raise ValueError("%s: index_tuple must name atoms in 0..%d, got %r" % (name, self.natoms - 1, index_tuple))
+            mask = torch.zeros(self.natoms)
+            mask[sel] = 1.0
+            w = mask if w is None else w * mask
+        self._norm = float(self.natoms) if w is None else float(w.double().pow(2).sum())
+        if not (self._norm > 0 and np.isfinite(self._norm)):
+            raise ValueError("%s: the weights%s must be finite and not all zero"
+                             % (name, " (with index_tuple applied)" if index_tuple is not None else ""))
+        self.weights = None if w is None else w.contiguous().to(self.device)
+        self._cell_struct = _lib.make_cell(self.cell)
+
+    def _batch(self, x):
+        if x.dim() not in (3, 4) or x.shape[-1] != 3 or x.shape[-2] == 0 or x.shape[-2] % self.natoms:
+            raise ValueError("intermediate_scattering: q_t must be [T, k * %d, 3] or [R, T, k * %d, 3], got %s"
+                             % (self.natoms, self.natoms, tuple(x.shape)))
+        if self.t_range > x.shape[-3]:
+            raise ValueError("intermediate_scattering: t_range = %d exceeds the %d frames of q_t" % (self.t_range, x.shape[-3]))
+        k = x.shape[-2] // self.natoms
+        lead = (tuple(x.shape[:-3]) + ((k,) if k > 1 else ()))
+        return (x if x.dim() == 4 else x.unsqueeze(0)), lead
+
+    def per_replica(self, q_t):
+        """F (or F_s) of every replica: [nbins, t_range], [R, ...], [k, ...] or [R, k, nbins, t_range]."""
+        x, lead = self._batch(q_t)
+        F = ops.IsfFn.apply(x, self.KINDS[self.kind], self.natoms, self._cell_struct, self.weights, self._norm, self._kvec,
+                            self._seg, self._seg_host, self.t_range, self.origin_stride)
+        return F.reshape(lead + (self.nbins, self.t_range))
+
+    def forward(self, q_t):
+        return self.k, self.per_replica(q_t).reshape(-1, self.nbins, self.t_range).mean(0)
+
+
+def relaxation(F):
+    """phi = F / F[..., :1], the intermediate scattering function normalised by its lag-0 value (S(k) for the coherent one, 1
+    for the self one); 0 where F[..., 0] is 0 (empty bins)."""
+    f0 = F[..., :1]
+    ok = f0 != 0
+    return torch.where(ok, F / torch.where(ok, f0, torch.ones_like(f0)), torch.zeros_like(F))
+
+
+def relaxation_time(phi, dt, level=math.exp(-1.0)):
+    """The time at which phi [..., L] (lag tau at index tau, spacing dt) first falls to `level`, per leading row: with a the
+    last lag before the first lag b = a + 1 at which phi <= level,
+
+        t = dt (a + (phi[a] - level) / (phi[a] - phi[b]))
+
+    the linear interpolation between the two, in closed form and differentiable in phi[a] and phi[b].  A row whose lag 0 is
+    already at or below the level gives 0; a row that never falls to it gives inf, with no gradient."""
+    L = phi.shape[-1]
+    below = phi <= level
+    hit = below.any(-1)
+    b = below.to(torch.int64).argmax(-1)                                   # the first lag at or below the level
+    a = (b - 1).clamp(min=0)
+    pa, pb = phi.gather(-1, a.unsqueeze(-1)).squeeze(-1), phi.gather(-1, b.unsqueeze(-1)).squeeze(-1)
+    inner = hit & (b > 0)
+    den = torch.where(inner, pa - pb, torch.ones_like(pa))
+    t = dt * (a.to(phi.dtype) + (pa - level) / den)
+    out = torch.where(inner, t, torch.zeros_like(t))
+    return torch.where(hit, out, torch.full_like(out, float("inf")))
 
 
 class vacf(Observable):

@@ -8,6 +8,7 @@ torch.autograd.Function wrappers that own the differentiation contract
     VirialFn                                                    pair virial of every frame (pressure)
     SkFn                                                        static structure factor of every frame
     MsdFn                                                       mean-squared displacement over all lags (+ fourth moment)
+    IsfFn                                                       intermediate scattering functions F(k,t), F_s(k,t)
 
 Everything here requires HIP tensors; there is no CPU path.
 """
@@ -1058,6 +1059,90 @@ class MsdFn(torch.autograd.Function):
             check(lib.mdg_msd_bwd(ptr(x4), nb, T, nc, group, ptr(weights), n_lags, origin_stride, ptr(g2), ptr(g4), ptr(gx),
                                   ptr(ws), stream_ptr(x4.device)), "mdg_msd_bwd")
         return gx.reshape(xshape), None, None, None, None, None
+
+
+ISF_WS_BYTES = 1 << 30          # IsfFn: rows per launch are chosen so that one call's workspace stays below this
+
+
+class IsfFn(torch.autograd.Function):
+    """F[row, b, tau] of x [n_batch, T, n_cols, 3] over the lags tau = 0 .. n_lags-1 (csrc/isf.hip, K18): the kernel side of
+    observable.intermediate_scattering.  kind 0: coherent, 1: self.  The n_cols columns are n_cols / group replicas of `group`
+    atoms; row = batch * (n_cols / group) + replica.  kvec int32 [M, 3], seg int32 [B + 1] on the device and seg_host (its
+    host copy) as for SkFn; weights [group] on the device or None, norm = sum of the squared weights; all constants.  Returns
+    [rows, B, n_lags].  The rows go through the kernels in chunks (whole batch entries, or runs of replicas of one batch entry)
+    whose workspace stays below ISF_WS_BYTES; a row's result does not depend on the chunking.  Differentiable once with respect
+    to the positions.  The torch.ops layer serves it when it is loaded (_torch_ops.get()), the ctypes bindings otherwise."""
+
+    @staticmethod
+    def _chunks(kind, nb, reps, T, group, M, n_lags):
+        """[(b0, b1, r0, r1)]: batch entries b0:b1 with replicas r0:r1 per call."""
+        per_row = 4 * max(int(_lib.load().mdg_isf_workspace(kind, 1, T, group, M, n_lags)), 1)
+        n = max(1, ISF_WS_BYTES // per_row)
+        if n >= reps:
+            step = min(nb, n // reps)
+            return [(b0, min(nb, b0 + step), 0, reps) for b0 in range(0, nb, step)]
+        return [(b, b + 1, r0, min(reps, r0 + n)) for b in range(nb) for r0 in range(0, reps, n)]
+
+    @staticmethod
+    def forward(ctx, x, kind, group, cell_struct, weights, norm, kvec, seg, seg_host, n_lags, origin_stride):
+        require_gpu(x, "x")
+        x4 = x.detach()
+        x4 = x4 if x4.is_contiguous() else x4.contiguous()
+        nb, T, nc = x4.shape[0], x4.shape[1], x4.shape[2]
+        if group < 1 or nc % group:
+            raise ValueError("IsfFn: the columns (%d) must be a multiple of the group (%d)" % (nc, group))
+        reps, M, B = nc // group, kvec.shape[0], seg.numel() - 1
+        kind, group, n_lags, origin_stride = int(kind), int(group), int(n_lags), int(origin_stride)
+        tops = _torch_ops.get()
+        lib = _lib.load()
+        cell = _torch_ops.cell_args(cell_struct) if tops is not None else None
+        chunks = IsfFn._chunks(kind, nb, reps, T, group, M, n_lags)
+        F = None if len(chunks) == 1 else torch.empty(nb, reps, B, n_lags, device=x4.device)
+        for b0, b1, r0, r1 in chunks:
+            xs = x4[b0:b1]
+            if tops is not None:
+                out = tops.isf_fwd(xs, kind, group, r0, r1 - r0, cell, weights, float(norm), kvec, seg, seg_host, n_lags,
+                                   origin_stride)
+            else:
+                rows = (b1 - b0) * (r1 - r0)
+                out = torch.empty(rows, B, n_lags, device=x4.device)
+                ws = torch.empty(max(int(lib.mdg_isf_workspace(kind, rows, T, group, M, n_lags)), 1), device=x4.device)
+                check(lib.mdg_isf_fwd(kind, ptr(xs), b1 - b0, T, nc, group, r0, r1 - r0, C.byref(cell_struct), ptr(weights),
+                                      float(norm), ptr(kvec), M, ptr(seg), B, n_lags, origin_stride, ptr(out), ptr(ws),
+                                      stream_ptr(x4.device)), "mdg_isf_fwd")
+            if F is None:
+                F = out
+            else:
+                F[b0:b1, r0:r1] = out.reshape(b1 - b0, r1 - r0, B, n_lags)
+        ctx.args = (kind, group, cell_struct, weights, norm, kvec, seg, seg_host, n_lags, origin_stride, x.shape)
+        ctx.save_for_backward(x4)
+        return F.reshape(nb * reps, B, n_lags)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gF):
+        (x4,) = ctx.saved_tensors
+        kind, group, cell_struct, weights, norm, kvec, seg, seg_host, n_lags, origin_stride, xshape = ctx.args
+        nb, T, nc = x4.shape[0], x4.shape[1], x4.shape[2]
+        reps, M, B = nc // group, kvec.shape[0], seg.numel() - 1
+        g = gF.detach().to(torch.float32).reshape(nb, reps, B, n_lags)
+        tops = _torch_ops.get()
+        lib = _lib.load()
+        cell = _torch_ops.cell_args(cell_struct) if tops is not None else None
+        gx = torch.empty_like(x4)                       # every element is written by exactly one call below
+        for b0, b1, r0, r1 in IsfFn._chunks(kind, nb, reps, T, group, M, n_lags):
+            xs, gs, gxs = x4[b0:b1], g[b0:b1, r0:r1], gx[b0:b1]
+            gs = gs if gs.is_contiguous() else gs.contiguous()
+            if tops is not None:
+                tops.isf_bwd(xs, kind, group, r0, r1 - r0, cell, weights, float(norm), kvec, seg, seg_host, n_lags,
+                             origin_stride, gs, gxs)
+            else:
+                rows = (b1 - b0) * (r1 - r0)
+                ws = torch.empty(max(int(lib.mdg_isf_workspace(kind, rows, T, group, M, n_lags)), 1), device=x4.device)
+                check(lib.mdg_isf_bwd(kind, ptr(xs), b1 - b0, T, nc, group, r0, r1 - r0, C.byref(cell_struct), ptr(weights),
+                                      float(norm), ptr(kvec), M, ptr(seg), B, n_lags, origin_stride, ptr(gs), ptr(gxs), ptr(ws),
+                                      stream_ptr(x4.device)), "mdg_isf_bwd")
+        return (gx.reshape(xshape),) + (None,) * 10
 
 
 class TemperatureFn(torch.autograd.Function):

@@ -53,6 +53,8 @@ struct RingLJ {
     float sig2, rc2, m1a, m1b, ka, kb, tsa, tsb, tea, teb;      // LJ 12-6 polynomial (KIND_LJ126)
     float ivx, ivy, ivz, hx, hy, hz;
     TermConst t0;                                               // any other single-term form goes through pair_eval
+    uint32_t rcm;                                               // cutoff test of ring_pair: bits(rc2) - 1 (0: nothing passes)
+    bool full;                                                  // even N and TrajArgs::lean: ring_sweep<..., FULL> (wave-uniform)
 };
 
 __device__ __forceinline__ RingLJ ring_constants(const TrajArgs& A, int m = 0) {
@@ -67,6 +69,8 @@ __device__ __forceinline__ RingLJ ring_constants(const TrajArgs& A, int m = 0) {
     K.ivx = A.cell.inv[0]; K.ivy = A.cell.inv[4]; K.ivz = A.cell.inv[8];
     K.hx = A.cell.h[0]; K.hy = A.cell.h[4]; K.hz = A.cell.h[8];
     K.t0 = t0;
+    K.rcm = t0.rc2 > 0.f ? __float_as_uint(t0.rc2) - 1u : 0u;          // (rc2 = 0 or not a number: no d2 is below it)
+    K.full = A.lean && !(A.prm.n_atoms & 1);
     return K;
 }
 
@@ -152,8 +156,15 @@ __device__ __forceinline__ void ring_pair(const RingLJ& K, const RingRdf& X, con
         if constexpr (JSIDE) { rj.x += CROSS ? cx.yx : cx; rj.y += CROSS ? cy.yx : cy; rj.z += CROSS ? cz.yx : cz; }
     }
     if constexpr (LEVEL >= 1) {
-        const bool ok0 = v0 && (d2.x != 0.f) && (d2.x < K.rc2);                       // topology.py:67
-        const bool ok1 = v1 && (d2.y != 0.f) && (d2.y < K.rc2);
+        // topology.py:67, d2 != 0 && d2 < rc2, as ONE unsigned compare: bits(d2) - 1 < bits(rc2) - 1.  d2 is a sum of squares
+        // (norm2_ref2: products and additions of them, no subtraction), so it is +0, positive or not a number -- never -0 and
+        // never negative -- and the bit patterns of such floats are ordered like their values (subnormals included; the kernels
+        // are built with subnormals kept).  d2 = +0: 0 - 1 wraps to the largest word and fails, as d2 != 0 does.  d2 > 0:
+        // bits(d2) - 1 < bits(rc2) - 1 <=> bits(d2) < bits(rc2) <=> d2 < rc2, rc2 = +inf included.  d2 not a number: its bits
+        // lie above those of +inf >= rc2 and fail, as both float compares do.  rc2 = 0 or not a number admits nothing in
+        // either form: ring_constants sets rcm = 0 there.
+        const bool ok0 = v0 && (__float_as_uint(d2.x) - 1u < K.rcm);
+        const bool ok1 = v1 && (__float_as_uint(d2.y) - 1u < K.rcm);
         // per pair: c1 = phi'/r, kk = (phi'' - phi'/r)/r^2 and the parameter factors tk (dth_k += tk (w.D) per directed
         // pair) -- from the even-power polynomial for LJ 12-6, from pair_eval for every other form
         f32x2 c1, kk, tk[MDG_MAX_THETA];
@@ -293,7 +304,15 @@ __device__ __forceinline__ RingMask ring_mask_load(const uint8_t* __restrict__ m
     return M;
 }
 
-template <int LEVEL, bool NEAR, int RDF, int KIND, bool MASK, bool SUMS = true>
+// FULL (N even, no mask; chosen wave-uniformly by ring_force): every lane < nl owns two atoms and every lane >= nl owns none, so
+// all existence flags of a pair operation -- vi*, the visitors' vj*, the eight masks built from them per ring step and what
+// ring_pair ANDs onto them -- are the one loop-invariant predicate lane < nl.  It is applied once, as a branch around the steps:
+// inside, every flag is a compile-time true.  The lanes kept out leave with the zero accumulators they entered with, which is
+// what the general sweep gives them too: each of its masked operations adds +-0 to a +0 accumulator.  ds_bpermute_b32 returns
+// zero for a source lane that is switched off, but an active lane (< nl) only ever reads lanes prev / 4 < nl, which are active:
+// the travelling accumulators see the same sources as in the general sweep.  The LDS copy is written, and the accumulators
+// are brought home and added up, by all lanes outside the branch, as before.
+template <int LEVEL, bool NEAR, int RDF, int KIND, bool MASK, bool SUMS = true, bool FULL = false>
 __device__ __forceinline__ void ring_sweep(const RingLJ& K, const RingRdf& X, const RingMask& M, int N, int lane, const Vec3x2& q,
                                            const Vec3x2& w, Vec3x2& f, Vec3x2& g, float (&th)[MDG_MAX_THETA], Vec3x2& rq,
                                            f32x2* __restrict__ lds) {
@@ -309,15 +328,17 @@ __device__ __forceinline__ void ring_sweep(const RingLJ& K, const RingRdf& X, co
     f32x2 S[MDG_MAX_THETA], D[MDG_MAX_THETA];                 // parameter sums: ring steps (undirected) / directed steps
 #pragma unroll
     for (int k = 0; k < MDG_MAX_THETA; ++k) { S[k] = f32x2{0.f, 0.f}; D[k] = S[k]; }
+    static_assert(!FULL || !MASK, "the full ring has no selection mask");
+    const int nsteps = (nl - 1) >> 1;
+    if (!FULL || lane < nl) {
     // step 0: the pair inside the lane, both directions (one copy for the histogram)
     {
-        const bool v = vi0 && vi1;
+        const bool v = FULL || (vi0 && vi1);
         bool vm = v;
         if constexpr (MASK) vm = v && ((ring_mask_word(M.w, lane >> 4) >> (2 * (lane & 15) + 1)) & 1u);   // (i0, i1)
         ring_pair<LEVEL, NEAR, true, false, RDF, KIND, SUMS>(K, X, q, w, q, w, vm, vm, v, RDF == 2 && v, fi, gi, fj, gj, D, ri, rj);
     }
     const int prev = lane < nl ? ((lane == 0 ? nl : lane) - 1) * 4 : lane * 4;     // bpermute address of lane l-1
-    const int nsteps = (nl - 1) >> 1;
     int idx = lane;
     Vec3x2 qj, wj = vzero();
 #pragma unroll 1
@@ -327,8 +348,8 @@ __device__ __forceinline__ void ring_sweep(const RingLJ& K, const RingRdf& X, co
         if constexpr (ring_level_force(LEVEL)) fj = ring_move(fj, prev);
         if constexpr (LEVEL >= 2) { wj.x = swx[idx]; wj.y = swy[idx]; wj.z = swz[idx]; gj = ring_move(gj, prev); }
         if constexpr (RDF == 2) rj = ring_move(rj, prev);
-        const bool vj0 = 2 * idx < N, vj1 = 2 * idx + 1 < N;
-        const bool s0 = vi0 && vj0, s1 = vi1 && vj1, c0 = vi0 && vj1, c1 = vi1 && vj0;
+        const bool vj0 = FULL || 2 * idx < N, vj1 = FULL || 2 * idx + 1 < N;
+        const bool s0 = FULL || (vi0 && vj0), s1 = FULL || (vi1 && vj1), c0 = FULL || (vi0 && vj1), c1 = FULL || (vi1 && vj0);
         bool ms0 = s0, ms1 = s1, mc0 = c0, mc1 = c1;
         if constexpr (MASK) {
             const uint32_t b0 = ring_mask_word(M.w, idx >> 4) >> (2 * (idx & 15)), b1 = ring_mask_word(M.w + 4, idx >> 4) >> (2 * (idx & 15));
@@ -343,8 +364,8 @@ __device__ __forceinline__ void ring_sweep(const RingLJ& K, const RingRdf& X, co
         idx -= 1; idx = idx < 0 ? idx + nl : idx;
         qj.x = sqx[idx]; qj.y = sqy[idx]; qj.z = sqz[idx];
         if constexpr (LEVEL >= 2) { wj.x = swx[idx]; wj.y = swy[idx]; wj.z = swz[idx]; }
-        const bool vj0 = 2 * idx < N, vj1 = 2 * idx + 1 < N;
-        const bool s0 = vi0 && vj0, s1 = vi1 && vj1, c0 = vi0 && vj1, c1 = vi1 && vj0;
+        const bool vj0 = FULL || 2 * idx < N, vj1 = FULL || 2 * idx + 1 < N;
+        const bool s0 = FULL || (vi0 && vj0), s1 = FULL || (vi1 && vj1), c0 = FULL || (vi0 && vj1), c1 = FULL || (vi1 && vj0);
         bool ms0 = s0, ms1 = s1, mc0 = c0, mc1 = c1;
         if constexpr (MASK) {
             const uint32_t b0 = ring_mask_word(M.w, idx >> 4) >> (2 * (idx & 15)), b1 = ring_mask_word(M.w + 4, idx >> 4) >> (2 * (idx & 15));
@@ -354,6 +375,7 @@ __device__ __forceinline__ void ring_sweep(const RingLJ& K, const RingRdf& X, co
         Vec3x2 fu = vzero(), gu = vzero(), ru = vzero();
         ring_pair<LEVEL, NEAR, false, false, RDF, KIND, SUMS>(K, X, q, w, qj, wj, ms0, ms1, s0 && once, s1 && once, fi, gi, fu, gu, D, ri, ru);
         ring_pair<LEVEL, NEAR, true, false, RDF, KIND, SUMS>(K, X, q, w, qj, wj, mc0, mc1, c0 && once, c1 && once, fi, gi, fu, gu, D, ri, ru);
+    }
     }
     // the travelling accumulators are nsteps lanes ahead of their owners
     int home = lane + nsteps; home = home >= nl ? home - nl : home;
@@ -397,15 +419,24 @@ __device__ __forceinline__ void ring_force(const RingLJ& K, const RingRdf& X, co
                                            const Vec3x2& q, const Vec3x2& w, Vec3x2& f, Vec3x2& g, float (&th)[MDG_MAX_THETA],
                                            Vec3x2& rq, f32x2* __restrict__ lds) {
     const bool near = ring_near(K, q);
+    // the full-ring sweep (even N, TrajArgs::lean) exists for the window form of the minimum image only: the general form is
+    // off the hot path (a replica with an atom outside the window), and the masked term keeps the general sweep
+    // -- and for LJ 12-6 (the even-power polynomial: LJ and ExcludedVolume(12)), where it is checked bit for bit against the general
+    // sweep; the pair_eval forms keep the general sweep (their Yukawa instantiation did not reproduce its bits under NHC; the cause
+    // is not established -- presumably pair_eval's products contract differently once the flags are constants)
+    constexpr bool FULL_OK = !MASK && KIND == KIND_LJ126;
+    const bool full = FULL_OK && near && K.full;
     if constexpr (RDF != 0) {
         if (with_rdf) {
-            if (near) ring_sweep<LEVEL, true, RDF, KIND, MASK, SUMS>(K, X, M, N, lane, q, w, f, g, th, rq, lds);
+            if (full) ring_sweep<LEVEL, true, RDF, KIND, MASK, SUMS, FULL_OK>(K, X, M, N, lane, q, w, f, g, th, rq, lds);
+            else if (near) ring_sweep<LEVEL, true, RDF, KIND, MASK, SUMS>(K, X, M, N, lane, q, w, f, g, th, rq, lds);
             else ring_sweep<LEVEL, false, RDF, KIND, MASK, SUMS>(K, X, M, N, lane, q, w, f, g, th, rq, lds);
             return;
         }
     }
     if constexpr (LEVEL >= 1) {
-        if (near) ring_sweep<LEVEL, true, 0, KIND, MASK, SUMS>(K, X, M, N, lane, q, w, f, g, th, rq, lds);
+        if (full) ring_sweep<LEVEL, true, 0, KIND, MASK, SUMS, FULL_OK>(K, X, M, N, lane, q, w, f, g, th, rq, lds);
+        else if (near) ring_sweep<LEVEL, true, 0, KIND, MASK, SUMS>(K, X, M, N, lane, q, w, f, g, th, rq, lds);
         else ring_sweep<LEVEL, false, 0, KIND, MASK, SUMS>(K, X, M, N, lane, q, w, f, g, th, rq, lds);
     }
 }

@@ -37,6 +37,9 @@ struct TrajArgs {
     // ring kernels only: the force at every saved frame, AoS [R, T, N, 3] like q_t (frames 1..T-1; null: not kept).  The
     // forward writes it, the adjoint reads it for its first evaluation of each interval (traj_adj_ring_kernel<..., FT>).
     float* f_t;
+    // ring kernels only: take the full-ring sweep (ring_sweep<..., FULL>, no per-pair existence flags) where N is even.
+    // Set where the launch is built, from MDG_RING_LEAN (=0: the general sweep for every N; A/B inside one build)
+    int lean;
 };
 
 constexpr int KMAX_ALL = MDG_MAX_TERMS * MDG_MAX_THETA;
@@ -903,6 +906,10 @@ bool ring_form(const MdgTrajParams& p, const MdgCell& cell, const MdgTerms& term
     return terms.n_terms == 1 && cell.diag && (!t.mask || t.kind == MDG_PAIR_LJ) && t.kind >= 0 && t.kind <= MDG_PAIR_YUKAWA &&
            p.n_atoms <= 128;
 }
+int ring_lean() {
+    static const int lean = [] { const char* e = getenv("MDG_RING_LEAN"); return !(e && e[0] == '0') ? 1 : 0; }();
+    return lean;
+}
 bool use_ring(const MdgTrajParams& p, const MdgCell& cell, const MdgTerms& terms) {
     return ring_form(p, cell, terms) && (p.block == 64 || (p.block == 0 && p.n_rep >= 1024));
 }
@@ -1140,7 +1147,7 @@ int traj_fwd_small_run(const MdgTrajParams* prm, const MdgCell* cell, const MdgT
     hipStream_t st = (hipStream_t)stream;
     if (rdf || (!stale && use_ring(*prm, *cell, *terms))) {
         MDG_CHECK_ARG(theta || terms->n_theta_total == 0, "%s: null theta", who);
-        a.f_t = o.f_t;
+        a.f_t = o.f_t; a.lean = ring_lean();
         if (!rdf) {
             MDG_RING_LAUNCH(traj_fwd_ring_kernel, false, , dim3(prm->n_rep), dim3(64), RING_LDS_FWD + ring_table_lds(*terms, false),
                             st, a, RingRdfArgs{});
@@ -1196,7 +1203,7 @@ int traj_adj_small_run(const MdgTrajParams* prm, const MdgCell* cell, const MdgT
     hipStream_t st = (hipStream_t)stream;
     if (rdf || (!stale && use_ring(*prm, *cell, *terms))) {
         MDG_CHECK_ARG(theta || terms->n_theta_total == 0, "%s: null theta", who);
-        a.f_t = o.f_t;
+        a.f_t = o.f_t; a.lean = ring_lean();
         if (!rdf) {
             // (tabulated kind: RING_TABLE_WAVES replicas per workgroup share the nodes and one pair of gradient planes)
             const bool rt = terms->t[0].kind == MDG_PAIR_TABLE;

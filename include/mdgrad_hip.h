@@ -961,6 +961,57 @@ int mdg_isf_tile_atoms(void);
 int mdg_isf_window(void);
 
 /* ------------------------------------------------------------------------------------
+ * K19  dihedral (torsion) terms over a static table of quadruples: the torsion energy with force, Hessian-vector product
+ *      and parameter gradients, the per-term angles of many frames, and their periodic soft histogram
+ *      (mdgrad_amd/interface.py DihedralPotentials, mdgrad_amd/observable.py Dihedrals / dihedral_distribution; the cosine is
+ *      torchmd/observable.py:181-197 compute_dihe, the energy the "multiharmonic" form of nff/nn/modules.py:253-257;
+ *      csrc/dihedral.hip)
+ *   top int32 [n_terms, 4] rows (i, j, k, l); cell_len host float[3], the diagonal of the cell.
+ *     b1 = x_j - x_i, b2 = x_k - x_j, b3 = x_l - x_k, each re-imaged with topology.get_offsets (-[b >= L/2] + [b < -L/2]);
+ *     n1 = b1 x b2, n2 = b2 x b3;  cos phi = n1.n2 / sqrt(|n1|^2 |n2|^2);  phi = atan2(|b2| b1.n2, n1.n2) in (-pi, pi] (IUPAC)
+ *     U = sum_{m = 0..4} coeff[type, m] cos^m phi
+ *   Degenerate terms: |n1|^2 <= eps^2 |b1|^2 |b2|^2 or |n2|^2 <= eps^2 |b2|^2 |b3|^2, eps = 2^-20 (K14's threshold), are skipped
+ *   everywhere: zero energy, force, H w, parameter gradient, histogram weight and gradient; phi = cos phi = 0, zero gradient.
+ *   inc_ptr int32 [n_atoms + 1], inc int32 [4 n_terms]: the incidence list of every atom as in f4 (entries 4 * term + role,
+ *   ascending per atom -- the order the per-atom sums run in).  No atomics on floats anywhere: bitwise reproducible.
+ *
+ *   mdg_dihedral_eval  mirrors mdg_bonded_eval (one launch): coeff device float [n_types, 5], type nullable device int32
+ *     [n_terms] with entries in [0, n_types) (null = all type 0); w nullable [n_atoms, 3], required for hw;
+ *     e_atom nullable [n_atoms] (energy of the terms whose FIRST atom this is); grad, hw nullable [n_atoms, 3]:
+ *     grad = (accumulate ? grad : 0) + out_scale * dU/dx, hw likewise with H w;  c_term, cd_term nullable [n_terms]:
+ *     cos phi of every term (MDG_DIHEDRAL_SKIPPED = 2 for a skipped term) and its directional derivative w.grad(cos phi)
+ *     (0 without w).
+ *   mdg_dihedral_coeff_grad  from c_term / cd_term: g_u [n_types, 5] = dU/dcoeff[s, m] = sum_{t of type s} c_t^m and
+ *     g_w [n_types, 5] = d(w.dU/dx)/dcoeff[s, m] = sum_t m c_t^(m-1) cd_t (either nullable), in a fixed order.
+ *   mdg_dihedral_phi_fwd  pos [n_frames, n_atoms, 3] -> phi, cosphi [n_frames, n_terms] (either nullable).
+ *   mdg_dihedral_phi_bwd  given g_phi and / or g_cos [n_frames, n_terms] (the other null), writes g_xyz [n_frames, n_atoms, 3];
+ *     d phi/dx in the Blondel-Karplus form, finite at phi = 0 and +-pi.
+ *   mdg_dihedral_hist_fwd  raw[b] = sum_i exp(-1/2 (wrap(phi_i - mu_b) / width)^2) over phi [n], mu_b = -pi + (b + 1/2) 2 pi / nbins,
+ *     wrap onto [-pi, pi) (nearest image only), 1 <= nbins <= 4096, 0 < width <= 0.5; centres farther than
+ *     5.3 width sqrt(2 ln 2) from phi are dropped (<= 2^-28 of a peak term each, as K14).  cosphi nullable [n]: with it, an entry
+ *     with phi == 0 and cosphi == 0 is a skipped term and carries no weight.  NaN if an angle is not finite.  scratch: int64
+ *     words of mdg_dihedral_hist_scratch().
+ *   mdg_dihedral_hist_bwd  given g_raw [nbins], writes g_phi [n] = sum_b g_raw[b] d raw[b] / d phi_i.
+ */
+#define MDG_DIHEDRAL_SKIPPED 2.0f
+int mdg_dihedral_eval(const float* pos, int n_atoms, const float* cell_len /*host*/, const int32_t* top, int n_terms,
+                      const float* coeff, const int32_t* type, int n_types, const int32_t* inc_ptr, const int32_t* inc,
+                      const float* w, float* e_atom, float* grad, float* hw, float* c_term, float* cd_term, float out_scale,
+                      int accumulate, void* stream);
+int mdg_dihedral_coeff_grad(const float* c_term, const float* cd_term, const int32_t* type, int n_terms, int n_types,
+                            float* g_u, float* g_w, void* stream);
+int mdg_dihedral_phi_fwd(const float* pos, int n_frames, int n_atoms, const float* cell_len /*host*/, const int32_t* top,
+                         int n_terms, float* phi, float* cosphi, void* stream);
+int mdg_dihedral_phi_bwd(const float* pos, int n_frames, int n_atoms, const float* cell_len /*host*/, const int32_t* top,
+                         int n_terms, const int32_t* inc_ptr, const int32_t* inc, const float* g_phi, const float* g_cos,
+                         float* g_xyz, void* stream);
+int64_t mdg_dihedral_hist_scratch(int64_t n, int nbins);
+int mdg_dihedral_hist_fwd(const float* phi, const float* cosphi, int64_t n, int nbins, float width, float* raw,
+                          int64_t* scratch, void* stream);
+int mdg_dihedral_hist_bwd(const float* phi, const float* cosphi, int64_t n, int nbins, float width, const float* g_raw,
+                          float* g_phi, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * f4  bonded terms over a static topology table (csrc/bonded.hip).
  * Replaces torchmd/interface.py:447-455 (BondPotentials.forward: harmonic in the SQUARED bond length,
  * 1/2 k (|b|^2 - ro)^2) and :496-508 (AnglePotentials.forward: 1/2 k (theta - theta0)^2 over triples (i, j, k) centred on

@@ -254,6 +254,14 @@ _SIGNATURES = {
     "mdg_isf_window": (C.c_int, []),
     "mdg_bonded_eval": (C.c_int, [P, C.c_int, C.POINTER(C.c_float), C.c_int, P, C.c_int, C.c_float, C.c_float, P, P, P, P, P, P,
                                   C.c_float, C.c_int, P]),
+    "mdg_dihedral_eval": (C.c_int, [P, C.c_int, C.POINTER(C.c_float), P, C.c_int, P, P, C.c_int, P, P, P, P, P, P, P, P,
+                                    C.c_float, C.c_int, P]),
+    "mdg_dihedral_coeff_grad": (C.c_int, [P, P, P, C.c_int, C.c_int, P, P, P]),
+    "mdg_dihedral_phi_fwd": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(C.c_float), P, C.c_int, P, P, P]),
+    "mdg_dihedral_phi_bwd": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(C.c_float), P, C.c_int, P, P, P, P, P, P]),
+    "mdg_dihedral_hist_scratch": (C.c_int64, [C.c_int64, C.c_int]),
+    "mdg_dihedral_hist_fwd": (C.c_int, [P, P, C.c_int64, C.c_int, C.c_float, P, P, P]),
+    "mdg_dihedral_hist_bwd": (C.c_int, [P, P, C.c_int64, C.c_int, C.c_float, P, P, P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -13,34 +13,9 @@
 // term-wise pass plus a scatter, and deterministic.  H w comes from forward-mode (dual-number) differentiation of the
 // gradient along (w_i - w_j [, w_k - w_j]): exact, no hand-written second derivatives of acos.
 #include "common.hpp"
+#include "dual.hpp"
 
 namespace {
-
-struct Dual {
-    float v, d;
-};
-__device__ __forceinline__ Dual operator+(Dual a, Dual b) { return {a.v + b.v, a.d + b.d}; }
-__device__ __forceinline__ Dual operator-(Dual a, Dual b) { return {a.v - b.v, a.d - b.d}; }
-__device__ __forceinline__ Dual operator*(Dual a, Dual b) { return {a.v * b.v, fmaf(a.d, b.v, a.v * b.d)}; }
-__device__ __forceinline__ Dual operator*(float a, Dual b) { return {a * b.v, a * b.d}; }
-__device__ __forceinline__ Dual operator-(Dual a, float b) { return {a.v - b, a.d}; }
-__device__ __forceinline__ Dual operator-(float a, Dual b) { return {a - b.v, -b.d}; }
-__device__ __forceinline__ Dual operator/(Dual a, Dual b) {
-    const float q = a.v / b.v;
-    return {q, (a.d - q * b.d) / b.v};
-}
-__device__ __forceinline__ Dual dsqrt(Dual a) {
-    const float s = sqrtf(a.v);
-    return {s, 0.5f * a.d / s};
-}
-__device__ __forceinline__ Dual dacos(Dual a) { return {acosf(a.v), -a.d / sqrtf(1.f - a.v * a.v)}; }
-
-__device__ __forceinline__ float fsqrt_(float a) { return sqrtf(a); }
-__device__ __forceinline__ Dual fsqrt_(Dual a) { return dsqrt(a); }
-__device__ __forceinline__ float facos_(float a) { return acosf(a); }
-__device__ __forceinline__ Dual facos_(Dual a) { return dacos(a); }
-__device__ __forceinline__ float val(float a) { return a; }
-__device__ __forceinline__ float val(Dual a) { return a.v; }
 
 // topology.get_offsets (topology.py:75-80): -[b >= L/2] + [b < -L/2]
 __device__ __forceinline__ float image_flag(float b, float L) { return (b < -0.5f * L ? 1.f : 0.f) - (b >= 0.5f * L ? 1.f : 0.f); }

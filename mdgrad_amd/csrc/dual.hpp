@@ -1,0 +1,35 @@
+// Dual numbers (value + one directional derivative) for forward-mode differentiation inside a kernel: the bonded terms
+// (csrc/bonded.hip) and the torsion term (csrc/dihedral.hip) get their Hessian-vector products from them.  Every function is
+// internal to the translation unit that includes this file.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace {
+
+struct Dual {
+    float v, d;
+};
+__device__ __forceinline__ Dual operator+(Dual a, Dual b) { return {a.v + b.v, a.d + b.d}; }
+__device__ __forceinline__ Dual operator-(Dual a, Dual b) { return {a.v - b.v, a.d - b.d}; }
+__device__ __forceinline__ Dual operator*(Dual a, Dual b) { return {a.v * b.v, fmaf(a.d, b.v, a.v * b.d)}; }
+__device__ __forceinline__ Dual operator*(float a, Dual b) { return {a * b.v, a * b.d}; }
+__device__ __forceinline__ Dual operator-(Dual a, float b) { return {a.v - b, a.d}; }
+__device__ __forceinline__ Dual operator-(float a, Dual b) { return {a - b.v, -b.d}; }
+__device__ __forceinline__ Dual operator/(Dual a, Dual b) {
+    const float q = a.v / b.v;
+    return {q, (a.d - q * b.d) / b.v};
+}
+__device__ __forceinline__ Dual dsqrt(Dual a) {
+    const float s = sqrtf(a.v);
+    return {s, 0.5f * a.d / s};
+}
+__device__ __forceinline__ Dual dacos(Dual a) { return {acosf(a.v), -a.d / sqrtf(1.f - a.v * a.v)}; }
+
+__device__ __forceinline__ float fsqrt_(float a) { return sqrtf(a); }
+__device__ __forceinline__ Dual fsqrt_(Dual a) { return dsqrt(a); }
+__device__ __forceinline__ float facos_(float a) { return acosf(a); }
+__device__ __forceinline__ Dual facos_(Dual a) { return dacos(a); }
+__device__ __forceinline__ float val(float a) { return a; }
+__device__ __forceinline__ float val(Dual a) { return a.v; }
+
+}  // namespace

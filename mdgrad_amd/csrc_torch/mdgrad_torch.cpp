@@ -16,6 +16,8 @@
 //   sk_fwd/sk_bwd    K16  observable.py structure_factor     -> mdg_sk_fwd / mdg_sk_bwd
 //   msd_fwd/msd_bwd  K17  observable.py msd                  -> mdg_msd_fwd / mdg_msd_bwd
 //   isf_fwd/isf_bwd  K18  observable.py intermediate_scattering -> mdg_isf_fwd / mdg_isf_bwd
+//   dihedral_eval    K19  interface.py DihedralPotentials     -> mdg_dihedral_eval
+//   dihedral_phi_fwd/_bwd, dihedral_hist_fwd/_bwd  K19  observable.py Dihedrals / dihedral_distribution -> mdg_dihedral_phi_* / _hist_*
 //   edge_geom(+_bwd) schnet.py:142                          -> mdg_edge_geom / mdg_edge_geom_bwd
 //   cfconv_fwd/_bwd  K9+K10 modules.py:531-571              -> mdg_cfconv_fwd(_bf16) / mdg_cfconv_bwd(_bf16)
 //   dense_ssp        K11/12 layers.py:86-134                -> mdg_dense
@@ -633,6 +635,100 @@ Tensor atb(const Tensor& A, const Tensor& B) {
     return Cm;
 }
 
+// ------------------------------------------------------------------------------------------------ K19
+// cell_len = the three diagonal lengths; top int32 [n_terms, 4]; inc_ptr / inc = the incidence list of ops.DihedralTable
+struct DihedralGeom { float L[3]; int n_atoms, n_terms; };
+DihedralGeom dihedral_geom(const Tensor& pos, at::ArrayRef<double> cell_len, const Tensor& top) {
+    check_f32(pos, "pos"); check_i32(top, "top"); same_device(pos, top, "top");
+    TORCH_CHECK(cell_len.size() == 3, "mdgrad: cell_len = the three diagonal lengths of the cell");
+    TORCH_CHECK(pos.dim() >= 2 && pos.size(-1) == 3 && pos.size(-2) > 0, "mdgrad: pos must be [..., N, 3]");
+    TORCH_CHECK(top.dim() == 2 && top.size(1) == 4, "mdgrad: top must be [n_terms, 4]");
+    DihedralGeom g;
+    for (int k = 0; k < 3; ++k) g.L[k] = (float)cell_len[k];
+    g.n_atoms = (int)pos.size(-2);
+    g.n_terms = (int)top.size(0);
+    return g;
+}
+void dihedral_inc_check(const Tensor& pos, const DihedralGeom& g, const Tensor& inc_ptr, const Tensor& inc) {
+    check_i32(inc_ptr, "inc_ptr"); check_i32(inc, "inc"); same_device(pos, inc_ptr, "inc_ptr"); same_device(pos, inc, "inc");
+    TORCH_CHECK(inc_ptr.numel() == g.n_atoms + 1 && inc.numel() == 4 * (int64_t)g.n_terms,
+                "mdgrad: inc_ptr must be [n_atoms + 1] and inc [4 n_terms]");
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> dihedral_eval(const Tensor& pos, at::ArrayRef<double> cell_len, const Tensor& top,
+                                                                 const Tensor& coeff, const OptTensor& type, const Tensor& inc_ptr,
+                                                                 const Tensor& inc, const OptTensor& w, bool want_energy,
+                                                                 bool want_terms) {
+    const DihedralGeom g = dihedral_geom(pos, cell_len, top);
+    TORCH_CHECK(pos.dim() == 2, "mdgrad: pos must be [N, 3]");
+    check_f32(coeff, "coeff"); same_device(pos, coeff, "coeff");
+    TORCH_CHECK(coeff.numel() >= 5 && coeff.numel() % 5 == 0, "mdgrad: coeff must be [n_types, 5]");
+    dihedral_inc_check(pos, g, inc_ptr, inc);
+    const int32_t* ty = nullptr;
+    if (type.has_value() && type->defined()) {
+        check_i32(*type, "type"); same_device(pos, *type, "type");
+        TORCH_CHECK(type->numel() == g.n_terms, "mdgrad: type must hold one entry per term");
+        ty = type->data_ptr<int32_t>();
+    }
+    const float* wp = fptr(w, "w");
+    if (wp) { same_device(pos, *w, "w"); TORCH_CHECK(w->sizes() == pos.sizes(), "mdgrad: w must have the shape of pos"); }
+    const auto o = pos.options();
+    Tensor e = at::empty({want_energy ? g.n_atoms : 0}, o), grad = at::empty_like(pos);
+    Tensor hw = wp ? at::empty_like(pos) : at::empty({0}, o);
+    Tensor ct = at::empty({want_terms ? g.n_terms : 0}, o), cd = at::empty({(want_terms && wp) ? g.n_terms : 0}, o);
+    ok(mdg_dihedral_eval(fptr(pos), g.n_atoms, g.L, top.data_ptr<int32_t>(), g.n_terms, fptr(coeff), ty, (int)(coeff.numel() / 5),
+                         inc_ptr.data_ptr<int32_t>(), inc.data_ptr<int32_t>(), wp, want_energy ? mptr(e) : nullptr, mptr(grad),
+                         wp ? mptr(hw) : nullptr, want_terms ? mptr(ct) : nullptr, (want_terms && wp) ? mptr(cd) : nullptr, 1.f, 0,
+                         stream_of(pos)));
+    return {e, grad, hw, ct, cd};
+}
+std::tuple<Tensor, Tensor> dihedral_phi_fwd(const Tensor& pos, at::ArrayRef<double> cell_len, const Tensor& top) {
+    const DihedralGeom g = dihedral_geom(pos, cell_len, top);
+    TORCH_CHECK(pos.dim() == 3 && pos.size(0) > 0, "mdgrad: pos must be [F, N, 3] with F > 0");
+    Tensor phi = at::empty({pos.size(0), g.n_terms}, pos.options()), cs = at::empty_like(phi);
+    ok(mdg_dihedral_phi_fwd(fptr(pos), (int)pos.size(0), g.n_atoms, g.L, top.data_ptr<int32_t>(), g.n_terms, mptr(phi), mptr(cs),
+                            stream_of(pos)));
+    return {phi, cs};
+}
+Tensor dihedral_phi_bwd(const Tensor& pos, at::ArrayRef<double> cell_len, const Tensor& top, const Tensor& inc_ptr, const Tensor& inc,
+                        const OptTensor& g_phi, const OptTensor& g_cos) {
+    const DihedralGeom g = dihedral_geom(pos, cell_len, top);
+    TORCH_CHECK(pos.dim() == 3 && pos.size(0) > 0, "mdgrad: pos must be [F, N, 3] with F > 0");
+    dihedral_inc_check(pos, g, inc_ptr, inc);
+    const float* gp = fptr(g_phi, "g_phi");
+    const float* gc = fptr(g_cos, "g_cos");
+    TORCH_CHECK(gp || gc, "mdgrad: g_phi or g_cos must be given");
+    const int64_t want = pos.size(0) * (int64_t)g.n_terms;
+    if (gp) { same_device(pos, *g_phi, "g_phi"); TORCH_CHECK(g_phi->numel() == want, "mdgrad: g_phi must be [F, n_terms]"); }
+    if (gc) { same_device(pos, *g_cos, "g_cos"); TORCH_CHECK(g_cos->numel() == want, "mdgrad: g_cos must be [F, n_terms]"); }
+    Tensor gx = at::empty_like(pos);
+    ok(mdg_dihedral_phi_bwd(fptr(pos), (int)pos.size(0), g.n_atoms, g.L, top.data_ptr<int32_t>(), g.n_terms,
+                            inc_ptr.data_ptr<int32_t>(), inc.data_ptr<int32_t>(), gp, gc, mptr(gx), stream_of(pos)));
+    return gx;
+}
+const float* dihedral_hist_check(const Tensor& phi, const OptTensor& cosphi) {
+    check_f32(phi, "phi");
+    const float* cp = fptr(cosphi, "cosphi");
+    if (cp) { same_device(phi, *cosphi, "cosphi"); TORCH_CHECK(cosphi->numel() == phi.numel(), "mdgrad: cosphi must have the shape of phi"); }
+    return cp;
+}
+Tensor dihedral_hist_fwd(const Tensor& phi, const OptTensor& cosphi, int64_t nbins, double width) {
+    const float* cp = dihedral_hist_check(phi, cosphi);
+    TORCH_CHECK(nbins >= 1 && nbins <= 4096, "mdgrad: nbins must be in [1, 4096]");
+    Tensor raw = at::empty({nbins}, phi.options());
+    Tensor scratch = at::empty({mdg_dihedral_hist_scratch(phi.numel(), (int)nbins)}, phi.options().dtype(at::kLong));
+    ok(mdg_dihedral_hist_fwd(fptr(phi), cp, phi.numel(), (int)nbins, (float)width, mptr(raw), scratch.data_ptr<int64_t>(),
+                             stream_of(phi)));
+    return raw;
+}
+Tensor dihedral_hist_bwd(const Tensor& phi, const OptTensor& cosphi, int64_t nbins, double width, const Tensor& g_raw) {
+    const float* cp = dihedral_hist_check(phi, cosphi);
+    check_f32(g_raw, "g_raw"); same_device(phi, g_raw, "g_raw");
+    TORCH_CHECK(nbins >= 1 && nbins <= 4096 && g_raw.numel() == nbins, "mdgrad: g_raw must have one entry per bin (1 .. 4096)");
+    Tensor g = at::empty_like(phi);
+    ok(mdg_dihedral_hist_bwd(fptr(phi), cp, phi.numel(), (int)nbins, (float)width, fptr(g_raw), mptr(g), stream_of(phi)));
+    return g;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(mdgrad, m) {
@@ -665,6 +761,13 @@ TORCH_LIBRARY(mdgrad, m) {
           "Tensor seg, int[] seg_host, int n_lags, int origin_stride) -> Tensor");
     m.def("isf_bwd(Tensor x, int kind, int group, int rep0, int n_reps, float[] cell, Tensor? weights, float norm, Tensor kvec, "
           "Tensor seg, int[] seg_host, int n_lags, int origin_stride, Tensor gF, Tensor(a!) gx) -> ()");
+    m.def("dihedral_eval(Tensor pos, float[] cell_len, Tensor top, Tensor coeff, Tensor? type, Tensor inc_ptr, Tensor inc, Tensor? w, "
+          "bool want_energy, bool want_terms) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
+    m.def("dihedral_phi_fwd(Tensor pos, float[] cell_len, Tensor top) -> (Tensor, Tensor)");
+    m.def("dihedral_phi_bwd(Tensor pos, float[] cell_len, Tensor top, Tensor inc_ptr, Tensor inc, Tensor? g_phi, Tensor? g_cos) -> "
+          "Tensor");
+    m.def("dihedral_hist_fwd(Tensor phi, Tensor? cosphi, int nbins, float width) -> Tensor");
+    m.def("dihedral_hist_bwd(Tensor phi, Tensor? cosphi, int nbins, float width, Tensor g_raw) -> Tensor");
     m.def("edge_geom(Tensor x, Tensor? w, Tensor nbr, Tensor offsets) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("edge_geom_bwd(Tensor? d_b, Tensor dd_b, Tensor? d, Tensor? dd, Tensor uhat, Tensor? ddel, Tensor col, Tensor eid, "
           "Tensor cnt) -> (Tensor, Tensor)");
@@ -697,6 +800,11 @@ TORCH_LIBRARY_IMPL(mdgrad, CUDA, m) {      // (the HIP backend registers under t
     m.impl("msd_bwd", msd_bwd);
     m.impl("isf_fwd", isf_fwd);
     m.impl("isf_bwd", isf_bwd);
+    m.impl("dihedral_eval", dihedral_eval);
+    m.impl("dihedral_phi_fwd", dihedral_phi_fwd);
+    m.impl("dihedral_phi_bwd", dihedral_phi_bwd);
+    m.impl("dihedral_hist_fwd", dihedral_hist_fwd);
+    m.impl("dihedral_hist_bwd", dihedral_hist_bwd);
     m.impl("edge_geom", edge_geom);
     m.impl("edge_geom_bwd", edge_geom_bwd);
     m.impl("cfconv_fwd", cfconv_fwd);

@@ -570,6 +570,135 @@ class AnglePotentials(_BondedTerm):
         return 0.5 * self.k * (torch.acos(cos) - self.thetao).pow(2).sum(-1)
 
 
+class DihedralPotentials(torch.nn.Module):
+    """Torsion term over quadruples (i, j, k, l): U = sum_terms sum_{m = 0..4} coeffs[type, m] cos^m phi, the reference's
+    "multiharmonic" dihedral form (nff/nn/modules.py:253-257); no counterpart in torchmd/interface.py.
+
+    With b1 = x_j - x_i, b2 = x_k - x_j, b3 = x_l - x_k (each re-imaged with topology.get_offsets on cell.diag(), like
+    BondPotentials / AnglePotentials), n1 = b1 x b2 and n2 = b2 x b3:  cos phi = n1.n2 / sqrt(|n1|^2 |n2|^2), which is
+    compute_dihe (torchmd/observable.py:181-197) of the row.  The energy is a polynomial in cos phi: no acos, no singularity at
+    phi = 0 or pi (the reference's acos(cos / 1.000001) fudge is not reproduced).  A term with three collinear atoms,
+    |n1|^2 <= eps^2 |b1|^2 |b2|^2 or |n2|^2 <= eps^2 |b2|^2 |b3|^2 with eps = 2^-20, is skipped: no energy, force or gradient.
+
+    `top` [n_terms, 4]; `coeffs` [5] or [n_types, 5], held as the parameter `coeffs` (trainable=False: a buffer); `types`
+    [n_terms] in [0, n_types) picks the row of every term (default: row 0).  from_opls builds it from OPLS constants.
+
+    A Stack member like BondPotentials: forward(xyz) is differentiable twice in xyz and once in coeffs on the HIP kernels
+    (ops.DihedralEnergyFn, csrc/dihedral.hip), and force / force_vjp serve the analytic adjoint and HIP-graph replay -- also
+    while coeffs requires grad: d(w.F)/dcoeffs comes out of the same launch.  float64 or host positions take the torch
+    restatement `_torch_energy`."""
+
+    accepts_into = True
+    accepts_accum = True
+    analytic = True
+
+    def __init__(self, system, top, coeffs, types=None, trainable=True):
+        super().__init__()
+        self.system = system
+        self.device = system.device
+        self.cell = torch.Tensor(system.get_cell()).diag().to(self.device)
+        self._n_atoms = system.get_number_of_atoms()
+        c = torch.as_tensor(coeffs, dtype=torch.float32).detach().clone()
+        if c.dim() not in (1, 2) or c.shape[-1] != 5:
+            raise ValueError("DihedralPotentials: coeffs must be [5] or [n_types, 5], got %s" % (tuple(c.shape),))
+        c = c.to(self.device)
+        if trainable:
+            self.coeffs = torch.nn.Parameter(c)
+        else:
+            self.register_buffer("coeffs", c)
+        self.n_types = 1 if c.dim() == 1 else int(c.shape[0])
+        self.top = torch.as_tensor(top).to(torch.long).reshape(-1, 4).to(self.device)
+        self.types = None if types is None else torch.as_tensor(types).to(torch.long).reshape(-1).to(self.device)
+        self._table = ops.DihedralTable(self.top, self._n_atoms, self.cell.detach().cpu().tolist(), self.device, types=self.types,
+                                        n_types=self.n_types)
+
+    @staticmethod
+    def opls_to_multiharmonic(V):
+        """OPLS constants V1..V4 [..., 4] of sum_m V_m / 2 (1 + (-1)^(m+1) cos(m phi)) (nff/nn/modules.py:259-264) -> the
+        coefficients [..., 5] of the same energy as a polynomial in cos phi:
+        [V1/2 + V2 + V3/2, V1/2 - 3 V3/2, -V2 + 4 V4, 2 V3, -4 V4]."""
+        V = torch.as_tensor(V)
+        V = V if V.is_floating_point() else V.to(torch.get_default_dtype())
+        v1, v2, v3, v4 = V.unbind(-1)
+        return torch.stack([v1 / 2 + v2 + v3 / 2, v1 / 2 - 3 * v3 / 2, -v2 + 4 * v4, 2 * v3, -4 * v4], -1)
+
+    @classmethod
+    def from_opls(cls, system, top, V, types=None, trainable=True):
+        return cls(system, top, cls.opls_to_multiharmonic(V), types=types, trainable=trainable)
+
+    def table(self):
+        return self._table
+
+    def _hip_ok(self, xyz=None):
+        if xyz is not None and (not xyz.is_cuda or xyz.dtype != torch.float32):
+            return False
+        return self.analytic
+
+    def _reset_topology(self, xyz):          # (static table)
+        pass
+
+    def _torch_energy(self, xyz):
+        """The same energy in torch ops, in the dtype and on the device of xyz (differentiable by autograd in xyz and coeffs)."""
+        top = self.top.to(xyz.device)
+        cell = self.cell.to(xyz)
+        i, j, k, l = top.unbind(1)
+        b1, b2, b3 = xyz[j] - xyz[i], xyz[k] - xyz[j], xyz[l] - xyz[k]
+        b1, b2, b3 = (b + get_offsets(b, cell, xyz.device).to(xyz) * cell for b in (b1, b2, b3))
+        n1, n2 = torch.cross(b1, b2, dim=-1), torch.cross(b2, b3, dim=-1)
+        N1, N2 = n1.pow(2).sum(-1), n2.pow(2).sum(-1)
+        eps2 = 2.0 ** -40
+        ok = (N1 > eps2 * b1.pow(2).sum(-1) * b2.pow(2).sum(-1)) & (N2 > eps2 * b2.pow(2).sum(-1) * b3.pow(2).sum(-1))
+        one = torch.ones_like(N1)
+        c = (n1 * n2).sum(-1) / torch.where(ok, N1 * N2, one).sqrt()
+        a = self.coeffs.to(xyz).reshape(-1, 5)
+        a = a[self.types.to(xyz.device)] if self.types is not None else a[:1].expand(c.shape[0], 5)
+        u = a[:, 0] + c * (a[:, 1] + c * (a[:, 2] + c * (a[:, 3] + c * a[:, 4])))
+        return torch.where(ok, u, torch.zeros_like(u)).sum(-1)
+
+    def forward(self, xyz):
+        if self._hip_ok(xyz):
+            return ops.DihedralEnergyFn.apply(xyz.contiguous(), self.coeffs, self._table)
+        return self._torch_energy(xyz)
+
+    # -- analytic-adjoint protocol (md._EOM.rhs_vjp, Stack.force / force_vjp) -------------------------------------
+    def supports_force_vjp(self):
+        return self._hip_ok()
+
+    def force(self, xyz, into=None):
+        o = ops.dihedral_eval(self._table, xyz.detach(), self.coeffs, into=None if into is None else (into, None), scale=-1.0)
+        return o["grad"]
+
+    def force_vjp(self, xyz, w, want_theta=True, accum=None, into=None):
+        """(F, d(w.F)/dx, [d(w.F)/dcoeffs]) in one launch plus the fixed-order reduction of the parameter part; `accum`
+        (ops.ThetaAccum): that part is added into its flat buffer instead (None returned)."""
+        need = bool(want_theta) and isinstance(self.coeffs, torch.nn.Parameter)
+        o = ops.dihedral_eval(self._table, xyz.detach(), self.coeffs, w=w.detach(), into=into, scale=-1.0, terms=need)
+        if not want_theta:
+            return o["grad"], o["hw"], None
+        if not need:
+            return o["grad"], o["hw"], ([] if accum is None else None)
+        gw = ops.dihedral_coeff_grad(self._table, o["c_term"], o["cd_term"], want_u=False)[1]       # d(w.dU/dx)/dcoeffs
+        if accum is not None:
+            jobs = ops.GradJobs()
+            jobs.axpy(accum.off[id(self.coeffs)], gw)
+            jobs.run(accum, alpha=-1.0, accumulate=True)
+            return o["grad"], o["hw"], None
+        return o["grad"], o["hw"], [-gw.reshape(self.coeffs.shape)]
+
+    # -- fixed-capacity topology (HIP-graph capture): the table is static, nothing can overflow ------------------
+    def supports_static_topology(self):
+        return self._hip_ok()
+
+    def set_static_topology(self, on=True):
+        pass
+
+    def static_overflow(self):
+        return False
+
+    def static_version(self):
+        return 0
+
+
 class Stack(torch.nn.Module):
     """torchmd/interface.py:364-403."""
 

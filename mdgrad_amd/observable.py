@@ -208,6 +208,95 @@ class angle_distribution(Angles):
         return self.bins, count, angles
 
 
+def compute_dihe(xyz, dihes):
+    """torchmd/observable.py:181-197: cos of the dihedral angle of every row (i, j, k, l) of `dihes` in every frame of xyz
+    [F, N, 3] -> [F, n].  No periodic imaging, as in the reference (Dihedrals images the bond vectors).  Torch ops with the
+    cross products taken along the last axis explicitly: the reference's torch.cross without `dim` picks the first axis of
+    size 3, so it is wrong for three frames or three rows."""
+    assert len(xyz.shape) == 3
+    d = torch.as_tensor(dihes).to(xyz.device).to(torch.long).reshape(-1, 4)
+    xi, xj, xk, xl = (xyz[:, d[:, a]] for a in range(4))
+    cross1 = torch.cross(xj - xi, xj - xk, dim=-1)
+    cross2 = torch.cross(xk - xj, xk - xl, dim=-1)
+    norm = (cross1.pow(2).sum(-1) * cross2.pow(2).sum(-1)).sqrt()
+    return (cross1 * cross2).sum(-1) / norm
+
+
+DIHEDRAL_MAX_BINS, DIHEDRAL_MAX_WIDTH = 4096, 0.5                      # csrc/dihedral.hip
+
+
+class Dihedrals(Observable):
+    """Signed dihedral angles over a static table `top` [n_terms, 4] of quadruples (i, j, k, l).
+
+    With b1 = x_j - x_i, b2 = x_k - x_j, b3 = x_l - x_k, each re-imaged with topology.get_offsets on the diagonal of the cell
+    (so wrapped frames, as Simulations returns them, are fine), n1 = b1 x b2 and n2 = b2 x b3:
+
+        phi = atan2(|b2| b1.n2, n1.n2)  in (-pi, pi]        cos phi = n1.n2 / sqrt(|n1|^2 |n2|^2)
+
+    This is the IUPAC sign.  cos phi is the reference's compute_dihe (torchmd/observable.py:181-197) wherever every bond vector
+    is shorter than half the box; the signed dihedral d_i of the polymer demo's compute_intcoord (demo/fold.py:57-72) is -phi
+    wherever that function does not clamp.  A term with three collinear atoms (|n1|^2 <= eps^2 |b1|^2 |b2|^2 or
+    |n2|^2 <= eps^2 |b2|^2 |b3|^2, eps = 2^-20) is skipped: phi = cos phi = 0 with zero gradient.
+
+    forward(xyz) -> phi [F, n_terms] and cos(xyz) -> cos phi [F, n_terms], with xyz reshaped to (-1, natoms, 3) like the other
+    observables: replica-stacked trajectories [T, R N, 3] give T R frames with a `top` over one replica's atoms; a `top` that
+    names atoms of the whole stacked system keeps them as T frames of R N atoms.  HIP kernels forward and backward
+    (ops.DihedralPhiFn, csrc/dihedral.hip); the gradient of phi has no 1 / sin phi and is finite at phi = 0 and +-pi.
+    Differentiable once."""
+
+    def __init__(self, system, top):
+        super().__init__(system)
+        self.top = torch.as_tensor(top).to(torch.long).reshape(-1, 4)
+        total = system.get_number_of_atoms()
+        if self.top.numel() and int(self.top.max()) >= self.natoms and total > self.natoms:
+            self.natoms = total                            # the table indexes the stacked system
+        self._table = ops.DihedralTable(self.top, self.natoms, self.cell.detach().cpu().tolist(), self.device)
+        self.n_terms = self._table.n_terms
+
+    def _phi_cos(self, xyz):
+        return ops.DihedralPhiFn.apply(xyz.reshape(-1, self.natoms, 3), self._table)
+
+    def cos(self, xyz):
+        return self._phi_cos(xyz)[1]
+
+    def forward(self, xyz):
+        return self._phi_cos(xyz)[0]
+
+
+class dihedral_distribution(Dihedrals):
+    """Periodic Gaussian-smeared histogram of the signed dihedral angles of Dihedrals, in the shape of angle_distribution:
+    forward(xyz) -> (bins, count, phi).
+
+        bins = linspace(-pi, pi, nbins + 1),   centres mu_b = -pi + (b + 1/2) 2 pi / nbins,   width default 2 pi / nbins
+        raw[b] = sum over frames and terms of exp(-1/2 (wrap(phi - mu_b) / width)^2),        count = raw / raw.sum()
+
+    wrap maps onto [-pi, pi): an angle near pi also feeds the bins near -pi.  Only the nearest image of a centre counts, so
+    width > 0.5 is refused (beyond it the neglected second image exceeds exp(-pi^2 / (2 0.25)) ~ 3e-9 of a peak term);
+    centres farther than 5.3 width sqrt(2 ln 2) from an angle are dropped (below 2^-28 of a peak term, the reach of
+    angle_distribution).  Skipped (degenerate) terms carry no weight.  phi [F, n_terms] is None with keep_angles=False.
+    HIP kernels forward and backward (ops.DihedralHistFn, ops.DihedralPhiFn), bitwise reproducible, differentiable once."""
+
+    def __init__(self, system, top, nbins, width=None, keep_angles=True):
+        super().__init__(system, top)
+        if not (isinstance(nbins, (int, np.integer)) and 1 <= int(nbins) <= DIHEDRAL_MAX_BINS):
+            raise ValueError("dihedral_distribution: nbins must be an integer in 1..%d, got %r" % (DIHEDRAL_MAX_BINS, nbins))
+        self.nbins = int(nbins)
+        self.spacing = 2.0 * math.pi / self.nbins
+        self.width = self.spacing if width is None else float(width)
+        if not (0.0 < self.width <= DIHEDRAL_MAX_WIDTH):
+            raise ValueError("dihedral_distribution: width must be in (0, %g] (nearest image only), got %r%s"
+                             % (DIHEDRAL_MAX_WIDTH, self.width, "; give a width with fewer than 13 bins" if width is None else ""))
+        self.coeff = -0.5 / self.width ** 2
+        self.bins = torch.linspace(-math.pi, math.pi, self.nbins + 1).to(self.device)
+        self.offsets = (-math.pi + (torch.arange(self.nbins, dtype=torch.float64) + 0.5) * self.spacing).to(torch.float32).to(self.device)
+        self.keep_angles = keep_angles
+
+    def forward(self, xyz):
+        phi, cos = self._phi_cos(xyz)
+        raw = ops.DihedralHistFn.apply(phi, cos, self.nbins, self.width)
+        return self.bins, raw / raw.sum(), (phi if self.keep_angles else None)
+
+
 SK_MAX_VECTORS, SK_MAX_BINS, SK_MAX_INDEX = 65536, 1024, 1024          # csrc/sk.hip
 
 

@@ -9,6 +9,8 @@ torch.autograd.Function wrappers that own the differentiation contract
     SkFn                                                        static structure factor of every frame
     MsdFn                                                       mean-squared displacement over all lags (+ fourth moment)
     IsfFn                                                       intermediate scattering functions F(k,t), F_s(k,t)
+    DihedralEnergyFn -> DihedralGradFn                          torsion term, order <= 2 in x, 1 in its coefficients
+    DihedralPhiFn, DihedralHistFn                               signed dihedral angles of every frame, their periodic histogram
 
 Everything here requires HIP tensors; there is no CPU path.
 """
@@ -338,6 +340,205 @@ class BondedEnergyFn(torch.autograd.Function):
     def backward(ctx, gU):
         (xyz,) = ctx.saved_tensors
         return gU * BondedGradFn.apply(xyz, ctx.tab, ctx.cache), None
+
+
+# ----------------------------------------------------------------------------- dihedral terms (K19)
+class DihedralTable:
+    """Static table of dihedral quadruples for the kernels of csrc/dihedral.hip: `top` [n_terms, 4] rows (i, j, k, l) as
+    int32 on the device, the optional per-term `types` in [0, n_types), and the incidence list of every atom -- entries
+    4 * term + role, ascending per atom -- built once on the host.  Indices outside [0, n_atoms) and rows that name an atom
+    twice are refused."""
+
+    def __init__(self, top, n_atoms, cell_len, device, types=None, n_types=1):
+        import numpy as np
+        t = torch.as_tensor(top).detach().cpu().numpy().astype(np.int64).reshape(-1, 4)
+        if t.size and (t.min() < 0 or t.max() >= n_atoms):
+            raise ValueError("mdgrad_amd: dihedral topology refers to atoms outside [0, %d)" % n_atoms)
+        s = np.sort(t, axis=1)
+        if t.size and bool((s[:, 1:] == s[:, :-1]).any()):
+            raise ValueError("mdgrad_amd: a dihedral row names the same atom twice")
+        self.n_atoms, self.n_terms, self.n_types = int(n_atoms), int(t.shape[0]), int(n_types)
+        if self.n_types < 1:
+            raise ValueError("mdgrad_amd: a dihedral table needs at least one type")
+        atoms = t.reshape(-1)
+        codes = (4 * np.repeat(np.arange(self.n_terms), 4) + np.tile(np.arange(4), self.n_terms)).astype(np.int64)
+        order = np.lexsort((codes, atoms))                       # by atom, then by (term, role)
+        ptr_ = np.zeros(n_atoms + 1, dtype=np.int64)
+        np.add.at(ptr_, atoms + 1, 1)
+        i32 = dict(dtype=torch.int32, device=device)
+        self.top = torch.as_tensor(t.astype(np.int32).copy(), **i32).contiguous()
+        self.inc_ptr = torch.as_tensor(np.cumsum(ptr_).astype(np.int32), **i32)
+        self.inc = torch.as_tensor(codes[order].astype(np.int32), **i32)
+        self.types = None
+        if types is not None:
+            ty = torch.as_tensor(types).detach().cpu().numpy().astype(np.int64).reshape(-1)
+            if ty.shape[0] != self.n_terms:
+                raise ValueError("mdgrad_amd: dihedral types must hold one entry per term (%d), got %d" % (self.n_terms, ty.shape[0]))
+            if ty.size and (ty.min() < 0 or ty.max() >= self.n_types):
+                raise ValueError("mdgrad_amd: dihedral types must lie in [0, %d)" % self.n_types)
+            self.types = torch.as_tensor(ty.astype(np.int32), **i32)
+        self.cell_len = (C.c_float * 3)(*[float(x) for x in cell_len])
+
+
+def _dihedral_coeff(tab, coeff):
+    require_gpu(coeff, "coeffs")
+    if coeff.numel() != 5 * tab.n_types:
+        raise ValueError("mdgrad_amd: coeffs must be [%d, 5] (got %s)" % (tab.n_types, tuple(coeff.shape)))
+    return coeff.detach().contiguous()
+
+
+def dihedral_eval(tab, xyz, coeff, w=None, energy=False, grad=True, into=None, scale=1.0, terms=False):
+    """One launch of mdg_dihedral_eval -> dict(e_atom, grad, hw, c_term, cd_term).  `into` = (grad buffer, hw buffer or
+    None): the per-atom outputs are ADDED onto them, times `scale`.  terms=True also returns cos phi of every term and, with
+    `w`, its directional derivative (what dihedral_coeff_grad reduces to the parameter gradients)."""
+    lib = _lib.load()
+    require_gpu(xyz, "xyz")
+    if xyz.shape != (tab.n_atoms, 3):
+        raise ValueError("mdgrad_amd: xyz must be [%d, 3] (got %s)" % (tab.n_atoms, tuple(xyz.shape)))
+    xyz = xyz.contiguous()
+    coeff = _dihedral_coeff(tab, coeff)
+    dev, N = xyz.device, tab.n_atoms
+    acc = into is not None
+    e = torch.empty(N, device=dev) if energy else None
+    g = (into[0] if acc else torch.empty(N, 3, device=dev)) if grad else None
+    hw = None
+    if w is not None:
+        require_gpu(w, "w")
+        w = w.contiguous()
+        hw = into[1] if acc else torch.empty(N, 3, device=dev)
+    ct = torch.empty(tab.n_terms, device=dev) if terms else None
+    cd = torch.empty(tab.n_terms, device=dev) if (terms and w is not None) else None
+    check(lib.mdg_dihedral_eval(ptr(xyz), N, tab.cell_len, ptr(tab.top), tab.n_terms, ptr(coeff), ptr(tab.types), tab.n_types,
+                                ptr(tab.inc_ptr), ptr(tab.inc), ptr(w), ptr(e), ptr(g), ptr(hw), ptr(ct), ptr(cd), float(scale),
+                                int(acc), stream_ptr(dev)), "mdg_dihedral_eval")
+    return dict(e_atom=e, grad=g, hw=hw, c_term=ct, cd_term=cd)
+
+
+def dihedral_coeff_grad(tab, c_term, cd_term=None, want_u=True):
+    """(dU/dcoeffs, d(w.dU/dx)/dcoeffs), each [n_types, 5] or None, from the per-term outputs of dihedral_eval: one launch,
+    fixed summation order."""
+    lib = _lib.load()
+    dev = c_term.device
+    gu = torch.empty(tab.n_types, 5, device=dev) if want_u else None
+    gw = torch.empty(tab.n_types, 5, device=dev) if cd_term is not None else None
+    check(lib.mdg_dihedral_coeff_grad(ptr(c_term), ptr(cd_term), ptr(tab.types), tab.n_terms, tab.n_types, ptr(gu), ptr(gw),
+                                      stream_ptr(dev)), "mdg_dihedral_coeff_grad")
+    return gu, gw
+
+
+class DihedralGradFn(torch.autograd.Function):
+    """(dU/dx, dU/dcoeffs) of the torsion term as a differentiable op; backward = the Hessian-vector product and the mixed
+    derivative d(w.dU/dx)/dcoeffs (the second autograd pass of torchmd/sovlers.py:229-233).  A cotangent on dU/dcoeffs (second
+    derivatives with respect to the coefficients alone, or dU/dcoeffs differentiated in x) is not provided."""
+
+    @staticmethod
+    def forward(ctx, xyz, coeff, tab, cache):
+        ctx.tab = tab
+        ctx.save_for_backward(xyz, coeff)
+        ctx.set_materialize_grads(False)
+        if cache is None:
+            o = dihedral_eval(tab, xyz, coeff, terms=True)
+            cache = (o["grad"], dihedral_coeff_grad(tab, o["c_term"])[0].reshape(coeff.shape))
+        return cache
+
+    @staticmethod
+    def backward(ctx, wg, wgth):
+        xyz, coeff = ctx.saved_tensors
+        if wgth is not None:
+            raise NotImplementedError("mdgrad_amd: derivatives of dU/dcoeffs of the torsion term (a cotangent on it) are not "
+                                      "provided by the HIP kernels")
+        if wg is None:
+            return None, None, None, None
+        o = dihedral_eval(ctx.tab, xyz, coeff, w=wg.detach().contiguous(), grad=False, terms=True)
+        gw = dihedral_coeff_grad(ctx.tab, o["c_term"], o["cd_term"], want_u=False)[1]
+        return o["hw"], gw.reshape(coeff.shape), None, None
+
+
+class DihedralEnergyFn(torch.autograd.Function):
+    """U(x, coeffs) = sum_terms sum_m coeffs[type, m] cos^m phi (csrc/dihedral.hip), differentiable twice in x and once in
+    the coefficients."""
+
+    @staticmethod
+    def forward(ctx, xyz, coeff, tab):
+        o = dihedral_eval(tab, xyz, coeff, energy=True, grad=True, terms=True)
+        ctx.tab = tab
+        ctx.cache = (o["grad"], dihedral_coeff_grad(tab, o["c_term"])[0].reshape(coeff.shape))
+        ctx.save_for_backward(xyz, coeff)
+        return o["e_atom"].sum()
+
+    @staticmethod
+    def backward(ctx, gU):
+        xyz, coeff = ctx.saved_tensors
+        g, gth = DihedralGradFn.apply(xyz, coeff, ctx.tab, ctx.cache)
+        return gU * g, gU * gth, None
+
+
+class DihedralPhiFn(torch.autograd.Function):
+    """(phi, cos phi) [F, n_terms] of every term of a DihedralTable in every frame of xyz [F, N, 3] (mdg_dihedral_phi_fwd /
+    _bwd), differentiable once.  Skipped (degenerate) terms give 0 in both with zero gradient."""
+
+    @staticmethod
+    def forward(ctx, xyz, tab):
+        lib = _lib.load()
+        require_gpu(xyz, "xyz")
+        if xyz.dim() != 3 or tuple(xyz.shape[1:]) != (tab.n_atoms, 3):
+            raise ValueError("mdgrad_amd: xyz must be [F, %d, 3] (got %s)" % (tab.n_atoms, tuple(xyz.shape)))
+        x3 = xyz.detach().contiguous()
+        F, dev = x3.shape[0], x3.device
+        phi, cos = torch.empty(F, tab.n_terms, device=dev), torch.empty(F, tab.n_terms, device=dev)
+        if F:
+            check(lib.mdg_dihedral_phi_fwd(ptr(x3), F, tab.n_atoms, tab.cell_len, ptr(tab.top), tab.n_terms, ptr(phi), ptr(cos),
+                                           stream_ptr(dev)), "mdg_dihedral_phi_fwd")
+        ctx.tab = tab
+        ctx.save_for_backward(x3)
+        ctx.set_materialize_grads(False)
+        return phi, cos
+
+    @staticmethod
+    def backward(ctx, g_phi, g_cos):
+        (x3,) = ctx.saved_tensors
+        tab = ctx.tab
+        if (g_phi is None and g_cos is None) or x3.shape[0] == 0:
+            return torch.zeros_like(x3), None
+        gp = None if g_phi is None else g_phi.detach().to(torch.float32).contiguous()
+        gc = None if g_cos is None else g_cos.detach().to(torch.float32).contiguous()
+        gx = torch.empty_like(x3)
+        check(_lib.load().mdg_dihedral_phi_bwd(ptr(x3), x3.shape[0], tab.n_atoms, tab.cell_len, ptr(tab.top), tab.n_terms,
+                                               ptr(tab.inc_ptr), ptr(tab.inc), ptr(gp), ptr(gc), ptr(gx), stream_ptr(x3.device)),
+              "mdg_dihedral_phi_bwd")
+        return gx, None
+
+
+class DihedralHistFn(torch.autograd.Function):
+    """raw[b] = sum exp(-1/2 (wrap(phi - mu_b) / width)^2) over all entries of phi, mu_b = -pi + (b + 1/2) 2 pi / nbins
+    (mdg_dihedral_hist_fwd / _bwd).  `cos` (the cosines that came with phi) only marks the skipped terms; the gradient goes
+    to phi."""
+
+    @staticmethod
+    def forward(ctx, phi, cos, nbins, width):
+        lib = _lib.load()
+        require_gpu(phi, "phi")
+        p = phi.detach().contiguous()
+        c = None if cos is None else cos.detach().contiguous()
+        dev, n = p.device, p.numel()
+        raw = torch.empty(int(nbins), device=dev)
+        scratch = torch.empty(int(lib.mdg_dihedral_hist_scratch(n, int(nbins))), dtype=torch.int64, device=dev)
+        check(lib.mdg_dihedral_hist_fwd(ptr(p), ptr(c), n, int(nbins), float(width), ptr(raw), ptr(scratch), stream_ptr(dev)),
+              "mdg_dihedral_hist_fwd")
+        ctx.args = (int(nbins), float(width), c is not None)
+        ctx.save_for_backward(*((p, c) if c is not None else (p,)))
+        return raw
+
+    @staticmethod
+    def backward(ctx, g_raw):
+        nbins, width, has_cos = ctx.args
+        p = ctx.saved_tensors[0]
+        c = ctx.saved_tensors[1] if has_cos else None
+        gr = g_raw.detach().to(torch.float32).contiguous()
+        gp = torch.empty_like(p)
+        check(_lib.load().mdg_dihedral_hist_bwd(ptr(p), ptr(c), p.numel(), nbins, width, ptr(gr), ptr(gp), stream_ptr(p.device)),
+              "mdg_dihedral_hist_bwd")
+        return gp, None, None, None
 
 
 # ----------------------------------------------------------------------------- fused trajectories

@@ -97,3 +97,28 @@ def generate_angle_list(nbr_list):
     except torch.cuda.OutOfMemoryError as e:
         raise ValueError("generate_angle_list: the triplet list does not fit in device memory (%s); "
                          "use angle_distribution(..., keep_angles=False) for the histogram alone" % e) from None
+
+
+def chain_dihedrals(n_atoms, start=0):
+    """[n_atoms - 3, 4] rows (i, i + 1, i + 2, i + 3) of a linear chain whose first atom is `start` (the quadruples the
+    polymer demo's internal coordinates run over, demo/fold.py:57-72); empty below four atoms."""
+    i = torch.arange(max(int(n_atoms) - 3, 0), dtype=torch.long)[:, None] + int(start)
+    return i + torch.arange(4, dtype=torch.long)[None, :]
+
+
+def dihedrals_from_bonds(bonds):
+    """Every proper torsion (i, j, k, l) of a bond graph: i-j, j-k and k-l bonded, i != k, j != l, i != l (three-rings give
+    none).  Each torsion appears once, with j < k, ordered lexicographically by (j, k, i, l).  bonds: [n_bonds, 2]; returns
+    int64 [n, 4] on the host."""
+    b = torch.as_tensor(bonds).detach().cpu().to(torch.long).reshape(-1, 2).tolist()
+    nbrs = {}
+    for i, j in b:
+        if i != j:
+            nbrs.setdefault(i, set()).add(j)
+            nbrs.setdefault(j, set()).add(i)
+    rows = []
+    for j, k in sorted({(min(i, j), max(i, j)) for i, j in b if i != j}):
+        for i in sorted(nbrs[j] - {k}):
+            for l in sorted(nbrs[k] - {j, i}):
+                rows.append((i, j, k, l))
+    return torch.tensor(rows, dtype=torch.long).reshape(-1, 4)

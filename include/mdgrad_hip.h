@@ -1012,6 +1012,37 @@ int mdg_dihedral_hist_bwd(const float* phi, const float* cosphi, int64_t n, int 
                           float* g_phi, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * K20  damped shifted-force Coulomb sum over the per-atom (ELL) list with one charge per atom (Wolf et al. 1999; Fennell and
+ *      Gezelter 2006; mdgrad_amd/interface.py CoulombPotentials, csrc/coulomb.hip).  With E(r) = erfc(alpha r) and
+ *      G(r) = g0 exp(-alpha^2 r^2), g0 = 2 alpha / sqrt(pi):
+ *        psi(r) = E/r - c0 + c1 (r - rc)      psi' = -E/r^2 - G/r + c1      psi'' = 2E/r^3 + 2G/r^2 + 2 alpha^2 G
+ *        U = conversion [ 1/2 sum_i sum_{j in row(i)} q_i q_j psi(r_ij) - self_s sum_i q_i^2 ]
+ *      MdgCoulombConsts is prepared by the host in double (c0, c1: 0 or the values that make psi / psi' vanish at rc; self_s:
+ *      c0/2 + alpha/sqrt(pi), or 0).  alpha == 0 takes E = 1, G = 0 without evaluating either function.
+ *   mdg_coulomb_eval  laid out like mdg_pair_eval_ell_into (same list, same `accumulate` bits: 1 = add onto grad / hw,
+ *     2 = the list was searched with a skin, re-apply the exact cutoff test per pair; same out_scale), q device float [n_atoms].
+ *     w nullable [n_atoms, 3], required for hw / potw.  Outputs, each nullable:
+ *       energy [1] = U (needs `partial`, mdg_coulomb_partial_size() floats; fixed-order block partials + a finish kernel)
+ *       grad [n_atoms, 3] = (accumulate & 1 ? grad : 0) + out_scale dU/dx,  hw likewise with H w
+ *       pot [n_atoms]  = sum_j q_j psi(r_ij)                      (dU/dq_i = conversion (pot_i - 2 self_s q_i))
+ *       potw [n_atoms] = sum_j q_j psi'(r_ij) rhat_ij.(w_i - w_j)  (d(w.dU/dx)/dq_i = conversion potw_i)
+ *     No atomics: bitwise reproducible.
+ *   mdg_coulomb_charge_reduce  out[p] = sum of val[i] over the atoms with slot(i) == p, p in [0, n_slots), in a fixed order:
+ *     slot(i) = types[i % group] (types device int32 [group], n_slots = number of types) or i % group (types null,
+ *     n_slots = group).  n_atoms must be a multiple of group.
+ */
+typedef struct MdgCoulombConsts {
+    double alpha, rc, c0, c1, g0, alpha2, conversion, self_s;
+} MdgCoulombConsts;
+int64_t mdg_coulomb_partial_size(int n_atoms);
+int mdg_coulomb_eval(const float* pos, int n_atoms, const MdgCell* cell /*host*/, const int32_t* col, const int32_t* shift,
+                     const int32_t* cnt, int max_nbr, const float* q, const MdgCoulombConsts* consts /*host*/, const float* w,
+                     float* energy, float* grad, float* hw, float* pot, float* potw, float* partial, float out_scale,
+                     int accumulate, void* stream);
+int mdg_coulomb_charge_reduce(const float* val, const int32_t* types, int n_atoms, int group, int n_slots, float* out,
+                              void* stream);
+
+/* ------------------------------------------------------------------------------------
  * f4  bonded terms over a static topology table (csrc/bonded.hip).
  * Replaces torchmd/interface.py:447-455 (BondPotentials.forward: harmonic in the SQUARED bond length,
  * 1/2 k (|b|^2 - ro)^2) and :496-508 (AnglePotentials.forward: 1/2 k (theta - theta0)^2 over triples (i, j, k) centred on

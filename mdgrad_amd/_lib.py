@@ -60,6 +60,11 @@ class MdgGradJob(C.Structure):
 GRAD_ATB, GRAD_COLSUM, GRAD_AXPY, GRAD_JOBS_MAX = 0, 1, 2, 32
 
 
+class MdgCoulombConsts(C.Structure):
+    """Constants of the damped shifted-force Coulomb sum, prepared in double (include/mdgrad_hip.h K20)."""
+    _fields_ = [(n, C.c_double) for n in ("alpha", "rc", "c0", "c1", "g0", "alpha2", "conversion", "self_s")]
+
+
 class MdgChainStage(C.Structure):
     """One Dense stage of mdg_row_chain (include/mdgrad_hip.h)."""
     _fields_ = [(n, C.c_void_p) for n in ("W", "bias", "in0", "in1", "res0", "res1", "aux0", "aux1", "out0", "out1", "sig",
@@ -262,6 +267,10 @@ _SIGNATURES = {
     "mdg_dihedral_hist_scratch": (C.c_int64, [C.c_int64, C.c_int]),
     "mdg_dihedral_hist_fwd": (C.c_int, [P, P, C.c_int64, C.c_int, C.c_float, P, P, P]),
     "mdg_dihedral_hist_bwd": (C.c_int, [P, P, C.c_int64, C.c_int, C.c_float, P, P, P]),
+    "mdg_coulomb_partial_size": (C.c_int64, [C.c_int]),
+    "mdg_coulomb_eval": (C.c_int, [P, C.c_int, C.POINTER(MdgCell), P, P, P, C.c_int, P, C.POINTER(MdgCoulombConsts), P,
+                                   P, P, P, P, P, P, C.c_float, C.c_int, P]),
+    "mdg_coulomb_charge_reduce": (C.c_int, [P, P, C.c_int, C.c_int, C.c_int, P, P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

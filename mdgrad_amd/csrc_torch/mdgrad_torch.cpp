@@ -17,6 +17,7 @@
 //   msd_fwd/msd_bwd  K17  observable.py msd                  -> mdg_msd_fwd / mdg_msd_bwd
 //   isf_fwd/isf_bwd  K18  observable.py intermediate_scattering -> mdg_isf_fwd / mdg_isf_bwd
 //   dihedral_eval    K19  interface.py DihedralPotentials     -> mdg_dihedral_eval
+//   coulomb_eval, coulomb_charge_reduce  K20  interface.py CoulombPotentials  -> mdg_coulomb_eval / mdg_coulomb_charge_reduce
 //   dihedral_phi_fwd/_bwd, dihedral_hist_fwd/_bwd  K19  observable.py Dihedrals / dihedral_distribution -> mdg_dihedral_phi_* / _hist_*
 //   edge_geom(+_bwd) schnet.py:142                          -> mdg_edge_geom / mdg_edge_geom_bwd
 //   cfconv_fwd/_bwd  K9+K10 modules.py:531-571              -> mdg_cfconv_fwd(_bf16) / mdg_cfconv_bwd(_bf16)
@@ -729,6 +730,51 @@ Tensor dihedral_hist_bwd(const Tensor& phi, const OptTensor& cosphi, int64_t nbi
     return g;
 }
 
+// ------------------------------------------------------------------------------------------------ K20
+// consts = (alpha, rc, c0, c1, g0, alpha2, conversion, self_s) of MdgCoulombConsts; q float [N].
+// (U [1] or [0], dU/dx [N,3], H w [N,3] or [0], pot [N] or [0], potw [N] or [0]); want_pot: pot without w, potw with it
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> coulomb_eval(const Tensor& pos, at::ArrayRef<double> cell, const Tensor& col,
+                                                                const Tensor& shift, const Tensor& cnt, const Tensor& q,
+                                                                at::ArrayRef<double> consts, const OptTensor& w, bool want_energy,
+                                                                bool want_pot) {
+    check_f32(pos, "pos"); check_f32(q, "q"); same_device(pos, q, "q");
+    TORCH_CHECK(pos.dim() == 2 && pos.size(1) == 3 && pos.size(0) > 0, "mdgrad: pos must be [N,3]");
+    TORCH_CHECK(q.numel() == pos.size(0), "mdgrad: q must hold one charge per atom");
+    TORCH_CHECK(consts.size() == 8, "mdgrad: consts = (alpha, rc, c0, c1, g0, alpha2, conversion, self_s)");
+    const MdgCell c = make_cell(cell);
+    const EllRef e = ell_of(pos, col, shift, cnt);
+    const MdgCoulombConsts k{consts[0], consts[1], consts[2], consts[3], consts[4], consts[5], consts[6], consts[7]};
+    const float* wp = fptr(w, "w");
+    if (wp) { same_device(pos, *w, "w"); TORCH_CHECK(w->sizes() == pos.sizes(), "mdgrad: w must have the shape of pos"); }
+    const int n = (int)pos.size(0);
+    const auto o = pos.options();
+    Tensor U = at::empty({want_energy ? 1 : 0}, o), g = at::empty_like(pos);
+    Tensor hw = wp ? at::empty_like(pos) : at::empty({0}, o);
+    Tensor pot = at::empty({(want_pot && !wp) ? n : 0}, o), potw = at::empty({(want_pot && wp) ? n : 0}, o);
+    Tensor partial = at::empty({mdg_coulomb_partial_size(n)}, o);
+    ok(mdg_coulomb_eval(fptr(pos), n, &c, e.col, e.shift, e.cnt, e.max_nbr, fptr(q), &k, wp, want_energy ? mptr(U) : nullptr,
+                        mptr(g), wp ? mptr(hw) : nullptr, (want_pot && !wp) ? mptr(pot) : nullptr, (want_pot && wp) ? mptr(potw) : nullptr,
+                        mptr(partial), 1.f, 0, stream_of(pos)));
+    return {U, g, hw, pot, potw};
+}
+// out [n_slots] = per-slot sums of val [N]; types int32 [group] or none (slot = atom of a replica, n_slots = group)
+Tensor coulomb_charge_reduce(const Tensor& val, const OptTensor& types, int64_t group, int64_t n_slots) {
+    check_f32(val, "val");
+    TORCH_CHECK(val.dim() == 1 && val.numel() > 0 && val.numel() <= INT32_MAX, "mdgrad: val must be [N]");
+    TORCH_CHECK(group > 0 && val.numel() % group == 0, "mdgrad: N must be a multiple of group");
+    const int32_t* ty = nullptr;
+    if (types.has_value() && types->defined()) {
+        check_i32(*types, "types"); same_device(val, *types, "types");
+        TORCH_CHECK(types->numel() == group, "mdgrad: types must hold one entry per atom of a replica");
+        ty = types->data_ptr<int32_t>();
+    }
+    TORCH_CHECK(n_slots > 0 && n_slots <= INT32_MAX && (ty || n_slots == group), "mdgrad: n_slots must be positive, and equal "
+                "group without types");
+    Tensor out = at::empty({n_slots}, val.options());
+    ok(mdg_coulomb_charge_reduce(fptr(val), ty, (int)val.numel(), (int)group, (int)n_slots, mptr(out), stream_of(val)));
+    return out;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(mdgrad, m) {
@@ -768,6 +814,9 @@ TORCH_LIBRARY(mdgrad, m) {
           "Tensor");
     m.def("dihedral_hist_fwd(Tensor phi, Tensor? cosphi, int nbins, float width) -> Tensor");
     m.def("dihedral_hist_bwd(Tensor phi, Tensor? cosphi, int nbins, float width, Tensor g_raw) -> Tensor");
+    m.def("coulomb_eval(Tensor pos, float[] cell, Tensor col, Tensor shift, Tensor cnt, Tensor q, float[] consts, Tensor? w, "
+          "bool want_energy, bool want_pot) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
+    m.def("coulomb_charge_reduce(Tensor val, Tensor? types, int group, int n_slots) -> Tensor");
     m.def("edge_geom(Tensor x, Tensor? w, Tensor nbr, Tensor offsets) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("edge_geom_bwd(Tensor? d_b, Tensor dd_b, Tensor? d, Tensor? dd, Tensor uhat, Tensor? ddel, Tensor col, Tensor eid, "
           "Tensor cnt) -> (Tensor, Tensor)");
@@ -805,6 +854,8 @@ TORCH_LIBRARY_IMPL(mdgrad, CUDA, m) {      // (the HIP backend registers under t
     m.impl("dihedral_phi_bwd", dihedral_phi_bwd);
     m.impl("dihedral_hist_fwd", dihedral_hist_fwd);
     m.impl("dihedral_hist_bwd", dihedral_hist_bwd);
+    m.impl("coulomb_eval", coulomb_eval);
+    m.impl("coulomb_charge_reduce", coulomb_charge_reduce);
     m.impl("edge_geom", edge_geom);
     m.impl("edge_geom_bwd", edge_geom_bwd);
     m.impl("cfconv_fwd", cfconv_fwd);

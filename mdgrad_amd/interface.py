@@ -1,6 +1,6 @@
 """Energy calculators with the reference's interface (torchmd/interface.py):
-GeneralInteraction :33-57, PairPotentials :217-300, Stack :364-403 (GNNPotentials lives in
-mdgrad_amd.nn).  forward(xyz) -> energy; _reset_topology(xyz) rebuilds the neighbour list.
+GeneralInteraction :33-57, PairPotentials :217-300, Electrostatics :303-361 (as CoulombPotentials), Stack :364-403
+(GNNPotentials lives in mdgrad_amd.nn).  forward(xyz) -> energy; _reset_topology(xyz) rebuilds the neighbour list.
 """
 import inspect
 import os
@@ -8,7 +8,7 @@ import os
 import torch
 from torch.nn import ModuleDict
 
-from . import _lib, ops
+from . import _lib, ops, units
 from .potentials import is_builtin_form
 from .topology import compute_dis, get_offsets
 
@@ -697,6 +697,216 @@ class DihedralPotentials(torch.nn.Module):
 
     def static_version(self):
         return 0
+
+
+class CoulombPotentials(GeneralInteraction):
+    """Point-charge electrostatics as a damped shifted-force real-space sum (Wolf et al. 1999; Fennell and Gezelter 2006):
+    pairwise, O(N), no reciprocal part, energy and force continuous at the cutoff.  The working counterpart of the
+    reference's Electrostatics (torchmd/interface.py:303-361), which overwrites q1 (so it multiplies q_j * q_j) and carries a
+    minus sign that makes like charges attract; with alpha = 0 and shift = "none" this class is the bare truncated Coulomb
+    sum that class meant to write.
+
+    With charges q_i, cutoff rc, damping alpha >= 0, E(r) = erfc(alpha r) and G(r) = (2 alpha / sqrt(pi)) exp(-alpha^2 r^2):
+
+        psi(r)   = E(r)/r - c0 + c1 (r - rc)
+        psi'(r)  = -E/r^2 - G/r + c1
+        psi''(r) = 2E/r^3 + 2G/r^2 + 2 alpha^2 G
+
+        shift = "none":       c0 = 0,         c1 = 0
+        shift = "potential":  c0 = E(rc)/rc,  c1 = 0
+        shift = "force":      c0 = E(rc)/rc,  c1 = E(rc)/rc^2 + G(rc)/rc     (default)
+
+        U = conversion * [ 1/2 sum_i sum_{j in row(i)} q_i q_j psi(r_ij)  -  s sum_i q_i^2 ]
+        s = c0/2 + alpha/sqrt(pi)                                            (s = 0 with self_energy=False)
+
+    row(i) is the neighbour row of the ELL list exactly as PairPotentials uses it: the same minimum image, the same
+    (d2 < rc^2) & (d2 != 0) test and the same index_tuple / ex_pairs mask (ops.build_mask); pairs stay inside their replica.
+    Excluded pairs simply do not interact (no erf correction).  `conversion` defaults to units.ke (eV Angstrom / e^2);
+    reduced-unit users pass 1.0.
+
+    `charges`: [n] with n = system.group_size (one replica's atoms, tiled over the replicas of System.replicate(R)), or
+    [n_types] together with `types` [n]; the parameter `charges` when trainable, otherwise a buffer.  The charges are not
+    constrained: neutrality is the user's business, and a cell that is not neutral has no Ewald limit -- the sum then
+    depends on the cutoff and alpha.
+
+    forward(xyz) is differentiable twice in xyz and once in charges on the HIP kernel (ops.CoulombEnergyFn,
+    csrc/coulomb.hip); force / force_vjp serve the analytic adjoint and HIP-graph replay, also while charges requires grad:
+    d(w.F)/dcharges comes from the same launch plus a fixed-order reduction.  float64 or host positions take the torch
+    restatement `_torch_energy`."""
+
+    accepts_into = True
+    accepts_accum = True
+    analytic = True
+
+    def __init__(self, system, charges, cutoff, alpha=0.0, shift="force", types=None, index_tuple=None, ex_pairs=None,
+                 conversion=units.ke, self_energy=True, trainable=False):
+        super().__init__(system)
+        self.cutoff = float(cutoff)
+        self.alpha, self.shift, self.self_energy = float(alpha), shift, bool(self_energy)
+        self.conversion = float(conversion)
+        self._consts = ops.coulomb_consts(self.cutoff, self.alpha, shift, self.conversion, self.self_energy)
+        n = self._group
+        q = torch.as_tensor(charges, dtype=torch.float32).detach().clone().reshape(-1)
+        if types is None:
+            if q.numel() != n:
+                raise ValueError("CoulombPotentials: charges must hold one entry per atom of a replica (%d), got %d; pass "
+                                 "`types` with per-type charges" % (n, q.numel()))
+            self.types = None
+        else:
+            ty = torch.as_tensor(types).detach().to(torch.long).reshape(-1).cpu()
+            if ty.numel() != n:
+                raise ValueError("CoulombPotentials: types must hold one entry per atom of a replica (%d), got %d" % (n, ty.numel()))
+            if ty.numel() and (int(ty.min()) < 0 or int(ty.max()) >= q.numel()):
+                raise ValueError("CoulombPotentials: types must lie in [0, %d)" % q.numel())
+            self.types = ty.to(self.device)
+        self._slot = None if self.types is None else self.types.to(torch.int32).contiguous()
+        self.n_slots = int(q.numel())
+        q = q.to(self.device)
+        if trainable:
+            self.charges = torch.nn.Parameter(q)
+        else:
+            self.register_buffer("charges", q)
+        self.index_tuple, self.ex_pairs = index_tuple, ex_pairs
+        self._mask = ops.build_mask(n, index_tuple, ex_pairs, system.device)
+        self._n_rep = system.get_number_of_atoms() // n
+        self._ell = None
+        if torch.device(self.device).type == "cuda":
+            self._reset_topology(torch.Tensor(system.get_positions()).to(system.device))
+
+    def _hip_ok(self, xyz=None):
+        if xyz is not None and (not xyz.is_cuda or xyz.dtype != torch.float32):
+            return False
+        return self.analytic and self._ell is not None
+
+    # -- topology: the lists of PairPotentials ---------------------------------------------------------------------
+    def _reset_topology(self, xyz, _cache=None):
+        self._topo_stamp = object()
+        st = self._static if self._static_on else None
+        vkey = ("verlet", float(self.cutoff), None if self._mask is None else self._mask.data_ptr(), self._group)
+        if st is not None and _cache is not None and vkey in _cache:
+            self._ell = _cache[vkey].ell             # a Stack member's Verlet list (exact cutoff re-applied per pair)
+        elif st is not None:
+            self._ell = self._shared_static_ell(xyz, _cache, st)
+        else:
+            self._ell = self._shared_ell(xyz, _cache)
+
+    def supports_static_topology(self):
+        return self._hip_ok()
+
+    def set_static_topology(self, on=True):
+        self._static_on = bool(on)
+        if on and self._static is None:
+            longest = int(self._ell.cnt.max().item())
+            self._static = dict(max_nbr=min(self._group - 1, (int(longest * 1.25) + 15) // 8 * 8),
+                                need=torch.zeros(2, dtype=torch.int32, device=self.device), version=0)
+
+    # -- the per-atom charge buffer the kernel reads ---------------------------------------------------------------
+    def _expand(self, charges):
+        """charges [n] or [n_types] -> one charge per atom of the (replica-stacked) system."""
+        q = charges if self.types is None else charges[self.types.to(charges.device)]
+        return q.repeat(self._n_rep) if self._n_rep > 1 else q
+
+    def _q_atom(self):
+        """charges[types] tiled over the replicas, in a persistent buffer that is refreshed when the charges changed (version
+        counter); inside a HIP-graph capture it is returned as it is -- the replaying pass refreshes it once before its first
+        replay (`prepare_pass`), so the captured steps carry no torch op for it."""
+        c = self.charges
+        buf = getattr(self, "_q_buf", None)
+        capturing = c.is_cuda and torch.cuda.is_current_stream_capturing()
+        if buf is None or buf.device != c.device:
+            if capturing:
+                return self._expand(c.detach()).contiguous()
+            buf = self._q_buf = torch.empty(self._n_rep * self._group, device=c.device, dtype=torch.float32)
+            self._q_key = None
+        if capturing:
+            return buf
+        key = (c.data_ptr(), c._version)
+        if self._q_key != key:
+            buf.copy_(self._expand(c.detach()))
+            self._q_key = key
+        return buf
+
+    def prepare_pass(self):
+        if self._hip_ok():
+            self._q_atom()
+
+    def _spec(self):
+        return ops.CoulombSpec(self._ell, self._consts, self._q_atom(), self._slot, self.n_slots)
+
+    # -- energy ----------------------------------------------------------------------------------------------------
+    def _pairs(self, xyz):
+        """Half list (i, j, image offsets) at xyz: the device list of the last rebuild when there is one (a list searched
+        with a skin is cut to the exact cutoff in _torch_energy), else every pair of a replica by torch ops with the
+        reference's minimum image and selection (torchmd/topology.py:30-73)."""
+        if self._ell is not None and xyz.is_cuda:
+            nbr, off = self._ell.half_list()
+            return nbr[:, 0], nbr[:, 1], off.to(xyz)
+        n, R = self._group, self._n_rep
+        cell = self.cell.detach().to(xyz)
+        cell = torch.diag(cell) if cell.dim() == 1 else cell
+        iu = torch.triu_indices(n, n, offset=1, device=xyz.device)
+        x = xyz.detach().reshape(R, n, 3)
+        D = x[:, iu[1]] - x[:, iu[0]]
+        s = D.matmul(cell.inverse())
+        o = -(s > 0.5).to(xyz) + (s < -0.5).to(xyz)
+        d2 = (D + o.matmul(cell)).pow(2).sum(-1)
+        keep = (d2 < self.cutoff ** 2) & (d2 != 0)
+        if self._mask is not None:
+            keep &= self._mask.to(xyz.device).bool()[iu[0], iu[1]][None, :]
+        rep, idx = torch.nonzero(keep, as_tuple=True)
+        return iu[0][idx] + rep * n, iu[1][idx] + rep * n, o[rep, idx]
+
+    def _torch_energy(self, xyz):
+        """The same energy in torch ops on the half list, in the dtype and on the device of xyz (differentiable by autograd in
+        xyz and charges)."""
+        k = self._consts
+        i, j, off = self._pairs(xyz)
+        cell = self.cell.detach().to(xyz)
+        cell = torch.diag(cell) if cell.dim() == 1 else cell
+        d = xyz[i] - xyz[j] - off.matmul(cell)
+        d2 = d.pow(2).sum(-1)
+        inside = (d2 < k.rc * k.rc) & (d2 != 0)
+        r = torch.where(inside, d2, torch.ones_like(d2)).sqrt()
+        E = torch.erfc(k.alpha * r) if k.alpha != 0.0 else torch.ones_like(r)
+        psi = E / r - k.c0 + k.c1 * (r - k.rc)
+        q = self._expand(self.charges.to(xyz))
+        pair = torch.where(inside, q[i] * q[j] * psi, torch.zeros_like(psi)).sum()
+        return k.conversion * (pair - k.self_s * q.pow(2).sum())
+
+    def forward(self, xyz):
+        if self._hip_ok(xyz):
+            return ops.CoulombEnergyFn.apply(xyz.contiguous(), self.charges, self._spec())
+        return self._torch_energy(xyz)
+
+    # -- analytic-adjoint protocol (md._EOM.rhs_vjp, Stack.force / force_vjp) -------------------------------------
+    def supports_force_vjp(self):
+        return self._hip_ok()
+
+    def force(self, xyz, into=None):
+        """F = -dU/dx in one kernel launch; `into` (a force buffer of another Stack member): added onto it in the same
+        launch and returned."""
+        o = ops.coulomb_eval(self._ell, xyz.detach(), self._q_atom(), self._consts, energy=False, grad=True,
+                             into=None if into is None else (into, None), scale=-1.0)
+        return o["grad"]
+
+    def force_vjp(self, xyz, w, want_theta=True, accum=None, into=None):
+        """(F, d(w.F)/dx, [d(w.F)/dcharges]) in one launch plus the fixed-order reduction of the charge part; `accum`
+        (ops.ThetaAccum): that part is added into its flat buffer instead (None returned).  `into` = (F, dq) buffers of
+        another Stack member: this term's force and d(w.F)/dx are added onto them in the same launch."""
+        need = bool(want_theta) and isinstance(self.charges, torch.nn.Parameter)
+        o = ops.coulomb_eval(self._ell, xyz.detach(), self._q_atom(), self._consts, w=w.detach(), energy=False, grad=True,
+                             into=into, scale=-1.0, want_pot=need)
+        if not want_theta:
+            return o["grad"], o["hw"], None
+        if not need:
+            return o["grad"], o["hw"], ([] if accum is None else None)
+        gw = ops.coulomb_charge_grad(o["potw"], self._slot, self.n_slots)          # d(w.dU/dx)/dcharges / conversion
+        if accum is not None:
+            jobs = ops.GradJobs()
+            jobs.axpy(accum.off[id(self.charges)], gw)
+            jobs.run(accum, alpha=-self.conversion, accumulate=True)
+            return o["grad"], o["hw"], None
+        return o["grad"], o["hw"], [(-self.conversion) * gw.reshape(self.charges.shape)]
 
 
 class Stack(torch.nn.Module):

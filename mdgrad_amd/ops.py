@@ -11,6 +11,7 @@ torch.autograd.Function wrappers that own the differentiation contract
     IsfFn                                                       intermediate scattering functions F(k,t), F_s(k,t)
     DihedralEnergyFn -> DihedralGradFn                          torsion term, order <= 2 in x, 1 in its coefficients
     DihedralPhiFn, DihedralHistFn                               signed dihedral angles of every frame, their periodic histogram
+    CoulombEnergyFn -> CoulombGradFn                            damped shifted-force Coulomb sum, order <= 2 in x, 1 in the charges
 
 Everything here requires HIP tensors; there is no CPU path.
 """
@@ -539,6 +540,138 @@ class DihedralHistFn(torch.autograd.Function):
         check(_lib.load().mdg_dihedral_hist_bwd(ptr(p), ptr(c), p.numel(), nbins, width, ptr(gr), ptr(gp), stream_ptr(p.device)),
               "mdg_dihedral_hist_bwd")
         return gp, None, None, None
+
+
+# ----------------------------------------------------------------------------- Coulomb sum with per-atom charges (K20)
+COULOMB_SHIFTS = ("none", "potential", "force")
+
+
+def coulomb_consts(cutoff, alpha=0.0, shift="force", conversion=1.0, self_energy=True):
+    """MdgCoulombConsts of the damped shifted-force sum, in double: c0, c1 make psi ("potential", "force") and psi' ("force")
+    vanish at the cutoff; self_s = c0 / 2 + alpha / sqrt(pi) is the self term (0 with self_energy=False)."""
+    if shift not in COULOMB_SHIFTS:
+        raise ValueError("mdgrad_amd: shift must be one of %s (got %r)" % (COULOMB_SHIFTS, shift))
+    alpha, rc = float(alpha), float(cutoff)
+    if not alpha >= 0.0:
+        raise ValueError("mdgrad_amd: alpha must be >= 0 (got %r)" % alpha)
+    if not rc > 0.0:
+        raise ValueError("mdgrad_amd: the cutoff must be positive (got %r)" % rc)
+    k = _lib.MdgCoulombConsts()
+    k.alpha, k.rc, k.alpha2, k.conversion = alpha, rc, alpha * alpha, float(conversion)
+    k.g0 = 2.0 * alpha / math.sqrt(math.pi)
+    E, G = math.erfc(alpha * rc), k.g0 * math.exp(-alpha * alpha * rc * rc)
+    k.c0 = E / rc if shift != "none" else 0.0
+    k.c1 = E / (rc * rc) + G / rc if shift == "force" else 0.0
+    k.self_s = 0.5 * k.c0 + alpha / math.sqrt(math.pi) if self_energy else 0.0
+    return k
+
+
+def coulomb_eval(ell, xyz, q_atom, consts, w=None, energy=True, grad=True, into=None, scale=1.0, want_pot=False):
+    """One launch of mdg_coulomb_eval -> dict(energy, grad, hw, pot, potw).  `into` = (grad buffer, hw buffer or None): the
+    per-atom outputs are ADDED onto them, times `scale`, as in pair_eval.  want_pot: without `w` the per-atom potential
+    pot_i = sum_j q_j psi(r_ij), with `w` potw_i = sum_j q_j psi'(r_ij) rhat_ij.(w_i - w_j) -- what coulomb_charge_grad reduces
+    to the charge gradients.  A list searched with a skin (ops.VerletList) gets the exact cutoff test per pair."""
+    lib = _lib.load()
+    require_gpu(xyz, "xyz")
+    require_gpu(q_atom, "q_atom")
+    N = ell.n_atoms
+    if xyz.shape != (N, 3):
+        raise ValueError("mdgrad_amd: xyz must be [%d, 3] (got %s)" % (N, tuple(xyz.shape)))
+    if q_atom.shape != (N,):
+        raise ValueError("mdgrad_amd: q_atom must be [%d] (got %s)" % (N, tuple(q_atom.shape)))
+    xyz = xyz.contiguous()
+    dev = xyz.device
+    acc = into is not None
+    e = torch.empty(1, device=dev) if energy else None
+    g = (into[0] if acc else torch.empty(N, 3, device=dev)) if grad else None
+    hw = pot = potw = None
+    if w is not None:
+        require_gpu(w, "w")
+        w = w.contiguous()
+        hw = into[1] if acc else torch.empty(N, 3, device=dev)
+        potw = torch.empty(N, device=dev) if want_pot else None
+    elif want_pot:
+        pot = torch.empty(N, device=dev)
+    partial = torch.empty(int(lib.mdg_coulomb_partial_size(N)), device=dev) if energy else None
+    recheck = bool(getattr(ell, "verlet", False))
+    check(lib.mdg_coulomb_eval(ptr(xyz), N, C.byref(ell.cell_struct), ptr(ell.col), ptr(ell.shift), ptr(ell.cnt), ell.max_nbr,
+                               ptr(q_atom), C.byref(consts), ptr(w), ptr(e), ptr(g), ptr(hw), ptr(pot), ptr(potw), ptr(partial),
+                               float(scale), int(acc) | (2 if recheck else 0), stream_ptr(dev)), "mdg_coulomb_eval")
+    return dict(energy=e, grad=g, hw=hw, pot=pot, potw=potw)
+
+
+def coulomb_charge_grad(pot, slot, n_slots):
+    """[n_slots] sums of the per-atom values `pot` [N] over the atoms of every charge slot, one launch in a fixed order:
+    `slot` = int32 [group] types of one replica's atoms (slot(i) = slot[i % group]) or None (slot(i) = i % n_slots)."""
+    lib = _lib.load()
+    require_gpu(pot, "pot")
+    pot = pot.contiguous()
+    group = int(slot.numel()) if slot is not None else int(n_slots)
+    out = torch.empty(int(n_slots), device=pot.device)
+    check(lib.mdg_coulomb_charge_reduce(ptr(pot), ptr(slot), pot.numel(), group, int(n_slots), ptr(out), stream_ptr(pot.device)),
+          "mdg_coulomb_charge_reduce")
+    return out
+
+
+class CoulombSpec:
+    """What the autograd functions below need beside the tensors: the list, the constants, the per-atom charge buffer
+    (charges[types] tiled over the replicas, kept current by CoulombPotentials) and the charge slots."""
+
+    def __init__(self, ell, consts, q_atom, slot, n_slots):
+        self.ell, self.consts, self.q_atom, self.slot, self.n_slots = ell, consts, q_atom, slot, int(n_slots)
+
+
+class CoulombGradFn(torch.autograd.Function):
+    """(dU/dx, dU/dcharges) as a differentiable op; backward = the Hessian-vector product and the mixed derivative
+    d(w.dU/dx)/dcharges (the second autograd pass of torchmd/sovlers.py:229-233).  A cotangent on dU/dcharges is not
+    provided."""
+
+    @staticmethod
+    def forward(ctx, xyz, charges, spec, cache):
+        ctx.spec = spec
+        ctx.save_for_backward(xyz, charges)
+        ctx.set_materialize_grads(False)
+        if cache is None:
+            cache = _coulomb_first_order(spec, xyz, charges, energy=False)[1:]
+        return cache
+
+    @staticmethod
+    def backward(ctx, wg, wq):
+        xyz, charges = ctx.saved_tensors
+        s = ctx.spec
+        if wq is not None:
+            raise NotImplementedError("mdgrad_amd: derivatives of dU/dcharges of the Coulomb term (a cotangent on it) are not "
+                                      "provided by the HIP kernels")
+        if wg is None:
+            return None, None, None, None
+        o = coulomb_eval(s.ell, xyz, s.q_atom, s.consts, w=wg.detach().contiguous(), energy=False, grad=False, want_pot=True)
+        gq = coulomb_charge_grad(o["potw"], s.slot, s.n_slots) * float(s.consts.conversion)
+        return o["hw"], gq.reshape(charges.shape), None, None
+
+
+def _coulomb_first_order(spec, xyz, charges, energy):
+    o = coulomb_eval(spec.ell, xyz, spec.q_atom, spec.consts, energy=energy, grad=True, want_pot=True)
+    k = spec.consts
+    dq_atom = float(k.conversion) * (o["pot"] - (2.0 * float(k.self_s)) * spec.q_atom)         # dU/dq_i
+    return o["energy"], o["grad"], coulomb_charge_grad(dq_atom, spec.slot, spec.n_slots).reshape(charges.shape)
+
+
+class CoulombEnergyFn(torch.autograd.Function):
+    """U(x, charges) of the damped shifted-force Coulomb sum (csrc/coulomb.hip), differentiable twice in x and once in
+    the charges."""
+
+    @staticmethod
+    def forward(ctx, xyz, charges, spec):
+        e, g, gq = _coulomb_first_order(spec, xyz, charges, energy=True)
+        ctx.spec, ctx.cache = spec, (g, gq)
+        ctx.save_for_backward(xyz, charges)
+        return e.reshape(())
+
+    @staticmethod
+    def backward(ctx, gU):
+        xyz, charges = ctx.saved_tensors
+        g, gq = CoulombGradFn.apply(xyz, charges, ctx.spec, ctx.cache)
+        return gU * g, gU * gq, None
 
 
 # ----------------------------------------------------------------------------- fused trajectories

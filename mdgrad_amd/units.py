@@ -5,6 +5,9 @@ fs = 0.09822694788464063        # Angstrom * sqrt(amu / eV)
 C = 6.241509125883258e+18
 m = 1e10
 _Nav = 6.022140857e+23
+# Coulomb constant in eV * Angstrom / e^2: what the reference's  k_e * units.C**-2 * (1 / EV_TO_J) * units.m  evaluates to
+# (torchmd/interface.py:331-333, k_e = 8.987551787e9, EV_TO_J = 1.60210e-19)
+ke = 14.400334017702676
 
 
 def get_unit_len(rho, mass, N_unitcell):

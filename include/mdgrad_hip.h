@@ -1043,6 +1043,34 @@ int mdg_coulomb_charge_reduce(const float* val, const int32_t* types, int n_atom
                               void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * K21  reciprocal-space part of the Ewald sum for point charges (mdgrad_amd/interface.py EwaldReciprocal, csrc/ewald.hip).
+ *      For one replica on a diagonal cell L = (Lx, Ly, Lz), V = Lx Ly Lz, with charges q_i and the wave vectors
+ *      k(n) = 2 pi (nx / Lx, ny / Ly, nz / Lz), integer n != 0 of one half space (k and -k contribute equally), |k| <= k_cutoff:
+ *        rho(k) = A + iB = sum_j q_j exp(i k.x_j)
+ *        c(k)   = (4 pi / V) exp(-k^2 / (4 alpha^2)) / k^2                      (host, double -> the float table `coef`)
+ *        U_rec  = conversion [ sum_k c(k) |rho(k)|^2  -  pi (sum_j q_j)^2 / (2 V alpha^2) ]
+ *      The second term (the neutralising background; zero for a neutral cell), the conversion and the self term
+ *      -alpha / sqrt(pi) sum q_i^2 (K20's self_s with shift "none") are the caller's: the kernels work on `coef` as given.
+ *      With c_i = cos k.x_i, s_i = sin k.x_i, a direction w, kw_i = k.w_i and sigma(k) = sum_j q_j kw_j exp(i k.x_j):
+ *        energy  = sum over replicas and k of coef(k) (A^2 + B^2)
+ *        dU/dx_i = sum_k 2 coef q_i k (B c_i - A s_i)
+ *        pot_i   = sum_k 2 coef (A c_i + B s_i)                                 (dU/dq_i before background and conversion)
+ *        (H w)_i = sum_k 2 coef q_i k [ Re sigma c_i + Im sigma s_i - kw_i (A c_i + B s_i) ]
+ *        potw_i  = sum_k 2 coef [ kw_i (B c_i - A s_i) + Re sigma s_i - Im sigma c_i ]       (d(w.dU/dx)/dq_i)
+ *   mdg_ewald_eval  pos [n_rep, n_atoms, 3] (the replicas of System.replicate; positions need not be wrapped), q [n_rep,
+ *     n_atoms], kvec int32 [n_vecs, 3] with |n_d| <= 1024 (the caller's guarantee: the table lives on the device), coef
+ *     [n_vecs], w nullable [n_rep, n_atoms, 3] (required for hw / potw).  Limits: n_atoms <= 32 768, 1 <= n_vecs <= 65 536.
+ *     workspace: mdg_ewald_workspace() floats; it holds (A, B, Re sigma, Im sigma) per (replica, vector) afterwards.
+ *     Outputs, each nullable: energy [1]; grad [n_rep n_atoms, 3] = (accumulate & 1 ? grad : 0) + out_scale dU/dx, hw
+ *     likewise with H w; pot, potw [n_rep n_atoms].  Three launches at most (modes, atoms, energy in double); every sum in
+ *     a fixed order, no atomics: bitwise reproducible.
+ */
+int64_t mdg_ewald_workspace(int n_rep, int n_atoms, int n_vecs);
+int mdg_ewald_eval(const float* pos, int n_rep, int n_atoms, const MdgCell* cell /*host*/, const float* q, const int32_t* kvec,
+                   const float* coef, int n_vecs, const float* w, float* energy, float* grad, float* hw, float* pot, float* potw,
+                   float* workspace, float out_scale, int accumulate, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * f4  bonded terms over a static topology table (csrc/bonded.hip).
  * Replaces torchmd/interface.py:447-455 (BondPotentials.forward: harmonic in the SQUARED bond length,
  * 1/2 k (|b|^2 - ro)^2) and :496-508 (AnglePotentials.forward: 1/2 k (theta - theta0)^2 over triples (i, j, k) centred on

@@ -271,6 +271,9 @@ _SIGNATURES = {
     "mdg_coulomb_eval": (C.c_int, [P, C.c_int, C.POINTER(MdgCell), P, P, P, C.c_int, P, C.POINTER(MdgCoulombConsts), P,
                                    P, P, P, P, P, P, C.c_float, C.c_int, P]),
     "mdg_coulomb_charge_reduce": (C.c_int, [P, P, C.c_int, C.c_int, C.c_int, P, P]),
+    "mdg_ewald_workspace": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "mdg_ewald_eval": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), P, P, P, C.c_int, P, P, P, P, P, P, P, C.c_float,
+                                 C.c_int, P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

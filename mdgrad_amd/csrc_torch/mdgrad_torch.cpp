@@ -18,6 +18,7 @@
 //   isf_fwd/isf_bwd  K18  observable.py intermediate_scattering -> mdg_isf_fwd / mdg_isf_bwd
 //   dihedral_eval    K19  interface.py DihedralPotentials     -> mdg_dihedral_eval
 //   coulomb_eval, coulomb_charge_reduce  K20  interface.py CoulombPotentials  -> mdg_coulomb_eval / mdg_coulomb_charge_reduce
+//   ewald_eval       K21  interface.py EwaldReciprocal      -> mdg_ewald_eval
 //   dihedral_phi_fwd/_bwd, dihedral_hist_fwd/_bwd  K19  observable.py Dihedrals / dihedral_distribution -> mdg_dihedral_phi_* / _hist_*
 //   edge_geom(+_bwd) schnet.py:142                          -> mdg_edge_geom / mdg_edge_geom_bwd
 //   cfconv_fwd/_bwd  K9+K10 modules.py:531-571              -> mdg_cfconv_fwd(_bf16) / mdg_cfconv_bwd(_bf16)
@@ -775,6 +776,38 @@ Tensor coulomb_charge_reduce(const Tensor& val, const OptTensor& types, int64_t 
     return out;
 }
 
+// ------------------------------------------------------------------------------------------------ K21
+// pos [R n, 3] (R = n_rep replicas of n atoms), q float [R n], kvec int32 [M,3] (|n_d| <= 1024: checked here with one device
+// read), coef float [M].  (energy [1] or [0], dU/dx [R n,3], H w [R n,3] or [0], pot [R n] or [0], potw [R n] or [0]) of
+// mdg_ewald_eval: no conversion, background or self term; want_pot: pot without w, potw with it
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> ewald_eval(const Tensor& pos, int64_t n_rep, at::ArrayRef<double> cell,
+                                                              const Tensor& q, const Tensor& kvec, const Tensor& coef,
+                                                              const OptTensor& w, bool want_energy, bool want_pot) {
+    check_f32(pos, "pos"); check_f32(q, "q"); check_f32(coef, "coef"); check_i32(kvec, "kvec");
+    same_device(pos, q, "q"); same_device(pos, kvec, "kvec"); same_device(pos, coef, "coef");
+    TORCH_CHECK(pos.dim() == 2 && pos.size(1) == 3 && pos.size(0) > 0, "mdgrad: pos must be [N,3]");
+    TORCH_CHECK(n_rep > 0 && pos.size(0) % n_rep == 0 && pos.size(0) <= INT32_MAX, "mdgrad: pos must hold n_rep replicas");
+    TORCH_CHECK(q.numel() == pos.size(0), "mdgrad: q must hold one charge per atom");
+    TORCH_CHECK(kvec.dim() == 2 && kvec.size(1) == 3 && kvec.size(0) >= 1 && kvec.size(0) <= 65536, "mdgrad: kvec must be [M,3], "
+                "1 <= M <= 65536");
+    TORCH_CHECK(coef.numel() == kvec.size(0), "mdgrad: coef must hold one entry per wave vector");
+    TORCH_CHECK(kvec.abs().max().item<int64_t>() <= 1024, "mdgrad: wave-vector indices must lie in [-1024, 1024]");
+    const MdgCell c = make_cell(cell);
+    const float* wp = fptr(w, "w");
+    if (wp) { same_device(pos, *w, "w"); TORCH_CHECK(w->sizes() == pos.sizes(), "mdgrad: w must have the shape of pos"); }
+    const int R = (int)n_rep, n = (int)(pos.size(0) / n_rep), M = (int)kvec.size(0);
+    const int64_t N = pos.size(0);
+    const auto o = pos.options();
+    Tensor U = at::empty({want_energy ? 1 : 0}, o), g = at::empty_like(pos);
+    Tensor hw = wp ? at::empty_like(pos) : at::empty({0}, o);
+    Tensor pot = at::empty({(want_pot && !wp) ? N : 0}, o), potw = at::empty({(want_pot && wp) ? N : 0}, o);
+    Tensor ws = at::empty({mdg_ewald_workspace(R, n, M)}, o);
+    ok(mdg_ewald_eval(fptr(pos), R, n, &c, fptr(q), kvec.data_ptr<int32_t>(), fptr(coef), M, wp, want_energy ? mptr(U) : nullptr,
+                      mptr(g), wp ? mptr(hw) : nullptr, (want_pot && !wp) ? mptr(pot) : nullptr,
+                      (want_pot && wp) ? mptr(potw) : nullptr, mptr(ws), 1.f, 0, stream_of(pos)));
+    return {U, g, hw, pot, potw};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(mdgrad, m) {
@@ -817,6 +850,8 @@ TORCH_LIBRARY(mdgrad, m) {
     m.def("coulomb_eval(Tensor pos, float[] cell, Tensor col, Tensor shift, Tensor cnt, Tensor q, float[] consts, Tensor? w, "
           "bool want_energy, bool want_pot) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("coulomb_charge_reduce(Tensor val, Tensor? types, int group, int n_slots) -> Tensor");
+    m.def("ewald_eval(Tensor pos, int n_rep, float[] cell, Tensor q, Tensor kvec, Tensor coef, Tensor? w, bool want_energy, "
+          "bool want_pot) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("edge_geom(Tensor x, Tensor? w, Tensor nbr, Tensor offsets) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("edge_geom_bwd(Tensor? d_b, Tensor dd_b, Tensor? d, Tensor? dd, Tensor uhat, Tensor? ddel, Tensor col, Tensor eid, "
           "Tensor cnt) -> (Tensor, Tensor)");
@@ -856,6 +891,7 @@ TORCH_LIBRARY_IMPL(mdgrad, CUDA, m) {      // (the HIP backend registers under t
     m.impl("dihedral_hist_bwd", dihedral_hist_bwd);
     m.impl("coulomb_eval", coulomb_eval);
     m.impl("coulomb_charge_reduce", coulomb_charge_reduce);
+    m.impl("ewald_eval", ewald_eval);
     m.impl("edge_geom", edge_geom);
     m.impl("edge_geom_bwd", edge_geom_bwd);
     m.impl("cfconv_fwd", cfconv_fwd);

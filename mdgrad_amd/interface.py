@@ -3,6 +3,7 @@ GeneralInteraction :33-57, PairPotentials :217-300, Electrostatics :303-361 (as 
 (GNNPotentials lives in mdgrad_amd.nn).  forward(xyz) -> energy; _reset_topology(xyz) rebuilds the neighbour list.
 """
 import inspect
+import math
 import os
 
 import torch
@@ -727,7 +728,8 @@ class CoulombPotentials(GeneralInteraction):
     `charges`: [n] with n = system.group_size (one replica's atoms, tiled over the replicas of System.replicate(R)), or
     [n_types] together with `types` [n]; the parameter `charges` when trainable, otherwise a buffer.  The charges are not
     constrained: neutrality is the user's business, and a cell that is not neutral has no Ewald limit -- the sum then
-    depends on the cutoff and alpha.
+    depends on the cutoff and alpha.  (The reciprocal part is a term of its own: with shift="none", EwaldReciprocal on top
+    of this class completes the Ewald sum -- see `ewald`.)
 
     forward(xyz) is differentiable twice in xyz and once in charges on the HIP kernel (ops.CoulombEnergyFn,
     csrc/coulomb.hip); force / force_vjp serve the analytic adjoint and HIP-graph replay, also while charges requires grad:
@@ -907,6 +909,172 @@ class CoulombPotentials(GeneralInteraction):
             jobs.run(accum, alpha=-self.conversion, accumulate=True)
             return o["grad"], o["hw"], None
         return o["grad"], o["hw"], [(-self.conversion) * gw.reshape(self.charges.shape)]
+
+
+class EwaldReciprocal(torch.nn.Module):
+    """The reciprocal-space part of the Ewald sum for the point charges of a CoulombPotentials (no counterpart in the
+    reference).  With `real` = CoulombPotentials(system, charges, cutoff, alpha, shift="none", self_energy=True) the two
+    terms together are the energy of the periodic system, independent of alpha up to the truncation of both sums:
+
+        k(n)   = 2 pi (nx / Lx, ny / Ly, nz / Lz),  integer n != 0,  |k| <= k_cutoff
+        rho(k) = sum_j q_j exp(i k.x_j)
+        c(k)   = (4 pi / V) exp(-k^2 / (4 alpha^2)) / k^2                                  (host, float64 -> float32 table)
+        U_rec  = conversion * [ sum_{k in half space} c(k) |rho(k)|^2  -  pi (sum_j q_j)^2 / (2 V alpha^2) ]
+
+    on a diagonal cell of lengths L, V = Lx Ly Lz.  k and -k contribute equally, so only the half space of
+    observable.sk_vectors is summed (nx > 0, or nx = 0 and ny > 0, or nx = ny = 0 and nz > 0); the second term is the
+    neutralising background, zero for a neutral cell.  The self term -alpha / sqrt(pi) sum q_i^2 is carried by `real`
+    (its self_s).  Every replica of System.replicate(R) has its own modes.
+
+    alpha, conversion, types and the `charges` tensor itself are taken from `real`: the same Parameter object when
+    trainable, so a Stack de-duplicates it and both terms add into the same gradient slot.  k_cutoff=None takes
+    2 alpha sqrt(-ln accuracy); `ewald` chooses alpha from the real-space cutoff the same way.  Not supported (ValueError):
+    a shifted or undamped `real`, one without self energy, index_tuple / ex_pairs on `real` (the erf correction for excluded
+    pairs is not implemented: excluded pairs would keep their reciprocal interaction), triclinic cells, 2-D systems.
+
+    forward(xyz) is differentiable twice in xyz and once in charges on the HIP kernels (ops.EwaldEnergyFn, csrc/ewald.hip);
+    force / force_vjp serve the analytic adjoint and HIP-graph replay like CoulombPotentials'.  float64 or host positions
+    take the torch restatement `_torch_energy`.  A Stack holding the term stays off the fused trajectory kernels."""
+
+    accepts_into = True
+    accepts_accum = True
+    analytic = True
+
+    def __init__(self, system, real, k_cutoff=None, accuracy=1e-5):
+        super().__init__()
+        if not isinstance(real, CoulombPotentials):
+            raise ValueError("EwaldReciprocal: `real` must be the CoulombPotentials carrying the real-space sum, got %s"
+                             % type(real).__name__)
+        if real.shift != "none":
+            raise ValueError("EwaldReciprocal: the real-space term has shift=%r; the Ewald real-space sum is the plain "
+                             "erfc(alpha r) / r (shift=\"none\"), a shifted one would be counted wrongly" % (real.shift,))
+        if real.alpha == 0.0:
+            raise ValueError("EwaldReciprocal: the real-space term has alpha = 0 (the bare Coulomb sum): there is no splitting "
+                             "and c(k) is undefined")
+        if not real.self_energy:
+            raise ValueError("EwaldReciprocal: the real-space term has self_energy=False; the self term -alpha/sqrt(pi) sum "
+                             "q_i^2 of the Ewald sum would be missing")
+        if real.index_tuple is not None or real.ex_pairs is not None:
+            raise ValueError("EwaldReciprocal: the real-space term has index_tuple / ex_pairs; the erf correction that removes "
+                             "excluded pairs from the reciprocal sum is not implemented")
+        if getattr(system, "dim", 3) != 3:
+            raise ValueError("EwaldReciprocal: system.dim = %r; the sum is over a three-dimensional lattice" % (system.dim,))
+        full = torch.Tensor(system.get_cell())
+        if full.dim() == 2 and bool((full - torch.diag(torch.diag(full)) != 0).any()):
+            raise ValueError("EwaldReciprocal: the cell must be diagonal (triclinic cells are not supported)")
+        if not 0.0 < float(accuracy) < 1.0:
+            raise ValueError("EwaldReciprocal: accuracy must lie in (0, 1), got %r" % (accuracy,))
+        self.system = system
+        self.device = system.device
+        self.cell = (full.diag() if full.dim() == 2 else full).to(self.device)
+        self._real = (real,)                                     # (a tuple: not registered as a sub-module a second time)
+        self.alpha, self.conversion, self.types = real.alpha, real.conversion, real.types
+        self.accuracy = float(accuracy)
+        self.k_cutoff = float(k_cutoff) if k_cutoff is not None else 2.0 * self.alpha * math.sqrt(-math.log(self.accuracy))
+        if isinstance(real.charges, torch.nn.Parameter):
+            self.charges = real.charges
+        else:
+            self.register_buffer("charges", real.charges)
+        self._slot, self.n_slots = real._slot, real.n_slots
+        self._group, self._n_rep = real._group, real._n_rep
+        lengths = self.cell.detach().cpu().to(torch.float64).numpy()          # the float32 lengths the kernels see
+        self._table = ops.EwaldTable(_lib.make_cell(system.get_cell()), lengths, self.alpha, self.k_cutoff, self.conversion,
+                                     self._n_rep, self._group, self.device)
+        self.n_vectors = self._table.n_vecs
+
+    def table(self):
+        return self._table
+
+    def _hip_ok(self, xyz=None):
+        if xyz is not None and (not xyz.is_cuda or xyz.dtype != torch.float32):
+            return False
+        return self.analytic and torch.device(self.device).type == "cuda"
+
+    def _reset_topology(self, xyz):          # (nothing to search)
+        pass
+
+    def _q_atom(self):
+        return self._real[0]._q_atom()
+
+    def prepare_pass(self):
+        if self._hip_ok():
+            self._q_atom()
+
+    def _spec(self):
+        return ops.EwaldSpec(self._table, self._q_atom(), self._slot, self.n_slots)
+
+    def _torch_energy(self, xyz):
+        """The same energy in torch ops, in the dtype and on the device of xyz (differentiable by autograd in xyz and
+        charges)."""
+        t = self._table
+        k = (2.0 * math.pi * t.n_host.to(torch.float64) / torch.as_tensor(t.lengths)).to(xyz)          # [M, 3]
+        cf = t.coef_host.to(xyz)
+        q = self._real[0]._expand(self.charges.to(xyz))
+        ph = xyz.matmul(k.t())
+        A = (q[:, None] * torch.cos(ph)).reshape(t.n_rep, t.n_atoms, -1).sum(1)
+        B = (q[:, None] * torch.sin(ph)).reshape(t.n_rep, t.n_atoms, -1).sum(1)
+        Q = q.reshape(t.n_rep, t.n_atoms).sum(1)
+        return self.conversion * ((cf * (A * A + B * B)).sum() - math.pi * Q.pow(2).sum() / (2.0 * t.volume * t.alpha ** 2))
+
+    def forward(self, xyz):
+        if self._hip_ok(xyz):
+            return ops.EwaldEnergyFn.apply(xyz.contiguous(), self.charges, self._spec())
+        return self._torch_energy(xyz)
+
+    # -- analytic-adjoint protocol (md._EOM.rhs_vjp, Stack.force / force_vjp) -------------------------------------
+    def supports_force_vjp(self):
+        return self._hip_ok()
+
+    def force(self, xyz, into=None):
+        """F = -dU/dx; `into` (a force buffer of another Stack member): added onto it in the same launch and returned."""
+        o = ops.ewald_eval(self._table, xyz.detach(), self._q_atom(), energy=False, grad=True,
+                           into=None if into is None else (into, None), scale=-1.0)
+        return o["grad"]
+
+    def force_vjp(self, xyz, w, want_theta=True, accum=None, into=None):
+        """(F, d(w.F)/dx, [d(w.F)/dcharges]) in one evaluation plus the fixed-order reduction of the charge part; `accum`
+        (ops.ThetaAccum): that part is added into its flat buffer instead (None returned).  `into` = (F, dq) buffers of
+        another Stack member: this term's force and d(w.F)/dx are added onto them in the same launch."""
+        need = bool(want_theta) and isinstance(self.charges, torch.nn.Parameter)
+        o = ops.ewald_eval(self._table, xyz.detach(), self._q_atom(), w=w.detach(), energy=False, grad=True, into=into,
+                           scale=-1.0, want_pot=need)
+        if not want_theta:
+            return o["grad"], o["hw"], None
+        if not need:
+            return o["grad"], o["hw"], ([] if accum is None else None)
+        gw = ops.coulomb_charge_grad(o["potw"], self._slot, self.n_slots)          # d(w.dU/dx)/dcharges
+        if accum is not None:
+            jobs = ops.GradJobs()
+            jobs.axpy(accum.off[id(self.charges)], gw)
+            jobs.run(accum, alpha=-1.0, accumulate=True)
+            return o["grad"], o["hw"], None
+        return o["grad"], o["hw"], [-gw.reshape(self.charges.shape)]
+
+    # -- fixed-capacity topology (HIP-graph capture): the tables are static, nothing can overflow -----------------
+    def supports_static_topology(self):
+        return self._hip_ok()
+
+    def set_static_topology(self, on=True):
+        pass
+
+    def static_overflow(self):
+        return False
+
+    def static_version(self):
+        return 0
+
+
+def ewald(system, charges, cutoff, accuracy=1e-5, k_cutoff=None, **kw):
+    """The two members of an Ewald sum with both truncation errors near `accuracy` (relative): alpha = sqrt(-ln accuracy) /
+    cutoff, so that erfc(alpha cutoff) ~ accuracy, and k_cutoff = 2 alpha sqrt(-ln accuracy).  Returns
+    {"coulomb_real": CoulombPotentials(system, charges, cutoff, alpha=alpha, shift="none", **kw),
+     "coulomb_recip": EwaldReciprocal(system, real, k_cutoff, accuracy)}, ready for Stack({..., **ewald(...)}); **kw: types,
+    conversion, trainable of CoulombPotentials."""
+    if not 0.0 < float(accuracy) < 1.0:
+        raise ValueError("ewald: accuracy must lie in (0, 1), got %r" % (accuracy,))
+    alpha = math.sqrt(-math.log(float(accuracy))) / float(cutoff)
+    real = CoulombPotentials(system, charges, cutoff, alpha=alpha, shift="none", self_energy=True, **kw)
+    return {"coulomb_real": real, "coulomb_recip": EwaldReciprocal(system, real, k_cutoff=k_cutoff, accuracy=accuracy)}
 
 
 class Stack(torch.nn.Module):

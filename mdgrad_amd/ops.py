@@ -12,6 +12,7 @@ torch.autograd.Function wrappers that own the differentiation contract
     DihedralEnergyFn -> DihedralGradFn                          torsion term, order <= 2 in x, 1 in its coefficients
     DihedralPhiFn, DihedralHistFn                               signed dihedral angles of every frame, their periodic histogram
     CoulombEnergyFn -> CoulombGradFn                            damped shifted-force Coulomb sum, order <= 2 in x, 1 in the charges
+    EwaldEnergyFn -> EwaldGradFn                                Ewald reciprocal-space sum, order <= 2 in x, 1 in the charges
 
 Everything here requires HIP tensors; there is no CPU path.
 """
@@ -19,6 +20,7 @@ import ctypes as C
 import math
 import weakref
 
+import numpy as np
 import torch
 from array import array as _array
 
@@ -671,6 +673,165 @@ class CoulombEnergyFn(torch.autograd.Function):
     def backward(ctx, gU):
         xyz, charges = ctx.saved_tensors
         g, gq = CoulombGradFn.apply(xyz, charges, ctx.spec, ctx.cache)
+        return gU * g, gU * gq, None
+
+
+# ----------------------------------------------------------------------------- Ewald reciprocal-space sum (K21)
+EWALD_MAX_INDEX = 1024
+EWALD_MAX_VECS = 65536
+
+
+def ewald_vectors(lengths, k_cutoff):
+    """The wave vectors of the reciprocal sum on a diagonal cell, on the host in float64: (n int32 [M, 3], |k|^2 float64 [M])
+    with k(n) = 2 pi n / L, n != 0, |k| <= k_cutoff, of the half space of observable.sk_vectors (nx > 0, or nx = 0 and ny > 0,
+    or nx = ny = 0 and nz > 0), sorted by |k|^2 and then by (nx, ny, nz)."""
+    L = np.asarray(lengths, dtype=np.float64).reshape(-1)
+    if L.shape != (3,) or not (L > 0).all():
+        raise ValueError("mdgrad_amd: ewald_vectors needs three positive cell lengths (got %r)" % (lengths,))
+    kc = float(k_cutoff)
+    if not kc > 0.0:
+        raise ValueError("mdgrad_amd: k_cutoff must be positive (got %r)" % (k_cutoff,))
+    nmax = np.floor(kc * L / (2 * np.pi)).astype(np.int64)
+    if int(nmax.max()) > EWALD_MAX_INDEX:
+        raise ValueError("mdgrad_amd: k_cutoff = %g reaches wave-vector indices beyond %d in this cell" % (kc, EWALD_MAX_INDEX))
+    ax = [np.arange(0, nmax[0] + 1), np.arange(-nmax[1], nmax[1] + 1), np.arange(-nmax[2], nmax[2] + 1)]
+    n = np.stack(np.meshgrid(*ax, indexing="ij"), -1).reshape(-1, 3)
+    half = (n[:, 0] > 0) | ((n[:, 0] == 0) & ((n[:, 1] > 0) | ((n[:, 1] == 0) & (n[:, 2] > 0))))
+    n = n[half]
+    k2 = ((2 * np.pi * n / L) ** 2).sum(1)
+    keep = k2 <= kc * kc
+    n, k2 = n[keep], k2[keep]
+    if len(n) == 0:
+        raise ValueError("mdgrad_amd: no wave vector below k_cutoff = %g (the smallest is 2 pi / L_max = %g)"
+                         % (kc, 2 * np.pi / L.max()))
+    if len(n) > EWALD_MAX_VECS:
+        raise ValueError("mdgrad_amd: %d wave vectors below k_cutoff = %g, at most %d (lower the accuracy or k_cutoff)"
+                         % (len(n), kc, EWALD_MAX_VECS))
+    order = np.lexsort((n[:, 2], n[:, 1], n[:, 0], k2))
+    return torch.from_numpy(n[order].astype(np.int32)), torch.from_numpy(k2[order])
+
+
+def ewald_coef(k2, volume, alpha):
+    """c(k) = (4 pi / V) exp(-k^2 / (4 alpha^2)) / k^2 in float64."""
+    k2 = torch.as_tensor(k2, dtype=torch.float64)
+    alpha = float(alpha)
+    if not alpha > 0.0:
+        raise ValueError("mdgrad_amd: the Ewald splitting parameter alpha must be positive (got %r)" % alpha)
+    return (4.0 * math.pi / float(volume)) * torch.exp(-k2 / (4.0 * alpha * alpha)) / k2
+
+
+class EwaldTable:
+    """What the reciprocal sum needs beside positions and charges, built once: the integer wave vectors and the table
+    conversion * c(k) as persistent device buffers (no torch op for them inside a graph capture), the cell, the replica
+    layout and the background constant  conversion * pi / (V alpha^2)."""
+
+    def __init__(self, cell_struct, lengths, alpha, k_cutoff, conversion, n_rep, n_atoms, device):
+        self.cell_struct, self.n_rep, self.n_atoms = cell_struct, int(n_rep), int(n_atoms)
+        self.alpha, self.k_cutoff, self.conversion = float(alpha), float(k_cutoff), float(conversion)
+        L = np.asarray(lengths, dtype=np.float64).reshape(3)
+        self.lengths, self.volume = L, float(np.prod(L))
+        self.n_host, self.k2_host = ewald_vectors(L, k_cutoff)
+        self.coef_host = ewald_coef(self.k2_host, self.volume, self.alpha)                # (without the conversion)
+        self.n_vecs = int(self.n_host.shape[0])
+        self.kvec = self.n_host.to(device).contiguous()
+        self.coef = (self.conversion * self.coef_host).to(torch.float32).to(device).contiguous()
+        self.background = self.conversion * math.pi / (self.volume * self.alpha * self.alpha)
+
+
+def ewald_eval(table, xyz, q_atom, w=None, energy=True, grad=True, into=None, scale=1.0, want_pot=False):
+    """One mdg_ewald_eval -> dict(energy, grad, hw, pot, potw), shaped like coulomb_eval; everything carries the table's
+    conversion, nothing the background term: energy = conversion sum_k c |rho|^2 over all replicas, grad = scale dU/dx, with
+    `w` hw = scale H w; want_pot: pot_i = conversion sum_k 2 c (A c_i + B s_i) without `w`, potw_i = d(w.dU/dx)/dq_i with it.
+    `into` = (grad buffer, hw buffer or None): grad / hw are ADDED onto them."""
+    lib = _lib.load()
+    require_gpu(xyz, "xyz")
+    require_gpu(q_atom, "q_atom")
+    N = table.n_rep * table.n_atoms
+    if xyz.shape != (N, 3):
+        raise ValueError("mdgrad_amd: xyz must be [%d, 3] (got %s)" % (N, tuple(xyz.shape)))
+    if q_atom.shape != (N,):
+        raise ValueError("mdgrad_amd: q_atom must be [%d] (got %s)" % (N, tuple(q_atom.shape)))
+    xyz = xyz.contiguous()
+    dev = xyz.device
+    acc = into is not None
+    e = torch.empty(1, device=dev) if energy else None
+    g = (into[0] if acc else torch.empty(N, 3, device=dev)) if grad else None
+    hw = pot = potw = None
+    if w is not None:
+        require_gpu(w, "w")
+        if w.shape != (N, 3):
+            raise ValueError("mdgrad_amd: w must be [%d, 3] (got %s)" % (N, tuple(w.shape)))
+        w = w.contiguous()
+        hw = into[1] if acc else torch.empty(N, 3, device=dev)
+        potw = torch.empty(N, device=dev) if want_pot else None
+    elif want_pot:
+        pot = torch.empty(N, device=dev)
+    ws = torch.empty(int(lib.mdg_ewald_workspace(table.n_rep, table.n_atoms, table.n_vecs)), device=dev)
+    check(lib.mdg_ewald_eval(ptr(xyz), table.n_rep, table.n_atoms, C.byref(table.cell_struct), ptr(q_atom), ptr(table.kvec),
+                             ptr(table.coef), table.n_vecs, ptr(w), ptr(e), ptr(g), ptr(hw), ptr(pot), ptr(potw), ptr(ws),
+                             float(scale), int(acc), stream_ptr(dev)), "mdg_ewald_eval")
+    return dict(energy=e, grad=g, hw=hw, pot=pot, potw=potw)
+
+
+class EwaldSpec:
+    """What the autograd functions below need beside the tensors: the table, the per-atom charge buffer and the charge slots
+    (those of the real-space CoulombPotentials the term belongs to)."""
+
+    def __init__(self, table, q_atom, slot, n_slots):
+        self.table, self.q_atom, self.slot, self.n_slots = table, q_atom, slot, int(n_slots)
+
+
+class EwaldGradFn(torch.autograd.Function):
+    """(dU/dx, dU/dcharges) of the reciprocal sum as a differentiable op; backward = the Hessian-vector product and the mixed
+    derivative d(w.dU/dx)/dcharges.  A cotangent on dU/dcharges is not provided."""
+
+    @staticmethod
+    def forward(ctx, xyz, charges, spec, cache):
+        ctx.spec = spec
+        ctx.save_for_backward(xyz, charges)
+        ctx.set_materialize_grads(False)
+        if cache is None:
+            cache = _ewald_first_order(spec, xyz, charges, energy=False)[1:]
+        return cache
+
+    @staticmethod
+    def backward(ctx, wg, wq):
+        xyz, charges = ctx.saved_tensors
+        s = ctx.spec
+        if wq is not None:
+            raise NotImplementedError("mdgrad_amd: derivatives of dU/dcharges of the Ewald reciprocal term (a cotangent on it) "
+                                      "are not provided by the HIP kernels")
+        if wg is None:
+            return None, None, None, None
+        o = ewald_eval(s.table, xyz, s.q_atom, w=wg.detach().contiguous(), energy=False, grad=False, want_pot=True)
+        gq = coulomb_charge_grad(o["potw"], s.slot, s.n_slots)
+        return o["hw"], gq.reshape(charges.shape), None, None
+
+
+def _ewald_first_order(spec, xyz, charges, energy):
+    t = spec.table
+    o = ewald_eval(t, xyz, spec.q_atom, energy=energy, grad=True, want_pot=True)
+    Q = spec.q_atom.reshape(t.n_rep, t.n_atoms).sum(1)                                   # net charge of every replica
+    dq_atom = o["pot"] - t.background * Q.repeat_interleave(t.n_atoms)                   # dU/dq_i
+    e = o["energy"] - (0.5 * t.background) * Q.pow(2).sum() if energy else None
+    return e, o["grad"], coulomb_charge_grad(dq_atom, spec.slot, spec.n_slots).reshape(charges.shape)
+
+
+class EwaldEnergyFn(torch.autograd.Function):
+    """U_rec(x, charges) of the Ewald reciprocal sum with its neutralising background (csrc/ewald.hip), differentiable twice
+    in x and once in the charges."""
+
+    @staticmethod
+    def forward(ctx, xyz, charges, spec):
+        e, g, gq = _ewald_first_order(spec, xyz, charges, energy=True)
+        ctx.spec, ctx.cache = spec, (g, gq)
+        ctx.save_for_backward(xyz, charges)
+        return e.reshape(())
+
+    @staticmethod
+    def backward(ctx, gU):
+        xyz, charges = ctx.saved_tensors
+        g, gq = EwaldGradFn.apply(xyz, charges, ctx.spec, ctx.cache)
         return gU * g, gU * gq, None
 
 

@@ -1071,6 +1071,36 @@ int mdg_ewald_eval(const float* pos, int n_rep, int n_atoms, const MdgCell* cell
                    float* workspace, float out_scale, int accumulate, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * K22  erf correction of the Ewald sum for excluded and scaled pairs (mdgrad_amd/interface.py EwaldExclusions,
+ *      csrc/ewald_excl.hip).  The reciprocal sum K21 runs over all charges; for a static list of pairs p = (i, j) of one replica,
+ *      each with a scale s_p in [0, 1], this term adds, with E1 = erf(alpha r), G = (2 alpha / sqrt(pi)) exp(-alpha^2 r^2):
+ *        chi(r)   = (s - E1) / r
+ *        chi'(r)  = -(s - E1) / r^2 - G / r
+ *        chi''(r) = 2 (s - E1) / r^3 + 2 G / r^2 + 2 alpha^2 G
+ *        U        = conversion * sum over the pairs of every replica of q_i q_j chi_{s_p}(r_ij)
+ *      r_ij = |x_lo - x_hi| (lo = min(i, j)) re-imaged like a bond vector (topology.get_offsets on the diagonal cell:
+ *      -[b >= L/2] + [b < -L/2], piecewise constant).  s = 0: the pair is excluded (K20's mask removes erfc/r, this removes the
+ *      erf/r of K21); s = 1: chi is K20's psi with shift "none".  No self term, no background term.  Below alpha r = 1 the erf
+ *      part comes from the power series of erf(x)/x (14 terms) -- the closed forms cancel in float32 -- and a coincident pair
+ *      (r == 0) contributes its limits: energy -q_i q_j 2 alpha / sqrt(pi), zero gradient, (H w)_i = q_i q_j (4 alpha^3 /
+ *      (3 sqrt(pi))) (w_i - w_j), pot -q_j 2 alpha / sqrt(pi), potw 0; the s / r part of such a pair is dropped.
+ *   mdg_ewald_excl_eval  pos [n_rep, n_atoms, 3] (need not be wrapped), q [n_rep, n_atoms], cell_len host float[3];
+ *     row_ptr int32 [n_atoms + 1], col int32 [nnz], scale float [nnz]: the CSR incidence list of one replica -- row(a) holds the
+ *     partners of atom a in ascending order (every pair twice, once per end) with the pair's scale; all replicas share it.
+ *     The caller guarantees 0 <= col < n_atoms and col != the row's atom.  w nullable [n_rep, n_atoms, 3] (required for hw /
+ *     potw).  Outputs, each nullable: energy [1] (needs `partial`: mdg_ewald_excl_partial_size() doubles; per-block sums in
+ *     double, then one fixed tree); grad [n_rep n_atoms, 3] = (accumulate & 1 ? grad : 0) + out_scale dU/dx, hw likewise with
+ *     H w -- an atom with an empty row leaves an accumulated buffer untouched; pot_i = sum_j q_j chi(r_ij), potw_i = sum_j q_j
+ *     chi'(r_ij) rhat_ij.(w_i - w_j) [n_rep n_atoms] (dU/dq_i = conversion pot_i).  One launch, plus the finish for the
+ *     energy; every sum in a fixed order, no atomics: bitwise reproducible.
+ */
+int64_t mdg_ewald_excl_partial_size(int n_rep, int n_atoms);
+int mdg_ewald_excl_eval(const float* pos, int n_rep, int n_atoms, const float* cell_len /*host*/, const int32_t* row_ptr,
+                        const int32_t* col, const float* scale, const float* q, double alpha, double conversion, const float* w,
+                        float* energy, float* grad, float* hw, float* pot, float* potw, double* partial, float out_scale,
+                        int accumulate, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * f4  bonded terms over a static topology table (csrc/bonded.hip).
  * Replaces torchmd/interface.py:447-455 (BondPotentials.forward: harmonic in the SQUARED bond length,
  * 1/2 k (|b|^2 - ro)^2) and :496-508 (AnglePotentials.forward: 1/2 k (theta - theta0)^2 over triples (i, j, k) centred on

@@ -274,6 +274,9 @@ _SIGNATURES = {
     "mdg_ewald_workspace": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "mdg_ewald_eval": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), P, P, P, C.c_int, P, P, P, P, P, P, P, C.c_float,
                                  C.c_int, P]),
+    "mdg_ewald_excl_partial_size": (C.c_int64, [C.c_int, C.c_int]),
+    "mdg_ewald_excl_eval": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(C.c_float), P, P, P, P, C.c_double, C.c_double, P,
+                                      P, P, P, P, P, P, C.c_float, C.c_int, P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

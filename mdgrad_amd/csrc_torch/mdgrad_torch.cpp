@@ -19,6 +19,7 @@
 //   dihedral_eval    K19  interface.py DihedralPotentials     -> mdg_dihedral_eval
 //   coulomb_eval, coulomb_charge_reduce  K20  interface.py CoulombPotentials  -> mdg_coulomb_eval / mdg_coulomb_charge_reduce
 //   ewald_eval       K21  interface.py EwaldReciprocal      -> mdg_ewald_eval
+//   ewald_excl_eval  K22  interface.py EwaldExclusions      -> mdg_ewald_excl_eval
 //   dihedral_phi_fwd/_bwd, dihedral_hist_fwd/_bwd  K19  observable.py Dihedrals / dihedral_distribution -> mdg_dihedral_phi_* / _hist_*
 //   edge_geom(+_bwd) schnet.py:142                          -> mdg_edge_geom / mdg_edge_geom_bwd
 //   cfconv_fwd/_bwd  K9+K10 modules.py:531-571              -> mdg_cfconv_fwd(_bf16) / mdg_cfconv_bwd(_bf16)
@@ -808,6 +809,45 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> ewald_eval(const Tensor& pos,
     return {U, g, hw, pot, potw};
 }
 
+// ------------------------------------------------------------------------------------------------ K22
+// pos [R n, 3], q float [R n], cell_len = the three diagonal lengths; row_ptr int32 [n + 1], col int32 [nnz], scale float [nnz]:
+// the CSR incidence list of ops.EwaldExclTable (checked here with device reads: the kernel indexes pos with col).
+// (energy [1] or [0], dU/dx [R n,3], H w [R n,3] or [0], pot [R n] or [0], potw [R n] or [0]) of mdg_ewald_excl_eval
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> ewald_excl_eval(const Tensor& pos, int64_t n_rep, at::ArrayRef<double> cell_len,
+                                                                   const Tensor& row_ptr, const Tensor& col, const Tensor& scale,
+                                                                   const Tensor& q, double alpha, double conversion,
+                                                                   const OptTensor& w, bool want_energy, bool want_pot) {
+    check_f32(pos, "pos"); check_f32(q, "q"); check_f32(scale, "scale"); check_i32(row_ptr, "row_ptr"); check_i32(col, "col");
+    same_device(pos, q, "q"); same_device(pos, scale, "scale"); same_device(pos, row_ptr, "row_ptr"); same_device(pos, col, "col");
+    TORCH_CHECK(pos.dim() == 2 && pos.size(1) == 3 && pos.size(0) > 0, "mdgrad: pos must be [N,3]");
+    TORCH_CHECK(n_rep > 0 && pos.size(0) % n_rep == 0 && pos.size(0) < (1LL << 29), "mdgrad: pos must hold n_rep replicas");
+    TORCH_CHECK(q.numel() == pos.size(0), "mdgrad: q must hold one charge per atom");
+    TORCH_CHECK(cell_len.size() == 3 && cell_len[0] > 0 && cell_len[1] > 0 && cell_len[2] > 0,
+                "mdgrad: cell_len = the three (positive) diagonal lengths of the cell");
+    TORCH_CHECK(alpha > 0.0, "mdgrad: alpha must be positive");
+    const int64_t N = pos.size(0), n = N / n_rep, nnz = col.numel();
+    TORCH_CHECK(row_ptr.dim() == 1 && row_ptr.numel() == n + 1, "mdgrad: row_ptr must be [n_atoms + 1]");
+    TORCH_CHECK(col.dim() == 1 && scale.dim() == 1 && scale.numel() == nnz, "mdgrad: col and scale must be [nnz]");
+    const Tensor rp = row_ptr.cpu();
+    const int32_t* r = rp.data_ptr<int32_t>();
+    TORCH_CHECK(r[0] == 0 && r[n] == nnz, "mdgrad: row_ptr must run from 0 to nnz");
+    for (int64_t a = 0; a < n; ++a) TORCH_CHECK(r[a] <= r[a + 1], "mdgrad: row_ptr must not decrease");
+    if (nnz > 0) TORCH_CHECK(col.min().item<int64_t>() >= 0 && col.max().item<int64_t>() < n, "mdgrad: col must lie in [0, n_atoms)");
+    const float* wp = fptr(w, "w");
+    if (wp) { same_device(pos, *w, "w"); TORCH_CHECK(w->sizes() == pos.sizes(), "mdgrad: w must have the shape of pos"); }
+    float L[3] = {(float)cell_len[0], (float)cell_len[1], (float)cell_len[2]};
+    const auto o = pos.options();
+    Tensor U = at::empty({want_energy ? 1 : 0}, o), g = at::empty_like(pos);
+    Tensor hw = wp ? at::empty_like(pos) : at::empty({0}, o);
+    Tensor pot = at::empty({(want_pot && !wp) ? N : 0}, o), potw = at::empty({(want_pot && wp) ? N : 0}, o);
+    Tensor partial = at::empty({mdg_ewald_excl_partial_size((int)n_rep, (int)n)}, o.dtype(at::kDouble));
+    ok(mdg_ewald_excl_eval(fptr(pos), (int)n_rep, (int)n, L, row_ptr.data_ptr<int32_t>(), col.data_ptr<int32_t>(), fptr(scale), fptr(q),
+                           alpha, conversion, wp, want_energy ? mptr(U) : nullptr, mptr(g), wp ? mptr(hw) : nullptr,
+                           (want_pot && !wp) ? mptr(pot) : nullptr, (want_pot && wp) ? mptr(potw) : nullptr,
+                           partial.data_ptr<double>(), 1.f, 0, stream_of(pos)));
+    return {U, g, hw, pot, potw};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(mdgrad, m) {
@@ -852,6 +892,8 @@ TORCH_LIBRARY(mdgrad, m) {
     m.def("coulomb_charge_reduce(Tensor val, Tensor? types, int group, int n_slots) -> Tensor");
     m.def("ewald_eval(Tensor pos, int n_rep, float[] cell, Tensor q, Tensor kvec, Tensor coef, Tensor? w, bool want_energy, "
           "bool want_pot) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
+    m.def("ewald_excl_eval(Tensor pos, int n_rep, float[] cell_len, Tensor row_ptr, Tensor col, Tensor scale, Tensor q, float alpha, "
+          "float conversion, Tensor? w, bool want_energy, bool want_pot) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("edge_geom(Tensor x, Tensor? w, Tensor nbr, Tensor offsets) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("edge_geom_bwd(Tensor? d_b, Tensor dd_b, Tensor? d, Tensor? dd, Tensor uhat, Tensor? ddel, Tensor col, Tensor eid, "
           "Tensor cnt) -> (Tensor, Tensor)");
@@ -892,6 +934,7 @@ TORCH_LIBRARY_IMPL(mdgrad, CUDA, m) {      // (the HIP backend registers under t
     m.impl("coulomb_eval", coulomb_eval);
     m.impl("coulomb_charge_reduce", coulomb_charge_reduce);
     m.impl("ewald_eval", ewald_eval);
+    m.impl("ewald_excl_eval", ewald_excl_eval);
     m.impl("edge_geom", edge_geom);
     m.impl("edge_geom_bwd", edge_geom_bwd);
     m.impl("cfconv_fwd", cfconv_fwd);

@@ -722,8 +722,8 @@ class CoulombPotentials(GeneralInteraction):
 
     row(i) is the neighbour row of the ELL list exactly as PairPotentials uses it: the same minimum image, the same
     (d2 < rc^2) & (d2 != 0) test and the same index_tuple / ex_pairs mask (ops.build_mask); pairs stay inside their replica.
-    Excluded pairs simply do not interact (no erf correction).  `conversion` defaults to units.ke (eV Angstrom / e^2);
-    reduced-unit users pass 1.0.
+    Excluded pairs simply do not interact (within an Ewald sum, EwaldExclusions adds their erf correction).  `conversion`
+    defaults to units.ke (eV Angstrom / e^2); reduced-unit users pass 1.0.
 
     `charges`: [n] with n = system.group_size (one replica's atoms, tiled over the replicas of System.replicate(R)), or
     [n_types] together with `types` [n]; the parameter `charges` when trainable, otherwise a buffer.  The charges are not
@@ -929,8 +929,10 @@ class EwaldReciprocal(torch.nn.Module):
     alpha, conversion, types and the `charges` tensor itself are taken from `real`: the same Parameter object when
     trainable, so a Stack de-duplicates it and both terms add into the same gradient slot.  k_cutoff=None takes
     2 alpha sqrt(-ln accuracy); `ewald` chooses alpha from the real-space cutoff the same way.  Not supported (ValueError):
-    a shifted or undamped `real`, one without self energy, index_tuple / ex_pairs on `real` (the erf correction for excluded
-    pairs is not implemented: excluded pairs would keep their reciprocal interaction), triclinic cells, 2-D systems.
+    a shifted or undamped `real`, one without self energy, index_tuple on `real`, triclinic cells, 2-D systems.  ex_pairs on
+    `real` need the third member of the sum: excluded pairs keep their reciprocal interaction erf(alpha r) / r, which
+    EwaldExclusions(system, real) removes -- pass it as `exclusions=` (or build all three with ewald(..., ex_pairs=));
+    without it such a `real` is refused.
 
     forward(xyz) is differentiable twice in xyz and once in charges on the HIP kernels (ops.EwaldEnergyFn, csrc/ewald.hip);
     force / force_vjp serve the analytic adjoint and HIP-graph replay like CoulombPotentials'.  float64 or host positions
@@ -940,7 +942,7 @@ class EwaldReciprocal(torch.nn.Module):
     accepts_accum = True
     analytic = True
 
-    def __init__(self, system, real, k_cutoff=None, accuracy=1e-5):
+    def __init__(self, system, real, k_cutoff=None, accuracy=1e-5, exclusions=None):
         super().__init__()
         if not isinstance(real, CoulombPotentials):
             raise ValueError("EwaldReciprocal: `real` must be the CoulombPotentials carrying the real-space sum, got %s"
@@ -954,9 +956,13 @@ class EwaldReciprocal(torch.nn.Module):
         if not real.self_energy:
             raise ValueError("EwaldReciprocal: the real-space term has self_energy=False; the self term -alpha/sqrt(pi) sum "
                              "q_i^2 of the Ewald sum would be missing")
-        if real.index_tuple is not None or real.ex_pairs is not None:
+        if exclusions is not None and (not isinstance(exclusions, EwaldExclusions) or exclusions._real[0] is not real):
+            raise ValueError("EwaldReciprocal: `exclusions` must be the EwaldExclusions built on the same real-space term")
+        if real.index_tuple is not None or (real.ex_pairs is not None and exclusions is None):
             raise ValueError("EwaldReciprocal: the real-space term has index_tuple / ex_pairs; the erf correction that removes "
-                             "excluded pairs from the reciprocal sum is not implemented")
+                             "excluded pairs from the reciprocal sum is not implemented for index_tuple, and for ex_pairs it is "
+                             "a term of its own: pass exclusions=EwaldExclusions(system, real), or build the three members "
+                             "with ewald(..., ex_pairs=)")
         if getattr(system, "dim", 3) != 3:
             raise ValueError("EwaldReciprocal: system.dim = %r; the sum is over a three-dimensional lattice" % (system.dim,))
         full = torch.Tensor(system.get_cell())
@@ -1064,17 +1070,197 @@ class EwaldReciprocal(torch.nn.Module):
         return 0
 
 
-def ewald(system, charges, cutoff, accuracy=1e-5, k_cutoff=None, **kw):
-    """The two members of an Ewald sum with both truncation errors near `accuracy` (relative): alpha = sqrt(-ln accuracy) /
+class EwaldExclusions(torch.nn.Module):
+    """The third member of the Ewald sum for molecules: the erf correction for the excluded and scaled pairs of a
+    CoulombPotentials (no counterpart in the reference).  The real-space term honours `ex_pairs` through its mask; the
+    reciprocal sum runs over all charges and cannot leave a pair out.  With `real` = CoulombPotentials(system, charges, cutoff,
+    alpha > 0, shift="none", self_energy=True, ex_pairs=P), E1(r) = erf(alpha r), G(r) = (2 alpha / sqrt(pi)) exp(-alpha^2 r^2)
+    and a scale s_p per pair p = (i, j) of P:
+
+        chi(r)   = (s - E1) / r
+        chi'(r)  = -(s - E1) / r^2 - G / r
+        chi''(r) = 2 (s - E1) / r^3 + 2 G / r^2 + 2 alpha^2 G
+        U_excl   = conversion * sum_{p in P, every replica} q_i q_j chi_{s_p}(r_ij)
+
+    r_ij is the length of x_i - x_j re-imaged on the diagonal cell the way BondPotentials / DihedralPotentials re-image a
+    bond vector (topology.get_offsets: non-strict >= on the +L/2 side, piecewise constant, no derivative), so wrapped and
+    unwrapped frames give the same value.  s = 0 (the default): the pair is fully excluded -- the mask removes erfc/r, this
+    term the erf/r of the reciprocal sum, together 1/r is gone; s = 0.5: the OPLS / AMBER 1-4 scaling; s = 1: chi equals the
+    real-space psi of shift="none", the pair is back to its full interaction.  `scale`: None, one float, or one float per row
+    of real.ex_pairs, each in [0, 1].  No self term and no background term here: both stay where they are.
+
+    A coincident pair (r == 0: Drude particles, virtual sites) contributes the limits of the erf part -- energy
+    -q_i q_j 2 alpha / sqrt(pi), zero gradient, (H w)_i = q_i q_j (4 alpha^3 / (3 sqrt(pi))) (w_i - w_j) -- and its s / r
+    part is dropped, like the pair kernels' d2 != 0 test.
+
+    The pairs, alpha, conversion, types and the `charges` tensor itself are taken from `real`: the same Parameter object
+    when trainable, so a Stack de-duplicates it and all three terms add into one gradient slot.  ValueError: `real` without
+    ex_pairs, shifted, undamped, without self energy or with index_tuple; a pair with i == j, an index outside the replica,
+    a pair listed twice in either orientation (the mask is idempotent, this sum would subtract such a pair twice); a
+    triclinic cell, system.dim != 3, a scale outside [0, 1].
+
+    forward(xyz) is differentiable twice in xyz and once in charges on the HIP kernel (ops.EwaldExclEnergyFn,
+    csrc/ewald_excl.hip: below alpha r = 1 the erf part comes from the power series of erf(x)/x, whose closed form cancels
+    in float32); force / force_vjp serve the analytic adjoint and HIP-graph replay like CoulombPotentials'.  float64 or host
+    positions take the torch restatement `_torch_energy`.  A Stack holding the term stays off the fused trajectory
+    kernels."""
+
+    accepts_into = True
+    accepts_accum = True
+    analytic = True
+
+    def __init__(self, system, real, scale=None):
+        super().__init__()
+        if not isinstance(real, CoulombPotentials):
+            raise ValueError("EwaldExclusions: `real` must be the CoulombPotentials carrying the real-space sum, got %s"
+                             % type(real).__name__)
+        if real.ex_pairs is None:
+            raise ValueError("EwaldExclusions: the real-space term has no ex_pairs: there is nothing to correct")
+        if real.index_tuple is not None:
+            raise ValueError("EwaldExclusions: the real-space term has index_tuple; the Ewald sum runs over all charges")
+        if real.shift != "none":
+            raise ValueError("EwaldExclusions: the real-space term has shift=%r; the Ewald real-space sum is the plain "
+                             "erfc(alpha r) / r (shift=\"none\")" % (real.shift,))
+        if real.alpha == 0.0:
+            raise ValueError("EwaldExclusions: the real-space term has alpha = 0 (the bare Coulomb sum): there is no splitting "
+                             "and nothing to correct")
+        if not real.self_energy:
+            raise ValueError("EwaldExclusions: the real-space term has self_energy=False; it is not the real-space member of "
+                             "an Ewald sum")
+        if getattr(system, "dim", 3) != 3:
+            raise ValueError("EwaldExclusions: system.dim = %r; the sum is over a three-dimensional lattice" % (system.dim,))
+        full = torch.Tensor(system.get_cell())
+        if full.dim() == 2 and bool((full - torch.diag(torch.diag(full)) != 0).any()):
+            raise ValueError("EwaldExclusions: the cell must be diagonal (triclinic cells are not supported)")
+        self.system = system
+        self.device = system.device
+        self.cell = (full.diag() if full.dim() == 2 else full).to(self.device)
+        self._real = (real,)                                     # (a tuple: not registered as a sub-module a second time)
+        self.alpha, self.conversion, self.types = real.alpha, real.conversion, real.types
+        if isinstance(real.charges, torch.nn.Parameter):
+            self.charges = real.charges
+        else:
+            self.register_buffer("charges", real.charges)
+        self._slot, self.n_slots = real._slot, real.n_slots
+        self._group, self._n_rep = real._group, real._n_rep
+        lengths = self.cell.detach().cpu().to(torch.float64).numpy()          # the float32 lengths the kernel sees
+        try:
+            self._table = ops.EwaldExclTable(real.ex_pairs, scale, self._group, self._n_rep, lengths, self.alpha,
+                                             self.conversion, self.device)
+        except ValueError as e:
+            raise ValueError("EwaldExclusions: " + str(e).replace("mdgrad_amd: ", "")) from None
+        self.pairs, self.scale = self._table.pairs, self._table.scale
+
+    def table(self):
+        return self._table
+
+    def _hip_ok(self, xyz=None):
+        if xyz is not None and (not xyz.is_cuda or xyz.dtype != torch.float32):
+            return False
+        return self.analytic and torch.device(self.device).type == "cuda"
+
+    def _reset_topology(self, xyz):          # (the pair list is static)
+        pass
+
+    def _q_atom(self):
+        return self._real[0]._q_atom()
+
+    def prepare_pass(self):
+        if self._hip_ok():
+            self._q_atom()
+
+    def _spec(self):
+        return ops.EwaldExclSpec(self._table, self._q_atom(), self._slot, self.n_slots)
+
+    def _torch_energy(self, xyz):
+        """The same energy in torch ops, in the dtype and on the device of xyz (differentiable by autograd in xyz and
+        charges)."""
+        t = self._table
+        rep = (torch.arange(t.n_rep) * t.n_atoms)[:, None]
+        i = (t.pairs[:, 0][None, :] + rep).reshape(-1).to(xyz.device)
+        j = (t.pairs[:, 1][None, :] + rep).reshape(-1).to(xyz.device)
+        s = t.scale.repeat(t.n_rep).to(xyz)
+        cell = self.cell.detach().to(xyz)
+        d = xyz[i] - xyz[j]
+        d = d + get_offsets(d.detach(), cell, xyz.device).to(xyz) * cell
+        d2 = d.pow(2).sum(-1)
+        apart = d2 != 0
+        r = torch.where(apart, d2, torch.ones_like(d2)).sqrt()
+        g0 = 2.0 * t.alpha / math.sqrt(math.pi)
+        chi = torch.where(apart, (s - torch.erf(t.alpha * r)) / r, torch.full_like(r, -g0))
+        q = self._real[0]._expand(self.charges.to(xyz))
+        return self.conversion * (q[i] * q[j] * chi).sum()
+
+    def forward(self, xyz):
+        if self._hip_ok(xyz):
+            return ops.EwaldExclEnergyFn.apply(xyz.contiguous(), self.charges, self._spec())
+        return self._torch_energy(xyz)
+
+    # -- analytic-adjoint protocol (md._EOM.rhs_vjp, Stack.force / force_vjp) -------------------------------------
+    def supports_force_vjp(self):
+        return self._hip_ok()
+
+    def force(self, xyz, into=None):
+        """F = -dU/dx in one launch; `into` (a force buffer of another Stack member): added onto it in the same launch and
+        returned."""
+        o = ops.ewald_excl_eval(self._table, xyz.detach(), self._q_atom(), energy=False, grad=True,
+                                into=None if into is None else (into, None), scale=-1.0)
+        return o["grad"]
+
+    def force_vjp(self, xyz, w, want_theta=True, accum=None, into=None):
+        """(F, d(w.F)/dx, [d(w.F)/dcharges]) in one launch plus the fixed-order reduction of the charge part; `accum`
+        (ops.ThetaAccum): that part is added into its flat buffer instead (None returned).  `into` = (F, dq) buffers of
+        another Stack member: this term's force and d(w.F)/dx are added onto them in the same launch."""
+        need = bool(want_theta) and isinstance(self.charges, torch.nn.Parameter)
+        o = ops.ewald_excl_eval(self._table, xyz.detach(), self._q_atom(), w=w.detach(), energy=False, grad=True, into=into,
+                                scale=-1.0, want_pot=need)
+        if not want_theta:
+            return o["grad"], o["hw"], None
+        if not need:
+            return o["grad"], o["hw"], ([] if accum is None else None)
+        gw = ops.coulomb_charge_grad(o["potw"], self._slot, self.n_slots)          # d(w.dU/dx)/dcharges / conversion
+        if accum is not None:
+            jobs = ops.GradJobs()
+            jobs.axpy(accum.off[id(self.charges)], gw)
+            jobs.run(accum, alpha=-self.conversion, accumulate=True)
+            return o["grad"], o["hw"], None
+        return o["grad"], o["hw"], [(-self.conversion) * gw.reshape(self.charges.shape)]
+
+    # -- fixed-capacity topology (HIP-graph capture): the table is static, nothing can overflow ------------------
+    def supports_static_topology(self):
+        return self._hip_ok()
+
+    def set_static_topology(self, on=True):
+        pass
+
+    def static_overflow(self):
+        return False
+
+    def static_version(self):
+        return 0
+
+
+def ewald(system, charges, cutoff, accuracy=1e-5, k_cutoff=None, ex_pairs=None, scale=None, **kw):
+    """The members of an Ewald sum with both truncation errors near `accuracy` (relative): alpha = sqrt(-ln accuracy) /
     cutoff, so that erfc(alpha cutoff) ~ accuracy, and k_cutoff = 2 alpha sqrt(-ln accuracy).  Returns
     {"coulomb_real": CoulombPotentials(system, charges, cutoff, alpha=alpha, shift="none", **kw),
      "coulomb_recip": EwaldReciprocal(system, real, k_cutoff, accuracy)}, ready for Stack({..., **ewald(...)}); **kw: types,
-    conversion, trainable of CoulombPotentials."""
+    conversion, trainable of CoulombPotentials.  With `ex_pairs` ([P, 2] pairs of one replica whose charges do not interact,
+    or interact scaled by `scale`: None, one float or one per pair) the real-space term masks them and a third member
+    "coulomb_excl": EwaldExclusions(system, real, scale) removes them from the reciprocal sum."""
     if not 0.0 < float(accuracy) < 1.0:
         raise ValueError("ewald: accuracy must lie in (0, 1), got %r" % (accuracy,))
     alpha = math.sqrt(-math.log(float(accuracy))) / float(cutoff)
-    real = CoulombPotentials(system, charges, cutoff, alpha=alpha, shift="none", self_energy=True, **kw)
-    return {"coulomb_real": real, "coulomb_recip": EwaldReciprocal(system, real, k_cutoff=k_cutoff, accuracy=accuracy)}
+    if ex_pairs is None:
+        if scale is not None:
+            raise ValueError("ewald: scale given without ex_pairs")
+        real = CoulombPotentials(system, charges, cutoff, alpha=alpha, shift="none", self_energy=True, **kw)
+        return {"coulomb_real": real, "coulomb_recip": EwaldReciprocal(system, real, k_cutoff=k_cutoff, accuracy=accuracy)}
+    real = CoulombPotentials(system, charges, cutoff, alpha=alpha, shift="none", self_energy=True, ex_pairs=ex_pairs, **kw)
+    excl = EwaldExclusions(system, real, scale=scale)
+    return {"coulomb_real": real,
+            "coulomb_recip": EwaldReciprocal(system, real, k_cutoff=k_cutoff, accuracy=accuracy, exclusions=excl),
+            "coulomb_excl": excl}
 
 
 class Stack(torch.nn.Module):

@@ -13,6 +13,7 @@ torch.autograd.Function wrappers that own the differentiation contract
     DihedralPhiFn, DihedralHistFn                               signed dihedral angles of every frame, their periodic histogram
     CoulombEnergyFn -> CoulombGradFn                            damped shifted-force Coulomb sum, order <= 2 in x, 1 in the charges
     EwaldEnergyFn -> EwaldGradFn                                Ewald reciprocal-space sum, order <= 2 in x, 1 in the charges
+    EwaldExclEnergyFn -> EwaldExclGradFn                        Ewald erf correction of excluded / scaled pairs, same orders
 
 Everything here requires HIP tensors; there is no CPU path.
 """
@@ -832,6 +833,165 @@ class EwaldEnergyFn(torch.autograd.Function):
     def backward(ctx, gU):
         xyz, charges = ctx.saved_tensors
         g, gq = EwaldGradFn.apply(xyz, charges, ctx.spec, ctx.cache)
+        return gU * g, gU * gq, None
+
+
+# ----------------------------------------------------------------------------- Ewald correction for excluded pairs (K22)
+class EwaldExclTable:
+    """What the erf correction of excluded / scaled pairs needs beside positions and charges, built once on the host: the
+    pairs of ONE replica as int64 [P, 2] with i < j (`pairs`), their scales float64 [P] (`scale`), and the CSR incidence list
+    the kernel walks -- row(a) = the partners of atom a in ascending order with the pair's scale, every pair once per end --
+    as persistent device buffers (no torch op for them inside a graph capture).  ValueError on a pair with i == j, an index
+    outside [0, n_atoms), a pair listed twice in either orientation (this sum would subtract it twice) or a scale outside
+    [0, 1]."""
+
+    def __init__(self, pairs, scale, n_atoms, n_rep, lengths, alpha, conversion, device):
+        n = int(n_atoms)
+        p = np.asarray(torch.as_tensor(pairs).detach().cpu().numpy(), dtype=np.int64).reshape(-1, 2)
+        if p.shape[0] == 0:
+            raise ValueError("mdgrad_amd: the list of excluded pairs is empty")
+        if p.min() < 0 or p.max() >= n:
+            raise ValueError("mdgrad_amd: an excluded pair refers to an index outside the replica [0, %d)" % n)
+        if bool((p[:, 0] == p[:, 1]).any()):
+            raise ValueError("mdgrad_amd: an excluded pair has i == j (%d)" % int(p[p[:, 0] == p[:, 1]][0, 0]))
+        p = np.stack([p.min(1), p.max(1)], 1)
+        key = p[:, 0] * n + p[:, 1]
+        if len(np.unique(key)) != len(key):
+            u, c = np.unique(key, return_counts=True)
+            d = int(u[c > 1][0])
+            raise ValueError("mdgrad_amd: the excluded pair (%d, %d) is listed twice (in either orientation): the correction "
+                             "would be applied twice" % (d // n, d % n))
+        if scale is None:
+            s = np.zeros(len(p), dtype=np.float64)
+        else:
+            s = np.asarray(torch.as_tensor(scale).detach().cpu().numpy(), dtype=np.float64).reshape(-1)
+            if s.size == 1:
+                s = np.full(len(p), float(s[0]))
+            if s.shape != (len(p),):
+                raise ValueError("mdgrad_amd: scale must be None, one number or one number per excluded pair (%d), got %d"
+                                 % (len(p), s.size))
+        if s.size and not bool(((s >= 0.0) & (s <= 1.0)).all()):
+            raise ValueError("mdgrad_amd: the scale of an excluded pair must lie in [0, 1]")
+        alpha = float(alpha)
+        if not alpha > 0.0:
+            raise ValueError("mdgrad_amd: the Ewald splitting parameter alpha must be positive (got %r)" % alpha)
+        L = np.asarray(lengths, dtype=np.float64).reshape(-1)
+        if L.shape != (3,) or not (L > 0).all():
+            raise ValueError("mdgrad_amd: EwaldExclTable needs three positive cell lengths (got %r)" % (lengths,))
+        self.pairs, self.scale = torch.from_numpy(p.copy()), torch.from_numpy(s.copy())
+        self.n_atoms, self.n_rep, self.n_pairs = n, int(n_rep), int(len(p))
+        self.alpha, self.conversion, self.lengths = alpha, float(conversion), L
+        self.cell_len = (C.c_float * 3)(*[float(x) for x in L])
+        atom = np.concatenate([p[:, 0], p[:, 1]])
+        other = np.concatenate([p[:, 1], p[:, 0]])
+        order = np.lexsort((other, atom))                          # by atom, then by partner
+        cnt = np.zeros(n + 1, dtype=np.int64)
+        np.add.at(cnt, atom + 1, 1)
+        self.row_ptr_host = np.cumsum(cnt).astype(np.int32)
+        self.col_host = other[order].astype(np.int32)
+        self.scl_host = np.concatenate([s, s])[order].astype(np.float32)
+        self.device = device
+        if torch.device(device).type == "cuda":
+            self.row_ptr = torch.as_tensor(self.row_ptr_host, device=device).contiguous()
+            self.col = torch.as_tensor(self.col_host, device=device).contiguous()
+            self.scl = torch.as_tensor(self.scl_host, device=device).contiguous()
+        else:
+            self.row_ptr = self.col = self.scl = None
+
+
+def ewald_excl_eval(table, xyz, q_atom, w=None, energy=True, grad=True, into=None, scale=1.0, want_pot=False):
+    """One launch of mdg_ewald_excl_eval (plus the finish for the energy) -> dict(energy, grad, hw, pot, potw), shaped like
+    coulomb_eval: energy and grad carry the table's conversion, pot_i = sum_j q_j chi(r_ij) and potw_i = sum_j q_j chi'(r_ij)
+    rhat_ij.(w_i - w_j) do not (dU/dq_i = conversion pot_i).  `into` = (grad buffer, hw buffer or None): grad / hw are ADDED
+    onto them, times `scale`; atoms without an excluded pair leave them untouched."""
+    lib = _lib.load()
+    require_gpu(xyz, "xyz")
+    require_gpu(q_atom, "q_atom")
+    N = table.n_rep * table.n_atoms
+    if xyz.shape != (N, 3):
+        raise ValueError("mdgrad_amd: xyz must be [%d, 3] (got %s)" % (N, tuple(xyz.shape)))
+    if q_atom.shape != (N,):
+        raise ValueError("mdgrad_amd: q_atom must be [%d] (got %s)" % (N, tuple(q_atom.shape)))
+    xyz = xyz.contiguous()
+    dev = xyz.device
+    acc = into is not None
+    e = torch.empty(1, device=dev) if energy else None
+    g = (into[0] if acc else torch.empty(N, 3, device=dev)) if grad else None
+    hw = pot = potw = None
+    if w is not None:
+        require_gpu(w, "w")
+        if w.shape != (N, 3):
+            raise ValueError("mdgrad_amd: w must be [%d, 3] (got %s)" % (N, tuple(w.shape)))
+        w = w.contiguous()
+        hw = into[1] if acc else torch.empty(N, 3, device=dev)
+        potw = torch.empty(N, device=dev) if want_pot else None
+    elif want_pot:
+        pot = torch.empty(N, device=dev)
+    partial = None
+    if energy:
+        partial = torch.empty(int(lib.mdg_ewald_excl_partial_size(table.n_rep, table.n_atoms)), device=dev, dtype=torch.float64)
+    check(lib.mdg_ewald_excl_eval(ptr(xyz), table.n_rep, table.n_atoms, table.cell_len, ptr(table.row_ptr), ptr(table.col),
+                                  ptr(table.scl), ptr(q_atom), table.alpha, table.conversion, ptr(w), ptr(e), ptr(g), ptr(hw), ptr(pot), ptr(potw), ptr(partial),
+                                  float(scale), int(acc), stream_ptr(dev)), "mdg_ewald_excl_eval")
+    return dict(energy=e, grad=g, hw=hw, pot=pot, potw=potw)
+
+
+class EwaldExclSpec:
+    """What the autograd functions below need beside the tensors: the table, the per-atom charge buffer and the charge slots
+    (those of the real-space CoulombPotentials the term belongs to)."""
+
+    def __init__(self, table, q_atom, slot, n_slots):
+        self.table, self.q_atom, self.slot, self.n_slots = table, q_atom, slot, int(n_slots)
+
+
+class EwaldExclGradFn(torch.autograd.Function):
+    """(dU/dx, dU/dcharges) of the excluded-pair correction as a differentiable op; backward = the Hessian-vector product and
+    the mixed derivative d(w.dU/dx)/dcharges.  A cotangent on dU/dcharges is not provided."""
+
+    @staticmethod
+    def forward(ctx, xyz, charges, spec, cache):
+        ctx.spec = spec
+        ctx.save_for_backward(xyz, charges)
+        ctx.set_materialize_grads(False)
+        if cache is None:
+            cache = _ewald_excl_first_order(spec, xyz, charges, energy=False)[1:]
+        return cache
+
+    @staticmethod
+    def backward(ctx, wg, wq):
+        xyz, charges = ctx.saved_tensors
+        s = ctx.spec
+        if wq is not None:
+            raise NotImplementedError("mdgrad_amd: derivatives of dU/dcharges of the Ewald exclusion term (a cotangent on it) "
+                                      "are not provided by the HIP kernels")
+        if wg is None:
+            return None, None, None, None
+        o = ewald_excl_eval(s.table, xyz, s.q_atom, w=wg.detach().contiguous(), energy=False, grad=False, want_pot=True)
+        gq = coulomb_charge_grad(o["potw"], s.slot, s.n_slots) * s.table.conversion
+        return o["hw"], gq.reshape(charges.shape), None, None
+
+
+def _ewald_excl_first_order(spec, xyz, charges, energy):
+    o = ewald_excl_eval(spec.table, xyz, spec.q_atom, energy=energy, grad=True, want_pot=True)
+    gq = coulomb_charge_grad(o["pot"], spec.slot, spec.n_slots) * spec.table.conversion            # dU/dq_i = conversion pot_i
+    return o["energy"], o["grad"], gq.reshape(charges.shape)
+
+
+class EwaldExclEnergyFn(torch.autograd.Function):
+    """U_excl(x, charges) of the excluded-pair correction (csrc/ewald_excl.hip), differentiable twice in x and once in the
+    charges."""
+
+    @staticmethod
+    def forward(ctx, xyz, charges, spec):
+        e, g, gq = _ewald_excl_first_order(spec, xyz, charges, energy=True)
+        ctx.spec, ctx.cache = spec, (g, gq)
+        ctx.save_for_backward(xyz, charges)
+        return e.reshape(())
+
+    @staticmethod
+    def backward(ctx, gU):
+        xyz, charges = ctx.saved_tensors
+        g, gq = EwaldExclGradFn.apply(xyz, charges, ctx.spec, ctx.cache)
         return gU * g, gU * gq, None
 
 

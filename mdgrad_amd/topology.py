@@ -122,3 +122,32 @@ def dihedrals_from_bonds(bonds):
             for l in sorted(nbrs[k] - {j, i}):
                 rows.append((i, j, k, l))
     return torch.tensor(rows, dtype=torch.long).reshape(-1, 4)
+
+
+def exclusions_from_bonds(bonds, n_bonds=2, return_separation=False):
+    """Every pair i < j of a bond graph joined by a path of at most `n_bonds` bonds (n_bonds = 2: the 1-2 and 1-3 pairs a
+    force field excludes from its non-bonded sums; 3 adds the 1-4 pairs), sorted and unique: int64 [P, 2] on the host.
+    return_separation: also the length of the shortest such path per pair, int64 [P] -- so that a caller can scale the pairs
+    three bonds apart (EwaldExclusions(..., scale=0.5 where it is 3)).  bonds: [n, 2]; self-bonds are ignored."""
+    n_bonds = int(n_bonds)
+    if n_bonds < 1:
+        raise ValueError("exclusions_from_bonds: n_bonds must be at least 1 (got %d)" % n_bonds)
+    nbrs = {}
+    for i, j in torch.as_tensor(bonds).detach().cpu().to(torch.long).reshape(-1, 2).tolist():
+        if i != j:
+            nbrs.setdefault(i, set()).add(j)
+            nbrs.setdefault(j, set()).add(i)
+    sep = {}
+    for a in sorted(nbrs):                                       # breadth-first from every atom, n_bonds levels deep
+        seen, front = {a}, {a}
+        for depth in range(1, n_bonds + 1):
+            front = {c for b in front for c in nbrs[b]} - seen
+            seen |= front
+            for c in front:
+                if a < c:
+                    sep[(a, c)] = depth
+    keys = sorted(sep)
+    pairs = torch.tensor(keys, dtype=torch.long).reshape(-1, 2)
+    if return_separation:
+        return pairs, torch.tensor([sep[k] for k in keys], dtype=torch.long)
+    return pairs

@@ -263,6 +263,17 @@ int mdg_traj_adj_small_stale(const MdgTrajParams* prm /*host*/, const MdgCell* c
                              float* adj_v0, float* adj_q0, float* adj_pv0, float* adj_theta,
                              int freq, int64_t count0, uint16_t* code, void* stream);
 
+/* Host only, no device needed.  The wave-per-replica kernels round d * inv to the image number with one fused
+ * multiply-add where the cell allows it: for the length h and the inverse inv of one axis (the diagonal entries of
+ * MdgCell::h / MdgCell::inv) this returns 1 and *inv_fused = a float c (inv or a neighbour within four ulps) for which
+ * rint of the EXACT product d c equals rint(fl(d inv)) for every float d with |d inv| < 1.5, or 0 when no such c exists
+ * (those cells keep the separately rounded product).  The launches call it themselves; exported for tests. */
+int mdg_min_image_fused_inv(float h, float inv, float* inv_fused /*host*/);
+/* != 0: a wave-per-replica launch of this system takes the full-ring sweep with the fused minimum image (the ring kernels
+ * run, N is even, one unmasked LJ 12-6 / ExcludedVolume(12) term, every axis has a multiplier, MDG_RING_LEAN is not 0);
+ * per replica it still needs every atom inside the window of the fast image.  The launches decide with the same code. */
+int mdg_traj_ring_fused_image(const MdgTrajParams* prm /*host*/, const MdgCell* cell /*host*/, const MdgTerms* terms /*host*/);
+
 
 /* Fused observable (extension): the radial distribution function of torchmd/observable.py:62-76 evaluated on frames
  * of the trajectory INSIDE the trajectory kernels -- the force sweep already holds every pair distance of a frame, so

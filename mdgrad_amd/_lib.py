@@ -127,6 +127,8 @@ _SIGNATURES = {
                                      P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "mdg_traj_ring_taken": (C.c_int, [C.POINTER(MdgTrajParams), C.POINTER(MdgCell), C.POINTER(MdgTerms)]),
     "mdg_traj_small_fits": (C.c_int, [C.c_int, C.c_int]),
+    "mdg_min_image_fused_inv": (C.c_int, [C.c_float, C.c_float, C.POINTER(C.c_float)]),
+    "mdg_traj_ring_fused_image": (C.c_int, [C.POINTER(MdgTrajParams), C.POINTER(MdgCell), C.POINTER(MdgTerms)]),
     "mdg_traj_fwd_small_ft": (C.c_int, [C.POINTER(MdgTrajParams), C.POINTER(MdgCell), C.POINTER(MdgTerms),
                                         P, P, P, P, P, P, P, P, P, P, P, P]),
     "mdg_traj_adj_small_ft": (C.c_int, [C.POINTER(MdgTrajParams), C.POINTER(MdgCell), C.POINTER(MdgTerms),

@@ -44,6 +44,16 @@ __device__ __forceinline__ float lane0(float v) {
 __device__ __forceinline__ f32x2 rcp2(f32x2 v) { return f32x2{__builtin_amdgcn_rcpf(v.x), __builtin_amdgcn_rcpf(v.y)}; }
 __device__ __forceinline__ float hsum(f32x2 v) { return v.x + v.y; }
 
+// min_image_diag2_near (common.hpp) in three packed instructions: o = fma(d, invf, M) - M is rint(d * invf) of the EXACT product,
+// and invf is a neighbour of inv (often inv itself) for which that switches from image 0 to image +-1 between the same two
+// floats as rint(fl(d * inv)) does.  Such a multiplier exists for most cell lengths, not for all; the host looks for it
+// (mdg_min_image_fused_inv, csrc/traj_small.hip) and a cell without one keeps min_image_diag2_near.
+__device__ __forceinline__ f32x2 min_image_diag2_near_fused(f32x2 d, float invf, float h) {
+    const float M = 12582912.f;
+    const f32x2 o = __builtin_elementwise_fma(d, f32x2{invf, invf}, f32x2{M, M}) - M;
+    return d - o * h;
+}
+
 struct Vec3x2 { f32x2 x, y, z; };
 __device__ __forceinline__ Vec3x2 vzero() { const f32x2 z = {0.f, 0.f}; return Vec3x2{z, z, z}; }
 __device__ __forceinline__ Vec3x2 ring_move(const Vec3x2& a, int s) { return Vec3x2{ring_move(a.x, s), ring_move(a.y, s), ring_move(a.z, s)}; }
@@ -52,9 +62,11 @@ __device__ __forceinline__ Vec3x2 ring_move(const Vec3x2& a, int s) { return Vec
 struct RingLJ {
     float sig2, rc2, m1a, m1b, ka, kb, tsa, tsb, tea, teb;      // LJ 12-6 polynomial (KIND_LJ126)
     float ivx, ivy, ivz, hx, hy, hz;
+    float fvx, fvy, fvz;                                        // multipliers of min_image_diag2_near_fused (TrajArgs::inv_f)
     TermConst t0;                                               // any other single-term form goes through pair_eval
     uint32_t rcm;                                               // cutoff test of ring_pair: bits(rc2) - 1 (0: nothing passes)
-    bool full;                                                  // even N and TrajArgs::lean: ring_sweep<..., FULL> (wave-uniform)
+    bool full;                                                  // even N, TrajArgs::lean and a fused multiplier on every axis:
+                                                                // ring_sweep<..., FULL> (wave-uniform)
 };
 
 __device__ __forceinline__ RingLJ ring_constants(const TrajArgs& A, int m = 0) {
@@ -70,7 +82,8 @@ __device__ __forceinline__ RingLJ ring_constants(const TrajArgs& A, int m = 0) {
     K.hx = A.cell.h[0]; K.hy = A.cell.h[4]; K.hz = A.cell.h[8];
     K.t0 = t0;
     K.rcm = t0.rc2 > 0.f ? __float_as_uint(t0.rc2) - 1u : 0u;          // (rc2 = 0 or not a number: no d2 is below it)
-    K.full = A.lean && !(A.prm.n_atoms & 1);
+    K.fvx = A.inv_f[0]; K.fvy = A.inv_f[1]; K.fvz = A.inv_f[2];
+    K.full = A.lean && A.fused_image && !(A.prm.n_atoms & 1);
     return K;
 }
 
@@ -108,18 +121,23 @@ __device__ __forceinline__ void ring_table_scatter2(const RingRdf& X, int idx, f
 // LEVEL 1: force.  LEVEL 2: force, H.w and the parameter sums.  LEVEL 3: LEVEL 2 without the force (the adjoint's
 // first evaluation of an interval when the forward pass stored the force of that frame: TrajArgs::f_t).
 // r0 / r1: the pair in .x / .y feeds the RDF (exists and, for RDF = 1, is the one copy of a pair met twice).
+// IMAGE: 0 = general minimum image, 1 = window form (min_image_diag2_near), 2 = window form with the multiply folded into the
+// rounding add (min_image_diag2_near_fused: the same image for every pair; the FULL sweep).
 // SUMS = false (LEVEL >= 2): without the parameter sums -- no tk factors, no TH accumulation, no table scatter: the adjoint's
 // first evaluation of an NHC interval, whose sums the midpoint evaluation overwrites before anything reads them (sovlers.py:160).
 constexpr bool ring_level_force(int level) { return level == 1 || level == 2; }
 
-template <int LEVEL, bool NEAR, bool CROSS, bool JSIDE, int RDF, int KIND, bool SUMS = true>
+template <int LEVEL, int IMAGE, bool CROSS, bool JSIDE, int RDF, int KIND, bool SUMS = true>
 __device__ __forceinline__ void ring_pair(const RingLJ& K, const RingRdf& X, const Vec3x2& qi, const Vec3x2& wi,
                                           const Vec3x2& qj, const Vec3x2& wj, bool v0, bool v1, bool r0, bool r1,
                                           Vec3x2& fi, Vec3x2& gi, Vec3x2& fj, Vec3x2& gj, f32x2 (&TH)[MDG_MAX_THETA],
                                           Vec3x2& ri, Vec3x2& rj) {
     f32x2 dx = (CROSS ? qj.x.yx : qj.x) - qi.x, dy = (CROSS ? qj.y.yx : qj.y) - qi.y,
           dz = (CROSS ? qj.z.yx : qj.z) - qi.z;                                       // D = x_j - x_i
-    if constexpr (NEAR) {
+    if constexpr (IMAGE == 2) {
+        dx = min_image_diag2_near_fused(dx, K.fvx, K.hx); dy = min_image_diag2_near_fused(dy, K.fvy, K.hy);
+        dz = min_image_diag2_near_fused(dz, K.fvz, K.hz);
+    } else if constexpr (IMAGE == 1) {
         dx = min_image_diag2_near(dx, K.ivx, K.hx); dy = min_image_diag2_near(dy, K.ivy, K.hy);
         dz = min_image_diag2_near(dz, K.ivz, K.hz);
     } else {
@@ -192,15 +210,18 @@ __device__ __forceinline__ void ring_pair(const RingLJ& K, const RingRdf& X, con
                 kk = (2.f * (e00 * (v0 - v1) + e10 * s0 + e11 * s1)) * (X.tinv_du * sel);
             }
         } else if constexpr (KIND == KIND_LJ126) {
-            // 1/d2 selected to 0 for a rejected pair: s6, s12 and everything below are then exactly zero
+            // 1/d2 selected to 0 for a rejected pair: s6, u and everything below are then exactly zero.
+            // With u = s6/d2 (the S6 factor) every quantity is u times a linear form in s6: c1 = u (m1a - m1b s6),
+            // kk = (u/d2)(kb s6 - ka), S12 factor = s6 u -- no s12, no 1/d2^2.  The linear forms are explicit fmas: every level and
+            // every sweep variant rounds c1 in the same way (the stored force is the bits of the rebuilt one).
             const f32x2 i2 = {ok0 ? __builtin_amdgcn_rcpf(d2.x) : 0.f, ok1 ? __builtin_amdgcn_rcpf(d2.y) : 0.f};
             const f32x2 s2 = K.sig2 * i2;
             const f32x2 s6 = s2 * s2 * s2;
-            const f32x2 s12 = s6 * s6;
-            c1 = (K.m1a * s6 - K.m1b * s12) * i2;
+            const f32x2 u = s6 * i2;
+            c1 = u * __builtin_elementwise_fma(f32x2{-K.m1b, -K.m1b}, s6, f32x2{K.m1a, K.m1a});
             if constexpr (LEVEL >= 2) {
-                kk = (K.kb * s12 - K.ka * s6) * (i2 * i2);
-                if constexpr (SUMS) { tk[0] = s6 * i2; tk[1] = s12 * i2; }   // (S6, S12: both parameter gradients are linear in these sums)
+                kk = (u * i2) * __builtin_elementwise_fma(f32x2{K.kb, K.kb}, s6, f32x2{-K.ka, -K.ka});
+                if constexpr (SUMS) { tk[0] = u; tk[1] = s6 * u; }   // (S6, S12: both parameter gradients are linear in these sums)
             }
         } else {
             // branch-free: a rejected pair is evaluated at the cutoff and multiplied by zero
@@ -312,6 +333,8 @@ __device__ __forceinline__ RingMask ring_mask_load(const uint8_t* __restrict__ m
 // zero for a source lane that is switched off, but an active lane (< nl) only ever reads lanes prev / 4 < nl, which are active:
 // the travelling accumulators see the same sources as in the general sweep.  The LDS copy is written, and the accumulators
 // are brought home and added up, by all lanes outside the branch, as before.
+// FULL also selects the three-instruction minimum image (ring_pair IMAGE = 2): ring_force takes it only where RingLJ::full
+// says that every axis has a fused multiplier.
 template <int LEVEL, bool NEAR, int RDF, int KIND, bool MASK, bool SUMS = true, bool FULL = false>
 __device__ __forceinline__ void ring_sweep(const RingLJ& K, const RingRdf& X, const RingMask& M, int N, int lane, const Vec3x2& q,
                                            const Vec3x2& w, Vec3x2& f, Vec3x2& g, float (&th)[MDG_MAX_THETA], Vec3x2& rq,
@@ -329,6 +352,8 @@ __device__ __forceinline__ void ring_sweep(const RingLJ& K, const RingRdf& X, co
 #pragma unroll
     for (int k = 0; k < MDG_MAX_THETA; ++k) { S[k] = f32x2{0.f, 0.f}; D[k] = S[k]; }
     static_assert(!FULL || !MASK, "the full ring has no selection mask");
+    static_assert(!FULL || NEAR, "the full ring runs on the window form of the minimum image");
+    constexpr int IMAGE = NEAR ? (FULL ? 2 : 1) : 0;              // (ring_pair's)
     const int nsteps = (nl - 1) >> 1;
     if (!FULL || lane < nl) {
     // step 0: the pair inside the lane, both directions (one copy for the histogram)
@@ -336,7 +361,7 @@ __device__ __forceinline__ void ring_sweep(const RingLJ& K, const RingRdf& X, co
         const bool v = FULL || (vi0 && vi1);
         bool vm = v;
         if constexpr (MASK) vm = v && ((ring_mask_word(M.w, lane >> 4) >> (2 * (lane & 15) + 1)) & 1u);   // (i0, i1)
-        ring_pair<LEVEL, NEAR, true, false, RDF, KIND, SUMS>(K, X, q, w, q, w, vm, vm, v, RDF == 2 && v, fi, gi, fj, gj, D, ri, rj);
+        ring_pair<LEVEL, IMAGE, true, false, RDF, KIND, SUMS>(K, X, q, w, q, w, vm, vm, v, RDF == 2 && v, fi, gi, fj, gj, D, ri, rj);
     }
     const int prev = lane < nl ? ((lane == 0 ? nl : lane) - 1) * 4 : lane * 4;     // bpermute address of lane l-1
     int idx = lane;
@@ -355,8 +380,8 @@ __device__ __forceinline__ void ring_sweep(const RingLJ& K, const RingRdf& X, co
             const uint32_t b0 = ring_mask_word(M.w, idx >> 4) >> (2 * (idx & 15)), b1 = ring_mask_word(M.w + 4, idx >> 4) >> (2 * (idx & 15));
             ms0 = s0 && (b0 & 1u); mc0 = c0 && (b0 & 2u); mc1 = c1 && (b1 & 1u); ms1 = s1 && (b1 & 2u);
         }
-        ring_pair<LEVEL, NEAR, false, true, RDF, KIND, SUMS>(K, X, q, w, qj, wj, ms0, ms1, s0, s1, fi, gi, fj, gj, S, ri, rj);
-        ring_pair<LEVEL, NEAR, true, true, RDF, KIND, SUMS>(K, X, q, w, qj, wj, mc0, mc1, c0, c1, fi, gi, fj, gj, S, ri, rj);
+        ring_pair<LEVEL, IMAGE, false, true, RDF, KIND, SUMS>(K, X, q, w, qj, wj, ms0, ms1, s0, s1, fi, gi, fj, gj, S, ri, rj);
+        ring_pair<LEVEL, IMAGE, true, true, RDF, KIND, SUMS>(K, X, q, w, qj, wj, mc0, mc1, c0, c1, fi, gi, fj, gj, S, ri, rj);
     }
     if (!(nl & 1)) {
         // antipodal lanes (k = nl/2) see each other from both sides -> directed evaluation, visitors not updated
@@ -373,8 +398,8 @@ __device__ __forceinline__ void ring_sweep(const RingLJ& K, const RingRdf& X, co
         }
         const bool once = RDF == 2 || 2 * lane < nl;
         Vec3x2 fu = vzero(), gu = vzero(), ru = vzero();
-        ring_pair<LEVEL, NEAR, false, false, RDF, KIND, SUMS>(K, X, q, w, qj, wj, ms0, ms1, s0 && once, s1 && once, fi, gi, fu, gu, D, ri, ru);
-        ring_pair<LEVEL, NEAR, true, false, RDF, KIND, SUMS>(K, X, q, w, qj, wj, mc0, mc1, c0 && once, c1 && once, fi, gi, fu, gu, D, ri, ru);
+        ring_pair<LEVEL, IMAGE, false, false, RDF, KIND, SUMS>(K, X, q, w, qj, wj, ms0, ms1, s0 && once, s1 && once, fi, gi, fu, gu, D, ri, ru);
+        ring_pair<LEVEL, IMAGE, true, false, RDF, KIND, SUMS>(K, X, q, w, qj, wj, mc0, mc1, c0 && once, c1 && once, fi, gi, fu, gu, D, ri, ru);
     }
     }
     // the travelling accumulators are nsteps lanes ahead of their owners

@@ -10,6 +10,7 @@
 //   adjoint  torchmd/sovlers.py:211-293 with backward branches :129-164 / :42-101
 //            (vjp of the RHS written out analytically)
 #include "common.hpp"
+#include <cmath>
 
 namespace {
 
@@ -40,6 +41,10 @@ struct TrajArgs {
     // ring kernels only: take the full-ring sweep (ring_sweep<..., FULL>, no per-pair existence flags) where N is even.
     // Set where the launch is built, from MDG_RING_LEAN (=0: the general sweep for every N; A/B inside one build)
     int lean;
+    // ring kernels only: per axis, the multiplier of min_image_diag2_near_fused (fused_image_multiplier below); fused_image =
+    // every axis has one.  Without it the even-N replicas run the window sweep with its per-pair flags, as with lean = 0.
+    float inv_f[3];
+    int fused_image;
 };
 
 constexpr int KMAX_ALL = MDG_MAX_TERMS * MDG_MAX_THETA;
@@ -910,6 +915,39 @@ int ring_lean() {
     static const int lean = [] { const char* e = getenv("MDG_RING_LEAN"); return !(e && e[0] == '0') ? 1 : 0; }();
     return lean;
 }
+// The multiplier of min_image_diag2_near_fused (traj_ring.hpp) for one axis of an orthorhombic cell: a float c for which
+// rint of the exact product d c picks the image that rint(fl(d inv)) picks, for every float d with |d inv| < 1.5.
+// fl(d inv) is monotone in d, so the rounded form leaves image 0 at one float tau, the smallest d > 0 with fl(d inv) > 0.5
+// (at exactly 0.5 both forms round to the even 0; the negative side is the mirror image: every operation is odd in d).  The
+// exact form switches between the same two floats iff pred(tau) c <= 0.5 < tau c; on either side of them both forms are
+// monotone and stay below 1.5, so they agree everywhere.  The products of two floats are exact in double.
+// inv itself is preferred, then its neighbours by distance, up to four ulps.  false: none of them qualifies.
+bool fused_image_multiplier(float h, float inv, float* out) {
+    if (!(h > 0.f) || !(inv > 0.f) || !std::isfinite(h) || !std::isfinite(inv)) return false;
+    auto rounded = [inv](float d) { volatile float s = d * inv; return (float)s; };     // (one rounding to float, no fma)
+    float tau = 0.5f * h;
+    if (!(tau > 0.f) || !std::isfinite(rounded(2.f * h))) return false;
+    int budget = 64;                                             // (h inv = 1 up to a few ulps: tau is next to h/2)
+    while (rounded(std::nextafterf(tau, 0.f)) > 0.5f && --budget > 0) tau = std::nextafterf(tau, 0.f);
+    while (!(rounded(tau) > 0.5f) && --budget > 0) tau = std::nextafterf(tau, INFINITY);
+    if (budget <= 0) return false;
+    const double below = (double)std::nextafterf(tau, 0.f), at = (double)tau;
+    for (int k = 0; k <= 8; ++k) {                               // 0, -1, +1, -2, +2, ... ulps
+        float c = inv;
+        const int steps = (k + 1) / 2;
+        for (int s = 0; s < steps; ++s) c = std::nextafterf(c, (k & 1) ? 0.f : INFINITY);
+        if (below * (double)c <= 0.5 && 0.5 < at * (double)c) { *out = c; return true; }
+    }
+    return false;
+}
+// TrajArgs::inv_f / fused_image from the cell the kernels use (orthorhombic: the diagonal entries)
+void set_fused_image(TrajArgs& a) {
+    a.fused_image = a.cell.diag ? 1 : 0;
+    for (int k = 0; k < 3; ++k) {
+        a.inv_f[k] = a.cell.inv[4 * k];
+        if (a.fused_image && !fused_image_multiplier(a.cell.h[4 * k], a.cell.inv[4 * k], &a.inv_f[k])) a.fused_image = 0;
+    }
+}
 bool use_ring(const MdgTrajParams& p, const MdgCell& cell, const MdgTerms& terms) {
     return ring_form(p, cell, terms) && (p.block == 64 || (p.block == 0 && p.n_rep >= 1024));
 }
@@ -1147,7 +1185,7 @@ int traj_fwd_small_run(const MdgTrajParams* prm, const MdgCell* cell, const MdgT
     hipStream_t st = (hipStream_t)stream;
     if (rdf || (!stale && use_ring(*prm, *cell, *terms))) {
         MDG_CHECK_ARG(theta || terms->n_theta_total == 0, "%s: null theta", who);
-        a.f_t = o.f_t; a.lean = ring_lean();
+        a.f_t = o.f_t; a.lean = ring_lean(); set_fused_image(a);
         if (!rdf) {
             MDG_RING_LAUNCH(traj_fwd_ring_kernel, false, , dim3(prm->n_rep), dim3(64), RING_LDS_FWD + ring_table_lds(*terms, false),
                             st, a, RingRdfArgs{});
@@ -1203,7 +1241,7 @@ int traj_adj_small_run(const MdgTrajParams* prm, const MdgCell* cell, const MdgT
     hipStream_t st = (hipStream_t)stream;
     if (rdf || (!stale && use_ring(*prm, *cell, *terms))) {
         MDG_CHECK_ARG(theta || terms->n_theta_total == 0, "%s: null theta", who);
-        a.f_t = o.f_t; a.lean = ring_lean();
+        a.f_t = o.f_t; a.lean = ring_lean(); set_fused_image(a);
         if (!rdf) {
             // (tabulated kind: RING_TABLE_WAVES replicas per workgroup share the nodes and one pair of gradient planes)
             const bool rt = terms->t[0].kind == MDG_PAIR_TABLE;
@@ -1252,6 +1290,22 @@ int traj_adj_small_run(const MdgTrajParams* prm, const MdgCell* cell, const MdgT
 extern "C" int mdg_traj_small_fits(int n_atoms, int table_nodes) {
     return n_atoms > 0 && table_nodes >= 0 && small_lds(n_atoms, table_nodes, false) <= SMALL_LDS_MAX &&
            small_lds(n_atoms, table_nodes, true) <= SMALL_LDS_MAX;
+}
+
+extern "C" int mdg_min_image_fused_inv(float h, float inv, float* inv_fused) {
+    float c = 0.f;
+    const bool ok = inv_fused && fused_image_multiplier(h, inv, &c);
+    if (ok) *inv_fused = c;
+    return ok ? 1 : 0;
+}
+
+extern "C" int mdg_traj_ring_fused_image(const MdgTrajParams* prm, const MdgCell* cell, const MdgTerms* terms) {
+    if (!prm || !cell || !terms || !use_ring(*prm, *cell, *terms)) return 0;
+    TrajArgs a{};
+    a.cell = *cell;
+    set_fused_image(a);
+    return ring_lean() && a.fused_image && !(prm->n_atoms & 1) && terms->n_terms == 1 && !terms->t[0].mask &&
+           ring_kind(terms->t[0]) == KIND_LJ126;
 }
 
 extern "C" int mdg_traj_ring_taken(const MdgTrajParams* prm, const MdgCell* cell, const MdgTerms* terms) {

@@ -61,6 +61,8 @@ __device__ __forceinline__ Vec3x2 ring_move(const Vec3x2& a, int s) { return Vec
 // ------------------------------------------------------------------------------------------------ pair sweep
 struct RingLJ {
     float sig2, rc2, m1a, m1b, ka, kb, tsa, tsb, tea, teb;      // LJ 12-6 polynomial (KIND_LJ126)
+    float a6, a12, b6, b12, sg6, sg12;                          // ... with sigma folded in (ring_pair): m1a sigma^6, m1b sigma^12,
+                                                                // ka sigma^6, kb sigma^12; sigma^6, sigma^12 themselves (ring_theta)
     float ivx, ivy, ivz, hx, hy, hz;
     float fvx, fvy, fvz;                                        // multipliers of min_image_diag2_near_fused (TrajArgs::inv_f)
     TermConst t0;                                               // any other single-term form goes through pair_eval
@@ -78,6 +80,8 @@ __device__ __forceinline__ RingLJ ring_constants(const TrajArgs& A, int m = 0) {
     K.ka = (42.f + 6.f) * e4 * cq; K.kb = (156.f + 12.f) * e4;         // phi'' - phi'/r = (kb s12 - ka s6) / d2
     K.tsa = 18.f * e4 * t0.k2 * cq; K.tsb = 72.f * e4 * t0.k2;         // d(w.F)/dsig from (S6, S12)
     K.tea = 12.f * cq; K.teb = 24.f;                                   // d(w.F)/deps
+    K.sg6 = K.sig2 * K.sig2 * K.sig2; K.sg12 = K.sg6 * K.sg6;
+    K.a6 = K.m1a * K.sg6; K.a12 = K.m1b * K.sg12; K.b6 = K.ka * K.sg6; K.b12 = K.kb * K.sg12;
     K.ivx = A.cell.inv[0]; K.ivy = A.cell.inv[4]; K.ivz = A.cell.inv[8];
     K.hx = A.cell.h[0]; K.hy = A.cell.h[4]; K.hz = A.cell.h[8];
     K.t0 = t0;
@@ -97,6 +101,8 @@ struct RingRdf {
     uint32_t* hist; float inv_h, tlo, fmax;                 // RDF = 1: fine histogram [nfine], t = d inv_h + tlo < fmax
     const float4* tab; float ulo, inv_hu, tmax;             // RDF = 2: cell cubics of (dL/dd)/d in u = d^2, t = (d2 - ulo) inv_hu < tmax
                                                             // (fmax / tmax: end of the grid or the observable's cutoff)
+    float toff, tzero;                                      //          t = fma(d2, inv_hu, toff), toff = -ulo inv_hu; tzero = (float)ncell:
+                                                            //          the all-zero cell behind the table, where a rejected pair is sent
     // KIND_TABLE (round 5; the tabulated pair model of traj_small.hip force_table_packed -- pairMLP + prior stacks,
     // scripts/fit_rdf_pair.py:355-368 -- register-resident): the nodes (c1_g, du dc1/du_g) of c1(u) = phi'(r)/r in LDS; the
     // fixed-point words of this workgroup's table gradient (fx64, common.hpp: one int64 per entry, integer LDS atomics:
@@ -157,21 +163,31 @@ __device__ __forceinline__ void ring_pair(const RingLJ& K, const RingRdf& X, con
     }
     if constexpr (RDF == 2) {
         // rdf_bwd_fine_kernel's gradient, d(dist)/dx_j = +D/d, d(dist)/dx_i = -D/d, from the table of (dL/dd)/d over
-        // u = d^2 (rdf_bwd_table_u_kernel): no square root, no division; a rejected pair adds +-0
+        // u = d^2 (rdf_bwd_table_u_kernel): no square root, no division
         // (d2 = 0: t = -ulo inv_hu < 0 -> rejected: the grid starts above zero)
-        f32x2 t = (d2 - X.ulo) * X.inv_hu;
+        // A rejected pair is sent to cell tzero = ncell, the all-zero cell the kernel keeps behind the table (tmax <= ncell: an
+        // accepted pair never reaches it): its cubic is +0 whatever the fraction, so the pair adds +-0 without a second select.
+        // The fraction is v_fract_f32: t - floor(t), which for t >= 0 is exactly t - (float)(int)t.
+        f32x2 t = __builtin_elementwise_fma(d2, f32x2{X.inv_hu, X.inv_hu}, f32x2{X.toff, X.toff});
         const uint32_t lim = __float_as_uint(X.tmax);
         const bool oka = r0 && __float_as_uint(t.x) < lim, okb = r1 && __float_as_uint(t.y) < lim;
-        t = f32x2{oka ? t.x : 0.f, okb ? t.y : 0.f};
+        t = f32x2{oka ? t.x : X.tzero, okb ? t.y : X.tzero};
         const int gA = (int)t.x, gB = (int)t.y;
-        const f32x2 fr = t - f32x2{(float)gA, (float)gB};
+        const f32x2 fr = {__builtin_amdgcn_fractf(t.x), __builtin_amdgcn_fractf(t.y)};
         const float4 ca = X.tab[gA], cb = X.tab[gB];
-        const float sdA = fmaf(fr.x, fmaf(fr.x, fmaf(fr.x, ca.w, ca.z), ca.y), ca.x);
-        const float sdB = fmaf(fr.y, fmaf(fr.y, fmaf(fr.y, cb.w, cb.z), cb.y), cb.x);
-        const f32x2 cw = {oka ? sdA : 0.f, okb ? sdB : 0.f};
-        const f32x2 cx = cw * dx, cy = cw * dy, cz = cw * dz;
-        ri.x -= cx; ri.y -= cy; ri.z -= cz;
-        if constexpr (JSIDE) { rj.x += CROSS ? cx.yx : cx; rj.y += CROSS ? cy.yx : cy; rj.z += CROSS ? cz.yx : cz; }
+        const f32x2 cw = {fmaf(fr.x, fmaf(fr.x, fmaf(fr.x, ca.w, ca.z), ca.y), ca.x),
+                          fmaf(fr.y, fmaf(fr.y, fmaf(fr.y, cb.w, cb.z), cb.y), cb.x)};
+        ri.x = __builtin_elementwise_fma(-cw, dx, ri.x); ri.y = __builtin_elementwise_fma(-cw, dy, ri.y);
+        ri.z = __builtin_elementwise_fma(-cw, dz, ri.z);
+        if constexpr (JSIDE) {
+            if constexpr (CROSS) {
+                rj.x = __builtin_elementwise_fma(cw.yx, dx.yx, rj.x); rj.y = __builtin_elementwise_fma(cw.yx, dy.yx, rj.y);
+                rj.z = __builtin_elementwise_fma(cw.yx, dz.yx, rj.z);
+            } else {
+                rj.x = __builtin_elementwise_fma(cw, dx, rj.x); rj.y = __builtin_elementwise_fma(cw, dy, rj.y);
+                rj.z = __builtin_elementwise_fma(cw, dz, rj.z);
+            }
+        }
     }
     if constexpr (LEVEL >= 1) {
         // topology.py:67, d2 != 0 && d2 < rc2, as ONE unsigned compare: bits(d2) - 1 < bits(rc2) - 1.  d2 is a sum of squares
@@ -210,18 +226,21 @@ __device__ __forceinline__ void ring_pair(const RingLJ& K, const RingRdf& X, con
                 kk = (2.f * (e00 * (v0 - v1) + e10 * s0 + e11 * s1)) * (X.tinv_du * sel);
             }
         } else if constexpr (KIND == KIND_LJ126) {
-            // 1/d2 selected to 0 for a rejected pair: s6, u and everything below are then exactly zero.
-            // With u = s6/d2 (the S6 factor) every quantity is u times a linear form in s6: c1 = u (m1a - m1b s6),
-            // kk = (u/d2)(kb s6 - ka), S12 factor = s6 u -- no s12, no 1/d2^2.  The linear forms are explicit fmas: every level and
-            // every sweep variant rounds c1 in the same way (the stored force is the bits of the rebuilt one).
+            // 1/d2 selected to 0 for a rejected pair: every power and everything below is then exactly zero.
+            // sigma lives in the launch constants, not in the pair: with p3 = 1/d2^3 and p4 = 1/d2^4 every quantity is a power
+            // times a linear form in p3: c1 = p4 (a6 - a12 p3), kk = (p4/d2)(b12 p3 - b6), a6 = m1a sigma^6, a12 = m1b sigma^12,
+            // b6 = ka sigma^6, b12 = kb sigma^12 -- no sigma^2/d2, no s12.  The parameter sums are those of the bare powers
+            // (S6 / sigma^6, S12 / sigma^12); ring_theta applies sigma^6 and sigma^12 once per evaluation.  The linear forms are
+            // explicit fmas: every level and every sweep variant rounds c1 in the same way (the stored force is the bits of the
+            // rebuilt one).
             const f32x2 i2 = {ok0 ? __builtin_amdgcn_rcpf(d2.x) : 0.f, ok1 ? __builtin_amdgcn_rcpf(d2.y) : 0.f};
-            const f32x2 s2 = K.sig2 * i2;
-            const f32x2 s6 = s2 * s2 * s2;
-            const f32x2 u = s6 * i2;
-            c1 = u * __builtin_elementwise_fma(f32x2{-K.m1b, -K.m1b}, s6, f32x2{K.m1a, K.m1a});
+            const f32x2 p2 = i2 * i2;
+            const f32x2 p3 = p2 * i2;
+            const f32x2 p4 = p2 * p2;
+            c1 = p4 * __builtin_elementwise_fma(f32x2{-K.a12, -K.a12}, p3, f32x2{K.a6, K.a6});
             if constexpr (LEVEL >= 2) {
-                kk = (u * i2) * __builtin_elementwise_fma(f32x2{K.kb, K.kb}, s6, f32x2{-K.ka, -K.ka});
-                if constexpr (SUMS) { tk[0] = u; tk[1] = s6 * u; }   // (S6, S12: both parameter gradients are linear in these sums)
+                kk = (p4 * i2) * __builtin_elementwise_fma(f32x2{K.b12, K.b12}, p3, f32x2{-K.b6, -K.b6});
+                if constexpr (SUMS) { tk[0] = p4; tk[1] = p3 * p4; }   // (both parameter gradients are linear in these sums)
             }
         } else {
             // branch-free: a rejected pair is evaluated at the cutoff and multiplied by zero
@@ -293,8 +312,8 @@ __device__ __forceinline__ void ring_lds_fence() {
 }
 
 // All pair terms of one replica.  Outputs: f (force; LEVEL 3 leaves it untouched), g (= dq of the augmented dynamics, already negated),
-// th[k] = this lane's part of the parameter sums over DIRECTED pairs (LEVEL 2; LJ 12-6: of s6 (w.D)/d2 and
-// s12 (w.D)/d2, other forms: of 1/2 d2phi/(dr dtheta_k) (w.D)/r), rq = dL/dq of the fused RDF for this frame (RDF = 2).
+// th[k] = this lane's part of the parameter sums over DIRECTED pairs (LEVEL 2; LJ 12-6: of (w.D)/d2^4 and
+// (w.D)/d2^7, i.e. s6 (w.D)/d2 and s12 (w.D)/d2 without sigma^6 / sigma^12 -- ring_theta<.., true>; other forms: of 1/2 d2phi/(dr dtheta_k) (w.D)/r), rq = dL/dq of the fused RDF for this frame (RDF = 2).
 // The ring has nl = ceil(N/2) lanes (the lanes that own atoms).  The visitors' positions and w do not move at all:
 // they sit in LDS ([6][64] f32x2, written once per evaluation) and lane l reads entry (l - k) mod nl at step k;
 // only the visitors' accumulators travel, through ds_bpermute_b32 (the LDS crossbar: no VALU slot, no memory).
@@ -832,13 +851,15 @@ __global__ __launch_bounds__(RDF ? 1024 : 64) void traj_fwd_ring_kernel(const Tr
 
 // parameter gradient of one augmented evaluation: wave totals of the sweep's sums, weighted with the interval
 // (NVE: both half steps carry the first evaluation's term, sovlers.py:82,101)
-template <int KIND>
+// FOLDED (LJ 12-6): the sums come from ring_pair, whose polynomial carries no sigma -- sigma^6 and sigma^12 join them here, once
+// per evaluation; the shared sweep of several terms (ring_pair_lj_multi) forms the sums with sigma inside.
+template <int KIND, bool FOLDED>
 __device__ __forceinline__ void ring_theta(const RingLJ& K, const float (&th)[MDG_MAX_THETA], float (&gth)[MDG_MAX_THETA],
                                            float h, bool nve) {
     if constexpr (KIND == KIND_TABLE) {
         // (the table gradient is scattered by the sweep itself)
     } else if constexpr (KIND == KIND_LJ126) {
-        const float t6 = wave_sum(th[0]), t12 = wave_sum(th[1]);
+        const float t6 = (FOLDED ? K.sg6 : 1.f) * wave_sum(th[0]), t12 = (FOLDED ? K.sg12 : 1.f) * wave_sum(th[1]);
         const float gs = K.tsa * t6 - K.tsb * t12, ge = K.tea * t6 - K.teb * t12;
         gth[0] += nve ? (gs * 0.5f * h) * 2.f : gs * h;
         gth[1] += nve ? (ge * 0.5f * h) * 2.f : ge * h;
@@ -898,6 +919,8 @@ __device__ __forceinline__ void ring_adj_intervals(const TrajArgs& A, const Ring
                                                    const RingMask (&M)[NT], bool live, size_t fr, int lane, f32x2* __restrict__ lds,
                                                    Vec3x2& lv, Vec3x2& lq, float& lp, float (&gth)[NT][MDG_MAX_THETA]) {
     constexpr bool PARK = ring_adj_parks(KIND, MASK, NT, FT);
+    // (ring_theta: several LJ 12-6 terms take ring_sweep_lj_multi in EVERY evaluation only without the fused observable)
+    static_assert(NT == 1 || !RDF, "several terms: no fused observable");
     const int N = A.prm.n_atoms, T = A.prm.n_frames, C = A.prm.n_chains, N3 = 3 * N;
     f32x2* park = lds + 6 * 64;
     f32x2 ms = {1.f, 1.f};
@@ -980,11 +1003,11 @@ __device__ __forceinline__ void ring_adj_intervals(const TrajArgs& A, const Ring
             if (lane < C && A.g_pv) nlp += A.g_pv[(fr + i - 1) * C + lane];
             lp = nlp;
 #pragma unroll
-            for (int m = 0; m < NT; ++m) ring_theta<KIND>(K[m], th[m], gth[m], h, false);     // :160
+            for (int m = 0; m < NT; ++m) ring_theta<KIND, NT == 1>(K[m], th[m], gth[m], h, false);     // :160
         } else {
             // verlet_update backward branch                          sovlers.py:42-101
 #pragma unroll
-            for (int m = 0; m < NT; ++m) ring_theta<KIND>(K[m], th[m], gth[m], h, true);      // :82,101
+            for (int m = 0; m < NT; ++m) ring_theta<KIND, NT == 1>(K[m], th[m], gth[m], h, true);      // :82,101
 #define MDG_RING_NVE(c)                                                                      \
             {                                                                                \
                 const f32x2 vhalf = v.c - 0.5f * (-f.c) * h;          /* :49-50 */           \
@@ -1036,24 +1059,28 @@ void traj_adj_ring_kernel(const TrajArgs A, const RingRdfArgs F) {
         if constexpr (MASK) M[m] = ring_mask_load(A.terms.t[m].mask, N, lane);
     }
     RingRdf X{};
-    int ncell = 0;
+    int ntab = 0;                                                     // float4 cells in front of the waves' slabs
     if constexpr (RDF) {
         // the cells of rdf_bwd_fine_kernel's table (8 per centre spacing over the same distances), equally spaced in d^2:
-        // one copy for the workgroup, loaded by all its waves
+        // one copy for the workgroup, loaded by all its waves, and behind it ONE all-zero cell (index ncell) for the pairs
+        // the observable rejects (ring_pair)
         float hu;
+        int ncell;
         rdf_u_grid(F.mu, F.nbins, F.reach_bins, X.ulo, hu, ncell);
         float4* tab = reinterpret_cast<float4*>(smr);
         for (int n = threadIdx.x; n < ncell; n += blockDim.x) tab[n] = F.tab[n];
-        X.tab = tab; X.inv_hu = 1.0f / hu;
+        if (threadIdx.x == 0) tab[ncell] = make_float4(0.f, 0.f, 0.f, 0.f);
+        X.tab = tab; X.inv_hu = 1.0f / hu; X.toff = -X.ulo * X.inv_hu; X.tzero = (float)ncell;
         X.tmax = fminf((float)ncell, (F.rc * F.rc - X.ulo) * X.inv_hu);
+        ntab = ncell + 1;
         __syncthreads();
     }
     // per wave: the ring buffers (6 x 64 f32x2) and, where the kernel parks state, its slab behind them
-    f32x2* lds = reinterpret_cast<f32x2*>(smr + 4 * ncell) + wid * ring_adj_slab(ring_adj_parks(KIND, MASK, NT, FT));
+    f32x2* lds = reinterpret_cast<f32x2*>(smr + 4 * ntab) + wid * ring_adj_slab(ring_adj_parks(KIND, MASK, NT, FT));
     if constexpr (KIND == KIND_TABLE) {
         // the nodes and the workgroup's two gradient planes behind the waves' ring buffers (6 x 64 f32x2 each)
         const MdgPairTerm& t0 = A.terms.t[0];
-        float2* ttab = reinterpret_cast<float2*>(smr + 4 * ncell + NWV * 6 * 64 * 2);
+        float2* ttab = reinterpret_cast<float2*>(smr + 4 * ntab + NWV * 6 * 64 * 2);
         unsigned long long* tg = reinterpret_cast<unsigned long long*>(ttab + t0.p);        // [2 p] int64 words
         int32_t* tflag = reinterpret_cast<int32_t*>(tg + 2 * t0.p);
         const float* thp = A.theta + t0.theta_off;

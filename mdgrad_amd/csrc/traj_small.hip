@@ -1257,9 +1257,10 @@ int traj_adj_small_run(const MdgTrajParams* prm, const MdgCell* cell, const MdgT
             return MDG_OK;
         }
         // RING_RDF_ADJ_WAVES replicas per workgroup share the table: 14 KB + 4 x (3 KB + 6 KB parked state) = 50 KB at the
-        // headline's 100 bins -- three workgroups, twelve waves, in the CU's 160 KB (a table near RING_RDF_MAX_CELLS leaves two)
+        // headline's 100 bins -- three workgroups, twelve waves, in the CU's 160 KB (a table near RING_RDF_MAX_CELLS leaves two).
+        // The table in LDS has one cell more than the one in HBM: the all-zero cell the kernel appends for rejected pairs.
         const int wpw = RING_RDF_ADJ_WAVES;
-        const size_t lds = sizeof(float4) * (size_t)P.ncell + wpw * ring_adj_wave_lds(*terms, o.f_t != nullptr);
+        const size_t lds = sizeof(float4) * (size_t)(P.ncell + 1) + wpw * ring_adj_wave_lds(*terms, o.f_t != nullptr);
         MDG_CHECK_ARG(lds <= device_lds_per_block(), "%s: %zu bytes of LDS per workgroup exceed the device's limit", who, lds);
         float4* tab = nullptr;                                        // (stream-ordered scratch: no state, re-entrant)
         MDG_HIP(hipMallocAsync((void**)&tab, sizeof(float4) * (size_t)P.ncell, st));

@@ -1112,6 +1112,41 @@ int mdg_ewald_excl_eval(const float* pos, int n_rep, int n_atoms, const float* c
                         int accumulate, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * K23  Stillinger-Weber two- plus three-body potential for one species over the per-atom (ELL) list (Stillinger and Weber
+ *      1985; mW water: Molinero and Moore 2009; mdgrad_amd/interface.py StillingerWeber, csrc/sw.hip).  With rc = a sigma and
+ *      g(r) = exp(gamma sigma / (r - rc)) for r < rc, exactly 0 otherwise:
+ *        phi2(r)       = A eps [B (sigma/r)^p - (sigma/r)^q] exp(sigma / (r - rc))
+ *        phi3(j, i, k) = lam eps (cos theta_jik - cos0)^2 g(r_ij) g(r_ik)                        (i = the centre)
+ *        U = 1/2 sum_i sum_{j in row(i)} phi2(r_ij) + sum_i sum_{j < k in row(i)} phi3(j, i, k)
+ *      The list may have been searched with any radius >= rc: every entry with r >= rc is skipped (r - rc is formed from
+ *      r = sqrt(d2); the exponentials are expf).  Rows are not staged, so their length is not capped.
+ *      MdgSWConsts holds the fixed constants and host copies of (epsilon, sigma, lam); `theta`, when not null, is a device
+ *      float[3] = (epsilon, sigma, lam) that the kernel reads instead (trainable parameters under HIP-graph replay: no host
+ *      value is baked into the launch).  Without theta the host values must satisfy epsilon > 0, sigma > 0, lam >= 0.
+ *   mdg_sw_eval  laid out like mdg_coulomb_eval (same list, same `accumulate` bits: 1 = add onto grad / hw, 2 = the list was
+ *     searched with a skin -- accepted, and nothing more to do: the support test is always applied; same out_scale).
+ *     w nullable [n_atoms, 3], required for hw / pthw.  Outputs, each nullable:
+ *       energy [1] = U (needs `partial`, mdg_sw_partial_size() floats; fixed-order block partials + a finish kernel)
+ *       grad [n_atoms, 3] = (accumulate & 1 ? grad : 0) + out_scale dU/dx,  hw likewise with H w.  dU/dx_i gathers the pairs of
+ *         i, the triplets centred on i, and the triplets centred on each neighbour j in which i is an end atom (the entries of
+ *         row(j) with j's own stored images)
+ *       pth [n_atoms, 3]  = d u_i / d(epsilon, sigma, lam) of u_i = 1/2 sum_j phi2 + the triplets centred on i
+ *                           (their sums over i are dU/d(epsilon, sigma, lam))
+ *       pthw [n_atoms, 3] = (w . grad_x) of the same three (their sums are d(w.dU/dx)/d(epsilon, sigma, lam))
+ *     H w and pthw come from one pass over Dual numbers seeded with w (csrc/dual.hpp).  No atomics: bitwise reproducible; the
+ *     value parts of a launch with w equal those of a launch without, bit for bit.
+ */
+typedef struct MdgSWConsts {
+    double epsilon, sigma, lam, a, gamma, cos0, A, B;
+    int32_t p, q;
+} MdgSWConsts;
+int64_t mdg_sw_partial_size(int n_atoms);
+int mdg_sw_eval(const float* pos, int n_atoms, const MdgCell* cell /*host*/, const int32_t* col, const int32_t* shift,
+                const int32_t* cnt, int max_nbr, const MdgSWConsts* consts /*host*/, const float* theta, const float* w,
+                float* energy, float* grad, float* hw, float* pth, float* pthw, float* partial, float out_scale,
+                int accumulate, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * f4  bonded terms over a static topology table (csrc/bonded.hip).
  * Replaces torchmd/interface.py:447-455 (BondPotentials.forward: harmonic in the SQUARED bond length,
  * 1/2 k (|b|^2 - ro)^2) and :496-508 (AnglePotentials.forward: 1/2 k (theta - theta0)^2 over triples (i, j, k) centred on

@@ -65,6 +65,12 @@ class MdgCoulombConsts(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("alpha", "rc", "c0", "c1", "g0", "alpha2", "conversion", "self_s")]
 
 
+class MdgSWConsts(C.Structure):
+    """Constants of the Stillinger-Weber term and host copies of (epsilon, sigma, lam) (include/mdgrad_hip.h K23)."""
+    _fields_ = [(n, C.c_double) for n in ("epsilon", "sigma", "lam", "a", "gamma", "cos0", "A", "B")] + \
+               [("p", C.c_int32), ("q", C.c_int32)]
+
+
 class MdgChainStage(C.Structure):
     """One Dense stage of mdg_row_chain (include/mdgrad_hip.h)."""
     _fields_ = [(n, C.c_void_p) for n in ("W", "bias", "in0", "in1", "res0", "res1", "aux0", "aux1", "out0", "out1", "sig",
@@ -273,6 +279,9 @@ _SIGNATURES = {
     "mdg_coulomb_eval": (C.c_int, [P, C.c_int, C.POINTER(MdgCell), P, P, P, C.c_int, P, C.POINTER(MdgCoulombConsts), P,
                                    P, P, P, P, P, P, C.c_float, C.c_int, P]),
     "mdg_coulomb_charge_reduce": (C.c_int, [P, P, C.c_int, C.c_int, C.c_int, P, P]),
+    "mdg_sw_partial_size": (C.c_int64, [C.c_int]),
+    "mdg_sw_eval": (C.c_int, [P, C.c_int, C.POINTER(MdgCell), P, P, P, C.c_int, C.POINTER(MdgSWConsts), P, P,
+                              P, P, P, P, P, P, C.c_float, C.c_int, P]),
     "mdg_ewald_workspace": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "mdg_ewald_eval": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), P, P, P, C.c_int, P, P, P, P, P, P, P, C.c_float,
                                  C.c_int, P]),

@@ -24,11 +24,17 @@ __device__ __forceinline__ Dual dsqrt(Dual a) {
     return {s, 0.5f * a.d / s};
 }
 __device__ __forceinline__ Dual dacos(Dual a) { return {acosf(a.v), -a.d / sqrtf(1.f - a.v * a.v)}; }
+__device__ __forceinline__ Dual dexp(Dual a) {
+    const float e = expf(a.v);
+    return {e, e * a.d};
+}
 
 __device__ __forceinline__ float fsqrt_(float a) { return sqrtf(a); }
 __device__ __forceinline__ Dual fsqrt_(Dual a) { return dsqrt(a); }
 __device__ __forceinline__ float facos_(float a) { return acosf(a); }
 __device__ __forceinline__ Dual facos_(Dual a) { return dacos(a); }
+__device__ __forceinline__ float fexp_(float a) { return expf(a); }
+__device__ __forceinline__ Dual fexp_(Dual a) { return dexp(a); }
 __device__ __forceinline__ float val(float a) { return a; }
 __device__ __forceinline__ float val(Dual a) { return a.v; }
 

@@ -20,6 +20,7 @@
 //   coulomb_eval, coulomb_charge_reduce  K20  interface.py CoulombPotentials  -> mdg_coulomb_eval / mdg_coulomb_charge_reduce
 //   ewald_eval       K21  interface.py EwaldReciprocal      -> mdg_ewald_eval
 //   ewald_excl_eval  K22  interface.py EwaldExclusions      -> mdg_ewald_excl_eval
+//   sw_eval          K23  interface.py StillingerWeber      -> mdg_sw_eval
 //   dihedral_phi_fwd/_bwd, dihedral_hist_fwd/_bwd  K19  observable.py Dihedrals / dihedral_distribution -> mdg_dihedral_phi_* / _hist_*
 //   edge_geom(+_bwd) schnet.py:142                          -> mdg_edge_geom / mdg_edge_geom_bwd
 //   cfconv_fwd/_bwd  K9+K10 modules.py:531-571              -> mdg_cfconv_fwd(_bf16) / mdg_cfconv_bwd(_bf16)
@@ -809,6 +810,39 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> ewald_eval(const Tensor& pos,
     return {U, g, hw, pot, potw};
 }
 
+// ------------------------------------------------------------------------------------------------ K23
+// consts = (epsilon, sigma, lam, a, gamma, cos0, A, B, p, q) of MdgSWConsts; theta: device (epsilon, sigma, lam) read by the
+// kernel instead of the first three.  (U [1] or [0], dU/dx [N,3], H w [N,3] or [0], pth [N,3] or [0], pthw [N,3] or [0]);
+// want_theta: pth without w, pthw with it
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> sw_eval(const Tensor& pos, at::ArrayRef<double> cell, const Tensor& col,
+                                                           const Tensor& shift, const Tensor& cnt, at::ArrayRef<double> consts,
+                                                           const OptTensor& theta, const OptTensor& w, bool want_energy,
+                                                           bool want_theta) {
+    check_f32(pos, "pos");
+    TORCH_CHECK(pos.dim() == 2 && pos.size(1) == 3 && pos.size(0) > 0 && pos.size(0) <= INT32_MAX, "mdgrad: pos must be [N,3]");
+    TORCH_CHECK(consts.size() == 10, "mdgrad: consts = (epsilon, sigma, lam, a, gamma, cos0, A, B, p, q)");
+    const MdgCell c = make_cell(cell);
+    const EllRef e = ell_of(pos, col, shift, cnt);
+    const MdgSWConsts k{consts[0], consts[1], consts[2], consts[3], consts[4], consts[5], consts[6], consts[7],
+                        (int32_t)consts[8], (int32_t)consts[9]};
+    TORCH_CHECK((double)k.p == consts[8] && (double)k.q == consts[9], "mdgrad: the exponents p, q must be integers");
+    const float* tp = fptr(theta, "theta");
+    if (tp) { same_device(pos, *theta, "theta"); TORCH_CHECK(theta->numel() == 3, "mdgrad: theta must be (epsilon, sigma, lam)"); }
+    const float* wp = fptr(w, "w");
+    if (wp) { same_device(pos, *w, "w"); TORCH_CHECK(w->sizes() == pos.sizes(), "mdgrad: w must have the shape of pos"); }
+    const int n = (int)pos.size(0);
+    const auto o = pos.options();
+    Tensor U = at::empty({want_energy ? 1 : 0}, o), g = at::empty_like(pos);
+    Tensor hw = wp ? at::empty_like(pos) : at::empty({0}, o);
+    Tensor pth = (want_theta && !wp) ? at::empty_like(pos) : at::empty({0}, o);
+    Tensor pthw = (want_theta && wp) ? at::empty_like(pos) : at::empty({0}, o);
+    Tensor partial = at::empty({mdg_sw_partial_size(n)}, o);
+    ok(mdg_sw_eval(fptr(pos), n, &c, e.col, e.shift, e.cnt, e.max_nbr, &k, tp, wp, want_energy ? mptr(U) : nullptr, mptr(g),
+                   wp ? mptr(hw) : nullptr, (want_theta && !wp) ? mptr(pth) : nullptr, (want_theta && wp) ? mptr(pthw) : nullptr,
+                   mptr(partial), 1.f, 0, stream_of(pos)));
+    return {U, g, hw, pth, pthw};
+}
+
 // ------------------------------------------------------------------------------------------------ K22
 // pos [R n, 3], q float [R n], cell_len = the three diagonal lengths; row_ptr int32 [n + 1], col int32 [nnz], scale float [nnz]:
 // the CSR incidence list of ops.EwaldExclTable (checked here with device reads: the kernel indexes pos with col).
@@ -890,6 +924,8 @@ TORCH_LIBRARY(mdgrad, m) {
     m.def("coulomb_eval(Tensor pos, float[] cell, Tensor col, Tensor shift, Tensor cnt, Tensor q, float[] consts, Tensor? w, "
           "bool want_energy, bool want_pot) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("coulomb_charge_reduce(Tensor val, Tensor? types, int group, int n_slots) -> Tensor");
+    m.def("sw_eval(Tensor pos, float[] cell, Tensor col, Tensor shift, Tensor cnt, float[] consts, Tensor? theta, Tensor? w, "
+          "bool want_energy, bool want_theta) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("ewald_eval(Tensor pos, int n_rep, float[] cell, Tensor q, Tensor kvec, Tensor coef, Tensor? w, bool want_energy, "
           "bool want_pot) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("ewald_excl_eval(Tensor pos, int n_rep, float[] cell_len, Tensor row_ptr, Tensor col, Tensor scale, Tensor q, float alpha, "
@@ -933,6 +969,7 @@ TORCH_LIBRARY_IMPL(mdgrad, CUDA, m) {      // (the HIP backend registers under t
     m.impl("dihedral_hist_bwd", dihedral_hist_bwd);
     m.impl("coulomb_eval", coulomb_eval);
     m.impl("coulomb_charge_reduce", coulomb_charge_reduce);
+    m.impl("sw_eval", sw_eval);
     m.impl("ewald_eval", ewald_eval);
     m.impl("ewald_excl_eval", ewald_excl_eval);
     m.impl("edge_geom", edge_geom);

@@ -1,11 +1,13 @@
 """Energy calculators with the reference's interface (torchmd/interface.py):
-GeneralInteraction :33-57, PairPotentials :217-300, Electrostatics :303-361 (as CoulombPotentials), Stack :364-403
+GeneralInteraction :33-57, PairPotentials :217-300, Electrostatics :303-361 (as CoulombPotentials), Stack :364-403;
+StillingerWeber (three-body, no counterpart in the reference)
 (GNNPotentials lives in mdgrad_amd.nn).  forward(xyz) -> energy; _reset_topology(xyz) rebuilds the neighbour list.
 """
 import inspect
 import math
 import os
 
+import numpy as np
 import torch
 from torch.nn import ModuleDict
 
@@ -909,6 +911,267 @@ class CoulombPotentials(GeneralInteraction):
             jobs.run(accum, alpha=-self.conversion, accumulate=True)
             return o["grad"], o["hw"], None
         return o["grad"], o["hw"], [(-self.conversion) * gw.reshape(self.charges.shape)]
+
+
+class StillingerWeber(GeneralInteraction):
+    """Stillinger-Weber potential for one species (Stillinger and Weber 1985): a short-ranged pair term plus a three-body
+    term that prefers the angle cos0 between the bonds of every atom to its near neighbours -- tetrahedral silicon
+    (`silicon`) and monatomic coarse-grained water (`mW`, Molinero and Moore 2009).  With rc = a sigma:
+
+        U    = sum_{i<j} phi2(r_ij) + sum_i sum_{j<k in row(i)} phi3(r_ij, r_ik, cos theta_jik)
+        phi2 = A eps [B (sigma/r)^p - (sigma/r)^q] exp(sigma / (r - a sigma))                    r < a sigma, else 0
+        phi3 = lam eps (cos theta - cos0)^2 exp(gamma sigma/(r_ij - a sigma)) exp(gamma sigma/(r_ik - a sigma))
+
+    row(i) is the neighbour row of the ELL list that PairPotentials would use at the cutoff a sigma: the same minimum image
+    and the same (d2 < rc^2) & (d2 != 0) test; triplets stay inside their replica (System.replicate).  There is no fixed
+    topology: the triplets are those of the current list.
+
+    `epsilon`, `sigma` and `lam` are the parameters when trainable, otherwise buffers; a, gamma, cos0, A, B and the integer
+    exponents 0 <= q < p <= 12 are constants.  Not covered: `index_tuple`, `ex_pairs` (both rejected) and per-type or
+    multi-species parameters (one (epsilon, sigma, lam) for all atoms).
+
+    A trainable sigma moves the cutoff a sigma.  The kernel always applies r < a sigma with the live sigma, so a list
+    searched with a larger radius is exact; the list is searched with `self.cutoff`, which is kept while
+    a sigma <= cutoff <= `cutoff_keep` a sigma and otherwise reset to `cutoff_reset` a sigma (sigma is read on the host
+    then, outside a HIP-graph capture only and only when its version counter moved; `static_version()` changes with the
+    cutoff, so captured graphs are rebuilt).
+
+    forward(xyz) is differentiable twice in xyz and once in (epsilon, sigma, lam) on the HIP kernel (ops.SWEnergyFn,
+    csrc/sw.hip); force / force_vjp serve the analytic adjoint and HIP-graph replay, also while the parameters require grad:
+    d(w.F)/d(epsilon, sigma, lam) comes from the same launch plus a fixed-order reduction.  float64 or host positions take
+    the torch restatement `_torch_energy`."""
+
+    accepts_into = True
+    accepts_accum = True
+    analytic = True
+    cutoff_reset = 1.02          # a reset list is searched with this multiple of a sigma ...
+    cutoff_keep = 1.05           # ... and kept while a sigma <= cutoff <= this multiple of a sigma (design constants)
+    # 1 kcal/mol in eV: 4184 J/mol over (1.602176634e-19 J/eV * 6.02214076e23 /mol), the exact SI values of 2019
+    KCAL_PER_MOL = 4184.0 / (1.602176634e-19 * 6.02214076e23)
+
+    def __init__(self, system, epsilon, sigma, lam=21.0, a=1.80, gamma=1.20, cos0=-1.0 / 3.0, A=7.049556277, B=0.6022245584,
+                 p=4, q=0, trainable=True, index_tuple=None, ex_pairs=None):
+        super().__init__(system)
+        if index_tuple is not None or ex_pairs is not None:
+            raise ValueError("StillingerWeber: index_tuple and ex_pairs are not supported (one species, every pair)")
+        self._consts = ops.sw_consts(epsilon, sigma, lam, a, gamma, cos0, A, B, p, q)
+        k = self._consts
+        self.a, self.gamma, self.cos0, self.A, self.B, self.p, self.q = k.a, k.gamma, k.cos0, k.A, k.B, int(k.p), int(k.q)
+        h = np.asarray(system.get_cell(), dtype=np.float64)
+        h = np.diag(h) if h.ndim == 1 else h
+        vol = abs(float(np.linalg.det(h)))
+        self._half_height = 0.5 * min(vol / float(np.linalg.norm(np.cross(h[(d + 1) % 3], h[(d + 2) % 3]))) for d in range(3))
+        if k.a * k.sigma > self._half_height:
+            raise ValueError("StillingerWeber: a * sigma = %g exceeds half the shortest cell height (%g)"
+                             % (k.a * k.sigma, self._half_height))
+        for name, v in (("epsilon", k.epsilon), ("sigma", k.sigma), ("lam", k.lam)):
+            t = torch.tensor([v], dtype=torch.float32, device=self.device)
+            if trainable:
+                setattr(self, name, torch.nn.Parameter(t))
+            else:
+                self.register_buffer(name, t)
+        self.index_tuple, self.ex_pairs, self._mask = None, None, None
+        self._n_rep = system.get_number_of_atoms() // self._group
+        self._ell = None
+        self.cutoff, self._cut_ver, self._list_ver, self._sig_key = None, 0, -1, None
+        self._sync_cutoff()
+        if torch.device(self.device).type == "cuda":
+            self._reset_topology(torch.Tensor(system.get_positions()).to(system.device))
+            self._theta()
+
+    @classmethod
+    def silicon(cls, system, **kw):
+        """Stillinger and Weber's silicon: epsilon = 2.1683 eV, sigma = 2.0951 Angstrom, lam = 21."""
+        kw.setdefault("lam", 21.0)
+        return cls(system, 2.1683, 2.0951, **kw)
+
+    @classmethod
+    def mW(cls, system, **kw):
+        """Molinero and Moore's monatomic water: epsilon = 6.189 kcal/mol (in eV), sigma = 2.3925 Angstrom, lam = 23.15."""
+        kw.setdefault("lam", 23.15)
+        return cls(system, 6.189 * cls.KCAL_PER_MOL, 2.3925, **kw)
+
+    def _hip_ok(self, xyz=None):
+        if xyz is not None and (not xyz.is_cuda or xyz.dtype != torch.float32):
+            return False
+        return self.analytic and self._ell is not None
+
+    # -- the cutoff the list is searched with ---------------------------------------------------------------------
+    def _sync_cutoff(self):
+        """Apply the cutoff rule to the current sigma; True when the cutoff was reset.  Inside a capture, or while sigma's
+        version counter has not moved, nothing is read."""
+        s = self.sigma
+        if s.is_cuda and torch.cuda.is_current_stream_capturing():
+            return False
+        key = (s.data_ptr(), s._version)
+        if key == self._sig_key:
+            return False
+        self._sig_key = key
+        rc = self.a * float(s.detach())                       # (one host read per change of sigma)
+        if not rc > 0.0:
+            raise ValueError("StillingerWeber: sigma must stay positive (got %g)" % (rc / self.a))
+        if self.cutoff is not None and rc <= self.cutoff <= self.cutoff_keep * rc:
+            return False
+        self.cutoff = self.cutoff_reset * rc
+        self._cut_ver += 1
+        return True
+
+    def static_version(self):
+        return (super().static_version(), self._cut_ver)
+
+    # -- topology: the lists of PairPotentials ---------------------------------------------------------------------
+    def _reset_topology(self, xyz, _cache=None):
+        self._topo_stamp = object()
+        self._sync_cutoff()
+        st = self._static if self._static_on else None
+        vkey = ("verlet", float(self.cutoff), None, self._group)
+        if st is not None and _cache is not None and vkey in _cache:
+            self._ell = _cache[vkey].ell             # a Stack member's Verlet list (the support test is applied per pair)
+        elif st is not None:
+            self._ell = self._shared_static_ell(xyz, _cache, st)
+        else:
+            self._ell = self._shared_ell(xyz, _cache)
+        self._list_ver = self._cut_ver
+
+    def supports_static_topology(self):
+        return self._hip_ok()
+
+    def set_static_topology(self, on=True):
+        self._static_on = bool(on)
+        self._sync_cutoff()
+        if on and self._static is None:
+            longest = int(self._ell.cnt.max().item())
+            self._static = dict(max_nbr=min(self._group - 1, (int(longest * 1.25) + 15) // 8 * 8),
+                                need=torch.zeros(2, dtype=torch.int32, device=self.device), version=0)
+
+    # -- the device copy of (epsilon, sigma, lam) the kernel reads -------------------------------------------------
+    def _theta(self):
+        """(epsilon, sigma, lam) in a persistent device buffer that is refreshed when one of them changed (version counters);
+        inside a HIP-graph capture it is returned as it is -- the replaying pass refreshes it once before its first replay
+        (`prepare_pass`), so the captured steps carry no torch op for it."""
+        ps = (self.epsilon, self.sigma, self.lam)
+        buf = getattr(self, "_theta_buf", None)
+        capturing = ps[0].is_cuda and torch.cuda.is_current_stream_capturing()
+        if buf is None or buf.device != ps[0].device:
+            if capturing:
+                return torch.cat([p.detach().reshape(-1) for p in ps])
+            buf = self._theta_buf = torch.empty(3, device=ps[0].device, dtype=torch.float32)
+            self._theta_key = None
+        if capturing:
+            return buf
+        key = tuple((p.data_ptr(), p._version) for p in ps)
+        if self._theta_key != key:
+            torch.cat([p.detach().reshape(-1).to(torch.float32) for p in ps], out=buf)
+            self._theta_key = key
+        return buf
+
+    def prepare_pass(self):
+        self._sync_cutoff()
+        if self._hip_ok():
+            self._theta()
+
+    def _current_list(self, xyz):
+        """The list to evaluate on: rebuilt here when sigma has moved the cutoff since the last search (never inside a
+        capture, where sigma is not read)."""
+        self._sync_cutoff()
+        if self._list_ver != self._cut_ver:
+            self._reset_topology(xyz.detach())
+        return self._ell
+
+    # -- energy ----------------------------------------------------------------------------------------------------
+    def _pairs(self, xyz, rc):
+        """Half list (i, j, image offsets) at xyz of every pair of a replica closer than rc, by torch ops with the
+        reference's minimum image (torchmd/topology.py:30-73)."""
+        n, R = self._group, self._n_rep
+        cell = self.cell.detach().to(xyz)
+        cell = torch.diag(cell) if cell.dim() == 1 else cell
+        iu = torch.triu_indices(n, n, offset=1, device=xyz.device)
+        x = xyz.detach().reshape(R, n, 3)
+        D = x[:, iu[1]] - x[:, iu[0]]
+        s = D.matmul(cell.inverse())
+        o = -(s > 0.5).to(xyz) + (s < -0.5).to(xyz)
+        d2 = (D + o.matmul(cell)).pow(2).sum(-1)
+        keep = (d2 < rc ** 2) & (d2 != 0)
+        rep, idx = torch.nonzero(keep, as_tuple=True)
+        return iu[0][idx] + rep * n, iu[1][idx] + rep * n, o[rep, idx]
+
+    def _torch_energy(self, xyz):
+        """The same energy in torch ops, in the dtype and on the device of xyz (differentiable by autograd in xyz and in
+        epsilon, sigma, lam): the pairs inside a sigma, then every triplet as two entries of one atom's row."""
+        eps, sig, lam = (p.to(xyz).reshape(()) for p in (self.epsilon, self.sigma, self.lam))
+        rc = self.a * sig
+        i, j, off = self._pairs(xyz, float(rc.detach()))
+        cell = self.cell.detach().to(xyz)
+        cell = torch.diag(cell) if cell.dim() == 1 else cell
+        d = xyz[i] - xyz[j] - off.matmul(cell)
+        r = d.pow(2).sum(-1).sqrt()
+        sr = sig / r
+        phi2 = self.A * eps * (self.B * sr ** self.p - sr ** self.q) * torch.exp(sig / (r - rc))
+        # rows: every pair as (centre, unit vector centre -> end, g), grouped by centre into a padded [N, K] table
+        N = xyz.shape[0]
+        centre = torch.cat([i, j])
+        u = torch.cat([-d, d]) / torch.cat([r, r])[:, None]
+        g = torch.exp(self.gamma * sig / (torch.cat([r, r]) - rc))
+        order = torch.argsort(centre, stable=True)
+        centre, u, g = centre[order], u[order], g[order]
+        cnt = torch.bincount(centre, minlength=N)
+        K = int(cnt.max()) if centre.numel() else 0
+        if K < 2:
+            return phi2.sum()
+        start = torch.cumsum(cnt, 0) - cnt
+        slot = torch.arange(centre.numel(), device=xyz.device) - start[centre]
+        U = xyz.new_zeros(N, K, 3).index_put((centre, slot), u)
+        G = xyz.new_zeros(N, K).index_put((centre, slot), g)             # (padding: g = 0, no contribution)
+        t = torch.triu_indices(K, K, offset=1, device=xyz.device)
+        c = (U[:, t[0]] * U[:, t[1]]).sum(-1)
+        phi3 = lam * eps * (c - self.cos0) ** 2 * G[:, t[0]] * G[:, t[1]]
+        return phi2.sum() + phi3.sum()
+
+    def forward(self, xyz):
+        if self._hip_ok(xyz):
+            ell = self._current_list(xyz)
+            return ops.SWEnergyFn.apply(xyz.contiguous(), self.epsilon, self.sigma, self.lam,
+                                        ops.SWSpec(ell, self._consts, self._theta()))
+        return self._torch_energy(xyz)
+
+    # -- analytic-adjoint protocol (md._EOM.rhs_vjp, Stack.force / force_vjp) -------------------------------------
+    def supports_force_vjp(self):
+        return self._hip_ok()
+
+    def force(self, xyz, into=None):
+        """F = -dU/dx in one kernel launch; `into` (a force buffer of another Stack member): added onto it in the same
+        launch and returned."""
+        o = ops.sw_eval(self._current_list(xyz), xyz.detach(), self._consts, self._theta(), energy=False, grad=True,
+                        into=None if into is None else (into, None), scale=-1.0)
+        return o["grad"]
+
+    def force_vjp(self, xyz, w, want_theta=True, accum=None, into=None):
+        """(F, d(w.F)/dx, [d(w.F)/d epsilon, d(w.F)/d sigma, d(w.F)/d lam]) in one launch plus the fixed-order reduction of
+        the parameter part; `accum` (ops.ThetaAccum): that part is added into its flat buffer instead (None returned).
+        `into` = (F, dq) buffers of another Stack member: this term's force and d(w.F)/dx are added onto them in the same
+        launch."""
+        params = [p for p in (self.epsilon, self.sigma, self.lam) if isinstance(p, torch.nn.Parameter)]
+        need = bool(want_theta) and bool(params)
+        o = ops.sw_eval(self._current_list(xyz), xyz.detach(), self._consts, self._theta(), w=w.detach(), energy=False,
+                        grad=True, into=into, scale=-1.0, want_theta=need)
+        if not want_theta:
+            return o["grad"], o["hw"], None
+        if not need:
+            return o["grad"], o["hw"], ([] if accum is None else None)
+        if accum is not None:
+            jobs = ops.GradJobs()
+            offs = [accum.off.get(id(p)) for p in params]
+            if len(params) == 3 and None not in offs and offs[1] == offs[0] + 1 and offs[2] == offs[0] + 2:
+                jobs.colsum(offs[0], o["pthw"])                  # the three parameters are adjacent in the flat buffer
+            else:
+                for col, p in enumerate((self.epsilon, self.sigma, self.lam)):
+                    if isinstance(p, torch.nn.Parameter) and accum.off.get(id(p)) is not None:
+                        jobs.colsum(accum.off[id(p)], o["pthw"][:, col:col + 1])
+            jobs.run(accum, alpha=-1.0, accumulate=True)
+            return o["grad"], o["hw"], None
+        gw = ops.sw_theta_sum(o["pthw"], alpha=-1.0)
+        return o["grad"], o["hw"], [gw[k:k + 1].reshape(p.shape) for k, p in enumerate((self.epsilon, self.sigma, self.lam))
+                                    if isinstance(p, torch.nn.Parameter)]
 
 
 class EwaldReciprocal(torch.nn.Module):

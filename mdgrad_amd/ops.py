@@ -14,6 +14,7 @@ torch.autograd.Function wrappers that own the differentiation contract
     CoulombEnergyFn -> CoulombGradFn                            damped shifted-force Coulomb sum, order <= 2 in x, 1 in the charges
     EwaldEnergyFn -> EwaldGradFn                                Ewald reciprocal-space sum, order <= 2 in x, 1 in the charges
     EwaldExclEnergyFn -> EwaldExclGradFn                        Ewald erf correction of excluded / scaled pairs, same orders
+    SWEnergyFn -> SWGradFn                                      Stillinger-Weber term, order <= 2 in x, 1 in (epsilon, sigma, lam)
 
 Everything here requires HIP tensors; there is no CPU path.
 """
@@ -675,6 +676,141 @@ class CoulombEnergyFn(torch.autograd.Function):
         xyz, charges = ctx.saved_tensors
         g, gq = CoulombGradFn.apply(xyz, charges, ctx.spec, ctx.cache)
         return gU * g, gU * gq, None
+
+
+# ----------------------------------------------------------------------------- Stillinger-Weber term (K23)
+def sw_consts(epsilon, sigma, lam=21.0, a=1.80, gamma=1.20, cos0=-1.0 / 3.0, A=7.049556277, B=0.6022245584, p=4, q=0):
+    """MdgSWConsts: the fixed constants of the Stillinger-Weber form and host copies of (epsilon, sigma, lam) -- the kernel
+    reads those three from a device buffer instead when sw_eval is given one."""
+    epsilon, sigma, lam, a, gamma = float(epsilon), float(sigma), float(lam), float(a), float(gamma)
+    if not epsilon > 0.0:
+        raise ValueError("mdgrad_amd: epsilon must be positive (got %r)" % epsilon)
+    if not sigma > 0.0:
+        raise ValueError("mdgrad_amd: sigma must be positive (got %r)" % sigma)
+    if not lam >= 0.0:
+        raise ValueError("mdgrad_amd: lam must be >= 0 (got %r)" % lam)
+    if not (a > 0.0 and gamma >= 0.0):
+        raise ValueError("mdgrad_amd: a must be positive and gamma >= 0 (got %r, %r)" % (a, gamma))
+    if int(p) != p or int(q) != q or not 0 <= int(q) < int(p) <= 12:
+        raise ValueError("mdgrad_amd: the exponents must be integers with 0 <= q < p <= 12 (got p = %r, q = %r)" % (p, q))
+    k = _lib.MdgSWConsts()
+    k.epsilon, k.sigma, k.lam, k.a, k.gamma, k.cos0, k.A, k.B = epsilon, sigma, lam, a, gamma, float(cos0), float(A), float(B)
+    k.p, k.q = int(p), int(q)
+    return k
+
+
+def sw_eval(ell, xyz, consts, theta=None, w=None, energy=True, grad=True, into=None, scale=1.0, want_theta=False):
+    """One launch of mdg_sw_eval -> dict(energy, grad, hw, pth, pthw).  `theta`: device float [3] = (epsilon, sigma, lam) that
+    the kernel reads in place of the host copies in `consts`.  `into` = (grad buffer, hw buffer or None): the per-atom outputs
+    are ADDED onto them, times `scale`, as in pair_eval.  want_theta: without `w` the per-atom parameter terms pth [N, 3] =
+    d u_i / d(epsilon, sigma, lam), with `w` their directional derivatives pthw [N, 3] -- what sw_theta_sum reduces.  The list
+    may have been searched with any radius >= a sigma (a skin, a kept cutoff): the kernel applies r < a sigma per pair."""
+    lib = _lib.load()
+    require_gpu(xyz, "xyz")
+    N = ell.n_atoms
+    if xyz.shape != (N, 3):
+        raise ValueError("mdgrad_amd: xyz must be [%d, 3] (got %s)" % (N, tuple(xyz.shape)))
+    if theta is not None:
+        require_gpu(theta, "theta")
+        if theta.shape != (3,) or not theta.is_contiguous():
+            raise ValueError("mdgrad_amd: theta must be a contiguous [3] tensor (got %s)" % (tuple(theta.shape),))
+    xyz = xyz.contiguous()
+    dev = xyz.device
+    acc = into is not None
+    e = torch.empty(1, device=dev) if energy else None
+    g = (into[0] if acc else torch.empty(N, 3, device=dev)) if grad else None
+    hw = pth = pthw = None
+    if w is not None:
+        require_gpu(w, "w")
+        w = w.contiguous()
+        hw = into[1] if acc else torch.empty(N, 3, device=dev)
+        pthw = torch.empty(N, 3, device=dev) if want_theta else None
+    elif want_theta:
+        pth = torch.empty(N, 3, device=dev)
+    partial = torch.empty(int(lib.mdg_sw_partial_size(N)), device=dev) if energy else None
+    recheck = bool(getattr(ell, "verlet", False))
+    check(lib.mdg_sw_eval(ptr(xyz), N, C.byref(ell.cell_struct), ptr(ell.col), ptr(ell.shift), ptr(ell.cnt), ell.max_nbr,
+                          C.byref(consts), ptr(theta), ptr(w), ptr(e), ptr(g), ptr(hw), ptr(pth), ptr(pthw), ptr(partial),
+                          float(scale), int(acc) | (2 if recheck else 0), stream_ptr(dev)), "mdg_sw_eval")
+    return dict(energy=e, grad=g, hw=hw, pth=pth, pthw=pthw)
+
+
+class _FlatOut:
+    """A bare output buffer with ThetaAccum's fields, for GradJobs.run."""
+
+    def __init__(self, n, device):
+        self.flat, self.t, self.idx = torch.empty(n, device=device, dtype=torch.float32), None, None
+
+
+def sw_theta_sum(per_atom, alpha=1.0):
+    """[3] = alpha * the sums over the atoms of the per-atom parameter terms [N, 3] of sw_eval, in the fixed order of
+    mdg_grad_jobs."""
+    out = _FlatOut(3, per_atom.device)
+    jobs = GradJobs()
+    jobs.colsum(0, per_atom)
+    jobs.run(out, alpha=alpha, accumulate=False)
+    return out.flat
+
+
+class SWSpec:
+    """What the autograd functions below need beside the tensors: the list, the constants and the device buffer
+    (epsilon, sigma, lam), kept current by StillingerWeber."""
+
+    def __init__(self, ell, consts, theta):
+        self.ell, self.consts, self.theta = ell, consts, theta
+
+
+def _sw_first_order(spec, xyz, energy):
+    o = sw_eval(spec.ell, xyz, spec.consts, spec.theta, energy=energy, grad=True, want_theta=True)
+    return o["energy"], o["grad"], sw_theta_sum(o["pth"])
+
+
+class SWGradFn(torch.autograd.Function):
+    """(dU/dx, dU/d(epsilon, sigma, lam)) as a differentiable op; backward = the Hessian-vector product and the mixed
+    derivative d(w.dU/dx)/d(epsilon, sigma, lam) (the second autograd pass of torchmd/sovlers.py:229-233).  A cotangent on
+    the parameter gradient is not provided."""
+
+    @staticmethod
+    def forward(ctx, xyz, eps, sigma, lam, spec, cache):
+        ctx.spec = spec
+        ctx.shapes = (eps.shape, sigma.shape, lam.shape)
+        ctx.save_for_backward(xyz)
+        ctx.set_materialize_grads(False)
+        if cache is None:
+            cache = _sw_first_order(spec, xyz, energy=False)[1:]
+        return cache
+
+    @staticmethod
+    def backward(ctx, wg, wth):
+        (xyz,) = ctx.saved_tensors
+        s = ctx.spec
+        if wth is not None:
+            raise NotImplementedError("mdgrad_amd: derivatives of dU/d(epsilon, sigma, lam) of the Stillinger-Weber term (a "
+                                      "cotangent on it) are not provided by the HIP kernels")
+        if wg is None:
+            return None, None, None, None, None, None
+        o = sw_eval(s.ell, xyz, s.consts, s.theta, w=wg.detach().contiguous(), energy=False, grad=False, want_theta=True)
+        gw = sw_theta_sum(o["pthw"])
+        return (o["hw"],) + tuple(gw[k].reshape(sh) for k, sh in enumerate(ctx.shapes)) + (None, None)
+
+
+class SWEnergyFn(torch.autograd.Function):
+    """U(x, epsilon, sigma, lam) of the Stillinger-Weber term (csrc/sw.hip), differentiable twice in x and once in the three
+    parameters."""
+
+    @staticmethod
+    def forward(ctx, xyz, eps, sigma, lam, spec):
+        e, g, gth = _sw_first_order(spec, xyz, energy=True)
+        ctx.spec, ctx.cache = spec, (g, gth)
+        ctx.shapes = (eps.shape, sigma.shape, lam.shape)
+        ctx.save_for_backward(xyz, eps, sigma, lam)
+        return e.reshape(())
+
+    @staticmethod
+    def backward(ctx, gU):
+        xyz, eps, sigma, lam = ctx.saved_tensors
+        g, gth = SWGradFn.apply(xyz, eps, sigma, lam, ctx.spec, ctx.cache)
+        return (gU * g,) + tuple((gU * gth[k]).reshape(sh) for k, sh in enumerate(ctx.shapes)) + (None,)
 
 
 # ----------------------------------------------------------------------------- Ewald reciprocal-space sum (K21)

@@ -1147,6 +1147,40 @@ int mdg_sw_eval(const float* pos, int n_atoms, const MdgCell* cell /*host*/, con
                 int accumulate, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * K24  Sutton-Chen (Finnis-Sinclair) embedded-atom potential for one species over the per-atom (ELL) list (Sutton and Chen
+ *      1990; mdgrad_amd/interface.py SuttonChen, csrc/eam.hip).  With S_k(r) = (a/r)^k - (a/rc)^k + k (r - rc) (a/rc)^k / rc
+ *      (shift = 1) or S_k(r) = (a/r)^k (shift = 0) for r < rc, exactly 0 otherwise:
+ *        rho_i = sum_{j in row(i)} S_m(r_ij),   u_i = 1/2 epsilon sum_{j in row(i)} S_n(r_ij) - epsilon c sqrt(rho_i),   U = sum_i u_i
+ *      An atom with rho_i = 0 (no neighbour inside rc) has embedding energy, F'(rho_i) and F''(rho_i) exactly 0.
+ *      The list may have been searched with any radius >= rc: every entry with r = sqrt(d2) >= rc is skipped.  Rows are not
+ *      staged, so their length is not capped.
+ *      MdgEAMConsts holds the constants (rc, n, m, shift) and host copies of (epsilon, a, c); `theta`, when not null, is a
+ *      device float[3] = (epsilon, a, c) that the kernels read instead (trainable parameters under HIP-graph replay).  Without
+ *      theta the host values must satisfy epsilon > 0, a > 0, c >= 0.  Always: rc > 0, 1 <= m < n <= 16.
+ *   mdg_eam_eval  argument for argument mdg_sw_eval (same list, same `accumulate` bits, same out_scale, same outputs) plus
+ *     atom_work [n_atoms, 4], a caller-owned device scratch that must not be null: one call enqueues the density pass, which
+ *     writes (rho_i, d rho_i, F'(rho_i), F''(rho_i) d rho_i) there (d rho_i = sum_j S_m'(r_ij) e_ij.(w_j - w_i), 0 without w),
+ *     then the force pass, which reads the neighbours' entries, then the finish kernel of the energy.  Outputs, each nullable:
+ *       energy [1] = U (needs `partial`, mdg_eam_partial_size() floats; fixed-order block partials + a finish kernel)
+ *       grad [n_atoms, 3] = (accumulate & 1 ? grad : 0) + out_scale dU/dx,  hw likewise with H w, where
+ *         dU/dx_i = -sum_j [epsilon S_n'(r_ij) + (F'_i + F'_j) S_m'(r_ij)] e_ij,  e_ij the unit vector i -> j
+ *       pth [n_atoms, 3]  = (u_i / epsilon,  (n/2 epsilon sum_j S_n + m rho_i F'(rho_i)) / a,  -epsilon sqrt(rho_i))
+ *                           = d u_i / d(epsilon, a, c)   (S_k is homogeneous of degree k in a; their sums over i are dU/dtheta)
+ *       pthw [n_atoms, 3] = (w . grad_x) of the same three (their sums are d(w.dU/dx)/d(epsilon, a, c))
+ *     H w and pthw come from both passes run over Dual numbers seeded with w (csrc/dual.hpp).  No atomics: bitwise
+ *     reproducible; the value parts of a launch with w equal those of a launch without, bit for bit.
+ */
+typedef struct MdgEAMConsts {
+    double epsilon, a, c, rc;
+    int32_t n, m, shift, pad_;
+} MdgEAMConsts;
+int64_t mdg_eam_partial_size(int n_atoms);
+int mdg_eam_eval(const float* pos, int n_atoms, const MdgCell* cell /*host*/, const int32_t* col, const int32_t* shift,
+                 const int32_t* cnt, int max_nbr, const MdgEAMConsts* consts /*host*/, const float* theta, const float* w,
+                 float* energy, float* grad, float* hw, float* pth, float* pthw, float* partial, float* atom_work,
+                 float out_scale, int accumulate, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * f4  bonded terms over a static topology table (csrc/bonded.hip).
  * Replaces torchmd/interface.py:447-455 (BondPotentials.forward: harmonic in the SQUARED bond length,
  * 1/2 k (|b|^2 - ro)^2) and :496-508 (AnglePotentials.forward: 1/2 k (theta - theta0)^2 over triples (i, j, k) centred on

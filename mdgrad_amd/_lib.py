@@ -71,6 +71,12 @@ class MdgSWConsts(C.Structure):
                [("p", C.c_int32), ("q", C.c_int32)]
 
 
+class MdgEAMConsts(C.Structure):
+    """Constants of the Sutton-Chen term and host copies of (epsilon, a, c) (include/mdgrad_hip.h K24)."""
+    _fields_ = [(n, C.c_double) for n in ("epsilon", "a", "c", "rc")] + \
+               [(n, C.c_int32) for n in ("n", "m", "shift", "pad_")]
+
+
 class MdgChainStage(C.Structure):
     """One Dense stage of mdg_row_chain (include/mdgrad_hip.h)."""
     _fields_ = [(n, C.c_void_p) for n in ("W", "bias", "in0", "in1", "res0", "res1", "aux0", "aux1", "out0", "out1", "sig",
@@ -282,6 +288,9 @@ _SIGNATURES = {
     "mdg_sw_partial_size": (C.c_int64, [C.c_int]),
     "mdg_sw_eval": (C.c_int, [P, C.c_int, C.POINTER(MdgCell), P, P, P, C.c_int, C.POINTER(MdgSWConsts), P, P,
                               P, P, P, P, P, P, C.c_float, C.c_int, P]),
+    "mdg_eam_partial_size": (C.c_int64, [C.c_int]),
+    "mdg_eam_eval": (C.c_int, [P, C.c_int, C.POINTER(MdgCell), P, P, P, C.c_int, C.POINTER(MdgEAMConsts), P, P,
+                               P, P, P, P, P, P, P, C.c_float, C.c_int, P]),
     "mdg_ewald_workspace": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "mdg_ewald_eval": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), P, P, P, C.c_int, P, P, P, P, P, P, P, C.c_float,
                                  C.c_int, P]),

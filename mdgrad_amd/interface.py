@@ -1,6 +1,6 @@
 """Energy calculators with the reference's interface (torchmd/interface.py):
 GeneralInteraction :33-57, PairPotentials :217-300, Electrostatics :303-361 (as CoulombPotentials), Stack :364-403;
-StillingerWeber (three-body, no counterpart in the reference)
+StillingerWeber (three-body, no counterpart in the reference), SuttonChen (embedded-atom, no counterpart in the reference)
 (GNNPotentials lives in mdgrad_amd.nn).  forward(xyz) -> energy; _reset_topology(xyz) rebuilds the neighbour list.
 """
 import inspect
@@ -1171,6 +1171,225 @@ class StillingerWeber(GeneralInteraction):
             return o["grad"], o["hw"], None
         gw = ops.sw_theta_sum(o["pthw"], alpha=-1.0)
         return o["grad"], o["hw"], [gw[k:k + 1].reshape(p.shape) for k, p in enumerate((self.epsilon, self.sigma, self.lam))
+                                    if isinstance(p, torch.nn.Parameter)]
+
+
+class SuttonChen(GeneralInteraction):
+    """Sutton-Chen embedded-atom potential for one species (Sutton and Chen 1990; the Finnis-Sinclair form of the
+    embedded-atom method): the cohesion of an fcc metal as a function of the local density, not a sum over pairs.  With
+    the parameters epsilon (energy), a (length), c (dimensionless) and the integer exponents n > m >= 1:
+
+        U      = sum_i [ 1/2 sum_{j != i} phi(r_ij)  -  epsilon c sqrt(rho_i) ]
+        rho_i  = sum_{j != i} f(r_ij)
+        phi(r) = epsilon S_n(r),   f(r) = S_m(r)
+        S_k(r) = (a/r)^k - (a/rc)^k + k (r - rc) (a/rc)^k / rc     for r < rc, else exactly 0     (shift="force")
+        S_k(r) = (a/r)^k                                            for r < rc, else exactly 0     (shift="none")
+
+    shift="force" (the default) makes S_k and S_k' vanish at rc = `cutoff`, the convention of CoulombPotentials; by convexity
+    S_k >= 0, so rho_i >= 0.  shift="none" is the potential as published.  An atom with no neighbour inside rc has
+    rho_i = 0; its embedding energy, F'(rho_i) and F''(rho_i) are defined as exactly 0 (F = -epsilon c sqrt(rho)).
+    A property of the model, whatever the shift: with the square-root embedding F'(rho) diverges as rho -> 0, so the
+    force between the two atoms of an isolated pair has a step at rc (2 F' f' tends to a constant there).  It is irrelevant
+    in condensed phases, where every atom keeps neighbours well inside rc.
+
+    The pair set, the minimum image and the (d2 < rc^2) & (d2 != 0) test are those of PairPotentials at the cutoff rc;
+    the replicas of System.replicate never see each other.  `cutoff` is an absolute length and does not move with a.
+
+    `epsilon`, `a` and `c` are one-element float32 parameters when trainable, otherwise buffers; n, m, cutoff and shift
+    are constants.  Not covered: `index_tuple`, `ex_pairs` (both rejected), several species, tabulated embedding functions.
+    `copper`, `nickel`, `silver` and `gold` carry the published constants (epsilon in eV, a in Angstrom), cutoff 2 a by default.
+
+    forward(xyz) is differentiable twice in xyz and once in (epsilon, a, c) on the HIP kernels (ops.EAMEnergyFn,
+    csrc/eam.hip: a density pass, then a force pass that reads the neighbours' embedding derivatives); force / force_vjp
+    serve the analytic adjoint and HIP-graph replay, also while the parameters require grad.  float64 or host positions take
+    the torch restatement `_torch_energy`."""
+
+    accepts_into = True
+    accepts_accum = True
+    analytic = True
+    PUBLISHED = {"copper": (1.2382e-2, 3.61, 39.432, 9, 6), "nickel": (1.5707e-2, 3.52, 39.432, 9, 6),
+                 "silver": (2.5415e-3, 4.09, 144.41, 12, 6), "gold": (1.2793e-2, 4.08, 34.408, 10, 8)}
+
+    def __init__(self, system, epsilon, a, c, n, m, cutoff, shift="force", trainable=True, index_tuple=None, ex_pairs=None):
+        super().__init__(system)
+        if index_tuple is not None or ex_pairs is not None:
+            raise ValueError("SuttonChen: index_tuple and ex_pairs are not supported (one species, every pair)")
+        self._consts = ops.eam_consts(epsilon, a, c, n, m, cutoff, shift)
+        k = self._consts
+        self.n, self.m, self.cutoff, self.shift = int(k.n), int(k.m), float(k.rc), shift
+        h = np.asarray(system.get_cell(), dtype=np.float64)
+        h = np.diag(h) if h.ndim == 1 else h
+        vol = abs(float(np.linalg.det(h)))
+        self._half_height = 0.5 * min(vol / float(np.linalg.norm(np.cross(h[(d + 1) % 3], h[(d + 2) % 3]))) for d in range(3))
+        if self.cutoff > self._half_height:
+            raise ValueError("SuttonChen: cutoff = %g exceeds half the shortest cell height (%g)"
+                             % (self.cutoff, self._half_height))
+        for name, v in (("epsilon", k.epsilon), ("a", k.a), ("c", k.c)):
+            t = torch.tensor([v], dtype=torch.float32, device=self.device)
+            if trainable:
+                setattr(self, name, torch.nn.Parameter(t))
+            else:
+                self.register_buffer(name, t)
+        self.index_tuple, self.ex_pairs, self._mask = None, None, None
+        self._n_rep = system.get_number_of_atoms() // self._group
+        self._ell = None
+        self._work = None
+        if torch.device(self.device).type == "cuda":
+            # the scratch of the density pass: persistent, so that a captured graph sees a fixed address
+            self._work = torch.empty(system.get_number_of_atoms(), 4, dtype=torch.float32, device=self.device)
+            self._reset_topology(torch.Tensor(system.get_positions()).to(system.device))
+            self._theta()
+
+    @classmethod
+    def _published(cls, name, system, cutoff, kw):
+        eps, a, c, n, m = cls.PUBLISHED[name]
+        return cls(system, eps, a, c, n, m, 2.0 * a if cutoff is None else cutoff, **kw)
+
+    @classmethod
+    def copper(cls, system, cutoff=None, **kw):
+        """Sutton and Chen's copper: epsilon = 1.2382e-2 eV, a = 3.61 Angstrom, c = 39.432, n = 9, m = 6."""
+        return cls._published("copper", system, cutoff, kw)
+
+    @classmethod
+    def nickel(cls, system, cutoff=None, **kw):
+        """Sutton and Chen's nickel: epsilon = 1.5707e-2 eV, a = 3.52 Angstrom, c = 39.432, n = 9, m = 6."""
+        return cls._published("nickel", system, cutoff, kw)
+
+    @classmethod
+    def silver(cls, system, cutoff=None, **kw):
+        """Sutton and Chen's silver: epsilon = 2.5415e-3 eV, a = 4.09 Angstrom, c = 144.41, n = 12, m = 6."""
+        return cls._published("silver", system, cutoff, kw)
+
+    @classmethod
+    def gold(cls, system, cutoff=None, **kw):
+        """Sutton and Chen's gold: epsilon = 1.2793e-2 eV, a = 4.08 Angstrom, c = 34.408, n = 10, m = 8."""
+        return cls._published("gold", system, cutoff, kw)
+
+    def _hip_ok(self, xyz=None):
+        if xyz is not None and (not xyz.is_cuda or xyz.dtype != torch.float32):
+            return False
+        return self.analytic and self._ell is not None
+
+    # -- topology: the lists of PairPotentials ---------------------------------------------------------------------
+    def _reset_topology(self, xyz, _cache=None):
+        self._topo_stamp = object()
+        st = self._static if self._static_on else None
+        vkey = ("verlet", float(self.cutoff), None, self._group)
+        if st is not None and _cache is not None and vkey in _cache:
+            self._ell = _cache[vkey].ell             # a Stack member's Verlet list (the support test is applied per pair)
+        elif st is not None:
+            self._ell = self._shared_static_ell(xyz, _cache, st)
+        else:
+            self._ell = self._shared_ell(xyz, _cache)
+
+    def supports_static_topology(self):
+        return self._hip_ok()
+
+    def set_static_topology(self, on=True):
+        self._static_on = bool(on)
+        if on and self._static is None:
+            longest = int(self._ell.cnt.max().item())
+            self._static = dict(max_nbr=min(self._group - 1, (int(longest * 1.25) + 15) // 8 * 8),
+                                need=torch.zeros(2, dtype=torch.int32, device=self.device), version=0)
+
+    # -- the device copy of (epsilon, a, c) the kernels read -------------------------------------------------------
+    def _theta(self):
+        """(epsilon, a, c) in a persistent device buffer that is refreshed when one of them changed (version counters);
+        inside a HIP-graph capture it is returned as it is -- the replaying pass refreshes it once before its first replay
+        (`prepare_pass`), so the captured steps carry no torch op for it and no host value of a parameter."""
+        ps = (self.epsilon, self.a, self.c)
+        buf = getattr(self, "_theta_buf", None)
+        capturing = ps[0].is_cuda and torch.cuda.is_current_stream_capturing()
+        if buf is None or buf.device != ps[0].device:
+            if capturing:
+                return torch.cat([p.detach().reshape(-1) for p in ps])
+            buf = self._theta_buf = torch.empty(3, device=ps[0].device, dtype=torch.float32)
+            self._theta_key = None
+        if capturing:
+            return buf
+        key = tuple((p.data_ptr(), p._version) for p in ps)
+        if self._theta_key != key:
+            torch.cat([p.detach().reshape(-1).to(torch.float32) for p in ps], out=buf)
+            self._theta_key = key
+        return buf
+
+    def prepare_pass(self):
+        if self._hip_ok():
+            self._theta()
+
+    def _scratch(self, xyz):
+        if self._work is None or self._work.device != xyz.device or self._work.shape[0] != xyz.shape[0]:
+            self._work = torch.empty(xyz.shape[0], 4, dtype=torch.float32, device=xyz.device)
+        return self._work
+
+    # -- energy ----------------------------------------------------------------------------------------------------
+    _pairs = StillingerWeber._pairs
+
+    def _shape(self, r, a, k):
+        s = (a / r) ** k
+        if self.shift == "none":
+            return s
+        q = (a / self.cutoff) ** k
+        return s - q + k * (r - self.cutoff) * q / self.cutoff
+
+    def _torch_energy(self, xyz):
+        """The same energy in torch ops, in the dtype and on the device of xyz (differentiable by autograd in xyz and in
+        epsilon, a, c)."""
+        eps, a, c = (p.to(xyz).reshape(()) for p in (self.epsilon, self.a, self.c))
+        i, j, off = self._pairs(xyz, self.cutoff)
+        cell = self.cell.detach().to(xyz)
+        cell = torch.diag(cell) if cell.dim() == 1 else cell
+        d = xyz[i] - xyz[j] - off.matmul(cell)
+        r = d.pow(2).sum(-1).sqrt()
+        f = self._shape(r, a, self.m)
+        rho = xyz.new_zeros(xyz.shape[0]).index_add(0, torch.cat([i, j]), torch.cat([f, f]))
+        dense = rho > 0                                      # rho = 0: no embedding energy, and no 0/0 in its derivatives
+        root = torch.where(dense, rho, torch.ones_like(rho)).sqrt() * dense.to(xyz)
+        return eps * (self._shape(r, a, self.n).sum() - c * root.sum())
+
+    def forward(self, xyz):
+        if self._hip_ok(xyz):
+            return ops.EAMEnergyFn.apply(xyz.contiguous(), self.epsilon, self.a, self.c,
+                                         ops.EAMSpec(self._ell, self._consts, self._theta(), self._scratch(xyz)))
+        return self._torch_energy(xyz)
+
+    # -- analytic-adjoint protocol (md._EOM.rhs_vjp, Stack.force / force_vjp) -------------------------------------
+    def supports_force_vjp(self):
+        return self._hip_ok()
+
+    def force(self, xyz, into=None):
+        """F = -dU/dx in one call (two kernels); `into` (a force buffer of another Stack member): added onto it in the
+        force pass and returned."""
+        o = ops.eam_eval(self._ell, xyz.detach(), self._consts, self._theta(), energy=False, grad=True,
+                         into=None if into is None else (into, None), scale=-1.0, work=self._scratch(xyz))
+        return o["grad"]
+
+    def force_vjp(self, xyz, w, want_theta=True, accum=None, into=None):
+        """(F, d(w.F)/dx, [d(w.F)/d epsilon, d(w.F)/d a, d(w.F)/d c]) in one call plus the fixed-order reduction of the
+        parameter part; `accum` (ops.ThetaAccum): that part is added into its flat buffer instead (None returned).
+        `into` = (F, dq) buffers of another Stack member: this term's force and d(w.F)/dx are added onto them in the
+        force pass."""
+        params = [p for p in (self.epsilon, self.a, self.c) if isinstance(p, torch.nn.Parameter)]
+        need = bool(want_theta) and bool(params)
+        o = ops.eam_eval(self._ell, xyz.detach(), self._consts, self._theta(), w=w.detach(), energy=False, grad=True,
+                         into=into, scale=-1.0, want_theta=need, work=self._scratch(xyz))
+        if not want_theta:
+            return o["grad"], o["hw"], None
+        if not need:
+            return o["grad"], o["hw"], ([] if accum is None else None)
+        if accum is not None:
+            jobs = ops.GradJobs()
+            offs = [accum.off.get(id(p)) for p in params]
+            if len(params) == 3 and None not in offs and offs[1] == offs[0] + 1 and offs[2] == offs[0] + 2:
+                jobs.colsum(offs[0], o["pthw"])                  # the three parameters are adjacent in the flat buffer
+            else:
+                for col, p in enumerate((self.epsilon, self.a, self.c)):
+                    if isinstance(p, torch.nn.Parameter) and accum.off.get(id(p)) is not None:
+                        jobs.colsum(accum.off[id(p)], o["pthw"][:, col:col + 1])
+            jobs.run(accum, alpha=-1.0, accumulate=True)
+            return o["grad"], o["hw"], None
+        gw = ops.eam_theta_sum(o["pthw"], alpha=-1.0)
+        return o["grad"], o["hw"], [gw[k:k + 1].reshape(p.shape) for k, p in enumerate((self.epsilon, self.a, self.c))
                                     if isinstance(p, torch.nn.Parameter)]
 
 

@@ -15,6 +15,7 @@ torch.autograd.Function wrappers that own the differentiation contract
     EwaldEnergyFn -> EwaldGradFn                                Ewald reciprocal-space sum, order <= 2 in x, 1 in the charges
     EwaldExclEnergyFn -> EwaldExclGradFn                        Ewald erf correction of excluded / scaled pairs, same orders
     SWEnergyFn -> SWGradFn                                      Stillinger-Weber term, order <= 2 in x, 1 in (epsilon, sigma, lam)
+    EAMEnergyFn -> EAMGradFn                                    Sutton-Chen term, order <= 2 in x, 1 in (epsilon, a, c)
 
 Everything here requires HIP tensors; there is no CPU path.
 """
@@ -810,6 +811,137 @@ class SWEnergyFn(torch.autograd.Function):
     def backward(ctx, gU):
         xyz, eps, sigma, lam = ctx.saved_tensors
         g, gth = SWGradFn.apply(xyz, eps, sigma, lam, ctx.spec, ctx.cache)
+        return (gU * g,) + tuple((gU * gth[k]).reshape(sh) for k, sh in enumerate(ctx.shapes)) + (None,)
+
+
+# ----------------------------------------------------------------------------- Sutton-Chen embedded-atom term (K24)
+EAM_SHIFTS = {"none": 0, "force": 1}
+
+
+def eam_consts(epsilon, a, c, n, m, cutoff, shift="force"):
+    """MdgEAMConsts: the constants (rc, n, m, shift) of the Sutton-Chen form and host copies of (epsilon, a, c) -- the kernels
+    read those three from a device buffer instead when eam_eval is given one."""
+    epsilon, a, c, cutoff = float(epsilon), float(a), float(c), float(cutoff)
+    if not epsilon > 0.0:
+        raise ValueError("mdgrad_amd: epsilon must be positive (got %r)" % epsilon)
+    if not a > 0.0:
+        raise ValueError("mdgrad_amd: the length a must be positive (got %r)" % a)
+    if not c >= 0.0:
+        raise ValueError("mdgrad_amd: c must be >= 0 (got %r)" % c)
+    if int(n) != n or int(m) != m or not 1 <= int(m) < int(n) <= 16:
+        raise ValueError("mdgrad_amd: the exponents must be integers with 1 <= m < n <= 16 (got n = %r, m = %r)" % (n, m))
+    if not cutoff > 0.0:
+        raise ValueError("mdgrad_amd: cutoff must be positive (got %r)" % cutoff)
+    if shift not in EAM_SHIFTS:
+        raise ValueError("mdgrad_amd: shift must be 'force' or 'none' (got %r)" % (shift,))
+    k = _lib.MdgEAMConsts()
+    k.epsilon, k.a, k.c, k.rc = epsilon, a, c, cutoff
+    k.n, k.m, k.shift, k.pad_ = int(n), int(m), EAM_SHIFTS[shift], 0
+    return k
+
+
+def eam_eval(ell, xyz, consts, theta=None, w=None, energy=True, grad=True, into=None, scale=1.0, want_theta=False, work=None):
+    """One call of mdg_eam_eval (density pass, force pass) -> dict(energy, grad, hw, pth, pthw), argument for argument sw_eval
+    with theta = device float [3] = (epsilon, a, c).  `work`: the [N, 4] float scratch of the density pass (a persistent buffer
+    of the caller, so that a captured graph sees a fixed address); allocated here when None.  The list may have been searched
+    with any radius >= rc (a skin): the kernels apply r < rc per pair."""
+    lib = _lib.load()
+    require_gpu(xyz, "xyz")
+    N = ell.n_atoms
+    if xyz.shape != (N, 3):
+        raise ValueError("mdgrad_amd: xyz must be [%d, 3] (got %s)" % (N, tuple(xyz.shape)))
+    if theta is not None:
+        require_gpu(theta, "theta")
+        if theta.shape != (3,) or not theta.is_contiguous():
+            raise ValueError("mdgrad_amd: theta must be a contiguous [3] tensor (got %s)" % (tuple(theta.shape),))
+    xyz = xyz.contiguous()
+    dev = xyz.device
+    if work is None:
+        work = torch.empty(N, 4, device=dev)
+    else:
+        require_gpu(work, "work")
+        if work.shape != (N, 4) or not work.is_contiguous():
+            raise ValueError("mdgrad_amd: work must be a contiguous [%d, 4] tensor (got %s)" % (N, tuple(work.shape)))
+    acc = into is not None
+    e = torch.empty(1, device=dev) if energy else None
+    g = (into[0] if acc else torch.empty(N, 3, device=dev)) if grad else None
+    hw = pth = pthw = None
+    if w is not None:
+        require_gpu(w, "w")
+        w = w.contiguous()
+        hw = into[1] if acc else torch.empty(N, 3, device=dev)
+        pthw = torch.empty(N, 3, device=dev) if want_theta else None
+    elif want_theta:
+        pth = torch.empty(N, 3, device=dev)
+    partial = torch.empty(int(lib.mdg_eam_partial_size(N)), device=dev) if energy else None
+    recheck = bool(getattr(ell, "verlet", False))
+    check(lib.mdg_eam_eval(ptr(xyz), N, C.byref(ell.cell_struct), ptr(ell.col), ptr(ell.shift), ptr(ell.cnt), ell.max_nbr,
+                           C.byref(consts), ptr(theta), ptr(w), ptr(e), ptr(g), ptr(hw), ptr(pth), ptr(pthw), ptr(partial),
+                           ptr(work), float(scale), int(acc) | (2 if recheck else 0), stream_ptr(dev)), "mdg_eam_eval")
+    return dict(energy=e, grad=g, hw=hw, pth=pth, pthw=pthw)
+
+
+eam_theta_sum = sw_theta_sum          # the same fixed-order column sums of a per-atom [N, 3] table (mdg_grad_jobs)
+
+
+class EAMSpec:
+    """What the autograd functions below need beside the tensors: the list, the constants, the device buffer (epsilon, a, c)
+    and the scratch of the density pass, kept current by SuttonChen."""
+
+    def __init__(self, ell, consts, theta, work=None):
+        self.ell, self.consts, self.theta, self.work = ell, consts, theta, work
+
+
+def _eam_first_order(spec, xyz, energy):
+    o = eam_eval(spec.ell, xyz, spec.consts, spec.theta, energy=energy, grad=True, want_theta=True, work=spec.work)
+    return o["energy"], o["grad"], eam_theta_sum(o["pth"])
+
+
+class EAMGradFn(torch.autograd.Function):
+    """(dU/dx, dU/d(epsilon, a, c)) as a differentiable op; backward = the Hessian-vector product and the mixed derivative
+    d(w.dU/dx)/d(epsilon, a, c).  A cotangent on the parameter gradient is not provided."""
+
+    @staticmethod
+    def forward(ctx, xyz, eps, a, c, spec, cache):
+        ctx.spec = spec
+        ctx.shapes = (eps.shape, a.shape, c.shape)
+        ctx.save_for_backward(xyz)
+        ctx.set_materialize_grads(False)
+        if cache is None:
+            cache = _eam_first_order(spec, xyz, energy=False)[1:]
+        return cache
+
+    @staticmethod
+    def backward(ctx, wg, wth):
+        (xyz,) = ctx.saved_tensors
+        s = ctx.spec
+        if wth is not None:
+            raise NotImplementedError("mdgrad_amd: derivatives of dU/d(epsilon, a, c) of the Sutton-Chen term (a cotangent on "
+                                      "it) are not provided by the HIP kernels")
+        if wg is None:
+            return None, None, None, None, None, None
+        o = eam_eval(s.ell, xyz, s.consts, s.theta, w=wg.detach().contiguous(), energy=False, grad=False, want_theta=True,
+                     work=s.work)
+        gw = eam_theta_sum(o["pthw"])
+        return (o["hw"],) + tuple(gw[k].reshape(sh) for k, sh in enumerate(ctx.shapes)) + (None, None)
+
+
+class EAMEnergyFn(torch.autograd.Function):
+    """U(x, epsilon, a, c) of the Sutton-Chen term (csrc/eam.hip), differentiable twice in x and once in the three
+    parameters."""
+
+    @staticmethod
+    def forward(ctx, xyz, eps, a, c, spec):
+        e, g, gth = _eam_first_order(spec, xyz, energy=True)
+        ctx.spec, ctx.cache = spec, (g, gth)
+        ctx.shapes = (eps.shape, a.shape, c.shape)
+        ctx.save_for_backward(xyz, eps, a, c)
+        return e.reshape(())
+
+    @staticmethod
+    def backward(ctx, gU):
+        xyz, eps, a, c = ctx.saved_tensors
+        g, gth = EAMGradFn.apply(xyz, eps, a, c, ctx.spec, ctx.cache)
         return (gU * g,) + tuple((gU * gth[k]).reshape(sh) for k, sh in enumerate(ctx.shapes)) + (None,)
 
 

@@ -110,6 +110,158 @@ class GeneralInteraction(torch.nn.Module):
         return -1 if self._static is None else self._static["version"]
 
 
+def _cat_f32(ps, out=None):
+    """The tensors of `ps`, flattened and concatenated as float32 (into `out` when given)."""
+    return torch.cat([p.detach().reshape(-1).to(torch.float32) for p in ps], out=out)
+
+
+class _DeviceMirror:
+    """Host-visible parameters mirrored into a persistent flat float32 device buffer that the kernels read.  `sources()`
+    returns the tensors, `pack(tensors, out=None)` writes their flat float32 image into `out` (or returns a fresh one);
+    `numel`: the size of that image when it is not the summed size of the sources.  get() refreshes the buffer when a source
+    changed (address or version counter); inside a HIP-graph capture it returns the buffer as it is -- the replaying pass
+    refreshes it once before its first replay (`prepare_pass`), so the captured steps carry no torch op for it -- or, when
+    there is no buffer yet, a freshly packed tensor."""
+
+    def __init__(self, sources, pack=_cat_f32, numel=None):
+        self.sources, self.pack, self.numel = sources, pack, numel
+        self.buf, self.key = None, None
+
+    def get(self):
+        ps = self.sources()
+        n = sum(p.numel() for p in ps) if self.numel is None else self.numel
+        capturing = ps[0].is_cuda and torch.cuda.is_current_stream_capturing()
+        buf = self.buf
+        if buf is None or buf.numel() != n or buf.device != ps[0].device:
+            if capturing:
+                return self.pack(ps)
+            buf = self.buf = torch.empty(n, device=ps[0].device, dtype=torch.float32)
+            self.key = None
+        if capturing:
+            return buf
+        key = tuple((p.data_ptr(), p._version) for p in ps)
+        if self.key != key:
+            self.pack(ps, out=buf)
+            self.key = key
+        return buf
+
+
+class _ListTerm(GeneralInteraction):
+    """A term evaluated on the ELL neighbour list of its cutoff and selection (`self._ell`): the choice of the list at a
+    rebuild, the fixed-capacity configuration, and the all-pairs search of the torch restatements."""
+
+    _ell = None
+
+    def _hip_ok(self, xyz=None):
+        if xyz is not None and (not xyz.is_cuda or xyz.dtype != torch.float32):
+            return False
+        return self.analytic and self._ell is not None
+
+    def _takes_verlet_list(self):
+        """Whether every evaluation on `_ell` re-applies the exact cutoff per pair, so that a list searched with a skin serves."""
+        return True
+
+    def _reset_topology(self, xyz, _cache=None):
+        self._topo_stamp = object()
+        st = self._static if self._static_on else None
+        vkey = ("verlet", float(self.cutoff), None if self._mask is None else self._mask.data_ptr(), self._group)
+        if st is not None and _cache is not None and vkey in _cache and self._takes_verlet_list():
+            self._ell = _cache[vkey].ell             # a Stack member's Verlet list (exact cutoff re-applied per pair)
+        elif st is not None:
+            self._ell = self._shared_static_ell(xyz, _cache, st)
+        else:
+            self._ell = self._shared_ell(xyz, _cache)
+
+    def supports_static_topology(self):
+        return self._hip_ok()
+
+    def set_static_topology(self, on=True):
+        self._static_on = bool(on)
+        if on and self._static is None:
+            longest = int(self._ell.cnt.max().item())
+            self._static = dict(max_nbr=min(self._group - 1, (int(longest * 1.25) + 15) // 8 * 8),
+                                need=torch.zeros(2, dtype=torch.int32, device=self.device), version=0)
+
+    def _all_pairs(self, xyz, rc, mask=None):
+        """Half list (i, j, image offsets) at xyz of every pair of a replica closer than rc (and selected by `mask`), by
+        torch ops with the reference's minimum image and selection (torchmd/topology.py:30-73)."""
+        n, R = self._group, self._n_rep
+        cell = self.cell.detach().to(xyz)
+        cell = torch.diag(cell) if cell.dim() == 1 else cell
+        iu = torch.triu_indices(n, n, offset=1, device=xyz.device)
+        x = xyz.detach().reshape(R, n, 3)
+        D = x[:, iu[1]] - x[:, iu[0]]
+        s = D.matmul(cell.inverse())
+        o = -(s > 0.5).to(xyz) + (s < -0.5).to(xyz)
+        d2 = (D + o.matmul(cell)).pow(2).sum(-1)
+        keep = (d2 < rc ** 2) & (d2 != 0)
+        if mask is not None:
+            keep &= mask.to(xyz.device).bool()[iu[0], iu[1]][None, :]
+        rep, idx = torch.nonzero(keep, as_tuple=True)
+        return iu[0][idx] + rep * n, iu[1][idx] + rep * n, o[rep, idx]
+
+
+class _StaticTerm:
+    """Mixin of a term on a static table: nothing to search at a rebuild, and under fixed capacities (HIP-graph capture)
+    nothing can overflow."""
+
+    def _reset_topology(self, xyz):
+        pass
+
+    def supports_static_topology(self):
+        return self._hip_ok()
+
+    def set_static_topology(self, on=True):
+        pass
+
+    def static_overflow(self):
+        return False
+
+    def static_version(self):
+        return 0
+
+
+def _param_tail(gw, param, alpha, want_theta, accum):
+    """The parameter part of force_vjp (the third element of its tuple) for a term with one parameter tensor: `gw` =
+    d(w.dU/dx)/dparam up to the factor `alpha` (-1 or -conversion), None when the parameter is not trainable.  With
+    `accum` (ops.ThetaAccum) alpha * gw is added into its flat buffer and None returned."""
+    if not want_theta:
+        return None
+    if gw is None:
+        return [] if accum is None else None
+    if accum is not None:
+        jobs = ops.GradJobs()
+        jobs.axpy(accum.off[id(param)], gw)
+        jobs.run(accum, alpha=alpha, accumulate=True)
+        return None
+    gw = gw.reshape(param.shape)
+    return [-gw if alpha == -1.0 else alpha * gw]
+
+
+def _theta3_tail(pthw, thetas, want_theta, accum):
+    """The parameter part of force_vjp for a term with three one-element parameters: `pthw` [N, 3] = the per-atom terms of
+    d(w.dU/dx)/dthetas (None when none of them is trainable); the result is minus its column sums, in the fixed order of
+    mdg_grad_jobs.  With `accum` (ops.ThetaAccum) they are added into its flat buffer and None returned."""
+    if not want_theta:
+        return None
+    if pthw is None:
+        return [] if accum is None else None
+    trainable = [isinstance(p, torch.nn.Parameter) for p in thetas]
+    if accum is not None:
+        jobs = ops.GradJobs()
+        offs = [accum.off.get(id(p)) for p, t in zip(thetas, trainable) if t]
+        if len(offs) == 3 and None not in offs and offs[1] == offs[0] + 1 and offs[2] == offs[0] + 2:
+            jobs.colsum(offs[0], pthw)                           # the three parameters are adjacent in the flat buffer
+        else:
+            for col, (p, t) in enumerate(zip(thetas, trainable)):
+                if t and accum.off.get(id(p)) is not None:
+                    jobs.colsum(accum.off[id(p)], pthw[:, col:col + 1])
+        jobs.run(accum, alpha=-1.0, accumulate=True)
+        return None
+    gw = ops.sw_theta_sum(pthw, alpha=-1.0)
+    return [gw[k:k + 1].reshape(p.shape) for k, (p, t) in enumerate(zip(thetas, trainable)) if t]
+
+
 class _LazyTopology:
     """(nbr_list, pair_dis, offsets) of PairPotentials._reset_topology, materialised on demand
     (the integrators ignore the return value; materialising costs a host sync)."""
@@ -229,7 +381,7 @@ class GNNPotentials(GeneralInteraction):
         return F, dq, gth
 
 
-class PairPotentials(GeneralInteraction):
+class PairPotentials(_ListTerm):
     """torchmd/interface.py:217-300.  `pair_model` is a module instance (the code's signature)
     or, as in the README snippet, a class plus its keyword arguments."""
 
@@ -247,11 +399,15 @@ class PairPotentials(GeneralInteraction):
         self.ex_pairs = ex_pairs
         self._mask = ops.build_mask(self._group, index_tuple, ex_pairs, system.device)
         self._nbr_override = None
+        self._theta_mirror = _DeviceMirror(self._mdg_params)
         self._reset_topology(torch.Tensor(system.get_positions()).to(system.device))
 
     # -- kernel-facing description ------------------------------------------------------
     def builtin(self):
         return is_builtin_form(self.model)
+
+    def _mdg_params(self):
+        return self.model.mdg_params()
 
     def mdg_term(self, theta_off=0):
         params = self.model.mdg_params()
@@ -269,16 +425,11 @@ class PairPotentials(GeneralInteraction):
     def offsets(self):
         return self._ell.half_list()[1]
 
+    def _takes_verlet_list(self):
+        return self.builtin()                        # (the module path reads every listed pair)
+
     def _reset_topology(self, xyz, _cache=None):
-        self._topo_stamp = object()
-        st = self._static if self._static_on else None
-        vkey = ("verlet", float(self.cutoff), None if self._mask is None else self._mask.data_ptr(), self._group)
-        if st is not None and _cache is not None and vkey in _cache and self.builtin():
-            self._ell = _cache[vkey].ell             # a Stack member's Verlet list (exact cutoff re-applied per pair)
-        elif st is not None:
-            self._ell = self._shared_static_ell(xyz, _cache, st)
-        else:
-            self._ell = self._shared_ell(xyz, _cache)
+        super()._reset_topology(xyz, _cache)
         return _LazyTopology(self, xyz.detach())
 
     def supports_static_topology(self):
@@ -287,14 +438,11 @@ class PairPotentials(GeneralInteraction):
         return self.builtin()
 
     def set_static_topology(self, on=True):
-        self._static_on = bool(on)
-        if on and self._static is None:
-            longest = int(self._ell.cnt.max().item())
-            self._static = dict(max_nbr=min(self._group - 1, (int(longest * 1.25) + 15) // 8 * 8),
-                                need=torch.zeros(2, dtype=torch.int32, device=self.device), version=0)
-            if not self.builtin():                    # module path works on the half list: edge capacity too
-                pairs = int(self._ell.half_list()[0].shape[0])
-                self._static["capacity"] = (int(pairs * 1.25) + 1023) // 1024 * 1024
+        fresh = on and self._static is None
+        super().set_static_topology(on)
+        if fresh and not self.builtin():              # module path works on the half list: edge capacity too
+            pairs = int(self._ell.half_list()[0].shape[0])
+            self._static["capacity"] = (int(pairs * 1.25) + 1023) // 1024 * 1024
 
     # -- analytic-adjoint protocol: used by the integrators' rhs_vjp --------------------------------
     analytic = True            # False: user-defined pair modules go through the autograd double-backward path
@@ -343,26 +491,12 @@ class PairPotentials(GeneralInteraction):
         return F, -ops._edge_scatter(hv, topo), gth
 
     def _theta(self, like):
-        """(flat parameter vector of the pair form, its parameters).  The vector lives in a persistent buffer that is
-        refreshed when a parameter changed (version counters); inside a HIP-graph capture it is returned as it is -- the
-        replaying pass refreshes it once before its first replay (`prepare_pass`), so the captured steps carry no `cat`."""
+        """(flat parameter vector of the pair form, its parameters): the vector is the device mirror of the parameters
+        (_DeviceMirror; re-allocated when their total size changes)."""
         params = self.model.mdg_params()
         if not params:
             return like.new_zeros(0), params
-        n = sum(p.numel() for p in params)
-        buf = getattr(self, "_theta_buf", None)
-        if buf is None or buf.numel() != n or buf.device != params[0].device:
-            if params[0].is_cuda and torch.cuda.is_current_stream_capturing():
-                return torch.cat([p.detach().reshape(-1) for p in params]), params
-            buf = self._theta_buf = torch.empty(n, device=params[0].device, dtype=torch.float32)
-            self._theta_key = None
-        if params[0].is_cuda and torch.cuda.is_current_stream_capturing():
-            return buf, params
-        key = tuple((p.data_ptr(), p._version) for p in params)
-        if self._theta_key != key:
-            torch.cat([p.detach().reshape(-1).to(torch.float32) for p in params], out=buf)
-            self._theta_key = key
-        return buf, params
+        return self._theta_mirror.get(), params
 
     def prepare_pass(self):
         if self.builtin():
@@ -452,13 +586,14 @@ class TPairPotentials(PairPotentials):
         return self._phi(compute_dis(xyz, nbr, off, self.cell)).sum()            # interface.py:207-215
 
 
-class _BondedTerm(torch.nn.Module):
+class _BondedTerm(_StaticTerm, torch.nn.Module):
     """Common part of BondPotentials / AnglePotentials: the static topology table on the device and the analytic-adjoint
     protocol (force / force_vjp) on mdg_bonded_eval (csrc/bonded.hip) -- one launch for energy, force and the
     Hessian-vector product, so a polymer Stack(pair + bond [+ angle] [+ GNN]) (demo/fold.py:131-161) keeps the analytic
     adjoint and HIP-graph replay instead of the reference's double backward.  No trainable parameters (k, ro / thetao are
     plain numbers in the reference); given as tensors that require grad they switch the term to the reference's torch
-    ops so that autograd reaches them."""
+    ops so that autograd reaches them.  (`_reset_topology` is _StaticTerm's no-op; AnglePotentials has none in the reference
+    and therefore cannot be a member of a Stack there.)"""
 
     _kind = None
     accepts_into = True
@@ -493,9 +628,6 @@ class _BondedTerm(torch.nn.Module):
                                               self.device)
         return t
 
-    def _reset_topology(self, xyz):          # (static table; absent for AnglePotentials in the reference, which therefore
-        pass                                 #  cannot be a member of a Stack there)
-
     def _torch_energy(self, xyz):
         raise NotImplementedError
 
@@ -517,18 +649,8 @@ class _BondedTerm(torch.nn.Module):
         o = ops.bonded_eval(self.table(), xyz.detach(), w=w.detach(), into=into, scale=-1.0)
         return o["grad"], o["hw"], ([] if (want_theta and accum is None) else None)
 
-    # -- fixed-capacity topology (HIP-graph capture): the table is static, nothing can overflow ------------------
-    def supports_static_topology(self):
-        return self._hip_ok()
-
-    def set_static_topology(self, on=True):
+    def set_static_topology(self, on=True):          # (the rest of the protocol: _StaticTerm)
         self.table()
-
-    def static_overflow(self):
-        return False
-
-    def static_version(self):
-        return 0
 
 
 class BondPotentials(_BondedTerm):
@@ -573,7 +695,7 @@ class AnglePotentials(_BondedTerm):
         return 0.5 * self.k * (torch.acos(cos) - self.thetao).pow(2).sum(-1)
 
 
-class DihedralPotentials(torch.nn.Module):
+class DihedralPotentials(_StaticTerm, torch.nn.Module):
     """Torsion term over quadruples (i, j, k, l): U = sum_terms sum_{m = 0..4} coeffs[type, m] cos^m phi, the reference's
     "multiharmonic" dihedral form (nff/nn/modules.py:253-257); no counterpart in torchmd/interface.py.
 
@@ -587,7 +709,7 @@ class DihedralPotentials(torch.nn.Module):
     [n_terms] in [0, n_types) picks the row of every term (default: row 0).  from_opls builds it from OPLS constants.
 
     A Stack member like BondPotentials: forward(xyz) is differentiable twice in xyz and once in coeffs on the HIP kernels
-    (ops.DihedralEnergyFn, csrc/dihedral.hip), and force / force_vjp serve the analytic adjoint and HIP-graph replay -- also
+    (ops.DihedralTerm, csrc/dihedral.hip), and force / force_vjp serve the analytic adjoint and HIP-graph replay -- also
     while coeffs requires grad: d(w.F)/dcoeffs comes out of the same launch.  float64 or host positions take the torch
     restatement `_torch_energy`."""
 
@@ -637,9 +759,6 @@ class DihedralPotentials(torch.nn.Module):
             return False
         return self.analytic
 
-    def _reset_topology(self, xyz):          # (static table)
-        pass
-
     def _torch_energy(self, xyz):
         """The same energy in torch ops, in the dtype and on the device of xyz (differentiable by autograd in xyz and coeffs)."""
         top = self.top.to(xyz.device)
@@ -660,7 +779,7 @@ class DihedralPotentials(torch.nn.Module):
 
     def forward(self, xyz):
         if self._hip_ok(xyz):
-            return ops.DihedralEnergyFn.apply(xyz.contiguous(), self.coeffs, self._table)
+            return ops.TermEnergyFn.apply(xyz.contiguous(), ops.DihedralTerm(self._table, self.coeffs), self.coeffs)
         return self._torch_energy(xyz)
 
     # -- analytic-adjoint protocol (md._EOM.rhs_vjp, Stack.force / force_vjp) -------------------------------------
@@ -676,33 +795,11 @@ class DihedralPotentials(torch.nn.Module):
         (ops.ThetaAccum): that part is added into its flat buffer instead (None returned)."""
         need = bool(want_theta) and isinstance(self.coeffs, torch.nn.Parameter)
         o = ops.dihedral_eval(self._table, xyz.detach(), self.coeffs, w=w.detach(), into=into, scale=-1.0, terms=need)
-        if not want_theta:
-            return o["grad"], o["hw"], None
-        if not need:
-            return o["grad"], o["hw"], ([] if accum is None else None)
-        gw = ops.dihedral_coeff_grad(self._table, o["c_term"], o["cd_term"], want_u=False)[1]       # d(w.dU/dx)/dcoeffs
-        if accum is not None:
-            jobs = ops.GradJobs()
-            jobs.axpy(accum.off[id(self.coeffs)], gw)
-            jobs.run(accum, alpha=-1.0, accumulate=True)
-            return o["grad"], o["hw"], None
-        return o["grad"], o["hw"], [-gw.reshape(self.coeffs.shape)]
-
-    # -- fixed-capacity topology (HIP-graph capture): the table is static, nothing can overflow ------------------
-    def supports_static_topology(self):
-        return self._hip_ok()
-
-    def set_static_topology(self, on=True):
-        pass
-
-    def static_overflow(self):
-        return False
-
-    def static_version(self):
-        return 0
+        gw = ops.dihedral_coeff_grad(self._table, o["c_term"], o["cd_term"], want_u=False)[1] if need else None
+        return o["grad"], o["hw"], _param_tail(gw, self.coeffs, -1.0, want_theta, accum)
 
 
-class CoulombPotentials(GeneralInteraction):
+class CoulombPotentials(_ListTerm):
     """Point-charge electrostatics as a damped shifted-force real-space sum (Wolf et al. 1999; Fennell and Gezelter 2006):
     pairwise, O(N), no reciprocal part, energy and force continuous at the cutoff.  The working counterpart of the
     reference's Electrostatics (torchmd/interface.py:303-361), which overwrites q1 (so it multiplies q_j * q_j) and carries a
@@ -733,7 +830,7 @@ class CoulombPotentials(GeneralInteraction):
     depends on the cutoff and alpha.  (The reciprocal part is a term of its own: with shift="none", EwaldReciprocal on top
     of this class completes the Ewald sum -- see `ewald`.)
 
-    forward(xyz) is differentiable twice in xyz and once in charges on the HIP kernel (ops.CoulombEnergyFn,
+    forward(xyz) is differentiable twice in xyz and once in charges on the HIP kernel (ops.CoulombTerm,
     csrc/coulomb.hip); force / force_vjp serve the analytic adjoint and HIP-graph replay, also while charges requires grad:
     d(w.F)/dcharges comes from the same launch plus a fixed-order reduction.  float64 or host positions take the torch
     restatement `_torch_energy`."""
@@ -774,68 +871,33 @@ class CoulombPotentials(GeneralInteraction):
         self._mask = ops.build_mask(n, index_tuple, ex_pairs, system.device)
         self._n_rep = system.get_number_of_atoms() // n
         self._ell = None
+        self._q_mirror = _DeviceMirror(self._charges, self._pack_charges, numel=self._n_rep * n)
         if torch.device(self.device).type == "cuda":
             self._reset_topology(torch.Tensor(system.get_positions()).to(system.device))
 
-    def _hip_ok(self, xyz=None):
-        if xyz is not None and (not xyz.is_cuda or xyz.dtype != torch.float32):
-            return False
-        return self.analytic and self._ell is not None
-
-    # -- topology: the lists of PairPotentials ---------------------------------------------------------------------
-    def _reset_topology(self, xyz, _cache=None):
-        self._topo_stamp = object()
-        st = self._static if self._static_on else None
-        vkey = ("verlet", float(self.cutoff), None if self._mask is None else self._mask.data_ptr(), self._group)
-        if st is not None and _cache is not None and vkey in _cache:
-            self._ell = _cache[vkey].ell             # a Stack member's Verlet list (exact cutoff re-applied per pair)
-        elif st is not None:
-            self._ell = self._shared_static_ell(xyz, _cache, st)
-        else:
-            self._ell = self._shared_ell(xyz, _cache)
-
-    def supports_static_topology(self):
-        return self._hip_ok()
-
-    def set_static_topology(self, on=True):
-        self._static_on = bool(on)
-        if on and self._static is None:
-            longest = int(self._ell.cnt.max().item())
-            self._static = dict(max_nbr=min(self._group - 1, (int(longest * 1.25) + 15) // 8 * 8),
-                                need=torch.zeros(2, dtype=torch.int32, device=self.device), version=0)
-
-    # -- the per-atom charge buffer the kernel reads ---------------------------------------------------------------
+    # -- the per-atom charge buffer the kernel reads (the lists are _ListTerm's, those of PairPotentials) ----------
     def _expand(self, charges):
         """charges [n] or [n_types] -> one charge per atom of the (replica-stacked) system."""
         q = charges if self.types is None else charges[self.types.to(charges.device)]
         return q.repeat(self._n_rep) if self._n_rep > 1 else q
 
+    def _charges(self):
+        return (self.charges,)
+
+    def _pack_charges(self, ps, out=None):
+        q = self._expand(ps[0].detach())
+        return q.contiguous() if out is None else out.copy_(q)
+
     def _q_atom(self):
-        """charges[types] tiled over the replicas, in a persistent buffer that is refreshed when the charges changed (version
-        counter); inside a HIP-graph capture it is returned as it is -- the replaying pass refreshes it once before its first
-        replay (`prepare_pass`), so the captured steps carry no torch op for it."""
-        c = self.charges
-        buf = getattr(self, "_q_buf", None)
-        capturing = c.is_cuda and torch.cuda.is_current_stream_capturing()
-        if buf is None or buf.device != c.device:
-            if capturing:
-                return self._expand(c.detach()).contiguous()
-            buf = self._q_buf = torch.empty(self._n_rep * self._group, device=c.device, dtype=torch.float32)
-            self._q_key = None
-        if capturing:
-            return buf
-        key = (c.data_ptr(), c._version)
-        if self._q_key != key:
-            buf.copy_(self._expand(c.detach()))
-            self._q_key = key
-        return buf
+        """charges[types] tiled over the replicas: the device mirror of the charges (_DeviceMirror)."""
+        return self._q_mirror.get()
 
     def prepare_pass(self):
         if self._hip_ok():
             self._q_atom()
 
-    def _spec(self):
-        return ops.CoulombSpec(self._ell, self._consts, self._q_atom(), self._slot, self.n_slots)
+    def _term(self):
+        return ops.CoulombTerm(self._ell, self._consts, self._q_atom(), self._slot, self.n_slots)
 
     # -- energy ----------------------------------------------------------------------------------------------------
     def _pairs(self, xyz):
@@ -845,20 +907,7 @@ class CoulombPotentials(GeneralInteraction):
         if self._ell is not None and xyz.is_cuda:
             nbr, off = self._ell.half_list()
             return nbr[:, 0], nbr[:, 1], off.to(xyz)
-        n, R = self._group, self._n_rep
-        cell = self.cell.detach().to(xyz)
-        cell = torch.diag(cell) if cell.dim() == 1 else cell
-        iu = torch.triu_indices(n, n, offset=1, device=xyz.device)
-        x = xyz.detach().reshape(R, n, 3)
-        D = x[:, iu[1]] - x[:, iu[0]]
-        s = D.matmul(cell.inverse())
-        o = -(s > 0.5).to(xyz) + (s < -0.5).to(xyz)
-        d2 = (D + o.matmul(cell)).pow(2).sum(-1)
-        keep = (d2 < self.cutoff ** 2) & (d2 != 0)
-        if self._mask is not None:
-            keep &= self._mask.to(xyz.device).bool()[iu[0], iu[1]][None, :]
-        rep, idx = torch.nonzero(keep, as_tuple=True)
-        return iu[0][idx] + rep * n, iu[1][idx] + rep * n, o[rep, idx]
+        return self._all_pairs(xyz, self.cutoff, self._mask)
 
     def _torch_energy(self, xyz):
         """The same energy in torch ops on the half list, in the dtype and on the device of xyz (differentiable by autograd in
@@ -879,7 +928,7 @@ class CoulombPotentials(GeneralInteraction):
 
     def forward(self, xyz):
         if self._hip_ok(xyz):
-            return ops.CoulombEnergyFn.apply(xyz.contiguous(), self.charges, self._spec())
+            return ops.TermEnergyFn.apply(xyz.contiguous(), self._term(), self.charges)
         return self._torch_energy(xyz)
 
     # -- analytic-adjoint protocol (md._EOM.rhs_vjp, Stack.force / force_vjp) -------------------------------------
@@ -900,20 +949,11 @@ class CoulombPotentials(GeneralInteraction):
         need = bool(want_theta) and isinstance(self.charges, torch.nn.Parameter)
         o = ops.coulomb_eval(self._ell, xyz.detach(), self._q_atom(), self._consts, w=w.detach(), energy=False, grad=True,
                              into=into, scale=-1.0, want_pot=need)
-        if not want_theta:
-            return o["grad"], o["hw"], None
-        if not need:
-            return o["grad"], o["hw"], ([] if accum is None else None)
-        gw = ops.coulomb_charge_grad(o["potw"], self._slot, self.n_slots)          # d(w.dU/dx)/dcharges / conversion
-        if accum is not None:
-            jobs = ops.GradJobs()
-            jobs.axpy(accum.off[id(self.charges)], gw)
-            jobs.run(accum, alpha=-self.conversion, accumulate=True)
-            return o["grad"], o["hw"], None
-        return o["grad"], o["hw"], [(-self.conversion) * gw.reshape(self.charges.shape)]
+        gw = ops.coulomb_charge_grad(o["potw"], self._slot, self.n_slots) if need else None
+        return o["grad"], o["hw"], _param_tail(gw, self.charges, -self.conversion, want_theta, accum)
 
 
-class StillingerWeber(GeneralInteraction):
+class StillingerWeber(_ListTerm):
     """Stillinger-Weber potential for one species (Stillinger and Weber 1985): a short-ranged pair term plus a three-body
     term that prefers the angle cos0 between the bonds of every atom to its near neighbours -- tetrahedral silicon
     (`silicon`) and monatomic coarse-grained water (`mW`, Molinero and Moore 2009).  With rc = a sigma:
@@ -936,7 +976,7 @@ class StillingerWeber(GeneralInteraction):
     then, outside a HIP-graph capture only and only when its version counter moved; `static_version()` changes with the
     cutoff, so captured graphs are rebuilt).
 
-    forward(xyz) is differentiable twice in xyz and once in (epsilon, sigma, lam) on the HIP kernel (ops.SWEnergyFn,
+    forward(xyz) is differentiable twice in xyz and once in (epsilon, sigma, lam) on the HIP kernel (ops.SWTerm,
     csrc/sw.hip); force / force_vjp serve the analytic adjoint and HIP-graph replay, also while the parameters require grad:
     d(w.F)/d(epsilon, sigma, lam) comes from the same launch plus a fixed-order reduction.  float64 or host positions take
     the torch restatement `_torch_energy`."""
@@ -973,6 +1013,7 @@ class StillingerWeber(GeneralInteraction):
         self.index_tuple, self.ex_pairs, self._mask = None, None, None
         self._n_rep = system.get_number_of_atoms() // self._group
         self._ell = None
+        self._theta_mirror = _DeviceMirror(self._thetas)
         self.cutoff, self._cut_ver, self._list_ver, self._sig_key = None, 0, -1, None
         self._sync_cutoff()
         if torch.device(self.device).type == "cuda":
@@ -990,11 +1031,6 @@ class StillingerWeber(GeneralInteraction):
         """Molinero and Moore's monatomic water: epsilon = 6.189 kcal/mol (in eV), sigma = 2.3925 Angstrom, lam = 23.15."""
         kw.setdefault("lam", 23.15)
         return cls(system, 6.189 * cls.KCAL_PER_MOL, 2.3925, **kw)
-
-    def _hip_ok(self, xyz=None):
-        if xyz is not None and (not xyz.is_cuda or xyz.dtype != torch.float32):
-            return False
-        return self.analytic and self._ell is not None
 
     # -- the cutoff the list is searched with ---------------------------------------------------------------------
     def _sync_cutoff(self):
@@ -1021,49 +1057,21 @@ class StillingerWeber(GeneralInteraction):
 
     # -- topology: the lists of PairPotentials ---------------------------------------------------------------------
     def _reset_topology(self, xyz, _cache=None):
-        self._topo_stamp = object()
         self._sync_cutoff()
-        st = self._static if self._static_on else None
-        vkey = ("verlet", float(self.cutoff), None, self._group)
-        if st is not None and _cache is not None and vkey in _cache:
-            self._ell = _cache[vkey].ell             # a Stack member's Verlet list (the support test is applied per pair)
-        elif st is not None:
-            self._ell = self._shared_static_ell(xyz, _cache, st)
-        else:
-            self._ell = self._shared_ell(xyz, _cache)
+        super()._reset_topology(xyz, _cache)         # (a Stack member's Verlet list serves: the support test is per pair)
         self._list_ver = self._cut_ver
 
-    def supports_static_topology(self):
-        return self._hip_ok()
-
     def set_static_topology(self, on=True):
-        self._static_on = bool(on)
         self._sync_cutoff()
-        if on and self._static is None:
-            longest = int(self._ell.cnt.max().item())
-            self._static = dict(max_nbr=min(self._group - 1, (int(longest * 1.25) + 15) // 8 * 8),
-                                need=torch.zeros(2, dtype=torch.int32, device=self.device), version=0)
+        super().set_static_topology(on)
 
     # -- the device copy of (epsilon, sigma, lam) the kernel reads -------------------------------------------------
+    def _thetas(self):
+        return self.epsilon, self.sigma, self.lam
+
     def _theta(self):
-        """(epsilon, sigma, lam) in a persistent device buffer that is refreshed when one of them changed (version counters);
-        inside a HIP-graph capture it is returned as it is -- the replaying pass refreshes it once before its first replay
-        (`prepare_pass`), so the captured steps carry no torch op for it."""
-        ps = (self.epsilon, self.sigma, self.lam)
-        buf = getattr(self, "_theta_buf", None)
-        capturing = ps[0].is_cuda and torch.cuda.is_current_stream_capturing()
-        if buf is None or buf.device != ps[0].device:
-            if capturing:
-                return torch.cat([p.detach().reshape(-1) for p in ps])
-            buf = self._theta_buf = torch.empty(3, device=ps[0].device, dtype=torch.float32)
-            self._theta_key = None
-        if capturing:
-            return buf
-        key = tuple((p.data_ptr(), p._version) for p in ps)
-        if self._theta_key != key:
-            torch.cat([p.detach().reshape(-1).to(torch.float32) for p in ps], out=buf)
-            self._theta_key = key
-        return buf
+        """(epsilon, sigma, lam) as the kernel reads them: their device mirror (_DeviceMirror)."""
+        return self._theta_mirror.get()
 
     def prepare_pass(self):
         self._sync_cutoff()
@@ -1079,28 +1087,12 @@ class StillingerWeber(GeneralInteraction):
         return self._ell
 
     # -- energy ----------------------------------------------------------------------------------------------------
-    def _pairs(self, xyz, rc):
-        """Half list (i, j, image offsets) at xyz of every pair of a replica closer than rc, by torch ops with the
-        reference's minimum image (torchmd/topology.py:30-73)."""
-        n, R = self._group, self._n_rep
-        cell = self.cell.detach().to(xyz)
-        cell = torch.diag(cell) if cell.dim() == 1 else cell
-        iu = torch.triu_indices(n, n, offset=1, device=xyz.device)
-        x = xyz.detach().reshape(R, n, 3)
-        D = x[:, iu[1]] - x[:, iu[0]]
-        s = D.matmul(cell.inverse())
-        o = -(s > 0.5).to(xyz) + (s < -0.5).to(xyz)
-        d2 = (D + o.matmul(cell)).pow(2).sum(-1)
-        keep = (d2 < rc ** 2) & (d2 != 0)
-        rep, idx = torch.nonzero(keep, as_tuple=True)
-        return iu[0][idx] + rep * n, iu[1][idx] + rep * n, o[rep, idx]
-
     def _torch_energy(self, xyz):
         """The same energy in torch ops, in the dtype and on the device of xyz (differentiable by autograd in xyz and in
         epsilon, sigma, lam): the pairs inside a sigma, then every triplet as two entries of one atom's row."""
         eps, sig, lam = (p.to(xyz).reshape(()) for p in (self.epsilon, self.sigma, self.lam))
         rc = self.a * sig
-        i, j, off = self._pairs(xyz, float(rc.detach()))
+        i, j, off = self._all_pairs(xyz, float(rc.detach()))
         cell = self.cell.detach().to(xyz)
         cell = torch.diag(cell) if cell.dim() == 1 else cell
         d = xyz[i] - xyz[j] - off.matmul(cell)
@@ -1130,8 +1122,7 @@ class StillingerWeber(GeneralInteraction):
     def forward(self, xyz):
         if self._hip_ok(xyz):
             ell = self._current_list(xyz)
-            return ops.SWEnergyFn.apply(xyz.contiguous(), self.epsilon, self.sigma, self.lam,
-                                        ops.SWSpec(ell, self._consts, self._theta()))
+            return ops.TermEnergyFn.apply(xyz.contiguous(), ops.SWTerm(ell, self._consts, self._theta()), *self._thetas())
         return self._torch_energy(xyz)
 
     # -- analytic-adjoint protocol (md._EOM.rhs_vjp, Stack.force / force_vjp) -------------------------------------
@@ -1150,31 +1141,13 @@ class StillingerWeber(GeneralInteraction):
         the parameter part; `accum` (ops.ThetaAccum): that part is added into its flat buffer instead (None returned).
         `into` = (F, dq) buffers of another Stack member: this term's force and d(w.F)/dx are added onto them in the same
         launch."""
-        params = [p for p in (self.epsilon, self.sigma, self.lam) if isinstance(p, torch.nn.Parameter)]
-        need = bool(want_theta) and bool(params)
+        need = bool(want_theta) and any(isinstance(p, torch.nn.Parameter) for p in self._thetas())
         o = ops.sw_eval(self._current_list(xyz), xyz.detach(), self._consts, self._theta(), w=w.detach(), energy=False,
                         grad=True, into=into, scale=-1.0, want_theta=need)
-        if not want_theta:
-            return o["grad"], o["hw"], None
-        if not need:
-            return o["grad"], o["hw"], ([] if accum is None else None)
-        if accum is not None:
-            jobs = ops.GradJobs()
-            offs = [accum.off.get(id(p)) for p in params]
-            if len(params) == 3 and None not in offs and offs[1] == offs[0] + 1 and offs[2] == offs[0] + 2:
-                jobs.colsum(offs[0], o["pthw"])                  # the three parameters are adjacent in the flat buffer
-            else:
-                for col, p in enumerate((self.epsilon, self.sigma, self.lam)):
-                    if isinstance(p, torch.nn.Parameter) and accum.off.get(id(p)) is not None:
-                        jobs.colsum(accum.off[id(p)], o["pthw"][:, col:col + 1])
-            jobs.run(accum, alpha=-1.0, accumulate=True)
-            return o["grad"], o["hw"], None
-        gw = ops.sw_theta_sum(o["pthw"], alpha=-1.0)
-        return o["grad"], o["hw"], [gw[k:k + 1].reshape(p.shape) for k, p in enumerate((self.epsilon, self.sigma, self.lam))
-                                    if isinstance(p, torch.nn.Parameter)]
+        return o["grad"], o["hw"], _theta3_tail(o["pthw"], self._thetas(), want_theta, accum)
 
 
-class SuttonChen(GeneralInteraction):
+class SuttonChen(_ListTerm):
     """Sutton-Chen embedded-atom potential for one species (Sutton and Chen 1990; the Finnis-Sinclair form of the
     embedded-atom method): the cohesion of an fcc metal as a function of the local density, not a sum over pairs.  With
     the parameters epsilon (energy), a (length), c (dimensionless) and the integer exponents n > m >= 1:
@@ -1199,7 +1172,7 @@ class SuttonChen(GeneralInteraction):
     are constants.  Not covered: `index_tuple`, `ex_pairs` (both rejected), several species, tabulated embedding functions.
     `copper`, `nickel`, `silver` and `gold` carry the published constants (epsilon in eV, a in Angstrom), cutoff 2 a by default.
 
-    forward(xyz) is differentiable twice in xyz and once in (epsilon, a, c) on the HIP kernels (ops.EAMEnergyFn,
+    forward(xyz) is differentiable twice in xyz and once in (epsilon, a, c) on the HIP kernels (ops.EAMTerm,
     csrc/eam.hip: a density pass, then a force pass that reads the neighbours' embedding derivatives); force / force_vjp
     serve the analytic adjoint and HIP-graph replay, also while the parameters require grad.  float64 or host positions take
     the torch restatement `_torch_energy`."""
@@ -1233,6 +1206,7 @@ class SuttonChen(GeneralInteraction):
         self.index_tuple, self.ex_pairs, self._mask = None, None, None
         self._n_rep = system.get_number_of_atoms() // self._group
         self._ell = None
+        self._theta_mirror = _DeviceMirror(self._thetas)
         self._work = None
         if torch.device(self.device).type == "cuda":
             # the scratch of the density pass: persistent, so that a captured graph sees a fixed address
@@ -1265,53 +1239,14 @@ class SuttonChen(GeneralInteraction):
         """Sutton and Chen's gold: epsilon = 1.2793e-2 eV, a = 4.08 Angstrom, c = 34.408, n = 10, m = 8."""
         return cls._published("gold", system, cutoff, kw)
 
-    def _hip_ok(self, xyz=None):
-        if xyz is not None and (not xyz.is_cuda or xyz.dtype != torch.float32):
-            return False
-        return self.analytic and self._ell is not None
+    # -- the device copy of (epsilon, a, c) the kernels read (the lists are _ListTerm's, those of PairPotentials) --
+    def _thetas(self):
+        return self.epsilon, self.a, self.c
 
-    # -- topology: the lists of PairPotentials ---------------------------------------------------------------------
-    def _reset_topology(self, xyz, _cache=None):
-        self._topo_stamp = object()
-        st = self._static if self._static_on else None
-        vkey = ("verlet", float(self.cutoff), None, self._group)
-        if st is not None and _cache is not None and vkey in _cache:
-            self._ell = _cache[vkey].ell             # a Stack member's Verlet list (the support test is applied per pair)
-        elif st is not None:
-            self._ell = self._shared_static_ell(xyz, _cache, st)
-        else:
-            self._ell = self._shared_ell(xyz, _cache)
-
-    def supports_static_topology(self):
-        return self._hip_ok()
-
-    def set_static_topology(self, on=True):
-        self._static_on = bool(on)
-        if on and self._static is None:
-            longest = int(self._ell.cnt.max().item())
-            self._static = dict(max_nbr=min(self._group - 1, (int(longest * 1.25) + 15) // 8 * 8),
-                                need=torch.zeros(2, dtype=torch.int32, device=self.device), version=0)
-
-    # -- the device copy of (epsilon, a, c) the kernels read -------------------------------------------------------
     def _theta(self):
-        """(epsilon, a, c) in a persistent device buffer that is refreshed when one of them changed (version counters);
-        inside a HIP-graph capture it is returned as it is -- the replaying pass refreshes it once before its first replay
-        (`prepare_pass`), so the captured steps carry no torch op for it and no host value of a parameter."""
-        ps = (self.epsilon, self.a, self.c)
-        buf = getattr(self, "_theta_buf", None)
-        capturing = ps[0].is_cuda and torch.cuda.is_current_stream_capturing()
-        if buf is None or buf.device != ps[0].device:
-            if capturing:
-                return torch.cat([p.detach().reshape(-1) for p in ps])
-            buf = self._theta_buf = torch.empty(3, device=ps[0].device, dtype=torch.float32)
-            self._theta_key = None
-        if capturing:
-            return buf
-        key = tuple((p.data_ptr(), p._version) for p in ps)
-        if self._theta_key != key:
-            torch.cat([p.detach().reshape(-1).to(torch.float32) for p in ps], out=buf)
-            self._theta_key = key
-        return buf
+        """(epsilon, a, c) as the kernels read them: their device mirror (_DeviceMirror), so that the captured steps carry
+        no host value of a parameter."""
+        return self._theta_mirror.get()
 
     def prepare_pass(self):
         if self._hip_ok():
@@ -1323,8 +1258,6 @@ class SuttonChen(GeneralInteraction):
         return self._work
 
     # -- energy ----------------------------------------------------------------------------------------------------
-    _pairs = StillingerWeber._pairs
-
     def _shape(self, r, a, k):
         s = (a / r) ** k
         if self.shift == "none":
@@ -1336,7 +1269,7 @@ class SuttonChen(GeneralInteraction):
         """The same energy in torch ops, in the dtype and on the device of xyz (differentiable by autograd in xyz and in
         epsilon, a, c)."""
         eps, a, c = (p.to(xyz).reshape(()) for p in (self.epsilon, self.a, self.c))
-        i, j, off = self._pairs(xyz, self.cutoff)
+        i, j, off = self._all_pairs(xyz, self.cutoff)
         cell = self.cell.detach().to(xyz)
         cell = torch.diag(cell) if cell.dim() == 1 else cell
         d = xyz[i] - xyz[j] - off.matmul(cell)
@@ -1349,8 +1282,8 @@ class SuttonChen(GeneralInteraction):
 
     def forward(self, xyz):
         if self._hip_ok(xyz):
-            return ops.EAMEnergyFn.apply(xyz.contiguous(), self.epsilon, self.a, self.c,
-                                         ops.EAMSpec(self._ell, self._consts, self._theta(), self._scratch(xyz)))
+            term = ops.EAMTerm(self._ell, self._consts, self._theta(), self._scratch(xyz))
+            return ops.TermEnergyFn.apply(xyz.contiguous(), term, *self._thetas())
         return self._torch_energy(xyz)
 
     # -- analytic-adjoint protocol (md._EOM.rhs_vjp, Stack.force / force_vjp) -------------------------------------
@@ -1369,31 +1302,13 @@ class SuttonChen(GeneralInteraction):
         parameter part; `accum` (ops.ThetaAccum): that part is added into its flat buffer instead (None returned).
         `into` = (F, dq) buffers of another Stack member: this term's force and d(w.F)/dx are added onto them in the
         force pass."""
-        params = [p for p in (self.epsilon, self.a, self.c) if isinstance(p, torch.nn.Parameter)]
-        need = bool(want_theta) and bool(params)
+        need = bool(want_theta) and any(isinstance(p, torch.nn.Parameter) for p in self._thetas())
         o = ops.eam_eval(self._ell, xyz.detach(), self._consts, self._theta(), w=w.detach(), energy=False, grad=True,
                          into=into, scale=-1.0, want_theta=need, work=self._scratch(xyz))
-        if not want_theta:
-            return o["grad"], o["hw"], None
-        if not need:
-            return o["grad"], o["hw"], ([] if accum is None else None)
-        if accum is not None:
-            jobs = ops.GradJobs()
-            offs = [accum.off.get(id(p)) for p in params]
-            if len(params) == 3 and None not in offs and offs[1] == offs[0] + 1 and offs[2] == offs[0] + 2:
-                jobs.colsum(offs[0], o["pthw"])                  # the three parameters are adjacent in the flat buffer
-            else:
-                for col, p in enumerate((self.epsilon, self.a, self.c)):
-                    if isinstance(p, torch.nn.Parameter) and accum.off.get(id(p)) is not None:
-                        jobs.colsum(accum.off[id(p)], o["pthw"][:, col:col + 1])
-            jobs.run(accum, alpha=-1.0, accumulate=True)
-            return o["grad"], o["hw"], None
-        gw = ops.eam_theta_sum(o["pthw"], alpha=-1.0)
-        return o["grad"], o["hw"], [gw[k:k + 1].reshape(p.shape) for k, p in enumerate((self.epsilon, self.a, self.c))
-                                    if isinstance(p, torch.nn.Parameter)]
+        return o["grad"], o["hw"], _theta3_tail(o["pthw"], self._thetas(), want_theta, accum)
 
 
-class EwaldReciprocal(torch.nn.Module):
+class EwaldReciprocal(_StaticTerm, torch.nn.Module):
     """The reciprocal-space part of the Ewald sum for the point charges of a CoulombPotentials (no counterpart in the
     reference).  With `real` = CoulombPotentials(system, charges, cutoff, alpha, shift="none", self_energy=True) the two
     terms together are the energy of the periodic system, independent of alpha up to the truncation of both sums:
@@ -1416,7 +1331,7 @@ class EwaldReciprocal(torch.nn.Module):
     EwaldExclusions(system, real) removes -- pass it as `exclusions=` (or build all three with ewald(..., ex_pairs=));
     without it such a `real` is refused.
 
-    forward(xyz) is differentiable twice in xyz and once in charges on the HIP kernels (ops.EwaldEnergyFn, csrc/ewald.hip);
+    forward(xyz) is differentiable twice in xyz and once in charges on the HIP kernels (ops.EwaldTerm, csrc/ewald.hip);
     force / force_vjp serve the analytic adjoint and HIP-graph replay like CoulombPotentials'.  float64 or host positions
     take the torch restatement `_torch_energy`.  A Stack holding the term stays off the fused trajectory kernels."""
 
@@ -1478,9 +1393,6 @@ class EwaldReciprocal(torch.nn.Module):
             return False
         return self.analytic and torch.device(self.device).type == "cuda"
 
-    def _reset_topology(self, xyz):          # (nothing to search)
-        pass
-
     def _q_atom(self):
         return self._real[0]._q_atom()
 
@@ -1488,8 +1400,8 @@ class EwaldReciprocal(torch.nn.Module):
         if self._hip_ok():
             self._q_atom()
 
-    def _spec(self):
-        return ops.EwaldSpec(self._table, self._q_atom(), self._slot, self.n_slots)
+    def _term(self):
+        return ops.EwaldTerm(self._table, self._q_atom(), self._slot, self.n_slots)
 
     def _torch_energy(self, xyz):
         """The same energy in torch ops, in the dtype and on the device of xyz (differentiable by autograd in xyz and
@@ -1506,7 +1418,7 @@ class EwaldReciprocal(torch.nn.Module):
 
     def forward(self, xyz):
         if self._hip_ok(xyz):
-            return ops.EwaldEnergyFn.apply(xyz.contiguous(), self.charges, self._spec())
+            return ops.TermEnergyFn.apply(xyz.contiguous(), self._term(), self.charges)
         return self._torch_energy(xyz)
 
     # -- analytic-adjoint protocol (md._EOM.rhs_vjp, Stack.force / force_vjp) -------------------------------------
@@ -1526,33 +1438,11 @@ class EwaldReciprocal(torch.nn.Module):
         need = bool(want_theta) and isinstance(self.charges, torch.nn.Parameter)
         o = ops.ewald_eval(self._table, xyz.detach(), self._q_atom(), w=w.detach(), energy=False, grad=True, into=into,
                            scale=-1.0, want_pot=need)
-        if not want_theta:
-            return o["grad"], o["hw"], None
-        if not need:
-            return o["grad"], o["hw"], ([] if accum is None else None)
-        gw = ops.coulomb_charge_grad(o["potw"], self._slot, self.n_slots)          # d(w.dU/dx)/dcharges
-        if accum is not None:
-            jobs = ops.GradJobs()
-            jobs.axpy(accum.off[id(self.charges)], gw)
-            jobs.run(accum, alpha=-1.0, accumulate=True)
-            return o["grad"], o["hw"], None
-        return o["grad"], o["hw"], [-gw.reshape(self.charges.shape)]
-
-    # -- fixed-capacity topology (HIP-graph capture): the tables are static, nothing can overflow -----------------
-    def supports_static_topology(self):
-        return self._hip_ok()
-
-    def set_static_topology(self, on=True):
-        pass
-
-    def static_overflow(self):
-        return False
-
-    def static_version(self):
-        return 0
+        gw = ops.coulomb_charge_grad(o["potw"], self._slot, self.n_slots) if need else None
+        return o["grad"], o["hw"], _param_tail(gw, self.charges, -1.0, want_theta, accum)
 
 
-class EwaldExclusions(torch.nn.Module):
+class EwaldExclusions(_StaticTerm, torch.nn.Module):
     """The third member of the Ewald sum for molecules: the erf correction for the excluded and scaled pairs of a
     CoulombPotentials (no counterpart in the reference).  The real-space term honours `ex_pairs` through its mask; the
     reciprocal sum runs over all charges and cannot leave a pair out.  With `real` = CoulombPotentials(system, charges, cutoff,
@@ -1581,7 +1471,7 @@ class EwaldExclusions(torch.nn.Module):
     a pair listed twice in either orientation (the mask is idempotent, this sum would subtract such a pair twice); a
     triclinic cell, system.dim != 3, a scale outside [0, 1].
 
-    forward(xyz) is differentiable twice in xyz and once in charges on the HIP kernel (ops.EwaldExclEnergyFn,
+    forward(xyz) is differentiable twice in xyz and once in charges on the HIP kernel (ops.EwaldExclTerm,
     csrc/ewald_excl.hip: below alpha r = 1 the erf part comes from the power series of erf(x)/x, whose closed form cancels
     in float32); force / force_vjp serve the analytic adjoint and HIP-graph replay like CoulombPotentials'.  float64 or host
     positions take the torch restatement `_torch_energy`.  A Stack holding the term stays off the fused trajectory
@@ -1641,9 +1531,6 @@ class EwaldExclusions(torch.nn.Module):
             return False
         return self.analytic and torch.device(self.device).type == "cuda"
 
-    def _reset_topology(self, xyz):          # (the pair list is static)
-        pass
-
     def _q_atom(self):
         return self._real[0]._q_atom()
 
@@ -1651,8 +1538,8 @@ class EwaldExclusions(torch.nn.Module):
         if self._hip_ok():
             self._q_atom()
 
-    def _spec(self):
-        return ops.EwaldExclSpec(self._table, self._q_atom(), self._slot, self.n_slots)
+    def _term(self):
+        return ops.EwaldExclTerm(self._table, self._q_atom(), self._slot, self.n_slots)
 
     def _torch_energy(self, xyz):
         """The same energy in torch ops, in the dtype and on the device of xyz (differentiable by autograd in xyz and
@@ -1675,7 +1562,7 @@ class EwaldExclusions(torch.nn.Module):
 
     def forward(self, xyz):
         if self._hip_ok(xyz):
-            return ops.EwaldExclEnergyFn.apply(xyz.contiguous(), self.charges, self._spec())
+            return ops.TermEnergyFn.apply(xyz.contiguous(), self._term(), self.charges)
         return self._torch_energy(xyz)
 
     # -- analytic-adjoint protocol (md._EOM.rhs_vjp, Stack.force / force_vjp) -------------------------------------
@@ -1696,30 +1583,8 @@ class EwaldExclusions(torch.nn.Module):
         need = bool(want_theta) and isinstance(self.charges, torch.nn.Parameter)
         o = ops.ewald_excl_eval(self._table, xyz.detach(), self._q_atom(), w=w.detach(), energy=False, grad=True, into=into,
                                 scale=-1.0, want_pot=need)
-        if not want_theta:
-            return o["grad"], o["hw"], None
-        if not need:
-            return o["grad"], o["hw"], ([] if accum is None else None)
-        gw = ops.coulomb_charge_grad(o["potw"], self._slot, self.n_slots)          # d(w.dU/dx)/dcharges / conversion
-        if accum is not None:
-            jobs = ops.GradJobs()
-            jobs.axpy(accum.off[id(self.charges)], gw)
-            jobs.run(accum, alpha=-self.conversion, accumulate=True)
-            return o["grad"], o["hw"], None
-        return o["grad"], o["hw"], [(-self.conversion) * gw.reshape(self.charges.shape)]
-
-    # -- fixed-capacity topology (HIP-graph capture): the table is static, nothing can overflow ------------------
-    def supports_static_topology(self):
-        return self._hip_ok()
-
-    def set_static_topology(self, on=True):
-        pass
-
-    def static_overflow(self):
-        return False
-
-    def static_version(self):
-        return 0
+        gw = ops.coulomb_charge_grad(o["potw"], self._slot, self.n_slots) if need else None
+        return o["grad"], o["hw"], _param_tail(gw, self.charges, -self.conversion, want_theta, accum)
 
 
 def ewald(system, charges, cutoff, accuracy=1e-5, k_cutoff=None, ex_pairs=None, scale=None, **kw):

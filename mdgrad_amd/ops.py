@@ -9,13 +9,15 @@ torch.autograd.Function wrappers that own the differentiation contract
     SkFn                                                        static structure factor of every frame
     MsdFn                                                       mean-squared displacement over all lags (+ fourth moment)
     IsfFn                                                       intermediate scattering functions F(k,t), F_s(k,t)
-    DihedralEnergyFn -> DihedralGradFn                          torsion term, order <= 2 in x, 1 in its coefficients
+    TermEnergyFn -> TermGradFn                                  every other term with parameters, order <= 2 in x, 1 in the
+                                                                parameters; what differs per kernel family is a small `term` object:
+      DihedralTerm                                              torsion term, parameters: its coefficients
+      CoulombTerm                                               damped shifted-force Coulomb sum, parameters: the charges
+      EwaldTerm                                                 Ewald reciprocal-space sum, parameters: the charges
+      EwaldExclTerm                                             Ewald erf correction of excluded / scaled pairs, the same
+      SWTerm                                                    Stillinger-Weber term, parameters: (epsilon, sigma, lam)
+      EAMTerm                                                   Sutton-Chen term, parameters: (epsilon, a, c)
     DihedralPhiFn, DihedralHistFn                               signed dihedral angles of every frame, their periodic histogram
-    CoulombEnergyFn -> CoulombGradFn                            damped shifted-force Coulomb sum, order <= 2 in x, 1 in the charges
-    EwaldEnergyFn -> EwaldGradFn                                Ewald reciprocal-space sum, order <= 2 in x, 1 in the charges
-    EwaldExclEnergyFn -> EwaldExclGradFn                        Ewald erf correction of excluded / scaled pairs, same orders
-    SWEnergyFn -> SWGradFn                                      Stillinger-Weber term, order <= 2 in x, 1 in (epsilon, sigma, lam)
-    EAMEnergyFn -> EAMGradFn                                    Sutton-Chen term, order <= 2 in x, 1 in (epsilon, a, c)
 
 Everything here requires HIP tensors; there is no CPU path.
 """
@@ -348,6 +350,110 @@ class BondedEnergyFn(torch.autograd.Function):
         return gU * BondedGradFn.apply(xyz, ctx.tab, ctx.cache), None
 
 
+# ----------------------------------------------------------------------------- terms with parameters: one autograd pair
+# Every term below (dihedral, Coulomb, Ewald, Ewald exclusions, Stillinger-Weber, Sutton-Chen) differentiates through this
+# pair.  PairGradFn / PairEnergyFn stay on their own (the empty-theta case, two C entry points), and so do BondedGradFn /
+# BondedEnergyFn (no parameters, ten lines).  A `term` holds what the two evaluations of its kernel family need and has
+#     first_order(xyz, energy) -> (U or None, dU/dx, packed)    packed: the flat dU/dparams, in the order of `params`
+#     second_order(xyz, w)     -> (H w, packed_w)               packed_w: the flat d(w.dU/dx)/dparams
+#     noun                                                      what the NotImplementedError below calls the parameter gradient
+def _split(packed, params):
+    """The flat `packed` as one tensor per parameter, in the parameter's shape."""
+    out, pos = [], 0
+    for p in params:
+        out.append(packed[pos:pos + p.numel()].reshape(p.shape))
+        pos += p.numel()
+    return out
+
+
+class TermGradFn(torch.autograd.Function):
+    """(dU/dx, packed dU/dparams) of a term as a differentiable op; backward = the Hessian-vector product and the mixed
+    derivative d(w.dU/dx)/dparams (the second autograd pass of torchmd/sovlers.py:229-233).  A cotangent on the parameter
+    gradient (second derivatives with respect to the parameters alone, or dU/dparams differentiated in x) is not provided."""
+
+    @staticmethod
+    def forward(ctx, xyz, term, cache, *params):
+        ctx.term = term
+        ctx.save_for_backward(xyz, *params)
+        ctx.set_materialize_grads(False)        # an unused output arrives as None, not as zeros: no device read
+        if cache is None:
+            cache = term.first_order(xyz, energy=False)[1:]
+        return cache
+
+    @staticmethod
+    def backward(ctx, wg, wpacked):
+        xyz, *params = ctx.saved_tensors
+        if wpacked is not None:
+            raise NotImplementedError("mdgrad_amd: derivatives of %s (a cotangent on it) are not provided by the HIP kernels"
+                                      % ctx.term.noun)
+        if wg is None:
+            return (None,) * (3 + len(params))
+        hw, packed_w = ctx.term.second_order(xyz, wg.detach().contiguous())
+        return (hw, None, None) + tuple(_split(packed_w, params))
+
+
+class TermEnergyFn(torch.autograd.Function):
+    """U(x, *params) of a term, differentiable twice in x and once in the parameters."""
+
+    @staticmethod
+    def forward(ctx, xyz, term, *params):
+        e, g, packed = term.first_order(xyz, energy=True)
+        ctx.term, ctx.cache = term, (g, packed)
+        ctx.save_for_backward(xyz, *params)
+        return e.reshape(())
+
+    @staticmethod
+    def backward(ctx, gU):
+        xyz, *params = ctx.saved_tensors
+        g, packed = TermGradFn.apply(xyz, ctx.term, ctx.cache, *params)
+        return (gU * g, None) + tuple(gU * t for t in _split(packed, params))
+
+
+def _eval_prologue(N, xyz, w, energy, grad, into, want_aux, aux_shape, q_atom=None):
+    """The common opening of coulomb_eval, sw_eval, eam_eval, ewald_eval and ewald_excl_eval: the device and shape checks
+    and the outputs -- energy [1], grad / hw [N, 3] (the buffers of `into` when given) and the auxiliary per-atom output of
+    `aux_shape` when wanted: without `w` the first-order one, with `w` its directional derivative.  Returns
+    (xyz, w, e, g, hw, aux, aux_w, acc).  (bonded_eval and dihedral_eval have per-atom energies and no per-atom auxiliary
+    output; they keep their own few lines.)"""
+    require_gpu(xyz, "xyz")
+    if q_atom is not None:
+        require_gpu(q_atom, "q_atom")
+    if xyz.shape != (N, 3):
+        raise ValueError("mdgrad_amd: xyz must be [%d, 3] (got %s)" % (N, tuple(xyz.shape)))
+    if q_atom is not None and q_atom.shape != (N,):
+        raise ValueError("mdgrad_amd: q_atom must be [%d] (got %s)" % (N, tuple(q_atom.shape)))
+    xyz = xyz.contiguous()
+    dev = xyz.device
+    acc = into is not None
+    e = torch.empty(1, device=dev) if energy else None
+    g = (into[0] if acc else torch.empty(N, 3, device=dev)) if grad else None
+    hw = aux = aux_w = None
+    if w is not None:
+        require_gpu(w, "w")
+        if w.shape != (N, 3):
+            raise ValueError("mdgrad_amd: w must be [%d, 3] (got %s)" % (N, tuple(w.shape)))
+        w = w.contiguous()
+        hw = into[1] if acc else torch.empty(N, 3, device=dev)
+        aux_w = torch.empty(aux_shape, device=dev) if want_aux else None
+    elif want_aux:
+        aux = torch.empty(aux_shape, device=dev)
+    return xyz, w, e, g, hw, aux, aux_w, acc
+
+
+def _check_theta(theta):
+    """`theta`, when given, is the contiguous device float [3] the SW / EAM kernels read their three parameters from."""
+    if theta is not None:
+        require_gpu(theta, "theta")
+        if theta.shape != (3,) or not theta.is_contiguous():
+            raise ValueError("mdgrad_amd: theta must be a contiguous [3] tensor (got %s)" % (tuple(theta.shape),))
+
+
+def _list_flags(acc, ell):
+    """The flags word of the list kernels: 1 = add onto the output buffers, 2 = the list was searched with a skin
+    (ops.VerletList), so the kernel applies the exact cutoff test per pair."""
+    return int(acc) | (2 if getattr(ell, "verlet", False) else 0)
+
+
 # ----------------------------------------------------------------------------- dihedral terms (K19)
 class DihedralTable:
     """Static table of dihedral quadruples for the kernels of csrc/dihedral.hip: `top` [n_terms, 4] rows (i, j, k, l) as
@@ -432,51 +538,22 @@ def dihedral_coeff_grad(tab, c_term, cd_term=None, want_u=True):
     return gu, gw
 
 
-class DihedralGradFn(torch.autograd.Function):
-    """(dU/dx, dU/dcoeffs) of the torsion term as a differentiable op; backward = the Hessian-vector product and the mixed
-    derivative d(w.dU/dx)/dcoeffs (the second autograd pass of torchmd/sovlers.py:229-233).  A cotangent on dU/dcoeffs (second
-    derivatives with respect to the coefficients alone, or dU/dcoeffs differentiated in x) is not provided."""
+class DihedralTerm:
+    """The torsion term for TermEnergyFn: U(x, coeffs) = sum_terms sum_m coeffs[type, m] cos^m phi (csrc/dihedral.hip) on a
+    DihedralTable."""
 
-    @staticmethod
-    def forward(ctx, xyz, coeff, tab, cache):
-        ctx.tab = tab
-        ctx.save_for_backward(xyz, coeff)
-        ctx.set_materialize_grads(False)
-        if cache is None:
-            o = dihedral_eval(tab, xyz, coeff, terms=True)
-            cache = (o["grad"], dihedral_coeff_grad(tab, o["c_term"])[0].reshape(coeff.shape))
-        return cache
+    noun = "dU/dcoeffs of the torsion term"
 
-    @staticmethod
-    def backward(ctx, wg, wgth):
-        xyz, coeff = ctx.saved_tensors
-        if wgth is not None:
-            raise NotImplementedError("mdgrad_amd: derivatives of dU/dcoeffs of the torsion term (a cotangent on it) are not "
-                                      "provided by the HIP kernels")
-        if wg is None:
-            return None, None, None, None
-        o = dihedral_eval(ctx.tab, xyz, coeff, w=wg.detach().contiguous(), grad=False, terms=True)
-        gw = dihedral_coeff_grad(ctx.tab, o["c_term"], o["cd_term"], want_u=False)[1]
-        return o["hw"], gw.reshape(coeff.shape), None, None
+    def __init__(self, tab, coeff):
+        self.tab, self.coeff = tab, coeff
 
+    def first_order(self, xyz, energy):
+        o = dihedral_eval(self.tab, xyz, self.coeff, energy=energy, grad=True, terms=True)
+        return (o["e_atom"].sum() if energy else None), o["grad"], dihedral_coeff_grad(self.tab, o["c_term"])[0].reshape(-1)
 
-class DihedralEnergyFn(torch.autograd.Function):
-    """U(x, coeffs) = sum_terms sum_m coeffs[type, m] cos^m phi (csrc/dihedral.hip), differentiable twice in x and once in
-    the coefficients."""
-
-    @staticmethod
-    def forward(ctx, xyz, coeff, tab):
-        o = dihedral_eval(tab, xyz, coeff, energy=True, grad=True, terms=True)
-        ctx.tab = tab
-        ctx.cache = (o["grad"], dihedral_coeff_grad(tab, o["c_term"])[0].reshape(coeff.shape))
-        ctx.save_for_backward(xyz, coeff)
-        return o["e_atom"].sum()
-
-    @staticmethod
-    def backward(ctx, gU):
-        xyz, coeff = ctx.saved_tensors
-        g, gth = DihedralGradFn.apply(xyz, coeff, ctx.tab, ctx.cache)
-        return gU * g, gU * gth, None
+    def second_order(self, xyz, w):
+        o = dihedral_eval(self.tab, xyz, self.coeff, w=w, grad=False, terms=True)
+        return o["hw"], dihedral_coeff_grad(self.tab, o["c_term"], o["cd_term"], want_u=False)[1].reshape(-1)
 
 
 class DihedralPhiFn(torch.autograd.Function):
@@ -577,31 +654,12 @@ def coulomb_eval(ell, xyz, q_atom, consts, w=None, energy=True, grad=True, into=
     pot_i = sum_j q_j psi(r_ij), with `w` potw_i = sum_j q_j psi'(r_ij) rhat_ij.(w_i - w_j) -- what coulomb_charge_grad reduces
     to the charge gradients.  A list searched with a skin (ops.VerletList) gets the exact cutoff test per pair."""
     lib = _lib.load()
-    require_gpu(xyz, "xyz")
-    require_gpu(q_atom, "q_atom")
     N = ell.n_atoms
-    if xyz.shape != (N, 3):
-        raise ValueError("mdgrad_amd: xyz must be [%d, 3] (got %s)" % (N, tuple(xyz.shape)))
-    if q_atom.shape != (N,):
-        raise ValueError("mdgrad_amd: q_atom must be [%d] (got %s)" % (N, tuple(q_atom.shape)))
-    xyz = xyz.contiguous()
-    dev = xyz.device
-    acc = into is not None
-    e = torch.empty(1, device=dev) if energy else None
-    g = (into[0] if acc else torch.empty(N, 3, device=dev)) if grad else None
-    hw = pot = potw = None
-    if w is not None:
-        require_gpu(w, "w")
-        w = w.contiguous()
-        hw = into[1] if acc else torch.empty(N, 3, device=dev)
-        potw = torch.empty(N, device=dev) if want_pot else None
-    elif want_pot:
-        pot = torch.empty(N, device=dev)
-    partial = torch.empty(int(lib.mdg_coulomb_partial_size(N)), device=dev) if energy else None
-    recheck = bool(getattr(ell, "verlet", False))
+    xyz, w, e, g, hw, pot, potw, acc = _eval_prologue(N, xyz, w, energy, grad, into, want_pot, (N,), q_atom)
+    partial = torch.empty(int(lib.mdg_coulomb_partial_size(N)), device=xyz.device) if energy else None
     check(lib.mdg_coulomb_eval(ptr(xyz), N, C.byref(ell.cell_struct), ptr(ell.col), ptr(ell.shift), ptr(ell.cnt), ell.max_nbr,
                                ptr(q_atom), C.byref(consts), ptr(w), ptr(e), ptr(g), ptr(hw), ptr(pot), ptr(potw), ptr(partial),
-                               float(scale), int(acc) | (2 if recheck else 0), stream_ptr(dev)), "mdg_coulomb_eval")
+                               float(scale), _list_flags(acc, ell), stream_ptr(xyz.device)), "mdg_coulomb_eval")
     return dict(energy=e, grad=g, hw=hw, pot=pot, potw=potw)
 
 
@@ -618,65 +676,24 @@ def coulomb_charge_grad(pot, slot, n_slots):
     return out
 
 
-class CoulombSpec:
-    """What the autograd functions below need beside the tensors: the list, the constants, the per-atom charge buffer
-    (charges[types] tiled over the replicas, kept current by CoulombPotentials) and the charge slots."""
+class CoulombTerm:
+    """The damped shifted-force Coulomb sum (csrc/coulomb.hip) for TermEnergyFn: the list, the constants, the per-atom charge
+    buffer (charges[types] tiled over the replicas, kept current by CoulombPotentials) and the charge slots."""
+
+    noun = "dU/dcharges of the Coulomb term"
 
     def __init__(self, ell, consts, q_atom, slot, n_slots):
         self.ell, self.consts, self.q_atom, self.slot, self.n_slots = ell, consts, q_atom, slot, int(n_slots)
 
+    def first_order(self, xyz, energy):
+        o = coulomb_eval(self.ell, xyz, self.q_atom, self.consts, energy=energy, grad=True, want_pot=True)
+        k = self.consts
+        dq_atom = float(k.conversion) * (o["pot"] - (2.0 * float(k.self_s)) * self.q_atom)         # dU/dq_i
+        return o["energy"], o["grad"], coulomb_charge_grad(dq_atom, self.slot, self.n_slots)
 
-class CoulombGradFn(torch.autograd.Function):
-    """(dU/dx, dU/dcharges) as a differentiable op; backward = the Hessian-vector product and the mixed derivative
-    d(w.dU/dx)/dcharges (the second autograd pass of torchmd/sovlers.py:229-233).  A cotangent on dU/dcharges is not
-    provided."""
-
-    @staticmethod
-    def forward(ctx, xyz, charges, spec, cache):
-        ctx.spec = spec
-        ctx.save_for_backward(xyz, charges)
-        ctx.set_materialize_grads(False)
-        if cache is None:
-            cache = _coulomb_first_order(spec, xyz, charges, energy=False)[1:]
-        return cache
-
-    @staticmethod
-    def backward(ctx, wg, wq):
-        xyz, charges = ctx.saved_tensors
-        s = ctx.spec
-        if wq is not None:
-            raise NotImplementedError("mdgrad_amd: derivatives of dU/dcharges of the Coulomb term (a cotangent on it) are not "
-                                      "provided by the HIP kernels")
-        if wg is None:
-            return None, None, None, None
-        o = coulomb_eval(s.ell, xyz, s.q_atom, s.consts, w=wg.detach().contiguous(), energy=False, grad=False, want_pot=True)
-        gq = coulomb_charge_grad(o["potw"], s.slot, s.n_slots) * float(s.consts.conversion)
-        return o["hw"], gq.reshape(charges.shape), None, None
-
-
-def _coulomb_first_order(spec, xyz, charges, energy):
-    o = coulomb_eval(spec.ell, xyz, spec.q_atom, spec.consts, energy=energy, grad=True, want_pot=True)
-    k = spec.consts
-    dq_atom = float(k.conversion) * (o["pot"] - (2.0 * float(k.self_s)) * spec.q_atom)         # dU/dq_i
-    return o["energy"], o["grad"], coulomb_charge_grad(dq_atom, spec.slot, spec.n_slots).reshape(charges.shape)
-
-
-class CoulombEnergyFn(torch.autograd.Function):
-    """U(x, charges) of the damped shifted-force Coulomb sum (csrc/coulomb.hip), differentiable twice in x and once in
-    the charges."""
-
-    @staticmethod
-    def forward(ctx, xyz, charges, spec):
-        e, g, gq = _coulomb_first_order(spec, xyz, charges, energy=True)
-        ctx.spec, ctx.cache = spec, (g, gq)
-        ctx.save_for_backward(xyz, charges)
-        return e.reshape(())
-
-    @staticmethod
-    def backward(ctx, gU):
-        xyz, charges = ctx.saved_tensors
-        g, gq = CoulombGradFn.apply(xyz, charges, ctx.spec, ctx.cache)
-        return gU * g, gU * gq, None
+    def second_order(self, xyz, w):
+        o = coulomb_eval(self.ell, xyz, self.q_atom, self.consts, w=w, energy=False, grad=False, want_pot=True)
+        return o["hw"], coulomb_charge_grad(o["potw"], self.slot, self.n_slots) * float(self.consts.conversion)
 
 
 # ----------------------------------------------------------------------------- Stillinger-Weber term (K23)
@@ -707,32 +724,13 @@ def sw_eval(ell, xyz, consts, theta=None, w=None, energy=True, grad=True, into=N
     d u_i / d(epsilon, sigma, lam), with `w` their directional derivatives pthw [N, 3] -- what sw_theta_sum reduces.  The list
     may have been searched with any radius >= a sigma (a skin, a kept cutoff): the kernel applies r < a sigma per pair."""
     lib = _lib.load()
-    require_gpu(xyz, "xyz")
     N = ell.n_atoms
-    if xyz.shape != (N, 3):
-        raise ValueError("mdgrad_amd: xyz must be [%d, 3] (got %s)" % (N, tuple(xyz.shape)))
-    if theta is not None:
-        require_gpu(theta, "theta")
-        if theta.shape != (3,) or not theta.is_contiguous():
-            raise ValueError("mdgrad_amd: theta must be a contiguous [3] tensor (got %s)" % (tuple(theta.shape),))
-    xyz = xyz.contiguous()
-    dev = xyz.device
-    acc = into is not None
-    e = torch.empty(1, device=dev) if energy else None
-    g = (into[0] if acc else torch.empty(N, 3, device=dev)) if grad else None
-    hw = pth = pthw = None
-    if w is not None:
-        require_gpu(w, "w")
-        w = w.contiguous()
-        hw = into[1] if acc else torch.empty(N, 3, device=dev)
-        pthw = torch.empty(N, 3, device=dev) if want_theta else None
-    elif want_theta:
-        pth = torch.empty(N, 3, device=dev)
-    partial = torch.empty(int(lib.mdg_sw_partial_size(N)), device=dev) if energy else None
-    recheck = bool(getattr(ell, "verlet", False))
+    _check_theta(theta)
+    xyz, w, e, g, hw, pth, pthw, acc = _eval_prologue(N, xyz, w, energy, grad, into, want_theta, (N, 3))
+    partial = torch.empty(int(lib.mdg_sw_partial_size(N)), device=xyz.device) if energy else None
     check(lib.mdg_sw_eval(ptr(xyz), N, C.byref(ell.cell_struct), ptr(ell.col), ptr(ell.shift), ptr(ell.cnt), ell.max_nbr,
                           C.byref(consts), ptr(theta), ptr(w), ptr(e), ptr(g), ptr(hw), ptr(pth), ptr(pthw), ptr(partial),
-                          float(scale), int(acc) | (2 if recheck else 0), stream_ptr(dev)), "mdg_sw_eval")
+                          float(scale), _list_flags(acc, ell), stream_ptr(xyz.device)), "mdg_sw_eval")
     return dict(energy=e, grad=g, hw=hw, pth=pth, pthw=pthw)
 
 
@@ -753,65 +751,25 @@ def sw_theta_sum(per_atom, alpha=1.0):
     return out.flat
 
 
-class SWSpec:
-    """What the autograd functions below need beside the tensors: the list, the constants and the device buffer
+class SWTerm:
+    """The Stillinger-Weber term (csrc/sw.hip) for TermEnergyFn: the list, the constants and the device buffer
     (epsilon, sigma, lam), kept current by StillingerWeber."""
+
+    noun = "dU/d(epsilon, sigma, lam) of the Stillinger-Weber term"
 
     def __init__(self, ell, consts, theta):
         self.ell, self.consts, self.theta = ell, consts, theta
 
+    def _eval(self, xyz, **kw):
+        return sw_eval(self.ell, xyz, self.consts, self.theta, **kw)
 
-def _sw_first_order(spec, xyz, energy):
-    o = sw_eval(spec.ell, xyz, spec.consts, spec.theta, energy=energy, grad=True, want_theta=True)
-    return o["energy"], o["grad"], sw_theta_sum(o["pth"])
+    def first_order(self, xyz, energy):
+        o = self._eval(xyz, energy=energy, grad=True, want_theta=True)
+        return o["energy"], o["grad"], sw_theta_sum(o["pth"])
 
-
-class SWGradFn(torch.autograd.Function):
-    """(dU/dx, dU/d(epsilon, sigma, lam)) as a differentiable op; backward = the Hessian-vector product and the mixed
-    derivative d(w.dU/dx)/d(epsilon, sigma, lam) (the second autograd pass of torchmd/sovlers.py:229-233).  A cotangent on
-    the parameter gradient is not provided."""
-
-    @staticmethod
-    def forward(ctx, xyz, eps, sigma, lam, spec, cache):
-        ctx.spec = spec
-        ctx.shapes = (eps.shape, sigma.shape, lam.shape)
-        ctx.save_for_backward(xyz)
-        ctx.set_materialize_grads(False)
-        if cache is None:
-            cache = _sw_first_order(spec, xyz, energy=False)[1:]
-        return cache
-
-    @staticmethod
-    def backward(ctx, wg, wth):
-        (xyz,) = ctx.saved_tensors
-        s = ctx.spec
-        if wth is not None:
-            raise NotImplementedError("mdgrad_amd: derivatives of dU/d(epsilon, sigma, lam) of the Stillinger-Weber term (a "
-                                      "cotangent on it) are not provided by the HIP kernels")
-        if wg is None:
-            return None, None, None, None, None, None
-        o = sw_eval(s.ell, xyz, s.consts, s.theta, w=wg.detach().contiguous(), energy=False, grad=False, want_theta=True)
-        gw = sw_theta_sum(o["pthw"])
-        return (o["hw"],) + tuple(gw[k].reshape(sh) for k, sh in enumerate(ctx.shapes)) + (None, None)
-
-
-class SWEnergyFn(torch.autograd.Function):
-    """U(x, epsilon, sigma, lam) of the Stillinger-Weber term (csrc/sw.hip), differentiable twice in x and once in the three
-    parameters."""
-
-    @staticmethod
-    def forward(ctx, xyz, eps, sigma, lam, spec):
-        e, g, gth = _sw_first_order(spec, xyz, energy=True)
-        ctx.spec, ctx.cache = spec, (g, gth)
-        ctx.shapes = (eps.shape, sigma.shape, lam.shape)
-        ctx.save_for_backward(xyz, eps, sigma, lam)
-        return e.reshape(())
-
-    @staticmethod
-    def backward(ctx, gU):
-        xyz, eps, sigma, lam = ctx.saved_tensors
-        g, gth = SWGradFn.apply(xyz, eps, sigma, lam, ctx.spec, ctx.cache)
-        return (gU * g,) + tuple((gU * gth[k]).reshape(sh) for k, sh in enumerate(ctx.shapes)) + (None,)
+    def second_order(self, xyz, w):
+        o = self._eval(xyz, w=w, energy=False, grad=False, want_theta=True)
+        return o["hw"], sw_theta_sum(o["pthw"])
 
 
 # ----------------------------------------------------------------------------- Sutton-Chen embedded-atom term (K24)
@@ -846,103 +804,36 @@ def eam_eval(ell, xyz, consts, theta=None, w=None, energy=True, grad=True, into=
     of the caller, so that a captured graph sees a fixed address); allocated here when None.  The list may have been searched
     with any radius >= rc (a skin): the kernels apply r < rc per pair."""
     lib = _lib.load()
-    require_gpu(xyz, "xyz")
-    N = ell.n_atoms
-    if xyz.shape != (N, 3):
-        raise ValueError("mdgrad_amd: xyz must be [%d, 3] (got %s)" % (N, tuple(xyz.shape)))
-    if theta is not None:
-        require_gpu(theta, "theta")
-        if theta.shape != (3,) or not theta.is_contiguous():
-            raise ValueError("mdgrad_amd: theta must be a contiguous [3] tensor (got %s)" % (tuple(theta.shape),))
-    xyz = xyz.contiguous()
-    dev = xyz.device
+    N, dev = ell.n_atoms, xyz.device
+    _check_theta(theta)
     if work is None:
         work = torch.empty(N, 4, device=dev)
     else:
         require_gpu(work, "work")
         if work.shape != (N, 4) or not work.is_contiguous():
             raise ValueError("mdgrad_amd: work must be a contiguous [%d, 4] tensor (got %s)" % (N, tuple(work.shape)))
-    acc = into is not None
-    e = torch.empty(1, device=dev) if energy else None
-    g = (into[0] if acc else torch.empty(N, 3, device=dev)) if grad else None
-    hw = pth = pthw = None
-    if w is not None:
-        require_gpu(w, "w")
-        w = w.contiguous()
-        hw = into[1] if acc else torch.empty(N, 3, device=dev)
-        pthw = torch.empty(N, 3, device=dev) if want_theta else None
-    elif want_theta:
-        pth = torch.empty(N, 3, device=dev)
+    xyz, w, e, g, hw, pth, pthw, acc = _eval_prologue(N, xyz, w, energy, grad, into, want_theta, (N, 3))
     partial = torch.empty(int(lib.mdg_eam_partial_size(N)), device=dev) if energy else None
-    recheck = bool(getattr(ell, "verlet", False))
     check(lib.mdg_eam_eval(ptr(xyz), N, C.byref(ell.cell_struct), ptr(ell.col), ptr(ell.shift), ptr(ell.cnt), ell.max_nbr,
                            C.byref(consts), ptr(theta), ptr(w), ptr(e), ptr(g), ptr(hw), ptr(pth), ptr(pthw), ptr(partial),
-                           ptr(work), float(scale), int(acc) | (2 if recheck else 0), stream_ptr(dev)), "mdg_eam_eval")
+                           ptr(work), float(scale), _list_flags(acc, ell), stream_ptr(dev)), "mdg_eam_eval")
     return dict(energy=e, grad=g, hw=hw, pth=pth, pthw=pthw)
 
 
 eam_theta_sum = sw_theta_sum          # the same fixed-order column sums of a per-atom [N, 3] table (mdg_grad_jobs)
 
 
-class EAMSpec:
-    """What the autograd functions below need beside the tensors: the list, the constants, the device buffer (epsilon, a, c)
-    and the scratch of the density pass, kept current by SuttonChen."""
+class EAMTerm(SWTerm):
+    """The Sutton-Chen term (csrc/eam.hip) for TermEnergyFn: the list, the constants, the device buffer (epsilon, a, c) and
+    the scratch of the density pass, kept current by SuttonChen; the two evaluations are SWTerm's."""
+
+    noun = "dU/d(epsilon, a, c) of the Sutton-Chen term"
 
     def __init__(self, ell, consts, theta, work=None):
         self.ell, self.consts, self.theta, self.work = ell, consts, theta, work
 
-
-def _eam_first_order(spec, xyz, energy):
-    o = eam_eval(spec.ell, xyz, spec.consts, spec.theta, energy=energy, grad=True, want_theta=True, work=spec.work)
-    return o["energy"], o["grad"], eam_theta_sum(o["pth"])
-
-
-class EAMGradFn(torch.autograd.Function):
-    """(dU/dx, dU/d(epsilon, a, c)) as a differentiable op; backward = the Hessian-vector product and the mixed derivative
-    d(w.dU/dx)/d(epsilon, a, c).  A cotangent on the parameter gradient is not provided."""
-
-    @staticmethod
-    def forward(ctx, xyz, eps, a, c, spec, cache):
-        ctx.spec = spec
-        ctx.shapes = (eps.shape, a.shape, c.shape)
-        ctx.save_for_backward(xyz)
-        ctx.set_materialize_grads(False)
-        if cache is None:
-            cache = _eam_first_order(spec, xyz, energy=False)[1:]
-        return cache
-
-    @staticmethod
-    def backward(ctx, wg, wth):
-        (xyz,) = ctx.saved_tensors
-        s = ctx.spec
-        if wth is not None:
-            raise NotImplementedError("mdgrad_amd: derivatives of dU/d(epsilon, a, c) of the Sutton-Chen term (a cotangent on "
-                                      "it) are not provided by the HIP kernels")
-        if wg is None:
-            return None, None, None, None, None, None
-        o = eam_eval(s.ell, xyz, s.consts, s.theta, w=wg.detach().contiguous(), energy=False, grad=False, want_theta=True,
-                     work=s.work)
-        gw = eam_theta_sum(o["pthw"])
-        return (o["hw"],) + tuple(gw[k].reshape(sh) for k, sh in enumerate(ctx.shapes)) + (None, None)
-
-
-class EAMEnergyFn(torch.autograd.Function):
-    """U(x, epsilon, a, c) of the Sutton-Chen term (csrc/eam.hip), differentiable twice in x and once in the three
-    parameters."""
-
-    @staticmethod
-    def forward(ctx, xyz, eps, a, c, spec):
-        e, g, gth = _eam_first_order(spec, xyz, energy=True)
-        ctx.spec, ctx.cache = spec, (g, gth)
-        ctx.shapes = (eps.shape, a.shape, c.shape)
-        ctx.save_for_backward(xyz, eps, a, c)
-        return e.reshape(())
-
-    @staticmethod
-    def backward(ctx, gU):
-        xyz, eps, a, c = ctx.saved_tensors
-        g, gth = EAMGradFn.apply(xyz, eps, a, c, ctx.spec, ctx.cache)
-        return (gU * g,) + tuple((gU * gth[k]).reshape(sh) for k, sh in enumerate(ctx.shapes)) + (None,)
+    def _eval(self, xyz, **kw):
+        return eam_eval(self.ell, xyz, self.consts, self.theta, work=self.work, **kw)
 
 
 # ----------------------------------------------------------------------------- Ewald reciprocal-space sum (K21)
@@ -1013,28 +904,9 @@ def ewald_eval(table, xyz, q_atom, w=None, energy=True, grad=True, into=None, sc
     `w` hw = scale H w; want_pot: pot_i = conversion sum_k 2 c (A c_i + B s_i) without `w`, potw_i = d(w.dU/dx)/dq_i with it.
     `into` = (grad buffer, hw buffer or None): grad / hw are ADDED onto them."""
     lib = _lib.load()
-    require_gpu(xyz, "xyz")
-    require_gpu(q_atom, "q_atom")
     N = table.n_rep * table.n_atoms
-    if xyz.shape != (N, 3):
-        raise ValueError("mdgrad_amd: xyz must be [%d, 3] (got %s)" % (N, tuple(xyz.shape)))
-    if q_atom.shape != (N,):
-        raise ValueError("mdgrad_amd: q_atom must be [%d] (got %s)" % (N, tuple(q_atom.shape)))
-    xyz = xyz.contiguous()
+    xyz, w, e, g, hw, pot, potw, acc = _eval_prologue(N, xyz, w, energy, grad, into, want_pot, (N,), q_atom)
     dev = xyz.device
-    acc = into is not None
-    e = torch.empty(1, device=dev) if energy else None
-    g = (into[0] if acc else torch.empty(N, 3, device=dev)) if grad else None
-    hw = pot = potw = None
-    if w is not None:
-        require_gpu(w, "w")
-        if w.shape != (N, 3):
-            raise ValueError("mdgrad_amd: w must be [%d, 3] (got %s)" % (N, tuple(w.shape)))
-        w = w.contiguous()
-        hw = into[1] if acc else torch.empty(N, 3, device=dev)
-        potw = torch.empty(N, device=dev) if want_pot else None
-    elif want_pot:
-        pot = torch.empty(N, device=dev)
     ws = torch.empty(int(lib.mdg_ewald_workspace(table.n_rep, table.n_atoms, table.n_vecs)), device=dev)
     check(lib.mdg_ewald_eval(ptr(xyz), table.n_rep, table.n_atoms, C.byref(table.cell_struct), ptr(q_atom), ptr(table.kvec),
                              ptr(table.coef), table.n_vecs, ptr(w), ptr(e), ptr(g), ptr(hw), ptr(pot), ptr(potw), ptr(ws),
@@ -1042,66 +914,26 @@ def ewald_eval(table, xyz, q_atom, w=None, energy=True, grad=True, into=None, sc
     return dict(energy=e, grad=g, hw=hw, pot=pot, potw=potw)
 
 
-class EwaldSpec:
-    """What the autograd functions below need beside the tensors: the table, the per-atom charge buffer and the charge slots
-    (those of the real-space CoulombPotentials the term belongs to)."""
+class EwaldTerm:
+    """The Ewald reciprocal sum with its neutralising background (csrc/ewald.hip) for TermEnergyFn: the table, the per-atom
+    charge buffer and the charge slots (those of the real-space CoulombPotentials the term belongs to)."""
+
+    noun = "dU/dcharges of the Ewald reciprocal term"
 
     def __init__(self, table, q_atom, slot, n_slots):
         self.table, self.q_atom, self.slot, self.n_slots = table, q_atom, slot, int(n_slots)
 
+    def first_order(self, xyz, energy):
+        t = self.table
+        o = ewald_eval(t, xyz, self.q_atom, energy=energy, grad=True, want_pot=True)
+        Q = self.q_atom.reshape(t.n_rep, t.n_atoms).sum(1)                                   # net charge of every replica
+        dq_atom = o["pot"] - t.background * Q.repeat_interleave(t.n_atoms)                   # dU/dq_i
+        e = o["energy"] - (0.5 * t.background) * Q.pow(2).sum() if energy else None
+        return e, o["grad"], coulomb_charge_grad(dq_atom, self.slot, self.n_slots)
 
-class EwaldGradFn(torch.autograd.Function):
-    """(dU/dx, dU/dcharges) of the reciprocal sum as a differentiable op; backward = the Hessian-vector product and the mixed
-    derivative d(w.dU/dx)/dcharges.  A cotangent on dU/dcharges is not provided."""
-
-    @staticmethod
-    def forward(ctx, xyz, charges, spec, cache):
-        ctx.spec = spec
-        ctx.save_for_backward(xyz, charges)
-        ctx.set_materialize_grads(False)
-        if cache is None:
-            cache = _ewald_first_order(spec, xyz, charges, energy=False)[1:]
-        return cache
-
-    @staticmethod
-    def backward(ctx, wg, wq):
-        xyz, charges = ctx.saved_tensors
-        s = ctx.spec
-        if wq is not None:
-            raise NotImplementedError("mdgrad_amd: derivatives of dU/dcharges of the Ewald reciprocal term (a cotangent on it) "
-                                      "are not provided by the HIP kernels")
-        if wg is None:
-            return None, None, None, None
-        o = ewald_eval(s.table, xyz, s.q_atom, w=wg.detach().contiguous(), energy=False, grad=False, want_pot=True)
-        gq = coulomb_charge_grad(o["potw"], s.slot, s.n_slots)
-        return o["hw"], gq.reshape(charges.shape), None, None
-
-
-def _ewald_first_order(spec, xyz, charges, energy):
-    t = spec.table
-    o = ewald_eval(t, xyz, spec.q_atom, energy=energy, grad=True, want_pot=True)
-    Q = spec.q_atom.reshape(t.n_rep, t.n_atoms).sum(1)                                   # net charge of every replica
-    dq_atom = o["pot"] - t.background * Q.repeat_interleave(t.n_atoms)                   # dU/dq_i
-    e = o["energy"] - (0.5 * t.background) * Q.pow(2).sum() if energy else None
-    return e, o["grad"], coulomb_charge_grad(dq_atom, spec.slot, spec.n_slots).reshape(charges.shape)
-
-
-class EwaldEnergyFn(torch.autograd.Function):
-    """U_rec(x, charges) of the Ewald reciprocal sum with its neutralising background (csrc/ewald.hip), differentiable twice
-    in x and once in the charges."""
-
-    @staticmethod
-    def forward(ctx, xyz, charges, spec):
-        e, g, gq = _ewald_first_order(spec, xyz, charges, energy=True)
-        ctx.spec, ctx.cache = spec, (g, gq)
-        ctx.save_for_backward(xyz, charges)
-        return e.reshape(())
-
-    @staticmethod
-    def backward(ctx, gU):
-        xyz, charges = ctx.saved_tensors
-        g, gq = EwaldGradFn.apply(xyz, charges, ctx.spec, ctx.cache)
-        return gU * g, gU * gq, None
+    def second_order(self, xyz, w):
+        o = ewald_eval(self.table, xyz, self.q_atom, w=w, energy=False, grad=False, want_pot=True)
+        return o["hw"], coulomb_charge_grad(o["potw"], self.slot, self.n_slots)
 
 
 # ----------------------------------------------------------------------------- Ewald correction for excluded pairs (K22)
@@ -1173,94 +1005,33 @@ def ewald_excl_eval(table, xyz, q_atom, w=None, energy=True, grad=True, into=Non
     rhat_ij.(w_i - w_j) do not (dU/dq_i = conversion pot_i).  `into` = (grad buffer, hw buffer or None): grad / hw are ADDED
     onto them, times `scale`; atoms without an excluded pair leave them untouched."""
     lib = _lib.load()
-    require_gpu(xyz, "xyz")
-    require_gpu(q_atom, "q_atom")
     N = table.n_rep * table.n_atoms
-    if xyz.shape != (N, 3):
-        raise ValueError("mdgrad_amd: xyz must be [%d, 3] (got %s)" % (N, tuple(xyz.shape)))
-    if q_atom.shape != (N,):
-        raise ValueError("mdgrad_amd: q_atom must be [%d] (got %s)" % (N, tuple(q_atom.shape)))
-    xyz = xyz.contiguous()
+    xyz, w, e, g, hw, pot, potw, acc = _eval_prologue(N, xyz, w, energy, grad, into, want_pot, (N,), q_atom)
     dev = xyz.device
-    acc = into is not None
-    e = torch.empty(1, device=dev) if energy else None
-    g = (into[0] if acc else torch.empty(N, 3, device=dev)) if grad else None
-    hw = pot = potw = None
-    if w is not None:
-        require_gpu(w, "w")
-        if w.shape != (N, 3):
-            raise ValueError("mdgrad_amd: w must be [%d, 3] (got %s)" % (N, tuple(w.shape)))
-        w = w.contiguous()
-        hw = into[1] if acc else torch.empty(N, 3, device=dev)
-        potw = torch.empty(N, device=dev) if want_pot else None
-    elif want_pot:
-        pot = torch.empty(N, device=dev)
     partial = None
     if energy:
         partial = torch.empty(int(lib.mdg_ewald_excl_partial_size(table.n_rep, table.n_atoms)), device=dev, dtype=torch.float64)
     check(lib.mdg_ewald_excl_eval(ptr(xyz), table.n_rep, table.n_atoms, table.cell_len, ptr(table.row_ptr), ptr(table.col),
-                                  ptr(table.scl), ptr(q_atom), table.alpha, table.conversion, ptr(w), ptr(e), ptr(g), ptr(hw), ptr(pot), ptr(potw), ptr(partial),
-                                  float(scale), int(acc), stream_ptr(dev)), "mdg_ewald_excl_eval")
+                                  ptr(table.scl), ptr(q_atom), table.alpha, table.conversion, ptr(w), ptr(e), ptr(g), ptr(hw),
+                                  ptr(pot), ptr(potw), ptr(partial), float(scale), int(acc), stream_ptr(dev)),
+          "mdg_ewald_excl_eval")
     return dict(energy=e, grad=g, hw=hw, pot=pot, potw=potw)
 
 
-class EwaldExclSpec:
-    """What the autograd functions below need beside the tensors: the table, the per-atom charge buffer and the charge slots
-    (those of the real-space CoulombPotentials the term belongs to)."""
+class EwaldExclTerm(EwaldTerm):
+    """The erf correction of excluded / scaled pairs (csrc/ewald_excl.hip) for TermEnergyFn; holds what EwaldTerm holds, with
+    an EwaldExclTable."""
 
-    def __init__(self, table, q_atom, slot, n_slots):
-        self.table, self.q_atom, self.slot, self.n_slots = table, q_atom, slot, int(n_slots)
+    noun = "dU/dcharges of the Ewald exclusion term"
 
+    def first_order(self, xyz, energy):
+        o = ewald_excl_eval(self.table, xyz, self.q_atom, energy=energy, grad=True, want_pot=True)
+        gq = coulomb_charge_grad(o["pot"], self.slot, self.n_slots) * self.table.conversion            # dU/dq_i = conversion pot_i
+        return o["energy"], o["grad"], gq
 
-class EwaldExclGradFn(torch.autograd.Function):
-    """(dU/dx, dU/dcharges) of the excluded-pair correction as a differentiable op; backward = the Hessian-vector product and
-    the mixed derivative d(w.dU/dx)/dcharges.  A cotangent on dU/dcharges is not provided."""
-
-    @staticmethod
-    def forward(ctx, xyz, charges, spec, cache):
-        ctx.spec = spec
-        ctx.save_for_backward(xyz, charges)
-        ctx.set_materialize_grads(False)
-        if cache is None:
-            cache = _ewald_excl_first_order(spec, xyz, charges, energy=False)[1:]
-        return cache
-
-    @staticmethod
-    def backward(ctx, wg, wq):
-        xyz, charges = ctx.saved_tensors
-        s = ctx.spec
-        if wq is not None:
-            raise NotImplementedError("mdgrad_amd: derivatives of dU/dcharges of the Ewald exclusion term (a cotangent on it) "
-                                      "are not provided by the HIP kernels")
-        if wg is None:
-            return None, None, None, None
-        o = ewald_excl_eval(s.table, xyz, s.q_atom, w=wg.detach().contiguous(), energy=False, grad=False, want_pot=True)
-        gq = coulomb_charge_grad(o["potw"], s.slot, s.n_slots) * s.table.conversion
-        return o["hw"], gq.reshape(charges.shape), None, None
-
-
-def _ewald_excl_first_order(spec, xyz, charges, energy):
-    o = ewald_excl_eval(spec.table, xyz, spec.q_atom, energy=energy, grad=True, want_pot=True)
-    gq = coulomb_charge_grad(o["pot"], spec.slot, spec.n_slots) * spec.table.conversion            # dU/dq_i = conversion pot_i
-    return o["energy"], o["grad"], gq.reshape(charges.shape)
-
-
-class EwaldExclEnergyFn(torch.autograd.Function):
-    """U_excl(x, charges) of the excluded-pair correction (csrc/ewald_excl.hip), differentiable twice in x and once in the
-    charges."""
-
-    @staticmethod
-    def forward(ctx, xyz, charges, spec):
-        e, g, gq = _ewald_excl_first_order(spec, xyz, charges, energy=True)
-        ctx.spec, ctx.cache = spec, (g, gq)
-        ctx.save_for_backward(xyz, charges)
-        return e.reshape(())
-
-    @staticmethod
-    def backward(ctx, gU):
-        xyz, charges = ctx.saved_tensors
-        g, gq = EwaldExclGradFn.apply(xyz, charges, ctx.spec, ctx.cache)
-        return gU * g, gU * gq, None
+    def second_order(self, xyz, w):
+        o = ewald_excl_eval(self.table, xyz, self.q_atom, w=w, energy=False, grad=False, want_pot=True)
+        return o["hw"], coulomb_charge_grad(o["potw"], self.slot, self.n_slots) * self.table.conversion
 
 
 # ----------------------------------------------------------------------------- fused trajectories

@@ -33,7 +33,7 @@ def _rel(a, b):
 def test_term_kernel_energy_force_hvp_and_parameter_gradients_golden():
     """One launch of mdg_dihedral_eval on the wrapped chain: U, F = -dU/dx, d(w.F)/dx = -H w and d(w.F)/dA against the
     reference (D2: autograd and double autograd of the polynomial on compute_dihe, float64); the same through autograd
-    (DihedralEnergyFn -> DihedralGradFn) with dU/dA, added onto another member's buffers, and bitwise reproducible."""
+    (TermEnergyFn -> TermGradFn on ops.DihedralTerm) with dU/dA, added onto another member's buffers, and bitwise reproducible."""
     from mdgrad_amd import ops
     from mdgrad_amd.interface import DihedralPotentials
     g, wrapped, L = _wrapped_d2()

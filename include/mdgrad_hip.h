@@ -1181,6 +1181,45 @@ int mdg_eam_eval(const float* pos, int n_atoms, const MdgCell* cell /*host*/, co
                  float out_scale, int accumulate, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * K25  Tersoff bond-order potential for one species over the per-atom (ELL) list (Tersoff 1988, 1989; the LAMMPS convention;
+ *      mdgrad_amd/interface.py Tersoff, csrc/tersoff.hip):
+ *        U       = 1/2 sum_i sum_{j in row(i)} fc(r_ij) [A exp(-lam1 r_ij) - b_ij B exp(-lam2 r_ij)]
+ *        b_ij    = (1 + (beta zeta_ij)^n)^(-1/(2n))
+ *        zeta_ij = sum_{k in row(i), k != j} fc(r_ik) g(cos theta_jik) exp[(lam3 (r_ij - r_ik))^m]
+ *        g(x)    = gamma (1 + c^2/d^2 - c^2/(d^2 + (h - x)^2)),  evaluated as gamma (1 + (c/d)^2 u^2 / (d^2 + u^2)), u = h - x
+ *        fc(r)   = 1 for r <= R - D,  1/2 - 1/2 sin(pi (r - R) / (2 D)) for R - D < r < R + D,  exactly 0 for r >= R + D
+ *      A bond with zeta_ij = 0 has b_ij = 1 and every derivative of b_ij exactly 0.
+ *      The list may have been searched with any radius >= R + D: every entry with r = sqrt(d2) >= R + D is skipped.  Rows are
+ *      not staged, so their length is not capped.
+ *      MdgTersoffConsts holds the constants and host copies of (A, B, h); `theta`, when not null, is a device float[3] =
+ *      (A, B, h) that the kernels read instead (trainable parameters under HIP-graph replay).  Without theta the host values
+ *      must satisfy A > 0, B > 0.  Always: lam1 > 0, lam2 > 0, D > 0, R > D, m = 1 or 3, n > 0, beta >= 0, d != 0.
+ *   mdg_tersoff_eval  argument for argument mdg_sw_eval (same list, same `accumulate` bits, same out_scale, same outputs) plus
+ *     bond_work, a caller-owned device scratch of mdg_tersoff_work_size(n_atoms, max_nbr) floats (4 per list slot), required
+ *     whenever grad or hw is requested: one call enqueues the bond pass, which writes (P, dP, b, db) of the bond in every slot
+ *     (P = dU/dzeta; dP, db = their directional derivatives along w, 0 without w), then, for grad / hw, the force pass, which
+ *     reads the entries of the atom's row and of its neighbours' rows, then the finish kernel of the energy.  Outputs, each
+ *     nullable:
+ *       energy [1] = U (needs `partial`, mdg_tersoff_partial_size() floats; fixed-order block partials + a finish kernel)
+ *       grad [n_atoms, 3] = (accumulate & 1 ? grad : 0) + out_scale dU/dx,  hw likewise with H w
+ *       pth [n_atoms, 3]  = d u_i / d(A, B, h) of u_i = 1/2 sum_{j in row(i)} fc (A exp(-lam1 r) - b_ij B exp(-lam2 r))
+ *                           (their sums over i are dU/d(A, B, h))
+ *       pthw [n_atoms, 3] = (w . grad_x) of the same three (their sums are d(w.dU/dx)/d(A, B, h))
+ *     H w and pthw come from both passes run over Dual numbers seeded with w (csrc/dual.hpp).  No atomics: bitwise
+ *     reproducible; the value parts of a launch with w equal those of a launch without, bit for bit.
+ */
+typedef struct MdgTersoffConsts {
+    double A, B, lam1, lam2, beta, n, c, d, h, R, D, lam3, gamma;
+    int32_t m, pad_;
+} MdgTersoffConsts;
+int64_t mdg_tersoff_partial_size(int n_atoms);
+int64_t mdg_tersoff_work_size(int n_atoms, int max_nbr);
+int mdg_tersoff_eval(const float* pos, int n_atoms, const MdgCell* cell /*host*/, const int32_t* col, const int32_t* shift,
+                     const int32_t* cnt, int max_nbr, const MdgTersoffConsts* consts /*host*/, const float* theta,
+                     const float* w, float* energy, float* grad, float* hw, float* pth, float* pthw, float* partial,
+                     float* bond_work, float out_scale, int accumulate, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * f4  bonded terms over a static topology table (csrc/bonded.hip).
  * Replaces torchmd/interface.py:447-455 (BondPotentials.forward: harmonic in the SQUARED bond length,
  * 1/2 k (|b|^2 - ro)^2) and :496-508 (AnglePotentials.forward: 1/2 k (theta - theta0)^2 over triples (i, j, k) centred on

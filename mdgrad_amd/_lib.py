@@ -77,6 +77,12 @@ class MdgEAMConsts(C.Structure):
                [(n, C.c_int32) for n in ("n", "m", "shift", "pad_")]
 
 
+class MdgTersoffConsts(C.Structure):
+    """Constants of the Tersoff term and host copies of (A, B, h) (include/mdgrad_hip.h K25)."""
+    _fields_ = [(n, C.c_double) for n in ("A", "B", "lam1", "lam2", "beta", "n", "c", "d", "h", "R", "D", "lam3", "gamma")] + \
+               [(n, C.c_int32) for n in ("m", "pad_")]
+
+
 class MdgChainStage(C.Structure):
     """One Dense stage of mdg_row_chain (include/mdgrad_hip.h)."""
     _fields_ = [(n, C.c_void_p) for n in ("W", "bias", "in0", "in1", "res0", "res1", "aux0", "aux1", "out0", "out1", "sig",
@@ -291,6 +297,10 @@ _SIGNATURES = {
     "mdg_eam_partial_size": (C.c_int64, [C.c_int]),
     "mdg_eam_eval": (C.c_int, [P, C.c_int, C.POINTER(MdgCell), P, P, P, C.c_int, C.POINTER(MdgEAMConsts), P, P,
                                P, P, P, P, P, P, P, C.c_float, C.c_int, P]),
+    "mdg_tersoff_partial_size": (C.c_int64, [C.c_int]),
+    "mdg_tersoff_work_size": (C.c_int64, [C.c_int, C.c_int]),
+    "mdg_tersoff_eval": (C.c_int, [P, C.c_int, C.POINTER(MdgCell), P, P, P, C.c_int, C.POINTER(MdgTersoffConsts), P, P,
+                                   P, P, P, P, P, P, P, C.c_float, C.c_int, P]),
     "mdg_ewald_workspace": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "mdg_ewald_eval": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), P, P, P, C.c_int, P, P, P, P, P, P, P, C.c_float,
                                  C.c_int, P]),

@@ -38,4 +38,19 @@ __device__ __forceinline__ Dual fexp_(Dual a) { return dexp(a); }
 __device__ __forceinline__ float val(float a) { return a; }
 __device__ __forceinline__ float val(Dual a) { return a.v; }
 
+// ---- what the bond-order term (csrc/tersoff.hip) adds: a constant added to a Dual, log, sin, cos, and x^p for x > 0 and a
+// real exponent p as exp(p log x), the same expression in float and in Dual so that the value parts round alike
+__device__ __forceinline__ Dual operator+(Dual a, float b) { return {a.v + b, a.d}; }
+__device__ __forceinline__ Dual dlog(Dual a) { return {logf(a.v), a.d / a.v}; }
+__device__ __forceinline__ Dual dsin(Dual a) { return {sinf(a.v), cosf(a.v) * a.d}; }
+__device__ __forceinline__ Dual dcos(Dual a) { return {cosf(a.v), -(sinf(a.v) * a.d)}; }
+__device__ __forceinline__ float flog_(float a) { return logf(a); }
+__device__ __forceinline__ Dual flog_(Dual a) { return dlog(a); }
+__device__ __forceinline__ float fsin_(float a) { return sinf(a); }
+__device__ __forceinline__ Dual fsin_(Dual a) { return dsin(a); }
+__device__ __forceinline__ float fcos_(float a) { return cosf(a); }
+__device__ __forceinline__ Dual fcos_(Dual a) { return dcos(a); }
+__device__ __forceinline__ float fpow_(float x, float p) { return fexp_(p * flog_(x)); }
+__device__ __forceinline__ Dual fpow_(Dual x, float p) { return fexp_(p * flog_(x)); }
+
 }  // namespace

@@ -22,6 +22,7 @@
 //   ewald_excl_eval  K22  interface.py EwaldExclusions      -> mdg_ewald_excl_eval
 //   sw_eval          K23  interface.py StillingerWeber      -> mdg_sw_eval
 //   eam_eval         K24  interface.py SuttonChen           -> mdg_eam_eval
+//   tersoff_eval     K25  interface.py Tersoff              -> mdg_tersoff_eval
 //   dihedral_phi_fwd/_bwd, dihedral_hist_fwd/_bwd  K19  observable.py Dihedrals / dihedral_distribution -> mdg_dihedral_phi_* / _hist_*
 //   edge_geom(+_bwd) schnet.py:142                          -> mdg_edge_geom / mdg_edge_geom_bwd
 //   cfconv_fwd/_bwd  K9+K10 modules.py:531-571              -> mdg_cfconv_fwd(_bf16) / mdg_cfconv_bwd(_bf16)
@@ -877,6 +878,39 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> eam_eval(const Tensor& pos, a
     return {U, g, hw, pth, pthw};
 }
 
+// ------------------------------------------------------------------------------------------------ K25
+// consts = (A, B, lam1, lam2, beta, n, c, d, h, R, D, lam3, gamma, m) of MdgTersoffConsts; theta: device (A, B, h) read by the
+// kernels instead of the host copies.  (U [1] or [0], dU/dx [N,3], H w [N,3] or [0], pth [N,3] or [0], pthw [N,3] or [0]);
+// want_theta: pth without w, pthw with it.  The scratch of the bond pass is allocated here.
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> tersoff_eval(const Tensor& pos, at::ArrayRef<double> cell, const Tensor& col,
+                                                                const Tensor& shift, const Tensor& cnt,
+                                                                at::ArrayRef<double> consts, const OptTensor& theta,
+                                                                const OptTensor& w, bool want_energy, bool want_theta) {
+    check_f32(pos, "pos");
+    TORCH_CHECK(pos.dim() == 2 && pos.size(1) == 3 && pos.size(0) > 0 && pos.size(0) <= INT32_MAX, "mdgrad: pos must be [N,3]");
+    TORCH_CHECK(consts.size() == 14, "mdgrad: consts = (A, B, lam1, lam2, beta, n, c, d, h, R, D, lam3, gamma, m)");
+    const MdgCell c = make_cell(cell);
+    const EllRef e = ell_of(pos, col, shift, cnt);
+    const MdgTersoffConsts k{consts[0], consts[1], consts[2], consts[3], consts[4], consts[5], consts[6], consts[7], consts[8],
+                             consts[9], consts[10], consts[11], consts[12], (int32_t)consts[13], 0};
+    TORCH_CHECK((double)k.m == consts[13], "mdgrad: the exponent m must be an integer");
+    const float* tp = fptr(theta, "theta");
+    if (tp) { same_device(pos, *theta, "theta"); TORCH_CHECK(theta->numel() == 3, "mdgrad: theta must be (A, B, h)"); }
+    const float* wp = fptr(w, "w");
+    if (wp) { same_device(pos, *w, "w"); TORCH_CHECK(w->sizes() == pos.sizes(), "mdgrad: w must have the shape of pos"); }
+    const int n = (int)pos.size(0);
+    const auto o = pos.options();
+    Tensor U = at::empty({want_energy ? 1 : 0}, o), g = at::empty_like(pos);
+    Tensor hw = wp ? at::empty_like(pos) : at::empty({0}, o);
+    Tensor pth = (want_theta && !wp) ? at::empty_like(pos) : at::empty({0}, o);
+    Tensor pthw = (want_theta && wp) ? at::empty_like(pos) : at::empty({0}, o);
+    Tensor partial = at::empty({mdg_tersoff_partial_size(n)}, o), work = at::empty({mdg_tersoff_work_size(n, e.max_nbr)}, o);
+    ok(mdg_tersoff_eval(fptr(pos), n, &c, e.col, e.shift, e.cnt, e.max_nbr, &k, tp, wp, want_energy ? mptr(U) : nullptr, mptr(g),
+                        wp ? mptr(hw) : nullptr, (want_theta && !wp) ? mptr(pth) : nullptr,
+                        (want_theta && wp) ? mptr(pthw) : nullptr, mptr(partial), mptr(work), 1.f, 0, stream_of(pos)));
+    return {U, g, hw, pth, pthw};
+}
+
 // ------------------------------------------------------------------------------------------------ K22
 // pos [R n, 3], q float [R n], cell_len = the three diagonal lengths; row_ptr int32 [n + 1], col int32 [nnz], scale float [nnz]:
 // the CSR incidence list of ops.EwaldExclTable (checked here with device reads: the kernel indexes pos with col).
@@ -962,6 +996,8 @@ TORCH_LIBRARY(mdgrad, m) {
           "bool want_energy, bool want_theta) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("eam_eval(Tensor pos, float[] cell, Tensor col, Tensor shift, Tensor cnt, float[] consts, Tensor? theta, Tensor? w, "
           "bool want_energy, bool want_theta) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
+    m.def("tersoff_eval(Tensor pos, float[] cell, Tensor col, Tensor shift, Tensor cnt, float[] consts, Tensor? theta, Tensor? w, "
+          "bool want_energy, bool want_theta) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("ewald_eval(Tensor pos, int n_rep, float[] cell, Tensor q, Tensor kvec, Tensor coef, Tensor? w, bool want_energy, "
           "bool want_pot) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("ewald_excl_eval(Tensor pos, int n_rep, float[] cell_len, Tensor row_ptr, Tensor col, Tensor scale, Tensor q, float alpha, "
@@ -1007,6 +1043,7 @@ TORCH_LIBRARY_IMPL(mdgrad, CUDA, m) {      // (the HIP backend registers under t
     m.impl("coulomb_charge_reduce", coulomb_charge_reduce);
     m.impl("sw_eval", sw_eval);
     m.impl("eam_eval", eam_eval);
+    m.impl("tersoff_eval", tersoff_eval);
     m.impl("ewald_eval", ewald_eval);
     m.impl("ewald_excl_eval", ewald_excl_eval);
     m.impl("edge_geom", edge_geom);

@@ -1,6 +1,6 @@
 """Energy calculators with the reference's interface (torchmd/interface.py):
 GeneralInteraction :33-57, PairPotentials :217-300, Electrostatics :303-361 (as CoulombPotentials), Stack :364-403;
-StillingerWeber (three-body, no counterpart in the reference), SuttonChen (embedded-atom, no counterpart in the reference)
+StillingerWeber (three-body), SuttonChen (embedded-atom), Tersoff (bond-order) -- none of the three has a counterpart in the reference
 (GNNPotentials lives in mdgrad_amd.nn).  forward(xyz) -> energy; _reset_topology(xyz) rebuilds the neighbour list.
 """
 import inspect
@@ -1305,6 +1305,172 @@ class SuttonChen(_ListTerm):
         need = bool(want_theta) and any(isinstance(p, torch.nn.Parameter) for p in self._thetas())
         o = ops.eam_eval(self._ell, xyz.detach(), self._consts, self._theta(), w=w.detach(), energy=False, grad=True,
                          into=into, scale=-1.0, want_theta=need, work=self._scratch(xyz))
+        return o["grad"], o["hw"], _theta3_tail(o["pthw"], self._thetas(), want_theta, accum)
+
+
+class Tersoff(_ListTerm):
+    """Tersoff bond-order potential for one species (Tersoff 1988 for silicon, 1989 for carbon; the LAMMPS convention): the
+    strength of a bond depends on the bond's environment, so silicon, carbon, germanium and their amorphous or defective
+    networks are described without a hard-wired tetrahedral angle.
+
+        U       = 1/2 sum_i sum_{j != i} fc(r_ij) [ A exp(-lam1 r_ij) - b_ij B exp(-lam2 r_ij) ]
+        b_ij    = (1 + (beta zeta_ij)^n)^(-1/(2n))
+        zeta_ij = sum_{k != i, j} fc(r_ik) g(cos theta_jik) exp[ (lam3 (r_ij - r_ik))^m ]                 m = 1 or 3
+        g(x)    = gamma (1 + c^2/d^2 - c^2/(d^2 + (h - x)^2))
+        fc(r)   = 1 for r <= R - D;  1/2 - 1/2 sin(pi (r - R) / (2 D)) for R - D < r < R + D;  exactly 0 for r >= R + D
+
+    A bond with zeta_ij = 0 (no third atom inside the cutoff) has b_ij = 1, and every derivative of b_ij there is defined
+    as exactly 0.  A property of the model, whatever the implementation: for n < 1 (both published sets) db/dzeta diverges
+    as zeta -> 0, so the second derivative of U diverges as a third atom crosses R + D next to a bond that had none; in
+    condensed phases every bond keeps third atoms well inside the cutoff.
+
+    The cutoff is R + D, an absolute length that no parameter moves.  The pair set, the minimum image and the
+    (d2 < rc^2) & (d2 != 0) test are those of PairPotentials at that cutoff; the replicas of System.replicate never see
+    each other.  The kernels apply the support of fc per pair, so a list searched with a skin is exact.
+
+    `A`, `B` and `h` are one-element float32 parameters when trainable, otherwise buffers; everything else is a constant.
+    Not covered: `index_tuple`, `ex_pairs` (both rejected), several species (one parameter set for all atoms, no mixing
+    rules).  `silicon` and `carbon` carry the published constants (energies in eV, lengths in Angstrom).
+
+    forward(xyz) is differentiable twice in xyz and once in (A, B, h) on the HIP kernels (ops.TersoffTerm,
+    csrc/tersoff.hip: a bond pass that stores dU/dzeta per list slot, then a force pass that reads the neighbours' slots);
+    force / force_vjp serve the analytic adjoint and HIP-graph replay, also while the parameters require grad.  float64 or
+    host positions take the torch restatement `_torch_energy`, which keeps the published form of g."""
+
+    accepts_into = True
+    accepts_accum = True
+    analytic = True
+    PUBLISHED = {"silicon": dict(A=1830.8, B=471.18, lam1=2.4799, lam2=1.7322, beta=1.1e-6, n=0.78734, c=1.0039e5, d=16.217,
+                                 h=-0.59825, R=2.85, D=0.15),
+                 "carbon": dict(A=1393.6, B=346.74, lam1=3.4879, lam2=2.2119, beta=1.5724e-7, n=0.72751, c=38049.0, d=4.3484,
+                                h=-0.57058, R=1.95, D=0.15)}
+
+    def __init__(self, system, A, B, lam1, lam2, beta, n, c, d, h, R, D, lam3=0.0, m=3, gamma=1.0, trainable=True,
+                 index_tuple=None, ex_pairs=None):
+        super().__init__(system)
+        if index_tuple is not None or ex_pairs is not None:
+            raise ValueError("Tersoff: index_tuple and ex_pairs are not supported (one species, every pair)")
+        self._consts = ops.tersoff_consts(A, B, lam1, lam2, beta, n, c, d, h, R, D, lam3, m, gamma)
+        k = self._consts
+        self.cutoff = float(k.R + k.D)
+        cell = np.asarray(system.get_cell(), dtype=np.float64)
+        cell = np.diag(cell) if cell.ndim == 1 else cell
+        vol = abs(float(np.linalg.det(cell)))
+        self._half_height = 0.5 * min(vol / float(np.linalg.norm(np.cross(cell[(a + 1) % 3], cell[(a + 2) % 3]))) for a in range(3))
+        if self.cutoff > self._half_height:
+            raise ValueError("Tersoff: R + D = %g exceeds half the shortest cell height (%g)" % (self.cutoff, self._half_height))
+        for name, v in (("A", k.A), ("B", k.B), ("h", k.h)):
+            t = torch.tensor([v], dtype=torch.float32, device=self.device)
+            if trainable:
+                setattr(self, name, torch.nn.Parameter(t))
+            else:
+                self.register_buffer(name, t)
+        self.index_tuple, self.ex_pairs, self._mask = None, None, None
+        self._n_rep = system.get_number_of_atoms() // self._group
+        self._ell = None
+        self._theta_mirror = _DeviceMirror(self._thetas)
+        self._work = None
+        if torch.device(self.device).type == "cuda":
+            self._reset_topology(torch.Tensor(system.get_positions()).to(system.device))
+            self._scratch()
+            self._theta()
+
+    @classmethod
+    def silicon(cls, system, **kw):
+        """Tersoff's silicon (1988, Si(C)): A = 1830.8 eV, B = 471.18 eV, lam1 = 2.4799, lam2 = 1.7322 / Angstrom,
+        beta = 1.1e-6, n = 0.78734, c = 1.0039e5, d = 16.217, h = -0.59825, R = 2.85, D = 0.15 Angstrom."""
+        return cls(system, **dict(cls.PUBLISHED["silicon"], **kw))
+
+    @classmethod
+    def carbon(cls, system, **kw):
+        """Tersoff's carbon (1989): A = 1393.6 eV, B = 346.74 eV, lam1 = 3.4879, lam2 = 2.2119 / Angstrom, beta = 1.5724e-7,
+        n = 0.72751, c = 38049, d = 4.3484, h = -0.57058, R = 1.95, D = 0.15 Angstrom."""
+        return cls(system, **dict(cls.PUBLISHED["carbon"], **kw))
+
+    # -- the device copy of (A, B, h) the kernels read (the lists are _ListTerm's, those of PairPotentials) --------
+    def _thetas(self):
+        return self.A, self.B, self.h
+
+    def _theta(self):
+        """(A, B, h) as the kernels read them: their device mirror (_DeviceMirror), so that the captured steps carry no
+        host value of a parameter."""
+        return self._theta_mirror.get()
+
+    def prepare_pass(self):
+        if self._hip_ok():
+            self._theta()
+            self._scratch()
+
+    def _scratch(self):
+        """The scratch of the bond pass, four floats per slot of the current list: persistent, so that a captured graph
+        sees a fixed address (under static topology max_nbr is fixed); re-allocated when a rebuild made the list wider."""
+        need = ops.tersoff_work_size(self._ell)
+        if self._work is None or self._work.device != self._ell.col.device or self._work.numel() < need:
+            self._work = torch.empty(need, dtype=torch.float32, device=self._ell.col.device)
+        return self._work
+
+    # -- energy ----------------------------------------------------------------------------------------------------
+    def _torch_energy(self, xyz):
+        """The same energy in torch ops, in the dtype and on the device of xyz (differentiable by autograd in xyz and in
+        A, B, h), with g in its published form: every pair as two directed bonds, grouped by centre into a padded [N, K]
+        table, zeta as a sum over the [N, K, K] pairs of entries of one row."""
+        k = self._consts
+        A, B, h = (p.to(xyz).reshape(()) for p in (self.A, self.B, self.h))
+        i, j, off = self._all_pairs(xyz, self.cutoff)
+        if i.numel() == 0:
+            return xyz.sum() * 0.0
+        cell = self.cell.detach().to(xyz)
+        cell = torch.diag(cell) if cell.dim() == 1 else cell
+        dv = xyz[i] - xyz[j] - off.matmul(cell)
+        r = dv.pow(2).sum(-1).sqrt()
+        taper = 0.5 - 0.5 * torch.sin((0.5 * math.pi / k.D) * (r - k.R))
+        fc = torch.where(r <= k.R - k.D, torch.ones_like(r), torch.where(r < k.R + k.D, taper, torch.zeros_like(r)))
+        N = xyz.shape[0]
+        centre = torch.cat([i, j])
+        u, r2, fc2 = torch.cat([-dv, dv]) / torch.cat([r, r])[:, None], torch.cat([r, r]), torch.cat([fc, fc])
+        order = torch.argsort(centre, stable=True)
+        centre, u, r2, fc2 = centre[order], u[order], r2[order], fc2[order]
+        cnt = torch.bincount(centre, minlength=N)
+        K = int(cnt.max())
+        start = torch.cumsum(cnt, 0) - cnt
+        slot = torch.arange(centre.numel(), device=xyz.device) - start[centre]
+        U = xyz.new_zeros(N, K, 3).index_put((centre, slot), u)
+        Rr = xyz.new_ones(N, K).index_put((centre, slot), r2)
+        F = xyz.new_zeros(N, K).index_put((centre, slot), fc2)              # (padding: fc = 0, no bond and no third atom)
+        cos = (U[:, :, None, :] * U[:, None, :, :]).sum(-1)                  # [N, j, k]
+        g = k.gamma * (1.0 + k.c ** 2 / k.d ** 2 - k.c ** 2 / (k.d ** 2 + (h - cos) ** 2))
+        E = torch.exp((k.lam3 * (Rr[:, :, None] - Rr[:, None, :])) ** int(k.m)) if k.lam3 != 0.0 else torch.ones_like(cos)
+        other = 1.0 - torch.eye(K, dtype=xyz.dtype, device=xyz.device)
+        zeta = (F[:, None, :] * g * E * other).sum(-1)
+        bonded = zeta > 0                                     # zeta = 0: b = 1, and no 0 * inf in its derivatives
+        z = torch.where(bonded, zeta, torch.ones_like(zeta))
+        b = torch.where(bonded, (1.0 + (k.beta * z) ** k.n) ** (-0.5 / k.n), torch.ones_like(zeta))
+        return 0.5 * (F * (A * torch.exp(-k.lam1 * Rr) - b * B * torch.exp(-k.lam2 * Rr))).sum()
+
+    def forward(self, xyz):
+        if self._hip_ok(xyz):
+            term = ops.TersoffTerm(self._ell, self._consts, self._theta(), self._scratch())
+            return ops.TermEnergyFn.apply(xyz.contiguous(), term, *self._thetas())
+        return self._torch_energy(xyz)
+
+    # -- analytic-adjoint protocol (md._EOM.rhs_vjp, Stack.force / force_vjp) -------------------------------------
+    def supports_force_vjp(self):
+        return self._hip_ok()
+
+    def force(self, xyz, into=None):
+        """F = -dU/dx in one call (two kernels); `into` (a force buffer of another Stack member): added onto it in the
+        force pass and returned."""
+        o = ops.tersoff_eval(self._ell, xyz.detach(), self._consts, self._theta(), energy=False, grad=True,
+                             into=None if into is None else (into, None), scale=-1.0, work=self._scratch())
+        return o["grad"]
+
+    def force_vjp(self, xyz, w, want_theta=True, accum=None, into=None):
+        """(F, d(w.F)/dx, [d(w.F)/dA, d(w.F)/dB, d(w.F)/dh]) in one call plus the fixed-order reduction of the parameter
+        part; `accum` (ops.ThetaAccum): that part is added into its flat buffer instead (None returned).  `into` = (F, dq)
+        buffers of another Stack member: this term's force and d(w.F)/dx are added onto them in the force pass."""
+        need = bool(want_theta) and any(isinstance(p, torch.nn.Parameter) for p in self._thetas())
+        o = ops.tersoff_eval(self._ell, xyz.detach(), self._consts, self._theta(), w=w.detach(), energy=False, grad=True,
+                             into=into, scale=-1.0, want_theta=need, work=self._scratch())
         return o["grad"], o["hw"], _theta3_tail(o["pthw"], self._thetas(), want_theta, accum)
 
 

@@ -17,6 +17,7 @@ torch.autograd.Function wrappers that own the differentiation contract
       EwaldExclTerm                                             Ewald erf correction of excluded / scaled pairs, the same
       SWTerm                                                    Stillinger-Weber term, parameters: (epsilon, sigma, lam)
       EAMTerm                                                   Sutton-Chen term, parameters: (epsilon, a, c)
+      TersoffTerm                                               Tersoff bond-order term, parameters: (A, B, h)
     DihedralPhiFn, DihedralHistFn                               signed dihedral angles of every frame, their periodic histogram
 
 Everything here requires HIP tensors; there is no CPU path.
@@ -351,7 +352,7 @@ class BondedEnergyFn(torch.autograd.Function):
 
 
 # ----------------------------------------------------------------------------- terms with parameters: one autograd pair
-# Every term below (dihedral, Coulomb, Ewald, Ewald exclusions, Stillinger-Weber, Sutton-Chen) differentiates through this
+# Every term below (dihedral, Coulomb, Ewald, Ewald exclusions, Stillinger-Weber, Sutton-Chen, Tersoff) differentiates through this
 # pair.  PairGradFn / PairEnergyFn stay on their own (the empty-theta case, two C entry points), and so do BondedGradFn /
 # BondedEnergyFn (no parameters, ten lines).  A `term` holds what the two evaluations of its kernel family need and has
 #     first_order(xyz, energy) -> (U or None, dU/dx, packed)    packed: the flat dU/dparams, in the order of `params`
@@ -410,7 +411,7 @@ class TermEnergyFn(torch.autograd.Function):
 
 
 def _eval_prologue(N, xyz, w, energy, grad, into, want_aux, aux_shape, q_atom=None):
-    """The common opening of coulomb_eval, sw_eval, eam_eval, ewald_eval and ewald_excl_eval: the device and shape checks
+    """The common opening of coulomb_eval, sw_eval, eam_eval, tersoff_eval, ewald_eval and ewald_excl_eval: the device and shape checks
     and the outputs -- energy [1], grad / hw [N, 3] (the buffers of `into` when given) and the auxiliary per-atom output of
     `aux_shape` when wanted: without `w` the first-order one, with `w` its directional derivative.  Returns
     (xyz, w, e, g, hw, aux, aux_w, acc).  (bonded_eval and dihedral_eval have per-atom energies and no per-atom auxiliary
@@ -441,7 +442,7 @@ def _eval_prologue(N, xyz, w, energy, grad, into, want_aux, aux_shape, q_atom=No
 
 
 def _check_theta(theta):
-    """`theta`, when given, is the contiguous device float [3] the SW / EAM kernels read their three parameters from."""
+    """`theta`, when given, is the contiguous device float [3] the SW / EAM / Tersoff kernels read their three parameters from."""
     if theta is not None:
         require_gpu(theta, "theta")
         if theta.shape != (3,) or not theta.is_contiguous():
@@ -834,6 +835,68 @@ class EAMTerm(SWTerm):
 
     def _eval(self, xyz, **kw):
         return eam_eval(self.ell, xyz, self.consts, self.theta, work=self.work, **kw)
+
+
+# ----------------------------------------------------------------------------- Tersoff bond-order term (K25)
+def tersoff_consts(A, B, lam1, lam2, beta, n, c, d, h, R, D, lam3=0.0, m=3, gamma=1.0):
+    """MdgTersoffConsts: the constants of the Tersoff form and host copies of (A, B, h) -- the kernels read those three from a
+    device buffer instead when tersoff_eval is given one."""
+    A, B, lam1, lam2, beta, n, c, d, h, R, D, lam3, gamma = (float(v) for v in (A, B, lam1, lam2, beta, n, c, d, h, R, D, lam3, gamma))
+    if not (A > 0.0 and B > 0.0):
+        raise ValueError("mdgrad_amd: A and B must be positive (got %r, %r)" % (A, B))
+    if not (lam1 > 0.0 and lam2 > 0.0):
+        raise ValueError("mdgrad_amd: lam1 and lam2 must be positive (got %r, %r)" % (lam1, lam2))
+    if not (D > 0.0 and R > D):
+        raise ValueError("mdgrad_amd: the cutoff needs D > 0 and R > D (got R = %r, D = %r)" % (R, D))
+    if int(m) != m or int(m) not in (1, 3):
+        raise ValueError("mdgrad_amd: m must be 1 or 3 (got %r)" % (m,))
+    if not (n > 0.0 and beta >= 0.0):
+        raise ValueError("mdgrad_amd: n must be positive and beta >= 0 (got %r, %r)" % (n, beta))
+    if d == 0.0:
+        raise ValueError("mdgrad_amd: d must not be 0")
+    k = _lib.MdgTersoffConsts()
+    k.A, k.B, k.lam1, k.lam2, k.beta, k.n, k.c, k.d, k.h, k.R, k.D, k.lam3, k.gamma = A, B, lam1, lam2, beta, n, c, d, h, R, D, lam3, gamma
+    k.m, k.pad_ = int(m), 0
+    return k
+
+
+def tersoff_work_size(ell):
+    """The number of floats of the bond-pass scratch for the list `ell` (4 per list slot)."""
+    return int(_lib.load().mdg_tersoff_work_size(ell.n_atoms, ell.max_nbr))
+
+
+def tersoff_eval(ell, xyz, consts, theta=None, w=None, energy=True, grad=True, into=None, scale=1.0, want_theta=False, work=None):
+    """One call of mdg_tersoff_eval (bond pass, force pass) -> dict(energy, grad, hw, pth, pthw), argument for argument sw_eval
+    with theta = device float [3] = (A, B, h).  `work`: the flat float scratch of the bond pass, at least tersoff_work_size(ell)
+    long (a persistent buffer of the caller, so that a captured graph sees a fixed address); allocated here when None.  The
+    list may have been searched with any radius >= R + D (a skin): the kernels apply r < R + D per pair."""
+    lib = _lib.load()
+    N, dev = ell.n_atoms, xyz.device
+    _check_theta(theta)
+    need = tersoff_work_size(ell)
+    if work is None:
+        work = torch.empty(need, device=dev)
+    else:
+        require_gpu(work, "work")
+        if work.dim() != 1 or work.numel() < need or work.dtype != torch.float32 or not work.is_contiguous():
+            raise ValueError("mdgrad_amd: work must be a contiguous flat float32 tensor of at least %d elements (got %s)"
+                             % (need, tuple(work.shape)))
+    xyz, w, e, g, hw, pth, pthw, acc = _eval_prologue(N, xyz, w, energy, grad, into, want_theta, (N, 3))
+    partial = torch.empty(int(lib.mdg_tersoff_partial_size(N)), device=dev) if energy else None
+    check(lib.mdg_tersoff_eval(ptr(xyz), N, C.byref(ell.cell_struct), ptr(ell.col), ptr(ell.shift), ptr(ell.cnt), ell.max_nbr,
+                               C.byref(consts), ptr(theta), ptr(w), ptr(e), ptr(g), ptr(hw), ptr(pth), ptr(pthw), ptr(partial),
+                               ptr(work), float(scale), _list_flags(acc, ell), stream_ptr(dev)), "mdg_tersoff_eval")
+    return dict(energy=e, grad=g, hw=hw, pth=pth, pthw=pthw)
+
+
+class TersoffTerm(EAMTerm):
+    """The Tersoff term (csrc/tersoff.hip) for TermEnergyFn: the list, the constants, the device buffer (A, B, h) and the
+    scratch of the bond pass, kept current by Tersoff; the two evaluations are SWTerm's."""
+
+    noun = "dU/d(A, B, h) of the Tersoff term"
+
+    def _eval(self, xyz, **kw):
+        return tersoff_eval(self.ell, xyz, self.consts, self.theta, work=self.work, **kw)
 
 
 # ----------------------------------------------------------------------------- Ewald reciprocal-space sum (K21)

@@ -1220,6 +1220,41 @@ int mdg_tersoff_eval(const float* pos, int n_atoms, const MdgCell* cell /*host*/
                      float* bond_work, float out_scale, int accumulate, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * K26  Tersoff bond-order potential for 1 <= S <= 4 species over the per-atom (ELL) list (Tersoff 1989, the multicomponent
+ *      paper; the LAMMPS convention with lam3 = 0; mdgrad_amd/interface.py TersoffMulti, csrc/tersoff_multi.hip).  With
+ *      a = types[i], b = types[j], c = types[k]:
+ *        U       = 1/2 sum_i sum_{j in row(i)} fc_ab(r_ij) [A_ab exp(-lam1_ab r_ij) - b_ij B_ab exp(-lam2_ab r_ij)]
+ *        b_ij    = (1 + (beta_a zeta_ij)^n_a)^(-1/(2 n_a)),   exactly 1 with zero derivatives where zeta_ij = 0
+ *        zeta_ij = sum_{k in row(i), k != j} fc_ac(r_ik) g_a(cos theta_jik)
+ *        g_a(x)  = gamma_a (1 + c_a^2/d_a^2 - c_a^2/(d_a^2 + (h_a - x)^2))
+ *        fc_ab   = 1 for r <= R_ab - D_ab,  1/2 - 1/2 sin(pi (r - R_ab) / (2 D_ab)) inside,  exactly 0 for r >= R_ab + D_ab
+ *      `types`: device int32 [n_atoms], values in [0, S) (checked by the caller; the kernels clamp what they read).
+ *      `tables`: device float [mdg_tersoff_multi_table_size(S)] = 8 S (S + 1) derived constants,
+ *        pair entry   tables[8 (a S + b) ...] = A, B, lam1, lam2, R, R - D, R + D, pi / (2 D)      (row = centre, column = end;
+ *                                               (a, b) and (b, a) are separate entries and may differ)
+ *        centre entry tables[8 S S + 8 a ...] = h, beta, n, -1/(2n), d^2, gamma, gamma (c/d)^2, 2 gamma (c/d)^2 d^2
+ *      The caller validates the entries (mdgrad_amd/ops.py tersoff_multi_tables: A, B, lam1, lam2 > 0, D > 0, R > D, n > 0,
+ *      beta >= 0, d != 0); being device data they are not read here.  The list may have been searched with any radius >=
+ *      max_ab (R_ab + D_ab): every entry is tested against the support of its own pair entry.
+ *   mdg_tersoff_multi_eval  the passes, bond_work, `accumulate`, out_scale and the outputs energy, grad, hw of
+ *     mdg_tersoff_eval (K25); mdg_tersoff_multi_work_size(n_atoms, max_nbr) floats of bond_work, required for grad or hw;
+ *     mdg_tersoff_multi_partial_size(n_atoms) floats of `partial`, required for energy.  The per-atom parameter outputs are
+ *       pth [n_atoms, 2 S S + S]  row i = d u_i / d(A [S, S], B [S, S], h [S]), flattened in that order: u_i depends on
+ *                                 A[a, :], B[a, :], h[a] only, every other word of the row is written as 0, so the column
+ *                                 sums over the atoms (one GRAD_COLSUM job of mdg_grad_jobs) are dU/d(A, B, h)
+ *       pthw, the same shape      (w . grad_x) of the same (the column sums are d(w.dU/dx)/d(A, B, h))
+ *     n_species outside [1, 4], null types or tables, grad / hw without bond_work: MDG_EINVAL.  No atomics: bitwise
+ *     reproducible; the value parts of a launch with w equal those of a launch without, bit for bit.
+ */
+int64_t mdg_tersoff_multi_partial_size(int n_atoms);
+int64_t mdg_tersoff_multi_work_size(int n_atoms, int max_nbr);
+int64_t mdg_tersoff_multi_table_size(int n_species);
+int mdg_tersoff_multi_eval(const float* pos, int n_atoms, const MdgCell* cell /*host*/, const int32_t* col, const int32_t* shift,
+                           const int32_t* cnt, int max_nbr, const int32_t* types, int n_species, const float* tables /*device*/,
+                           const float* w, float* energy, float* grad, float* hw, float* pth, float* pthw, float* partial,
+                           float* bond_work, float out_scale, int accumulate, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * f4  bonded terms over a static topology table (csrc/bonded.hip).
  * Replaces torchmd/interface.py:447-455 (BondPotentials.forward: harmonic in the SQUARED bond length,
  * 1/2 k (|b|^2 - ro)^2) and :496-508 (AnglePotentials.forward: 1/2 k (theta - theta0)^2 over triples (i, j, k) centred on

@@ -301,6 +301,11 @@ _SIGNATURES = {
     "mdg_tersoff_work_size": (C.c_int64, [C.c_int, C.c_int]),
     "mdg_tersoff_eval": (C.c_int, [P, C.c_int, C.POINTER(MdgCell), P, P, P, C.c_int, C.POINTER(MdgTersoffConsts), P, P,
                                    P, P, P, P, P, P, P, C.c_float, C.c_int, P]),
+    "mdg_tersoff_multi_partial_size": (C.c_int64, [C.c_int]),
+    "mdg_tersoff_multi_work_size": (C.c_int64, [C.c_int, C.c_int]),
+    "mdg_tersoff_multi_table_size": (C.c_int64, [C.c_int]),
+    "mdg_tersoff_multi_eval": (C.c_int, [P, C.c_int, C.POINTER(MdgCell), P, P, P, C.c_int, P, C.c_int, P, P,
+                                         P, P, P, P, P, P, P, C.c_float, C.c_int, P]),
     "mdg_ewald_workspace": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "mdg_ewald_eval": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), P, P, P, C.c_int, P, P, P, P, P, P, P, C.c_float,
                                  C.c_int, P]),

@@ -1,6 +1,6 @@
 """Energy calculators with the reference's interface (torchmd/interface.py):
 GeneralInteraction :33-57, PairPotentials :217-300, Electrostatics :303-361 (as CoulombPotentials), Stack :364-403;
-StillingerWeber (three-body), SuttonChen (embedded-atom), Tersoff (bond-order) -- none of the three has a counterpart in the reference
+StillingerWeber (three-body), SuttonChen (embedded-atom), Tersoff (bond-order) and TersoffMulti (the same for several species) -- none of them has a counterpart in the reference
 (GNNPotentials lives in mdgrad_amd.nn).  forward(xyz) -> energy; _reset_topology(xyz) rebuilds the neighbour list.
 """
 import inspect
@@ -1472,6 +1472,283 @@ class Tersoff(_ListTerm):
         o = ops.tersoff_eval(self._ell, xyz.detach(), self._consts, self._theta(), w=w.detach(), energy=False, grad=True,
                              into=into, scale=-1.0, want_theta=need, work=self._scratch())
         return o["grad"], o["hw"], _theta3_tail(o["pthw"], self._thetas(), want_theta, accum)
+
+
+def _theta_flat_tail(pthw, thetas, want_theta, accum):
+    """The parameter part of force_vjp for a term whose per-atom table `pthw` [N, P] holds, column block by column block, the
+    terms of d(w.dU/dx)/dthetas flattened in the order of `thetas` (None when none of them is trainable); the result is minus
+    its column sums, in the fixed order of mdg_grad_jobs, shaped like the parameters.  With `accum` (ops.ThetaAccum) they are
+    added into its flat buffer and None returned."""
+    if not want_theta:
+        return None
+    if pthw is None:
+        return [] if accum is None else None
+    trainable = [isinstance(p, torch.nn.Parameter) for p in thetas]
+    starts = np.cumsum([0] + [p.numel() for p in thetas]).tolist()
+    if accum is not None:
+        jobs = ops.GradJobs()
+        offs = [accum.off.get(id(p)) for p, t in zip(thetas, trainable) if t]
+        if len(offs) == len(thetas) and None not in offs and all(o == offs[0] + s for o, s in zip(offs, starts)):
+            jobs.colsum(offs[0], pthw)                           # the parameters are adjacent in the flat buffer, in this order
+        else:
+            for k, (p, t) in enumerate(zip(thetas, trainable)):
+                if t and accum.off.get(id(p)) is not None:
+                    jobs.colsum(accum.off[id(p)], pthw[:, starts[k]:starts[k + 1]])
+        jobs.run(accum, alpha=-1.0, accumulate=True)
+        return None
+    gw = ops.tersoff_multi_theta_sum(pthw, alpha=-1.0)
+    return [gw[starts[k]:starts[k + 1]].reshape(p.shape) for k, (p, t) in enumerate(zip(thetas, trainable)) if t]
+
+
+class TersoffMulti(_ListTerm):
+    """Tersoff bond-order potential for 1 <= S <= 4 species (Tersoff 1989, "Modeling solid-state chemistry: interatomic
+    potentials for multicomponent systems"; the LAMMPS convention with lam3 = 0): SiC, SiGe and their alloys from the
+    one-species sets and the paper's mixing rules.  Atom i has the species t_i = `types`[i]; with a = t_i, b = t_j, c = t_k
+
+        U       = 1/2 sum_i sum_{j != i} fc_ab(r_ij) [ A_ab exp(-lam1_ab r_ij) - b_ij B_ab exp(-lam2_ab r_ij) ]
+        b_ij    = (1 + (beta_a zeta_ij)^n_a)^(-1/(2 n_a)),        zeta_ij = 0: b_ij = 1 with every derivative 0 (as in Tersoff)
+        zeta_ij = sum_{k != i, j} fc_ac(r_ik) g_a(cos theta_jik)
+        g_a(x)  = gamma_a (1 + c_a^2/d_a^2 - c_a^2/(d_a^2 + (h_a - x)^2))
+        fc_ab   = 1 for r <= R_ab - D_ab;  1/2 - 1/2 sin(pi (r - R_ab) / (2 D_ab)) inside;  exactly 0 for r >= R_ab + D_ab
+
+    The pair constants (A, B, lam1, lam2, R, D) are [S, S] tables, row = the species of the centre of the directed bond,
+    column = the species of its end; (beta, n, c, d, h, gamma) belong to the centre's species.  chi is folded into B_ab
+    (B[a, b], a != b, is where chi lives), omega = 1.
+
+    TersoffMulti(system, types, species, chi) takes S one-species sets (dicts with the keys of Tersoff.PUBLISHED and an
+    optional gamma) and mixes them (`mix`): A_ab = sqrt(A_a A_b), B_ab = chi_ab sqrt(B_a B_b), lam_ab = (lam_a + lam_b) / 2
+    for both exponents, and, with the paper's inner and outer radii R - D and R + D, the geometric means of each, from which
+    R_ab and D_ab follow.  chi is [S, S], symmetric with unit diagonal (default: ones).  `from_tables` takes the tables
+    themselves, for sets that do not follow the mixing rules.  `silicon_carbide` (types: 0 = Si, 1 = C; chi = 0.9776) and
+    `silicon_germanium` (0 = Si, 1 = Ge; chi = 1.00061) carry the published constants; PUBLISHED adds germanium to Tersoff's.
+    `types` holds one entry per atom of a replica, in [0, S); every replica of System.replicate has the same species.
+
+    `A` [S, S], `B` [S, S] and `h` [S] are float32 parameters when trainable, otherwise buffers; everything else is constant.
+    A[a, b] and A[b, a] (likewise B) are separate entries that the constructors fill equally: a fit that wants them tied
+    ties their gradients (sums the two and writes the sum to both).
+
+    The cutoff is max_ab (R_ab + D_ab), an absolute length that no parameter moves; the pair set, the minimum image and the
+    test (d2 < rc^2) & (d2 != 0) are those of PairPotentials at that cutoff, and the kernels apply the support of fc_ab per
+    list entry with the entry's own R_ab + D_ab, so a list searched with a skin is exact.  Not covered (ValueError where it
+    can be asked for): lam3 != 0 (or m != 3 in a species set), angular constants that depend on the whole triplet,
+    `index_tuple`, `ex_pairs`, S > 4, the pressure of the term.
+
+    forward(xyz) is differentiable twice in xyz and once in (A, B, h) on the HIP kernels (ops.TersoffMultiTerm,
+    csrc/tersoff_multi.hip: the two passes of csrc/tersoff.hip with every constant looked up by species in a device table);
+    force / force_vjp serve the analytic adjoint and HIP-graph replay, also while the parameters require grad.  float64 or
+    host positions take the torch restatement `_torch_energy`, which keeps the published form of g.  A Stack holding the
+    term stays off the fused trajectory kernels."""
+
+    accepts_into = True
+    accepts_accum = True
+    analytic = True
+    MAX_SPECIES = ops.TERSOFF_MULTI_MAX_SPECIES
+    PUBLISHED = dict(Tersoff.PUBLISHED,
+                     germanium=dict(A=1769.0, B=419.23, lam1=2.4451, lam2=1.7047, beta=9.0166e-7, n=0.75627, c=1.0643e5,
+                                    d=15.652, h=-0.43884, R=2.95, D=0.15))
+    CHI = {"SiC": 0.9776, "SiGe": 1.00061}
+
+    def __init__(self, system, types, species, chi=None, trainable=True, index_tuple=None, ex_pairs=None):
+        pair, centre = self.mix(species, chi)
+        self._setup(system, types, pair, centre, trainable, index_tuple, ex_pairs)
+
+    @classmethod
+    def from_tables(cls, system, types, pair, centre, trainable=True, index_tuple=None, ex_pairs=None):
+        """The term from its tables: pair = dict of [S, S] arrays A, B, lam1, lam2, R, D (row = centre species, column = end
+        species), centre = dict of [S] arrays beta, n, c, d, h, gamma."""
+        self = cls.__new__(cls)
+        self._setup(system, types, pair, centre, trainable, index_tuple, ex_pairs)
+        return self
+
+    @classmethod
+    def silicon_carbide(cls, system, types, **kw):
+        """Tersoff's SiC (1989): the silicon and carbon sets, chi_SiC = 0.9776.  types: 0 = Si, 1 = C."""
+        chi = [[1.0, cls.CHI["SiC"]], [cls.CHI["SiC"], 1.0]]
+        return cls(system, types, [cls.PUBLISHED["silicon"], cls.PUBLISHED["carbon"]], chi=chi, **kw)
+
+    @classmethod
+    def silicon_germanium(cls, system, types, **kw):
+        """Tersoff's SiGe (1989): the silicon and germanium sets, chi_SiGe = 1.00061.  types: 0 = Si, 1 = Ge."""
+        chi = [[1.0, cls.CHI["SiGe"]], [cls.CHI["SiGe"], 1.0]]
+        return cls(system, types, [cls.PUBLISHED["silicon"], cls.PUBLISHED["germanium"]], chi=chi, **kw)
+
+    @classmethod
+    def mix(cls, species, chi=None):
+        """(pair, centre) tables of S one-species sets under Tersoff's mixing rules (class docstring), in float64."""
+        species = list(species)
+        S = len(species)
+        if not 1 <= S <= cls.MAX_SPECIES:
+            raise ValueError("TersoffMulti: species must hold 1 to %d parameter sets (got %d)" % (cls.MAX_SPECIES, S))
+        for a, p in enumerate(species):
+            if float(p.get("lam3", 0.0)) != 0.0 or int(p.get("m", 3)) != 3:
+                raise ValueError("TersoffMulti: species[%d] has lam3 = %r, m = %r; only lam3 = 0 (m = 3) is covered"
+                                 % (a, p.get("lam3", 0.0), p.get("m", 3)))
+            missing = [k for k in ("A", "B", "lam1", "lam2", "beta", "n", "c", "d", "h", "R", "D") if k not in p]
+            if missing:
+                raise ValueError("TersoffMulti: species[%d] lacks %s" % (a, ", ".join(missing)))
+        X = np.ones((S, S)) if chi is None else np.asarray(chi, dtype=np.float64)
+        if X.shape != (S, S) or not np.array_equal(X, X.T) or not (np.diag(X) == 1.0).all():
+            raise ValueError("TersoffMulti: chi must be a symmetric [%d, %d] matrix with unit diagonal (got %r)"
+                             % (S, S, X.tolist()))
+        col = lambda k: np.array([float(p[k]) for p in species], dtype=np.float64)
+        geo = lambda v: np.sqrt(np.outer(v, v))
+        mean = lambda v: 0.5 * (v[:, None] + v[None, :])
+        rin, rout = geo(col("R") - col("D")), geo(col("R") + col("D"))
+        pair = dict(A=geo(col("A")), B=X * geo(col("B")), lam1=mean(col("lam1")), lam2=mean(col("lam2")),
+                    R=0.5 * (rin + rout), D=0.5 * (rout - rin))
+        centre = {k: col(k) for k in ("beta", "n", "c", "d", "h")}
+        centre["gamma"] = np.array([float(p.get("gamma", 1.0)) for p in species], dtype=np.float64)
+        return pair, centre
+
+    def _setup(self, system, types, pair, centre, trainable, index_tuple, ex_pairs):
+        _ListTerm.__init__(self, system)
+        if index_tuple is not None or ex_pairs is not None:
+            raise ValueError("TersoffMulti: index_tuple and ex_pairs are not supported (every pair interacts)")
+        centre = dict(centre)
+        S = int(np.asarray(centre["h"]).reshape(-1).shape[0])
+        centre.setdefault("gamma", np.ones(S))
+        if S > self.MAX_SPECIES:
+            raise ValueError("TersoffMulti: S = %d species; at most %d are supported" % (S, self.MAX_SPECIES))
+        self._image = ops.tersoff_multi_tables(pair, centre)                # (validates every entry)
+        self.n_species = S
+        self._pair = {k: np.asarray(pair[k], dtype=np.float64).reshape(S, S) for k in ops.TERSOFF_MULTI_PAIR}
+        self._centre = {k: np.asarray(centre[k], dtype=np.float64).reshape(S) for k in ops.TERSOFF_MULTI_CENTRE}
+        ty = np.asarray(torch.as_tensor(types).detach().cpu().numpy()).reshape(-1)
+        if ty.shape[0] != self._group:
+            raise ValueError("TersoffMulti: types must hold one entry per atom of a replica (%d), got %d" % (self._group, ty.shape[0]))
+        if not np.issubdtype(ty.dtype, np.integer) or ty.min() < 0 or ty.max() >= S:
+            raise ValueError("TersoffMulti: types must be integers in [0, %d)" % S)
+        self.cutoff = float((self._pair["R"] + self._pair["D"]).max())
+        cell = np.asarray(system.get_cell(), dtype=np.float64)
+        cell = np.diag(cell) if cell.ndim == 1 else cell
+        vol = abs(float(np.linalg.det(cell)))
+        self._half_height = 0.5 * min(vol / float(np.linalg.norm(np.cross(cell[(a + 1) % 3], cell[(a + 2) % 3]))) for a in range(3))
+        if self.cutoff > self._half_height:
+            raise ValueError("TersoffMulti: max (R + D) = %g exceeds half the shortest cell height (%g)"
+                             % (self.cutoff, self._half_height))
+        for name in ("A", "B", "h"):
+            t = torch.tensor((self._pair if name != "h" else self._centre)[name], dtype=torch.float32, device=self.device)
+            if trainable:
+                setattr(self, name, torch.nn.Parameter(t))
+            else:
+                self.register_buffer(name, t)
+        self.index_tuple, self.ex_pairs, self._mask = None, None, None
+        self._n_rep = system.get_number_of_atoms() // self._group
+        self.types = torch.as_tensor(np.tile(ty.astype(np.int32), self._n_rep), device=self.device)   # one entry per atom
+        self._ell = None
+        self._template = torch.as_tensor(self._image, device=self.device)
+        self._table_mirror = _DeviceMirror(self._thetas, pack=self._pack_tables, numel=int(self._image.shape[0]))
+        self._work = None
+        if torch.device(self.device).type == "cuda":
+            self._reset_topology(torch.Tensor(system.get_positions()).to(system.device))
+            self._scratch()
+            self._tables()
+
+    # -- the device table the kernels read: the constants plus the current (A, B, h) ------------------------------
+    def _thetas(self):
+        return self.A, self.B, self.h
+
+    def _pack_tables(self, ps, out=None):
+        """The table image (ops.tersoff_multi_tables) with the current A, B, h in their columns, by device ops only."""
+        S = self.n_species
+        A, B, h = (p.detach().to(torch.float32) for p in ps)
+        out = self._template.to(A.device).clone() if out is None else out.copy_(self._template)
+        pair, centre = out[:8 * S * S].view(S * S, 8), out[8 * S * S:].view(S, 8)
+        pair[:, 0].copy_(A.reshape(-1))
+        pair[:, 1].copy_(B.reshape(-1))
+        centre[:, 0].copy_(h.reshape(-1))
+        return out
+
+    def _tables(self):
+        """The derived constants as the kernels read them: a device mirror (_DeviceMirror) rewritten when A, B or h changed,
+        so that the captured steps carry no host value of a parameter."""
+        return self._table_mirror.get()
+
+    def prepare_pass(self):
+        if self._hip_ok():
+            self._tables()
+            self._scratch()
+
+    def _scratch(self):
+        """The scratch of the bond pass, four floats per slot of the current list: persistent, so that a captured graph
+        sees a fixed address (under static topology max_nbr is fixed); re-allocated when a rebuild made the list wider."""
+        need = ops.tersoff_multi_work_size(self._ell)
+        if self._work is None or self._work.device != self._ell.col.device or self._work.numel() < need:
+            self._work = torch.empty(need, dtype=torch.float32, device=self._ell.col.device)
+        return self._work
+
+    # -- energy ----------------------------------------------------------------------------------------------------
+    def _torch_energy(self, xyz):
+        """The same energy in torch ops, in the dtype and on the device of xyz (differentiable by autograd in xyz and in
+        A, B, h), with g in its published form: every pair as two directed bonds with the constants of (centre species, end
+        species), grouped by centre into a padded [N, K] table, zeta as a sum over the [N, K, K] pairs of entries of a row."""
+        const = lambda v: torch.as_tensor(v, dtype=xyz.dtype, device=xyz.device)
+        A, B, h = (p.to(xyz) for p in (self.A, self.B, self.h))
+        i, j, off = self._all_pairs(xyz, self.cutoff)
+        if i.numel() == 0:
+            return xyz.sum() * 0.0
+        cell = self.cell.detach().to(xyz)
+        cell = torch.diag(cell) if cell.dim() == 1 else cell
+        dv = xyz[i] - xyz[j] - off.matmul(cell)
+        r = dv.pow(2).sum(-1).sqrt()
+        ty = self.types.to(xyz.device).long()
+        N = xyz.shape[0]
+        centre, end = torch.cat([i, j]), torch.cat([j, i])
+        u, r2 = torch.cat([-dv, dv]) / torch.cat([r, r])[:, None], torch.cat([r, r])
+        ta, tb = ty[centre], ty[end]
+        Rab, Dab = const(self._pair["R"])[ta, tb], const(self._pair["D"])[ta, tb]
+        taper = 0.5 - 0.5 * torch.sin((0.5 * math.pi / Dab) * (r2 - Rab))
+        fc2 = torch.where(r2 <= Rab - Dab, torch.ones_like(r2), torch.where(r2 < Rab + Dab, taper, torch.zeros_like(r2)))
+        vR = A[ta, tb] * torch.exp(-const(self._pair["lam1"])[ta, tb] * r2)
+        vA = B[ta, tb] * torch.exp(-const(self._pair["lam2"])[ta, tb] * r2)
+        order = torch.argsort(centre, stable=True)
+        centre, u, fc2, vR, vA = centre[order], u[order], fc2[order], vR[order], vA[order]
+        cnt = torch.bincount(centre, minlength=N)
+        K = int(cnt.max())
+        start = torch.cumsum(cnt, 0) - cnt
+        slot = torch.arange(centre.numel(), device=xyz.device) - start[centre]
+        U = xyz.new_zeros(N, K, 3).index_put((centre, slot), u)
+        F = xyz.new_zeros(N, K).index_put((centre, slot), fc2)              # (padding: fc = 0, no bond and no third atom)
+        VR = xyz.new_zeros(N, K).index_put((centre, slot), vR)
+        VA = xyz.new_zeros(N, K).index_put((centre, slot), vA)
+        cos = (U[:, :, None, :] * U[:, None, :, :]).sum(-1)                  # [N, j, k]
+        per = lambda name: const(self._centre[name])[ty][:, None, None]      # the centre's constants
+        c2, d2 = per("c") ** 2, per("d") ** 2
+        g = per("gamma") * (1.0 + c2 / d2 - c2 / (d2 + (h[ty][:, None, None] - cos) ** 2))
+        other = 1.0 - torch.eye(K, dtype=xyz.dtype, device=xyz.device)
+        zeta = (F[:, None, :] * g * other).sum(-1)
+        bonded = zeta > 0                                     # zeta = 0: b = 1, and no 0 * inf in its derivatives
+        z = torch.where(bonded, zeta, torch.ones_like(zeta))
+        beta, n = per("beta")[:, :, 0], per("n")[:, :, 0]
+        b = torch.where(bonded, (1.0 + (beta * z) ** n) ** (-0.5 / n), torch.ones_like(zeta))
+        return 0.5 * (F * (VR - b * VA)).sum()
+
+    def _term(self):
+        return ops.TersoffMultiTerm(self._ell, self.types, self.n_species, self._tables(), self._scratch())
+
+    def forward(self, xyz):
+        if self._hip_ok(xyz):
+            return ops.TermEnergyFn.apply(xyz.contiguous(), self._term(), *self._thetas())
+        return self._torch_energy(xyz)
+
+    # -- analytic-adjoint protocol (md._EOM.rhs_vjp, Stack.force / force_vjp) -------------------------------------
+    def supports_force_vjp(self):
+        return self._hip_ok()
+
+    def force(self, xyz, into=None):
+        """F = -dU/dx in one call (two kernels); `into` (a force buffer of another Stack member): added onto it in the
+        force pass and returned."""
+        o = self._term()._eval(xyz.detach(), energy=False, grad=True, into=None if into is None else (into, None), scale=-1.0)
+        return o["grad"]
+
+    def force_vjp(self, xyz, w, want_theta=True, accum=None, into=None):
+        """(F, d(w.F)/dx, [d(w.F)/dA, d(w.F)/dB, d(w.F)/dh]) in one call plus the fixed-order reduction of the parameter
+        part, shaped like the parameters; `accum` (ops.ThetaAccum): that part is added into its flat buffer instead (None
+        returned).  `into` = (F, dq) buffers of another Stack member: this term's force and d(w.F)/dx are added onto them
+        in the force pass."""
+        need = bool(want_theta) and any(isinstance(p, torch.nn.Parameter) for p in self._thetas())
+        o = self._term()._eval(xyz.detach(), w=w.detach(), energy=False, grad=True, into=into, scale=-1.0, want_theta=need)
+        return o["grad"], o["hw"], _theta_flat_tail(o["pthw"], self._thetas(), want_theta, accum)
 
 
 class EwaldReciprocal(_StaticTerm, torch.nn.Module):

@@ -18,6 +18,7 @@ torch.autograd.Function wrappers that own the differentiation contract
       SWTerm                                                    Stillinger-Weber term, parameters: (epsilon, sigma, lam)
       EAMTerm                                                   Sutton-Chen term, parameters: (epsilon, a, c)
       TersoffTerm                                               Tersoff bond-order term, parameters: (A, B, h)
+      TersoffMultiTerm                                          the same for up to four species: (A [S,S], B [S,S], h [S])
     DihedralPhiFn, DihedralHistFn                               signed dihedral angles of every frame, their periodic histogram
 
 Everything here requires HIP tensors; there is no CPU path.
@@ -897,6 +898,125 @@ class TersoffTerm(EAMTerm):
 
     def _eval(self, xyz, **kw):
         return tersoff_eval(self.ell, xyz, self.consts, self.theta, work=self.work, **kw)
+
+
+# ----------------------------------------------------------------------------- multi-species Tersoff term (K26)
+TERSOFF_MULTI_MAX_SPECIES = 4
+TERSOFF_MULTI_PAIR = ("A", "B", "lam1", "lam2", "R", "D")
+TERSOFF_MULTI_CENTRE = ("beta", "n", "c", "d", "h", "gamma")
+
+
+def tersoff_multi_tables(pair, centre):
+    """The table image mdg_tersoff_multi_eval reads, as a host float32 array of 8 S (S + 1) derived constants, from
+    pair = dict of [S, S] arrays A, B, lam1, lam2, R, D (row = centre species, column = end species) and centre = dict of [S]
+    arrays beta, n, c, d, h, gamma:
+        pair entry   out[8 (a S + b) ...] = A, B, lam1, lam2, R, R - D, R + D, pi / (2 D)
+        centre entry out[8 S S + 8 a ...] = h, beta, n, -1/(2n), d^2, gamma, gamma (c/d)^2, 2 gamma (c/d)^2 d^2
+    Every entry is validated: A, B, lam1, lam2 > 0; D > 0; R > D; n > 0; beta >= 0; d != 0."""
+    cen = {k: np.asarray(centre[k], dtype=np.float64).reshape(-1) for k in TERSOFF_MULTI_CENTRE}
+    S = cen["h"].shape[0]
+    if not 1 <= S <= TERSOFF_MULTI_MAX_SPECIES:
+        raise ValueError("mdgrad_amd: the number of species must lie in [1, %d] (got %d)" % (TERSOFF_MULTI_MAX_SPECIES, S))
+    for k, v in cen.items():
+        if v.shape != (S,):
+            raise ValueError("mdgrad_amd: centre[%r] must hold %d entries (got %s)" % (k, S, v.shape))
+    pr = {}
+    for k in TERSOFF_MULTI_PAIR:
+        pr[k] = np.asarray(pair[k], dtype=np.float64)
+        if pr[k].shape != (S, S):
+            raise ValueError("mdgrad_amd: pair[%r] must be [%d, %d] (got %s)" % (k, S, S, pr[k].shape))
+    for k in ("A", "B", "lam1", "lam2"):
+        if not (pr[k] > 0.0).all():
+            raise ValueError("mdgrad_amd: every entry of %s must be positive (got %r)" % (k, pr[k].tolist()))
+    if not ((pr["D"] > 0.0) & (pr["R"] > pr["D"])).all():
+        raise ValueError("mdgrad_amd: the cutoffs need D > 0 and R > D for every pair (got R = %r, D = %r)"
+                         % (pr["R"].tolist(), pr["D"].tolist()))
+    if not ((cen["n"] > 0.0) & (cen["beta"] >= 0.0)).all():
+        raise ValueError("mdgrad_amd: n must be positive and beta >= 0 for every species (got %r, %r)"
+                         % (cen["n"].tolist(), cen["beta"].tolist()))
+    if (cen["d"] == 0.0).any():
+        raise ValueError("mdgrad_amd: d must not be 0")
+    out = np.empty(8 * S * (S + 1), dtype=np.float32)
+    P = out[:8 * S * S].reshape(S, S, 8)
+    for c, v in enumerate((pr["A"], pr["B"], pr["lam1"], pr["lam2"], pr["R"], pr["R"] - pr["D"], pr["R"] + pr["D"],
+                           0.5 * np.pi / pr["D"])):
+        P[:, :, c] = v
+    Cn = out[8 * S * S:].reshape(S, 8)
+    cd2 = (cen["c"] / cen["d"]) ** 2
+    for c, v in enumerate((cen["h"], cen["beta"], cen["n"], -0.5 / cen["n"], cen["d"] ** 2, cen["gamma"], cen["gamma"] * cd2,
+                           2.0 * cen["gamma"] * cd2 * cen["d"] ** 2)):
+        Cn[:, c] = v
+    return out
+
+
+def tersoff_multi_work_size(ell):
+    """The number of floats of the bond-pass scratch for the list `ell` (4 per list slot)."""
+    return int(_lib.load().mdg_tersoff_multi_work_size(ell.n_atoms, ell.max_nbr))
+
+
+def tersoff_multi_eval(ell, xyz, types, n_species, tables, w=None, energy=True, grad=True, into=None, scale=1.0, want_theta=False,
+                       work=None):
+    """One call of mdg_tersoff_multi_eval (bond pass, force pass) -> dict(energy, grad, hw, pth, pthw), argument for argument
+    tersoff_eval with `types` (device int32 [N], values in [0, n_species): not read here) and `tables` (device float32, the
+    image of tersoff_multi_tables) in place of the constants and theta.  pth / pthw are [N, 2 S S + S]: row i holds
+    d u_i / d(A [S, S], B [S, S], h [S]) flattened in that order, zero outside A[t_i, :], B[t_i, :], h[t_i] -- what
+    tersoff_multi_theta_sum reduces.  The list may have been searched with any radius >= max (R + D)."""
+    lib = _lib.load()
+    N, dev, S = ell.n_atoms, xyz.device, int(n_species)
+    if not 1 <= S <= TERSOFF_MULTI_MAX_SPECIES:
+        raise ValueError("mdgrad_amd: n_species must lie in [1, %d] (got %r)" % (TERSOFF_MULTI_MAX_SPECIES, n_species))
+    require_gpu(types, "types", dtype=None)
+    if types.shape != (N,) or types.dtype != torch.int32 or not types.is_contiguous():
+        raise ValueError("mdgrad_amd: types must be a contiguous int32 [%d] tensor (got %s %s)" % (N, types.dtype, tuple(types.shape)))
+    require_gpu(tables, "tables")
+    if tables.shape != (8 * S * (S + 1),) or tables.dtype != torch.float32 or not tables.is_contiguous():
+        raise ValueError("mdgrad_amd: tables must be a contiguous float32 [%d] tensor (got %s)" % (8 * S * (S + 1), tuple(tables.shape)))
+    need = tersoff_multi_work_size(ell)
+    if work is None:
+        work = torch.empty(need, device=dev)
+    else:
+        require_gpu(work, "work")
+        if work.dim() != 1 or work.numel() < need or work.dtype != torch.float32 or not work.is_contiguous():
+            raise ValueError("mdgrad_amd: work must be a contiguous flat float32 tensor of at least %d elements (got %s)"
+                             % (need, tuple(work.shape)))
+    xyz, w, e, g, hw, pth, pthw, acc = _eval_prologue(N, xyz, w, energy, grad, into, want_theta, (N, 2 * S * S + S))
+    partial = torch.empty(int(lib.mdg_tersoff_multi_partial_size(N)), device=dev) if energy else None
+    check(lib.mdg_tersoff_multi_eval(ptr(xyz), N, C.byref(ell.cell_struct), ptr(ell.col), ptr(ell.shift), ptr(ell.cnt),
+                                     ell.max_nbr, ptr(types), S, ptr(tables), ptr(w), ptr(e), ptr(g), ptr(hw), ptr(pth),
+                                     ptr(pthw), ptr(partial), ptr(work), float(scale), _list_flags(acc, ell), stream_ptr(dev)),
+          "mdg_tersoff_multi_eval")
+    return dict(energy=e, grad=g, hw=hw, pth=pth, pthw=pthw)
+
+
+def tersoff_multi_theta_sum(per_atom, alpha=1.0):
+    """[2 S S + S] = alpha * the sums over the atoms of the per-atom parameter terms [N, 2 S S + S] of tersoff_multi_eval, in
+    (A, B, h) order and in the fixed order of mdg_grad_jobs."""
+    out = _FlatOut(per_atom.shape[1], per_atom.device)
+    jobs = GradJobs()
+    jobs.colsum(0, per_atom)
+    jobs.run(out, alpha=alpha, accumulate=False)
+    return out.flat
+
+
+class TersoffMultiTerm:
+    """The multi-species Tersoff term (csrc/tersoff_multi.hip) for TermEnergyFn: the list, the species of the atoms, the device
+    table and the scratch of the bond pass, kept current by TersoffMulti."""
+
+    noun = "dU/d(A, B, h) of the multi-species Tersoff term"
+
+    def __init__(self, ell, types, n_species, tables, work=None):
+        self.ell, self.types, self.n_species, self.tables, self.work = ell, types, n_species, tables, work
+
+    def _eval(self, xyz, **kw):
+        return tersoff_multi_eval(self.ell, xyz, self.types, self.n_species, self.tables, work=self.work, **kw)
+
+    def first_order(self, xyz, energy):
+        o = self._eval(xyz, energy=energy, grad=True, want_theta=True)
+        return o["energy"], o["grad"], tersoff_multi_theta_sum(o["pth"])
+
+    def second_order(self, xyz, w):
+        o = self._eval(xyz, w=w, energy=False, grad=False, want_theta=True)
+        return o["hw"], tersoff_multi_theta_sum(o["pthw"])
 
 
 # ----------------------------------------------------------------------------- Ewald reciprocal-space sum (K21)

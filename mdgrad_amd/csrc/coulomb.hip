@@ -8,7 +8,7 @@
 //   E = erfc(alpha r), G = g0 exp(-alpha^2 r^2):  psi = E/r - c0 + c1 (r - rc),  psi' = -E/r^2 - G/r + c1,
 //   psi'' = 2E/r^3 + 2G/r^2 + 2 alpha^2 G   -- one erfcf and one expf per pair (the library functions, not the fast
 //   intrinsics); alpha == 0 takes E = 1, G = 0 without calling either.
-#include "common.hpp"
+#include "manybody.hpp"
 
 namespace {
 
@@ -109,15 +109,6 @@ __global__ void coulomb_ell_kernel(const CoulombArgs A) {
     }
 }
 
-// one wave, fixed summation order
-__global__ void coulomb_ell_finish(const float* __restrict__ partial, int nblocks, float* energy) {
-    const int lane = threadIdx.x;
-    float s = 0.f;
-    for (int b = lane; b < nblocks; b += 64) s += partial[b];
-    s = wave_sum(s);
-    if (lane == 0) energy[0] = s;
-}
-
 // types == null: one wave per slot p = atom of a replica, lanes stride over the replicas.
 // types != null: one 256-thread block per type, threads stride over all atoms.  Fixed order either way.
 __global__ void coulomb_charge_reduce_kernel(const float* __restrict__ val, const int32_t* __restrict__ types, int N, int group,
@@ -148,11 +139,7 @@ int coulomb_lpa(int N) {                     // (pick_lpa of csrc/pair_ell.hip)
 
 }  // namespace
 
-extern "C" int64_t mdg_coulomb_partial_size(int n_atoms) {
-    if (n_atoms <= 0) return 0;
-    const int apb = 256 / coulomb_lpa(n_atoms);
-    return (int64_t)((n_atoms + apb - 1) / apb);
-}
+extern "C" int64_t mdg_coulomb_partial_size(int n_atoms) { return atom_blocks(n_atoms, coulomb_lpa(n_atoms), 256); }
 
 #define MDG_COULOMB_LAUNCH(LPA_)                                                                       \
     case LPA_:                                                                                         \
@@ -180,12 +167,11 @@ extern "C" int mdg_coulomb_eval(const float* pos, int n_atoms, const MdgCell* ce
                   (float)k->alpha2, (float)k->conversion, (float)k->self_s,
                   grad, hw, pot, potw, energy ? partial : nullptr, out_scale, accumulate & 1, (accumulate >> 1) & 1};
     const int lpa = coulomb_lpa(n_atoms);
-    const int apb = 256 / lpa;
-    const int nblocks = (n_atoms + apb - 1) / apb;
+    const int nblocks = (int)atom_blocks(n_atoms, lpa, 256);
     dim3 grid(nblocks);
     hipStream_t st = (hipStream_t)stream;
     switch (lpa) { MDG_COULOMB_LAUNCH(8) MDG_COULOMB_LAUNCH(16) MDG_COULOMB_LAUNCH(32) MDG_COULOMB_LAUNCH(64) }
-    if (energy) hipLaunchKernelGGL(coulomb_ell_finish, dim3(1), dim3(64), 0, st, partial, nblocks, energy);
+    if (energy) hipLaunchKernelGGL(energy_finish, dim3(1), dim3(64), 0, st, partial, nblocks, energy);
     MDG_CHECK_LAUNCH("coulomb_ell_kernel");
     return MDG_OK;
 }

@@ -37,6 +37,12 @@ __device__ __forceinline__ float fexp_(float a) { return expf(a); }
 __device__ __forceinline__ Dual fexp_(Dual a) { return dexp(a); }
 __device__ __forceinline__ float val(float a) { return a; }
 __device__ __forceinline__ float val(Dual a) { return a.v; }
+// building and reading a number of either kind: mk<T>(v, d) = v (+ t d), dual_part(x) = d (0 for a float)
+template <class T> __device__ __forceinline__ T mk(float v, float d);
+template <> __device__ __forceinline__ float mk<float>(float v, float) { return v; }
+template <> __device__ __forceinline__ Dual mk<Dual>(float v, float d) { return {v, d}; }
+__device__ __forceinline__ float dual_part(float) { return 0.f; }
+__device__ __forceinline__ float dual_part(Dual a) { return a.d; }
 
 // ---- what the bond-order term (csrc/tersoff.hip) adds: a constant added to a Dual, log, sin, cos, and x^p for x > 0 and a
 // real exponent p as exp(p log x), the same expression in float and in Dual so that the value parts round alike

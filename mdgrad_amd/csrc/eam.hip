@@ -25,9 +25,8 @@
 // and the Dual instantiation round the value parts identically, so dU/dx of a LEVEL 1 launch equals that of a LEVEL 2 launch bit
 // for bit.
 #pragma clang fp contract(off)
-#include <type_traits>
-#include "common.hpp"
 #include "dual.hpp"
+#include "manybody.hpp"
 
 namespace {
 
@@ -53,14 +52,8 @@ struct EamK {                                  // per-thread constants
     int n, m;
 };
 
-template <class T> __device__ __forceinline__ T eam_mk(float v, float d);
-template <> __device__ __forceinline__ float eam_mk<float>(float v, float) { return v; }
-template <> __device__ __forceinline__ Dual eam_mk<Dual>(float v, float d) { return {v, d}; }
-__device__ __forceinline__ float eam_dual(float) { return 0.f; }
-__device__ __forceinline__ float eam_dual(Dual a) { return a.d; }
-
 template <class T> __device__ __forceinline__ T eam_pow(T x, int n) {
-    T r = eam_mk<T>(1.f, 0.f);
+    T r = mk<T>(1.f, 0.f);
     while (n > 0) { if (n & 1) r = r * x; x = x * x; n >>= 1; }
     return r;
 }
@@ -86,12 +79,12 @@ template <class T> struct EamEdge { T ex, ey, ez, r, ir; };
 // (dx, dy, dz) = end - centre with the stored image applied, (ax, ay, az) = w_end - w_centre.  False outside the support.
 template <class T>
 __device__ __forceinline__ bool eam_edge(const EamK& K, float dx, float dy, float dz, float ax, float ay, float az, EamEdge<T>& e) {
-    const T x = eam_mk<T>(dx, ax), y = eam_mk<T>(dy, ay), z = eam_mk<T>(dz, az);
+    const T x = mk<T>(dx, ax), y = mk<T>(dy, ay), z = mk<T>(dz, az);
     const T d2 = x * x + y * y + z * z;
     const float rv = sqrtf(val(d2));
     if (!(rv > 0.f && rv < K.rc)) return false;              // the support test, on the r that r - rc is formed from
     e.r = fsqrt_(d2);
-    e.ir = eam_mk<T>(1.f, 0.f) / e.r;
+    e.ir = mk<T>(1.f, 0.f) / e.r;
     e.ex = x * e.ir; e.ey = y * e.ir; e.ez = z * e.ir;
     return true;
 }
@@ -123,7 +116,7 @@ __device__ __forceinline__ T eam_density(const EamArgs& A, const EamK& K, int i,
     const float xi = A.pos[3 * i], yi = A.pos[3 * i + 1], zi = A.pos[3 * i + 2];
     float wxi = 0.f, wyi = 0.f, wzi = 0.f;
     if (LEVEL >= 2) { wxi = A.w[3 * i]; wyi = A.w[3 * i + 1]; wzi = A.w[3 * i + 2]; }
-    T rho = eam_mk<T>(0.f, 0.f);
+    T rho = mk<T>(0.f, 0.f);
     const int n = min(A.cnt[i], A.max_nbr);
     const size_t row = (size_t)i * A.max_nbr;
     for (int s = sub; s < n; s += EAM_LPA) {
@@ -146,12 +139,12 @@ __global__ void __launch_bounds__(EAM_BLOCK) eam_density_kernel(const EamArgs A)
     const T part = eam_density<T, LEVEL>(A, K, i, sub);
     const float rho = group_sum<EAM_LPA>(val(part));
     float drho = 0.f;
-    if (LEVEL >= 2) drho = group_sum<EAM_LPA>(eam_dual(part));
+    if (LEVEL >= 2) drho = group_sum<EAM_LPA>(dual_part(part));
     if (sub != 0) return;
-    T Fp = eam_mk<T>(0.f, 0.f);
-    if (rho > 0.f) Fp = eam_mk<T>(-0.5f * (K.eps * K.c), 0.f) / fsqrt_(eam_mk<T>(rho, drho));   // dual part: F''(rho) d rho
+    T Fp = mk<T>(0.f, 0.f);
+    if (rho > 0.f) Fp = mk<T>(-0.5f * (K.eps * K.c), 0.f) / fsqrt_(mk<T>(rho, drho));   // dual part: F''(rho) d rho
     float* o = A.work + 4 * (size_t)i;
-    o[0] = rho > 0.f ? rho : 0.f; o[1] = rho > 0.f ? drho : 0.f; o[2] = val(Fp); o[3] = eam_dual(Fp);
+    o[0] = rho > 0.f ? rho : 0.f; o[1] = rho > 0.f ? drho : 0.f; o[2] = val(Fp); o[3] = dual_part(Fp);
 }
 
 // ---- pass 2
@@ -174,16 +167,11 @@ __device__ __forceinline__ void eam_atom(const EamArgs& A, const EamK& K, int i,
             T Sm, dSm;
             eam_shape<T>(e, sr, K.m, K.fm, K.qm, K.lm, K.rc, Sm, dSm);
             const float* wj = A.work + 4 * (size_t)j;
-            const T FpJ = eam_mk<T>(wj[2], wj[3]);
+            const T FpJ = mk<T>(wj[2], wj[3]);
             const T du = K.eps * dSn + (FpI + FpJ) * dSm;                   // dU/dr_ij;  d r / d x_i = -e
             gx = gx - du * e.ex; gy = gy - du * e.ey; gz = gz - du * e.ez;
         }
     }
-}
-
-__device__ __forceinline__ void eam_store3(float* dst, int i, float os, int oacc, float x, float y, float z) {
-    if (oacc) { dst[3 * i] = fmaf(os, x, dst[3 * i]); dst[3 * i + 1] = fmaf(os, y, dst[3 * i + 1]); dst[3 * i + 2] = fmaf(os, z, dst[3 * i + 2]); }
-    else { dst[3 * i] = os * x; dst[3 * i + 1] = os * y; dst[3 * i + 2] = os * z; }
 }
 
 // LEVEL 0: U        1: + grad, pth        2: + hw, pthw
@@ -197,13 +185,13 @@ __global__ void __launch_bounds__(EAM_BLOCK) eam_force_kernel(const EamArgs A) {
     if (i < A.N) {
         const EamK K = eam_constants(A);
         const float* wi = A.work + 4 * (size_t)i;
-        const T zero = eam_mk<T>(0.f, 0.f);
-        const T R = eam_mk<T>(wi[0], wi[1]), FpI = eam_mk<T>(wi[2], wi[3]);
+        const T zero = mk<T>(0.f, 0.f);
+        const T R = mk<T>(wi[0], wi[1]), FpI = mk<T>(wi[2], wi[3]);
         T SP = zero, gx = zero, gy = zero, gz = zero;
         eam_atom<T, LEVEL>(A, K, i, sub, FpI, SP, gx, gy, gz);
         float o[8];
         o[0] = val(SP); o[1] = val(gx); o[2] = val(gy); o[3] = val(gz);
-        o[4] = eam_dual(SP); o[5] = eam_dual(gx); o[6] = eam_dual(gy); o[7] = eam_dual(gz);
+        o[4] = dual_part(SP); o[5] = dual_part(gx); o[6] = dual_part(gy); o[7] = dual_part(gz);
         o[0] = group_sum<EAM_LPA>(o[0]);
         if (LEVEL >= 1) {
 #pragma unroll
@@ -215,18 +203,18 @@ __global__ void __launch_bounds__(EAM_BLOCK) eam_force_kernel(const EamArgs A) {
         }
         if (sub == 0) {
             // u_i = eps (1/2 sum_j S_n - c sqrt(rho_i)) and its parameter derivatives
-            const T S = eam_mk<T>(o[0], o[4]);
+            const T S = mk<T>(o[0], o[4]);
             const T sq = val(R) > 0.f ? fsqrt_(R) : zero;
             const T pe = 0.5f * S - K.c * sq;
             en = K.eps * val(pe);
             if (LEVEL >= 1) {
                 const T pa = (1.f / K.a) * ((0.5f * K.fn * K.eps) * S + K.fm * (R * FpI));
                 const T pc = (-K.eps) * sq;
-                if (A.grad) eam_store3(A.grad, i, A.oscale, A.oacc, o[1], o[2], o[3]);
+                if (A.grad) store3(A.grad, i, A.oscale, A.oacc, o[1], o[2], o[3]);
                 if (A.pth) { A.pth[3 * i] = val(pe); A.pth[3 * i + 1] = val(pa); A.pth[3 * i + 2] = val(pc); }
                 if (LEVEL >= 2) {
-                    if (A.hw) eam_store3(A.hw, i, A.oscale, A.oacc, o[5], o[6], o[7]);
-                    if (A.pthw) { A.pthw[3 * i] = eam_dual(pe); A.pthw[3 * i + 1] = eam_dual(pa); A.pthw[3 * i + 2] = eam_dual(pc); }
+                    if (A.hw) store3(A.hw, i, A.oscale, A.oacc, o[5], o[6], o[7]);
+                    if (A.pthw) { A.pthw[3 * i] = dual_part(pe); A.pthw[3 * i + 1] = dual_part(pa); A.pthw[3 * i + 2] = dual_part(pc); }
                 }
             }
         }
@@ -237,22 +225,9 @@ __global__ void __launch_bounds__(EAM_BLOCK) eam_force_kernel(const EamArgs A) {
     }
 }
 
-// one wave, fixed summation order
-__global__ void eam_finish(const float* __restrict__ partial, int nblocks, float* energy) {
-    const int lane = threadIdx.x;
-    float s = 0.f;
-    for (int b = lane; b < nblocks; b += 64) s += partial[b];
-    s = wave_sum(s);
-    if (lane == 0) energy[0] = s;
-}
-
 }  // namespace
 
-extern "C" int64_t mdg_eam_partial_size(int n_atoms) {
-    if (n_atoms <= 0) return 0;
-    const int apb = EAM_BLOCK / EAM_LPA;
-    return (int64_t)((n_atoms + apb - 1) / apb);
-}
+extern "C" int64_t mdg_eam_partial_size(int n_atoms) { return atom_blocks(n_atoms, EAM_LPA, EAM_BLOCK); }
 
 extern "C" int mdg_eam_eval(const float* pos, int n_atoms, const MdgCell* cell, const int32_t* col, const int32_t* shift,
                             const int32_t* cnt, int max_nbr, const MdgEAMConsts* k, const float* theta, const float* w,
@@ -279,15 +254,12 @@ extern "C" int mdg_eam_eval(const float* pos, int n_atoms, const MdgCell* cell, 
     const int nblocks = (int)mdg_eam_partial_size(n_atoms);
     dim3 grid(nblocks);
     hipStream_t st = (hipStream_t)stream;
-    if (level == 2) {
-        hipLaunchKernelGGL((eam_density_kernel<2>), grid, dim3(EAM_BLOCK), 0, st, a);
-        hipLaunchKernelGGL((eam_force_kernel<2>), grid, dim3(EAM_BLOCK), 0, st, a);
-    } else {
-        hipLaunchKernelGGL((eam_density_kernel<1>), grid, dim3(EAM_BLOCK), 0, st, a);
-        if (level == 1) hipLaunchKernelGGL((eam_force_kernel<1>), grid, dim3(EAM_BLOCK), 0, st, a);
-        else hipLaunchKernelGGL((eam_force_kernel<0>), grid, dim3(EAM_BLOCK), 0, st, a);
-    }
-    if (energy) hipLaunchKernelGGL(eam_finish, dim3(1), dim3(64), 0, st, partial, nblocks, energy);
+    with_level(level, [&](auto L) {
+        constexpr int LV = decltype(L)::value;
+        hipLaunchKernelGGL((eam_density_kernel<(LV >= 2 ? 2 : 1)>), grid, dim3(EAM_BLOCK), 0, st, a);    // (0 and 1: the float pass)
+        hipLaunchKernelGGL((eam_force_kernel<LV>), grid, dim3(EAM_BLOCK), 0, st, a);
+    });
+    if (energy) hipLaunchKernelGGL(energy_finish, dim3(1), dim3(64), 0, st, partial, nblocks, energy);
     MDG_CHECK_LAUNCH("eam_force_kernel");
     return MDG_OK;
 }

@@ -24,8 +24,8 @@
 // No fused multiply-adds are formed by the compiler in this file: the float and the Dual instantiation then round the value
 // parts identically, so dU/dx of a LEVEL 1 launch equals that of a LEVEL 2 launch bit for bit.
 #pragma clang fp contract(off)
-#include "common.hpp"
 #include "dual.hpp"
+#include "manybody.hpp"
 
 namespace {
 
@@ -47,14 +47,8 @@ struct SwK {                                   // per-thread constants
     float eps, sigma, lam, le, rc, gs, gamma, cos0, A, B, fp, fq; int p, q;
 };
 
-template <class T> __device__ __forceinline__ T sw_mk(float v, float d);
-template <> __device__ __forceinline__ float sw_mk<float>(float v, float) { return v; }
-template <> __device__ __forceinline__ Dual sw_mk<Dual>(float v, float d) { return {v, d}; }
-__device__ __forceinline__ float sw_dual(float) { return 0.f; }
-__device__ __forceinline__ float sw_dual(Dual a) { return a.d; }
-
 template <class T> __device__ __forceinline__ T sw_pow(T x, int n) {
-    T r = sw_mk<T>(1.f, 0.f);
+    T r = mk<T>(1.f, 0.f);
     while (n > 0) { if (n & 1) r = r * x; x = x * x; n >>= 1; }
     return r;
 }
@@ -65,8 +59,8 @@ template <class T> struct SwEdge { T ex, ey, ez, r, ir, inv, g; };
 // (dx, dy, dz) = end - centre with the stored image applied, (ax, ay, az) = w_end - w_centre.  False outside the support.
 template <class T>
 __device__ __forceinline__ bool sw_edge(const SwK& K, float dx, float dy, float dz, float ax, float ay, float az, SwEdge<T>& e) {
-    const T x = sw_mk<T>(dx, ax), y = sw_mk<T>(dy, ay), z = sw_mk<T>(dz, az);
-    const T one = sw_mk<T>(1.f, 0.f);
+    const T x = mk<T>(dx, ax), y = mk<T>(dy, ay), z = mk<T>(dz, az);
+    const T one = mk<T>(1.f, 0.f);
     const T d2 = x * x + y * y + z * z;
     const float rv = sqrtf(val(d2));
     if (!(rv > 0.f && rv < K.rc)) return false;              // the support test, on the r that r - rc is formed from
@@ -83,7 +77,7 @@ __device__ __forceinline__ void sw_atom(const SwArgs& A, const SwK& K, int i, in
     const float xi = A.pos[3 * i], yi = A.pos[3 * i + 1], zi = A.pos[3 * i + 2];
     float wxi = 0.f, wyi = 0.f, wzi = 0.f;
     if (LEVEL >= 2) { wxi = A.w[3 * i]; wyi = A.w[3 * i + 1]; wzi = A.w[3 * i + 2]; }
-    const T zero = sw_mk<T>(0.f, 0.f);
+    const T zero = mk<T>(0.f, 0.f);
     T gx = zero, gy = zero, gz = zero;                       // dU/dx_i
     T S2 = zero, S2s = zero, S3 = zero, S3s = zero;          // sum e2, sum d e2 / d sigma, sum t3, sum d t3 / d sigma
     const int n = min(A.cnt[i], A.max_nbr);
@@ -177,15 +171,10 @@ __device__ __forceinline__ void sw_atom(const SwArgs& A, const SwK& K, int i, in
         out[1] = val(gx); out[2] = val(gy); out[3] = val(gz);
         out[4] = val(pe); out[5] = val(psg); out[6] = val(pl);
         if (LEVEL >= 2) {
-            out[7] = sw_dual(gx); out[8] = sw_dual(gy); out[9] = sw_dual(gz);
-            out[10] = sw_dual(pe); out[11] = sw_dual(psg); out[12] = sw_dual(pl);
+            out[7] = dual_part(gx); out[8] = dual_part(gy); out[9] = dual_part(gz);
+            out[10] = dual_part(pe); out[11] = dual_part(psg); out[12] = dual_part(pl);
         }
     }
-}
-
-__device__ __forceinline__ void sw_store3(float* dst, int i, float os, int oacc, float x, float y, float z) {
-    if (oacc) { dst[3 * i] = fmaf(os, x, dst[3 * i]); dst[3 * i + 1] = fmaf(os, y, dst[3 * i + 1]); dst[3 * i + 2] = fmaf(os, z, dst[3 * i + 2]); }
-    else { dst[3 * i] = os * x; dst[3 * i + 1] = os * y; dst[3 * i + 2] = os * z; }
 }
 
 // LEVEL 0: U        1: + grad, pth        2: + hw, pthw
@@ -213,11 +202,11 @@ __global__ void __launch_bounds__(SW_BLOCK) sw_ell_kernel(const SwArgs A) {
         if (sub == 0) {
             e = o[0];
             if (LEVEL >= 1) {
-                if (A.grad) sw_store3(A.grad, i, A.oscale, A.oacc, o[1], o[2], o[3]);
+                if (A.grad) store3(A.grad, i, A.oscale, A.oacc, o[1], o[2], o[3]);
                 if (A.pth) { A.pth[3 * i] = o[4]; A.pth[3 * i + 1] = o[5]; A.pth[3 * i + 2] = o[6]; }
             }
             if (LEVEL >= 2) {
-                if (A.hw) sw_store3(A.hw, i, A.oscale, A.oacc, o[7], o[8], o[9]);
+                if (A.hw) store3(A.hw, i, A.oscale, A.oacc, o[7], o[8], o[9]);
                 if (A.pthw) { A.pthw[3 * i] = o[10]; A.pthw[3 * i + 1] = o[11]; A.pthw[3 * i + 2] = o[12]; }
             }
         }
@@ -228,22 +217,9 @@ __global__ void __launch_bounds__(SW_BLOCK) sw_ell_kernel(const SwArgs A) {
     }
 }
 
-// one wave, fixed summation order
-__global__ void sw_finish(const float* __restrict__ partial, int nblocks, float* energy) {
-    const int lane = threadIdx.x;
-    float s = 0.f;
-    for (int b = lane; b < nblocks; b += 64) s += partial[b];
-    s = wave_sum(s);
-    if (lane == 0) energy[0] = s;
-}
-
 }  // namespace
 
-extern "C" int64_t mdg_sw_partial_size(int n_atoms) {
-    if (n_atoms <= 0) return 0;
-    const int apb = SW_BLOCK / SW_LPA;
-    return (int64_t)((n_atoms + apb - 1) / apb);
-}
+extern "C" int64_t mdg_sw_partial_size(int n_atoms) { return atom_blocks(n_atoms, SW_LPA, SW_BLOCK); }
 
 extern "C" int mdg_sw_eval(const float* pos, int n_atoms, const MdgCell* cell, const int32_t* col, const int32_t* shift,
                            const int32_t* cnt, int max_nbr, const MdgSWConsts* k, const float* theta, const float* w,
@@ -268,10 +244,8 @@ extern "C" int mdg_sw_eval(const float* pos, int n_atoms, const MdgCell* cell, c
     const int nblocks = (int)mdg_sw_partial_size(n_atoms);
     dim3 grid(nblocks);
     hipStream_t st = (hipStream_t)stream;
-    if (level == 2) hipLaunchKernelGGL((sw_ell_kernel<2>), grid, dim3(SW_BLOCK), 0, st, a);
-    else if (level == 1) hipLaunchKernelGGL((sw_ell_kernel<1>), grid, dim3(SW_BLOCK), 0, st, a);
-    else hipLaunchKernelGGL((sw_ell_kernel<0>), grid, dim3(SW_BLOCK), 0, st, a);
-    if (energy) hipLaunchKernelGGL(sw_finish, dim3(1), dim3(64), 0, st, partial, nblocks, energy);
+    with_level(level, [&](auto L) { hipLaunchKernelGGL((sw_ell_kernel<decltype(L)::value>), grid, dim3(SW_BLOCK), 0, st, a); });
+    if (energy) hipLaunchKernelGGL(energy_finish, dim3(1), dim3(64), 0, st, partial, nblocks, energy);
     MDG_CHECK_LAUNCH("sw_ell_kernel");
     return MDG_OK;
 }

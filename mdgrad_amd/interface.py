@@ -238,28 +238,77 @@ def _param_tail(gw, param, alpha, want_theta, accum):
     return [-gw if alpha == -1.0 else alpha * gw]
 
 
-def _theta3_tail(pthw, thetas, want_theta, accum):
-    """The parameter part of force_vjp for a term with three one-element parameters: `pthw` [N, 3] = the per-atom terms of
-    d(w.dU/dx)/dthetas (None when none of them is trainable); the result is minus its column sums, in the fixed order of
-    mdg_grad_jobs.  With `accum` (ops.ThetaAccum) they are added into its flat buffer and None returned."""
+def _theta_flat_tail(pthw, thetas, want_theta, accum):
+    """The parameter part of force_vjp for a term whose per-atom table `pthw` [N, P] holds, column block by column block, the
+    terms of d(w.dU/dx)/dthetas flattened in the order of `thetas` (None when none of them is trainable); the result is minus
+    its column sums, in the fixed order of mdg_grad_jobs, shaped like the parameters.  With `accum` (ops.ThetaAccum) they are
+    added into its flat buffer and None returned."""
     if not want_theta:
         return None
     if pthw is None:
         return [] if accum is None else None
     trainable = [isinstance(p, torch.nn.Parameter) for p in thetas]
+    starts = np.cumsum([0] + [p.numel() for p in thetas]).tolist()
     if accum is not None:
         jobs = ops.GradJobs()
         offs = [accum.off.get(id(p)) for p, t in zip(thetas, trainable) if t]
-        if len(offs) == 3 and None not in offs and offs[1] == offs[0] + 1 and offs[2] == offs[0] + 2:
-            jobs.colsum(offs[0], pthw)                           # the three parameters are adjacent in the flat buffer
+        if len(offs) == len(thetas) and None not in offs and all(o == offs[0] + s for o, s in zip(offs, starts)):
+            jobs.colsum(offs[0], pthw)                           # the parameters are adjacent in the flat buffer, in this order
         else:
-            for col, (p, t) in enumerate(zip(thetas, trainable)):
+            for k, (p, t) in enumerate(zip(thetas, trainable)):
                 if t and accum.off.get(id(p)) is not None:
-                    jobs.colsum(accum.off[id(p)], pthw[:, col:col + 1])
+                    jobs.colsum(accum.off[id(p)], pthw[:, starts[k]:starts[k + 1]])
         jobs.run(accum, alpha=-1.0, accumulate=True)
         return None
-    gw = ops.sw_theta_sum(pthw, alpha=-1.0)
-    return [gw[k:k + 1].reshape(p.shape) for k, (p, t) in enumerate(zip(thetas, trainable)) if t]
+    gw = ops.theta_sum(pthw, alpha=-1.0)
+    return [gw[starts[k]:starts[k + 1]].reshape(p.shape) for k, (p, t) in enumerate(zip(thetas, trainable)) if t]
+
+
+class _ManyBodyTerm(_ListTerm):
+    """A many-body term on the ELL list whose kernels return per-atom parameter terms (ops.SWTerm and its kin): the energy
+    through ops.TermEnergyFn, the analytic-adjoint protocol (md._EOM.rhs_vjp, Stack.force / force_vjp) and the persistent
+    scratch of a two-pass kernel, all expressed through `_term(xyz)`, the ops.*Term on the current list, parameters and
+    scratch.  A module adds its parameters (`_thetas`), their device mirror, `_torch_energy` and its presets."""
+
+    accepts_into = True
+    accepts_accum = True
+    analytic = True
+    _work = None
+    _work_size = None            # ops.*_work_size of a kernel pair with a per-slot scratch
+
+    def _term(self, xyz):
+        raise NotImplementedError
+
+    def _scratch(self):
+        """The scratch of the bond pass, four floats per slot of the current list: persistent, so that a captured graph
+        sees a fixed address (under static topology max_nbr is fixed); re-allocated when a rebuild made the list wider."""
+        need = self._work_size(self._ell)
+        if self._work is None or self._work.device != self._ell.col.device or self._work.numel() < need:
+            self._work = torch.empty(need, dtype=torch.float32, device=self._ell.col.device)
+        return self._work
+
+    def forward(self, xyz):
+        if self._hip_ok(xyz):
+            return ops.TermEnergyFn.apply(xyz.contiguous(), self._term(xyz), *self._thetas())
+        return self._torch_energy(xyz)
+
+    def supports_force_vjp(self):
+        return self._hip_ok()
+
+    def force(self, xyz, into=None):
+        """F = -dU/dx in one call of the term's kernels; `into` (a force buffer of another Stack member): added onto it in
+        the same call and returned."""
+        o = self._term(xyz)._eval(xyz.detach(), energy=False, grad=True, into=None if into is None else (into, None), scale=-1.0)
+        return o["grad"]
+
+    def force_vjp(self, xyz, w, want_theta=True, accum=None, into=None):
+        """(F, d(w.F)/dx, [d(w.F)/dtheta for every trainable parameter of `_thetas`, shaped like it]) in one call plus the
+        fixed-order reduction of the parameter part; `accum` (ops.ThetaAccum): that part is added into its flat buffer
+        instead (None returned).  `into` = (F, dq) buffers of another Stack member: this term's force and d(w.F)/dx are
+        added onto them in the same call."""
+        need = bool(want_theta) and any(isinstance(p, torch.nn.Parameter) for p in self._thetas())
+        o = self._term(xyz)._eval(xyz.detach(), w=w.detach(), energy=False, grad=True, into=into, scale=-1.0, want_theta=need)
+        return o["grad"], o["hw"], _theta_flat_tail(o["pthw"], self._thetas(), want_theta, accum)
 
 
 class _LazyTopology:
@@ -953,7 +1002,7 @@ class CoulombPotentials(_ListTerm):
         return o["grad"], o["hw"], _param_tail(gw, self.charges, -self.conversion, want_theta, accum)
 
 
-class StillingerWeber(_ListTerm):
+class StillingerWeber(_ManyBodyTerm):
     """Stillinger-Weber potential for one species (Stillinger and Weber 1985): a short-ranged pair term plus a three-body
     term that prefers the angle cos0 between the bonds of every atom to its near neighbours -- tetrahedral silicon
     (`silicon`) and monatomic coarse-grained water (`mW`, Molinero and Moore 2009).  With rc = a sigma:
@@ -981,9 +1030,6 @@ class StillingerWeber(_ListTerm):
     d(w.F)/d(epsilon, sigma, lam) comes from the same launch plus a fixed-order reduction.  float64 or host positions take
     the torch restatement `_torch_energy`."""
 
-    accepts_into = True
-    accepts_accum = True
-    analytic = True
     cutoff_reset = 1.02          # a reset list is searched with this multiple of a sigma ...
     cutoff_keep = 1.05           # ... and kept while a sigma <= cutoff <= this multiple of a sigma (design constants)
     # 1 kcal/mol in eV: 4184 J/mol over (1.602176634e-19 J/eV * 6.02214076e23 /mol), the exact SI values of 2019
@@ -1119,35 +1165,11 @@ class StillingerWeber(_ListTerm):
         phi3 = lam * eps * (c - self.cos0) ** 2 * G[:, t[0]] * G[:, t[1]]
         return phi2.sum() + phi3.sum()
 
-    def forward(self, xyz):
-        if self._hip_ok(xyz):
-            ell = self._current_list(xyz)
-            return ops.TermEnergyFn.apply(xyz.contiguous(), ops.SWTerm(ell, self._consts, self._theta()), *self._thetas())
-        return self._torch_energy(xyz)
-
-    # -- analytic-adjoint protocol (md._EOM.rhs_vjp, Stack.force / force_vjp) -------------------------------------
-    def supports_force_vjp(self):
-        return self._hip_ok()
-
-    def force(self, xyz, into=None):
-        """F = -dU/dx in one kernel launch; `into` (a force buffer of another Stack member): added onto it in the same
-        launch and returned."""
-        o = ops.sw_eval(self._current_list(xyz), xyz.detach(), self._consts, self._theta(), energy=False, grad=True,
-                        into=None if into is None else (into, None), scale=-1.0)
-        return o["grad"]
-
-    def force_vjp(self, xyz, w, want_theta=True, accum=None, into=None):
-        """(F, d(w.F)/dx, [d(w.F)/d epsilon, d(w.F)/d sigma, d(w.F)/d lam]) in one launch plus the fixed-order reduction of
-        the parameter part; `accum` (ops.ThetaAccum): that part is added into its flat buffer instead (None returned).
-        `into` = (F, dq) buffers of another Stack member: this term's force and d(w.F)/dx are added onto them in the same
-        launch."""
-        need = bool(want_theta) and any(isinstance(p, torch.nn.Parameter) for p in self._thetas())
-        o = ops.sw_eval(self._current_list(xyz), xyz.detach(), self._consts, self._theta(), w=w.detach(), energy=False,
-                        grad=True, into=into, scale=-1.0, want_theta=need)
-        return o["grad"], o["hw"], _theta3_tail(o["pthw"], self._thetas(), want_theta, accum)
+    def _term(self, xyz):
+        return ops.SWTerm(self._current_list(xyz), self._consts, self._theta())
 
 
-class SuttonChen(_ListTerm):
+class SuttonChen(_ManyBodyTerm):
     """Sutton-Chen embedded-atom potential for one species (Sutton and Chen 1990; the Finnis-Sinclair form of the
     embedded-atom method): the cohesion of an fcc metal as a function of the local density, not a sum over pairs.  With
     the parameters epsilon (energy), a (length), c (dimensionless) and the integer exponents n > m >= 1:
@@ -1177,9 +1199,6 @@ class SuttonChen(_ListTerm):
     serve the analytic adjoint and HIP-graph replay, also while the parameters require grad.  float64 or host positions take
     the torch restatement `_torch_energy`."""
 
-    accepts_into = True
-    accepts_accum = True
-    analytic = True
     PUBLISHED = {"copper": (1.2382e-2, 3.61, 39.432, 9, 6), "nickel": (1.5707e-2, 3.52, 39.432, 9, 6),
                  "silver": (2.5415e-3, 4.09, 144.41, 12, 6), "gold": (1.2793e-2, 4.08, 34.408, 10, 8)}
 
@@ -1252,6 +1271,7 @@ class SuttonChen(_ListTerm):
         if self._hip_ok():
             self._theta()
 
+    # (not the base's: the density pass keeps four floats per atom, sized by the positions, not per list slot)
     def _scratch(self, xyz):
         if self._work is None or self._work.device != xyz.device or self._work.shape[0] != xyz.shape[0]:
             self._work = torch.empty(xyz.shape[0], 4, dtype=torch.float32, device=xyz.device)
@@ -1280,35 +1300,11 @@ class SuttonChen(_ListTerm):
         root = torch.where(dense, rho, torch.ones_like(rho)).sqrt() * dense.to(xyz)
         return eps * (self._shape(r, a, self.n).sum() - c * root.sum())
 
-    def forward(self, xyz):
-        if self._hip_ok(xyz):
-            term = ops.EAMTerm(self._ell, self._consts, self._theta(), self._scratch(xyz))
-            return ops.TermEnergyFn.apply(xyz.contiguous(), term, *self._thetas())
-        return self._torch_energy(xyz)
-
-    # -- analytic-adjoint protocol (md._EOM.rhs_vjp, Stack.force / force_vjp) -------------------------------------
-    def supports_force_vjp(self):
-        return self._hip_ok()
-
-    def force(self, xyz, into=None):
-        """F = -dU/dx in one call (two kernels); `into` (a force buffer of another Stack member): added onto it in the
-        force pass and returned."""
-        o = ops.eam_eval(self._ell, xyz.detach(), self._consts, self._theta(), energy=False, grad=True,
-                         into=None if into is None else (into, None), scale=-1.0, work=self._scratch(xyz))
-        return o["grad"]
-
-    def force_vjp(self, xyz, w, want_theta=True, accum=None, into=None):
-        """(F, d(w.F)/dx, [d(w.F)/d epsilon, d(w.F)/d a, d(w.F)/d c]) in one call plus the fixed-order reduction of the
-        parameter part; `accum` (ops.ThetaAccum): that part is added into its flat buffer instead (None returned).
-        `into` = (F, dq) buffers of another Stack member: this term's force and d(w.F)/dx are added onto them in the
-        force pass."""
-        need = bool(want_theta) and any(isinstance(p, torch.nn.Parameter) for p in self._thetas())
-        o = ops.eam_eval(self._ell, xyz.detach(), self._consts, self._theta(), w=w.detach(), energy=False, grad=True,
-                         into=into, scale=-1.0, want_theta=need, work=self._scratch(xyz))
-        return o["grad"], o["hw"], _theta3_tail(o["pthw"], self._thetas(), want_theta, accum)
+    def _term(self, xyz):
+        return ops.EAMTerm(self._ell, self._consts, self._theta(), self._scratch(xyz))
 
 
-class Tersoff(_ListTerm):
+class Tersoff(_ManyBodyTerm):
     """Tersoff bond-order potential for one species (Tersoff 1988 for silicon, 1989 for carbon; the LAMMPS convention): the
     strength of a bond depends on the bond's environment, so silicon, carbon, germanium and their amorphous or defective
     networks are described without a hard-wired tetrahedral angle.
@@ -1337,9 +1333,7 @@ class Tersoff(_ListTerm):
     force / force_vjp serve the analytic adjoint and HIP-graph replay, also while the parameters require grad.  float64 or
     host positions take the torch restatement `_torch_energy`, which keeps the published form of g."""
 
-    accepts_into = True
-    accepts_accum = True
-    analytic = True
+    _work_size = staticmethod(ops.tersoff_work_size)
     PUBLISHED = {"silicon": dict(A=1830.8, B=471.18, lam1=2.4799, lam2=1.7322, beta=1.1e-6, n=0.78734, c=1.0039e5, d=16.217,
                                  h=-0.59825, R=2.85, D=0.15),
                  "carbon": dict(A=1393.6, B=346.74, lam1=3.4879, lam2=2.2119, beta=1.5724e-7, n=0.72751, c=38049.0, d=4.3484,
@@ -1401,14 +1395,6 @@ class Tersoff(_ListTerm):
             self._theta()
             self._scratch()
 
-    def _scratch(self):
-        """The scratch of the bond pass, four floats per slot of the current list: persistent, so that a captured graph
-        sees a fixed address (under static topology max_nbr is fixed); re-allocated when a rebuild made the list wider."""
-        need = ops.tersoff_work_size(self._ell)
-        if self._work is None or self._work.device != self._ell.col.device or self._work.numel() < need:
-            self._work = torch.empty(need, dtype=torch.float32, device=self._ell.col.device)
-        return self._work
-
     # -- energy ----------------------------------------------------------------------------------------------------
     def _torch_energy(self, xyz):
         """The same energy in torch ops, in the dtype and on the device of xyz (differentiable by autograd in xyz and in
@@ -1447,60 +1433,11 @@ class Tersoff(_ListTerm):
         b = torch.where(bonded, (1.0 + (k.beta * z) ** k.n) ** (-0.5 / k.n), torch.ones_like(zeta))
         return 0.5 * (F * (A * torch.exp(-k.lam1 * Rr) - b * B * torch.exp(-k.lam2 * Rr))).sum()
 
-    def forward(self, xyz):
-        if self._hip_ok(xyz):
-            term = ops.TersoffTerm(self._ell, self._consts, self._theta(), self._scratch())
-            return ops.TermEnergyFn.apply(xyz.contiguous(), term, *self._thetas())
-        return self._torch_energy(xyz)
-
-    # -- analytic-adjoint protocol (md._EOM.rhs_vjp, Stack.force / force_vjp) -------------------------------------
-    def supports_force_vjp(self):
-        return self._hip_ok()
-
-    def force(self, xyz, into=None):
-        """F = -dU/dx in one call (two kernels); `into` (a force buffer of another Stack member): added onto it in the
-        force pass and returned."""
-        o = ops.tersoff_eval(self._ell, xyz.detach(), self._consts, self._theta(), energy=False, grad=True,
-                             into=None if into is None else (into, None), scale=-1.0, work=self._scratch())
-        return o["grad"]
-
-    def force_vjp(self, xyz, w, want_theta=True, accum=None, into=None):
-        """(F, d(w.F)/dx, [d(w.F)/dA, d(w.F)/dB, d(w.F)/dh]) in one call plus the fixed-order reduction of the parameter
-        part; `accum` (ops.ThetaAccum): that part is added into its flat buffer instead (None returned).  `into` = (F, dq)
-        buffers of another Stack member: this term's force and d(w.F)/dx are added onto them in the force pass."""
-        need = bool(want_theta) and any(isinstance(p, torch.nn.Parameter) for p in self._thetas())
-        o = ops.tersoff_eval(self._ell, xyz.detach(), self._consts, self._theta(), w=w.detach(), energy=False, grad=True,
-                             into=into, scale=-1.0, want_theta=need, work=self._scratch())
-        return o["grad"], o["hw"], _theta3_tail(o["pthw"], self._thetas(), want_theta, accum)
+    def _term(self, xyz):
+        return ops.TersoffTerm(self._ell, self._consts, self._theta(), self._scratch())
 
 
-def _theta_flat_tail(pthw, thetas, want_theta, accum):
-    """The parameter part of force_vjp for a term whose per-atom table `pthw` [N, P] holds, column block by column block, the
-    terms of d(w.dU/dx)/dthetas flattened in the order of `thetas` (None when none of them is trainable); the result is minus
-    its column sums, in the fixed order of mdg_grad_jobs, shaped like the parameters.  With `accum` (ops.ThetaAccum) they are
-    added into its flat buffer and None returned."""
-    if not want_theta:
-        return None
-    if pthw is None:
-        return [] if accum is None else None
-    trainable = [isinstance(p, torch.nn.Parameter) for p in thetas]
-    starts = np.cumsum([0] + [p.numel() for p in thetas]).tolist()
-    if accum is not None:
-        jobs = ops.GradJobs()
-        offs = [accum.off.get(id(p)) for p, t in zip(thetas, trainable) if t]
-        if len(offs) == len(thetas) and None not in offs and all(o == offs[0] + s for o, s in zip(offs, starts)):
-            jobs.colsum(offs[0], pthw)                           # the parameters are adjacent in the flat buffer, in this order
-        else:
-            for k, (p, t) in enumerate(zip(thetas, trainable)):
-                if t and accum.off.get(id(p)) is not None:
-                    jobs.colsum(accum.off[id(p)], pthw[:, starts[k]:starts[k + 1]])
-        jobs.run(accum, alpha=-1.0, accumulate=True)
-        return None
-    gw = ops.tersoff_multi_theta_sum(pthw, alpha=-1.0)
-    return [gw[starts[k]:starts[k + 1]].reshape(p.shape) for k, (p, t) in enumerate(zip(thetas, trainable)) if t]
-
-
-class TersoffMulti(_ListTerm):
+class TersoffMulti(_ManyBodyTerm):
     """Tersoff bond-order potential for 1 <= S <= 4 species (Tersoff 1989, "Modeling solid-state chemistry: interatomic
     potentials for multicomponent systems"; the LAMMPS convention with lam3 = 0): SiC, SiGe and their alloys from the
     one-species sets and the paper's mixing rules.  Atom i has the species t_i = `types`[i]; with a = t_i, b = t_j, c = t_k
@@ -1539,9 +1476,7 @@ class TersoffMulti(_ListTerm):
     host positions take the torch restatement `_torch_energy`, which keeps the published form of g.  A Stack holding the
     term stays off the fused trajectory kernels."""
 
-    accepts_into = True
-    accepts_accum = True
-    analytic = True
+    _work_size = staticmethod(ops.tersoff_multi_work_size)
     MAX_SPECIES = ops.TERSOFF_MULTI_MAX_SPECIES
     PUBLISHED = dict(Tersoff.PUBLISHED,
                      germanium=dict(A=1769.0, B=419.23, lam1=2.4451, lam2=1.7047, beta=9.0166e-7, n=0.75627, c=1.0643e5,
@@ -1669,14 +1604,6 @@ class TersoffMulti(_ListTerm):
             self._tables()
             self._scratch()
 
-    def _scratch(self):
-        """The scratch of the bond pass, four floats per slot of the current list: persistent, so that a captured graph
-        sees a fixed address (under static topology max_nbr is fixed); re-allocated when a rebuild made the list wider."""
-        need = ops.tersoff_multi_work_size(self._ell)
-        if self._work is None or self._work.device != self._ell.col.device or self._work.numel() < need:
-            self._work = torch.empty(need, dtype=torch.float32, device=self._ell.col.device)
-        return self._work
-
     # -- energy ----------------------------------------------------------------------------------------------------
     def _torch_energy(self, xyz):
         """The same energy in torch ops, in the dtype and on the device of xyz (differentiable by autograd in xyz and in
@@ -1723,32 +1650,8 @@ class TersoffMulti(_ListTerm):
         b = torch.where(bonded, (1.0 + (beta * z) ** n) ** (-0.5 / n), torch.ones_like(zeta))
         return 0.5 * (F * (VR - b * VA)).sum()
 
-    def _term(self):
+    def _term(self, xyz):
         return ops.TersoffMultiTerm(self._ell, self.types, self.n_species, self._tables(), self._scratch())
-
-    def forward(self, xyz):
-        if self._hip_ok(xyz):
-            return ops.TermEnergyFn.apply(xyz.contiguous(), self._term(), *self._thetas())
-        return self._torch_energy(xyz)
-
-    # -- analytic-adjoint protocol (md._EOM.rhs_vjp, Stack.force / force_vjp) -------------------------------------
-    def supports_force_vjp(self):
-        return self._hip_ok()
-
-    def force(self, xyz, into=None):
-        """F = -dU/dx in one call (two kernels); `into` (a force buffer of another Stack member): added onto it in the
-        force pass and returned."""
-        o = self._term()._eval(xyz.detach(), energy=False, grad=True, into=None if into is None else (into, None), scale=-1.0)
-        return o["grad"]
-
-    def force_vjp(self, xyz, w, want_theta=True, accum=None, into=None):
-        """(F, d(w.F)/dx, [d(w.F)/dA, d(w.F)/dB, d(w.F)/dh]) in one call plus the fixed-order reduction of the parameter
-        part, shaped like the parameters; `accum` (ops.ThetaAccum): that part is added into its flat buffer instead (None
-        returned).  `into` = (F, dq) buffers of another Stack member: this term's force and d(w.F)/dx are added onto them
-        in the force pass."""
-        need = bool(want_theta) and any(isinstance(p, torch.nn.Parameter) for p in self._thetas())
-        o = self._term()._eval(xyz.detach(), w=w.detach(), energy=False, grad=True, into=into, scale=-1.0, want_theta=need)
-        return o["grad"], o["hw"], _theta_flat_tail(o["pthw"], self._thetas(), want_theta, accum)
 
 
 class EwaldReciprocal(_StaticTerm, torch.nn.Module):

@@ -743,14 +743,17 @@ class _FlatOut:
         self.flat, self.t, self.idx = torch.empty(n, device=device, dtype=torch.float32), None, None
 
 
-def sw_theta_sum(per_atom, alpha=1.0):
-    """[3] = alpha * the sums over the atoms of the per-atom parameter terms [N, 3] of sw_eval, in the fixed order of
-    mdg_grad_jobs."""
-    out = _FlatOut(3, per_atom.device)
+def theta_sum(per_atom, alpha=1.0):
+    """[P] = alpha * the sums over the atoms of the per-atom parameter terms [N, P] of sw_eval, eam_eval, tersoff_eval (P = 3)
+    or tersoff_multi_eval (P = 2 S S + S, in (A, B, h) order), in the fixed order of mdg_grad_jobs."""
+    out = _FlatOut(per_atom.shape[1], per_atom.device)
     jobs = GradJobs()
     jobs.colsum(0, per_atom)
     jobs.run(out, alpha=alpha, accumulate=False)
     return out.flat
+
+
+sw_theta_sum = eam_theta_sum = tersoff_multi_theta_sum = theta_sum          # the names the terms were introduced with
 
 
 class SWTerm:
@@ -767,11 +770,11 @@ class SWTerm:
 
     def first_order(self, xyz, energy):
         o = self._eval(xyz, energy=energy, grad=True, want_theta=True)
-        return o["energy"], o["grad"], sw_theta_sum(o["pth"])
+        return o["energy"], o["grad"], theta_sum(o["pth"])
 
     def second_order(self, xyz, w):
         o = self._eval(xyz, w=w, energy=False, grad=False, want_theta=True)
-        return o["hw"], sw_theta_sum(o["pthw"])
+        return o["hw"], theta_sum(o["pthw"])
 
 
 # ----------------------------------------------------------------------------- Sutton-Chen embedded-atom term (K24)
@@ -822,9 +825,6 @@ def eam_eval(ell, xyz, consts, theta=None, w=None, energy=True, grad=True, into=
     return dict(energy=e, grad=g, hw=hw, pth=pth, pthw=pthw)
 
 
-eam_theta_sum = sw_theta_sum          # the same fixed-order column sums of a per-atom [N, 3] table (mdg_grad_jobs)
-
-
 class EAMTerm(SWTerm):
     """The Sutton-Chen term (csrc/eam.hip) for TermEnergyFn: the list, the constants, the device buffer (epsilon, a, c) and
     the scratch of the density pass, kept current by SuttonChen; the two evaluations are SWTerm's."""
@@ -866,6 +866,17 @@ def tersoff_work_size(ell):
     return int(_lib.load().mdg_tersoff_work_size(ell.n_atoms, ell.max_nbr))
 
 
+def _bond_work(work, need, device):
+    """The flat float32 scratch of a bond pass, at least `need` long: `work` validated, or a fresh buffer when it is None."""
+    if work is None:
+        return torch.empty(need, device=device)
+    require_gpu(work, "work")
+    if work.dim() != 1 or work.numel() < need or work.dtype != torch.float32 or not work.is_contiguous():
+        raise ValueError("mdgrad_amd: work must be a contiguous flat float32 tensor of at least %d elements (got %s)"
+                         % (need, tuple(work.shape)))
+    return work
+
+
 def tersoff_eval(ell, xyz, consts, theta=None, w=None, energy=True, grad=True, into=None, scale=1.0, want_theta=False, work=None):
     """One call of mdg_tersoff_eval (bond pass, force pass) -> dict(energy, grad, hw, pth, pthw), argument for argument sw_eval
     with theta = device float [3] = (A, B, h).  `work`: the flat float scratch of the bond pass, at least tersoff_work_size(ell)
@@ -874,14 +885,7 @@ def tersoff_eval(ell, xyz, consts, theta=None, w=None, energy=True, grad=True, i
     lib = _lib.load()
     N, dev = ell.n_atoms, xyz.device
     _check_theta(theta)
-    need = tersoff_work_size(ell)
-    if work is None:
-        work = torch.empty(need, device=dev)
-    else:
-        require_gpu(work, "work")
-        if work.dim() != 1 or work.numel() < need or work.dtype != torch.float32 or not work.is_contiguous():
-            raise ValueError("mdgrad_amd: work must be a contiguous flat float32 tensor of at least %d elements (got %s)"
-                             % (need, tuple(work.shape)))
+    work = _bond_work(work, tersoff_work_size(ell), dev)
     xyz, w, e, g, hw, pth, pthw, acc = _eval_prologue(N, xyz, w, energy, grad, into, want_theta, (N, 3))
     partial = torch.empty(int(lib.mdg_tersoff_partial_size(N)), device=dev) if energy else None
     check(lib.mdg_tersoff_eval(ptr(xyz), N, C.byref(ell.cell_struct), ptr(ell.col), ptr(ell.shift), ptr(ell.cnt), ell.max_nbr,
@@ -971,14 +975,7 @@ def tersoff_multi_eval(ell, xyz, types, n_species, tables, w=None, energy=True, 
     require_gpu(tables, "tables")
     if tables.shape != (8 * S * (S + 1),) or tables.dtype != torch.float32 or not tables.is_contiguous():
         raise ValueError("mdgrad_amd: tables must be a contiguous float32 [%d] tensor (got %s)" % (8 * S * (S + 1), tuple(tables.shape)))
-    need = tersoff_multi_work_size(ell)
-    if work is None:
-        work = torch.empty(need, device=dev)
-    else:
-        require_gpu(work, "work")
-        if work.dim() != 1 or work.numel() < need or work.dtype != torch.float32 or not work.is_contiguous():
-            raise ValueError("mdgrad_amd: work must be a contiguous flat float32 tensor of at least %d elements (got %s)"
-                             % (need, tuple(work.shape)))
+    work = _bond_work(work, tersoff_multi_work_size(ell), dev)
     xyz, w, e, g, hw, pth, pthw, acc = _eval_prologue(N, xyz, w, energy, grad, into, want_theta, (N, 2 * S * S + S))
     partial = torch.empty(int(lib.mdg_tersoff_multi_partial_size(N)), device=dev) if energy else None
     check(lib.mdg_tersoff_multi_eval(ptr(xyz), N, C.byref(ell.cell_struct), ptr(ell.col), ptr(ell.shift), ptr(ell.cnt),
@@ -988,19 +985,9 @@ def tersoff_multi_eval(ell, xyz, types, n_species, tables, w=None, energy=True, 
     return dict(energy=e, grad=g, hw=hw, pth=pth, pthw=pthw)
 
 
-def tersoff_multi_theta_sum(per_atom, alpha=1.0):
-    """[2 S S + S] = alpha * the sums over the atoms of the per-atom parameter terms [N, 2 S S + S] of tersoff_multi_eval, in
-    (A, B, h) order and in the fixed order of mdg_grad_jobs."""
-    out = _FlatOut(per_atom.shape[1], per_atom.device)
-    jobs = GradJobs()
-    jobs.colsum(0, per_atom)
-    jobs.run(out, alpha=alpha, accumulate=False)
-    return out.flat
-
-
-class TersoffMultiTerm:
+class TersoffMultiTerm(SWTerm):
     """The multi-species Tersoff term (csrc/tersoff_multi.hip) for TermEnergyFn: the list, the species of the atoms, the device
-    table and the scratch of the bond pass, kept current by TersoffMulti."""
+    table and the scratch of the bond pass, kept current by TersoffMulti; the two evaluations are SWTerm's."""
 
     noun = "dU/d(A, B, h) of the multi-species Tersoff term"
 
@@ -1009,14 +996,6 @@ class TersoffMultiTerm:
 
     def _eval(self, xyz, **kw):
         return tersoff_multi_eval(self.ell, xyz, self.types, self.n_species, self.tables, work=self.work, **kw)
-
-    def first_order(self, xyz, energy):
-        o = self._eval(xyz, energy=energy, grad=True, want_theta=True)
-        return o["energy"], o["grad"], tersoff_multi_theta_sum(o["pth"])
-
-    def second_order(self, xyz, w):
-        o = self._eval(xyz, w=w, energy=False, grad=False, want_theta=True)
-        return o["hw"], tersoff_multi_theta_sum(o["pthw"])
 
 
 # ----------------------------------------------------------------------------- Ewald reciprocal-space sum (K21)

@@ -8,9 +8,9 @@ kernels, A = the float64 sum of the absolute contributions of the bond halves an
 evaluates gamma (1 + (c/d)^2 u^2 / (d^2 + u^2)), so their agreement is part of every comparison.  `within` prints the largest
 observed err / (2^-24 A).
 
-On an MI355X the largest observed ratios over all cases of this file were U 3.32 (gas37), dU/dx 23.76 (three replicas of the
-16-atom gas), H.w 51.23 (c64), dU/dtheta 4.23 (replicas), d(w.dU/dx)/dtheta 3.59 (tric64), the sum of the forces 0.07; si64
-alone: 2.67, 6.29, 23.04, 2.55, 1.55, 0.05; the perfect lattice: U 2.32, the forces against zero 2.23.  No case exceeds 64, so
+On an MI355X the largest observed ratios over all cases of this file were U 3.32 (gas37), dU/dx 23.35 (three replicas of the
+16-atom gas), H.w 51.98 (c64), dU/dtheta 4.23 (replicas), d(w.dU/dx)/dtheta 3.59 (tric64), the sum of the forces 0.05; si64
+alone: 2.67, 6.29, 22.92, 2.55, 1.55, 0.03; the perfect lattice: U 2.32, the forces against zero 2.30.  No case exceeds 64, so
 no bound is taken from a float32 evaluation of the reference.  H.w is the largest throughout; the likely reason is that it
 carries the second derivatives of g, whose argument u = h - cos theta is a difference of two numbers of order one half (a few
 2^-24 of cos theta are 2^-22 of u at the tetrahedral angle), once more than dU/dx does."""

@@ -13,8 +13,9 @@ replicas of the 16-atom gas), H.w 54.26 (s3_64), dU/dtheta 23.22 (s3_64), d(w.dU
 skin, against float64: dU/dx 5.04, H.w 19.39.  No case exceeds 64.  H.w is the largest throughout, as for the one-species kernel.
 The single-species limits (S = 1 and S = 2 with identical silicon sets on si64) against the one-species float64 reference: U
 2.40, dU/dx 6.54, H.w 22.80, dU/d(A, B, h) 4.90, d(w.dU/dx)/d(A, B, h) 1.43.  They are NOT bit-identical to the outputs of the
-one-species kernel (U, dU/dx and H.w all differ in the last bits): this kernel takes the pair parts of i -> j and j -> i
-separately, each with its own table entry, where the one-species kernel merges them into one expression."""
+one-species kernel (U, dU/dx and H.w all differ in the last bits), although both run the same code (csrc/tersoff_core.hpp):
+the table holds constants derived in float64 on the host (pi / (2 D), -1/(2n), gamma (c/d)^2 ...), the one-species kernel
+derives them in float32 from its arguments, and the two do not round alike."""
 import numpy as np
 import pytest
 import torch

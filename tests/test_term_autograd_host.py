@@ -1,6 +1,7 @@
 """The shared Python layer of the interaction terms, without a GPU: the generic autograd pair (ops.TermEnergyFn ->
 ops.TermGradFn) on a toy term written in torch, the device mirror of host-visible parameters (interface._DeviceMirror) on CPU
-tensors, and the no-accum branches of the two parameter tails of force_vjp.
+tensors, the no-accum branches of the two parameter tails of force_vjp, and the flat tail on three one-element parameters
+against the three-scalar tail it replaced (the reductions it queues, run here by a host stand-in of GradJobs.run).
 
 Tolerance: torch.equal where the hand formula and autograd do the same operations; otherwise 1e-12 of the largest entry --
 float64 round-off on numbers of order one, not a measured quantity."""
@@ -170,8 +171,92 @@ def test_single_parameter_tail_without_accum():
 def test_three_scalar_tail_without_accum():
     th = [torch.nn.Parameter(torch.ones(1)) for _ in range(3)]
     pthw = torch.ones(4, 3)
-    assert interface._theta3_tail(pthw, th, False, None) is None
+    assert interface._theta_flat_tail(pthw, th, False, None) is None
     frozen = [t.detach() for t in th]
-    assert interface._theta3_tail(None, frozen, True, None) == []
-    assert interface._theta3_tail(None, frozen, True, ops.ThetaAccum(th)) is None
-    assert interface._theta3_tail(pthw, th, False, ops.ThetaAccum(th)) is None
+    assert interface._theta_flat_tail(None, frozen, True, None) == []
+    assert interface._theta_flat_tail(None, frozen, True, ops.ThetaAccum(th)) is None
+    assert interface._theta_flat_tail(pthw, th, False, ops.ThetaAccum(th)) is None
+
+
+def _three_scalar_tail(pthw, thetas, want_theta, accum):
+    """The tail that StillingerWeber, SuttonChen and Tersoff used before they took _theta_flat_tail, restated: the reference of
+    the test below."""
+    if not want_theta:
+        return None
+    if pthw is None:
+        return [] if accum is None else None
+    trainable = [isinstance(p, torch.nn.Parameter) for p in thetas]
+    if accum is not None:
+        jobs = ops.GradJobs()
+        offs = [accum.off.get(id(p)) for p, t in zip(thetas, trainable) if t]
+        if len(offs) == 3 and None not in offs and offs[1] == offs[0] + 1 and offs[2] == offs[0] + 2:
+            jobs.colsum(offs[0], pthw)
+        else:
+            for col, (p, t) in enumerate(zip(thetas, trainable)):
+                if t and accum.off.get(id(p)) is not None:
+                    jobs.colsum(accum.off[id(p)], pthw[:, col:col + 1])
+        jobs.run(accum, alpha=-1.0, accumulate=True)
+        return None
+    gw = ops.theta_sum(pthw, alpha=-1.0)
+    return [gw[k:k + 1].reshape(p.shape) for k, (p, t) in enumerate(zip(thetas, trainable)) if t]
+
+
+def _tail_cases():
+    """name -> (thetas, parameters of the accumulator or None), three one-element parameters each."""
+    def three():
+        return [torch.nn.Parameter(torch.tensor([float(k + 1)])) for k in range(3)]
+    cases = {}
+    th = three()
+    cases["adjacent"] = (th, list(th))
+    th = three()
+    cases["scattered"] = (th, [th[0], torch.nn.Parameter(torch.zeros(2)), th[2], th[1]])
+    th = three()
+    cases["adjacent elsewhere"] = (th, [torch.nn.Parameter(torch.zeros(2, 2))] + list(th))
+    th = three()
+    th[1] = th[1].detach()
+    cases["partly frozen"] = (th, [th[0], th[2]])
+    th = three()
+    cases["one parameter not in the accumulator"] = (th, [th[2], th[0]])
+    th = three()
+    cases["no accumulator"] = (th, None)
+    th = three()
+    th[0] = th[0].detach()
+    cases["no accumulator, partly frozen"] = (th, None)
+    return cases
+
+
+@pytest.mark.parametrize("case", sorted(_tail_cases()))
+def test_flat_tail_on_three_scalars_queues_and_returns_what_the_three_scalar_tail_did(case, monkeypatch):
+    log = []
+
+    def run(self, acc, alpha=1.0, accumulate=True):                 # GradJobs.run on the host: column sums only
+        for kind, off, rows, m, n, ts, row_map in self.jobs:
+            assert kind == ops._lib.GRAD_COLSUM and ts[1:] == [None, None, None] and row_map is None
+            log.append((off, rows, m, n, ts[0].clone(), float(alpha), bool(accumulate)))
+            add = alpha * ts[0].sum(0)
+            acc.flat[off:off + m] = acc.flat[off:off + m] + add if accumulate else add
+    monkeypatch.setattr(ops.GradJobs, "run", run)
+    pthw = torch.tensor([[1.0, -2.0, 4.0], [0.5, 8.0, -16.0], [32.0, 0.25, 64.0], [-128.0, 256.0, 0.125]])
+    thetas, params = _tail_cases()[case]
+    out = []
+    for tail in (_three_scalar_tail, interface._theta_flat_tail):
+        del log[:]
+        accum = None
+        if params is not None:
+            accum = ops.ThetaAccum(params)
+            accum.flat.copy_(torch.arange(accum.n, dtype=torch.float32) + 0.5)     # (something to accumulate onto)
+        got = tail(pthw, thetas, True, accum)
+        out.append((list(log), got, None if accum is None else accum.flat.clone()))
+    (jobs_a, got_a, flat_a), (jobs_b, got_b, flat_b) = out
+    assert len(jobs_a) == len(jobs_b) and len(jobs_a) >= 1
+    for a, b in zip(jobs_a, jobs_b):
+        assert a[:4] == b[:4] and a[5:] == b[5:], "offset, rows, width, alpha, accumulate"
+        assert a[4].shape == b[4].shape and torch.equal(a[4], b[4])
+    if params is None:
+        assert len(got_a) == len(got_b) == sum(isinstance(p, torch.nn.Parameter) for p in thetas)
+        for a, b in zip(got_a, got_b):
+            assert a.shape == b.shape == (1,) and torch.equal(a, b)
+        assert flat_a is None and flat_b is None
+    else:
+        assert got_a is None and got_b is None and torch.equal(flat_a, flat_b)
+        assert not torch.equal(flat_a, torch.arange(flat_a.numel(), dtype=torch.float32) + 0.5)

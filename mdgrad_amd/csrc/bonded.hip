@@ -4,14 +4,21 @@
 //
 //   bond  (interface.py:447-455)  U = 1/2 k (|b|^2 - ro)^2          b  = x_i - x_j + o L       -- SQUARED length vs ro
 //   angle (interface.py:496-508)  U = 1/2 k (theta - theta0)^2      b1 = x_i - x_j + o1 L, b2 = x_k - x_j + o2 L,
-//                                 theta = acos( b1.b2 / sqrt(|b1|^2 |b2|^2) )
+//                                 theta = atan2(|b1 x b2|, b1.b2): the reference's acos( b1.b2 / sqrt(|b1|^2 |b2|^2) ) without
+//                                 its loss of precision near 0 and pi -- in float32 the acos form's force is off by
+//                                 ~2.5e-7 / sin^2 theta (1 - cos^2 cancels) and divides by zero at collinearity; the force
+//                                 comes from the cross product instead (angle_grad), as in csrc/adf.hip
+//   collinear angle terms:        |b1 x b2|^2 <= (2^-20)^2 |b1|^2 |b2|^2 (three atoms on a line, or a bond vector of length
+//                                 zero): the term keeps its energy (theta = 0 or pi) and contributes zero force and zero H w --
+//                                 theta has a kink there, zero is its symmetric subgradient (csrc/adf.hip, csrc/dihedral.hip)
 //   image flags (topology.py:75-80, NON-strict on the upper side):  o = -[b >= L/2] + [b < -L/2]  per component,
 //   L = diagonal of the cell (both classes take cell.diag()); o is piecewise constant, so it carries no derivative.
 //
 // Atom-centric: thread n walks the incidence list of atom n (entries 4 term + role, sorted by term: a fixed summation
 // order) and re-derives each term it takes part in -- a chain atom sits in <= 2 bonds / <= 3 angles, cheaper than a
 // term-wise pass plus a scatter, and deterministic.  H w comes from forward-mode (dual-number) differentiation of the
-// gradient along (w_i - w_j [, w_k - w_j]): exact, no hand-written second derivatives of acos.
+// gradient along (w_i - w_j [, w_k - w_j]): the same expressions in float and in Dual (csrc/dual.hpp), no hand-written second
+// derivatives.
 #include "common.hpp"
 #include "dual.hpp"
 
@@ -44,24 +51,33 @@ __device__ __forceinline__ void bond_grad(const T (&b)[3], float k, float ro, T 
     for (int a = 0; a < 3; ++a) g[a] = c * b[a];
 }
 
-// dU/db1, dU/db2 of the angle term
+constexpr float ANGLE_EPS2 = 9.094947017729282e-13f;     // (2^-20)^2
+
+// dU/db1, dU/db2 of the angle term: dU/db = k (theta - theta0) dtheta/db with c = b1 x b2, theta = atan2(|c|, b1.b2),
+// dtheta/db1 = b1 x c / (|b1|^2 |c|), dtheta/db2 = c x b2 / (|b2|^2 |c|).  A collinear term (see the header) gets its energy and
+// a zero gradient, value and derivative part alike.
 template <typename T>
 __device__ __forceinline__ void angle_grad(const T (&b1)[3], const T (&b2)[3], float k, float th0, T (&g1)[3], T (&g2)[3], float& U) {
-    const T dot = b1[0] * b2[0] + b1[1] * b2[1] + b1[2] * b2[2];         // interface.py:500
-    const T n1 = b1[0] * b1[0] + b1[1] * b1[1] + b1[2] * b1[2];
-    const T n2 = b2[0] * b2[0] + b2[1] * b2[1] + b2[2] * b2[2];
-    const T nrm = fsqrt_(n1 * n2);                                         // :501
-    const T cs = dot / nrm;                                                // :503
-    const T th = facos_(cs);                                               // :505
+    const T dot = dot3(b1, b2), n1 = dot3(b1, b1), n2 = dot3(b2, b2);
+    T c[3];
+    cross3(b1, b2, c);
+    const T cc = dot3(c, c);
+    const bool flat = val(cc) <= ANGLE_EPS2 * val(n1) * val(n2);
+    const T sn = fsqrt_(cc);
+    const T th = fatan2_(sn, dot);
     const float dth = val(th) - th0;
-    U = 0.5f * k * dth * dth;                                              // :507
-    // dU/dcos = k (theta - theta0) * (-1 / sqrt(1 - cos^2)) ;  dcos/db1 = b2 / nrm - cos b1 / n1
-    const T one_m = 1.f - cs * cs;
-    const T dUdc = (-k) * ((th - th0) / fsqrt_(one_m));
+    U = 0.5f * k * dth * dth;                                              // interface.py:507
+    // (a collinear term divides by zero below, in the derivative part of sn already; none of it is kept)
+    const T f = k * (th - th0);
+    const T s1 = f / (n1 * sn), s2 = f / (n2 * sn);
+    T c1[3], c2[3];
+    cross3(b1, c, c1);
+    cross3(c, b2, c2);
+    const T zero = mk<T>(0.f, 0.f);
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        g1[a] = dUdc * (b2[a] / nrm - cs * (b1[a] / n1));
-        g2[a] = dUdc * (b1[a] / nrm - cs * (b2[a] / n2));
+        g1[a] = flat ? zero : s1 * c1[a];
+        g2[a] = flat ? zero : s2 * c2[a];
     }
 }
 

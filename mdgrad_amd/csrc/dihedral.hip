@@ -50,14 +50,7 @@ __device__ __forceinline__ float dh_image(float b, float L) { return b + ((b < -
 __device__ __forceinline__ Dual operator+(float a, Dual b) { return {a + b.v, b.d}; }
 __device__ __forceinline__ Dual operator*(Dual a, float b) { return {a.v * b, a.d * b}; }
 
-template <typename T>
-__device__ __forceinline__ T dot3(const T (&a)[3], const T (&b)[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
-template <typename T>
-__device__ __forceinline__ void cross3(const T (&a)[3], const T (&b)[3], T (&c)[3]) {
-    c[0] = a[1] * b[2] - a[2] * b[1];
-    c[1] = a[2] * b[0] - a[0] * b[2];
-    c[2] = a[0] * b[1] - a[1] * b[0];
-}
+// (dot3 / cross3 of three-vectors of either kind: csrc/dual.hpp)
 
 // the three imaged bond vectors of term t of a frame at `pos`
 __device__ __forceinline__ void bonds_of(const float* __restrict__ pos, const int32_t* __restrict__ q, const float* L, float (&b1)[3],

@@ -59,4 +59,20 @@ __device__ __forceinline__ Dual fcos_(Dual a) { return dcos(a); }
 __device__ __forceinline__ float fpow_(float x, float p) { return fexp_(p * flog_(x)); }
 __device__ __forceinline__ Dual fpow_(Dual x, float p) { return fexp_(p * flog_(x)); }
 
+// ---- what the angle term (csrc/bonded.hip) adds: atan2, and the dot / cross product of three-vectors of either kind (the torsion
+// term, csrc/dihedral.hip, uses the same two).  d atan2(y, x) = (x dy - y dx) / (x^2 + y^2)
+__device__ __forceinline__ Dual datan2(Dual y, Dual x) {
+    return {atan2f(y.v, x.v), (x.v * y.d - y.v * x.d) / (x.v * x.v + y.v * y.v)};
+}
+__device__ __forceinline__ float fatan2_(float y, float x) { return atan2f(y, x); }
+__device__ __forceinline__ Dual fatan2_(Dual y, Dual x) { return datan2(y, x); }
+template <typename T>
+__device__ __forceinline__ T dot3(const T (&a)[3], const T (&b)[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
+template <typename T>
+__device__ __forceinline__ void cross3(const T (&a)[3], const T (&b)[3], T (&c)[3]) {
+    c[0] = a[1] * b[2] - a[2] * b[1];
+    c[1] = a[2] * b[0] - a[0] * b[2];
+    c[2] = a[0] * b[1] - a[1] * b[0];
+}
+
 }  // namespace

@@ -724,9 +724,18 @@ class BondPotentials(_BondedTerm):
 
 class AnglePotentials(_BondedTerm):
     """Harmonic angle term 1/2 k (theta - theta0)^2 over triples (i, j, k) centred on j
-    (torchmd/interface.py:457-510)."""
+    (torchmd/interface.py:457-510).
+
+    With b1 = x_i - x_j and b2 = x_k - x_j (each re-imaged with topology.get_offsets on cell.diag()) the angle is
+    theta = atan2(|b1 x b2|, b1.b2) and d theta/db comes from the cross product: the reference's acos(b1.b2 / sqrt(|b1|^2 |b2|^2))
+    loses ~2.5e-7 / sin^2 theta of the force in float32 and divides by zero at collinearity; this form stays accurate for a
+    stiff chain (theta0 = pi) down to sin theta ~ 1e-5.  A term with |b1 x b2|^2 <= eps^2 |b1|^2 |b2|^2, eps = 2^-20 (three
+    collinear atoms -- a rod built along an axis --, or a bond vector of length zero), keeps its energy (theta = 0 or pi) and
+    contributes zero force and zero H.w: theta has a kink there, zero is its symmetric subgradient (the convention of
+    csrc/adf.hip and DihedralPotentials).  The HIP kernel and `_torch_energy` are the same function."""
 
     _kind = _lib.BONDED_ANGLE
+    _eps = 2.0 ** -20
 
     def __init__(self, system, top, k, thetao):
         super().__init__(system, top)
@@ -740,8 +749,12 @@ class AnglePotentials(_BondedTerm):
         b2 = xyz[self.top[:, 2]] - xyz[self.top[:, 1]]
         b1 = b1 + get_offsets(b1, self.cell, self.device) * self.cell
         b2 = b2 + get_offsets(b2, self.cell, self.device) * self.cell
-        cos = (b1 * b2).sum(-1) / (b1.pow(2).sum(-1) * b2.pow(2).sum(-1)).sqrt()
-        return 0.5 * self.k * (torch.acos(cos) - self.thetao).pow(2).sum(-1)
+        C, dot = torch.cross(b1, b2, dim=-1).pow(2).sum(-1), (b1 * b2).sum(-1)
+        regular = C > self._eps ** 2 * b1.pow(2).sum(-1) * b2.pow(2).sum(-1)
+        one = torch.ones_like(C)
+        theta = torch.where(regular, torch.atan2(torch.where(regular, C, one).sqrt(), torch.where(regular, dot, one)),
+                            torch.atan2(C.detach().sqrt(), dot.detach()))            # collinear: 0 or pi, no gradient
+        return 0.5 * self.k * (theta - self.thetao).pow(2).sum(-1)
 
 
 class DihedralPotentials(_StaticTerm, torch.nn.Module):

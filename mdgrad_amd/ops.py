@@ -274,7 +274,9 @@ class PairEnergyFn(torch.autograd.Function):
 class BondedTable:
     """Static topology table of a bonded term for mdg_bonded_eval (csrc/bonded.hip): `top` [n_terms, 2 | 3] atom indices
     (torchmd/interface.py:406-510) as int32 on the device, plus the incidence list of every atom -- entries
-    4 * term + role, ascending per atom -- built once on the host."""
+    4 * term + role, ascending per atom -- built once on the host.  Negative indices count from the end; indices outside
+    [0, n_atoms) and rows that name an atom twice (a bond i == j, a repeated atom in an angle) are refused; duplicate rows are
+    kept, each a term of its own."""
 
     def __init__(self, kind, top, n_atoms, cell_len, k, x0, device):
         import numpy as np
@@ -283,6 +285,9 @@ class BondedTable:
         t = np.where(t < 0, t + n_atoms, t)                      # (the reference's xyz[top] accepts negative indices)
         if t.size and (t.min() < 0 or t.max() >= n_atoms):
             raise ValueError("mdgrad_amd: bonded topology refers to atoms outside [0, %d)" % n_atoms)
+        s = np.sort(t, axis=1)
+        if t.size and bool((s[:, 1:] == s[:, :-1]).any()):
+            raise ValueError("mdgrad_amd: a bonded row names the same atom twice")
         self.kind, self.n_atoms, self.n_terms = int(kind), int(n_atoms), int(t.shape[0])
         atoms = t.reshape(-1)
         codes = (4 * np.repeat(np.arange(self.n_terms), width) + np.tile(np.arange(width), self.n_terms)).astype(np.int64)
@@ -312,6 +317,8 @@ def bonded_eval(tab, xyz, w=None, energy=False, grad=True, into=None, scale=1.0)
     hw = None
     if w is not None:
         require_gpu(w, "w")
+        if w.shape != (N, 3):
+            raise ValueError("mdgrad_amd: w must be [%d, 3] (got %s)" % (N, tuple(w.shape)))
         w = w.contiguous()
         hw = into[1] if acc else torch.empty(N, 3, device=dev)
     check(lib.mdg_bonded_eval(ptr(xyz), N, tab.cell_len, tab.kind, ptr(tab.top), tab.n_terms, tab.k, tab.x0, ptr(tab.inc_ptr),

@@ -195,6 +195,10 @@ int mdg_pair_eval_ell_into(const float* pos, int n_atoms, const MdgCell* cell /*
  *   g_* are dL/d(frames) (any may be NULL = zeros); outputs adj_v0,adj_q0 [R,N,3],
  *   adj_pv0 [R,C], adj_theta [R,K] (sum over R on the caller's side; for an MDG_PAIR_TABLE term only that sum is
  *   defined: the wave-per-replica kernels hand the table gradient of eight replicas to the first one's row).
+ *   Where the wave-per-replica kernels run (mdg_traj_ring_taken) adj_v0 / adj_q0 may be NULL too -- a caller that wants
+ *   adj_theta alone: the launch then leaves out the work that only they need, and, where g_v is NULL, the Hessian-vector
+ *   product of the last interval's first evaluation, whose direction is zero (MDG_RING_SKIP_UNREAD=0 in the environment
+ *   keeps all of that work; adj_theta is the same bits either way).  Every other route refuses NULL adj_v0 / adj_q0.
  * nonfinite (optional int32[R]): set to 1 for replicas whose state became non-finite.
  */
 typedef struct MdgTrajParams {

@@ -14,9 +14,12 @@
 //     the visitors' accumulators, which travel with them from lane to lane (ds_bpermute_b32: the LDS crossbar,
 //     no VALU slot).  The visitors' positions and adjoint direction w are read from a 3 KB LDS copy written once
 //     per evaluation (conflict-free ds_read_b64).  Steps 1..(nl-1)/2 cover every pair of lanes once; step 0 (the
-//     pair inside a lane) and, for even nl, the antipodal step nl/2 (lanes that meet from both sides) are
-//     evaluated in both directions without the travelling update.  Afterwards one more bpermute brings the
-//     travelling accumulators home.  N = 108: 55 packed pair operations per evaluation instead of 2 x 54.
+//     pair inside a lane) is evaluated in both directions without the travelling update.  For even nl the
+//     antipodal step nl/2 (lanes that meet from both sides) costs ONE operation per lane: the lower lane of the
+//     two takes the straight pairs, the upper one the crossed pairs, and each hands the visitors' sums to its
+//     antipode (the masked and multi-term sweeps keep the directed form: both lanes evaluate all four pairs).
+//     Afterwards one more bpermute brings the travelling accumulators home.  N = 108: 54 packed pair operations
+//     per evaluation -- one per lane and step, the minimum -- instead of 2 x 54.
 //     (A 64-lane ring rotated by DPP wave_ror:1 -- full rate, tools/micro/dpp_rot.hip -- spends 65 operations
 //     and 24 VALU moves per step: measured slower.)
 //   * sums over atoms (kinetic energy, lam.v, the two LJ parameter sums) are wave reductions; the Nose-Hoover
@@ -57,6 +60,9 @@ __device__ __forceinline__ f32x2 min_image_diag2_near_fused(f32x2 d, float invf,
 struct Vec3x2 { f32x2 x, y, z; };
 __device__ __forceinline__ Vec3x2 vzero() { const f32x2 z = {0.f, 0.f}; return Vec3x2{z, z, z}; }
 __device__ __forceinline__ Vec3x2 ring_move(const Vec3x2& a, int s) { return Vec3x2{ring_move(a.x, s), ring_move(a.y, s), ring_move(a.z, s)}; }
+// the two halves exchanged where c holds (c may differ from lane to lane: two selects per register pair)
+__device__ __forceinline__ f32x2 ring_swap_if(bool c, f32x2 v) { return f32x2{c ? v.y : v.x, c ? v.x : v.y}; }
+__device__ __forceinline__ Vec3x2 ring_swap_if(bool c, const Vec3x2& a) { return Vec3x2{ring_swap_if(c, a.x), ring_swap_if(c, a.y), ring_swap_if(c, a.z)}; }
 
 // ------------------------------------------------------------------------------------------------ pair sweep
 struct RingLJ {
@@ -415,10 +421,40 @@ __device__ __forceinline__ void ring_sweep(const RingLJ& K, const RingRdf& X, co
             const uint32_t b0 = ring_mask_word(M.w, idx >> 4) >> (2 * (idx & 15)), b1 = ring_mask_word(M.w + 4, idx >> 4) >> (2 * (idx & 15));
             ms0 = s0 && (b0 & 1u); mc0 = c0 && (b0 & 2u); mc1 = c1 && (b1 & 1u); ms1 = s1 && (b1 & 2u);
         }
-        const bool once = RDF == 2 || 2 * lane < nl;
-        Vec3x2 fu = vzero(), gu = vzero(), ru = vzero();
-        ring_pair<LEVEL, IMAGE, false, false, RDF, KIND, SUMS>(K, X, q, w, qj, wj, ms0, ms1, s0 && once, s1 && once, fi, gi, fu, gu, D, ri, ru);
-        ring_pair<LEVEL, IMAGE, true, false, RDF, KIND, SUMS>(K, X, q, w, qj, wj, mc0, mc1, c0 && once, c1 && once, fi, gi, fu, gu, D, ri, ru);
+        if constexpr (MASK) {
+            // the masked term keeps the directed form: both lanes evaluate all four pairs, the visitors are not updated
+            // (the lower lane of the two feeds the histogram)
+            const bool once = RDF == 2 || 2 * lane < nl;
+            Vec3x2 fu = vzero(), gu = vzero(), ru = vzero();
+            ring_pair<LEVEL, IMAGE, false, false, RDF, KIND, SUMS>(K, X, q, w, qj, wj, ms0, ms1, s0 && once, s1 && once, fi, gi, fu, gu, D, ri, ru);
+            ring_pair<LEVEL, IMAGE, true, false, RDF, KIND, SUMS>(K, X, q, w, qj, wj, mc0, mc1, c0 && once, c1 && once, fi, gi, fu, gu, D, ri, ru);
+        } else {
+            // each pair once: the lower lane of the two (lane < nl/2) takes the straight pairs, the upper one the crossed
+            // pairs -- through the SAME straight operation, on visitor operands whose halves it has swapped (selects on a
+            // lane-dependent condition: op_sel cannot differ between lanes).  The operation updates fresh visitor
+            // accumulators; the upper lane swaps them back, and each lane hands them to the lane they belong to -- its
+            // antipode, which is the lane it has just read -- in one ds_bpermute_b32 per register.  The pairs count as
+            // undirected ones (S), and every lane deposits both of its pairs in the histogram.
+            const bool up = 2 * lane >= nl;
+            qj.x = ring_swap_if(up, qj.x); qj.y = ring_swap_if(up, qj.y); qj.z = ring_swap_if(up, qj.z);
+            if constexpr (LEVEL >= 2) { wj.x = ring_swap_if(up, wj.x); wj.y = ring_swap_if(up, wj.y); wj.z = ring_swap_if(up, wj.z); }
+            const bool a0 = FULL || (up ? c0 : s0), a1 = FULL || (up ? c1 : s1);
+            const int mate = (FULL || lane < nl) ? idx * 4 : lane * 4;     // (a lane without atoms keeps its own zeros)
+            Vec3x2 fa = vzero(), ga = vzero(), ra = vzero();
+            ring_pair<LEVEL, IMAGE, false, true, RDF, KIND, SUMS>(K, X, q, w, qj, wj, a0, a1, a0, a1, fi, gi, fa, ga, S, ri, ra);
+            if constexpr (ring_level_force(LEVEL)) {
+                fa = ring_move(ring_swap_if(up, fa), mate);
+                fi.x += fa.x; fi.y += fa.y; fi.z += fa.z;
+            }
+            if constexpr (LEVEL >= 2) {
+                ga = ring_move(ring_swap_if(up, ga), mate);
+                gi.x += ga.x; gi.y += ga.y; gi.z += ga.z;
+            }
+            if constexpr (RDF == 2) {
+                ra = ring_move(ring_swap_if(up, ra), mate);
+                ri.x += ra.x; ri.y += ra.y; ri.z += ra.z;
+            }
+        }
     }
     }
     // the travelling accumulators are nsteps lanes ahead of their owners
@@ -945,7 +981,23 @@ __device__ __forceinline__ void ring_adj_intervals(const TrajArgs& A, const Ring
             if constexpr (NHC) ring_park(park, 0, lane, lv);          // (NVE: w IS lv, live through the sweep anyway)
             ring_park(park, 1, lane, lq);
         }
-        ring_force_terms<FT ? 3 : 2, RDF ? 2 : 0, KIND, MASK, NT, !NHC>(K, X, M, with_rdf, N, lane, q, w, f, dq, th, rq, lds);
+        // The last interval without an incoming dL/dv_{T-1} (A.g_v null): lam_v = 0, so w = 0 and this evaluation's H.w and
+        // parameter sums vanish -- what is left of it is the fused observable's frame gradient, the geometry-only sweep
+        // of frame 0.  dq = -0 is what the full sweep returns for w = 0 (g = -(+0)): lam_q + dq h/2 keeps the bits of lam_q.
+        // (Where the force is read back, FT: without it the evaluation has the force to build.)
+        constexpr bool COLD_OK = FT && NT == 1 && KIND != KIND_TABLE;
+        const bool cold = COLD_OK && A.skip_unread && !A.g_v && i == T - 1;
+        if (cold) {
+            if constexpr (COLD_OK) {
+                ring_force<0, RDF ? 2 : 0, KIND, MASK>(K[0], X, M[0], with_rdf, N, lane, q, w, f, dq, th[0], rq, lds);
+                const f32x2 nz = {-0.f, -0.f};
+                dq = Vec3x2{nz, nz, nz};
+#pragma unroll
+                for (int k = 0; k < MDG_MAX_THETA; ++k) th[0][k] = 0.f;
+            }
+        } else {
+            ring_force_terms<FT ? 3 : 2, RDF ? 2 : 0, KIND, MASK, NT, !NHC>(K, X, M, with_rdf, N, lane, q, w, f, dq, th, rq, lds);
+        }
         if constexpr (PARK) {
             if constexpr (NHC) lv = ring_unpark(park, 0, lane); else lv = w;
             lq = ring_unpark(park, 1, lane);
@@ -1107,7 +1159,8 @@ void traj_adj_ring_kernel(const TrajArgs A, const RingRdfArgs F) {
     if (nhc) ring_adj_intervals<true, RDF, KIND, MASK, NT, FT>(A, F, K, X, M, live, fr, lane, lds, lv, lq, lp, gth);
     else ring_adj_intervals<false, RDF, KIND, MASK, NT, FT>(A, F, K, X, M, live, fr, lane, lds, lv, lq, lp, gth);
     if constexpr (RDF) {
-        if (ring_frame_selected(F, 0)) {                              // frame 0: no force evaluation there
+        // (its only reader is adj_q0: without that output the sweep is left out, TrajArgs::skip_unread)
+        if (ring_frame_selected(F, 0) && (A.adj_q0 || !A.skip_unread)) {       // frame 0: no force evaluation there
             const Vec3x2 q = ring_load(A.q_t + fr * N3, N, lane), wu = vzero();
             Vec3x2 fu, gu, rq = vzero();
             float tu[MDG_MAX_THETA];
@@ -1116,8 +1169,8 @@ void traj_adj_ring_kernel(const TrajArgs A, const RingRdfArgs F) {
         }
     }
     if (live) {
-        ring_store(A.adj_v0 + (size_t)rep * N3, lv, N, lane);
-        ring_store(A.adj_q0 + (size_t)rep * N3, lq, N, lane);
+        if (A.adj_v0) ring_store(A.adj_v0 + (size_t)rep * N3, lv, N, lane);
+        if (A.adj_q0) ring_store(A.adj_q0 + (size_t)rep * N3, lq, N, lane);
         if (nhc && lane < C && A.adj_pv0) A.adj_pv0[(size_t)rep * C + lane] = lp;
     }
     if constexpr (KIND == KIND_TABLE) {

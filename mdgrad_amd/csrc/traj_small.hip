@@ -45,6 +45,10 @@ struct TrajArgs {
     // every axis has one.  Without it the even-N replicas run the window sweep with its per-pair flags, as with lean = 0.
     float inv_f[3];
     int fused_image;
+    // ring adjoint only: leave out the work whose results nobody reads -- the geometry-only sweep of frame 0 where adj_q0 is
+    // null, and H.w of the last interval's first evaluation where g_v is null (its direction w is zero).  Set where the
+    // launch is built, from MDG_RING_SKIP_UNREAD (=0: all of it is computed as before, null outputs are just not stored)
+    int skip_unread;
 };
 
 constexpr int KMAX_ALL = MDG_MAX_TERMS * MDG_MAX_THETA;
@@ -915,6 +919,10 @@ int ring_lean() {
     static const int lean = [] { const char* e = getenv("MDG_RING_LEAN"); return !(e && e[0] == '0') ? 1 : 0; }();
     return lean;
 }
+int ring_skip_unread() {
+    static const int skip = [] { const char* e = getenv("MDG_RING_SKIP_UNREAD"); return !(e && e[0] == '0') ? 1 : 0; }();
+    return skip;
+}
 // The multiplier of min_image_diag2_near_fused (traj_ring.hpp) for one axis of an orthorhombic cell: a float c for which
 // rint of the exact product d c picks the image that rint(fl(d inv)) picks, for every float d with |d inv| < 1.5.
 // fl(d inv) is monotone in d, so the rounded form leaves image 0 at one float tau, the smallest d > 0 with fl(d inv) > 0.5
@@ -1217,7 +1225,8 @@ int traj_fwd_small_run(const MdgTrajParams* prm, const MdgCell* cell, const MdgT
 }
 
 // The adjoint launch behind every mdg_traj_adj_small* entry point; routes as traj_fwd_small_run.  (adj_pv0 is not among the
-// required buffers: no entry point of this file ever asked for it.)
+// required buffers: no entry point of this file ever asked for it.  The ring kernels take null adj_v0 / adj_q0 as well -- a
+// caller that differentiates with respect to the parameters only -- and then skip what only those outputs need.)
 int traj_adj_small_run(const MdgTrajParams* prm, const MdgCell* cell, const MdgTerms* terms,
                        const float* theta, const float* mass, const float* t_grid,
                        const float* v_t, const float* q_t, const float* pv_t,
@@ -1227,8 +1236,9 @@ int traj_adj_small_run(const MdgTrajParams* prm, const MdgCell* cell, const MdgT
     if (rc) return rc;
     const char* who = small_who(true, o);
     const bool stale = o.extra == SmallOpt::STALE, rdf = o.extra == SmallOpt::RDF;
+    const bool ring = rdf || (!stale && use_ring(*prm, *cell, *terms));
     // (theta / dL/d(raw): per entry point, as in traj_fwd_small_run)
-    MDG_CHECK_ARG(mass && t_grid && v_t && q_t && adj_v0 && adj_q0 &&
+    MDG_CHECK_ARG(mass && t_grid && v_t && q_t && (ring || (adj_v0 && adj_q0)) &&
                   (!rdf || ((theta || terms->n_theta_total == 0) && o.g_raw)), "%s: null buffer", who);
     MDG_CHECK_ARG(prm->ensemble == 1 || pv_t, "%s: NHC needs pv_t", who);
     RdfFinePlan P;
@@ -1239,9 +1249,9 @@ int traj_adj_small_run(const MdgTrajParams* prm, const MdgCell* cell, const MdgT
     a.g_v = g_v; a.g_q = g_q; a.g_pv = g_pv;
     a.adj_v0 = adj_v0; a.adj_q0 = adj_q0; a.adj_pv0 = adj_pv0; a.adj_theta = adj_theta;
     hipStream_t st = (hipStream_t)stream;
-    if (rdf || (!stale && use_ring(*prm, *cell, *terms))) {
+    if (ring) {
         MDG_CHECK_ARG(theta || terms->n_theta_total == 0, "%s: null theta", who);
-        a.f_t = o.f_t; a.lean = ring_lean(); set_fused_image(a);
+        a.f_t = o.f_t; a.lean = ring_lean(); a.skip_unread = ring_skip_unread(); set_fused_image(a);
         if (!rdf) {
             // (tabulated kind: RING_TABLE_WAVES replicas per workgroup share the nodes and one pair of gradient planes)
             const bool rt = terms->t[0].kind == MDG_PAIR_TABLE;

@@ -1338,6 +1338,9 @@ class FusedTrajFn(torch.autograd.Function):
     def forward(ctx, v0, q0, pv0, t, theta, spec, fuse=False):
         lib = _lib.load()
         require_gpu(v0, "v0"), require_gpu(q0, "q0"), require_gpu(t, "t")
+        # the gradient of an output the loss does not use arrives as None, not as a trajectory-sized block of zeros that
+        # the adjoint launch would read frame by frame (its g_v / g_q / g_pv are nullable)
+        ctx.set_materialize_grads(False)
         batched = v0.dim() == 3
         R = v0.shape[0] if batched else 1
         N, T = spec.n_atoms, t.shape[0]
@@ -1466,9 +1469,12 @@ class FusedTrajFn(torch.autograd.Function):
             gq = torch.zeros_like(q_t) if gq is None else gq.clone()
             gq[:, fuse.start::fuse.stride] += gsel
             g_raw = None
-        adj_v = torch.empty(R, N, 3, device=dev)
-        adj_q = torch.empty(R, N, 3, device=dev)
-        adj_p = torch.empty(R, len(spec.Q), device=dev) if nhc else None
+        # a fit of the potential's parameters never asks for the gradient of the initial state: the ring adjoint (the route
+        # that kept the forces) then takes null outputs and skips the work only they need; the other routes always fill them
+        want_state = any(ctx.needs_input_grad[0:3]) or ctx.f_t is None
+        adj_v = torch.empty(R, N, 3, device=dev) if want_state else None
+        adj_q = torch.empty(R, N, 3, device=dev) if want_state else None
+        adj_p = torch.empty(R, len(spec.Q), device=dev) if nhc and want_state else None
         KT = spec.n_theta_total
         adj_th = torch.zeros(R, KT, device=dev) if KT else None
         prm = spec.params(R, T)
@@ -1546,7 +1552,7 @@ class FusedTrajFn(torch.autograd.Function):
             flags = launch(spec.terms)
             if flags is not None:
                 check_large(flags)
-        if not ctx.batched:
+        if not ctx.batched and want_state:
             adj_v, adj_q = adj_v[0], adj_q[0]
             adj_p = adj_p[0] if nhc else None
         gth = adj_th.sum(0) if adj_th is not None else None

@@ -396,8 +396,37 @@ int mdg_rdf_fwd(const float* xyz, int n_frames, int n_atoms, const MdgCell* cell
                 float cutoff, const uint8_t* mask, const float* mu /*[nbins]*/, float coeff,
                 int nbins, float* raw, float* partial, void* stream);
 /* same, with the caller's guarantee that mu is an equally spaced grid (mu_k = mu[0] + k*spacing, as
- * torch.linspace gives): enables the recurrence kernels (one lane per pair with wave-private LDS
- * histograms when there are >= 1024 frames, 8 bins per thread otherwise). */
+ * torch.linspace gives).  Forward, in order of preference (mdg_rdf_fwd_variant tells which one a shape takes):
+ *   FINE    >= 1024 frames of 64 .. 1024 atoms whose fine grid fits the LDS: pairs counted on a fine integer
+ *           histogram, smeared onto the centres once;
+ *   HALF    >= 1024 frames, <= 4096 atoms, s*spacing in [0.8455, 1.5] and ~120 bins at most: one wave per frame,
+ *           one lane per pair, half-width lane-private LDS columns, eight waves per workgroup;
+ *   LANE    >= 1024 frames, <= 4096 atoms, s*spacing >= 0.405: the same with full-width columns (reach 5 or 11 bins);
+ *   BLOCK8  s*spacing <= 1 and >= 16 bins: persistent workgroups, 8 bins per thread with the Gaussian recurrence;
+ *   DIRECT  everything else, and every call of mdg_rdf_fwd: one bin per thread.
+ * (s = sqrt(-coeff log2 e).)  More than 512 bins are refused.  Backward (mdg_rdf_bwd_variant):
+ *   ATOM    fewer than 1024 frames or more than 4096 atoms: 16 lanes per (frame, atom);
+ *   TABLE   s*spacing in [0.465, 1] and at most 4096 table nodes: one wave per frame, dL/dd from a cubic-Hermite table;
+ *   FRAME   otherwise: one wave per frame, bin recurrence over 6 or 11 bins each side (s*spacing >= 0.465) or the
+ *           direct sum; refused when a frame does not fit the LDS.
+ * A scratch allocation that fails is MDG_ELAUNCH in both directions. */
+#define MDG_RDF_FWD_DIRECT 0
+#define MDG_RDF_FWD_BLOCK8 1
+#define MDG_RDF_FWD_LANE   2
+#define MDG_RDF_FWD_HALF   3
+#define MDG_RDF_FWD_FINE   4
+#define MDG_RDF_BWD_ATOM   0
+#define MDG_RDF_BWD_TABLE  1
+#define MDG_RDF_BWD_FRAME  2
+#define MDG_RDF_PLAN_INFO  6
+/* Host only, no launch: the variant the shape takes (spacing <= 0: no guarantee on mu), or -1 where the launch would
+ * refuse it.  info, when not NULL, receives MDG_RDF_PLAN_INFO words: {reach in bins, waves per workgroup, workgroups,
+ * dynamic LDS bytes, row stride of the LDS coordinates, forward: 1 when that stride is the compile-time 128 /
+ * backward: cells of the derivative table}. */
+int mdg_rdf_fwd_variant(int n_frames, int n_atoms, int nbins, float spacing, float coeff, int diag, int masked,
+                        int32_t* info);
+int mdg_rdf_bwd_variant(int n_frames, int n_atoms, int nbins, float spacing, float coeff, int diag, int masked,
+                        int32_t* info);
 int mdg_rdf_fwd_uniform(const float* xyz, int n_frames, int n_atoms, const MdgCell* cell /*host*/,
                         float cutoff, const uint8_t* mask, const float* mu, float spacing, float coeff,
                         int nbins, float* raw, float* partial, void* stream);

@@ -4,18 +4,19 @@
 // backward through it.  The [pairs, bins] exp matrix of the reference is never
 // materialised.
 //
-// forward : few frames / arbitrary centres -- persistent blocks stride over (frame, candidate chunk) work
-//           items, compact the accepted i<j distances into LDS in a fixed order, thread k owns bin k (or
-//           an 8-bin block with the Gaussian recurrence) and sweeps them (rdf_fwd_kernel,
-//           rdf_fwd_block8_kernel).  Many frames, equally spaced centres (the replica-batched training
-//           shape) -- one wave per frame, one lane per pair, lane-private LDS histogram columns
-//           (rdf_fwd_half_kernel / rdf_fwd_lane_kernel).  Per-block / per-wave partial histograms are added
-//           by a second kernel in a fixed order => no atomics, reproducible.  exp is v_exp_f32.
-// backward: each accepted pair contributes dL/dd = sum_k g_raw[k] * 2 coeff (d - mu_k) e_k along +/- its
-//           unit separation vector.  Many frames: one wave per frame, dL/dd from a fine table, cyclic pair
-//           order with one end's gradient in registers (rdf_bwd_fine_kernel) or the bin recurrence in
-//           round-robin-tournament order (rdf_bwd_kernel); few frames: (frame, atom) gather
-//           (rdf_bwd_atom_kernel).  LDS accumulation without atomics.
+// forward : rdf_fwd_plan (host side, end of this file) picks, in this order: fine -- >= 1024 frames of 64 .. 1024 atoms,
+//           equally spaced centres: pairs counted on a fine integer histogram per workgroup, smeared onto the centres once
+//           (rdf_fwd_fine_kernel); half / lane -- >= 1024 frames, equally spaced centres: one wave per frame, one lane per
+//           pair, lane-private LDS histogram columns of half or full width (rdf_fwd_half_kernel, rdf_fwd_lane_kernel);
+//           block8 / direct -- few frames or arbitrary centres: persistent blocks stride over (frame, candidate chunk) work
+//           items, compact the accepted i<j distances into LDS in a fixed order, a thread owns an 8-bin block with the
+//           Gaussian recurrence (rdf_fwd_block8_kernel) or bin k (rdf_fwd_kernel).  Partial histograms are added by a
+//           second kernel in a fixed order, integer counts commute => no float atomics, reproducible.  exp is v_exp_f32.
+// backward: each accepted pair contributes dL/dd = sum_k g_raw[k] * 2 coeff (d - mu_k) e_k along +/- its unit separation
+//           vector.  rdf_bwd_plan: table / frame -- many frames, one wave per frame, dL/dd from a fine table, cyclic pair
+//           order with one end's gradient in registers (rdf_bwd_fine_kernel) or the bin recurrence in round-robin-
+//           tournament order (rdf_bwd_kernel); atom -- few frames, (frame, atom) gather (rdf_bwd_atom_kernel).  LDS
+//           accumulation without atomics.  mdg_rdf_fwd_variant / mdg_rdf_bwd_variant report the plan of a shape.
 #include "common.hpp"
 #include <type_traits>
 
@@ -41,7 +42,7 @@ __device__ __forceinline__ void pair_from_flat(long long c, int N, int& i, int& 
 //
 // Thread layout: nbins <= RDF_BLOCK.  G = RDF_BLOCK / nbins thread groups; thread (g, k) owns
 // bin k and sweeps the compacted distances 4g..4g+3, 4(g+G).., ... (ds_read_b128); the groups
-// are combined in group order at the end.  Bins beyond RDF_BLOCK are handled by the slow path.
+// are combined in group order at the end.  More than RDF_BLOCK bins are refused (rdf_fwd_impl).
 template <bool DIAG>
 __global__ __launch_bounds__(RDF_BLOCK) void rdf_fwd_kernel(
     const float* __restrict__ xyz, int nF, int N, MdgCell cell, float rc2, const uint8_t* __restrict__ mask,
@@ -646,22 +647,28 @@ __device__ __forceinline__ FineGrid fine_grid(const float* __restrict__ mu, int 
     return G;
 }
 
-// node table of dL/dd: tab[n] = (sum_k sg_k x e , hf * d/dd of that), x = s (x_n - mu_k), e = exp2(-x^2)
-__device__ __forceinline__ float2 rdf_fine_node(const FineGrid& G, const float* __restrict__ mu, float coeff, int nbins,
-                                                const float* __restrict__ g_raw, int R, int n) {
+// S = dL/dd = sum_k sg_k x e and S' = dS/dd at the distance r, x = s (r - mu_k), e = exp2(-x^2), over the 2R + 3 centres
+// around the nearest one: the node value of both derivative tables
+__device__ __forceinline__ float2 rdf_node_sum(const float* __restrict__ mu, float coeff, int nbins,
+                                               const float* __restrict__ g_raw, int R, float r) {
     const float sc = sqrtf(-coeff * LOG2E);
     const float mu0 = mu[0], dmu = (mu[nbins - 1] - mu0) / (float)(nbins - 1);
-    const float x = fmaf((float)n, G.hf, G.xlo);
-    const int kc = (int)rintf((x - mu0) / dmu);
+    const int kc = (int)rintf((r - mu0) / dmu);
     float val = 0.f, der = 0.f;
     for (int k = max(0, kc - R - 1); k <= min(nbins - 1, kc + R + 1); ++k) {
-        const float xs = (x - mu[k]) * sc;
+        const float xs = (r - mu[k]) * sc;
         const float e = __builtin_amdgcn_exp2f(-xs * xs);
         const float sg = g_raw[k] * 2.f * coeff / sc;
         val = fmaf(sg * xs, e, val);
         der = fmaf(sg * sc * (1.f - 2.f * 0.69314718056f * xs * xs), e, der);
     }
-    return make_float2(val, der * G.hf);
+    return make_float2(val, der);
+}
+// node table of dL/dd: tab[n] = (S, hf S') at x_n
+__device__ __forceinline__ float2 rdf_fine_node(const FineGrid& G, const float* __restrict__ mu, float coeff, int nbins,
+                                                const float* __restrict__ g_raw, int R, int n) {
+    const float2 s_ = rdf_node_sum(mu, coeff, nbins, g_raw, R, fmaf((float)n, G.hf, G.xlo));
+    return make_float2(s_.x, s_.y * G.hf);
 }
 // cell n = nodes n and n + 1: the cubic Hermite interpolant of {value, hf slope} at both ends, stored as its
 // monomial coefficients in the cell coordinate f in [0, 1) (c0 + f (c1 + f (c2 + f c3)): three fma per pair)
@@ -683,21 +690,11 @@ __global__ void rdf_bwd_table_u_kernel(const float* __restrict__ mu, float coeff
     rdf_u_grid(mu, nbins, R, ulo, hu, ncell);
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= ncell) return;
-    const float sc = sqrtf(-coeff * LOG2E);
-    const float mu0 = mu[0], dmu = (mu[nbins - 1] - mu0) / (float)(nbins - 1);
     auto node = [&](int m) {
         const float r = sqrtf(fmaf((float)m, hu, ulo));
-        const int kc = (int)rintf((r - mu0) / dmu);
-        float val = 0.f, der = 0.f;                                  // S and dS/dd, as rdf_fine_node
-        for (int k = max(0, kc - R - 1); k <= min(nbins - 1, kc + R + 1); ++k) {
-            const float xs = (r - mu[k]) * sc;
-            const float e = __builtin_amdgcn_exp2f(-xs * xs);
-            const float sg = g_raw[k] * 2.f * coeff / sc;
-            val = fmaf(sg * xs, e, val);
-            der = fmaf(sg * sc * (1.f - 2.f * 0.69314718056f * xs * xs), e, der);
-        }
+        const float2 s_ = rdf_node_sum(mu, coeff, nbins, g_raw, R, r);
         const float ir = 1.0f / r;
-        return make_float2(val * ir, hu * (der * ir - val * ir * ir) * (0.5f * ir));
+        return make_float2(s_.x * ir, hu * (s_.y * ir - s_.x * ir * ir) * (0.5f * ir));
     };
     const float2 a_ = node(n), b_ = node(n + 1);
     tab[n] = make_float4(a_.x, a_.y, 3.f * (b_.x - a_.x) - 2.f * a_.y - b_.y, 2.f * (a_.x - b_.x) + a_.y + b_.y);
@@ -1168,6 +1165,39 @@ __global__ void rdf_bwd_atom_kernel(const float* __restrict__ xyz, int nF, int N
 
 }  // namespace
 
+// ---------------------------------------------------------------------------------------------------------
+// Host side.  Every entry point checks its arguments, plans and launches.  A plan (RdfFwdPlan, RdfBwdPlan) is a pure
+// function of the shape -- no HIP call -- that names the kernel variant and holds everything its launch needs.  What a
+// variant cannot do (LDS, table sizes) is kept apart from what is merely preferred (many frames, enough atoms).
+constexpr size_t RDF_LDS_BUDGET = 156 * 1024;    // dynamic LDS a forward plan may ask for
+constexpr size_t RDF_LDS_MAX = 160 * 1024;       // the CU's LDS
+constexpr int RDF_MANY_FRAMES = 1024;            // from here on one wave per frame fills the chip
+
+struct RdfFrames {                               // the leading arguments of every frame kernel
+    const float* xyz; int nF, N; const MdgCell* cell; float rc2; const uint8_t* mask; const float* mu; float coeff; int nbins;
+    hipStream_t st;
+};
+template <class K, class... Tail>
+static void rdf_launch(K kernel, int grid, int block, size_t lds, const RdfFrames& a, Tail... tail) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, a.st, a.xyz, a.nF, a.N, *a.cell, a.rc2, a.mask, a.mu, a.coeff,
+                       a.nbins, tail...);
+}
+
+// f(DIAG, MASKED, PX, R) with compile-time constants, for exactly the combinations the kernels are built for: a reach
+// out of Rs; 128-column coordinate rows (PX = 128: immediate LDS offsets) for the common shape, orthorhombic without a
+// mask, and the run-time stride (PX = 0) for the four (DIAG, MASKED) cases otherwise.  Kernels that only distinguish
+// the cell go through rdf_dispatch<0>(diag, false, false, 0, ...).
+template <int V> using RdfInt = std::integral_constant<int, V>;
+template <int... Rs, class F>
+static void rdf_dispatch(bool diag, bool masked, bool px128, int R, F&& f) {
+    auto with_r = [&](auto d, auto m, auto px) { (void)((R == Rs && (f(d, m, px, RdfInt<Rs>{}), true)) || ...); };
+    if (px128) with_r(std::true_type{}, std::false_type{}, RdfInt<128>{});
+    else if (diag && masked) with_r(std::true_type{}, std::true_type{}, RdfInt<0>{});
+    else if (diag) with_r(std::true_type{}, std::false_type{}, RdfInt<0>{});
+    else if (masked) with_r(std::false_type{}, std::true_type{}, RdfInt<0>{});
+    else with_r(std::false_type{}, std::false_type{}, RdfInt<0>{});
+}
+
 static int rdf_grid(int n_frames, int n_atoms) {
     const long long npair = (long long)n_atoms * (n_atoms - 1) / 2;
     const long long items = (long long)n_frames * ((npair + RDF_CHUNK - 1) / RDF_CHUNK);
@@ -1177,6 +1207,11 @@ static int rdf_grid(int n_frames, int n_atoms) {
 extern "C" int64_t mdg_rdf_partial_size(int n_frames, int n_atoms, int nbins) {
     (void)n_frames; (void)n_atoms;
     return (int64_t)RDF_MAX_BLOCKS * nbins;      // one partial histogram per persistent block / wave
+}
+
+// scaled spacing Ds = s * spacing of equally spaced centres, s = sqrt(-coeff log2 e); 0: the caller makes no such statement
+static float rdf_spacing_s(float spacing, float coeff) {
+    return spacing > 0.f && coeff < 0.f ? spacing * sqrtf(-coeff * LOG2E) : 0.f;
 }
 
 // lane-per-pair kernel: reach R (bins) for the scaled spacing Ds, waves per workgroup that fit the LDS
@@ -1197,141 +1232,174 @@ static size_t rdf_lane_lds(int nw, int R, int pxld, int nbins) {
     return sizeof(float) * ((size_t)(nbins + 2 * R) + (size_t)nw * ((size_t)(nbins + 4 * R) * 64 + 3 * (size_t)pxld));
 }
 
-static int rdf_fwd_impl(const float* xyz, int n_frames, int n_atoms, const MdgCell* cell, float cutoff,
-                        const uint8_t* mask, const float* mu, float coeff, int nbins, float* raw,
-                        float* partial, float spacing_s, void* stream) {
-    MDG_CHECK_ARG(xyz && cell && mu && raw && partial, "rdf_fwd: null buffer");
-    MDG_CHECK_ARG(n_frames > 0 && n_atoms > 1 && nbins > 0, "rdf_fwd: bad sizes");
-    MDG_CHECK_ARG(nbins <= RDF_BLOCK, "rdf_fwd: nbins > %d not supported", RDF_BLOCK);
-    MDG_CHECK_ARG(coeff < 0.f, "rdf_fwd: coeff must be negative (-0.5 / width^2)");
-    const int nblocks = rdf_grid(n_frames, n_atoms);
-    hipStream_t st = (hipStream_t)stream;
-    // equally spaced centres with Ds = s * spacing <= 1: 8-bin blocks + recurrence (spacing_s is the
-    // caller's statement that mu is a linspace; <= 0 selects the direct kernel)
+// ---- shared with the fused observable of the trajectory kernels and csrc/rdf_cell.hip (common.hpp): the one sizing of
+// the fine grids for centres mu0 + k spacing and exp(coeff x^2)
+RdfFinePlan mdg_rdf_fine_plan(float spacing, float coeff, int nbins) {
+    RdfFinePlan P{};
+    if (!(spacing > 0.f) || !(coeff < 0.f) || nbins < 2) return P;
+    P.sc = sqrtf(-coeff * LOG2E);                                 // exp(coeff x^2) = exp2(-(sc x)^2)
+    P.reach = 5.3f / P.sc;                                        // beyond: below 2^-28 of the peak
+    P.h = 0.004f / P.sc;                                          // sc h = 0.004 (error bound: see rdf_fwd_fine_kernel)
+    const double span = (double)(nbins - 1) * spacing + 2.0 * P.reach;
+    const long long nfine = (long long)ceil(span / P.h) + 1;
+    P.nfine = nfine <= RDF_FINE_MAX ? nfine : 0;                  // 0: does not fit the workgroup's LDS histogram
+    const float spacing_s = spacing * P.sc;
+    const int R = rdf_lane_reach(spacing_s);
+    if (R && spacing_s <= 1.0f && fine_nodes(nbins, R) <= 4096) { P.reach_bins = R; P.ncell = fine_nodes(nbins, R) - 1; }
+    return P;
+}
+
+enum class RdfFwd { direct = MDG_RDF_FWD_DIRECT, block8 = MDG_RDF_FWD_BLOCK8, lane = MDG_RDF_FWD_LANE,
+                    half = MDG_RDF_FWD_HALF, fine = MDG_RDF_FWD_FINE };
+struct RdfFwdPlan {
+    RdfFwd variant;
+    int R, waves, grid;                  // reach in bins (lane, half), waves per workgroup, workgroups
+    size_t lds, scratch_words;           // dynamic LDS bytes; stream-ordered scratch, 32-bit words
+    int pxld; bool px128;                // lane, half, fine: row stride of the LDS coordinates; it is the compile-time 128
+    int n_entries, iters, n_padded; uint32_t pad_entry;   // lane, half: pair table entries, sweep iterations, padding
+    RdfFinePlan fine;                    // fine: nfine, h, reach of the integer histogram
+};
+static RdfFwdPlan rdf_fwd_plan(int n_frames, int n_atoms, int nbins, float spacing, float coeff, bool diag, bool masked) {
+    RdfFwdPlan P{};
+    // spacing_s is the caller's statement that mu is a linspace; 0 selects the direct kernel
+    const float spacing_s = rdf_spacing_s(spacing, coeff);
+    const bool many = n_frames >= RDF_MANY_FRAMES;
     // ---- many frames, equally spaced centres: fine integer histogram (see rdf_fwd_fine_kernel) when it fits the LDS
     // (the first-order term of the binning error averages out statistically, ~ (s h) 0.4 / sqrt(pairs near a centre):
     //  small systems -- cheap anyway -- keep the exact lane-private kernels below)
-    if (n_frames >= 1024 && nbins >= 2 && spacing_s > 0.f && n_atoms >= 64 && n_atoms <= RDF_FINE_ATOMS) {
-        const float sc = sqrtf(-coeff * LOG2E);                   // exp(coeff x^2) = exp2(-(sc x)^2)
-        const float spacing = spacing_s / sc;
-        const float reach = 5.3f / sc;                            // beyond: below 2^-28 of the peak
-        const float h = 0.004f / sc;                              // sc h = 0.004 (error bound: see the kernel)
-        const double span = (double)(nbins - 1) * spacing + 2.0 * reach;
-        const long long nfine = (long long)ceil(span / h) + 1;
-        const int ld = (n_atoms + 1) & ~1;
-        const size_t lds = sizeof(float) * ((size_t)nfine + RDF_FINE_WAVES * 3 * (size_t)ld);
-        if (nfine <= RDF_FINE_MAX && lds <= 156 * 1024) {
-            const long long npair = (long long)n_atoms * (n_atoms - 1) / 2;
-            uint32_t* scratch = nullptr;                          // [nfine] global histogram | count | pair table
-            const size_t words = (size_t)nfine + 4 + (size_t)npair + 128;
-            if (hipMallocAsync((void**)&scratch, sizeof(uint32_t) * words, st) == hipSuccess && scratch) {
-                uint32_t* ghist = scratch;
-                int32_t* count = reinterpret_cast<int32_t*>(scratch + nfine);
-                uint32_t* tab = scratch + nfine + 4;
-                MDG_HIP(hipMemsetAsync(ghist, 0, sizeof(uint32_t) * (size_t)(nfine + 4), st));
-                hipLaunchKernelGGL(rdf_fine_table_kernel, dim3(1), dim3(1024), 0, st, n_atoms, mask, tab, count);
-                int grid = (n_frames + RDF_FINE_WAVES - 1) / RDF_FINE_WAVES;
-                if (grid > 256) grid = 256;                       // one resident workgroup (16 waves) per CU
-                // (the fine grid starts at mu[0] - reach; the kernels read mu[0] themselves: no host copy)
-                if (cell->diag)
-                    hipLaunchKernelGGL(rdf_fwd_fine_kernel<true>, dim3(grid), dim3(64 * RDF_FINE_WAVES), lds, st, xyz, n_frames, n_atoms,
-                                       *cell, cutoff * cutoff, tab, count, mu, reach, 1.0f / h, (int)nfine, ld, ghist);
-                else
-                    hipLaunchKernelGGL(rdf_fwd_fine_kernel<false>, dim3(grid), dim3(64 * RDF_FINE_WAVES), lds, st, xyz, n_frames, n_atoms,
-                                       *cell, cutoff * cutoff, tab, count, mu, reach, 1.0f / h, (int)nfine, ld, ghist);
-                hipLaunchKernelGGL(rdf_fine_finish_kernel, dim3(nbins), dim3(64), 0, st, ghist, (int)nfine, h, mu, sc, reach,
-                                   nbins, raw);
-                (void)hipFreeAsync(scratch, st);
-                MDG_CHECK_LAUNCH("rdf_fwd_fine_kernel");
-                return MDG_OK;
-            }
-        }
+    P.fine = mdg_rdf_fine_plan(spacing, coeff, nbins);
+    const int ld = (n_atoms + 1) & ~1;
+    const size_t lds_fine = sizeof(float) * ((size_t)P.fine.nfine + RDF_FINE_WAVES * 3 * (size_t)ld);
+    const bool fine_can = P.fine.nfine > 0 && n_atoms <= RDF_FINE_ATOMS && lds_fine <= RDF_LDS_BUDGET;
+    if (fine_can && many && n_atoms >= 64) {
+        P.variant = RdfFwd::fine; P.waves = RDF_FINE_WAVES; P.lds = lds_fine; P.pxld = ld;
+        P.grid = min((n_frames + RDF_FINE_WAVES - 1) / RDF_FINE_WAVES, 256);   // one resident workgroup (16 waves) per CU
+        const long long npair = (long long)n_atoms * (n_atoms - 1) / 2;
+        P.scratch_words = (size_t)P.fine.nfine + 4 + (size_t)npair + 128;   // [nfine] global histogram | count | pair table
+        return P;
     }
-    const int R = n_frames >= 1024 && nbins >= 2 && n_atoms <= RDF_TABLE_MAX_ATOMS ? rdf_fwd_reach(spacing_s) : 0;
-    if (R) {
+    // ---- many frames, equally spaced centres: one wave per frame, one lane per pair
+    const int R = nbins >= 2 && n_atoms <= RDF_TABLE_MAX_ATOMS ? rdf_fwd_reach(spacing_s) : 0;
+    if (R && many) {
         // coordinate stride: even, with at least two NaN columns after the atoms for the padding entries;
         // compile-time (immediate LDS offsets) for the common shape: orthorhombic, no mask
         const int npad_col = (n_atoms + 1) & ~1;
-        const bool px128 = npad_col + 2 <= 128 && cell->diag && !mask;
-        const int pxld = px128 ? 128 : npad_col + 2;
+        P.px128 = npad_col + 2 <= 128 && diag && !masked;
+        P.pxld = P.px128 ? 128 : npad_col + 2;
         int nw = 4;
-        while (nw > 1 && rdf_lane_lds(nw, R, pxld, nbins) > 156 * 1024) nw >>= 1;
-        const size_t lds = rdf_lane_lds(nw, R, pxld, nbins);
-        int n_entries = 0;
-        for (int i = 0; i + 1 < n_atoms; ++i) n_entries += rdf_row_entries(i, n_atoms);
-        const int iters = (((n_entries + 63) / 64) + 3) & ~3;               // (the loop is unrolled by four)
-        const int n_padded = (iters + 5) * 64;
-        const uint32_t pad_entry = (uint32_t)(4 * npad_col) | ((uint32_t)(4 * npad_col) << 16);
-        uint32_t* tab = nullptr;
-        if (lds <= 156 * 1024 && hipMallocAsync((void**)&tab, sizeof(uint32_t) * (size_t)n_padded, st) == hipSuccess && tab) {
-            hipLaunchKernelGGL(rdf_pair_table_kernel, dim3(n_atoms), dim3(256), 0, st, tab, n_atoms, n_entries, n_padded,
-                               pad_entry);
+        while (nw > 1 && rdf_lane_lds(nw, R, P.pxld, nbins) > RDF_LDS_BUDGET) nw >>= 1;
+        const size_t lds = rdf_lane_lds(nw, R, P.pxld, nbins);
+        if (lds <= RDF_LDS_BUDGET) {
+            P.R = R;
+            // sum of rdf_row_entries(i, N) over the rows i < N - 1: row i holds ceil(N / 2) - floor((i + 1) / 2)
+            const int N = n_atoms;
+            P.n_entries = (N - 1) * ((N + 1) / 2) - ((N - 1) / 2) * (N / 2);
+            P.iters = (((P.n_entries + 63) / 64) + 3) & ~3;                   // (the loop is unrolled by four)
+            P.n_padded = (P.iters + 5) * 64;
+            P.pad_entry = (uint32_t)(4 * npad_col) | ((uint32_t)(4 * npad_col) << 16);
+            P.scratch_words = (size_t)P.n_padded;
             // half-width columns, eight waves per workgroup, when they fit (R = 5, 100 bins: 137 KB)
             const size_t rows_h = (size_t)((nbins + 4 * R + 3) & ~1);
-            const size_t lds_half = sizeof(float) * (rows_h + 8 * (rows_h * 32 + 3 * (size_t)pxld));
+            const size_t lds_half = sizeof(float) * (rows_h + 8 * (rows_h * 32 + 3 * (size_t)P.pxld));
             // (spacing_s <= 1.5: the recurrence multipliers of a rejected pair, y0 clamped to 20, stay finite)
-            if (R == 5 && spacing_s <= 1.5f && lds_half <= 156 * 1024) {
-                int gridh = (n_frames + 7) / 8;
-                if (gridh > RDF_MAX_BLOCKS / 8) gridh = RDF_MAX_BLOCKS / 8;
-#define MDG_RDF_HALF(D, MK, PX)                                                                                        \
-    hipLaunchKernelGGL((rdf_fwd_half_kernel<D, 5, MK, PX>), dim3(gridh), dim3(512), lds_half, st, xyz, n_frames,       \
-                       n_atoms, *cell, cutoff * cutoff, mask, mu, coeff, nbins, tab, iters, pxld, partial)
-                if (px128) MDG_RDF_HALF(true, false, 128);
-                else if (cell->diag && mask) MDG_RDF_HALF(true, true, 0);
-                else if (cell->diag) MDG_RDF_HALF(true, false, 0);
-                else if (mask) MDG_RDF_HALF(false, true, 0);
-                else MDG_RDF_HALF(false, false, 0);
-#undef MDG_RDF_HALF
-                hipLaunchKernelGGL(rdf_finish_kernel, dim3(nbins), dim3(64), 0, st, partial, gridh * 8, nbins, raw);
-                (void)hipFreeAsync(tab, st);
-                MDG_CHECK_LAUNCH("rdf_fwd_half_kernel");
-                return MDG_OK;
-            }
-            int grid = (n_frames + nw - 1) / nw;
-            if (grid > RDF_MAX_BLOCKS / nw) grid = RDF_MAX_BLOCKS / nw;
-#define MDG_RDF_LANE(D, RR, MK, PX)                                                                                    \
-    hipLaunchKernelGGL((rdf_fwd_lane_kernel<D, RR, MK, PX>), dim3(grid), dim3(64 * nw), lds, st, xyz, n_frames,        \
-                       n_atoms, *cell, cutoff * cutoff, mask, mu, coeff, nbins, tab, iters, pxld, partial)
-#define MDG_RDF_LANE_R(RR)                                             \
-    do {                                                               \
-        if (px128) MDG_RDF_LANE(true, RR, false, 128);                 \
-        else if (cell->diag && mask) MDG_RDF_LANE(true, RR, true, 0);  \
-        else if (cell->diag) MDG_RDF_LANE(true, RR, false, 0);         \
-        else if (mask) MDG_RDF_LANE(false, RR, true, 0);               \
-        else MDG_RDF_LANE(false, RR, false, 0);                        \
-    } while (0)
-            if (R == 5) MDG_RDF_LANE_R(5); else MDG_RDF_LANE_R(11);
-#undef MDG_RDF_LANE_R
-#undef MDG_RDF_LANE
-            hipLaunchKernelGGL(rdf_finish_kernel, dim3(nbins), dim3(64), 0, st, partial, grid * nw, nbins, raw);
-            (void)hipFreeAsync(tab, st);
-            MDG_CHECK_LAUNCH("rdf_fwd_lane_kernel");
-            return MDG_OK;
+            const bool half = R == 5 && spacing_s <= 1.5f && lds_half <= RDF_LDS_BUDGET;
+            P.variant = half ? RdfFwd::half : RdfFwd::lane;
+            P.waves = half ? 8 : nw;
+            P.lds = half ? lds_half : lds;
+            P.grid = min((n_frames + P.waves - 1) / P.waves, RDF_MAX_BLOCKS / P.waves);
+            return P;
         }
-        if (tab) (void)hipFreeAsync(tab, st);
     }
+    // ---- few frames or arbitrary centres: persistent blocks over (frame, candidate chunk) work items.
+    // Equally spaced centres with Ds = s * spacing <= 1: 8-bin blocks + recurrence
     const int nblk = (nbins + RDF_KB - 1) / RDF_KB;
     const bool block8 = spacing_s > 0.f && spacing_s <= 1.0f && nbins >= 2 * RDF_KB && nblk <= RDF_BLOCK;
-    if (block8) {
-        const int G = RDF_BLOCK / nblk;
-        const size_t lds = sizeof(float) * (RDF_BLOCK + 16 + (size_t)G * nblk * RDF_KB);
-        if (cell->diag)
-            hipLaunchKernelGGL(rdf_fwd_block8_kernel<true>, dim3(nblocks), dim3(RDF_BLOCK), lds, st, xyz, n_frames,
-                               n_atoms, *cell, cutoff * cutoff, mask, mu, coeff, nbins, partial);
-        else
-            hipLaunchKernelGGL(rdf_fwd_block8_kernel<false>, dim3(nblocks), dim3(RDF_BLOCK), lds, st, xyz, n_frames,
-                               n_atoms, *cell, cutoff * cutoff, mask, mu, coeff, nbins, partial);
-    } else if (cell->diag)
-        hipLaunchKernelGGL(rdf_fwd_kernel<true>, dim3(nblocks), dim3(RDF_BLOCK), 0, st, xyz, n_frames, n_atoms,
-                           *cell, cutoff * cutoff, mask, mu, coeff, nbins, partial);
+    P.variant = block8 ? RdfFwd::block8 : RdfFwd::direct;
+    P.waves = RDF_BLOCK / 64;
+    P.grid = rdf_grid(n_frames, n_atoms);
+    P.lds = block8 ? sizeof(float) * (RDF_BLOCK + 16 + (size_t)(RDF_BLOCK / nblk) * nblk * RDF_KB) : 0;
+    return P;
+}
+
+// stream-ordered scratch (no state, re-entrant); a failed allocation is an error in both directions
+template <class T>
+static T* rdf_scratch(size_t count, hipStream_t st, const char* who) {
+    T* p = nullptr;
+    if (hipMallocAsync((void**)&p, sizeof(T) * count, st) == hipSuccess && p) return p;
+    mdg_set_error("%s: scratch allocation failed", who);
+    return nullptr;
+}
+static void rdf_fine_finish_launch(const uint32_t* ghist, const RdfFinePlan& G, const float* mu, int nbins, float* raw,
+                                   hipStream_t st) {
+    hipLaunchKernelGGL(rdf_fine_finish_kernel, dim3(nbins), dim3(64), 0, st, ghist, (int)G.nfine, G.h, mu, G.sc, G.reach,
+                       nbins, raw);
+}
+
+static int rdf_launch_fine(const RdfFwdPlan& P, const RdfFrames& a, float* raw) {
+    const int nfine = (int)P.fine.nfine;
+    uint32_t* ghist = rdf_scratch<uint32_t>(P.scratch_words, a.st, "rdf_fwd");    // [nfine] | count | pair table
+    if (!ghist) return MDG_ELAUNCH;
+    int32_t* count = reinterpret_cast<int32_t*>(ghist + nfine);
+    uint32_t* tab = ghist + nfine + 4;
+    MDG_HIP(hipMemsetAsync(ghist, 0, sizeof(uint32_t) * (size_t)(nfine + 4), a.st));
+    hipLaunchKernelGGL(rdf_fine_table_kernel, dim3(1), dim3(1024), 0, a.st, a.N, a.mask, tab, count);
+    // (the fine grid starts at mu[0] - reach; the kernels read mu[0] themselves: no host copy)
+    rdf_dispatch<0>(a.cell->diag, false, false, 0, [&](auto d, auto...) {
+        hipLaunchKernelGGL(rdf_fwd_fine_kernel<decltype(d)::value>, dim3(P.grid), dim3(64 * RDF_FINE_WAVES), P.lds, a.st, a.xyz,
+                           a.nF, a.N, *a.cell, a.rc2, tab, count, a.mu, P.fine.reach, 1.0f / P.fine.h, nfine, P.pxld, ghist);
+    });
+    rdf_fine_finish_launch(ghist, P.fine, a.mu, a.nbins, raw, a.st);
+    (void)hipFreeAsync(ghist, a.st);
+    MDG_CHECK_LAUNCH("rdf_fwd_fine_kernel");
+    return MDG_OK;
+}
+// half, lane: the pair table, the sweep, the sum over the waves' partial histograms
+static int rdf_launch_pairs(const RdfFwdPlan& P, const RdfFrames& a, float* raw, float* partial) {
+    uint32_t* tab = rdf_scratch<uint32_t>(P.scratch_words, a.st, "rdf_fwd");
+    if (!tab) return MDG_ELAUNCH;
+    hipLaunchKernelGGL(rdf_pair_table_kernel, dim3(a.N), dim3(256), 0, a.st, tab, a.N, P.n_entries, P.n_padded, P.pad_entry);
+    const bool half = P.variant == RdfFwd::half;
+    if (half)
+        rdf_dispatch<5>(a.cell->diag, a.mask != nullptr, P.px128, P.R, [&](auto d, auto m, auto px, auto r) {
+            rdf_launch(rdf_fwd_half_kernel<decltype(d)::value, decltype(r)::value, decltype(m)::value, decltype(px)::value>,
+                       P.grid, 64 * P.waves, P.lds, a, tab, P.iters, P.pxld, partial);
+        });
     else
-        hipLaunchKernelGGL(rdf_fwd_kernel<false>, dim3(nblocks), dim3(RDF_BLOCK), 0, st, xyz, n_frames, n_atoms,
-                           *cell, cutoff * cutoff, mask, mu, coeff, nbins, partial);
-    hipLaunchKernelGGL(rdf_finish_kernel, dim3(nbins), dim3(64), 0, st, partial, nblocks, nbins, raw);
+        rdf_dispatch<5, 11>(a.cell->diag, a.mask != nullptr, P.px128, P.R, [&](auto d, auto m, auto px, auto r) {
+            rdf_launch(rdf_fwd_lane_kernel<decltype(d)::value, decltype(r)::value, decltype(m)::value, decltype(px)::value>,
+                       P.grid, 64 * P.waves, P.lds, a, tab, P.iters, P.pxld, partial);
+        });
+    hipLaunchKernelGGL(rdf_finish_kernel, dim3(a.nbins), dim3(64), 0, a.st, partial, P.grid * P.waves, a.nbins, raw);
+    (void)hipFreeAsync(tab, a.st);
+    MDG_CHECK_LAUNCH(half ? "rdf_fwd_half_kernel" : "rdf_fwd_lane_kernel");
+    return MDG_OK;
+}
+// block8, direct: the persistent blocks, the sum over their partial histograms
+static int rdf_launch_blocks(const RdfFwdPlan& P, const RdfFrames& a, float* raw, float* partial) {
+    rdf_dispatch<0>(a.cell->diag, false, false, 0, [&](auto d, auto...) {
+        if (P.variant == RdfFwd::block8) rdf_launch(rdf_fwd_block8_kernel<decltype(d)::value>, P.grid, RDF_BLOCK, P.lds, a, partial);
+        else rdf_launch(rdf_fwd_kernel<decltype(d)::value>, P.grid, RDF_BLOCK, P.lds, a, partial);
+    });
+    hipLaunchKernelGGL(rdf_finish_kernel, dim3(a.nbins), dim3(64), 0, a.st, partial, P.grid, a.nbins, raw);
     MDG_CHECK_LAUNCH("rdf_fwd_kernel");
     return MDG_OK;
 }
 
+static int rdf_fwd_impl(const float* xyz, int n_frames, int n_atoms, const MdgCell* cell, float cutoff,
+                        const uint8_t* mask, const float* mu, float coeff, int nbins, float* raw,
+                        float* partial, float spacing, void* stream) {
+    MDG_CHECK_ARG(xyz && cell && mu && raw && partial, "rdf_fwd: null buffer");
+    MDG_CHECK_ARG(n_frames > 0 && n_atoms > 1 && nbins > 0, "rdf_fwd: bad sizes");
+    MDG_CHECK_ARG(nbins <= RDF_BLOCK, "rdf_fwd: nbins > %d not supported", RDF_BLOCK);
+    MDG_CHECK_ARG(coeff < 0.f, "rdf_fwd: coeff must be negative (-0.5 / width^2)");
+    const RdfFwdPlan P = rdf_fwd_plan(n_frames, n_atoms, nbins, spacing, coeff, cell->diag != 0, mask != nullptr);
+    const RdfFrames a{xyz, n_frames, n_atoms, cell, cutoff * cutoff, mask, mu, coeff, nbins, (hipStream_t)stream};
+    switch (P.variant) {
+    case RdfFwd::fine: return rdf_launch_fine(P, a, raw);
+    case RdfFwd::half: case RdfFwd::lane: return rdf_launch_pairs(P, a, raw, partial);
+    default: return rdf_launch_blocks(P, a, raw, partial);
+    }
+}
 extern "C" int mdg_rdf_fwd(const float* xyz, int n_frames, int n_atoms, const MdgCell* cell, float cutoff,
                            const uint8_t* mask, const float* mu, float coeff, int nbins, float* raw,
                            float* partial, void* stream) {
@@ -1341,78 +1409,94 @@ extern "C" int mdg_rdf_fwd(const float* xyz, int n_frames, int n_atoms, const Md
 extern "C" int mdg_rdf_fwd_uniform(const float* xyz, int n_frames, int n_atoms, const MdgCell* cell, float cutoff,
                                    const uint8_t* mask, const float* mu, float spacing, float coeff, int nbins,
                                    float* raw, float* partial, void* stream) {
-    const float spacing_s = spacing > 0.f && coeff < 0.f ? spacing * sqrtf(-coeff * 1.4426950408889634f) : 0.f;
-    return rdf_fwd_impl(xyz, n_frames, n_atoms, cell, cutoff, mask, mu, coeff, nbins, raw, partial, spacing_s, stream);
+    return rdf_fwd_impl(xyz, n_frames, n_atoms, cell, cutoff, mask, mu, coeff, nbins, raw, partial, spacing, stream);
+}
+
+enum class RdfBwd { atom = MDG_RDF_BWD_ATOM, table = MDG_RDF_BWD_TABLE, frame = MDG_RDF_BWD_FRAME };
+struct RdfBwdPlan {
+    RdfBwd variant;
+    int R, waves, grid;                  // reach in bins (table: of the tabulated sum), waves per workgroup, workgroups
+    size_t lds;                          // dynamic LDS bytes
+    int ldw, cells;                      // table: length of the index-doubled rows, cells of the cubic-Hermite table
+    bool fits;                           // false: no variant holds this shape
+};
+
+// waves (= frames) per workgroup of the wave-per-frame kernels, limited by the `per_wave` floats of LDS each one needs
+static void rdf_bwd_waves(RdfBwdPlan& P, int n_frames, size_t shared, size_t per_wave) {
+    P.waves = 4;
+    while (P.waves > 1 && sizeof(float) * (shared + P.waves * per_wave) > 150 * 1024) P.waves >>= 1;
+    P.lds = sizeof(float) * (shared + P.waves * per_wave);
+    P.grid = (n_frames + P.waves - 1) / P.waves;
+    P.fits = P.lds <= RDF_LDS_MAX;
+}
+static RdfBwdPlan rdf_bwd_plan(int n_frames, int n_atoms, int nbins, float spacing, float coeff) {
+    RdfBwdPlan P{};
+    // few frames or frames too large for LDS: (frame, atom) gather variant, 16 lanes per atom
+    if (n_frames < RDF_MANY_FRAMES || n_atoms > 4096) {
+        P.variant = RdfBwd::atom; P.waves = 4; P.lds = sizeof(float) * 2 * nbins; P.fits = true;
+        P.grid = (int)(((long long)n_frames * n_atoms + 15) / 16);
+        return P;
+    }
+    P.R = nbins >= 2 ? rdf_lane_reach(rdf_spacing_s(spacing, coeff)) : 0;
+    // table of dL/dd on the fine nodes, then the wave-per-frame kernel with a table lookup per pair: for width ~ spacing
+    // (Ds <= 1) and at most 4096 nodes
+    P.cells = mdg_rdf_fine_plan(spacing, coeff, nbins).ncell;
+    if (P.cells) {
+        // index-doubled rows: the last lane group's idle lanes reach index 64 ceil(N/64) - 1 + N/2 + 1
+        P.ldw = (max(2 * n_atoms, 64 * ((n_atoms + 63) / 64) + n_atoms / 2 + 1) + 2) & ~1;
+        rdf_bwd_waves(P, n_frames, 4 * (size_t)P.cells, 6 * (size_t)P.ldw);
+        P.variant = RdfBwd::table;
+        if (P.fits) return P;
+    }
+    // the bin recurrence (R > 0) or the direct sum, one wave per frame with the 6N floats of its frame
+    P.ldw = P.cells = 0;
+    rdf_bwd_waves(P, n_frames, 2 * (size_t)nbins + 6 * (size_t)P.R, 6 * (size_t)n_atoms);
+    P.variant = RdfBwd::frame;
+    return P;
+}
+
+static int rdf_launch_bwd_atom(const RdfBwdPlan& P, const RdfFrames& a, const float* g_raw, float* g_xyz, int uniform) {
+    rdf_dispatch<0>(a.cell->diag, false, false, 0, [&](auto d, auto...) {
+        rdf_launch(rdf_bwd_atom_kernel<decltype(d)::value, 16>, P.grid, 64 * P.waves, P.lds, a, g_raw, g_xyz, uniform);
+    });
+    MDG_CHECK_LAUNCH("rdf_bwd_atom_kernel");
+    return MDG_OK;
+}
+static int rdf_launch_bwd_table(const RdfBwdPlan& P, const RdfFrames& a, const float* g_raw, float* g_xyz) {
+    float4* tab = rdf_scratch<float4>((size_t)P.cells, a.st, "rdf_bwd");
+    if (!tab) return MDG_ELAUNCH;
+    hipLaunchKernelGGL(rdf_bwd_table_kernel, dim3((P.cells + 255) / 256), dim3(256), 0, a.st, a.mu, a.coeff, a.nbins, g_raw, P.R, tab);
+    rdf_dispatch<0>(a.cell->diag, false, false, 0, [&](auto d, auto...) {
+        hipLaunchKernelGGL(rdf_bwd_fine_kernel<decltype(d)::value>, dim3(P.grid), dim3(64 * P.waves), P.lds, a.st, a.xyz, a.nF,
+                           a.N, *a.cell, a.rc2, a.mask, a.mu, a.nbins, P.R, tab, P.ldw, g_xyz);
+    });
+    (void)hipFreeAsync(tab, a.st);
+    MDG_CHECK_LAUNCH("rdf_bwd_fine_kernel");
+    return MDG_OK;
+}
+static int rdf_launch_bwd_frame(const RdfBwdPlan& P, const RdfFrames& a, const float* g_raw, float* g_xyz, int uniform) {
+    rdf_dispatch<6, 11, 0>(a.cell->diag, false, false, P.R, [&](auto d, auto, auto, auto r) {
+        rdf_launch(rdf_bwd_kernel<decltype(d)::value, decltype(r)::value>, P.grid, 64 * P.waves, P.lds, a, g_raw, g_xyz, uniform);
+    });
+    MDG_CHECK_LAUNCH("rdf_bwd_kernel");
+    return MDG_OK;
 }
 
 static int rdf_bwd_impl(const float* xyz, int n_frames, int n_atoms, const MdgCell* cell, float cutoff,
                         const uint8_t* mask, const float* mu, float coeff, int nbins, const float* g_raw,
-                        float* g_xyz, float spacing_s, void* stream) {
+                        float* g_xyz, float spacing, void* stream) {
     MDG_CHECK_ARG(xyz && cell && mu && g_raw && g_xyz, "rdf_bwd: null buffer");
     MDG_CHECK_ARG(n_frames > 0 && n_atoms > 1 && nbins > 0, "rdf_bwd: bad sizes");
     MDG_CHECK_ARG(coeff < 0.f, "rdf_bwd: coeff must be negative (-0.5 / width^2)");
-    hipStream_t st = (hipStream_t)stream;
-    const int uniform = spacing_s > 0.f;
-    // few frames or frames too large for LDS: (frame, atom) gather variant
-    if (n_frames < 1024 || n_atoms > 4096) {
-        constexpr int LPA = 16, BLK = 256;
-        const long long rows = (long long)n_frames * n_atoms;
-        const int nb = (int)((rows + BLK / LPA - 1) / (BLK / LPA));
-        const size_t l2 = sizeof(float) * 2 * nbins;
-        if (cell->diag)
-            hipLaunchKernelGGL((rdf_bwd_atom_kernel<true, LPA>), dim3(nb), dim3(BLK), l2, st, xyz, n_frames, n_atoms,
-                               *cell, cutoff * cutoff, mask, mu, coeff, nbins, g_raw, g_xyz, uniform);
-        else
-            hipLaunchKernelGGL((rdf_bwd_atom_kernel<false, LPA>), dim3(nb), dim3(BLK), l2, st, xyz, n_frames, n_atoms,
-                               *cell, cutoff * cutoff, mask, mu, coeff, nbins, g_raw, g_xyz, uniform);
-        MDG_CHECK_LAUNCH("rdf_bwd_atom_kernel");
-        return MDG_OK;
+    const RdfBwdPlan P = rdf_bwd_plan(n_frames, n_atoms, nbins, spacing, coeff);
+    MDG_CHECK_ARG(P.fits, "rdf_bwd: N=%d does not fit the LDS-resident frame kernel", n_atoms);
+    const RdfFrames a{xyz, n_frames, n_atoms, cell, cutoff * cutoff, mask, mu, coeff, nbins, (hipStream_t)stream};
+    const int uniform = rdf_spacing_s(spacing, coeff) > 0.f;
+    switch (P.variant) {
+    case RdfBwd::atom: return rdf_launch_bwd_atom(P, a, g_raw, g_xyz, uniform);
+    case RdfBwd::table: return rdf_launch_bwd_table(P, a, g_raw, g_xyz);
+    default: return rdf_launch_bwd_frame(P, a, g_raw, g_xyz, uniform);
     }
-    const int R = nbins >= 2 ? rdf_lane_reach(spacing_s) : 0;
-    if (R && spacing_s <= 1.0f && fine_nodes(nbins, R) <= 4096) {
-        // table of dL/dd on the fine nodes (stream-ordered scratch: no state, re-entrant), then the
-        // wave-per-frame kernel with a table lookup per pair
-        const int nn = fine_nodes(nbins, R);
-        const size_t tabf = 4 * (size_t)(nn - 1);
-        // index-doubled rows: the last lane group's idle lanes reach index 64 ceil(N/64) - 1 + N/2 + 1
-        const int ldw = (max(2 * n_atoms, 64 * ((n_atoms + 63) / 64) + n_atoms / 2 + 1) + 2) & ~1;
-        int wpb = 4;
-        while (wpb > 1 && sizeof(float) * (tabf + (size_t)wpb * 6 * ldw) > 150 * 1024) wpb >>= 1;
-        const size_t lds = sizeof(float) * (tabf + (size_t)wpb * 6 * ldw);
-        if (lds <= 160 * 1024) {
-            float4* tab = nullptr;
-            if (hipMallocAsync((void**)&tab, sizeof(float4) * (size_t)(nn - 1), st) != hipSuccess || !tab) {
-                mdg_set_error("rdf_bwd: scratch allocation failed");
-                return MDG_ELAUNCH;
-            }
-            hipLaunchKernelGGL(rdf_bwd_table_kernel, dim3((nn + 254) / 256), dim3(256), 0, st, mu, coeff, nbins, g_raw, R, tab);
-            const int nblocks = (n_frames + wpb - 1) / wpb;
-            if (cell->diag)
-                hipLaunchKernelGGL(rdf_bwd_fine_kernel<true>, dim3(nblocks), dim3(64 * wpb), lds, st, xyz, n_frames, n_atoms,
-                                   *cell, cutoff * cutoff, mask, mu, nbins, R, tab, ldw, g_xyz);
-            else
-                hipLaunchKernelGGL(rdf_bwd_fine_kernel<false>, dim3(nblocks), dim3(64 * wpb), lds, st, xyz, n_frames, n_atoms,
-                                   *cell, cutoff * cutoff, mask, mu, nbins, R, tab, ldw, g_xyz);
-            (void)hipFreeAsync(tab, st);
-            MDG_CHECK_LAUNCH("rdf_bwd_fine_kernel");
-            return MDG_OK;
-        }
-    }
-    // waves (= frames) per workgroup limited by the 6N floats of LDS each one needs
-    const size_t tables = 2 * (size_t)nbins + 6 * (size_t)R;
-    int wpb = 4;
-    while (wpb > 1 && sizeof(float) * (tables + (size_t)wpb * 6 * n_atoms) > 150 * 1024) wpb >>= 1;
-    const size_t lds = sizeof(float) * (tables + (size_t)wpb * 6 * n_atoms);
-    MDG_CHECK_ARG(lds <= 160 * 1024, "rdf_bwd: N=%d does not fit the LDS-resident frame kernel", n_atoms);
-    const int nblocks = (n_frames + wpb - 1) / wpb;
-#define MDG_RDF_BWD(D, RR)                                                                                        \
-    hipLaunchKernelGGL((rdf_bwd_kernel<D, RR>), dim3(nblocks), dim3(64 * wpb), lds, st, xyz, n_frames, n_atoms, *cell, \
-                       cutoff * cutoff, mask, mu, coeff, nbins, g_raw, g_xyz, uniform)
-    if (cell->diag) { if (R == 6) MDG_RDF_BWD(true, 6); else if (R == 11) MDG_RDF_BWD(true, 11); else MDG_RDF_BWD(true, 0); }
-    else            { if (R == 6) MDG_RDF_BWD(false, 6); else if (R == 11) MDG_RDF_BWD(false, 11); else MDG_RDF_BWD(false, 0); }
-#undef MDG_RDF_BWD
-    MDG_CHECK_LAUNCH("rdf_bwd_kernel");
-    return MDG_OK;
 }
 
 extern "C" int mdg_rdf_bwd(const float* xyz, int n_frames, int n_atoms, const MdgCell* cell, float cutoff,
@@ -1424,36 +1508,30 @@ extern "C" int mdg_rdf_bwd(const float* xyz, int n_frames, int n_atoms, const Md
 extern "C" int mdg_rdf_bwd_uniform(const float* xyz, int n_frames, int n_atoms, const MdgCell* cell, float cutoff,
                                    const uint8_t* mask, const float* mu, float spacing, float coeff, int nbins,
                                    const float* g_raw, float* g_xyz, void* stream) {
-    const float spacing_s = spacing > 0.f && coeff < 0.f ? spacing * sqrtf(-coeff * 1.4426950408889634f) : 0.f;
-    return rdf_bwd_impl(xyz, n_frames, n_atoms, cell, cutoff, mask, mu, coeff, nbins, g_raw, g_xyz, spacing_s, stream);
+    return rdf_bwd_impl(xyz, n_frames, n_atoms, cell, cutoff, mask, mu, coeff, nbins, g_raw, g_xyz, spacing, stream);
 }
 
-// fine grid of the integer-histogram forward for centres mu0 + k spacing and exp(coeff x^2): number of fine bins, or
-// 0 when it does not fit the workgroup's LDS histogram
-static long long rdf_fine_bins(float spacing, float coeff, int nbins, float* reach, float* h) {
-    if (!(spacing > 0.f) || !(coeff < 0.f) || nbins < 2) return 0;
-    const float sc = sqrtf(-coeff * LOG2E);
-    *reach = 5.3f / sc;
-    *h = 0.004f / sc;
-    const double span = (double)(nbins - 1) * spacing + 2.0 * (*reach);
-    const long long nfine = (long long)ceil(span / *h) + 1;
-    return nfine <= RDF_FINE_MAX ? nfine : 0;
+// The plans' answers without a launch: MDG_RDF_FWD_* / MDG_RDF_BWD_*, or -1 where the launch would refuse the shape.
+// info (may be null): MDG_RDF_PLAN_INFO words {R, waves per workgroup, workgroups, LDS bytes, row stride (forward: of the
+// coordinates, backward: ldw), forward: 1 for 128-column rows / backward: table cells}
+static int rdf_report(int variant, int32_t* info, const int32_t (&v)[MDG_RDF_PLAN_INFO]) {
+    for (int k = 0; info && k < MDG_RDF_PLAN_INFO; ++k) info[k] = v[k];
+    return variant;
+}
+extern "C" int mdg_rdf_fwd_variant(int n_frames, int n_atoms, int nbins, float spacing, float coeff, int diag, int masked,
+                                   int32_t* info) {
+    if (!(n_frames > 0 && n_atoms > 1 && nbins > 0 && nbins <= RDF_BLOCK && coeff < 0.f)) return -1;
+    const RdfFwdPlan P = rdf_fwd_plan(n_frames, n_atoms, nbins, spacing, coeff, diag != 0, masked != 0);
+    return rdf_report((int)P.variant, info, {P.R, P.waves, P.grid, (int32_t)P.lds, P.pxld, P.px128});
+}
+extern "C" int mdg_rdf_bwd_variant(int n_frames, int n_atoms, int nbins, float spacing, float coeff, int, int, int32_t* info) {
+    if (!(n_frames > 0 && n_atoms > 1 && nbins > 0 && coeff < 0.f)) return -1;
+    const RdfBwdPlan P = rdf_bwd_plan(n_frames, n_atoms, nbins, spacing, coeff);      // (neither the cell nor a mask matters)
+    return P.fits ? rdf_report((int)P.variant, info, {P.R, P.waves, P.grid, (int32_t)P.lds, P.ldw, P.cells}) : -1;
 }
 
-// ---- shared with the fused observable of the trajectory kernels (common.hpp)
-RdfFinePlan mdg_rdf_fine_plan(float spacing, float coeff, int nbins) {
-    RdfFinePlan P{};
-    if (!(spacing > 0.f) || !(coeff < 0.f) || nbins < 2) return P;
-    P.sc = sqrtf(-coeff * LOG2E);
-    P.nfine = rdf_fine_bins(spacing, coeff, nbins, &P.reach, &P.h);
-    const float spacing_s = spacing * P.sc;
-    const int R = rdf_lane_reach(spacing_s);
-    if (R && spacing_s <= 1.0f && fine_nodes(nbins, R) <= 4096) { P.reach_bins = R; P.ncell = fine_nodes(nbins, R) - 1; }
-    return P;
-}
 int mdg_rdf_fine_finish(const uint32_t* ghist, const RdfFinePlan& P, const float* mu, int nbins, float* raw, hipStream_t st) {
-    hipLaunchKernelGGL(rdf_fine_finish_kernel, dim3(nbins), dim3(64), 0, st, ghist, (int)P.nfine, P.h, mu, P.sc, P.reach,
-                       nbins, raw);
+    rdf_fine_finish_launch(ghist, P, mu, nbins, raw, st);
     MDG_CHECK_LAUNCH("rdf_fine_finish_kernel");
     return MDG_OK;
 }
@@ -1474,17 +1552,16 @@ int mdg_rdf_bwd_table_u(const float* mu, float coeff, int nbins, const float* g_
 }
 
 extern "C" int mdg_rdf_ell_supported(float spacing, float coeff, int nbins) {
-    float reach, h;
-    return rdf_fine_bins(spacing, coeff, nbins, &reach, &h) > 0;
+    return mdg_rdf_fine_plan(spacing, coeff, nbins).nfine > 0;
 }
 
 extern "C" int mdg_rdf_fwd_ell(const float* pos, int64_t n_atoms_total, const MdgCell* cell, const int32_t* col,
                                const int32_t* shift, const int32_t* cnt, int max_nbr, const float* mu, float spacing,
                                float coeff, int nbins, float* raw, void* stream) {
     MDG_CHECK_ARG(pos && cell && col && shift && cnt && mu && raw && n_atoms_total > 0 && max_nbr > 0, "rdf_fwd_ell: bad arguments");
-    float reach, h;
-    const long long nfine = rdf_fine_bins(spacing, coeff, nbins, &reach, &h);
-    MDG_CHECK_ARG(nfine > 0, "rdf_fwd_ell: the fine grid for these centres does not fit (see mdg_rdf_ell_supported)");
+    const RdfFinePlan G = mdg_rdf_fine_plan(spacing, coeff, nbins);
+    const long long nfine = G.nfine;
+    MDG_CHECK_ARG(nfine > 0,"rdf_fwd_ell: the fine grid for these centres does not fit (see mdg_rdf_ell_supported)");
     hipStream_t st = (hipStream_t)stream;
     uint32_t* ghist = nullptr;
     MDG_HIP(hipMallocAsync((void**)&ghist, sizeof(uint32_t) * (size_t)nfine, st));
@@ -1492,10 +1569,9 @@ extern "C" int mdg_rdf_fwd_ell(const float* pos, int64_t n_atoms_total, const Md
     const long long n_slots = (long long)n_atoms_total * max_nbr;
     long long grid = (n_slots + 1023) / 1024;
     if (grid > 256) grid = 256;
-    const float sc = sqrtf(-coeff * LOG2E);
     hipLaunchKernelGGL(rdf_fwd_ell_kernel, dim3((unsigned)grid), dim3(1024), sizeof(uint32_t) * (size_t)nfine, st, pos, n_slots,
-                       *cell, col, shift, cnt, max_nbr, mu, reach, 1.0f / h, (int)nfine, ghist);
-    hipLaunchKernelGGL(rdf_fine_finish_kernel, dim3(nbins), dim3(64), 0, st, ghist, (int)nfine, h, mu, sc, reach, nbins, raw);
+                       *cell, col, shift, cnt, max_nbr, mu, G.reach, 1.0f / G.h, (int)nfine, ghist);
+    rdf_fine_finish_launch(ghist, G, mu, nbins, raw, st);
     (void)hipFreeAsync(ghist, st);
     MDG_CHECK_LAUNCH("rdf_fwd_ell_kernel");
     return MDG_OK;

@@ -1623,6 +1623,39 @@ def _rdf_pair_table(g_raw, mu, coeff, cutoff, nodes=4096):
     return torch.stack((c1, du * dc1), 1).reshape(-1).contiguous(), u0, du
 
 
+def _rdf_list_cutoff(cutoff, coeff, mu_last):
+    """Cutoff of the pair search of the list-based RDF paths."""
+    if mu_last is None or not coeff < 0:
+        return float(cutoff)
+    # The pair search is trimmed to the reach of the Gaussians, and the bound follows the user's `width`: the
+    # fine grid of the list kernels ends 5.3 / s beyond the last centre (s = sqrt(-coeff log2 e)), where a pair's
+    # term in the LAST bin is exp2(-5.3^2) = 2^-28.1 of a peak term -- small, not zero: with ~ as many pairs in
+    # the dropped shell as around the last centre, the last bin loses < 2^-24 of its count (half an ulp of the
+    # fp32 sum) and every other bin less.  Never beyond the reference's own cutoff_boundary = end + 0.5
+    # (observable.py:52), which wide Gaussians reach first (tests: width x3, x8 at 2 744 atoms vs the oracle).
+    return min(float(cutoff), float(mu_last) + 1.02 * 5.3 / math.sqrt(-coeff * 1.4426950408889634) + 1e-6)
+
+
+RDF_FWD_VARIANTS = ("direct", "block8", "lane", "half", "fine")      # MDG_RDF_FWD_* of include/mdgrad_hip.h
+RDF_BWD_VARIANTS = ("atom", "table", "frame")                        # MDG_RDF_BWD_*
+
+
+def rdf_route(F, N, nbins, spacing, coeff, cutoff, cell_struct, mask):
+    """Where RdfRawFn sends F frames of N atoms (no GPU needed): ("cell", None, None) -- the sweep over the cell bins
+    (csrc/rdf_cell.hip) --, ("list", None, None) -- a cell-list neighbour list --, or ("frames", fwd, bwd) with the
+    kernel variants of csrc/rdf.hip (RDF_FWD_VARIANTS / RDF_BWD_VARIANTS; None where the library refuses the shape).
+    cutoff: that of the pair search (_rdf_list_cutoff)."""
+    lib = _lib.load()
+    if (N >= RDF_LIST_ATOMS and mask is None and spacing > 0 and cell_struct.diag
+            and _use_cell_list(N, cell_struct, float(cutoff))
+            and lib.mdg_rdf_ell_supported(float(spacing), float(coeff), nbins)):
+        direct = RDF_CELL_DIRECT and lib.mdg_rdf_cell_supported(N, C.byref(cell_struct), float(cutoff))
+        return ("cell" if direct else "list"), None, None
+    shape = (F, N, nbins, float(spacing), float(coeff), int(cell_struct.diag), int(mask is not None), None)
+    fwd, bwd = lib.mdg_rdf_fwd_variant(*shape), lib.mdg_rdf_bwd_variant(*shape)
+    return "frames", (RDF_FWD_VARIANTS[fwd] if fwd >= 0 else None), (RDF_BWD_VARIANTS[bwd] if bwd >= 0 else None)
+
+
 class RdfRawFn(torch.autograd.Function):
     """raw[k] = sum over frames and i<j pairs (d < cutoff) of exp(coeff (d - mu_k)^2)
     (the GaussianSmearing(...).sum(0) of torchmd/observable.py:70)."""
@@ -1636,48 +1669,32 @@ class RdfRawFn(torch.autograd.Function):
         F, N, B = x3.shape[0], x3.shape[1], mu.shape[0]
         dev = x.device
         raw = torch.empty(B, device=dev)
+        muc = mu.detach().to(torch.float32).contiguous()
+        list_cut = _rdf_list_cutoff(cutoff, coeff, mu_last)
+        route = rdf_route(F, N, B, spacing, coeff, list_cut, cell_struct, mask)[0]
         ctx.ell = None
-        list_cut = float(cutoff)
-        if mu_last is not None and coeff < 0:
-            # The pair search is trimmed to the reach of the Gaussians, and the bound follows the user's `width`: the
-            # fine grid of the list kernels ends 5.3 / s beyond the last centre (s = sqrt(-coeff log2 e)), where a pair's
-            # term in the LAST bin is exp2(-5.3^2) = 2^-28.1 of a peak term -- small, not zero: with ~ as many pairs in
-            # the dropped shell as around the last centre, the last bin loses < 2^-24 of its count (half an ulp of the
-            # fp32 sum) and every other bin less.  Never beyond the reference's own cutoff_boundary = end + 0.5
-            # (observable.py:52), which wide Gaussians reach first (tests: width x3, x8 at 2 744 atoms vs the oracle).
-            list_cut = min(list_cut, float(mu_last) + 1.02 * 5.3 / math.sqrt(-coeff * 1.4426950408889634) + 1e-6)
-        if (N >= RDF_LIST_ATOMS and mask is None and spacing > 0 and cell_struct.diag
-                and _use_cell_list(N, cell_struct, list_cut)
-                and lib.mdg_rdf_ell_supported(float(spacing), float(coeff), B)):
+        if route == "frames":
+            partial = torch.empty(int(lib.mdg_rdf_partial_size(F, N, B)), device=dev)
+            check(lib.mdg_rdf_fwd_uniform(ptr(x3), F, N, C.byref(cell_struct), float(cutoff), ptr(mask), ptr(muc),
+                                          float(spacing), float(coeff), B, ptr(raw), ptr(partial), stream_ptr(dev)),
+                  "mdg_rdf_fwd")
+        else:
             # large systems: pair search through the cell list (frames = groups of one list), every listed pair
             # counted on the fine integer grid; the gradient is a tabulated pair force over the same list
-            flat = x3.reshape(F * N, 3)
+            x3 = x3.reshape(F * N, 3)
             cutoff = list_cut
-            muc = mu.detach().to(torch.float32).contiguous()
-            if RDF_CELL_DIRECT and lib.mdg_rdf_cell_supported(N, C.byref(cell_struct), float(cutoff)):
+            if route == "cell":
                 # ... without materialising the list: search + count in one sweep over the cell bins (csrc/rdf_cell.hip);
                 # the backward pass sweeps the same bins with the tabulated pair force
-                scratch = torch.empty(int(lib.mdg_rdf_cell_scratch(F, N, C.byref(cell_struct), float(cutoff))) + 4,
+                ctx.ell = torch.empty(int(lib.mdg_rdf_cell_scratch(F, N, C.byref(cell_struct), float(cutoff))) + 4,
                                       dtype=torch.int32, device=dev)
-                check(lib.mdg_rdf_fwd_cell(ptr(flat), F, N, C.byref(cell_struct), float(cutoff), ptr(muc), float(spacing),
-                                           float(coeff), B, ptr(raw), ptr(scratch), stream_ptr(dev)), "mdg_rdf_fwd_cell")
-                ctx.ell = scratch
-                ctx.args = (float(coeff), float(cutoff), cell_struct, mask, xyz.shape, float(spacing))
-                ctx.save_for_backward(flat, muc)
-                return raw
-            ell = build_ell(flat, cell_struct, cutoff, group=N)
-            check(lib.mdg_rdf_fwd_ell(ptr(flat), F * N, C.byref(cell_struct), ptr(ell.col), ptr(ell.shift), ptr(ell.cnt),
-                                      ell.max_nbr, ptr(muc), float(spacing), float(coeff), B, ptr(raw), stream_ptr(dev)),
-                  "mdg_rdf_fwd_ell")
-            ctx.ell = ell
-            ctx.args = (float(coeff), float(cutoff), cell_struct, mask, xyz.shape, float(spacing))
-            ctx.save_for_backward(flat, muc)
-            return raw
-        partial = torch.empty(int(lib.mdg_rdf_partial_size(F, N, B)), device=dev)
-        muc = mu.detach().to(torch.float32).contiguous()
-        check(lib.mdg_rdf_fwd_uniform(ptr(x3), F, N, C.byref(cell_struct), float(cutoff), ptr(mask), ptr(muc),
-                                      float(spacing), float(coeff), B, ptr(raw), ptr(partial), stream_ptr(dev)),
-              "mdg_rdf_fwd")
+                check(lib.mdg_rdf_fwd_cell(ptr(x3), F, N, C.byref(cell_struct), float(cutoff), ptr(muc), float(spacing),
+                                           float(coeff), B, ptr(raw), ptr(ctx.ell), stream_ptr(dev)), "mdg_rdf_fwd_cell")
+            else:
+                ctx.ell = ell = build_ell(x3, cell_struct, cutoff, group=N)
+                check(lib.mdg_rdf_fwd_ell(ptr(x3), F * N, C.byref(cell_struct), ptr(ell.col), ptr(ell.shift), ptr(ell.cnt),
+                                          ell.max_nbr, ptr(muc), float(spacing), float(coeff), B, ptr(raw), stream_ptr(dev)),
+                      "mdg_rdf_fwd_ell")
         ctx.args = (float(coeff), float(cutoff), cell_struct, mask, xyz.shape, float(spacing))
         ctx.save_for_backward(x3, muc)
         return raw

@@ -696,11 +696,31 @@ def test_rdf_bitwise_reproducible_and_nonuniform_edge_cases():
         close(gx, gxo, 1e-3, 1e-4 * float(gxo.abs().max()), "grad nb=%d" % nb)
 
 
+def rdf_variants(F, N, nbins, spacing, coeff, cs, mask, cutoff=3.0):
+    """(forward, backward) kernel variant of csrc/rdf.hip that RdfRawFn runs for this shape."""
+    from mdgrad_amd import ops
+    route = ops.rdf_route(F, N, nbins, spacing, coeff, cutoff, cs, mask)
+    assert route[0] == "frames"
+    return route[1:]
+
+
+def rdf_plan_info(direction, F, N, nbins, spacing, coeff, cs, mask):
+    """The MDG_RDF_PLAN_INFO words of the plan: reach R, waves per workgroup, workgroups, LDS bytes, row stride, and
+    (forward) whether the rows are the compile-time 128 columns."""
+    import ctypes
+    from mdgrad_amd import _lib
+    info = (ctypes.c_int32 * 6)()
+    fn = getattr(_lib.load(), "mdg_rdf_%s_variant" % direction)
+    assert fn(F, N, nbins, spacing, coeff, int(cs.diag), int(mask is not None), info) >= 0
+    return list(info)
+
+
 def test_rdf_kernel_variants_agree():
-    """>= 1024 frames with equally spaced centres run the lane-per-pair forward and the wave-per-frame
-    tournament backward (both with the Gaussian recurrence); fewer frames the 8-bin-block forward and the
-    (frame, atom) gather backward; spacing 0 the direct kernels.  Same histogram and gradients, and the
-    many-frame kernels are bitwise reproducible."""
+    """1100 frames of 108 atoms with equally spaced centres: the fine integer histogram forward and the fine-table
+    backward at width = spacing and 1.6 x, the full-column lane-per-pair forward (R = 5) and the wave-per-frame tournament
+    backward with the Gaussian recurrence (R = 6) at 0.4 x; 550 frames the 8-bin-block (0.4 x: direct) forward and the
+    (frame, atom) gather backward; spacing 0 the direct kernels.  Same histogram and gradients, and the many-frame kernels
+    are bitwise reproducible."""
     from mdgrad_amd import ops, _lib
     g = load_golden("rdf")
     rng = np.random.default_rng(11)
@@ -708,10 +728,15 @@ def test_rdf_kernel_variants_agree():
     frames = np.stack([np.mod(base + rng.normal(0, 0.05, base.shape), g["cell"]) for _ in range(1100)]).astype(np.float32)
     cs = _lib.make_cell(g["cell"])
     w = torch.linspace(-1, 1, 100, device=DEV)
-    for width_scale in (1.0, 1.6, 0.4):                # half-column R=5, full-column R=11, full-column R=5 (narrow)
+    runs = {1.0: (("fine", "table"), ("block8", "atom")), 1.6: (("fine", "table"), ("block8", "atom")),
+            0.4: (("lane", "frame"), ("direct", "atom"))}
+    for width_scale in (1.0, 1.6, 0.4):
         mu = torch.linspace(0.75, 2.5, 100, device=DEV)
         spacing = float(mu[1] - mu[0])
         coeff = float(-0.5 / (width_scale * spacing) ** 2)
+        assert rdf_variants(1100, 108, 100, spacing, coeff, cs, None) == runs[width_scale][0]
+        assert rdf_variants(550, 108, 100, spacing, coeff, cs, None) == runs[width_scale][1]
+        assert rdf_variants(1100, 108, 100, 0.0, coeff, cs, None) == ("direct", "frame")
 
         def grad_of(x, sp):
             x = T(x, DEV).requires_grad_(True)
@@ -729,12 +754,13 @@ def test_rdf_kernel_variants_agree():
         close(g_all, g_direct, 1e-4, 3e-5 * float(g_direct.abs().max()), "recurrence vs direct rdf backward")
         close(g_all, torch.cat([p_[1] for p_ in parts]), 1e-4, 3e-5 * float(g_direct.abs().max()),
               "tournament vs gather rdf backward")
-    # an odd atom count and a masked (species-selected) histogram through the lane kernel
+    # an odd atom count and a masked (species-selected) histogram through the fine-histogram kernel (a shorter pair table)
     sub = frames[:, :107]
     mask = ops.build_mask(107, index_tuple=(list(range(0, 50)), list(range(50, 107))), device=DEV)
     mu = torch.linspace(0.75, 2.5, 100, device=DEV)
     spacing = float(mu[1] - mu[0])
     coeff = float(-0.5 / spacing ** 2)
+    assert rdf_variants(1100, 107, 100, spacing, coeff, cs, mask) == ("fine", "table")
     xs = T(sub, DEV)
     a = ops.RdfRawFn.apply(xs, mu, coeff, 3.0, cs, mask, spacing)
     b = ops.RdfRawFn.apply(xs, mu, coeff, 3.0, cs, mask, 0.0)
@@ -1393,10 +1419,11 @@ def test_fused_lj_outside_the_near_window_and_256_atoms_vs_oracle(shift, n_cells
 
 
 def test_rdf_lane_kernels_general_variants():
-    """The many-frame RDF kernels outside their fast path: frames translated by 0.3 cell (clamped minimum
-    image), a triclinic cell, 150 atoms (run-time coordinate stride, no 128-column rows), and an even atom
-    count with a species mask (the half step of the backward's cyclic order) -- each against the direct
-    kernels on the same input."""
+    """The many-frame RDF kernels of 64 .. 1 024 atoms -- the fine integer histogram forward, the fine-table backward --
+    outside their fast path: frames translated by 0.3 cell (clamped minimum image), a triclinic cell, 150 atoms, and an
+    even atom count with a species mask (a shorter pair table; the half step of the backward's cyclic order) -- each
+    against the direct kernels on the same input.  (The lane-per-pair kernels these shapes ran before the fine histogram:
+    test_rdf_variants_below_the_fine_histogram.)"""
     from mdgrad_amd import ops, _lib
     g = load_golden("rdf")
     rng = np.random.default_rng(12)
@@ -1418,6 +1445,7 @@ def test_rdf_lane_kernels_general_variants():
         return out
 
     def check(x, cs, mask, what, cutoff=3.0):
+        assert rdf_variants(x.shape[0], x.shape[1], 100, spacing, coeff, cs, mask, cutoff) == ("fine", "table"), what
         (ra, ga), (rb, gb) = both(x, cs, mask, cutoff)
         close(ra, rb, 2e-5, 1e-6 * float(rb.max()), what + ": forward")
         close(ga, gb, 1e-4, 3e-5 * float(gb.abs().max()), what + ": backward")
@@ -1432,18 +1460,83 @@ def test_rdf_lane_kernels_general_variants():
     check(frames, cs, mask, "even N with a mask")
 
 
+_TRI_CELL = [[4.8, 0, 0], [0.7, 4.8, 0], [-0.5, 0.4, 4.8]]
+# (bins, width / spacing, triclinic, masked) -> forward (variant, R, waves per workgroup, 128-column rows), backward
+# (variant, R): the smallest shapes that reach the lane-per-pair kernels in the forms no other test runs
+_RDF_48 = [
+    ((100, 1.0, False, True), ("half", 5, 8, 0), ("table", 6)),        # run-time stride, masked
+    ((100, 1.0, True, False), ("half", 5, 8, 0), ("table", 6)),        # DIAG = false
+    ((100, 1.6, False, False), ("lane", 11, 4, 1), ("table", 11)),     # R = 11, 128-column rows
+    ((100, 1.6, True, False), ("lane", 11, 4, 0), ("table", 11)),      # R = 11, DIAG = false
+    # width = 0.4 spacing: the forward holds; the recurrence backward (rdf_bwd_kernel<., 6>) measures a largest error of
+    # 9.155e-03 where 8.016e-03 is allowed (max |g| = 260: 3.5e-5 of it against the 3e-5 allowed).  Not traced further; the
+    # likely cause: it steps the scaled distance by s * spacing = 2.1 per bin, i.e. takes the float32 linspace centres as exactly equidistant -- they are to
+    # an ulp of 2.5, 2.9e-5 in scaled units at s = 120 -- and 48 atoms leave few pairs per atom to average that over (the
+    # same variants pass at 108 atoms in test_rdf_kernel_variants_agree).  The kernel is as it was before the plans.
+    pytest.param((100, 0.4, False, False), ("lane", 5, 4, 1), ("frame", 6),
+                 marks=pytest.mark.xfail(strict=True, raises=AssertionError,
+                                         reason="backward: max err 9.155e-03, allowed 8.016e-03 (rdf_bwd_kernel<., 6> at 48 atoms)")),
+    ((500, 1.6, False, False), ("lane", 11, 1, 1), ("frame", 11)),     # one wave per workgroup; rdf_bwd_kernel<., 11>
+]
+
+
+@pytest.mark.parametrize("case,fwd,bwd", _RDF_48)
+def test_rdf_variants_below_the_fine_histogram(case, fwd, bwd):
+    """1 024 frames of 48 atoms (below the 64 atoms of the fine integer histogram): the half-width kernel masked and in a
+    triclinic cell, the full-column lane kernel with R = 11 (orthorhombic and triclinic) and with one wave per workgroup
+    (500 bins), the recurrence backward with R = 6 and R = 11 -- the variant is asserted first, then the result is compared
+    with the direct kernels (spacing 0) on the same input, as in test_rdf_lane_kernels_general_variants.  Measured: five
+    cases hold; at width = 0.4 spacing the backward misses, largest error 9.155e-03 against 8.016e-03 allowed (expected
+    failure, see _RDF_48)."""
+    from mdgrad_amd import ops, _lib
+    nbins, width_scale, tri, masked = case
+    g = load_golden("rdf")
+    rng = np.random.default_rng(13)
+    base = g["xyz"][0][:48]
+    L = np.asarray(g["cell"], np.float32)
+    frames = np.stack([np.mod(base + rng.normal(0, 0.05, base.shape), L) for _ in range(1024)]).astype(np.float32)
+    mu = torch.linspace(0.75, 2.5, nbins, device=DEV)
+    spacing = float(mu[1] - mu[0])
+    coeff = float(-0.5 / (width_scale * spacing) ** 2)
+    w = torch.linspace(-1, 1, nbins, device=DEV)
+    cs = _lib.make_cell(np.array(_TRI_CELL, np.float32)) if tri else _lib.make_cell(g["cell"])
+    cutoff = 2.3 if tri else 3.0
+    mask = ops.build_mask(48, index_tuple=(list(range(0, 20)), list(range(20, 48))), device=DEV) if masked else None
+    assert rdf_variants(1024, 48, nbins, spacing, coeff, cs, mask, cutoff) == (fwd[0], bwd[0])
+    info = rdf_plan_info("fwd", 1024, 48, nbins, spacing, coeff, cs, mask)
+    assert (info[0], info[1], info[5]) == fwd[1:]
+    assert rdf_plan_info("bwd", 1024, 48, nbins, spacing, coeff, cs, mask)[0] == bwd[1]
+    assert rdf_variants(1024, 48, nbins, 0.0, coeff, cs, mask, cutoff) == ("direct", "frame")
+    out = []
+    for sp in (spacing, 0.0):
+        xg = T(frames, DEV).requires_grad_(True)
+        raw = ops.RdfRawFn.apply(xg, mu, coeff, cutoff, cs, mask, sp)
+        (gx,) = torch.autograd.grad((raw * w).sum(), xg)
+        out.append((raw.detach(), gx))
+    (ra, ga), (rb, gb) = out
+    close(ra, rb, 2e-5, 1e-6 * float(rb.max()), "forward")
+    close(ga, gb, 1e-4, 3e-5 * float(gb.abs().max()), "backward")
+
+
+# (bins, atoms) -> forward (variant, R, waves per workgroup, 128-column rows); the backward is the fine table throughout
+_RDF_COUNTS = {(37, 108): ("fine", 0, 16, 0), (200, 108): ("lane", 5, 2, 1), (100, 20): ("half", 5, 8, 1),
+               (64, 7): ("half", 5, 8, 1), (100, 300): ("fine", 0, 16, 0), (100, 400): ("lane", 5, 4, 0)}
+
+
 @pytest.mark.parametrize("nbins,n_atoms", [(37, 108), (200, 108), (100, 20), (64, 7), (100, 300), (100, 400)])
 def test_rdf_lane_kernels_other_bin_and_atom_counts(nbins, n_atoms):
-    """Many-frame RDF kernels away from the 100-bin / 108-atom shape: odd and large bin counts (the half-width
-    kernel only fits ~100 bins; more rows fall back to full-width columns with fewer waves), tiny atom counts
-    (most lanes idle, padding entries dominate the pair table) -- against the direct kernels."""
+    """Many-frame RDF kernels away from the 100-bin / 108-atom shape.  37 bins and 300 atoms stay with the fine integer
+    histogram; 200 bins exceed its fine grid and the half-width kernel's LDS: full-width columns, two waves; 20 and 7
+    atoms (below the fine histogram's 64; most lanes idle, padding entries dominate the pair table): half-width columns
+    with 128-column rows; 400 atoms (fine histogram plus sixteen frames exceed the LDS): full-width columns with a run-time
+    stride -- against the direct kernels."""
     from mdgrad_amd import ops, _lib
     g = load_golden("rdf")
     rng = np.random.default_rng(100 + nbins + n_atoms)
     L = np.asarray(g["cell"], np.float32)
     if n_atoms <= 108:
         base = g["xyz"][0][:n_atoms]
-    else:                                   # (300: half-width columns with a run-time stride; 400: full-width)
+    else:
         base = rng.uniform(0, 1, (n_atoms, 3)) * L
     frames = np.stack([np.mod(base + rng.normal(0, 0.05, base.shape), L) for _ in range(1040)]).astype(np.float32)
     mu = torch.linspace(0.75, 2.5, nbins, device=DEV)
@@ -1451,6 +1544,9 @@ def test_rdf_lane_kernels_other_bin_and_atom_counts(nbins, n_atoms):
     coeff = float(-0.5 / spacing ** 2)
     w = torch.linspace(-1, 1, nbins, device=DEV)
     cs = _lib.make_cell(g["cell"])
+    assert rdf_variants(1040, n_atoms, nbins, spacing, coeff, cs, None) == (_RDF_COUNTS[(nbins, n_atoms)][0], "table")
+    info = rdf_plan_info("fwd", 1040, n_atoms, nbins, spacing, coeff, cs, None)
+    assert (info[0], info[1], info[5]) == _RDF_COUNTS[(nbins, n_atoms)][1:]
     out = []
     for sp in (spacing, 0.0):
         xg = T(frames, DEV).requires_grad_(True)

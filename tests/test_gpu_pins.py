@@ -273,9 +273,10 @@ def _oracle_rdf_chunked(frames, cell, nbins, r_range, width, wgt, chunk=100):
 
 @pytest.mark.parametrize("width_scale", [1.0, 1.6, 0.4])
 def test_many_frame_rdf_kernels_vs_oracle(width_scale):
-    """1 100 frames of the 108-atom box through rdf(): half-width forward + fine-table backward (width =
-    spacing), full-width forward + recurrence backward (1.6 x), narrow full-width (0.4 x) -- g(r) and
+    """1 100 frames of the 108-atom box through rdf(): fine integer histogram forward + fine-table backward (width =
+    spacing and 1.6 x), full-width lane-per-pair forward (R = 5) + recurrence backward (0.4 x) -- g(r) and
     d(sum g w)/dxyz against the oracle itself (not a sibling kernel)."""
+    from mdgrad_amd import ops
     from mdgrad_amd.observable import rdf
     g = load_golden("rdf")
     rng = np.random.default_rng(11)
@@ -287,7 +288,10 @@ def test_many_frame_rdf_kernels_vs_oracle(width_scale):
     wgt = torch.linspace(-1, 1, nbins)
     system = mk_system(base, g["cell"])
     x = T(frames, DEV).requires_grad_(True)
-    count, bins, gr = rdf(system, nbins=nbins, r_range=rr, width=width)(x)
+    obs = rdf(system, nbins=nbins, r_range=rr, width=width)
+    route = ops.rdf_route(1100, 108, nbins, obs.spacing, obs.coeff, obs.cutoff_boundary, obs._cell_struct, None)
+    assert route == ("frames",) + {1.0: ("fine", "table"), 1.6: ("fine", "table"), 0.4: ("lane", "frame")}[width_scale]
+    count, bins, gr = obs(x)
     (gx,) = torch.autograd.grad((gr * wgt.to(DEV)).sum(), x)
     g_o, gx_o = _oracle_rdf_chunked(frames, g["cell"], nbins, rr, width, wgt)
     close(gr, g_o, 1e-4, 1e-4, "g(r), 1100 frames, width x%.1f" % width_scale)            # g(r): abs 1e-4

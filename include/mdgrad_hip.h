@@ -427,6 +427,10 @@ int mdg_rdf_fwd_variant(int n_frames, int n_atoms, int nbins, float spacing, flo
                         int32_t* info);
 int mdg_rdf_bwd_variant(int n_frames, int n_atoms, int nbins, float spacing, float coeff, int diag, int masked,
                         int32_t* info);
+/* Host only: the fine integer grid of these centres -- the one the FINE variant, mdg_rdf_fwd_ell and mdg_rdf_fwd_cell count
+ * on: `bins` bins (0: it does not fit) of width h from mu[0] - reach -- and the nodes per centre spacing of the backward's
+ * derivative table; any pointer may be NULL.  0, or -1 where the centres have no such grid (spacing <= 0, coeff >= 0). */
+int mdg_rdf_fine_grid(float spacing, float coeff, int nbins, int32_t* bins, float* h, float* reach, int32_t* table_sub);
 int mdg_rdf_fwd_uniform(const float* xyz, int n_frames, int n_atoms, const MdgCell* cell /*host*/,
                         float cutoff, const uint8_t* mask, const float* mu, float spacing, float coeff,
                         int nbins, float* raw, float* partial, void* stream);

@@ -179,6 +179,8 @@ _SIGNATURES = {
                                       C.c_int, P, P, P]),
     "mdg_rdf_fwd_variant": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
     "mdg_rdf_bwd_variant": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
+    "mdg_rdf_fine_grid": (C.c_int, [C.c_float, C.c_float, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                                    C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
     "mdg_rdf_ell_supported": (C.c_int, [C.c_float, C.c_float, C.c_int]),
     "mdg_rdf_fwd_ell": (C.c_int, [P, C.c_int64, C.POINTER(MdgCell), P, P, P, C.c_int, P, C.c_float, C.c_float, C.c_int, P, P]),
     "mdg_rdf_cell_supported": (C.c_int, [C.c_int, C.POINTER(MdgCell), C.c_float]),

@@ -230,6 +230,8 @@ __global__ __launch_bounds__(RDF_BLOCK) void rdf_fwd_block8_kernel(
 // (R + 1/2) Ds >= 4.65 away, where the Gaussian is below 2^-21.6 of the peak: a relative 3e-7 of a bin's count
 // in the worst case, under the fp32 rounding of a sum of thousands of terms.  Real bin k lives in row
 // k + 2R; rows outside [2R, 2R + nbins) are write-only padding so that no deposit needs a bounds test.
+// The recurrence places the neighbours of bin kc at mu[kc] +- s dmu; every deposited value is taken to the centre as given
+// by a first-order factor (rdf_centre_offset below).
 // The columns are summed in a fixed order at the end => bitwise reproducible.
 //
 // The pairs come from a table built once per call (it stays in L1/L2): entry = (4 i) | (4 j2) << 16 stands for
@@ -266,6 +268,16 @@ constexpr int RDF_TABLE_MAX_ATOMS = 4096;      // 4 j < 2^16 and a table of at m
 // K_0 = K_1 = 1.  Bins are handled two adjacent rows at a time (one ds_read2st64 / ds_write2st64 and one packed
 // fma per two bins): the packed power {r^s, r^(s+1)} advances by r^2.  Outward chain s = 0 (the centre) .. R,
 // inward chain s = 1 .. R.
+// The recurrences of the lane and half kernels step from a centre to its neighbours by Ds = s dmu: they take the centres as
+// exactly equidistant.  The float32 linspace centres are that to an ulp only, and a centre's shift is the same for every pair
+// of its bin, so it does not average out (1.3e-6 .. 8e-6 of the largest bin against the float64 sum, growing like 1 / sigma).
+// Per row, 2 ln 2 x the scaled offset of the centre as given from the grid the recurrence walks, delta_k = s (mu_k - mu_0) -
+// k Ds: a value reached from anchor row a belongs to x + (delta_k - delta_a) and is multiplied by 1 + x 2 ln 2 (delta_k -
+// delta_a), the first order of exp2(-(x - eps)^2) / exp2(-x^2) (eps < 1e-4: the second order is below 1e-8).
+__device__ __forceinline__ float rdf_centre_offset(float centre, float mu0, float sc, float Ds, int k) {
+    return (float)(1.3862943611198906 * (((double)centre - (double)mu0) * (double)sc - (double)k * (double)Ds));
+}
+
 template <int R>
 struct RdfLane {
     static constexpr int NPO = (R + 1) / 2, NPI = R / 2;
@@ -305,25 +317,29 @@ struct RdfLane {
     }
     // branch-free: a rejected pair adds +0 (a bitwise no-op) around bin 0.  Plain read-add-write on the
     // lane-private column: ds_add_f32 is serialised per lane in the LDS atomic unit (measured 9x slower).
-    __device__ __forceinline__ void rows_add_store(Rows& w, float d, float m, bool ok) const {
-        const float x0 = (d - m) * sc;
-        const float a_ = ok ? 2.f * Ds * x0 : 0.f;
+    // dl = the offsets of rdf_centre_offsets at the window's first row (bin kc - R): the value the recurrence gives for the
+    // bin s rows from kc belongs to a centre at mu[kc] +- s dmu; the factor 1 + x eps takes it to the centre as given.
+    __device__ __forceinline__ void rows_add_store(Rows& w, float d, float m, bool ok, const float* dl) const {
+        const float x0 = ok ? (d - m) * sc : 0.f;
+        const float a_ = 2.f * Ds * x0;
         const float e0 = ok ? __builtin_amdgcn_exp2f(-x0 * x0) : 0.f;
         const float rp = __builtin_amdgcn_exp2f(a_ - Ds2), rm = __builtin_amdgcn_exp2f(-a_ - Ds2);
         const float rp2 = rp * rp, rm2 = rm * rm;
+        const float dc = dl[R];
+        auto fix = [&](int s_) { return fmaf(x0 - (float)s_ * Ds, dl[R + s_] - dc, 1.f); };      // s_ < 0: towards smaller mu
         f32x2 Po = e0 * f32x2{1.f, rp}, Pi = e0 * f32x2{rm2, rm};
 #pragma unroll
         for (int m_ = 0; m_ < NPO; ++m_) {
-            w.vo[m_] += Ko[m_] * Po;
+            w.vo[m_] += Ko[m_] * Po * f32x2{fix(2 * m_), fix(2 * m_ + 1)};
             if (m_ + 1 < NPO || TAIL_O) Po *= rp2;
         }
 #pragma unroll
         for (int m_ = 0; m_ < NPI; ++m_) {
-            w.vi[m_] += Ki[m_] * Pi;
+            w.vi[m_] += Ki[m_] * Pi * f32x2{fix(-2 * m_ - 2), fix(-2 * m_ - 1)};
             if (m_ + 1 < NPI || TAIL_I) Pi *= rm2;
         }
-        if (TAIL_O) w.vlo += Klast * Po.x;                       // Po = {e0 r^R, .} after NPO steps (R even)
-        if (TAIL_I) w.vli += Klast * Pi.y;                       // Pi = {., e0 r^R} after NPI steps (R odd)
+        if (TAIL_O) w.vlo += Klast * Po.x * fix(R);              // Po = {e0 r^R, .} after NPO steps (R even)
+        if (TAIL_I) w.vli += Klast * Pi.y * fix(-R);             // Pi = {., e0 r^R} after NPI steps (R odd)
         float* h = w.h;
 #pragma unroll
         for (int m_ = 0; m_ < NPO; ++m_) { h[(R + 2 * m_) * 64] = w.vo[m_].x; h[(R + 2 * m_ + 1) * 64] = w.vo[m_].y; }
@@ -391,11 +407,16 @@ __global__ __launch_bounds__(256) void rdf_fwd_lane_kernel(
     float* hist = sm + (size_t)wid * ((size_t)rows * 64 + 3 * PXLD);
     float* px = hist + (size_t)rows * 64;                       // [3][PXLD]   (8-byte aligned: rows * 64 and PXLD are even)
     float* smu = sm + (size_t)nw * ((size_t)rows * 64 + 3 * PXLD);   // [nbins + 2R] centres incl. extrapolated pads
+    float* sdl = smu + nbins + 2 * R;                           // [nbins + 4R] rdf_centre_offset of every histogram row
     RdfLane<R> K;
     K.init(mu, coeff, nbins);
     for (int k = threadIdx.x; k < nbins + 2 * R; k += blockDim.x) {
         const int kk = k - R;
         smu[k] = (kk >= 0 && kk < nbins) ? mu[kk] : fmaf((float)kk, K.dmu, K.mu0);
+    }
+    for (int k = threadIdx.x; k < rows; k += blockDim.x) {
+        const int kk = k - 2 * R;
+        sdl[k] = rdf_centre_offset((kk >= 0 && kk < nbins) ? mu[kk] : fmaf((float)kk, K.dmu, K.mu0), K.mu0, K.sc, K.Ds, kk);
     }
     for (int e = lane; e < rows * 64; e += 64) hist[e] = 0.f;
     for (int e = lane; e < 3 * PXLD; e += 64) px[e] = (e >= N && e < PXLD) ? __builtin_nanf("") : 0.f;
@@ -427,8 +448,9 @@ __global__ __launch_bounds__(256) void rdf_fwd_lane_kernel(
                     okA = okA & (mask[(size_t)mi * N + min(mj, N - 1)] != 0);
                     okB = okB & (mask[(size_t)mi * N + min(mj + 1, N - 1)] != 0);
                 }
-                // v_sqrt_f32 (1 ulp): far below the Gaussian's own rounding
-                dd = f32x2{__builtin_amdgcn_sqrtf(d2.x), __builtin_amdgcn_sqrtf(d2.y)};
+                // correctly rounded: an error of v_sqrt_f32 (1 ulp) that does not average to zero moves every distance like a
+                // shift of the centres, 1 / sigma times as much in the histogram (see rdf_centre_offset)
+                dd = f32x2{sqrtf(d2.x), sqrtf(d2.y)};
                 const f32x2 tk = (dd - K.mu0) * K.inv_dmu;
                 kA = (int)rintf(tk.x); kB = (int)rintf(tk.y);
                 okA = okA & (kA >= -R) & (kA <= nbins - 1 + R);
@@ -446,15 +468,15 @@ __global__ __launch_bounds__(256) void rdf_fwd_lane_kernel(
             locate_a(tp[0]);
             locate_b();
             auto step = [&](uint32_t& t, const uint32_t* next) {
-                const f32x2 d_ = dd, m_ = mm; const int kb = kB; const bool oa = okA, ob = okB;
+                const f32x2 d_ = dd, m_ = mm; const int ka = kA, kb = kB; const bool oa = okA, ob = okB;
                 typename RdfLane<R>::Rows w;
                 K.rows_load(col, kA, w);
                 locate_a(t);
                 t = *next;
-                K.rows_add_store(w, d_.x, m_.x, oa);
+                K.rows_add_store(w, d_.x, m_.x, oa, sdl + ka + R);
                 K.rows_load(col, kb, w);
                 locate_b();
-                K.rows_add_store(w, d_.y, m_.y, ob);
+                K.rows_add_store(w, d_.y, m_.y, ob, sdl + kb + R);
             };
             for (int it = 0; it < iters; it += 4) {
                 tp += 256;
@@ -503,6 +525,7 @@ __global__ __launch_bounds__(512) void rdf_fwd_half_kernel(
     float* hist = sm + (size_t)wid * ((size_t)rows * 32 + 3 * PXLD);
     float* px = hist + (size_t)rows * 32;                       // [3][PXLD]
     float* smu = sm + (size_t)nw * ((size_t)rows * 32 + 3 * PXLD);   // [rows] centre of every row
+    float* sdl = smu + rows;                                    // [rows] rdf_centre_offset of every row
     const float sc = sqrtf(-coeff * LOG2E);
     const float mu0 = mu[0];
     const float dmu = (mu[nbins - 1] - mu0) / (float)(nbins - 1), inv_dmu = 1.f / dmu;
@@ -510,7 +533,9 @@ __global__ __launch_bounds__(512) void rdf_fwd_half_kernel(
     const float c2 = __builtin_amdgcn_exp2f(-2.f * Ds2), c4 = (c2 * c2) * (c2 * c2);
     for (int r = threadIdx.x; r < rows; r += blockDim.x) {
         const int kk = r - PADL;
-        smu[r] = (kk >= 0 && kk < nbins) ? mu[kk] : fmaf((float)kk, dmu, mu0);
+        const float c_ = (kk >= 0 && kk < nbins) ? mu[kk] : fmaf((float)kk, dmu, mu0);
+        smu[r] = c_;
+        sdl[r] = rdf_centre_offset(c_, mu0, sc, Ds, kk);
     }
     for (int e = lane; e < rows * 32; e += 64) hist[e] = 0.f;
     for (int e = lane; e < 3 * PXLD; e += 64) px[e] = (e >= N && e < PXLD) ? __builtin_nanf("") : 0.f;
@@ -519,6 +544,7 @@ __global__ __launch_bounds__(512) void rdf_fwd_half_kernel(
     const int gw = blockIdx.x * nw + wid, nwaves = gridDim.x * nw;
     float* hcol = hist + col + (size_t)(boff + PADL) * 32;      // row of bin boff
     const float* smub = smu + boff + PADL;
+    const float* sdlb = sdl + boff + PADL;
     // R + 1 rows upwards from bin k + boff.  A rejected pair comes in as (1e4, bin 0): y0 clamps to 20, E0
     // underflows to an exact 0 and every product with the (finite) multipliers stays 0.
     // In two parts: the values of all four deposits of a step are computed first, so that the four dependent
@@ -531,9 +557,14 @@ __global__ __launch_bounds__(512) void rdf_fwd_half_kernel(
         const float E0 = __builtin_amdgcn_exp2f(-y0 * y0), r0 = __builtin_amdgcn_exp2f(fmaf(y0, twoDs, -Ds2));
         const float r1 = r0 * c2, r2 = r1 * c2;
         f32x2 P = {E0, E0 * r0}, M = f32x2{r0, r1} * f32x2{r1, r2};     // {rho_0 rho_1, rho_1 rho_2}
+        // row t above the base row sits at y0 - t Ds on the recurrence's grid: to the centre as given (rdf_centre_offset)
+        const float* dl = sdlb + k;
+        const float d0 = dl[0];
 #pragma unroll
         for (int m_ = 0; m_ < HR / 2; ++m_) {
-            w.P[m_] = P;
+            const f32x2 fx = {fmaf(y0 - (float)(2 * m_) * Ds, dl[2 * m_] - d0, 1.f),
+                              fmaf(y0 - (float)(2 * m_ + 1) * Ds, dl[2 * m_ + 1] - d0, 1.f)};
+            w.P[m_] = P * fx;
             if (m_ + 1 < HR / 2) { P *= M; M *= c4; }
         }
     };
@@ -574,7 +605,7 @@ __global__ __launch_bounds__(512) void rdf_fwd_half_kernel(
                     okB = okB & (mask[(size_t)mi * N + min(mj + 1, N - 1)] != 0);
                 }
                 half_add(prev[1]);
-                const f32x2 dd = {__builtin_amdgcn_sqrtf(d2.x), __builtin_amdgcn_sqrtf(d2.y)};
+                const f32x2 dd = {sqrtf(d2.x), sqrtf(d2.y)};                     // correctly rounded: see rdf_fwd_lane_kernel
                 const f32x2 tk = (dd - mu0) * inv_dmu;
                 int kA = (int)rintf(tk.x), kB = (int)rintf(tk.y);
                 okA = okA & (kA >= -R) & (kA <= nbins - 1 + R);
@@ -624,13 +655,16 @@ __global__ __launch_bounds__(512) void rdf_fwd_half_kernel(
 // Fine-grid backward for equally spaced centres (width ~ spacing): dL/dd(d) = sum_k g_k 2 coeff (d - mu_k) e_k(d)
 // is ONE smooth function of the distance.  A tiny kernel tabulates it -- value and hf * slope on RDF_SUB nodes
 // per centre spacing, x_n = xlo + n hf -- and the per-pair work shrinks from a 13-bin Gaussian sum to the
-// evaluation of the cell's cubic Hermite interpolant from LDS (interpolation error ~ (hf/sigma)^4 / 384 * 3
-// < 2e-6 of a unit contribution for hf = sigma / 8).
+// evaluation of the cell's cubic Hermite interpolant from LDS (interpolation error (hf/sigma)^4 / 384 * 5.8 -- the largest
+// fourth derivative of t exp(-t^2 / 2), at t = 0.6 -- = 1.5e-6 of a unit contribution g / sigma for hf = sigma / 10, i.e.
+// width = spacing; tests/test_rdf_ref_host.py holds the float64 restatement of the table below 2e-6.  With eight nodes
+// per spacing, and 3 taken for that derivative, it measured 3.6e-6.)
 // (The transposed idea for the forward pass -- every pair deposits its four Hermite weights into per-wave
 //  node accumulators with fixed-point ds_add_u32, Gaussians evaluated once per wave at the end -- halves the
 //  arithmetic but is bound by the LDS atomic unit, ~15 cycles per wave instruction and CU plus 2-3-way address
 //  conflicts: 13.5 ms against 11.6 ms for the lane-private columns of rdf_fwd_lane_kernel.  Measured, removed.)
-constexpr int RDF_SUB = 8;
+constexpr int RDF_SUB = 10;      // nodes per centre spacing of this table (the u-space table of the ring adjoint: RDF_SUB_U)
+constexpr int RDF_SUB_U = 8;     // rdf_u_grid (common.hpp)
 
 struct FineGrid { float xlo, hf, inv_hf; int nn; };
 
@@ -1229,7 +1263,7 @@ static int rdf_fwd_reach(float spacing_s) {
     return 0;
 }
 static size_t rdf_lane_lds(int nw, int R, int pxld, int nbins) {
-    return sizeof(float) * ((size_t)(nbins + 2 * R) + (size_t)nw * ((size_t)(nbins + 4 * R) * 64 + 3 * (size_t)pxld));
+    return sizeof(float) * ((size_t)(nbins + 2 * R) + (size_t)(nbins + 4 * R) + (size_t)nw * ((size_t)(nbins + 4 * R) * 64 + 3 * (size_t)pxld));
 }
 
 // ---- shared with the fused observable of the trajectory kernels and csrc/rdf_cell.hip (common.hpp): the one sizing of
@@ -1245,7 +1279,9 @@ RdfFinePlan mdg_rdf_fine_plan(float spacing, float coeff, int nbins) {
     P.nfine = nfine <= RDF_FINE_MAX ? nfine : 0;                  // 0: does not fit the workgroup's LDS histogram
     const float spacing_s = spacing * P.sc;
     const int R = rdf_lane_reach(spacing_s);
-    if (R && spacing_s <= 1.0f && fine_nodes(nbins, R) <= 4096) { P.reach_bins = R; P.ncell = fine_nodes(nbins, R) - 1; }
+    // (the u-space table of the ring adjoint: RDF_SUB_U cells per spacing, rdf_u_grid)
+    const int ncell_u = (nbins - 1 + 2 * (R + 1)) * RDF_SUB_U;
+    if (R && spacing_s <= 1.0f && ncell_u + 1 <= 4096) { P.reach_bins = R; P.ncell = ncell_u; }
     return P;
 }
 
@@ -1300,7 +1336,7 @@ static RdfFwdPlan rdf_fwd_plan(int n_frames, int n_atoms, int nbins, float spaci
             P.scratch_words = (size_t)P.n_padded;
             // half-width columns, eight waves per workgroup, when they fit (R = 5, 100 bins: 137 KB)
             const size_t rows_h = (size_t)((nbins + 4 * R + 3) & ~1);
-            const size_t lds_half = sizeof(float) * (rows_h + 8 * (rows_h * 32 + 3 * (size_t)P.pxld));
+            const size_t lds_half = sizeof(float) * (2 * rows_h + 8 * (rows_h * 32 + 3 * (size_t)P.pxld));
             // (spacing_s <= 1.5: the recurrence multipliers of a rejected pair, y0 clamped to 20, stay finite)
             const bool half = R == 5 && spacing_s <= 1.5f && lds_half <= RDF_LDS_BUDGET;
             P.variant = half ? RdfFwd::half : RdfFwd::lane;
@@ -1440,7 +1476,10 @@ static RdfBwdPlan rdf_bwd_plan(int n_frames, int n_atoms, int nbins, float spaci
     P.R = nbins >= 2 ? rdf_lane_reach(rdf_spacing_s(spacing, coeff)) : 0;
     // table of dL/dd on the fine nodes, then the wave-per-frame kernel with a table lookup per pair: for width ~ spacing
     // (Ds <= 1) and at most 4096 nodes
-    P.cells = mdg_rdf_fine_plan(spacing, coeff, nbins).ncell;
+    {
+        const float spacing_s = rdf_spacing_s(spacing, coeff);
+        P.cells = P.R && spacing_s <= 1.0f && fine_nodes(nbins, P.R) <= 4096 ? fine_nodes(nbins, P.R) - 1 : 0;
+    }
     if (P.cells) {
         // index-doubled rows: the last lane group's idle lanes reach index 64 ceil(N/64) - 1 + N/2 + 1
         P.ldw = (max(2 * n_atoms, 64 * ((n_atoms + 63) / 64) + n_atoms / 2 + 1) + 2) & ~1;
@@ -1529,6 +1568,18 @@ extern "C" int mdg_rdf_bwd_variant(int n_frames, int n_atoms, int nbins, float s
     const RdfBwdPlan P = rdf_bwd_plan(n_frames, n_atoms, nbins, spacing, coeff);      // (neither the cell nor a mask matters)
     return P.fits ? rdf_report((int)P.variant, info, {P.R, P.waves, P.grid, (int32_t)P.lds, P.ldw, P.cells}) : -1;
 }
+// The grids of mdg_rdf_fine_plan for these centres, host only: the fine integer histogram of the FINE variant, of
+// mdg_rdf_fwd_ell and of mdg_rdf_fwd_cell (bins -- 0: it does not fit --, bin width h, reach: it starts at mu[0] - reach) and
+// the nodes per centre spacing of the backward's derivative table.  Returns 0, or -1 for centres without a grid.
+extern "C" int mdg_rdf_fine_grid(float spacing, float coeff, int nbins, int32_t* bins, float* h, float* reach, int32_t* table_sub) {
+    const RdfFinePlan P = mdg_rdf_fine_plan(spacing, coeff, nbins);
+    if (!(P.sc > 0.f)) return -1;
+    if (bins) *bins = (int32_t)P.nfine;
+    if (h) *h = P.h;
+    if (reach) *reach = P.reach;
+    if (table_sub) *table_sub = RDF_SUB;
+    return 0;
+}
 
 int mdg_rdf_fine_finish(const uint32_t* ghist, const RdfFinePlan& P, const float* mu, int nbins, float* raw, hipStream_t st) {
     rdf_fine_finish_launch(ghist, P, mu, nbins, raw, st);
@@ -1537,7 +1588,7 @@ int mdg_rdf_fine_finish(const uint32_t* ghist, const RdfFinePlan& P, const float
 }
 int mdg_rdf_bwd_table(const float* mu, float coeff, int nbins, const float* g_raw, const RdfFinePlan& P, float4* tab,
                       hipStream_t st) {
-    const int nn = P.ncell + 1;
+    const int nn = fine_nodes(nbins, P.reach_bins);                   // (this table's own grid: RDF_SUB nodes per spacing)
     hipLaunchKernelGGL(rdf_bwd_table_kernel, dim3((nn + 254) / 256), dim3(256), 0, st, mu, coeff, nbins, g_raw, P.reach_bins, tab);
     MDG_CHECK_LAUNCH("rdf_bwd_table_kernel");
     return MDG_OK;

@@ -1656,6 +1656,28 @@ def rdf_route(F, N, nbins, spacing, coeff, cutoff, cell_struct, mask):
     return "frames", (RDF_FWD_VARIANTS[fwd] if fwd >= 0 else None), (RDF_BWD_VARIANTS[bwd] if bwd >= 0 else None)
 
 
+def rdf_plan(direction, F, N, nbins, spacing, coeff, cell_struct, mask):
+    """The launch plan of csrc/rdf.hip for this shape (no GPU needed), direction "fwd" or "bwd": the MDG_RDF_PLAN_INFO words
+    of mdg_rdf_fwd_variant / mdg_rdf_bwd_variant by name, and from mdg_rdf_fine_grid the forward's fine integer grid
+    (fine_bins of width fine_h from mu[0] - fine_reach: also the one the cell sweep and the list route count on) and the
+    backward table's nodes per centre spacing (table_sub)."""
+    lib = _lib.load()
+    info = (C.c_int32 * 6)()
+    fn = getattr(lib, "mdg_rdf_%s_variant" % direction)
+    v = fn(F, N, nbins, float(spacing), float(coeff), int(cell_struct.diag), int(mask is not None), info)
+    if v < 0:
+        return None
+    out = dict(variant=(RDF_FWD_VARIANTS if direction == "fwd" else RDF_BWD_VARIANTS)[v], R=info[0], waves=info[1],
+               workgroups=info[2], lds_bytes=info[3], stride=info[4])
+    bins, sub, h, reach = C.c_int32(0), C.c_int32(0), C.c_float(0.0), C.c_float(0.0)
+    lib.mdg_rdf_fine_grid(float(spacing), float(coeff), nbins, C.byref(bins), C.byref(h), C.byref(reach), C.byref(sub))
+    if direction == "fwd":
+        out.update(rows128=bool(info[5]), fine_bins=bins.value, fine_h=h.value, fine_reach=reach.value)
+    else:
+        out.update(cells=info[5], table_sub=sub.value)
+    return out
+
+
 class RdfRawFn(torch.autograd.Function):
     """raw[k] = sum over frames and i<j pairs (d < cutoff) of exp(coeff (d - mu_k)^2)
     (the GaussianSmearing(...).sum(0) of torchmd/observable.py:70)."""

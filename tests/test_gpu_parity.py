@@ -1469,13 +1469,16 @@ _RDF_48 = [
     ((100, 1.6, False, False), ("lane", 11, 4, 1), ("table", 11)),     # R = 11, 128-column rows
     ((100, 1.6, True, False), ("lane", 11, 4, 0), ("table", 11)),      # R = 11, DIAG = false
     # width = 0.4 spacing: the forward holds; the recurrence backward (rdf_bwd_kernel<., 6>) measures a largest error of
-    # 9.155e-03 where 8.016e-03 is allowed (max |g| = 260: 3.5e-5 of it against the 3e-5 allowed).  Not traced further; the
-    # likely cause: it steps the scaled distance by s * spacing = 2.1 per bin, i.e. takes the float32 linspace centres as exactly equidistant -- they are to
-    # an ulp of 2.5, 2.9e-5 in scaled units at s = 120 -- and 48 atoms leave few pairs per atom to average that over (the
-    # same variants pass at 108 atoms in test_rdf_kernel_variants_agree).  The kernel is as it was before the plans.
+    # 9.155e-03 where 8.016e-03 is allowed (max |g| = 260: 3.5e-5 of it against the 3e-5 allowed).  Against float64
+    # (tests/test_gpu_rdf_ref.py, "lane/frame R=6 width 0.4": same shape, no half-cell pairs) the kernel is sound: the
+    # plain formula evaluated in float32 on the CPU is itself 3.1e-5 of an atom's scale from float64 -- ulp(d) x s,
+    # s = 120 --, the kernel 4.6e-5 where 10 x that floor, 3.1e-4, is allowed.  The 3e-5 of this sibling comparison sits
+    # at the float32 floor of the shape: a tolerance this case cannot meet, not a kernel error (the same variants pass
+    # at 108 atoms in test_rdf_kernel_variants_agree).
     pytest.param((100, 0.4, False, False), ("lane", 5, 4, 1), ("frame", 6),
                  marks=pytest.mark.xfail(strict=True, raises=AssertionError,
-                                         reason="backward: max err 9.155e-03, allowed 8.016e-03 (rdf_bwd_kernel<., 6> at 48 atoms)")),
+                                         reason="backward: max err 9.155e-03, allowed 8.016e-03 = 3e-5 max|g|; the float32 floor "
+                                                "of this shape is 3.1e-5 (rdf_bwd_kernel<., 6> is within 10 x floor of float64)")),
     ((500, 1.6, False, False), ("lane", 11, 1, 1), ("frame", 11)),     # one wave per workgroup; rdf_bwd_kernel<., 11>
 ]
 
@@ -1487,7 +1490,7 @@ def test_rdf_variants_below_the_fine_histogram(case, fwd, bwd):
     (500 bins), the recurrence backward with R = 6 and R = 11 -- the variant is asserted first, then the result is compared
     with the direct kernels (spacing 0) on the same input, as in test_rdf_lane_kernels_general_variants.  Measured: five
     cases hold; at width = 0.4 spacing the backward misses, largest error 9.155e-03 against 8.016e-03 allowed (expected
-    failure, see _RDF_48)."""
+    failure, see _RDF_48: the allowance is the float32 floor of that shape, the kernel holds against float64)."""
     from mdgrad_amd import ops, _lib
     nbins, width_scale, tri, masked = case
     g = load_golden("rdf")

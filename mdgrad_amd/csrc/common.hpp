@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <type_traits>
 #include "../../include/mdgrad_hip.h"
 
 #define MDG_WAVE 64
@@ -387,4 +388,32 @@ __device__ __forceinline__ void block_sum_n(float (&v)[NV], float* red) {
         for (int w = 0; w < nw; ++w) s += red[w * NV + k];
         v[k] = s;
     }
+}
+
+// -- what the per-atom terms share at their outputs and launches (sw, eam, tersoff, tersoff_multi, coulomb, ewald, ewald_excl) --
+// dst[3 i ...] = os * (x, y, z), added onto what is there when oacc (the force sums of a Stack)
+__device__ __forceinline__ void store3(float* dst, int i, float os, int oacc, float x, float y, float z) {
+    if (oacc) { dst[3 * i] = fmaf(os, x, dst[3 * i]); dst[3 * i + 1] = fmaf(os, y, dst[3 * i + 1]); dst[3 * i + 2] = fmaf(os, z, dst[3 * i + 2]); }
+    else { dst[3 * i] = os * x; dst[3 * i + 1] = os * y; dst[3 * i + 2] = os * z; }
+}
+
+// the one-workgroup energy sums in double (csrc/ewald.hip, ewald_excl.hip): one value per thread of a workgroup of BLOCK threads,
+// added by a fixed tree in `red` [BLOCK] (LDS); the sum is left in red[0], behind a barrier
+template <int BLOCK>
+__device__ __forceinline__ void tree_sum(double s, double* red) {
+    const int t = threadIdx.x;
+    red[t] = s;
+    __syncthreads();
+    for (int o = BLOCK / 2; o > 0; o >>= 1) {
+        if (t < o) red[t] += red[t + o];
+        __syncthreads();
+    }
+}
+
+// f(std::integral_constant<int, LEVEL>()) for the run-time level 0, 1 or 2: the caller launches kernel<decltype(L)::value>
+template <class F>
+inline void with_level(int level, F&& f) {
+    if (level == 2) f(std::integral_constant<int, 2>());
+    else if (level == 1) f(std::integral_constant<int, 1>());
+    else f(std::integral_constant<int, 0>());
 }

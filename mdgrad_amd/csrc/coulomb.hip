@@ -86,19 +86,11 @@ __global__ void coulomb_ell_kernel(const CoulombArgs A) {
             e = qc * (0.5f * pt - A.self_s * qi);
             const float os = A.oscale;
             if (LEVEL >= 1) {
-                if (A.grad) {
-                    if (A.oacc) { A.grad[3 * i] = fmaf(os, gx, A.grad[3 * i]); A.grad[3 * i + 1] = fmaf(os, gy, A.grad[3 * i + 1]);
-                                  A.grad[3 * i + 2] = fmaf(os, gz, A.grad[3 * i + 2]); }
-                    else { A.grad[3 * i] = os * gx; A.grad[3 * i + 1] = os * gy; A.grad[3 * i + 2] = os * gz; }
-                }
+                if (A.grad) store3(A.grad, i, os, A.oacc, gx, gy, gz);
                 if (A.pot) A.pot[i] = pt;
             }
             if (LEVEL >= 2) {
-                if (A.hw) {
-                    if (A.oacc) { A.hw[3 * i] = fmaf(os, hx, A.hw[3 * i]); A.hw[3 * i + 1] = fmaf(os, hy, A.hw[3 * i + 1]);
-                                  A.hw[3 * i + 2] = fmaf(os, hz, A.hw[3 * i + 2]); }
-                    else { A.hw[3 * i] = os * hx; A.hw[3 * i + 1] = os * hy; A.hw[3 * i + 2] = os * hz; }
-                }
+                if (A.hw) store3(A.hw, i, os, A.oacc, hx, hy, hz);
                 if (A.potw) A.potw[i] = pw;
             }
         }
@@ -141,13 +133,6 @@ int coulomb_lpa(int N) {                     // (pick_lpa of csrc/pair_ell.hip)
 
 extern "C" int64_t mdg_coulomb_partial_size(int n_atoms) { return atom_blocks(n_atoms, coulomb_lpa(n_atoms), 256); }
 
-#define MDG_COULOMB_LAUNCH(LPA_)                                                                       \
-    case LPA_:                                                                                         \
-        if (level == 2) hipLaunchKernelGGL((coulomb_ell_kernel<LPA_, 2>), grid, dim3(256), 0, st, a);  \
-        else if (level == 1) hipLaunchKernelGGL((coulomb_ell_kernel<LPA_, 1>), grid, dim3(256), 0, st, a); \
-        else hipLaunchKernelGGL((coulomb_ell_kernel<LPA_, 0>), grid, dim3(256), 0, st, a);             \
-        break;
-
 extern "C" int mdg_coulomb_eval(const float* pos, int n_atoms, const MdgCell* cell, const int32_t* col, const int32_t* shift,
                                 const int32_t* cnt, int max_nbr, const float* q, const MdgCoulombConsts* k, const float* w,
                                 float* energy, float* grad, float* hw, float* pot, float* potw, float* partial, float out_scale,
@@ -170,7 +155,15 @@ extern "C" int mdg_coulomb_eval(const float* pos, int n_atoms, const MdgCell* ce
     const int nblocks = (int)atom_blocks(n_atoms, lpa, 256);
     dim3 grid(nblocks);
     hipStream_t st = (hipStream_t)stream;
-    switch (lpa) { MDG_COULOMB_LAUNCH(8) MDG_COULOMB_LAUNCH(16) MDG_COULOMB_LAUNCH(32) MDG_COULOMB_LAUNCH(64) }
+    with_level(level, [&](auto L) {
+        constexpr int LV = decltype(L)::value;
+        switch (lpa) {
+            case 8: hipLaunchKernelGGL((coulomb_ell_kernel<8, LV>), grid, dim3(256), 0, st, a); break;
+            case 16: hipLaunchKernelGGL((coulomb_ell_kernel<16, LV>), grid, dim3(256), 0, st, a); break;
+            case 32: hipLaunchKernelGGL((coulomb_ell_kernel<32, LV>), grid, dim3(256), 0, st, a); break;
+            default: hipLaunchKernelGGL((coulomb_ell_kernel<64, LV>), grid, dim3(256), 0, st, a);
+        }
+    });
     if (energy) hipLaunchKernelGGL(energy_finish, dim3(1), dim3(64), 0, st, partial, nblocks, energy);
     MDG_CHECK_LAUNCH("coulomb_ell_kernel");
     return MDG_OK;

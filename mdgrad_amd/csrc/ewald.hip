@@ -171,24 +171,10 @@ __global__ __launch_bounds__(EW_ATOM_BLOCK) void ewald_atom_kernel(const EwArgs 
     }
     // sums in turns -> 2 q_i (2 pi / L_d) per axis
     const float os = A.oscale, c2 = 2.f * a.w * EW_TWO_PI;
-    if (A.grad) {
-        float* o = A.grad + 3 * at;
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            const float x = c2 * v[d] / A.L[d];
-            o[d] = A.oacc ? fmaf(os, x, o[d]) : os * x;
-        }
-    }
+    if (A.grad) store3(A.grad + 3 * at, 0, os, A.oacc, c2 * v[0] / A.L[0], c2 * v[1] / A.L[1], c2 * v[2] / A.L[2]);
     if (A.pot) A.pot[at] = 2.f * v[3];
     if (HASW) {
-        if (A.hw) {
-            float* o = A.hw + 3 * at;
-#pragma unroll
-            for (int d = 0; d < 3; ++d) {
-                const float x = c2 * v[4 + d] / A.L[d];
-                o[d] = A.oacc ? fmaf(os, x, o[d]) : os * x;
-            }
-        }
+        if (A.hw) store3(A.hw + 3 * at, 0, os, A.oacc, c2 * v[NV - 4] / A.L[0], c2 * v[NV - 3] / A.L[1], c2 * v[NV - 2] / A.L[2]);
         if (A.potw) A.potw[at] = 2.f * v[NV - 1];
     }
 }
@@ -210,12 +196,7 @@ __global__ __launch_bounds__(EW_BLOCK) void ewald_energy_kernel(const float4* __
         }
         s += sr;
     }
-    red[t] = s;
-    __syncthreads();
-    for (int o = EW_BLOCK / 2; o > 0; o >>= 1) {
-        if (t < o) red[t] += red[t + o];
-        __syncthreads();
-    }
+    tree_sum<EW_BLOCK>(s, red);
     if (t == 0) energy[0] = (float)red[0];
 }
 

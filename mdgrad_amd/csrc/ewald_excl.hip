@@ -129,20 +129,10 @@ __global__ __launch_bounds__(XC_BLOCK) void ewald_excl_kernel(const ExclArgs A) 
         e = 0.5 * (double)qc * (double)pt;
         const float os = A.oscale;
         const bool touch = !(A.oacc && lo == hi);        // an empty row adds nothing: the buffer keeps its bits
-        if (LEVEL >= 1 && A.grad && touch) {
-            float* o = A.grad + 3 * i;
-            gx *= qc; gy *= qc; gz *= qc;
-            if (A.oacc) { o[0] = fmaf(os, gx, o[0]); o[1] = fmaf(os, gy, o[1]); o[2] = fmaf(os, gz, o[2]); }
-            else { o[0] = os * gx; o[1] = os * gy; o[2] = os * gz; }
-        }
+        if (LEVEL >= 1 && A.grad && touch) store3(A.grad + 3 * i, 0, os, A.oacc, qc * gx, qc * gy, qc * gz);
         if (A.pot) A.pot[i] = pt;
         if (LEVEL >= 2) {
-            if (A.hw && touch) {
-                float* o = A.hw + 3 * i;
-                hx *= qc; hy *= qc; hz *= qc;
-                if (A.oacc) { o[0] = fmaf(os, hx, o[0]); o[1] = fmaf(os, hy, o[1]); o[2] = fmaf(os, hz, o[2]); }
-                else { o[0] = os * hx; o[1] = os * hy; o[2] = os * hz; }
-            }
+            if (A.hw && touch) store3(A.hw + 3 * i, 0, os, A.oacc, qc * hx, qc * hy, qc * hz);
             if (A.potw) A.potw[i] = pw;
         }
     }
@@ -165,12 +155,7 @@ __global__ __launch_bounds__(XC_BLOCK) void ewald_excl_finish(const double* __re
     const int t = threadIdx.x;
     double s = 0.0;
     for (long long b = t; b < nblocks; b += XC_BLOCK) s += partial[b];
-    red[t] = s;
-    __syncthreads();
-    for (int o = XC_BLOCK / 2; o > 0; o >>= 1) {
-        if (t < o) red[t] += red[t + o];
-        __syncthreads();
-    }
+    tree_sum<XC_BLOCK>(s, red);
     if (t == 0) energy[0] = (float)red[0];
 }
 
@@ -216,9 +201,7 @@ extern "C" int mdg_ewald_excl_eval(const float* pos, int n_rep, int n_atoms, con
     const dim3 grid((unsigned)nblocks), block(XC_BLOCK);
     hipStream_t st = (hipStream_t)stream;
     const int level = w ? 2 : (grad ? 1 : 0);
-    if (level == 2) hipLaunchKernelGGL((ewald_excl_kernel<2>), grid, block, 0, st, a);
-    else if (level == 1) hipLaunchKernelGGL((ewald_excl_kernel<1>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((ewald_excl_kernel<0>), grid, block, 0, st, a);
+    with_level(level, [&](auto L) { hipLaunchKernelGGL((ewald_excl_kernel<decltype(L)::value>), grid, block, 0, st, a); });
     MDG_CHECK_LAUNCH("ewald_excl_kernel");
     if (energy) {
         hipLaunchKernelGGL(ewald_excl_finish, dim3(1), block, 0, st, partial, nblocks, energy);

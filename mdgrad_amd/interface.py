@@ -205,6 +205,11 @@ class _StaticTerm:
     """Mixin of a term on a static table: nothing to search at a rebuild, and under fixed capacities (HIP-graph capture)
     nothing can overflow."""
 
+    def _hip_ok(self, xyz=None):
+        if xyz is not None and (not xyz.is_cuda or xyz.dtype != torch.float32):
+            return False
+        return self.analytic
+
     def _reset_topology(self, xyz):
         pass
 
@@ -264,28 +269,18 @@ def _theta_flat_tail(pthw, thetas, want_theta, accum):
     return [gw[starts[k]:starts[k + 1]].reshape(p.shape) for k, (p, t) in enumerate(zip(thetas, trainable)) if t]
 
 
-class _ManyBodyTerm(_ListTerm):
-    """A many-body term on the ELL list whose kernels return per-atom parameter terms (ops.SWTerm and its kin): the energy
-    through ops.TermEnergyFn, the analytic-adjoint protocol (md._EOM.rhs_vjp, Stack.force / force_vjp) and the persistent
-    scratch of a two-pass kernel, all expressed through `_term(xyz)`, the ops.*Term on the current list, parameters and
-    scratch.  A module adds its parameters (`_thetas`), their device mirror, `_torch_energy` and its presets."""
+class _KernelTerm:
+    """Mixin of a term whose kernels sit behind an ops.*Term with an `_eval` (ops.SWTerm and its kin, ops._ChargeTerm):
+    the energy through ops.TermEnergyFn and the force of the analytic-adjoint protocol (md._EOM.rhs_vjp, Stack.force /
+    force_vjp), expressed through `_term(xyz)`, the ops.*Term on the current list or table and parameters, and `_thetas()`,
+    the parameters.  force_vjp differs in its parameter part and is written by the two families below."""
 
     accepts_into = True
     accepts_accum = True
     analytic = True
-    _work = None
-    _work_size = None            # ops.*_work_size of a kernel pair with a per-slot scratch
 
     def _term(self, xyz):
         raise NotImplementedError
-
-    def _scratch(self):
-        """The scratch of the bond pass, four floats per slot of the current list: persistent, so that a captured graph
-        sees a fixed address (under static topology max_nbr is fixed); re-allocated when a rebuild made the list wider."""
-        need = self._work_size(self._ell)
-        if self._work is None or self._work.device != self._ell.col.device or self._work.numel() < need:
-            self._work = torch.empty(need, dtype=torch.float32, device=self._ell.col.device)
-        return self._work
 
     def forward(self, xyz):
         if self._hip_ok(xyz):
@@ -301,6 +296,23 @@ class _ManyBodyTerm(_ListTerm):
         o = self._term(xyz)._eval(xyz.detach(), energy=False, grad=True, into=None if into is None else (into, None), scale=-1.0)
         return o["grad"]
 
+
+class _ManyBodyTerm(_KernelTerm, _ListTerm):
+    """A many-body term on the ELL list whose kernels return per-atom parameter terms (ops.SWTerm and its kin): _KernelTerm
+    with the parameter part of force_vjp and the persistent scratch of a two-pass kernel.  A module adds its parameters
+    (`_thetas`), their device mirror, `_torch_energy` and its presets."""
+
+    _work = None
+    _work_size = None            # ops.*_work_size of a kernel pair with a per-slot scratch
+
+    def _scratch(self):
+        """The scratch of the bond pass, four floats per slot of the current list: persistent, so that a captured graph
+        sees a fixed address (under static topology max_nbr is fixed); re-allocated when a rebuild made the list wider."""
+        need = self._work_size(self._ell)
+        if self._work is None or self._work.device != self._ell.col.device or self._work.numel() < need:
+            self._work = torch.empty(need, dtype=torch.float32, device=self._ell.col.device)
+        return self._work
+
     def force_vjp(self, xyz, w, want_theta=True, accum=None, into=None):
         """(F, d(w.F)/dx, [d(w.F)/dtheta for every trainable parameter of `_thetas`, shaped like it]) in one call plus the
         fixed-order reduction of the parameter part; `accum` (ops.ThetaAccum): that part is added into its flat buffer
@@ -309,6 +321,29 @@ class _ManyBodyTerm(_ListTerm):
         need = bool(want_theta) and any(isinstance(p, torch.nn.Parameter) for p in self._thetas())
         o = self._term(xyz)._eval(xyz.detach(), w=w.detach(), energy=False, grad=True, into=into, scale=-1.0, want_theta=need)
         return o["grad"], o["hw"], _theta_flat_tail(o["pthw"], self._thetas(), want_theta, accum)
+
+
+class _ChargeTerm(_KernelTerm):
+    """Mixin of a point-charge term (ops._ChargeTerm): _KernelTerm with the charges as the one parameter, their per-atom
+    device buffer `_q_atom()` and the charge part of force_vjp, scaled by what the term's kernel leaves out
+    (ops._ChargeTerm.pot_scale)."""
+
+    def _thetas(self):
+        return (self.charges,)
+
+    def prepare_pass(self):
+        if self._hip_ok():
+            self._q_atom()
+
+    def force_vjp(self, xyz, w, want_theta=True, accum=None, into=None):
+        """(F, d(w.F)/dx, [d(w.F)/dcharges]) in one evaluation plus the fixed-order reduction of the charge part; `accum`
+        (ops.ThetaAccum): that part is added into its flat buffer instead (None returned).  `into` = (F, dq) buffers of
+        another Stack member: this term's force and d(w.F)/dx are added onto them in the same launch."""
+        need = bool(want_theta) and isinstance(self.charges, torch.nn.Parameter)
+        term = self._term(xyz)
+        o = term._eval(xyz.detach(), w=w.detach(), energy=False, grad=True, into=into, scale=-1.0, want_pot=need)
+        gw = term.charge_grad(o["potw"]) if need else None
+        return o["grad"], o["hw"], _param_tail(gw, self.charges, -term.pot_scale, want_theta, accum)
 
 
 class _LazyTopology:
@@ -816,11 +851,6 @@ class DihedralPotentials(_StaticTerm, torch.nn.Module):
     def table(self):
         return self._table
 
-    def _hip_ok(self, xyz=None):
-        if xyz is not None and (not xyz.is_cuda or xyz.dtype != torch.float32):
-            return False
-        return self.analytic
-
     def _torch_energy(self, xyz):
         """The same energy in torch ops, in the dtype and on the device of xyz (differentiable by autograd in xyz and coeffs)."""
         top = self.top.to(xyz.device)
@@ -861,7 +891,7 @@ class DihedralPotentials(_StaticTerm, torch.nn.Module):
         return o["grad"], o["hw"], _param_tail(gw, self.coeffs, -1.0, want_theta, accum)
 
 
-class CoulombPotentials(_ListTerm):
+class CoulombPotentials(_ChargeTerm, _ListTerm):
     """Point-charge electrostatics as a damped shifted-force real-space sum (Wolf et al. 1999; Fennell and Gezelter 2006):
     pairwise, O(N), no reciprocal part, energy and force continuous at the cutoff.  The working counterpart of the
     reference's Electrostatics (torchmd/interface.py:303-361), which overwrites q1 (so it multiplies q_j * q_j) and carries a
@@ -897,10 +927,6 @@ class CoulombPotentials(_ListTerm):
     d(w.F)/dcharges comes from the same launch plus a fixed-order reduction.  float64 or host positions take the torch
     restatement `_torch_energy`."""
 
-    accepts_into = True
-    accepts_accum = True
-    analytic = True
-
     def __init__(self, system, charges, cutoff, alpha=0.0, shift="force", types=None, index_tuple=None, ex_pairs=None,
                  conversion=units.ke, self_energy=True, trainable=False):
         super().__init__(system)
@@ -933,7 +959,7 @@ class CoulombPotentials(_ListTerm):
         self._mask = ops.build_mask(n, index_tuple, ex_pairs, system.device)
         self._n_rep = system.get_number_of_atoms() // n
         self._ell = None
-        self._q_mirror = _DeviceMirror(self._charges, self._pack_charges, numel=self._n_rep * n)
+        self._q_mirror = _DeviceMirror(self._thetas, self._pack_charges, numel=self._n_rep * n)
         if torch.device(self.device).type == "cuda":
             self._reset_topology(torch.Tensor(system.get_positions()).to(system.device))
 
@@ -943,9 +969,6 @@ class CoulombPotentials(_ListTerm):
         q = charges if self.types is None else charges[self.types.to(charges.device)]
         return q.repeat(self._n_rep) if self._n_rep > 1 else q
 
-    def _charges(self):
-        return (self.charges,)
-
     def _pack_charges(self, ps, out=None):
         q = self._expand(ps[0].detach())
         return q.contiguous() if out is None else out.copy_(q)
@@ -954,11 +977,7 @@ class CoulombPotentials(_ListTerm):
         """charges[types] tiled over the replicas: the device mirror of the charges (_DeviceMirror)."""
         return self._q_mirror.get()
 
-    def prepare_pass(self):
-        if self._hip_ok():
-            self._q_atom()
-
-    def _term(self):
+    def _term(self, xyz=None):
         return ops.CoulombTerm(self._ell, self._consts, self._q_atom(), self._slot, self.n_slots)
 
     # -- energy ----------------------------------------------------------------------------------------------------
@@ -987,32 +1006,6 @@ class CoulombPotentials(_ListTerm):
         q = self._expand(self.charges.to(xyz))
         pair = torch.where(inside, q[i] * q[j] * psi, torch.zeros_like(psi)).sum()
         return k.conversion * (pair - k.self_s * q.pow(2).sum())
-
-    def forward(self, xyz):
-        if self._hip_ok(xyz):
-            return ops.TermEnergyFn.apply(xyz.contiguous(), self._term(), self.charges)
-        return self._torch_energy(xyz)
-
-    # -- analytic-adjoint protocol (md._EOM.rhs_vjp, Stack.force / force_vjp) -------------------------------------
-    def supports_force_vjp(self):
-        return self._hip_ok()
-
-    def force(self, xyz, into=None):
-        """F = -dU/dx in one kernel launch; `into` (a force buffer of another Stack member): added onto it in the same
-        launch and returned."""
-        o = ops.coulomb_eval(self._ell, xyz.detach(), self._q_atom(), self._consts, energy=False, grad=True,
-                             into=None if into is None else (into, None), scale=-1.0)
-        return o["grad"]
-
-    def force_vjp(self, xyz, w, want_theta=True, accum=None, into=None):
-        """(F, d(w.F)/dx, [d(w.F)/dcharges]) in one launch plus the fixed-order reduction of the charge part; `accum`
-        (ops.ThetaAccum): that part is added into its flat buffer instead (None returned).  `into` = (F, dq) buffers of
-        another Stack member: this term's force and d(w.F)/dx are added onto them in the same launch."""
-        need = bool(want_theta) and isinstance(self.charges, torch.nn.Parameter)
-        o = ops.coulomb_eval(self._ell, xyz.detach(), self._q_atom(), self._consts, w=w.detach(), energy=False, grad=True,
-                             into=into, scale=-1.0, want_pot=need)
-        gw = ops.coulomb_charge_grad(o["potw"], self._slot, self.n_slots) if need else None
-        return o["grad"], o["hw"], _param_tail(gw, self.charges, -self.conversion, want_theta, accum)
 
 
 class StillingerWeber(_ManyBodyTerm):
@@ -1667,7 +1660,58 @@ class TersoffMulti(_ManyBodyTerm):
         return ops.TersoffMultiTerm(self._ell, self.types, self.n_species, self._tables(), self._scratch())
 
 
-class EwaldReciprocal(_StaticTerm, torch.nn.Module):
+class _EwaldMember(_ChargeTerm, _StaticTerm, torch.nn.Module):
+    """Common part of EwaldReciprocal / EwaldExclusions, the members of an Ewald sum built on its real-space term `real`:
+    what they refuse of it, the fields they adopt from it -- alpha, conversion, types, the charge slots, the replica layout
+    and the `charges` tensor itself (the same Parameter object when trainable) --, the lengths of the diagonal cell, and the
+    static table their kernels read.  `name` is the class name the messages carry; `why` = what a shifted, an undamped and
+    a self-energy-free `real` would do to this member."""
+
+    def __init__(self, system, real, name, why):
+        super().__init__()
+        if not isinstance(real, CoulombPotentials):
+            raise ValueError("%s: `real` must be the CoulombPotentials carrying the real-space sum, got %s"
+                             % (name, type(real).__name__))
+        if real.shift != "none":
+            raise ValueError("%s: the real-space term has shift=%r; the Ewald real-space sum is the plain "
+                             "erfc(alpha r) / r (shift=\"none\")%s" % (name, real.shift, why[0]))
+        if real.alpha == 0.0:
+            raise ValueError("%s: the real-space term has alpha = 0 (the bare Coulomb sum): there is no splitting "
+                             "and %s" % (name, why[1]))
+        if not real.self_energy:
+            raise ValueError("%s: the real-space term has self_energy=False; %s" % (name, why[2]))
+        if getattr(system, "dim", 3) != 3:
+            raise ValueError("%s: system.dim = %r; the sum is over a three-dimensional lattice" % (name, system.dim))
+        full = torch.Tensor(system.get_cell())
+        if full.dim() == 2 and bool((full - torch.diag(torch.diag(full)) != 0).any()):
+            raise ValueError("%s: the cell must be diagonal (triclinic cells are not supported)" % name)
+        self.system = system
+        self.device = system.device
+        self.cell = (full.diag() if full.dim() == 2 else full).to(self.device)
+        self._real = (real,)                                     # (a tuple: not registered as a sub-module a second time)
+        self.alpha, self.conversion, self.types = real.alpha, real.conversion, real.types
+        if isinstance(real.charges, torch.nn.Parameter):
+            self.charges = real.charges
+        else:
+            self.register_buffer("charges", real.charges)
+        self._slot, self.n_slots = real._slot, real.n_slots
+        self._group, self._n_rep = real._group, real._n_rep
+        self._lengths = self.cell.detach().cpu().to(torch.float64).numpy()    # the float32 lengths the kernels see
+
+    def table(self):
+        return self._table
+
+    def _hip_ok(self, xyz=None):
+        return super()._hip_ok(xyz) and torch.device(self.device).type == "cuda"
+
+    def _q_atom(self):
+        return self._real[0]._q_atom()
+
+    def _term(self, xyz=None):
+        return self._ops_term(self._table, self._q_atom(), self._slot, self.n_slots)
+
+
+class EwaldReciprocal(_EwaldMember):
     """The reciprocal-space part of the Ewald sum for the point charges of a CoulombPotentials (no counterpart in the
     reference).  With `real` = CoulombPotentials(system, charges, cutoff, alpha, shift="none", self_energy=True) the two
     terms together are the energy of the periodic system, independent of alpha up to the truncation of both sums:
@@ -1694,24 +1738,12 @@ class EwaldReciprocal(_StaticTerm, torch.nn.Module):
     force / force_vjp serve the analytic adjoint and HIP-graph replay like CoulombPotentials'.  float64 or host positions
     take the torch restatement `_torch_energy`.  A Stack holding the term stays off the fused trajectory kernels."""
 
-    accepts_into = True
-    accepts_accum = True
-    analytic = True
+    _ops_term = ops.EwaldTerm
 
     def __init__(self, system, real, k_cutoff=None, accuracy=1e-5, exclusions=None):
-        super().__init__()
-        if not isinstance(real, CoulombPotentials):
-            raise ValueError("EwaldReciprocal: `real` must be the CoulombPotentials carrying the real-space sum, got %s"
-                             % type(real).__name__)
-        if real.shift != "none":
-            raise ValueError("EwaldReciprocal: the real-space term has shift=%r; the Ewald real-space sum is the plain "
-                             "erfc(alpha r) / r (shift=\"none\"), a shifted one would be counted wrongly" % (real.shift,))
-        if real.alpha == 0.0:
-            raise ValueError("EwaldReciprocal: the real-space term has alpha = 0 (the bare Coulomb sum): there is no splitting "
-                             "and c(k) is undefined")
-        if not real.self_energy:
-            raise ValueError("EwaldReciprocal: the real-space term has self_energy=False; the self term -alpha/sqrt(pi) sum "
-                             "q_i^2 of the Ewald sum would be missing")
+        super().__init__(system, real, "EwaldReciprocal",
+                         (", a shifted one would be counted wrongly", "c(k) is undefined",
+                          "the self term -alpha/sqrt(pi) sum q_i^2 of the Ewald sum would be missing"))
         if exclusions is not None and (not isinstance(exclusions, EwaldExclusions) or exclusions._real[0] is not real):
             raise ValueError("EwaldReciprocal: `exclusions` must be the EwaldExclusions built on the same real-space term")
         if real.index_tuple is not None or (real.ex_pairs is not None and exclusions is None):
@@ -1719,48 +1751,13 @@ class EwaldReciprocal(_StaticTerm, torch.nn.Module):
                              "excluded pairs from the reciprocal sum is not implemented for index_tuple, and for ex_pairs it is "
                              "a term of its own: pass exclusions=EwaldExclusions(system, real), or build the three members "
                              "with ewald(..., ex_pairs=)")
-        if getattr(system, "dim", 3) != 3:
-            raise ValueError("EwaldReciprocal: system.dim = %r; the sum is over a three-dimensional lattice" % (system.dim,))
-        full = torch.Tensor(system.get_cell())
-        if full.dim() == 2 and bool((full - torch.diag(torch.diag(full)) != 0).any()):
-            raise ValueError("EwaldReciprocal: the cell must be diagonal (triclinic cells are not supported)")
         if not 0.0 < float(accuracy) < 1.0:
             raise ValueError("EwaldReciprocal: accuracy must lie in (0, 1), got %r" % (accuracy,))
-        self.system = system
-        self.device = system.device
-        self.cell = (full.diag() if full.dim() == 2 else full).to(self.device)
-        self._real = (real,)                                     # (a tuple: not registered as a sub-module a second time)
-        self.alpha, self.conversion, self.types = real.alpha, real.conversion, real.types
         self.accuracy = float(accuracy)
         self.k_cutoff = float(k_cutoff) if k_cutoff is not None else 2.0 * self.alpha * math.sqrt(-math.log(self.accuracy))
-        if isinstance(real.charges, torch.nn.Parameter):
-            self.charges = real.charges
-        else:
-            self.register_buffer("charges", real.charges)
-        self._slot, self.n_slots = real._slot, real.n_slots
-        self._group, self._n_rep = real._group, real._n_rep
-        lengths = self.cell.detach().cpu().to(torch.float64).numpy()          # the float32 lengths the kernels see
-        self._table = ops.EwaldTable(_lib.make_cell(system.get_cell()), lengths, self.alpha, self.k_cutoff, self.conversion,
-                                     self._n_rep, self._group, self.device)
+        self._table = ops.EwaldTable(_lib.make_cell(system.get_cell()), self._lengths, self.alpha, self.k_cutoff,
+                                     self.conversion, self._n_rep, self._group, self.device)
         self.n_vectors = self._table.n_vecs
-
-    def table(self):
-        return self._table
-
-    def _hip_ok(self, xyz=None):
-        if xyz is not None and (not xyz.is_cuda or xyz.dtype != torch.float32):
-            return False
-        return self.analytic and torch.device(self.device).type == "cuda"
-
-    def _q_atom(self):
-        return self._real[0]._q_atom()
-
-    def prepare_pass(self):
-        if self._hip_ok():
-            self._q_atom()
-
-    def _term(self):
-        return ops.EwaldTerm(self._table, self._q_atom(), self._slot, self.n_slots)
 
     def _torch_energy(self, xyz):
         """The same energy in torch ops, in the dtype and on the device of xyz (differentiable by autograd in xyz and
@@ -1775,33 +1772,8 @@ class EwaldReciprocal(_StaticTerm, torch.nn.Module):
         Q = q.reshape(t.n_rep, t.n_atoms).sum(1)
         return self.conversion * ((cf * (A * A + B * B)).sum() - math.pi * Q.pow(2).sum() / (2.0 * t.volume * t.alpha ** 2))
 
-    def forward(self, xyz):
-        if self._hip_ok(xyz):
-            return ops.TermEnergyFn.apply(xyz.contiguous(), self._term(), self.charges)
-        return self._torch_energy(xyz)
 
-    # -- analytic-adjoint protocol (md._EOM.rhs_vjp, Stack.force / force_vjp) -------------------------------------
-    def supports_force_vjp(self):
-        return self._hip_ok()
-
-    def force(self, xyz, into=None):
-        """F = -dU/dx; `into` (a force buffer of another Stack member): added onto it in the same launch and returned."""
-        o = ops.ewald_eval(self._table, xyz.detach(), self._q_atom(), energy=False, grad=True,
-                           into=None if into is None else (into, None), scale=-1.0)
-        return o["grad"]
-
-    def force_vjp(self, xyz, w, want_theta=True, accum=None, into=None):
-        """(F, d(w.F)/dx, [d(w.F)/dcharges]) in one evaluation plus the fixed-order reduction of the charge part; `accum`
-        (ops.ThetaAccum): that part is added into its flat buffer instead (None returned).  `into` = (F, dq) buffers of
-        another Stack member: this term's force and d(w.F)/dx are added onto them in the same launch."""
-        need = bool(want_theta) and isinstance(self.charges, torch.nn.Parameter)
-        o = ops.ewald_eval(self._table, xyz.detach(), self._q_atom(), w=w.detach(), energy=False, grad=True, into=into,
-                           scale=-1.0, want_pot=need)
-        gw = ops.coulomb_charge_grad(o["potw"], self._slot, self.n_slots) if need else None
-        return o["grad"], o["hw"], _param_tail(gw, self.charges, -1.0, want_theta, accum)
-
-
-class EwaldExclusions(_StaticTerm, torch.nn.Module):
+class EwaldExclusions(_EwaldMember):
     """The third member of the Ewald sum for molecules: the erf correction for the excluded and scaled pairs of a
     CoulombPotentials (no counterpart in the reference).  The real-space term honours `ex_pairs` through its mask; the
     reciprocal sum runs over all charges and cannot leave a pair out.  With `real` = CoulombPotentials(system, charges, cutoff,
@@ -1836,69 +1808,21 @@ class EwaldExclusions(_StaticTerm, torch.nn.Module):
     positions take the torch restatement `_torch_energy`.  A Stack holding the term stays off the fused trajectory
     kernels."""
 
-    accepts_into = True
-    accepts_accum = True
-    analytic = True
+    _ops_term = ops.EwaldExclTerm
 
     def __init__(self, system, real, scale=None):
-        super().__init__()
-        if not isinstance(real, CoulombPotentials):
-            raise ValueError("EwaldExclusions: `real` must be the CoulombPotentials carrying the real-space sum, got %s"
-                             % type(real).__name__)
+        super().__init__(system, real, "EwaldExclusions",
+                         ("", "nothing to correct", "it is not the real-space member of an Ewald sum"))
         if real.ex_pairs is None:
             raise ValueError("EwaldExclusions: the real-space term has no ex_pairs: there is nothing to correct")
         if real.index_tuple is not None:
             raise ValueError("EwaldExclusions: the real-space term has index_tuple; the Ewald sum runs over all charges")
-        if real.shift != "none":
-            raise ValueError("EwaldExclusions: the real-space term has shift=%r; the Ewald real-space sum is the plain "
-                             "erfc(alpha r) / r (shift=\"none\")" % (real.shift,))
-        if real.alpha == 0.0:
-            raise ValueError("EwaldExclusions: the real-space term has alpha = 0 (the bare Coulomb sum): there is no splitting "
-                             "and nothing to correct")
-        if not real.self_energy:
-            raise ValueError("EwaldExclusions: the real-space term has self_energy=False; it is not the real-space member of "
-                             "an Ewald sum")
-        if getattr(system, "dim", 3) != 3:
-            raise ValueError("EwaldExclusions: system.dim = %r; the sum is over a three-dimensional lattice" % (system.dim,))
-        full = torch.Tensor(system.get_cell())
-        if full.dim() == 2 and bool((full - torch.diag(torch.diag(full)) != 0).any()):
-            raise ValueError("EwaldExclusions: the cell must be diagonal (triclinic cells are not supported)")
-        self.system = system
-        self.device = system.device
-        self.cell = (full.diag() if full.dim() == 2 else full).to(self.device)
-        self._real = (real,)                                     # (a tuple: not registered as a sub-module a second time)
-        self.alpha, self.conversion, self.types = real.alpha, real.conversion, real.types
-        if isinstance(real.charges, torch.nn.Parameter):
-            self.charges = real.charges
-        else:
-            self.register_buffer("charges", real.charges)
-        self._slot, self.n_slots = real._slot, real.n_slots
-        self._group, self._n_rep = real._group, real._n_rep
-        lengths = self.cell.detach().cpu().to(torch.float64).numpy()          # the float32 lengths the kernel sees
         try:
-            self._table = ops.EwaldExclTable(real.ex_pairs, scale, self._group, self._n_rep, lengths, self.alpha,
+            self._table = ops.EwaldExclTable(real.ex_pairs, scale, self._group, self._n_rep, self._lengths, self.alpha,
                                              self.conversion, self.device)
         except ValueError as e:
             raise ValueError("EwaldExclusions: " + str(e).replace("mdgrad_amd: ", "")) from None
         self.pairs, self.scale = self._table.pairs, self._table.scale
-
-    def table(self):
-        return self._table
-
-    def _hip_ok(self, xyz=None):
-        if xyz is not None and (not xyz.is_cuda or xyz.dtype != torch.float32):
-            return False
-        return self.analytic and torch.device(self.device).type == "cuda"
-
-    def _q_atom(self):
-        return self._real[0]._q_atom()
-
-    def prepare_pass(self):
-        if self._hip_ok():
-            self._q_atom()
-
-    def _term(self):
-        return ops.EwaldExclTerm(self._table, self._q_atom(), self._slot, self.n_slots)
 
     def _torch_energy(self, xyz):
         """The same energy in torch ops, in the dtype and on the device of xyz (differentiable by autograd in xyz and
@@ -1918,32 +1842,6 @@ class EwaldExclusions(_StaticTerm, torch.nn.Module):
         chi = torch.where(apart, (s - torch.erf(t.alpha * r)) / r, torch.full_like(r, -g0))
         q = self._real[0]._expand(self.charges.to(xyz))
         return self.conversion * (q[i] * q[j] * chi).sum()
-
-    def forward(self, xyz):
-        if self._hip_ok(xyz):
-            return ops.TermEnergyFn.apply(xyz.contiguous(), self._term(), self.charges)
-        return self._torch_energy(xyz)
-
-    # -- analytic-adjoint protocol (md._EOM.rhs_vjp, Stack.force / force_vjp) -------------------------------------
-    def supports_force_vjp(self):
-        return self._hip_ok()
-
-    def force(self, xyz, into=None):
-        """F = -dU/dx in one launch; `into` (a force buffer of another Stack member): added onto it in the same launch and
-        returned."""
-        o = ops.ewald_excl_eval(self._table, xyz.detach(), self._q_atom(), energy=False, grad=True,
-                                into=None if into is None else (into, None), scale=-1.0)
-        return o["grad"]
-
-    def force_vjp(self, xyz, w, want_theta=True, accum=None, into=None):
-        """(F, d(w.F)/dx, [d(w.F)/dcharges]) in one launch plus the fixed-order reduction of the charge part; `accum`
-        (ops.ThetaAccum): that part is added into its flat buffer instead (None returned).  `into` = (F, dq) buffers of
-        another Stack member: this term's force and d(w.F)/dx are added onto them in the same launch."""
-        need = bool(want_theta) and isinstance(self.charges, torch.nn.Parameter)
-        o = ops.ewald_excl_eval(self._table, xyz.detach(), self._q_atom(), w=w.detach(), energy=False, grad=True, into=into,
-                                scale=-1.0, want_pot=need)
-        gw = ops.coulomb_charge_grad(o["potw"], self._slot, self.n_slots) if need else None
-        return o["grad"], o["hw"], _param_tail(gw, self.charges, -self.conversion, want_theta, accum)
 
 
 def ewald(system, charges, cutoff, accuracy=1e-5, k_cutoff=None, ex_pairs=None, scale=None, **kw):

@@ -12,9 +12,9 @@ torch.autograd.Function wrappers that own the differentiation contract
     TermEnergyFn -> TermGradFn                                  every other term with parameters, order <= 2 in x, 1 in the
                                                                 parameters; what differs per kernel family is a small `term` object:
       DihedralTerm                                              torsion term, parameters: its coefficients
-      CoulombTerm                                               damped shifted-force Coulomb sum, parameters: the charges
-      EwaldTerm                                                 Ewald reciprocal-space sum, parameters: the charges
-      EwaldExclTerm                                             Ewald erf correction of excluded / scaled pairs, the same
+      CoulombTerm, EwaldTerm, EwaldExclTerm                     the point-charge terms (damped shifted-force sum, Ewald reciprocal
+                                                                sum, erf correction of excluded pairs) on _ChargeTerm, parameters:
+                                                                the charges; `pot_scale` says which factor their kernel leaves out
       SWTerm                                                    Stillinger-Weber term, parameters: (epsilon, sigma, lam)
       EAMTerm                                                   Sutton-Chen term, parameters: (epsilon, a, c)
       TersoffTerm                                               Tersoff bond-order term, parameters: (A, B, h)
@@ -685,24 +685,62 @@ def coulomb_charge_grad(pot, slot, n_slots):
     return out
 
 
-class CoulombTerm:
-    """The damped shifted-force Coulomb sum (csrc/coulomb.hip) for TermEnergyFn: the list, the constants, the per-atom charge
-    buffer (charges[types] tiled over the replicas, kept current by CoulombPotentials) and the charge slots."""
+class _ChargeTerm:
+    """A point-charge term for TermEnergyFn: the per-atom charge buffer `q_atom` (charges[types] tiled over the replicas, kept
+    current by CoulombPotentials) and the charge slots, around the term's one evaluation `_eval(xyz, **kw)` -- called like
+    SWTerm._eval, returning the dict of coulomb_eval.  `pot_scale` is the factor that `pot` / `potw` of the term's kernel still
+    owe (docs/KERNELS.md, "What the charge kernels' outputs carry"): the conversion where the kernel leaves it out, 1.0
+    where its table holds it.  Nowhere else is that written.  What is a term's own -- a self term, a background term --
+    it adds in `_own`."""
+
+    pot_scale = 1.0
+
+    def __init__(self, q_atom, slot, n_slots):
+        self.q_atom, self.slot, self.n_slots = q_atom, slot, int(n_slots)
+
+    def _eval(self, xyz, **kw):
+        raise NotImplementedError
+
+    def charge_grad(self, per_atom):
+        """coulomb_charge_grad over the term's slots: nothing is scaled (force_vjp hands -pot_scale to its reduction)."""
+        return coulomb_charge_grad(per_atom, self.slot, self.n_slots)
+
+    def charge_grad_w(self, potw):
+        """The per-atom `potw` (or `pot`) of `_eval` -> the [n_slots] charge gradient: reduced first, then times the owed
+        scale (no multiplication where nothing is owed)."""
+        gw = self.charge_grad(potw)
+        return gw if self.pot_scale == 1.0 else gw * self.pot_scale
+
+    def _own(self, e, pot):
+        """(U, dU/dcharges [n_slots]) from the kernel's energy (None when not asked for) and per-atom `pot`."""
+        return e, self.charge_grad_w(pot)
+
+    def first_order(self, xyz, energy):
+        o = self._eval(xyz, energy=energy, grad=True, want_pot=True)
+        e, gq = self._own(o["energy"], o["pot"])
+        return e, o["grad"], gq
+
+    def second_order(self, xyz, w):
+        o = self._eval(xyz, w=w, energy=False, grad=False, want_pot=True)
+        return o["hw"], self.charge_grad_w(o["potw"])
+
+
+class CoulombTerm(_ChargeTerm):
+    """The damped shifted-force Coulomb sum (csrc/coulomb.hip): the list and the constants beside what _ChargeTerm holds."""
 
     noun = "dU/dcharges of the Coulomb term"
 
     def __init__(self, ell, consts, q_atom, slot, n_slots):
-        self.ell, self.consts, self.q_atom, self.slot, self.n_slots = ell, consts, q_atom, slot, int(n_slots)
+        super().__init__(q_atom, slot, n_slots)
+        self.ell, self.consts, self.pot_scale = ell, consts, float(consts.conversion)
 
-    def first_order(self, xyz, energy):
-        o = coulomb_eval(self.ell, xyz, self.q_atom, self.consts, energy=energy, grad=True, want_pot=True)
-        k = self.consts
-        dq_atom = float(k.conversion) * (o["pot"] - (2.0 * float(k.self_s)) * self.q_atom)         # dU/dq_i
-        return o["energy"], o["grad"], coulomb_charge_grad(dq_atom, self.slot, self.n_slots)
+    def _eval(self, xyz, **kw):
+        return coulomb_eval(self.ell, xyz, self.q_atom, self.consts, **kw)
 
-    def second_order(self, xyz, w):
-        o = coulomb_eval(self.ell, xyz, self.q_atom, self.consts, w=w, energy=False, grad=False, want_pot=True)
-        return o["hw"], coulomb_charge_grad(o["potw"], self.slot, self.n_slots) * float(self.consts.conversion)
+    def _own(self, e, pot):
+        """The self term -(2 self_s) q_i stands inside the conversion, which is applied per atom, before the reduction."""
+        dq_atom = self.pot_scale * (pot - (2.0 * float(self.consts.self_s)) * self.q_atom)           # dU/dq_i
+        return e, self.charge_grad(dq_atom)
 
 
 # ----------------------------------------------------------------------------- Stillinger-Weber term (K23)
@@ -1083,26 +1121,26 @@ def ewald_eval(table, xyz, q_atom, w=None, energy=True, grad=True, into=None, sc
     return dict(energy=e, grad=g, hw=hw, pot=pot, potw=potw)
 
 
-class EwaldTerm:
-    """The Ewald reciprocal sum with its neutralising background (csrc/ewald.hip) for TermEnergyFn: the table, the per-atom
-    charge buffer and the charge slots (those of the real-space CoulombPotentials the term belongs to)."""
+class EwaldTerm(_ChargeTerm):
+    """The Ewald reciprocal sum with its neutralising background (csrc/ewald.hip): the table beside what _ChargeTerm holds (the
+    charge slots are those of the real-space CoulombPotentials the term belongs to).  Nothing is owed: the table's `coef`
+    and `background` hold the conversion."""
 
     noun = "dU/dcharges of the Ewald reciprocal term"
 
     def __init__(self, table, q_atom, slot, n_slots):
-        self.table, self.q_atom, self.slot, self.n_slots = table, q_atom, slot, int(n_slots)
+        super().__init__(q_atom, slot, n_slots)
+        self.table = table
 
-    def first_order(self, xyz, energy):
+    def _eval(self, xyz, **kw):
+        return ewald_eval(self.table, xyz, self.q_atom, **kw)
+
+    def _own(self, e, pot):
+        """The background term, in the energy and in dU/dq_i."""
         t = self.table
-        o = ewald_eval(t, xyz, self.q_atom, energy=energy, grad=True, want_pot=True)
         Q = self.q_atom.reshape(t.n_rep, t.n_atoms).sum(1)                                   # net charge of every replica
-        dq_atom = o["pot"] - t.background * Q.repeat_interleave(t.n_atoms)                   # dU/dq_i
-        e = o["energy"] - (0.5 * t.background) * Q.pow(2).sum() if energy else None
-        return e, o["grad"], coulomb_charge_grad(dq_atom, self.slot, self.n_slots)
-
-    def second_order(self, xyz, w):
-        o = ewald_eval(self.table, xyz, self.q_atom, w=w, energy=False, grad=False, want_pot=True)
-        return o["hw"], coulomb_charge_grad(o["potw"], self.slot, self.n_slots)
+        dq_atom = pot - t.background * Q.repeat_interleave(t.n_atoms)                        # dU/dq_i
+        return None if e is None else e - (0.5 * t.background) * Q.pow(2).sum(), self.charge_grad_w(dq_atom)
 
 
 # ----------------------------------------------------------------------------- Ewald correction for excluded pairs (K22)
@@ -1187,20 +1225,18 @@ def ewald_excl_eval(table, xyz, q_atom, w=None, energy=True, grad=True, into=Non
     return dict(energy=e, grad=g, hw=hw, pot=pot, potw=potw)
 
 
-class EwaldExclTerm(EwaldTerm):
-    """The erf correction of excluded / scaled pairs (csrc/ewald_excl.hip) for TermEnergyFn; holds what EwaldTerm holds, with
-    an EwaldExclTable."""
+class EwaldExclTerm(_ChargeTerm):
+    """The erf correction of excluded / scaled pairs (csrc/ewald_excl.hip): an EwaldExclTable beside what _ChargeTerm holds.
+    No self term, no background term: dU/dq_i = conversion pot_i."""
 
     noun = "dU/dcharges of the Ewald exclusion term"
 
-    def first_order(self, xyz, energy):
-        o = ewald_excl_eval(self.table, xyz, self.q_atom, energy=energy, grad=True, want_pot=True)
-        gq = coulomb_charge_grad(o["pot"], self.slot, self.n_slots) * self.table.conversion            # dU/dq_i = conversion pot_i
-        return o["energy"], o["grad"], gq
+    def __init__(self, table, q_atom, slot, n_slots):
+        super().__init__(q_atom, slot, n_slots)
+        self.table, self.pot_scale = table, table.conversion
 
-    def second_order(self, xyz, w):
-        o = ewald_excl_eval(self.table, xyz, self.q_atom, w=w, energy=False, grad=False, want_pot=True)
-        return o["hw"], coulomb_charge_grad(o["potw"], self.slot, self.n_slots) * self.table.conversion
+    def _eval(self, xyz, **kw):
+        return ewald_excl_eval(self.table, xyz, self.q_atom, **kw)
 
 
 # ----------------------------------------------------------------------------- fused trajectories

@@ -181,8 +181,14 @@ __device__ __forceinline__ void ring_pair(const RingLJ& K, const RingRdf& X, con
         const int gA = (int)t.x, gB = (int)t.y;
         const f32x2 fr = {__builtin_amdgcn_fractf(t.x), __builtin_amdgcn_fractf(t.y)};
         const float4 ca = X.tab[gA], cb = X.tab[gB];
-        const f32x2 cw = {fmaf(fr.x, fmaf(fr.x, fmaf(fr.x, ca.w, ca.z), ca.y), ca.x),
-                          fmaf(fr.y, fmaf(fr.y, fmaf(fr.y, cb.w, cb.z), cb.y), cb.x)};
+        // The two cubics are six scalar fmas on the registers the two ds_read_b128 land in.  Left to itself the SLP vectoriser
+        // pairs the chains into three v_pk_fma_f32 and interleaves the two register quads with six v_mov_b32 to feed them: twice
+        // the cycles of the scalar form (tools/micro/valu_rate.hip).  The empty asm on one chain's result is a register
+        // barrier that costs no instruction: the chains no longer end in one vector the vectoriser can start from.
+        float cwa = fmaf(fr.x, fmaf(fr.x, fmaf(fr.x, ca.w, ca.z), ca.y), ca.x);
+        const float cwb = fmaf(fr.y, fmaf(fr.y, fmaf(fr.y, cb.w, cb.z), cb.y), cb.x);
+        asm("" : "+v"(cwa));
+        const f32x2 cw = {cwa, cwb};
         ri.x = __builtin_elementwise_fma(-cw, dx, ri.x); ri.y = __builtin_elementwise_fma(-cw, dy, ri.y);
         ri.z = __builtin_elementwise_fma(-cw, dz, ri.z);
         if constexpr (JSIDE) {
@@ -350,6 +356,17 @@ __device__ __forceinline__ RingMask ring_mask_load(const uint8_t* __restrict__ m
     return M;
 }
 
+// The visitors of ring step k: entry (lane - k) mod nl of each of the six rows.  A lane passes entry 0 once, at step lane + 1, so
+// the entry is the lane's own less k, and nl further up from then on: one compare (of the lane with the scalar k), one select
+// between two loop-invariant addresses and one subtraction of the scalar 8 k give the byte address of the first row; the other
+// rows are DS offset fields of the same register (64 entries = 512 bytes apart).
+struct RingVisitor {
+    const f32x2 *lo, *hi;                                           // row 0: the lane's own entry, and nl entries above it
+    int lane;
+};
+__device__ __forceinline__ RingVisitor ring_visitor(const f32x2* lds, int nl, int lane) { return RingVisitor{lds + lane, lds + lane + nl, lane}; }
+__device__ __forceinline__ const f32x2* ring_visitor_at(const RingVisitor& V, int k) { return (k > V.lane ? V.hi : V.lo) - k; }
+
 // FULL (N even, no mask; chosen wave-uniformly by ring_force): every lane < nl owns two atoms and every lane >= nl owns none, so
 // all existence flags of a pair operation -- vi*, the visitors' vj*, the eight masks built from them per ring step and what
 // ring_pair ANDs onto them -- are the one loop-invariant predicate lane < nl.  It is applied once, as a branch around the steps:
@@ -389,19 +406,24 @@ __device__ __forceinline__ void ring_sweep(const RingLJ& K, const RingRdf& X, co
         ring_pair<LEVEL, IMAGE, true, false, RDF, KIND, SUMS>(K, X, q, w, q, w, vm, vm, v, RDF == 2 && v, fi, gi, fj, gj, D, ri, rj);
     }
     const int prev = lane < nl ? ((lane == 0 ? nl : lane) - 1) * 4 : lane * 4;     // bpermute address of lane l-1
-    int idx = lane;
+    const RingVisitor V = ring_visitor(lds, nl, lane);
+    // (the visitors' existence flags from the address: entry idx holds atoms 2 idx, 2 idx + 1, and 2 idx < N <=> idx < ceil(N/2),
+    //  2 idx + 1 < N <=> idx < floor(N/2))
+    const f32x2* const vend0 = lds + nl;
+    const f32x2* const vend1 = lds + (N >> 1);
     Vec3x2 qj, wj = vzero();
 #pragma unroll 1
     for (int k = 1; k <= nsteps; ++k) {
-        idx -= 1; idx = idx < 0 ? idx + nl : idx;
-        qj.x = sqx[idx]; qj.y = sqy[idx]; qj.z = sqz[idx];
+        const f32x2* const vp = ring_visitor_at(V, k);
+        qj.x = vp[0]; qj.y = vp[64]; qj.z = vp[128];
         if constexpr (ring_level_force(LEVEL)) fj = ring_move(fj, prev);
-        if constexpr (LEVEL >= 2) { wj.x = swx[idx]; wj.y = swy[idx]; wj.z = swz[idx]; gj = ring_move(gj, prev); }
+        if constexpr (LEVEL >= 2) { wj.x = vp[192]; wj.y = vp[256]; wj.z = vp[320]; gj = ring_move(gj, prev); }
         if constexpr (RDF == 2) rj = ring_move(rj, prev);
-        const bool vj0 = FULL || 2 * idx < N, vj1 = FULL || 2 * idx + 1 < N;
+        const bool vj0 = FULL || vp < vend0, vj1 = FULL || vp < vend1;
         const bool s0 = FULL || (vi0 && vj0), s1 = FULL || (vi1 && vj1), c0 = FULL || (vi0 && vj1), c1 = FULL || (vi1 && vj0);
         bool ms0 = s0, ms1 = s1, mc0 = c0, mc1 = c1;
         if constexpr (MASK) {
+            const int idx = (int)(vp - lds);
             const uint32_t b0 = ring_mask_word(M.w, idx >> 4) >> (2 * (idx & 15)), b1 = ring_mask_word(M.w + 4, idx >> 4) >> (2 * (idx & 15));
             ms0 = s0 && (b0 & 1u); mc0 = c0 && (b0 & 2u); mc1 = c1 && (b1 & 1u); ms1 = s1 && (b1 & 2u);
         }
@@ -411,13 +433,14 @@ __device__ __forceinline__ void ring_sweep(const RingLJ& K, const RingRdf& X, co
     if (!(nl & 1)) {
         // antipodal lanes (k = nl/2) see each other from both sides -> directed evaluation, visitors not updated
         // (the lower lane of the two feeds the histogram)
-        idx -= 1; idx = idx < 0 ? idx + nl : idx;
-        qj.x = sqx[idx]; qj.y = sqy[idx]; qj.z = sqz[idx];
-        if constexpr (LEVEL >= 2) { wj.x = swx[idx]; wj.y = swy[idx]; wj.z = swz[idx]; }
-        const bool vj0 = FULL || 2 * idx < N, vj1 = FULL || 2 * idx + 1 < N;
+        const f32x2* const vp = ring_visitor_at(V, nsteps + 1);
+        qj.x = vp[0]; qj.y = vp[64]; qj.z = vp[128];
+        if constexpr (LEVEL >= 2) { wj.x = vp[192]; wj.y = vp[256]; wj.z = vp[320]; }
+        const bool vj0 = FULL || vp < vend0, vj1 = FULL || vp < vend1;
         const bool s0 = FULL || (vi0 && vj0), s1 = FULL || (vi1 && vj1), c0 = FULL || (vi0 && vj1), c1 = FULL || (vi1 && vj0);
         bool ms0 = s0, ms1 = s1, mc0 = c0, mc1 = c1;
         if constexpr (MASK) {
+            const int idx = (int)(vp - lds);
             const uint32_t b0 = ring_mask_word(M.w, idx >> 4) >> (2 * (idx & 15)), b1 = ring_mask_word(M.w + 4, idx >> 4) >> (2 * (idx & 15));
             ms0 = s0 && (b0 & 1u); mc0 = c0 && (b0 & 2u); mc1 = c1 && (b1 & 1u); ms1 = s1 && (b1 & 2u);
         }
@@ -439,7 +462,7 @@ __device__ __forceinline__ void ring_sweep(const RingLJ& K, const RingRdf& X, co
             qj.x = ring_swap_if(up, qj.x); qj.y = ring_swap_if(up, qj.y); qj.z = ring_swap_if(up, qj.z);
             if constexpr (LEVEL >= 2) { wj.x = ring_swap_if(up, wj.x); wj.y = ring_swap_if(up, wj.y); wj.z = ring_swap_if(up, wj.z); }
             const bool a0 = FULL || (up ? c0 : s0), a1 = FULL || (up ? c1 : s1);
-            const int mate = (FULL || lane < nl) ? idx * 4 : lane * 4;     // (a lane without atoms keeps its own zeros)
+            const int mate = (FULL || lane < nl) ? (int)(vp - lds) * 4 : lane * 4;     // (a lane without atoms keeps its own zeros)
             Vec3x2 fa = vzero(), ga = vzero(), ra = vzero();
             ring_pair<LEVEL, IMAGE, false, true, RDF, KIND, SUMS>(K, X, q, w, qj, wj, a0, a1, a0, a1, fi, gi, fa, ga, S, ri, ra);
             if constexpr (ring_level_force(LEVEL)) {
@@ -612,15 +635,18 @@ __device__ __forceinline__ void ring_sweep_lj_multi(const RingLJ (&K)[NT], const
     }
     const int prev = lane < nl ? ((lane == 0 ? nl : lane) - 1) * 4 : lane * 4;
     const int nsteps = (nl - 1) >> 1;
-    int idx = lane;
+    const RingVisitor V = ring_visitor(lds, nl, lane);
+    const f32x2* const vend0 = lds + nl;                             // (the visitors' existence flags: see ring_sweep)
+    const f32x2* const vend1 = lds + (N >> 1);
     Vec3x2 qj, wj = vzero();
 #pragma unroll 1
     for (int k = 1; k <= nsteps; ++k) {
-        idx -= 1; idx = idx < 0 ? idx + nl : idx;
-        qj.x = sqx[idx]; qj.y = sqy[idx]; qj.z = sqz[idx];
+        const f32x2* const vp = ring_visitor_at(V, k);
+        const int idx = (int)(vp - lds);
+        qj.x = vp[0]; qj.y = vp[64]; qj.z = vp[128];
         if constexpr (ring_level_force(LEVEL)) fj = ring_move(fj, prev);
-        if constexpr (LEVEL >= 2) { wj.x = swx[idx]; wj.y = swy[idx]; wj.z = swz[idx]; gj = ring_move(gj, prev); }
-        const bool vj0 = 2 * idx < N, vj1 = 2 * idx + 1 < N;
+        if constexpr (LEVEL >= 2) { wj.x = vp[192]; wj.y = vp[256]; wj.z = vp[320]; gj = ring_move(gj, prev); }
+        const bool vj0 = vp < vend0, vj1 = vp < vend1;
         const bool s0 = vi0 && vj0, s1 = vi1 && vj1, c0 = vi0 && vj1, c1 = vi1 && vj0;
         bool ms0[NT], ms1[NT], mc0[NT], mc1[NT];
 #pragma unroll
@@ -632,10 +658,11 @@ __device__ __forceinline__ void ring_sweep_lj_multi(const RingLJ (&K)[NT], const
         ring_pair_lj_multi<LEVEL, NEAR, true, true, NT>(K, q, w, qj, wj, mc0, mc1, fi, gi, fj, gj, S);
     }
     if (!(nl & 1)) {                                                  // antipodal lanes: directed evaluation, visitors not updated
-        idx -= 1; idx = idx < 0 ? idx + nl : idx;
-        qj.x = sqx[idx]; qj.y = sqy[idx]; qj.z = sqz[idx];
-        if constexpr (LEVEL >= 2) { wj.x = swx[idx]; wj.y = swy[idx]; wj.z = swz[idx]; }
-        const bool vj0 = 2 * idx < N, vj1 = 2 * idx + 1 < N;
+        const f32x2* const vp = ring_visitor_at(V, nsteps + 1);
+        const int idx = (int)(vp - lds);
+        qj.x = vp[0]; qj.y = vp[64]; qj.z = vp[128];
+        if constexpr (LEVEL >= 2) { wj.x = vp[192]; wj.y = vp[256]; wj.z = vp[320]; }
+        const bool vj0 = vp < vend0, vj1 = vp < vend1;
         const bool s0 = vi0 && vj0, s1 = vi1 && vj1, c0 = vi0 && vj1, c1 = vi1 && vj0;
         bool ms0[NT], ms1[NT], mc0[NT], mc1[NT];
 #pragma unroll

@@ -3,9 +3,15 @@
 // packing, or does it take two passes?  Also v_pk_mul / v_pk_add, v_rcp_f32, v_rndne_f32 + v_med3_f32 (the minimum image),
 // ds_read_b96 / ds_read_b128 gathers at random 12 / 16-byte slots (the column-tile candidates).
 // Each kernel: 16 independent accumulator chains per lane (no dependency stalls), `iters` x 16 instructions, 8 waves per SIMD.
+// The plain forms of the ring loops (csrc/traj_ring.hpp) -- moves, selects, integer adds, conversions, compares, v_med3, v_sqrt
+// and a packed fma with one scalar source -- follow the same protocol (`valu_rate plain [waves per SIMD]`, default 8: eight
+// workgroups of four waves per CU; the ring adjoint itself runs at 3, and the second argument repeats the rows there).
+// "cycles" are of the 2.4 GHz the table assumes throughout, profiles/r05_valu_rate.txt included: weights relative to one another.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s line %d\n", hipGetErrorString(e_), __LINE__); return 1; } } while (0)
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -83,6 +89,72 @@ __global__ __launch_bounds__(256) void k_rndne_med3(float* out, int iters, float
     for (int k = 0; k < NCH; ++k) s += acc[k];
     out[blockIdx.x * blockDim.x + threadIdx.x] = s;
 }
+// k_fma with the first wave's cycle counter (clock64) and constant-rate counter (wall_clock64, 100 MHz) around the loop
+__global__ __launch_bounds__(256) void k_clock(float* out, long long* clk, int iters, float a, float b) {
+    float acc[NCH];
+    for (int k = 0; k < NCH; ++k) acc[k] = threadIdx.x * 1e-3f + k;
+    const long long c0 = clock64(), w0 = wall_clock64();
+    for (int it = 0; it < iters; ++it) {
+#pragma unroll
+        for (int k = 0; k < NCH; ++k) asm volatile("v_fma_f32 %0, %1, %2, %0" : "+v"(acc[k]) : "v"(a), "v"(b));
+    }
+    const long long c1 = clock64(), w1 = wall_clock64();
+    float s = 0.f;
+    for (int k = 0; k < NCH; ++k) s += acc[k];
+    out[blockIdx.x * blockDim.x + threadIdx.x] = s;
+    if (blockIdx.x == 0 && threadIdx.x == 0) { clk[0] = c1 - c0; clk[1] = w1 - w0; }
+}
+// plain forms: one instruction per chain, the chain's register as source and destination
+#define PLAIN_KERNEL(NAME, INIT, ...)                                                          \
+    __global__ __launch_bounds__(256) void NAME(float* out, int iters, float a, float b) {     \
+        float acc[NCH];                                                                        \
+        const unsigned long long m = __builtin_amdgcn_ballot_w64((threadIdx.x & 1) != 0);      \
+        const int ia = __builtin_bit_cast(int, a);                                             \
+        (void)m; (void)ia;                                                                     \
+        for (int k = 0; k < NCH; ++k) acc[k] = INIT;                                           \
+        for (int it = 0; it < iters; ++it) {                                                   \
+            _Pragma("unroll") for (int k = 0; k < NCH; ++k) asm volatile(__VA_ARGS__);         \
+        }                                                                                      \
+        float s = 0.f;                                                                         \
+        for (int k = 0; k < NCH; ++k) s += acc[k];                                             \
+        out[blockIdx.x * blockDim.x + threadIdx.x] = s;                                        \
+    }
+PLAIN_KERNEL(k_mov, threadIdx.x * 1e-3f + k, "v_mov_b32 %0, %1" : "+v"(acc[k]) : "v"(a))
+PLAIN_KERNEL(k_cndmask, threadIdx.x * 1e-3f + k, "v_cndmask_b32_e64 %0, %0, %1, %2" : "+v"(acc[k]) : "v"(a), "s"(m))
+PLAIN_KERNEL(k_add_u32, threadIdx.x * 1e-3f + k, "v_add_u32 %0, %1, %0" : "+v"(acc[k]) : "v"(ia))
+PLAIN_KERNEL(k_cvt_i32, threadIdx.x * 1e-3f + k, "v_cvt_i32_f32 %0, %0" : "+v"(acc[k]))
+PLAIN_KERNEL(k_fract, threadIdx.x * 1e-3f + k, "v_fract_f32 %0, %0" : "+v"(acc[k]))
+PLAIN_KERNEL(k_med3, threadIdx.x * 1e-3f + k, "v_med3_f32 %0, %0, %1, %2" : "+v"(acc[k]) : "v"(a), "v"(b))
+PLAIN_KERNEL(k_sqrt, threadIdx.x * 1e-3f + k + 1.f, "v_sqrt_f32 %0, %0" : "+v"(acc[k]))
+// the compare writes a lane mask, not a vector register: sixteen masks, counted at the end
+__global__ __launch_bounds__(256) void k_cmp_lt_u32(float* out, int iters, float a, float b) {
+    float acc[NCH];
+    unsigned long long mk[NCH];
+    const int ia = __builtin_bit_cast(int, a);
+    for (int k = 0; k < NCH; ++k) { acc[k] = threadIdx.x * 1e-3f + k; mk[k] = 0ull; }
+    for (int it = 0; it < iters; ++it) {
+#pragma unroll
+        for (int k = 0; k < NCH; ++k) asm volatile("v_cmp_lt_u32_e64 %0, %1, %2" : "=s"(mk[k]) : "v"(acc[k]), "v"(ia));
+    }
+    float s = 0.f;
+    for (int k = 0; k < NCH; ++k) s += acc[k] + (float)__builtin_popcountll(mk[k]);
+    out[blockIdx.x * blockDim.x + threadIdx.x] = s;
+}
+// packed fma whose first factor is a scalar register pair (the launch constants of ring_pair)
+__global__ __launch_bounds__(256) void k_pk_fma_sgpr(float* out, int iters, float a, float b) {
+    f32x2 acc[NCH];
+    const f32x2 av = {__builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, a))),
+                      __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, a * 1.01f)))};
+    const f32x2 bv = {b, b * 0.99f};
+    for (int k = 0; k < NCH; ++k) acc[k] = f32x2{threadIdx.x * 1e-3f + k, 1.f};
+    for (int it = 0; it < iters; ++it) {
+#pragma unroll
+        for (int k = 0; k < NCH; ++k) asm volatile("v_pk_fma_f32 %0, %1, %2, %0" : "+v"(acc[k]) : "s"(av), "v"(bv));
+    }
+    float s = 0.f;
+    for (int k = 0; k < NCH; ++k) s += acc[k].x + acc[k].y;
+    out[blockIdx.x * blockDim.x + threadIdx.x] = s;
+}
 // LDS gathers: every lane reads `iters` x 8 slots at pseudo-random positions of a 1 536-slot table (the tile size of lj4096)
 template <int BYTES>
 __global__ __launch_bounds__(256) void k_lds_gather(float* out, int iters, int nslot) {
@@ -121,9 +193,12 @@ float timed(F&& launch, hipEvent_t e0, hipEvent_t e1) {
     return ms / 5.f;
 }
 
-int main() {
+int main(int argc, char** argv) {
     float* out;
-    const int grid = 256 * 8, block = 256;                       // 8 workgroups of 4 waves per CU = 8 waves per SIMD
+    const bool plain = argc > 1 && !strcmp(argv[1], "plain");
+    const int wps = plain && argc > 2 ? atoi(argv[2]) : 8;
+    if (wps < 1 || wps > 8) { printf("waves per SIMD: 1 .. 8\n"); return 1; }
+    const int grid = 256 * wps, block = 256;                     // wps workgroups of 4 waves per CU = wps waves per SIMD (default 8)
     CK(hipMalloc(&out, sizeof(float) * grid * block));
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
     const int iters = 4096;
@@ -135,6 +210,32 @@ int main() {
         printf("%-22s %8.3f ms  %6.2f cycles per wave-instruction and SIMD  %7.1f TFLOP/s\n", NAME, ms,         \
                ms * 1e-3 * simd_cycles_per_s / insts, insts * 64.0 * (FLOP_PER_LANE) / (ms * 1e-3) / 1e12);          \
     } while (0)
+    if (plain) {
+        printf("# %d waves per SIMD (%d workgroups of 4 waves on each of 256 CUs), %d x %d instructions per wave\n", wps, wps, iters, NCH);
+        RUN("v_fma_f32", k_fma, 2);
+        RUN("v_mov_b32", k_mov, 0);
+        RUN("v_cndmask_b32", k_cndmask, 0);
+        RUN("v_add_u32", k_add_u32, 0);
+        RUN("v_cvt_i32_f32", k_cvt_i32, 0);
+        RUN("v_fract_f32", k_fract, 1);
+        RUN("v_cmp_lt_u32", k_cmp_lt_u32, 0);
+        RUN("v_med3_f32", k_med3, 1);
+        RUN("v_sqrt_f32", k_sqrt, 1);
+        RUN("v_pk_fma_f32", k_pk_fma, 4);
+        RUN("v_pk_fma_f32 (SGPR src)", k_pk_fma_sgpr, 4);
+        RUN("v_pk_mul_f32", k_pk_mul, 2);
+        RUN("v_pk_add_f32", k_pk_add, 2);
+        RUN("v_rcp_f32", k_rcp, 1);
+        // the shader clock while such a kernel runs: cycle counter against the constant 100 MHz counter, first wave of the grid
+        long long* clk;
+        CK(hipMalloc(&clk, 2 * sizeof(long long)));
+        hipLaunchKernelGGL(k_clock, dim3(grid), dim3(block), 0, 0, out, clk, iters, 1.0001f, 0.9999f);
+        long long h[2];
+        CK(hipMemcpy(h, clk, sizeof(h), hipMemcpyDeviceToHost));
+        printf("# shader clock during the v_fma_f32 kernel: %lld cycles in %lld ticks of 100 MHz = %.3f GHz (the cycles above are of 2.4 GHz)\n",
+               h[0], h[1], h[1] > 0 ? (double)h[0] / (double)h[1] * 0.1 : 0.0);
+        return 0;
+    }
     RUN("v_fma_f32", k_fma, 2);
     RUN("v_pk_fma_f32", k_pk_fma, 4);
     RUN("v_pk_mul_f32", k_pk_mul, 2);

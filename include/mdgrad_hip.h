@@ -1292,6 +1292,52 @@ int mdg_tersoff_multi_eval(const float* pos, int n_atoms, const MdgCell* cell /*
                            float* bond_work, float out_scale, int accumulate, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * K27  Tabulated embedded-atom potential ("eam/alloy") for 1 <= S <= 4 species over the per-atom (ELL) list
+ *      (mdgrad_amd/interface.py EAM, csrc/eam_table.hip).  With a = types[i], b = types[j]:
+ *        rho_i = sum_{j in row(i)} f_b(r_ij),   u_i = 1/2 sum_{j in row(i)} phi_ab(r_ij) + F_a(rho_i),   U = sum_i u_i
+ *      Every function is a cubic-Hermite interpolant on a uniform grid with node entries (value, h * derivative), the
+ *      convention of MDG_PAIR_TABLE.  phi and f live on r_g = r_min + g h_r, g = 0 .. n_r - 1, with r_{n_r - 1} = rc; F on
+ *      rho_g = rho_min + g h_rho, g = 0 .. n_rho - 1.  Outside its grid (r < r_min; rho < rho_min or rho > rho_max) a function
+ *      continues linearly with the end node's value and slope.  An atom with an empty row has rho_i = 0 and gets F_a(0) from
+ *      the table (not the "exactly 0" rule of K24).  Every entry with r = sqrt(d2) >= rc or r = 0 is skipped, so the list may
+ *      have been searched with any radius >= rc.
+ *      `types`: device int32 [n_atoms], values in [0, S) (checked by the caller; the kernels clamp what they read).
+ *      `tables`: device float [mdg_eam_table_size(S, n_r, n_rho)], the node entries in the order
+ *        pair [S (S + 1) / 2, n_r, 2]   phi of the unordered pair (a, b) at index hi (hi + 1) / 2 + lo  (the lower triangle)
+ *        density [S, n_r, 2]            f_b: the density an atom of species b contributes
+ *        embed [S, n_rho, 2]            F_a
+ *      Being device data they are not read here.  MdgEAMTableConsts holds the grids: n_species, n_r, n_rho, r_min, h_r, rc,
+ *      rho_min, h_rho, and pin_cutoff (1: the gradient of the last node of every phi and f table is returned as exactly 0).
+ *   mdg_eam_table_eval  the passes, atom_work [n_atoms, 4], `accumulate`, out_scale and the outputs energy, grad, hw of
+ *     mdg_eam_eval (K24), with  dU/dx_i = -sum_j [phi_ab'(r_ij) + F_a'(rho_i) f_b'(r_ij) + F_b'(rho_j) f_a'(r_ij)] e_ij;
+ *     mdg_eam_table_partial_size(n_atoms) floats of `partial`, required for energy.  The parameter outputs are
+ *       gtab [mdg_eam_table_size()]   dU/dtables, the layout of `tables` (a call without w)
+ *       gtabw, the same shape         d(w.dU/dx)/dtables (a call with w)
+ *     Either needs `fx`, a caller-owned device scratch of mdg_eam_table_fx_size(S, n_r, n_rho) int64 words: the contributions
+ *     (1/2 basis(r_ij) to phi_ab and F_a'(rho_i) basis(r_ij) to f_b per list entry, basis(rho_i) to F_a per atom; with w their
+ *     directional derivatives) are added as fixed-point numbers with integer atomics, one word per entry, at a power-of-two
+ *     scale per table family that the density pass derives on the device from measured upper bounds (max |basis|, max |F'|,
+ *     max |F'' d rho|) so that no sum can leave 2^62: order-independent, no flag, no host read.  A table set of at most 6144
+ *     words is summed per workgroup in LDS first (48 KiB at most), a larger one in global memory alone.  A finish kernel
+ *     writes the floats.  MDG_EINVAL: a null buffer, n_species outside [1, 4], n_r or n_rho outside [4, 4096], h_r <= 0 or h_rho <= 0,
+ *     rc <= r_min, r_min < 0, hw / gtabw without w, w without hw or gtabw, gtab together with w, gtab / gtabw without fx.
+ *     No float atomics: bitwise reproducible; the value parts of a launch with w equal those of a launch without, bit for bit.
+ *   mdg_eam_table_size / _fx_size return -1 for sizes outside the limits.
+ */
+typedef struct MdgEAMTableConsts {
+    double r_min, h_r, rc, rho_min, h_rho;
+    int32_t n_species, n_r, n_rho, pin_cutoff;
+} MdgEAMTableConsts;
+int64_t mdg_eam_table_partial_size(int n_atoms);
+int64_t mdg_eam_table_size(int n_species, int n_r, int n_rho);
+int64_t mdg_eam_table_fx_size(int n_species, int n_r, int n_rho);
+int mdg_eam_table_eval(const float* pos, int n_atoms, const MdgCell* cell /*host*/, const int32_t* col, const int32_t* shift,
+                       const int32_t* cnt, int max_nbr, const int32_t* types, const MdgEAMTableConsts* consts /*host*/,
+                       const float* tables /*device*/, const float* w, float* energy, float* grad, float* hw, float* gtab,
+                       float* gtabw, float* partial, float* atom_work, int64_t* fx, float out_scale, int accumulate,
+                       void* stream);
+
+/* ------------------------------------------------------------------------------------
  * f4  bonded terms over a static topology table (csrc/bonded.hip).
  * Replaces torchmd/interface.py:447-455 (BondPotentials.forward: harmonic in the SQUARED bond length,
  * 1/2 k (|b|^2 - ro)^2) and :496-508 (AnglePotentials.forward: 1/2 k (theta - theta0)^2 over triples (i, j, k) centred on

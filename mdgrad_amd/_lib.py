@@ -77,6 +77,12 @@ class MdgEAMConsts(C.Structure):
                [(n, C.c_int32) for n in ("n", "m", "shift", "pad_")]
 
 
+class MdgEAMTableConsts(C.Structure):
+    """The grids of the tabulated embedded-atom term (include/mdgrad_hip.h K27)."""
+    _fields_ = [(n, C.c_double) for n in ("r_min", "h_r", "rc", "rho_min", "h_rho")] + \
+               [(n, C.c_int32) for n in ("n_species", "n_r", "n_rho", "pin_cutoff")]
+
+
 class MdgTersoffConsts(C.Structure):
     """Constants of the Tersoff term and host copies of (A, B, h) (include/mdgrad_hip.h K25)."""
     _fields_ = [(n, C.c_double) for n in ("A", "B", "lam1", "lam2", "beta", "n", "c", "d", "h", "R", "D", "lam3", "gamma")] + \
@@ -310,6 +316,11 @@ _SIGNATURES = {
     "mdg_tersoff_multi_table_size": (C.c_int64, [C.c_int]),
     "mdg_tersoff_multi_eval": (C.c_int, [P, C.c_int, C.POINTER(MdgCell), P, P, P, C.c_int, P, C.c_int, P, P,
                                          P, P, P, P, P, P, P, C.c_float, C.c_int, P]),
+    "mdg_eam_table_partial_size": (C.c_int64, [C.c_int]),
+    "mdg_eam_table_size": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "mdg_eam_table_fx_size": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "mdg_eam_table_eval": (C.c_int, [P, C.c_int, C.POINTER(MdgCell), P, P, P, C.c_int, P, C.POINTER(MdgEAMTableConsts), P, P,
+                                     P, P, P, P, P, P, P, P, C.c_float, C.c_int, P]),
     "mdg_ewald_workspace": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "mdg_ewald_eval": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), P, P, P, C.c_int, P, P, P, P, P, P, P, C.c_float,
                                  C.c_int, P]),

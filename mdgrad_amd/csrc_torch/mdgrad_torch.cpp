@@ -24,6 +24,7 @@
 //   eam_eval         K24  interface.py SuttonChen           -> mdg_eam_eval
 //   tersoff_eval     K25  interface.py Tersoff              -> mdg_tersoff_eval
 //   tersoff_multi_eval  K26  interface.py TersoffMulti      -> mdg_tersoff_multi_eval
+//   eam_table_eval   K27  interface.py EAM                  -> mdg_eam_table_eval
 //   dihedral_phi_fwd/_bwd, dihedral_hist_fwd/_bwd  K19  observable.py Dihedrals / dihedral_distribution -> mdg_dihedral_phi_* / _hist_*
 //   edge_geom(+_bwd) schnet.py:142                          -> mdg_edge_geom / mdg_edge_geom_bwd
 //   cfconv_fwd/_bwd  K9+K10 modules.py:531-571              -> mdg_cfconv_fwd(_bf16) / mdg_cfconv_bwd(_bf16)
@@ -951,6 +952,52 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> tersoff_multi_eval(const Tens
     return {U, g, hw, pth, pthw};
 }
 
+// ------------------------------------------------------------------------------------------------ K27
+// types: int32 [N] with values in [0, n_species) (read back once to check them); consts = (n_species, n_r, n_rho, r_min, rc,
+// rho_min, rho_max, pin_cutoff) of the grids; tables: the flat node image (pair, density, embed) of mdg_eam_table_size floats.
+// (U [1] or [0], dU/dx [N,3], H w [N,3] or [0], gtab [table size] or [0], gtabw likewise or [0]); want_theta: gtab without w,
+// gtabw with it.  The scratch of the density pass and of the fixed-point scatter is allocated here.
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> eam_table_eval(const Tensor& pos, at::ArrayRef<double> cell, const Tensor& col,
+                                                                  const Tensor& shift, const Tensor& cnt, const Tensor& types,
+                                                                  at::ArrayRef<double> consts, const Tensor& tables,
+                                                                  const OptTensor& w, bool want_energy, bool want_theta) {
+    check_f32(pos, "pos");
+    TORCH_CHECK(pos.dim() == 2 && pos.size(1) == 3 && pos.size(0) > 0 && pos.size(0) <= INT32_MAX, "mdgrad: pos must be [N,3]");
+    TORCH_CHECK(consts.size() == 8, "mdgrad: consts = (n_species, n_r, n_rho, r_min, rc, rho_min, rho_max, pin_cutoff)");
+    const MdgCell c = make_cell(cell);
+    const EllRef e = ell_of(pos, col, shift, cnt);
+    MdgEAMTableConsts k{};
+    k.n_species = (int32_t)consts[0]; k.n_r = (int32_t)consts[1]; k.n_rho = (int32_t)consts[2]; k.pin_cutoff = (int32_t)consts[7];
+    TORCH_CHECK((double)k.n_species == consts[0] && (double)k.n_r == consts[1] && (double)k.n_rho == consts[2] &&
+                (double)k.pin_cutoff == consts[7], "mdgrad: n_species, n_r, n_rho and pin_cutoff must be integers");
+    TORCH_CHECK(k.n_species >= 1 && k.n_species <= 4, "mdgrad: n_species must lie in [1, 4] (got ", k.n_species, ")");
+    TORCH_CHECK(k.n_r >= 4 && k.n_r <= 4096 && k.n_rho >= 4 && k.n_rho <= 4096, "mdgrad: n_r and n_rho must lie in [4, 4096]");
+    k.r_min = consts[3]; k.rc = consts[4]; k.rho_min = consts[5];
+    k.h_r = (k.rc - k.r_min) / (k.n_r - 1); k.h_rho = (consts[6] - k.rho_min) / (k.n_rho - 1);
+    check_i32(types, "types"); same_device(pos, types, "types");
+    TORCH_CHECK(types.dim() == 1 && types.size(0) == pos.size(0), "mdgrad: types must hold one entry per atom");
+    TORCH_CHECK(types.min().item<int32_t>() >= 0 && types.max().item<int32_t>() < k.n_species,
+                "mdgrad: types must lie in [0, n_species)");
+    check_f32(tables, "tables"); same_device(pos, tables, "tables");
+    const int64_t P = mdg_eam_table_size(k.n_species, k.n_r, k.n_rho);
+    TORCH_CHECK(tables.numel() == P, "mdgrad: tables must hold ", P, " floats (pair, density, embed)");
+    const float* wp = fptr(w, "w");
+    if (wp) { same_device(pos, *w, "w"); TORCH_CHECK(w->sizes() == pos.sizes(), "mdgrad: w must have the shape of pos"); }
+    const int n = (int)pos.size(0);
+    const auto o = pos.options();
+    Tensor U = at::empty({want_energy ? 1 : 0}, o), g = at::empty_like(pos);
+    Tensor hw = wp ? at::empty_like(pos) : at::empty({0}, o);
+    Tensor gtab = (want_theta && !wp) ? at::empty({P}, o) : at::empty({0}, o);
+    Tensor gtabw = (want_theta && wp) ? at::empty({P}, o) : at::empty({0}, o);
+    Tensor partial = at::empty({mdg_eam_table_partial_size(n)}, o), work = at::empty({(int64_t)n, 4}, o);
+    Tensor fx = at::empty({want_theta ? mdg_eam_table_fx_size(k.n_species, k.n_r, k.n_rho) : 0}, o.dtype(at::kLong));
+    ok(mdg_eam_table_eval(fptr(pos), n, &c, e.col, e.shift, e.cnt, e.max_nbr, types.data_ptr<int32_t>(), &k, fptr(tables), wp,
+                          want_energy ? mptr(U) : nullptr, mptr(g), wp ? mptr(hw) : nullptr,
+                          (want_theta && !wp) ? mptr(gtab) : nullptr, (want_theta && wp) ? mptr(gtabw) : nullptr, mptr(partial),
+                          mptr(work), want_theta ? fx.data_ptr<int64_t>() : nullptr, 1.f, 0, stream_of(pos)));
+    return {U, g, hw, gtab, gtabw};
+}
+
 // ------------------------------------------------------------------------------------------------ K22
 // pos [R n, 3], q float [R n], cell_len = the three diagonal lengths; row_ptr int32 [n + 1], col int32 [nnz], scale float [nnz]:
 // the CSR incidence list of ops.EwaldExclTable (checked here with device reads: the kernel indexes pos with col).
@@ -1040,6 +1087,8 @@ TORCH_LIBRARY(mdgrad, m) {
           "bool want_energy, bool want_theta) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("tersoff_multi_eval(Tensor pos, float[] cell, Tensor col, Tensor shift, Tensor cnt, Tensor types, int n_species, "
           "Tensor tables, Tensor? w, bool want_energy, bool want_theta) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
+    m.def("eam_table_eval(Tensor pos, float[] cell, Tensor col, Tensor shift, Tensor cnt, Tensor types, float[] consts, "
+          "Tensor tables, Tensor? w, bool want_energy, bool want_theta) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("ewald_eval(Tensor pos, int n_rep, float[] cell, Tensor q, Tensor kvec, Tensor coef, Tensor? w, bool want_energy, "
           "bool want_pot) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("ewald_excl_eval(Tensor pos, int n_rep, float[] cell_len, Tensor row_ptr, Tensor col, Tensor scale, Tensor q, float alpha, "
@@ -1087,6 +1136,7 @@ TORCH_LIBRARY_IMPL(mdgrad, CUDA, m) {      // (the HIP backend registers under t
     m.impl("eam_eval", eam_eval);
     m.impl("tersoff_eval", tersoff_eval);
     m.impl("tersoff_multi_eval", tersoff_multi_eval);
+    m.impl("eam_table_eval", eam_table_eval);
     m.impl("ewald_eval", ewald_eval);
     m.impl("ewald_excl_eval", ewald_excl_eval);
     m.impl("edge_geom", edge_geom);

@@ -1,6 +1,6 @@
 """Energy calculators with the reference's interface (torchmd/interface.py):
 GeneralInteraction :33-57, PairPotentials :217-300, Electrostatics :303-361 (as CoulombPotentials), Stack :364-403;
-StillingerWeber (three-body), SuttonChen (embedded-atom), Tersoff (bond-order) and TersoffMulti (the same for several species) -- none of them has a counterpart in the reference
+StillingerWeber (three-body), SuttonChen (embedded-atom), EAM (tabulated embedded-atom, alloys), Tersoff (bond-order) and TersoffMulti (the same for several species) -- none of them has a counterpart in the reference
 (GNNPotentials lives in mdgrad_amd.nn).  forward(xyz) -> energy; _reset_topology(xyz) rebuilds the neighbour list.
 """
 import inspect
@@ -1308,6 +1308,388 @@ class SuttonChen(_ManyBodyTerm):
 
     def _term(self, xyz):
         return ops.EAMTerm(self._ell, self._consts, self._theta(), self._scratch(xyz))
+
+
+def _hermite(nodes, which, x, x0, h):
+    """Table `which[m]` of `nodes` [K, n, 2] at x[m]: the cubic-Hermite interpolant of the node entries (value, h * derivative)
+    on the grid x0 + g h, continued linearly below the first and above the last node (differentiable in x and in nodes)."""
+    n = nodes.shape[1]
+    u = (x - x0) / h
+    g = u.detach().floor().clamp(0, n - 2).long()
+    t = u - g.to(u)
+    lo, hi = nodes[which, g], nodes[which, g + 1]
+    c = t.clamp(0.0, 1.0)
+    s = 1.0 - c
+    inside = (1.0 + 2.0 * c) * s * s * lo[:, 0] + c * s * s * lo[:, 1] + c * c * (3.0 - 2.0 * c) * hi[:, 0] - c * c * s * hi[:, 1]
+    below, above = lo[:, 0] + t * lo[:, 1], hi[:, 0] + (t - 1.0) * hi[:, 1]
+    return torch.where(t < 0, below, torch.where(t > 1, above, inside))
+
+
+def _five_point(y):
+    """h * dy/dx at every point of the uniform samples y [..., n] by the formula LAMMPS builds its setfl splines from:
+    (y[m-2] - y[m+2] + 8 (y[m+1] - y[m-1])) / 12 inside, central differences next to the ends, one-sided at the ends."""
+    y = np.asarray(y, dtype=np.float64)
+    d = np.empty_like(y)
+    d[..., 0], d[..., -1] = y[..., 1] - y[..., 0], y[..., -1] - y[..., -2]
+    d[..., 1], d[..., -2] = 0.5 * (y[..., 2] - y[..., 0]), 0.5 * (y[..., -1] - y[..., -3])
+    d[..., 2:-2] = (y[..., :-4] - y[..., 4:] + 8.0 * (y[..., 3:-1] - y[..., 1:-3])) / 12.0
+    return d
+
+
+class EAM(_ManyBodyTerm):
+    """Tabulated embedded-atom potential for 1 <= S <= 4 species (Daw and Baskes 1984; the "eam/alloy" form in which the
+    potentials of Mishin, Zhou, Mendelev are distributed as setfl files).  Atom i has the species t_i = `types`[i]; with
+    a = t_i, b = t_j:
+
+        U     = sum_i [ 1/2 sum_{j != i} phi_ab(r_ij) + F_a(rho_i) ]
+        rho_i = sum_{j != i} f_b(r_ij)
+
+    The density an atom contributes depends on its own species only, and phi_ab = phi_ba is stored once per unordered pair:
+    S (S + 1) / 2 pair tables, pair (a, b) at index hi (hi + 1) / 2 + lo (the lower triangle: 00, 10, 11, 20, ...).  The pair
+    set, the minimum image and the 0 < r < rc test are those of SuttonChen at rc = `cutoff`; the replicas of System.replicate
+    never see each other; a list searched with a skin is exact.
+
+    Every function is a cubic-Hermite interpolant on a uniform grid; a node entry is (value, h * derivative), the convention
+    of the tabulated pair model.  phi and f are tabulated in r on r_g = r_min + g h_r, g = 0 .. n_r - 1, with r_{n_r - 1} =
+    cutoff; F in rho on rho_g = rho_min + g h_rho over `rho_range` = (rho_min, rho_max).  4 <= n_r, n_rho <= 4096.  Outside
+    its grid (r < r_min; rho < rho_min or rho > rho_max) a function continues linearly with the end node's value and slope:
+    every argument has a finite, C1 value.  An atom without a neighbour inside the cutoff has rho = 0 and gets F_a(0) from
+    the table -- unlike SuttonChen, where its embedding energy is exactly 0.
+
+    The nodes are the parameters: `pair_nodes` [S (S + 1) / 2, n_r, 2], `density_nodes` [S, n_r, 2], `embed_nodes`
+    [S, n_rho, 2].  `trainable` names those that are nn.Parameters ("pair", "density", "embed"; True = all, False = none),
+    the rest are buffers; `dtype` is their storage type (the kernels read a float32 mirror).  With pin_cutoff=True (the
+    default) the last node of every phi and f table is held at (0, 0), so that energy and force are continuous at the
+    cutoff: the constructor sets those entries to zero and their gradient entries come back as exact zeros.
+
+    `from_functions` tabulates Python callables, `from_sutton_chen` is the tabulated twin of SuttonChen, `from_setfl` /
+    `write_setfl` read and write the setfl text format.  Not covered: functions given as nn.Modules and re-tabulated per
+    pass, the Finnis-Sinclair form with a density function per pair (f_ab) and funcfl files, `index_tuple` and `ex_pairs`
+    (both rejected), the pressure of the term, the fused trajectory kernels (a Stack holding the term stays off them).
+
+    forward(xyz) is differentiable twice in xyz and once in the nodes on the HIP kernels (ops.EAMTableTerm,
+    csrc/eam_table.hip: the two passes of csrc/eam.hip with every function looked up by species in a device table, and an
+    order-independent fixed-point scatter for the node gradients); force / force_vjp serve the analytic adjoint and
+    HIP-graph replay, also while the nodes require grad.  float64 or host positions take the torch restatement
+    `_torch_energy`."""
+
+    MAX_SPECIES = ops.EAM_TABLE_MAX_SPECIES
+    TABLES = ("pair", "density", "embed")
+
+    def __init__(self, system, types, pair_nodes, density_nodes, embed_nodes, cutoff, r_min, rho_range,
+                 trainable=("pair", "density", "embed"), pin_cutoff=True, dtype=torch.float32, index_tuple=None, ex_pairs=None):
+        super().__init__(system)
+        if index_tuple is not None or ex_pairs is not None:
+            raise ValueError("EAM: index_tuple and ex_pairs are not supported (every pair interacts)")
+        if trainable is True or trainable is False:
+            trainable = self.TABLES if trainable else ()
+        trainable = tuple(trainable)
+        if any(name not in self.TABLES for name in trainable):
+            raise ValueError("EAM: trainable names tables among %r (got %r)" % (self.TABLES, trainable))
+        nodes = [torch.as_tensor(v).detach().to("cpu", torch.float64).clone() for v in (pair_nodes, density_nodes, embed_nodes)]
+        if any(v.dim() != 3 or v.shape[2] != 2 for v in nodes):
+            raise ValueError("EAM: every node tensor is [tables, nodes, 2] (got %s)" % ([tuple(v.shape) for v in nodes],))
+        S, n_r, n_rho = int(nodes[1].shape[0]), int(nodes[1].shape[1]), int(nodes[2].shape[1])
+        if not 1 <= S <= self.MAX_SPECIES:
+            raise ValueError("EAM: S = %d species; 1 to %d are supported" % (S, self.MAX_SPECIES))
+        if tuple(nodes[0].shape) != (S * (S + 1) // 2, n_r, 2) or int(nodes[2].shape[0]) != S:
+            raise ValueError("EAM: for S = %d species on n_r = %d nodes pair_nodes is [%d, %d, 2] and embed_nodes [%d, n_rho, 2] "
+                             "(got %s, %s)" % (S, n_r, S * (S + 1) // 2, n_r, S, tuple(nodes[0].shape), tuple(nodes[2].shape)))
+        if not all(bool(torch.isfinite(v).all()) for v in nodes):
+            raise ValueError("EAM: the node entries must be finite")
+        rho_range = tuple(float(v) for v in rho_range)
+        if len(rho_range) != 2:
+            raise ValueError("EAM: rho_range = (rho_min, rho_max) (got %r)" % (rho_range,))
+        self._consts = ops.eam_table_consts(S, n_r, n_rho, r_min, cutoff, rho_range[0], rho_range[1], pin_cutoff)
+        k = self._consts
+        self.n_species, self.n_r, self.n_rho, self.pin_cutoff = S, n_r, n_rho, bool(pin_cutoff)
+        self.cutoff, self.r_min, self.rho_range = float(k.rc), float(k.r_min), rho_range
+        self.h_r, self.h_rho = float(k.h_r), float(k.h_rho)
+        ty = np.asarray(torch.as_tensor(types).detach().cpu().numpy()).reshape(-1)
+        if ty.shape[0] != self._group:
+            raise ValueError("EAM: types must hold one entry per atom of a replica (%d), got %d" % (self._group, ty.shape[0]))
+        if not np.issubdtype(ty.dtype, np.integer) or ty.min() < 0 or ty.max() >= S:
+            raise ValueError("EAM: types must be integers in [0, %d)" % S)
+        h = np.asarray(system.get_cell(), dtype=np.float64)
+        h = np.diag(h) if h.ndim == 1 else h
+        vol = abs(float(np.linalg.det(h)))
+        self._half_height = 0.5 * min(vol / float(np.linalg.norm(np.cross(h[(d + 1) % 3], h[(d + 2) % 3]))) for d in range(3))
+        if self.cutoff > self._half_height:
+            raise ValueError("EAM: cutoff = %g exceeds half the shortest cell height (%g)" % (self.cutoff, self._half_height))
+        if self.pin_cutoff:
+            nodes[0][:, -1, :] = 0.0
+            nodes[1][:, -1, :] = 0.0
+        self._select, pos = [], 0
+        for name, v in zip(self.TABLES, nodes):
+            t = v.to(self.device, dtype)
+            if name in trainable:
+                setattr(self, name + "_nodes", torch.nn.Parameter(t))
+                self._select.append((pos, pos + t.numel()))
+            else:
+                self.register_buffer(name + "_nodes", t)
+            pos += t.numel()
+        self.trainable = tuple(name for name in self.TABLES if name in trainable)
+        self.density_at_origin = None                                   # f_b(0) of a setfl file, kept for write_setfl
+        self.index_tuple, self.ex_pairs, self._mask = None, None, None
+        self._n_rep = system.get_number_of_atoms() // self._group
+        self.types = torch.as_tensor(np.tile(ty.astype(np.int32), self._n_rep), device=self.device)   # one entry per atom
+        self._ell = None
+        self._table_mirror = _DeviceMirror(self._nodes)
+        self._work, self._fx = None, None
+        if torch.device(self.device).type == "cuda":
+            # the scratch of the density pass and of the fixed-point scatter: persistent, so that a captured graph sees fixed addresses
+            self._work = torch.empty(system.get_number_of_atoms(), 4, dtype=torch.float32, device=self.device)
+            self._fx = torch.empty(ops.eam_table_fx_size(k), dtype=torch.int64, device=self.device)
+            self._reset_topology(torch.Tensor(system.get_positions()).to(system.device))
+            self._tables()
+
+    # -- constructors ----------------------------------------------------------------------------------------------
+    @staticmethod
+    def tabulate(fn, x0, x1, n):
+        """[n, 2] float64 node entries (value, h * derivative) of `fn` on n points from x0 to x1.  `fn` maps a float64 tensor
+        to a tensor of its shape and is differentiated by autograd, or is a pair (fn, dfn) with the derivative supplied."""
+        x = torch.linspace(float(x0), float(x1), int(n), dtype=torch.float64)
+        h = (float(x1) - float(x0)) / (int(n) - 1)
+        if isinstance(fn, (tuple, list)):
+            y, dy = fn[0](x), fn[1](x)
+        else:
+            with torch.enable_grad():
+                xg = x.clone().requires_grad_(True)
+                y = fn(xg)
+                (dy,) = torch.autograd.grad(y.sum(), xg)
+        return torch.stack([torch.as_tensor(y).detach().double(), h * torch.as_tensor(dy).detach().double()], -1)
+
+    @classmethod
+    def from_functions(cls, system, types, pair, density, embed, cutoff, r_min, rho_range, n_r=1024, n_rho=1024, **kw):
+        """The term from Python callables, tabulated in float64 (`tabulate`): `density` and `embed` hold one function per
+        species; `pair` one per unordered species pair, as a dict keyed (a, b) (either order) or a list in the order of the
+        lower triangle (00, 10, 11, 20, ...)."""
+        density, embed = list(density), list(embed)
+        S = len(density)
+        if len(embed) != S or not 1 <= S <= cls.MAX_SPECIES:
+            raise ValueError("EAM: density and embed hold one function per species, 1 to %d of them (got %d, %d)"
+                             % (cls.MAX_SPECIES, S, len(embed)))
+        order = [(a, b) for a in range(S) for b in range(a + 1)]
+        if isinstance(pair, dict):
+            missing = [ab for ab in order if ab not in pair and ab[::-1] not in pair]
+            if missing:
+                raise ValueError("EAM: pair lacks a function for the species pairs %r" % (missing,))
+            pair = [pair[ab] if ab in pair else pair[ab[::-1]] for ab in order]
+        pair = list(pair)
+        if len(pair) != len(order):
+            raise ValueError("EAM: pair holds %d functions for %d species (got %d)" % (len(order), S, len(pair)))
+        pn = torch.stack([cls.tabulate(f, r_min, cutoff, n_r) for f in pair])
+        dn = torch.stack([cls.tabulate(f, r_min, cutoff, n_r) for f in density])
+        en = torch.stack([cls.tabulate(f, rho_range[0], rho_range[1], n_rho) for f in embed])
+        return cls(system, types, pn, dn, en, cutoff, r_min, rho_range, **kw)
+
+    @classmethod
+    def from_sutton_chen(cls, system, preset_or_constants, cutoff=None, shift="force", rho_range=None, r_min=None, n_r=1024,
+                         n_rho=1024, **kw):
+        """The tabulated twin of SuttonChen: phi = epsilon S_n, f = S_m, F = -epsilon c sqrt(rho) for a preset name of
+        SuttonChen.PUBLISHED or the constants (epsilon, a, c, n, m); cutoff 2 a and r_min a / 2 by default.  rho_range defaults
+        to (rho_lo / 2, 3 rho_hi / 2) of the densities at the system's positions; rho_min must be positive, because sqrt(rho)
+        has no finite slope at 0."""
+        eps, a, c, n, m = SuttonChen.PUBLISHED[preset_or_constants] if isinstance(preset_or_constants, str) else preset_or_constants
+        eps, a, c, n, m = float(eps), float(a), float(c), int(n), int(m)
+        cutoff = 2.0 * a if cutoff is None else float(cutoff)
+        r_min = 0.5 * a if r_min is None else float(r_min)
+        if shift not in ops.EAM_SHIFTS:
+            raise ValueError("EAM: shift must be 'force' or 'none' (got %r)" % (shift,))
+
+        def S(k):
+            q = (a / cutoff) ** k if shift == "force" else 0.0
+            return (lambda r: (a / r) ** k - q + k * (r - cutoff) * q / cutoff), (lambda r: -k * (a / r) ** k / r + k * q / cutoff)
+        Sn, Sm = S(n), S(m)
+        if rho_range is None:
+            probe = cls.__new__(cls)
+            GeneralInteraction.__init__(probe, system)
+            probe._n_rep = system.get_number_of_atoms() // probe._group
+            x = torch.as_tensor(np.asarray(system.get_positions()), dtype=torch.float64)
+            i, j, off = probe._all_pairs(x, cutoff)
+            cell = probe.cell.detach().to(x)
+            cell = torch.diag(cell) if cell.dim() == 1 else cell
+            r = (x[i] - x[j] - off.matmul(cell)).pow(2).sum(-1).sqrt()
+            rho = x.new_zeros(x.shape[0]).index_add(0, torch.cat([i, j]), torch.cat([Sm[0](r)] * 2))
+            rho_range = (0.5 * float(rho.min()), 1.5 * float(rho.max()))
+        if not float(rho_range[0]) > 0.0:
+            raise ValueError("EAM.from_sutton_chen: rho_min must be positive: sqrt(rho) has no finite slope at 0 (got %r)" % (rho_range[0],))
+        pair = (lambda r: eps * Sn[0](r)), (lambda r: eps * Sn[1](r))
+        embed = (lambda p: -eps * c * p.sqrt()), (lambda p: -0.5 * eps * c / p.sqrt())
+        ty = np.zeros(getattr(system, "group_size", system.get_number_of_atoms()), dtype=np.int64)
+        kw.setdefault("pin_cutoff", shift == "force")        # (as published the functions do not vanish at the cutoff)
+        return cls.from_functions(system, ty, [pair], [Sm], [embed], cutoff, r_min, rho_range, n_r, n_rho, **kw)
+
+    @staticmethod
+    def read_setfl(path_or_file):
+        """The content of a setfl ("eam/alloy") text file: dict(comments [3], elements [S], header [S] (atomic number, mass,
+        lattice constant, lattice), n_rho, d_rho, n_r, d_r, cutoff, F [S, n_rho], f [S, n_r], z2r [S (S + 1) / 2, n_r] =
+        r phi(r) in the order of the lower triangle), numbers in float64."""
+        text = path_or_file.read() if hasattr(path_or_file, "read") else open(path_or_file).read()
+        lines = text.splitlines()
+        if len(lines) < 6:
+            raise ValueError("EAM: not a setfl file (fewer than six lines)")
+        head = lines[3].split()
+        S = int(head[0])
+        elements = head[1:1 + S]
+        if len(elements) != S or S < 1:
+            raise ValueError("EAM: line 4 of a setfl file is 'N element_1 ... element_N' (got %r)" % lines[3])
+        g = lines[4].replace("D", "E").replace("d", "e").split()
+        n_rho, d_rho, n_r, d_r, cutoff = int(g[0]), float(g[1]), int(g[2]), float(g[3]), float(g[4])
+        tok = " ".join(lines[5:]).split()
+        pos, header, F, f = 0, [], [], []
+        num = lambda t: float(t.replace("D", "E").replace("d", "e"))
+        need = S * (4 + n_rho + n_r) + S * (S + 1) // 2 * n_r
+        if len(tok) < need:
+            raise ValueError("EAM: the setfl file holds %d entries after line 5, %d are needed" % (len(tok), need))
+        for _ in range(S):
+            header.append((int(tok[pos]), num(tok[pos + 1]), num(tok[pos + 2]), tok[pos + 3]))
+            pos += 4
+            F.append([num(t) for t in tok[pos:pos + n_rho]])
+            pos += n_rho
+            f.append([num(t) for t in tok[pos:pos + n_r]])
+            pos += n_r
+        z = []
+        for _ in range(S * (S + 1) // 2):
+            z.append([num(t) for t in tok[pos:pos + n_r]])
+            pos += n_r
+        return dict(comments=lines[:3], elements=elements, header=header, n_rho=n_rho, d_rho=d_rho, n_r=n_r, d_r=d_r, cutoff=cutoff,
+                    F=np.array(F, dtype=np.float64), f=np.array(f, dtype=np.float64), z2r=np.array(z, dtype=np.float64))
+
+    @classmethod
+    def from_setfl(cls, system, types, path_or_file, elements=None, **kw):
+        """The term from a setfl ("eam/alloy") file.  `elements` selects and orders the file's elements as species 0, 1, ...
+        (default: all, in file order).  The file tabulates F on rho = g d_rho and f, r phi on r = g d_r, g from 0: the grid
+        point r = 0 is dropped (r_min = d_r, r phi divided by r on the rest), and rc is the largest grid point that does not
+        exceed the file's cutoff, so n_r = floor(cutoff / d_r) nodes are kept.  Node slopes come from the five-point formula
+        LAMMPS builds its splines from, applied on the file's full grid to F, f and r phi (phi' = (r phi)' / r - phi / r);
+        the node values are the file's, so pin_cutoff defaults to False here.  f(0) is kept in `density_at_origin` for
+        `write_setfl`."""
+        d = cls.read_setfl(path_or_file)
+        names = d["elements"]
+        elements = list(names) if elements is None else list(elements)
+        if any(e not in names for e in elements):
+            raise ValueError("EAM: the setfl file holds %r, not %r" % (names, [e for e in elements if e not in names]))
+        idx = [names.index(e) for e in elements]
+        gc = min(int(math.floor(d["cutoff"] / d["d_r"] + 1e-9)), d["n_r"] - 1)
+        if gc < 4 or d["n_rho"] < 4:
+            raise ValueError("EAM: the setfl grids are too short (n_rho = %d, %d points of r inside the cutoff)" % (d["n_rho"], gc))
+        r = d["d_r"] * np.arange(1, gc + 1)
+        tri = lambda a, b: max(a, b) * (max(a, b) + 1) // 2 + min(a, b)
+        z, dz = d["z2r"], _five_point(d["z2r"])
+        pair = []
+        for a in range(len(idx)):
+            for b in range(a + 1):
+                p = tri(idx[a], idx[b])
+                phi = z[p, 1:gc + 1] / r
+                pair.append(np.stack([phi, dz[p, 1:gc + 1] / r - d["d_r"] * phi / r], -1))
+        dens = np.stack([d["f"][idx, 1:gc + 1], _five_point(d["f"])[idx, 1:gc + 1]], -1)
+        emb = np.stack([d["F"][idx], _five_point(d["F"])[idx]], -1)
+        kw.setdefault("pin_cutoff", False)
+        self = cls(system, types, np.stack(pair), dens, emb, float(r[-1]), d["d_r"], (0.0, (d["n_rho"] - 1) * d["d_rho"]), **kw)
+        self.density_at_origin = d["f"][idx, 0].copy()
+        self.elements, self.setfl_header = elements, [d["header"][k] for k in idx]
+        return self
+
+    def write_setfl(self, path_or_file, elements=None, header=None, comments=None):
+        """The node values as a setfl file (the inverse of `from_setfl` for them; the slopes are not part of the format).  The
+        grids must be those of the format: rho_min = 0 and r_min = h_r.  f(0) is `density_at_origin` when the term was read
+        from a file, otherwise the linear continuation; r phi at r = 0 is written as 0."""
+        if abs(self.rho_range[0]) > 0.0 or abs(self.r_min - self.h_r) > 1e-9 * self.h_r:
+            raise ValueError("EAM.write_setfl: a setfl grid starts at 0: rho_min = 0 and r_min = h_r are needed (got %r, %r, h_r = %r)"
+                             % (self.rho_range[0], self.r_min, self.h_r))
+        S = self.n_species
+        elements = list(elements or getattr(self, "elements", None) or ["X%d" % a for a in range(S)])
+        header = list(header or getattr(self, "setfl_header", None) or [(0, 1.0, 0.0, "fcc")] * S)
+        comments = list(comments or ["tabulated embedded-atom potential", "written by mdgrad_amd.interface.EAM.write_setfl", ""])
+        pn, dn, en = (v.detach().cpu().double().numpy() for v in self._nodes())
+        r = self.r_min + self.h_r * np.arange(self.n_r)
+        f0 = dn[:, 0, 0] - dn[:, 0, 1] if self.density_at_origin is None else np.asarray(self.density_at_origin)
+        out = [str(c) for c in comments[:3]] + ["%d %s" % (S, " ".join(elements))]
+        out.append("%d %.17g %d %.17g %.17g" % (self.n_rho, self.h_rho, self.n_r + 1, self.h_r, self.cutoff))
+        rows = lambda v: [" ".join("%.17g" % x for x in v[k:k + 5]) for k in range(0, len(v), 5)]
+        for a in range(S):
+            out.append("%d %.17g %.17g %s" % tuple(header[a]))
+            out += rows(en[a, :, 0]) + rows(np.concatenate([[f0[a]], dn[a, :, 0]]))
+        for p in range(S * (S + 1) // 2):
+            out += rows(np.concatenate([[0.0], r * pn[p, :, 0]]))
+        text = "\n".join(out) + "\n"
+        if hasattr(path_or_file, "write"):
+            path_or_file.write(text)
+        else:
+            with open(path_or_file, "w") as fh:
+                fh.write(text)
+
+    # -- the device tables the kernels read: the flat float32 image (pair, density, embed) of the nodes ---------------
+    def _nodes(self):
+        return self.pair_nodes, self.density_nodes, self.embed_nodes
+
+    def _thetas(self):
+        """The trainable node tensors, in the order of parameters()."""
+        return tuple(getattr(self, name + "_nodes") for name in self.trainable)
+
+    def _tables(self):
+        """The nodes as the kernels read them: a device mirror (_DeviceMirror) rewritten when a node tensor changed, so that
+        the captured steps carry no host value of a parameter."""
+        return self._table_mirror.get()
+
+    def prepare_pass(self):
+        if self._hip_ok():
+            self._tables()
+
+    # (not the base's: the density pass keeps four floats per atom, sized by the positions, not per list slot)
+    def _scratch(self, xyz):
+        if self._work is None or self._work.device != xyz.device or self._work.shape[0] != xyz.shape[0]:
+            self._work = torch.empty(xyz.shape[0], 4, dtype=torch.float32, device=xyz.device)
+        if self._fx is None or self._fx.device != xyz.device:
+            self._fx = torch.empty(ops.eam_table_fx_size(self._consts), dtype=torch.int64, device=xyz.device)
+        return self._work
+
+    # -- energy ----------------------------------------------------------------------------------------------------
+    def _torch_energy(self, xyz):
+        """The same energy in torch ops, in the dtype and on the device of xyz (differentiable by autograd in xyz and in the
+        three node tensors)."""
+        pn, dn, en = (v.to(xyz) for v in self._nodes())
+        if self.pin_cutoff:                                   # the last node of phi and f is held at (0, 0): no gradient reaches it
+            keep = torch.ones(self.n_r, 1, dtype=xyz.dtype, device=xyz.device)
+            keep[-1] = 0.0
+            pn, dn = pn * keep, dn * keep
+        i, j, off = self._all_pairs(xyz, self.cutoff)
+        cell = self.cell.detach().to(xyz)
+        cell = torch.diag(cell) if cell.dim() == 1 else cell
+        r = (xyz[i] - xyz[j] - off.matmul(cell)).pow(2).sum(-1).sqrt()
+        ty = self.types.to(xyz.device).long()
+        a, b = ty[i], ty[j]
+        hi, lo = torch.maximum(a, b), torch.minimum(a, b)
+        phi = _hermite(pn, hi * (hi + 1) // 2 + lo, r, self.r_min, self.h_r)
+        to_i, to_j = _hermite(dn, b, r, self.r_min, self.h_r), _hermite(dn, a, r, self.r_min, self.h_r)
+        rho = xyz.new_zeros(xyz.shape[0]).index_add(0, torch.cat([i, j]), torch.cat([to_i, to_j]))
+        return phi.sum() + _hermite(en, ty, rho, self.rho_range[0], self.h_rho).sum()
+
+    def _term(self, xyz):
+        work = self._scratch(xyz)
+        return ops.EAMTableTerm(self._ell, self.types, self._consts, self._tables(), work, self._fx, self._select)
+
+    def force_vjp(self, xyz, w, want_theta=True, accum=None, into=None):
+        """(F, d(w.F)/dx, [d(w.F)/dnodes for every trainable node tensor, shaped like it]) in one call of the term's kernels;
+        `accum` (ops.ThetaAccum): the node part is added into its flat buffer at the parameters' offsets instead (None
+        returned).  `into` = (F, dq) buffers of another Stack member: this term's force and d(w.F)/dx are added onto them."""
+        ps = self._thetas()
+        need = bool(want_theta) and len(ps) > 0
+        o = self._term(xyz)._eval(xyz.detach(), w=w.detach(), energy=False, grad=True, into=into, scale=-1.0, want_theta=need)
+        if not want_theta:
+            return o["grad"], o["hw"], None
+        if not ps:
+            return o["grad"], o["hw"], ([] if accum is None else None)
+        g = o["gtabw"]
+        if accum is None:
+            return o["grad"], o["hw"], [-g[a:b].reshape(p.shape) for p, (a, b) in zip(ps, self._select)]
+        jobs = ops.GradJobs()
+        for p, (a, b) in zip(ps, self._select):
+            if accum.off.get(id(p)) is not None:
+                jobs.axpy(accum.off[id(p)], g[a:b])
+        jobs.run(accum, alpha=-1.0, accumulate=True)
+        return o["grad"], o["hw"], None
 
 
 class Tersoff(_ManyBodyTerm):

@@ -17,6 +17,7 @@ torch.autograd.Function wrappers that own the differentiation contract
                                                                 the charges; `pot_scale` says which factor their kernel leaves out
       SWTerm                                                    Stillinger-Weber term, parameters: (epsilon, sigma, lam)
       EAMTerm                                                   Sutton-Chen term, parameters: (epsilon, a, c)
+      EAMTableTerm                                              tabulated embedded-atom term, parameters: the trainable node tables
       TersoffTerm                                               Tersoff bond-order term, parameters: (A, B, h)
       TersoffMultiTerm                                          the same for up to four species: (A [S,S], B [S,S], h [S])
     DihedralPhiFn, DihedralHistFn                               signed dihedral angles of every frame, their periodic histogram
@@ -881,6 +882,111 @@ class EAMTerm(SWTerm):
 
     def _eval(self, xyz, **kw):
         return eam_eval(self.ell, xyz, self.consts, self.theta, work=self.work, **kw)
+
+
+# ----------------------------------------------------------------------------- tabulated embedded-atom term (K27)
+EAM_TABLE_MAX_SPECIES = 4
+EAM_TABLE_NODES = (4, 4096)
+
+
+def eam_table_consts(n_species, n_r, n_rho, r_min, cutoff, rho_min, rho_max, pin_cutoff=True):
+    """MdgEAMTableConsts: the grids of the tabulated embedded-atom term -- n_r nodes on [r_min, cutoff] for phi and f, n_rho nodes
+    on [rho_min, rho_max] for F."""
+    S, n_r, n_rho = int(n_species), int(n_r), int(n_rho)
+    r_min, cutoff, rho_min, rho_max = float(r_min), float(cutoff), float(rho_min), float(rho_max)
+    if not 1 <= S <= EAM_TABLE_MAX_SPECIES:
+        raise ValueError("mdgrad_amd: the number of species must lie in [1, %d] (got %d)" % (EAM_TABLE_MAX_SPECIES, S))
+    lo, hi = EAM_TABLE_NODES
+    if not (lo <= n_r <= hi and lo <= n_rho <= hi):
+        raise ValueError("mdgrad_amd: the node counts must lie in [%d, %d] (got n_r = %d, n_rho = %d)" % (lo, hi, n_r, n_rho))
+    if not (r_min >= 0.0 and cutoff > r_min):
+        raise ValueError("mdgrad_amd: the r grid needs 0 <= r_min < cutoff (got %r, %r)" % (r_min, cutoff))
+    if not rho_max > rho_min:
+        raise ValueError("mdgrad_amd: the rho grid needs rho_min < rho_max (got %r, %r)" % (rho_min, rho_max))
+    k = _lib.MdgEAMTableConsts()
+    k.r_min, k.h_r, k.rc, k.rho_min, k.h_rho = r_min, (cutoff - r_min) / (n_r - 1), cutoff, rho_min, (rho_max - rho_min) / (n_rho - 1)
+    k.n_species, k.n_r, k.n_rho, k.pin_cutoff = S, n_r, n_rho, int(bool(pin_cutoff))
+    return k
+
+
+def eam_table_size(consts):
+    """The number of floats of the flat table image (pair, density, embed) on the grids of `consts`."""
+    return int(_lib.load().mdg_eam_table_size(consts.n_species, consts.n_r, consts.n_rho))
+
+
+def eam_table_fx_size(consts):
+    """The number of int64 words of the fixed-point scratch of the table gradient on the grids of `consts`."""
+    return int(_lib.load().mdg_eam_table_fx_size(consts.n_species, consts.n_r, consts.n_rho))
+
+
+def eam_table_eval(ell, xyz, types, consts, tables, w=None, energy=True, grad=True, into=None, scale=1.0, want_theta=False,
+                   work=None, fx=None):
+    """One call of mdg_eam_table_eval (density pass, force pass, and for the table gradient its prologue and finish kernels)
+    -> dict(energy, grad, hw, gtab, gtabw), argument for argument eam_eval with `types` (device int32 [N], values in
+    [0, n_species): not read here), `consts` (eam_table_consts) and `tables` (device float32, the flat node image in the order
+    pair, density, embed) in place of the constants and theta.  want_theta: without `w` gtab = dU/dtables, with `w` gtabw =
+    d(w.dU/dx)/dtables, flat in the layout of `tables`.  `work` [N, 4] and `fx` (int64 [eam_table_fx_size]): the scratch of the
+    density pass and of the fixed-point scatter, persistent buffers of the caller (a captured graph sees fixed addresses);
+    allocated here when None.  The list may have been searched with any radius >= cutoff (a skin)."""
+    lib = _lib.load()
+    N, dev = ell.n_atoms, xyz.device
+    n_tab = eam_table_size(consts)
+    require_gpu(types, "types", dtype=None)
+    if types.shape != (N,) or types.dtype != torch.int32 or not types.is_contiguous():
+        raise ValueError("mdgrad_amd: types must be a contiguous int32 [%d] tensor (got %s %s)" % (N, types.dtype, tuple(types.shape)))
+    require_gpu(tables, "tables")
+    if tables.shape != (n_tab,) or tables.dtype != torch.float32 or not tables.is_contiguous():
+        raise ValueError("mdgrad_amd: tables must be a contiguous float32 [%d] tensor (got %s)" % (n_tab, tuple(tables.shape)))
+    if work is None:
+        work = torch.empty(N, 4, device=dev)
+    else:
+        require_gpu(work, "work")
+        if work.shape != (N, 4) or not work.is_contiguous():
+            raise ValueError("mdgrad_amd: work must be a contiguous [%d, 4] tensor (got %s)" % (N, tuple(work.shape)))
+    if want_theta:
+        if fx is None:
+            fx = torch.empty(eam_table_fx_size(consts), dtype=torch.int64, device=dev)
+        else:
+            require_gpu(fx, "fx", dtype=None)
+            if fx.shape != (eam_table_fx_size(consts),) or fx.dtype != torch.int64 or not fx.is_contiguous():
+                raise ValueError("mdgrad_amd: fx must be a contiguous int64 [%d] tensor (got %s %s)"
+                                 % (eam_table_fx_size(consts), fx.dtype, tuple(fx.shape)))
+    xyz, w, e, g, hw, gtab, gtabw, acc = _eval_prologue(N, xyz, w, energy, grad, into, want_theta, (n_tab,))
+    partial = torch.empty(int(lib.mdg_eam_table_partial_size(N)), device=dev) if energy else None
+    check(lib.mdg_eam_table_eval(ptr(xyz), N, C.byref(ell.cell_struct), ptr(ell.col), ptr(ell.shift), ptr(ell.cnt), ell.max_nbr,
+                                 ptr(types), C.byref(consts), ptr(tables), ptr(w), ptr(e), ptr(g), ptr(hw), ptr(gtab), ptr(gtabw),
+                                 ptr(partial), ptr(work), ptr(fx) if want_theta else None, float(scale), _list_flags(acc, ell),
+                                 stream_ptr(dev)), "mdg_eam_table_eval")
+    return dict(energy=e, grad=g, hw=hw, gtab=gtab, gtabw=gtabw)
+
+
+class EAMTableTerm:
+    """The tabulated embedded-atom term (csrc/eam_table.hip) for TermEnergyFn: the list, the species of the atoms, the grids,
+    the device tables and the two scratch buffers, kept current by interface.EAM.  The parameter gradient comes back reduced
+    (flat, in the layout of the tables); `select` = the (start, stop) ranges of it that belong to the trainable tensors, in
+    their order, is what first_order / second_order return as "packed"."""
+
+    noun = "dU/dnodes of the tabulated embedded-atom term"
+
+    def __init__(self, ell, types, consts, tables, work=None, fx=None, select=()):
+        self.ell, self.types, self.consts, self.tables, self.work, self.fx = ell, types, consts, tables, work, fx
+        self.select = tuple(select)
+
+    def _eval(self, xyz, **kw):
+        return eam_table_eval(self.ell, xyz, self.types, self.consts, self.tables, work=self.work, fx=self.fx, **kw)
+
+    def _packed(self, flat):
+        if len(self.select) == 1:
+            return flat[self.select[0][0]:self.select[0][1]]
+        return torch.cat([flat[a:b] for a, b in self.select]) if self.select else flat[:0]
+
+    def first_order(self, xyz, energy):
+        o = self._eval(xyz, energy=energy, grad=True, want_theta=bool(self.select))
+        return o["energy"], o["grad"], self._packed(o["gtab"]) if self.select else xyz.new_zeros(0)
+
+    def second_order(self, xyz, w):
+        o = self._eval(xyz, w=w, energy=False, grad=False, want_theta=bool(self.select))
+        return o["hw"], self._packed(o["gtabw"]) if self.select else xyz.new_zeros(0)
 
 
 # ----------------------------------------------------------------------------- Tersoff bond-order term (K25)

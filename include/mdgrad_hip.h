@@ -1338,6 +1338,46 @@ int mdg_eam_table_eval(const float* pos, int n_atoms, const MdgCell* cell /*host
                        void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * K28  Stillinger-Weber potential for 1 <= S <= 4 species over the per-atom (ELL) list (the LAMMPS `pair_style sw`
+ *      convention; mdgrad_amd/interface.py StillingerWeberMulti, csrc/sw_multi.hip).  With a = types[i] (the centre),
+ *      b = types[j], c = types[k]:
+ *        U        = 1/2 sum_i sum_{j in row(i)} phi2_ab(r_ij) + sum_i sum_{j<k in row(i)} phi3_abc(r_ij, r_ik, cos theta_jik)
+ *        phi2_ab  = A_ab eps_ab [B_ab (sigma_ab/r)^p_ab - (sigma_ab/r)^q_ab] exp(sigma_ab / (r - a_ab sigma_ab))
+ *        g_ab     = exp(gamma_ab sigma_ab / (r - a_ab sigma_ab)),      both exactly 0 for r >= a_ab sigma_ab
+ *        phi3_abc = K_a{bc} (cos theta - cos0_abc)^2 g_ab(r_ij) g_ac(r_ik),   K_a{bc} = (lam_abc eps3_abc + lam_acb eps3_acb) / 2
+ *      `types`: device int32 [n_atoms], values in [0, S) (checked by the caller; the kernel clamps what it reads).
+ *      `tables`: device float [mdg_sw_multi_table_size(S)] = 12 S S + 4 S S S derived constants,
+ *        pair entry    tables[12 (a S + b) ...]                 = eps, sigma, a sigma, gamma sigma, gamma, A, B, p, q, a, A eps, 0
+ *                                                                 (row = centre, column = end; (a, b) and (b, a) are separate
+ *                                                                 entries and may differ; p, q integers, 0 <= q < p <= 12)
+ *        triplet entry tables[12 S S + 4 ((a S + b) S + c) ...] = K_a{bc}, cos0_abc, w_abc, 0
+ *                                                                 (K and cos0 symmetric in b, c; w_abc = eps3_abc / 2, eps3_abb
+ *                                                                 for b = c: d K_a{bc} / d lam_abc)
+ *      The caller validates the entries (mdgrad_amd/ops.py sw_multi_tables); being device data they are not read here.  The
+ *      list may have been searched with any radius >= max_ab a_ab sigma_ab: every entry is tested against the support of its
+ *      own pair entry.  With asymmetric pair tables the force of a pair is the derivative of (phi2_ab + phi2_ba) / 2.
+ *   mdg_sw_multi_eval  one launch, laid out like mdg_sw_eval (K23): the same list, `accumulate` bits, out_scale and the outputs
+ *     energy, grad, hw; mdg_sw_multi_partial_size(n_atoms) floats of `partial`, required for energy.  The per-atom parameter
+ *     outputs are
+ *       pth [n_atoms, 2 S S + S S S]  row i = d u_i / d(eps [S, S], sigma [S, S], lam [S, S, S]), flattened in that order, of
+ *                                     u_i = 1/2 sum_j phi2_ab + the triplets centred on i: it depends on eps[a, :],
+ *                                     sigma[a, :], lam[a, :, :] only, every other word of the row is written as 0, and
+ *                                     lam[a, b, c], lam[a, c, b] hold w_abc, w_acb times the sum of their unordered class, so
+ *                                     the column sums over the atoms (one GRAD_COLSUM job of mdg_grad_jobs) are
+ *                                     dU/d(eps, sigma, lam)
+ *       pthw, the same shape          (w . grad_x) of the same (the column sums are d(w.dU/dx)/d(eps, sigma, lam))
+ *     n_species outside [1, 4], null types or tables: MDG_EINVAL.  No atomics: bitwise reproducible; the value parts of a
+ *     launch with w equal those of a launch without, bit for bit.
+ *   mdg_sw_multi_table_size returns 0 for n_species outside [1, 4].
+ */
+int64_t mdg_sw_multi_partial_size(int n_atoms);
+int64_t mdg_sw_multi_table_size(int n_species);
+int mdg_sw_multi_eval(const float* pos, int n_atoms, const MdgCell* cell /*host*/, const int32_t* col, const int32_t* shift,
+                      const int32_t* cnt, int max_nbr, const int32_t* types, int n_species, const float* tables /*device*/,
+                      const float* w, float* energy, float* grad, float* hw, float* pth, float* pthw, float* partial,
+                      float out_scale, int accumulate, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * f4  bonded terms over a static topology table (csrc/bonded.hip).
  * Replaces torchmd/interface.py:447-455 (BondPotentials.forward: harmonic in the SQUARED bond length,
  * 1/2 k (|b|^2 - ro)^2) and :496-508 (AnglePotentials.forward: 1/2 k (theta - theta0)^2 over triples (i, j, k) centred on

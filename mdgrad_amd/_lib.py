@@ -316,6 +316,10 @@ _SIGNATURES = {
     "mdg_tersoff_multi_table_size": (C.c_int64, [C.c_int]),
     "mdg_tersoff_multi_eval": (C.c_int, [P, C.c_int, C.POINTER(MdgCell), P, P, P, C.c_int, P, C.c_int, P, P,
                                          P, P, P, P, P, P, P, C.c_float, C.c_int, P]),
+    "mdg_sw_multi_partial_size": (C.c_int64, [C.c_int]),
+    "mdg_sw_multi_table_size": (C.c_int64, [C.c_int]),
+    "mdg_sw_multi_eval": (C.c_int, [P, C.c_int, C.POINTER(MdgCell), P, P, P, C.c_int, P, C.c_int, P, P,
+                                    P, P, P, P, P, P, C.c_float, C.c_int, P]),
     "mdg_eam_table_partial_size": (C.c_int64, [C.c_int]),
     "mdg_eam_table_size": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "mdg_eam_table_fx_size": (C.c_int64, [C.c_int, C.c_int, C.c_int]),

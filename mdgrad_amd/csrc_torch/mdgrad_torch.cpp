@@ -24,6 +24,7 @@
 //   eam_eval         K24  interface.py SuttonChen           -> mdg_eam_eval
 //   tersoff_eval     K25  interface.py Tersoff              -> mdg_tersoff_eval
 //   tersoff_multi_eval  K26  interface.py TersoffMulti      -> mdg_tersoff_multi_eval
+//   sw_multi_eval    K28  interface.py StillingerWeberMulti -> mdg_sw_multi_eval
 //   eam_table_eval   K27  interface.py EAM                  -> mdg_eam_table_eval
 //   dihedral_phi_fwd/_bwd, dihedral_hist_fwd/_bwd  K19  observable.py Dihedrals / dihedral_distribution -> mdg_dihedral_phi_* / _hist_*
 //   edge_geom(+_bwd) schnet.py:142                          -> mdg_edge_geom / mdg_edge_geom_bwd
@@ -952,6 +953,43 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> tersoff_multi_eval(const Tens
     return {U, g, hw, pth, pthw};
 }
 
+// ------------------------------------------------------------------------------------------------ K28
+// types: int32 [N] with values in [0, n_species) (read back once to check them); tables: the derived constants of
+// mdg_sw_multi_table_size(n_species) floats (mdgrad_amd/ops.py sw_multi_tables).  (U [1] or [0], dU/dx [N,3], H w [N,3] or
+// [0], pth [N, 2 S S + S S S] or [0], pthw likewise or [0]); want_theta: pth without w, pthw with it.
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> sw_multi_eval(const Tensor& pos, at::ArrayRef<double> cell, const Tensor& col,
+                                                                 const Tensor& shift, const Tensor& cnt, const Tensor& types,
+                                                                 int64_t n_species, const Tensor& tables, const OptTensor& w,
+                                                                 bool want_energy, bool want_theta) {
+    check_f32(pos, "pos");
+    TORCH_CHECK(pos.dim() == 2 && pos.size(1) == 3 && pos.size(0) > 0 && pos.size(0) <= INT32_MAX, "mdgrad: pos must be [N,3]");
+    TORCH_CHECK(n_species >= 1 && n_species <= 4, "mdgrad: n_species must lie in [1, 4] (got ", n_species, ")");
+    const MdgCell c = make_cell(cell);
+    const EllRef e = ell_of(pos, col, shift, cnt);
+    check_i32(types, "types"); same_device(pos, types, "types");
+    TORCH_CHECK(types.dim() == 1 && types.size(0) == pos.size(0), "mdgrad: types must hold one entry per atom");
+    TORCH_CHECK(types.min().item<int32_t>() >= 0 && types.max().item<int32_t>() < n_species,
+                "mdgrad: types must lie in [0, n_species)");
+    check_f32(tables, "tables"); same_device(pos, tables, "tables");
+    TORCH_CHECK(tables.numel() == mdg_sw_multi_table_size((int)n_species),
+                "mdgrad: tables must hold 12 S S + 4 S S S floats for S = n_species");
+    const float* wp = fptr(w, "w");
+    if (wp) { same_device(pos, *w, "w"); TORCH_CHECK(w->sizes() == pos.sizes(), "mdgrad: w must have the shape of pos"); }
+    const int n = (int)pos.size(0);
+    const int64_t P = 2 * n_species * n_species + n_species * n_species * n_species;
+    const auto o = pos.options();
+    Tensor U = at::empty({want_energy ? 1 : 0}, o), g = at::empty_like(pos);
+    Tensor hw = wp ? at::empty_like(pos) : at::empty({0}, o);
+    Tensor pth = (want_theta && !wp) ? at::empty({(int64_t)n, P}, o) : at::empty({0}, o);
+    Tensor pthw = (want_theta && wp) ? at::empty({(int64_t)n, P}, o) : at::empty({0}, o);
+    Tensor partial = at::empty({mdg_sw_multi_partial_size(n)}, o);
+    ok(mdg_sw_multi_eval(fptr(pos), n, &c, e.col, e.shift, e.cnt, e.max_nbr, types.data_ptr<int32_t>(), (int)n_species,
+                         fptr(tables), wp, want_energy ? mptr(U) : nullptr, mptr(g), wp ? mptr(hw) : nullptr,
+                         (want_theta && !wp) ? mptr(pth) : nullptr, (want_theta && wp) ? mptr(pthw) : nullptr, mptr(partial),
+                         1.f, 0, stream_of(pos)));
+    return {U, g, hw, pth, pthw};
+}
+
 // ------------------------------------------------------------------------------------------------ K27
 // types: int32 [N] with values in [0, n_species) (read back once to check them); consts = (n_species, n_r, n_rho, r_min, rc,
 // rho_min, rho_max, pin_cutoff) of the grids; tables: the flat node image (pair, density, embed) of mdg_eam_table_size floats.
@@ -1087,6 +1125,8 @@ TORCH_LIBRARY(mdgrad, m) {
           "bool want_energy, bool want_theta) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("tersoff_multi_eval(Tensor pos, float[] cell, Tensor col, Tensor shift, Tensor cnt, Tensor types, int n_species, "
           "Tensor tables, Tensor? w, bool want_energy, bool want_theta) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
+    m.def("sw_multi_eval(Tensor pos, float[] cell, Tensor col, Tensor shift, Tensor cnt, Tensor types, int n_species, "
+          "Tensor tables, Tensor? w, bool want_energy, bool want_theta) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("eam_table_eval(Tensor pos, float[] cell, Tensor col, Tensor shift, Tensor cnt, Tensor types, float[] consts, "
           "Tensor tables, Tensor? w, bool want_energy, bool want_theta) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("ewald_eval(Tensor pos, int n_rep, float[] cell, Tensor q, Tensor kvec, Tensor coef, Tensor? w, bool want_energy, "
@@ -1136,6 +1176,7 @@ TORCH_LIBRARY_IMPL(mdgrad, CUDA, m) {      // (the HIP backend registers under t
     m.impl("eam_eval", eam_eval);
     m.impl("tersoff_eval", tersoff_eval);
     m.impl("tersoff_multi_eval", tersoff_multi_eval);
+    m.impl("sw_multi_eval", sw_multi_eval);
     m.impl("eam_table_eval", eam_table_eval);
     m.impl("ewald_eval", ewald_eval);
     m.impl("ewald_excl_eval", ewald_excl_eval);

@@ -1,6 +1,6 @@
 """Energy calculators with the reference's interface (torchmd/interface.py):
 GeneralInteraction :33-57, PairPotentials :217-300, Electrostatics :303-361 (as CoulombPotentials), Stack :364-403;
-StillingerWeber (three-body), SuttonChen (embedded-atom), EAM (tabulated embedded-atom, alloys), Tersoff (bond-order) and TersoffMulti (the same for several species) -- none of them has a counterpart in the reference
+StillingerWeber (three-body), StillingerWeberMulti (the same for several species), SuttonChen (embedded-atom), EAM (tabulated embedded-atom, alloys), Tersoff (bond-order) and TersoffMulti (the same for several species) -- none of them has a counterpart in the reference
 (GNNPotentials lives in mdgrad_amd.nn).  forward(xyz) -> energy; _reset_topology(xyz) rebuilds the neighbour list.
 """
 import inspect
@@ -1023,7 +1023,7 @@ class StillingerWeber(_ManyBodyTerm):
 
     `epsilon`, `sigma` and `lam` are the parameters when trainable, otherwise buffers; a, gamma, cos0, A, B and the integer
     exponents 0 <= q < p <= 12 are constants.  Not covered: `index_tuple`, `ex_pairs` (both rejected) and per-type or
-    multi-species parameters (one (epsilon, sigma, lam) for all atoms).
+    multi-species parameters (one (epsilon, sigma, lam) for all atoms): those are StillingerWeberMulti's.
 
     A trainable sigma moves the cutoff a sigma.  The kernel always applies r < a sigma with the live sigma, so a list
     searched with a larger radius is exact; the list is searched with `self.cutoff`, which is kept while
@@ -1173,6 +1173,329 @@ class StillingerWeber(_ManyBodyTerm):
 
     def _term(self, xyz):
         return ops.SWTerm(self._current_list(xyz), self._consts, self._theta())
+
+
+class StillingerWeberMulti(_ManyBodyTerm):
+    """Stillinger-Weber potential for 1 <= S <= 4 species in the convention of LAMMPS `pair_style sw`: compounds and mixtures
+    (CdTe, GaN, SiGe, mW water with a solute) from tables per ordered pair and per triplet of species.  Atom i has the species
+    t_i = `types`[i]; with a = t_i (the centre), b = t_j, c = t_k
+
+        U      = 1/2 sum_i sum_{j != i} phi2_ab(r_ij) + sum_i sum_{j<k in row(i)} phi3_abc(r_ij, r_ik, cos theta_jik)
+        phi2_ab  = A_ab eps_ab [B_ab (sigma_ab/r)^p_ab - (sigma_ab/r)^q_ab] exp(sigma_ab / (r - a_ab sigma_ab))   r < a_ab sigma_ab, else 0
+        g_ab     = exp(gamma_ab sigma_ab / (r - a_ab sigma_ab))                                                   r < a_ab sigma_ab, else 0
+        phi3_abc = K_a{bc} (cos theta - cos0_abc)^2 g_ab(r_ij) g_ac(r_ik),    K_a{bc} = (lam_abc eps3_abc + lam_acb eps3_acb) / 2
+
+    The pair constants (epsilon, sigma, a, gamma, A, B, p, q) are [S, S] tables, row = the species of the centre, column =
+    the species of the end (the convention of TersoffMulti); a LAMMPS file supplies them from its (a, b, b) lines.  (lam,
+    epsilon3, cos0) are [S, S, S] tables (centre, end, end) from the (a, b, c) lines.  The two ends of a triplet are unordered:
+    cos0 must be symmetric in them (anything else is rejected) and the strength enters through the symmetrised K, so the
+    energy is a function of every table entry; dU/dlam[a, b, c] and dU/dlam[a, c, b] each receive half of their class's
+    derivative, times their own epsilon3.  The pair tables need not be symmetric: U2 = 1/2 sum_i sum_j phi2_{t_i t_j}, so the
+    force of a pair is the derivative of (phi2_ab + phi2_ba) / 2.  [a, b] and [b, a] are separate entries that the
+    constructors fill equally: a fit that wants them tied ties their gradients (sums the two and writes the sum to both).
+
+    StillingerWeberMulti(system, types, species) takes S one-species sets (dicts with epsilon, sigma, lam and optionally a,
+    gamma, cos0, A, B, p, q; PUBLISHED holds silicon and mW) and mixes them (`mix`) by this rule, which is a definition of
+    this class and not a claim about any published compound set: sigma_ab, a_ab, gamma_ab are arithmetic means, epsilon_ab
+    = sqrt(epsilon_a epsilon_b); A, B, p, q, cos0 are those of the centre; with lam_ab = sqrt(lam_a lam_b),
+    lam_abc = sqrt(lam_ab lam_ac) and epsilon3_abc = sqrt(epsilon_ab epsilon_ac), so that lam_abc epsilon3_abc =
+    sqrt(lam_ab epsilon_ab lam_ac epsilon_ac).  `from_tables` takes the tables themselves and `from_sw_file` reads a LAMMPS
+    `.sw` file, which is how published compound sets reach the class.  S = 1 with epsilon3 = epsilon is StillingerWeber.
+    `types` holds one entry per atom of a replica, in [0, S); every replica of System.replicate has the same species.
+
+    `epsilon` [S, S], `sigma` [S, S] and `lam` [S, S, S] are float32 parameters when trainable, otherwise buffers; everything
+    else is constant.  The cutoff is max_ab a_ab sigma_ab; a trainable sigma moves it, by the rule and the design constants of
+    StillingerWeber: the list is searched with `cutoff_reset` times it and kept while it stays within `cutoff_keep` (one host
+    read per change of sigma, never inside a HIP-graph capture; `static_version()` changes with the cutoff).  The kernel
+    applies each entry's own support r < a_ab sigma_ab with the live sigma, so a list searched with a larger radius or a skin
+    is exact.  Not covered (ValueError where it can be asked for): `index_tuple`, `ex_pairs`, S > 4, non-integer exponents,
+    the pressure of the term, the fused trajectory kernels (a Stack holding the term stays on force / force_vjp).
+
+    forward(xyz) is differentiable twice in xyz and once in (epsilon, sigma, lam) on the HIP kernel (ops.SWMultiTerm,
+    csrc/sw_multi.hip: csrc/sw.hip with every constant looked up by species in a device table); force / force_vjp serve the
+    analytic adjoint and HIP-graph replay, also while the parameters require grad.  float64 or host positions take the torch
+    restatement `_torch_energy`."""
+
+    MAX_SPECIES = ops.SW_MULTI_MAX_SPECIES
+    cutoff_reset, cutoff_keep = StillingerWeber.cutoff_reset, StillingerWeber.cutoff_keep
+    DEFAULTS = dict(a=1.80, gamma=1.20, cos0=-1.0 / 3.0, A=7.049556277, B=0.6022245584, p=4, q=0)   # StillingerWeber's
+    PUBLISHED = dict(silicon=dict(epsilon=2.1683, sigma=2.0951, lam=21.0),
+                     mW=dict(epsilon=6.189 * StillingerWeber.KCAL_PER_MOL, sigma=2.3925, lam=23.15))
+
+    def __init__(self, system, types, species, trainable=True, index_tuple=None, ex_pairs=None):
+        pair, triplet = self.mix(species)
+        self._setup(system, types, pair, triplet, trainable, index_tuple, ex_pairs)
+
+    @classmethod
+    def from_tables(cls, system, types, pair, triplet, trainable=True, index_tuple=None, ex_pairs=None):
+        """The term from its tables: pair = dict of [S, S] arrays epsilon, sigma, a, gamma, A, B, p, q (row = centre species,
+        column = end species), triplet = dict of [S, S, S] arrays lam, epsilon3, cos0 (centre, end, end)."""
+        self = cls.__new__(cls)
+        self._setup(system, types, pair, triplet, trainable, index_tuple, ex_pairs)
+        return self
+
+    @classmethod
+    def mix(cls, species):
+        """(pair, triplet) tables of S one-species sets under the mixing rule of the class docstring, in float64."""
+        species = list(species)
+        S = len(species)
+        if not 1 <= S <= cls.MAX_SPECIES:
+            raise ValueError("StillingerWeberMulti: species must hold 1 to %d parameter sets (got %d)" % (cls.MAX_SPECIES, S))
+        for a, p in enumerate(species):
+            missing = [k for k in ("epsilon", "sigma", "lam") if k not in p]
+            if missing:
+                raise ValueError("StillingerWeberMulti: species[%d] lacks %s" % (a, ", ".join(missing)))
+            unknown = [k for k in p if k not in ("epsilon", "sigma", "lam") and k not in cls.DEFAULTS]
+            if unknown:
+                raise ValueError("StillingerWeberMulti: species[%d] has unknown keys %s" % (a, ", ".join(unknown)))
+        col = lambda k: np.array([float(p.get(k, cls.DEFAULTS.get(k))) for p in species], dtype=np.float64)
+        if not ((col("epsilon") > 0.0) & (col("lam") >= 0.0)).all():
+            raise ValueError("StillingerWeberMulti: every species needs epsilon > 0 and lam >= 0")
+        geo = lambda v: np.sqrt(np.outer(v, v))
+        mean = lambda v: 0.5 * (v[:, None] + v[None, :])
+        row = lambda v: np.repeat(v[:, None], S, axis=1)                      # the centre's value
+        pair = dict(epsilon=geo(col("epsilon")), sigma=mean(col("sigma")), a=mean(col("a")), gamma=mean(col("gamma")),
+                    A=row(col("A")), B=row(col("B")), p=row(col("p")), q=row(col("q")))
+        lam2 = geo(col("lam"))
+        triplet = dict(lam=np.sqrt(lam2[:, :, None] * lam2[:, None, :]),
+                       epsilon3=np.sqrt(pair["epsilon"][:, :, None] * pair["epsilon"][:, None, :]),
+                       cos0=np.repeat(np.repeat(col("cos0")[:, None, None], S, axis=1), S, axis=2))
+        return pair, triplet
+
+    @staticmethod
+    def read_sw_file(path, elements):
+        """(pair, triplet) tables of a LAMMPS `.sw` file for the species `elements` (the element name of each species index).
+        `#` starts a comment; an entry is 14 whitespace-separated tokens `e1 e2 e3 epsilon sigma a lambda gamma costheta0 A B
+        p q tol` (e1 = the centre) and may continue over several lines.  Entries that name an element not in `elements` are
+        skipped.  The pair tables come from the (a, b, b) entries, lam, epsilon3 (the entry's epsilon) and cos0 from the
+        (a, b, c) entries; `tol` is ignored (this class has no tolerance cutoff for the exponential).  ValueError: a missing
+        or repeated entry (naming the triplet), a non-integer exponent, tokens that do not form whole entries."""
+        elements = [str(e) for e in elements]
+        S = len(elements)
+        if not 1 <= S <= StillingerWeberMulti.MAX_SPECIES or len(set(elements)) != S:
+            raise ValueError("StillingerWeberMulti: elements must hold 1 to %d distinct names (got %r)"
+                             % (StillingerWeberMulti.MAX_SPECIES, elements))
+        with open(path) as f:
+            tokens = [t for line in f for t in line.split("#", 1)[0].split()]
+        if len(tokens) % 14:
+            raise ValueError("StillingerWeberMulti: %s holds %d tokens, not a whole number of 14-token entries" % (path, len(tokens)))
+        index = {e: k for k, e in enumerate(elements)}
+        seen = {}
+        for n in range(0, len(tokens), 14):
+            names, rest = tokens[n:n + 3], tokens[n + 3:n + 14]
+            try:
+                vals = [float(v) for v in rest]
+            except ValueError:
+                raise ValueError("StillingerWeberMulti: %s: entry %s has a non-numeric field (%r)" % (path, " ".join(names), rest))
+            if any(e not in index for e in names):
+                continue
+            key = tuple(index[e] for e in names)
+            if key in seen:
+                raise ValueError("StillingerWeberMulti: %s: the triplet %s appears twice" % (path, " ".join(names)))
+            if vals[8] != int(vals[8]) or vals[9] != int(vals[9]):
+                raise ValueError("StillingerWeberMulti: %s: the triplet %s has non-integer exponents p = %r, q = %r (not covered)"
+                                 % (path, " ".join(names), vals[8], vals[9]))
+            seen[key] = vals
+        pair = {k: np.zeros((S, S)) for k in ops.SW_MULTI_PAIR}
+        triplet = {k: np.zeros((S, S, S)) for k in ops.SW_MULTI_TRIPLET}
+        for a in range(S):
+            for b in range(S):
+                for c in range(S):
+                    if (a, b, c) not in seen:
+                        raise ValueError("StillingerWeberMulti: %s has no entry for the triplet %s %s %s"
+                                         % (path, elements[a], elements[b], elements[c]))
+                    eps, sig, aa, lam, gam, cos0, A, B, p, q, _tol = seen[(a, b, c)]
+                    triplet["lam"][a, b, c], triplet["epsilon3"][a, b, c], triplet["cos0"][a, b, c] = lam, eps, cos0
+                    if b == c:
+                        for k, v in zip(ops.SW_MULTI_PAIR, (eps, sig, aa, gam, A, B, p, q)):
+                            pair[k][a, b] = v
+        return pair, triplet
+
+    @classmethod
+    def from_sw_file(cls, system, types, path, elements, trainable=True, index_tuple=None, ex_pairs=None):
+        """The term from a LAMMPS `.sw` file (`read_sw_file`): `elements` lists the element name of each species index."""
+        pair, triplet = cls.read_sw_file(path, elements)
+        return cls.from_tables(system, types, pair, triplet, trainable=trainable, index_tuple=index_tuple, ex_pairs=ex_pairs)
+
+    def _setup(self, system, types, pair, triplet, trainable, index_tuple, ex_pairs):
+        _ListTerm.__init__(self, system)
+        if index_tuple is not None or ex_pairs is not None:
+            raise ValueError("StillingerWeberMulti: index_tuple and ex_pairs are not supported (every pair interacts)")
+        for name, keys, given in (("pair", ops.SW_MULTI_PAIR, pair), ("triplet", ops.SW_MULTI_TRIPLET, triplet)):
+            missing = [k for k in keys if k not in given]
+            if missing:
+                raise ValueError("StillingerWeberMulti: %s lacks %s" % (name, ", ".join(missing)))
+        S = int(np.asarray(pair["epsilon"]).shape[0]) if np.asarray(pair["epsilon"]).ndim == 2 else -1
+        if S > self.MAX_SPECIES:
+            raise ValueError("StillingerWeberMulti: S = %d species; at most %d are supported" % (S, self.MAX_SPECIES))
+        try:
+            self._image = ops.sw_multi_tables(pair, triplet)                   # (validates every entry)
+        except ValueError as e:
+            raise ValueError(str(e).replace("mdgrad_amd:", "StillingerWeberMulti:")) from None
+        self.n_species = S
+        self._pair = {k: np.asarray(pair[k], dtype=np.float64).reshape(S, S) for k in ops.SW_MULTI_PAIR}
+        self._triplet = {k: np.asarray(triplet[k], dtype=np.float64).reshape(S, S, S) for k in ops.SW_MULTI_TRIPLET}
+        ty = np.asarray(torch.as_tensor(types).detach().cpu().numpy()).reshape(-1)
+        if ty.shape[0] != self._group:
+            raise ValueError("StillingerWeberMulti: types must hold one entry per atom of a replica (%d), got %d"
+                             % (self._group, ty.shape[0]))
+        if not np.issubdtype(ty.dtype, np.integer) or ty.min() < 0 or ty.max() >= S:
+            raise ValueError("StillingerWeberMulti: types must be integers in [0, %d)" % S)
+        cell = np.asarray(system.get_cell(), dtype=np.float64)
+        cell = np.diag(cell) if cell.ndim == 1 else cell
+        vol = abs(float(np.linalg.det(cell)))
+        self._half_height = 0.5 * min(vol / float(np.linalg.norm(np.cross(cell[(d + 1) % 3], cell[(d + 2) % 3]))) for d in range(3))
+        rc = float((self._pair["a"] * self._pair["sigma"]).max())
+        if rc > self._half_height:
+            raise ValueError("StillingerWeberMulti: max a * sigma = %g exceeds half the shortest cell height (%g)"
+                             % (rc, self._half_height))
+        for name in ("epsilon", "sigma", "lam"):
+            t = torch.tensor((self._triplet if name == "lam" else self._pair)[name], dtype=torch.float32, device=self.device)
+            if trainable:
+                setattr(self, name, torch.nn.Parameter(t))
+            else:
+                self.register_buffer(name, t)
+        self.index_tuple, self.ex_pairs, self._mask = None, None, None
+        self._n_rep = system.get_number_of_atoms() // self._group
+        self.types = torch.as_tensor(np.tile(ty.astype(np.int32), self._n_rep), device=self.device)   # one entry per atom
+        self._ell = None
+        self._template = torch.as_tensor(self._image, device=self.device)
+        self._a32 = torch.tensor(self._pair["a"], dtype=torch.float32, device=self.device)
+        self._e3 = torch.tensor(self._triplet["epsilon3"], dtype=torch.float32, device=self.device)
+        self._table_mirror = _DeviceMirror(self._thetas, pack=self._pack_tables, numel=int(self._image.shape[0]))
+        self.cutoff, self._cut_ver, self._list_ver, self._sig_key = None, 0, -1, None
+        self._sync_cutoff()
+        if torch.device(self.device).type == "cuda":
+            self._reset_topology(torch.Tensor(system.get_positions()).to(system.device))
+            self._tables()
+
+    # -- the cutoff the list is searched with: StillingerWeber's rule on max_ab a_ab sigma_ab ------------------------
+    def _sync_cutoff(self):
+        """Apply the cutoff rule to the current sigma; True when the cutoff was reset.  Inside a capture, or while sigma's
+        version counter has not moved, nothing is read."""
+        s = self.sigma
+        if s.is_cuda and torch.cuda.is_current_stream_capturing():
+            return False
+        key = (s.data_ptr(), s._version)
+        if key == self._sig_key:
+            return False
+        self._sig_key = key
+        sd = s.detach()
+        rc, smin = torch.stack([(self._a32.to(sd.device) * sd).max(), sd.min()]).tolist()   # (one host read per change of sigma)
+        if not smin > 0.0:
+            raise ValueError("StillingerWeberMulti: every sigma must stay positive (got %g)" % smin)
+        if rc > self._half_height:
+            raise ValueError("StillingerWeberMulti: max a * sigma = %g exceeds half the shortest cell height (%g)"
+                             % (rc, self._half_height))
+        if self.cutoff is not None and rc <= self.cutoff <= self.cutoff_keep * rc:
+            return False
+        self.cutoff = self.cutoff_reset * rc
+        self._cut_ver += 1
+        return True
+
+    def static_version(self):
+        return (super().static_version(), self._cut_ver)
+
+    def _reset_topology(self, xyz, _cache=None):
+        self._sync_cutoff()
+        super()._reset_topology(xyz, _cache)         # (a Stack member's Verlet list serves: the support test is per entry)
+        self._list_ver = self._cut_ver
+
+    def set_static_topology(self, on=True):
+        self._sync_cutoff()
+        super().set_static_topology(on)
+
+    def _current_list(self, xyz):
+        """The list to evaluate on: rebuilt here when sigma has moved the cutoff since the last search (never inside a
+        capture, where sigma is not read)."""
+        self._sync_cutoff()
+        if self._list_ver != self._cut_ver:
+            self._reset_topology(xyz.detach())
+        return self._ell
+
+    # -- the device table the kernel reads: the constants plus what follows from the current (epsilon, sigma, lam) -----
+    def _thetas(self):
+        return self.epsilon, self.sigma, self.lam
+
+    def _pack_tables(self, ps, out=None):
+        """The table image (ops.sw_multi_tables) with the current epsilon, sigma, lam and the entries derived from them
+        (a sigma, gamma sigma, A epsilon, the symmetrised K), by device ops only."""
+        S = self.n_species
+        eps, sig, lam = (p.detach().to(torch.float32) for p in ps)
+        tmpl = self._template.to(eps.device)
+        out = tmpl.clone() if out is None else out.copy_(tmpl)
+        n2 = ops.SW_MULTI_PAIR_FLOATS * S * S
+        pair, cpair = out[:n2].view(S * S, ops.SW_MULTI_PAIR_FLOATS), tmpl[:n2].view(S * S, ops.SW_MULTI_PAIR_FLOATS)
+        eps, sig = eps.reshape(-1), sig.reshape(-1)
+        pair[:, 0].copy_(eps)
+        pair[:, 1].copy_(sig)
+        pair[:, 2].copy_(cpair[:, 9] * sig)
+        pair[:, 3].copy_(cpair[:, 4] * sig)
+        pair[:, 10].copy_(cpair[:, 5] * eps)
+        le = lam * self._e3.to(eps.device)
+        out[n2:].view(S, S, S, ops.SW_MULTI_TRIPLET_FLOATS)[..., 0].copy_(0.5 * (le + le.transpose(1, 2)))
+        return out
+
+    def _tables(self):
+        """The derived constants as the kernel reads them: a device mirror (_DeviceMirror) rewritten when epsilon, sigma or
+        lam changed, so that the captured steps carry no host value of a parameter."""
+        return self._table_mirror.get()
+
+    def prepare_pass(self):
+        self._sync_cutoff()
+        if self._hip_ok():
+            self._tables()
+
+    # -- energy ----------------------------------------------------------------------------------------------------
+    def _torch_energy(self, xyz):
+        """The same energy in torch ops, in the dtype and on the device of xyz (differentiable by autograd in xyz and in
+        epsilon, sigma, lam): every pair as two directed bonds with the constants of (centre species, end species), grouped
+        by centre into a padded [N, K] table, then every triplet as two entries of one atom's row."""
+        const = lambda v: torch.as_tensor(v, dtype=xyz.dtype, device=xyz.device)
+        eps, sig, lam = (p.to(xyz) for p in (self.epsilon, self.sigma, self.lam))
+        a_t = const(self._pair["a"])
+        i, j, off = self._all_pairs(xyz, float((a_t * sig.detach()).max()))
+        if i.numel() == 0:
+            return xyz.sum() * 0.0
+        cell = self.cell.detach().to(xyz)
+        cell = torch.diag(cell) if cell.dim() == 1 else cell
+        dv = xyz[i] - xyz[j] - off.matmul(cell)
+        r = dv.pow(2).sum(-1).sqrt()
+        ty = self.types.to(xyz.device).long()
+        N = xyz.shape[0]
+        centre, end = torch.cat([i, j]), torch.cat([j, i])
+        u, r2 = torch.cat([-dv, dv]) / torch.cat([r, r])[:, None], torch.cat([r, r])
+        ta, tb = ty[centre], ty[end]
+        sg = sig[ta, tb]
+        rc = a_t[ta, tb] * sg
+        inside = r2 < rc
+        rs = torch.where(inside, r2, 0.5 * rc.detach())                  # (a harmless r outside the support: no 1/0, no nan)
+        per = lambda name: const(self._pair[name])[ta, tb]
+        sr = sg / rs
+        phi2 = per("A") * eps[ta, tb] * (per("B") * sr ** per("p") - sr ** per("q")) * torch.exp(sg / (rs - rc))
+        U2 = 0.5 * torch.where(inside, phi2, torch.zeros_like(phi2)).sum()
+        g = torch.where(inside, torch.exp(per("gamma") * sg / (rs - rc)), torch.zeros_like(rs))
+        order = torch.argsort(centre, stable=True)
+        centre, u, g, tb = centre[order], u[order], g[order], tb[order]
+        cnt = torch.bincount(centre, minlength=N)
+        K = int(cnt.max())
+        if K < 2:
+            return U2
+        start = torch.cumsum(cnt, 0) - cnt
+        slot = torch.arange(centre.numel(), device=xyz.device) - start[centre]
+        Uv = xyz.new_zeros(N, K, 3).index_put((centre, slot), u)
+        G = xyz.new_zeros(N, K).index_put((centre, slot), g)                # (padding: g = 0, no contribution)
+        Tb = torch.zeros(N, K, dtype=torch.long, device=xyz.device).index_put((centre, slot), tb)
+        t = torch.triu_indices(K, K, offset=1, device=xyz.device)
+        cth = (Uv[:, t[0]] * Uv[:, t[1]]).sum(-1)
+        ca, cb, cc = ty[:, None].expand(N, t.shape[1]), Tb[:, t[0]], Tb[:, t[1]]
+        le = lam * const(self._triplet["epsilon3"])
+        Kt = 0.5 * (le[ca, cb, cc] + le[ca, cc, cb])
+        phi3 = Kt * (cth - const(self._triplet["cos0"])[ca, cb, cc]) ** 2 * G[:, t[0]] * G[:, t[1]]
+        return U2 + phi3.sum()
+
+    def _term(self, xyz):
+        return ops.SWMultiTerm(self._current_list(xyz), self.types, self.n_species, self._tables())
 
 
 class SuttonChen(_ManyBodyTerm):

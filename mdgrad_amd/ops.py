@@ -16,6 +16,7 @@ torch.autograd.Function wrappers that own the differentiation contract
                                                                 sum, erf correction of excluded pairs) on _ChargeTerm, parameters:
                                                                 the charges; `pot_scale` says which factor their kernel leaves out
       SWTerm                                                    Stillinger-Weber term, parameters: (epsilon, sigma, lam)
+      SWMultiTerm                                               the same for up to four species: (epsilon [S,S], sigma [S,S], lam [S,S,S])
       EAMTerm                                                   Sutton-Chen term, parameters: (epsilon, a, c)
       EAMTableTerm                                              tabulated embedded-atom term, parameters: the trainable node tables
       TersoffTerm                                               Tersoff bond-order term, parameters: (A, B, h)
@@ -791,7 +792,8 @@ class _FlatOut:
 
 def theta_sum(per_atom, alpha=1.0):
     """[P] = alpha * the sums over the atoms of the per-atom parameter terms [N, P] of sw_eval, eam_eval, tersoff_eval (P = 3)
-    or tersoff_multi_eval (P = 2 S S + S, in (A, B, h) order), in the fixed order of mdg_grad_jobs."""
+    or tersoff_multi_eval (P = 2 S S + S, in (A, B, h) order) or sw_multi_eval (P = 2 S S + S S S, in (epsilon, sigma, lam)
+    order), in the fixed order of mdg_grad_jobs."""
     out = _FlatOut(per_atom.shape[1], per_atom.device)
     jobs = GradJobs()
     jobs.colsum(0, per_atom)
@@ -1147,6 +1149,113 @@ class TersoffMultiTerm(SWTerm):
 
     def _eval(self, xyz, **kw):
         return tersoff_multi_eval(self.ell, xyz, self.types, self.n_species, self.tables, work=self.work, **kw)
+
+
+# ----------------------------------------------------------------------------- multi-species Stillinger-Weber term (K28)
+SW_MULTI_MAX_SPECIES = 4
+SW_MULTI_PAIR = ("epsilon", "sigma", "a", "gamma", "A", "B", "p", "q")
+SW_MULTI_TRIPLET = ("lam", "epsilon3", "cos0")
+SW_MULTI_PAIR_FLOATS, SW_MULTI_TRIPLET_FLOATS = 12, 4
+
+
+def sw_multi_tables(pair, triplet):
+    """The table image mdg_sw_multi_eval reads, as a host float32 array of 12 S S + 4 S S S derived constants, from
+    pair = dict of [S, S] arrays epsilon, sigma, a, gamma, A, B, p, q (row = centre species, column = end species) and
+    triplet = dict of [S, S, S] arrays lam, epsilon3, cos0 (centre, end, end):
+        pair entry    out[12 (a S + b) ...]                 = epsilon, sigma, a sigma, gamma sigma, gamma, A, B, p, q, a, A epsilon, 0
+        triplet entry out[12 S S + 4 ((a S + b) S + c) ...] = K_a{bc}, cos0_abc, w_abc, 0
+    with K_a{bc} = (lam_abc epsilon3_abc + lam_acb epsilon3_acb) / 2 and w_abc = epsilon3_abc / 2 (epsilon3_abb for b = c),
+    the weight of lam_abc in K_a{bc}.  Every entry is validated: epsilon, sigma, a, A > 0; gamma, lam, epsilon3 >= 0; p, q
+    integers with 0 <= q < p <= 12; cos0 symmetric in its two ends."""
+    pr = {k: np.asarray(pair[k], dtype=np.float64) for k in SW_MULTI_PAIR}
+    S = pr["epsilon"].shape[0] if pr["epsilon"].ndim == 2 else -1
+    if not 1 <= S <= SW_MULTI_MAX_SPECIES:
+        raise ValueError("mdgrad_amd: the number of species must lie in [1, %d] (got epsilon of shape %s)"
+                         % (SW_MULTI_MAX_SPECIES, pr["epsilon"].shape))
+    for k, v in pr.items():
+        if v.shape != (S, S):
+            raise ValueError("mdgrad_amd: pair[%r] must be [%d, %d] (got %s)" % (k, S, S, v.shape))
+    tr = {k: np.asarray(triplet[k], dtype=np.float64) for k in SW_MULTI_TRIPLET}
+    for k, v in tr.items():
+        if v.shape != (S, S, S):
+            raise ValueError("mdgrad_amd: triplet[%r] must be [%d, %d, %d] (got %s)" % (k, S, S, S, v.shape))
+    for k in ("epsilon", "sigma", "a", "A"):
+        if not (pr[k] > 0.0).all():
+            raise ValueError("mdgrad_amd: every entry of %s must be positive (got %r)" % (k, pr[k].tolist()))
+    if not (pr["gamma"] >= 0.0).all():
+        raise ValueError("mdgrad_amd: every entry of gamma must be >= 0 (got %r)" % pr["gamma"].tolist())
+    for k in ("lam", "epsilon3"):
+        if not (tr[k] >= 0.0).all():
+            raise ValueError("mdgrad_amd: every entry of %s must be >= 0 (got %r)" % (k, tr[k].tolist()))
+    p, q = pr["p"], pr["q"]
+    if not ((np.rint(p) == p) & (np.rint(q) == q) & (0 <= q) & (q < p) & (p <= 12)).all():
+        raise ValueError("mdgrad_amd: the exponents must be integers with 0 <= q < p <= 12 for every pair (got p = %r, q = %r)"
+                         % (p.tolist(), q.tolist()))
+    if not np.isfinite(tr["cos0"]).all() or not np.array_equal(tr["cos0"], tr["cos0"].transpose(0, 2, 1)):
+        raise ValueError("mdgrad_amd: cos0[a, b, c] must equal cos0[a, c, b]: the two ends of a triplet are unordered (got %r)"
+                         % tr["cos0"].tolist())
+    out = np.zeros(SW_MULTI_PAIR_FLOATS * S * S + SW_MULTI_TRIPLET_FLOATS * S ** 3, dtype=np.float32)
+    P = out[:SW_MULTI_PAIR_FLOATS * S * S].reshape(S, S, SW_MULTI_PAIR_FLOATS)
+    eps, sig, gam = (pr[k].astype(np.float32) for k in ("epsilon", "sigma", "gamma"))
+    a32, A32 = pr["a"].astype(np.float32), pr["A"].astype(np.float32)
+    for c, v in enumerate((eps, sig, a32 * sig, gam * sig, gam, A32, pr["B"], p, q, a32, A32 * eps)):
+        P[:, :, c] = v                                # (the derived entries in float32, as the module's device pack forms them)
+    T = out[SW_MULTI_PAIR_FLOATS * S * S:].reshape(S, S, S, SW_MULTI_TRIPLET_FLOATS)
+    le = tr["lam"].astype(np.float32) * tr["epsilon3"].astype(np.float32)
+    T[..., 0] = np.float32(0.5) * (le + le.transpose(0, 2, 1))
+    T[..., 1] = tr["cos0"]
+    T[..., 2] = sw_multi_lam_weight(tr["epsilon3"])
+    return out
+
+
+def sw_multi_lam_weight(epsilon3):
+    """w_abc = d K_a{bc} / d lam_abc: epsilon3_abc / 2, and epsilon3_abb for b = c (float32 [S, S, S])."""
+    e3 = np.asarray(epsilon3, dtype=np.float32)
+    S = e3.shape[0]
+    same = np.eye(S, dtype=bool)[None, :, :]
+    return np.where(same, e3, np.float32(0.5) * e3).astype(np.float32)
+
+
+def sw_multi_eval(ell, xyz, types, n_species, tables, w=None, energy=True, grad=True, into=None, scale=1.0, want_theta=False):
+    """One launch of mdg_sw_multi_eval -> dict(energy, grad, hw, pth, pthw), argument for argument sw_eval with `types` (device
+    int32 [N], values in [0, n_species): not read here) and `tables` (device float32, the image of sw_multi_tables) in place of
+    the constants and theta.  Layout of pth / pthw [N, 2 S S + S S S]: row i holds d u_i / d(epsilon [S, S], sigma [S, S],
+    lam [S, S, S]) flattened in that order, for u_i = 1/2 sum_j phi2 + the triplets centred on i.  With a = types[i] it is zero
+    outside epsilon[a, :], sigma[a, :], lam[a, :, :]; the words lam[a, b, c] and lam[a, c, b] hold w_abc and w_acb times the
+    sum T_a{bc} of (cos theta - cos0)^2 g g over the triplets of the unordered class {b, c} centred on i, i.e. each ordering
+    receives half of the class's derivative times its own epsilon3 (both halves for b = c).  The column sums over the atoms
+    (theta_sum) are therefore dU/d(epsilon, sigma, lam) in the parameters' shapes, with no index map.  The list may have been
+    searched with any radius >= max a sigma: the kernel applies r < a_ab sigma_ab per entry."""
+    lib = _lib.load()
+    N, dev, S = ell.n_atoms, xyz.device, int(n_species)
+    if not 1 <= S <= SW_MULTI_MAX_SPECIES:
+        raise ValueError("mdgrad_amd: n_species must lie in [1, %d] (got %r)" % (SW_MULTI_MAX_SPECIES, n_species))
+    require_gpu(types, "types", dtype=None)
+    if types.shape != (N,) or types.dtype != torch.int32 or not types.is_contiguous():
+        raise ValueError("mdgrad_amd: types must be a contiguous int32 [%d] tensor (got %s %s)" % (N, types.dtype, tuple(types.shape)))
+    require_gpu(tables, "tables")
+    size = SW_MULTI_PAIR_FLOATS * S * S + SW_MULTI_TRIPLET_FLOATS * S ** 3
+    if tables.shape != (size,) or tables.dtype != torch.float32 or not tables.is_contiguous():
+        raise ValueError("mdgrad_amd: tables must be a contiguous float32 [%d] tensor (got %s)" % (size, tuple(tables.shape)))
+    xyz, w, e, g, hw, pth, pthw, acc = _eval_prologue(N, xyz, w, energy, grad, into, want_theta, (N, 2 * S * S + S ** 3))
+    partial = torch.empty(int(lib.mdg_sw_multi_partial_size(N)), device=dev) if energy else None
+    check(lib.mdg_sw_multi_eval(ptr(xyz), N, C.byref(ell.cell_struct), ptr(ell.col), ptr(ell.shift), ptr(ell.cnt), ell.max_nbr,
+                                ptr(types), S, ptr(tables), ptr(w), ptr(e), ptr(g), ptr(hw), ptr(pth), ptr(pthw), ptr(partial),
+                                float(scale), _list_flags(acc, ell), stream_ptr(dev)), "mdg_sw_multi_eval")
+    return dict(energy=e, grad=g, hw=hw, pth=pth, pthw=pthw)
+
+
+class SWMultiTerm(SWTerm):
+    """The multi-species Stillinger-Weber term (csrc/sw_multi.hip) for TermEnergyFn: the list, the species of the atoms and the
+    device table, kept current by StillingerWeberMulti; the two evaluations are SWTerm's."""
+
+    noun = "dU/d(epsilon, sigma, lam) of the multi-species Stillinger-Weber term"
+
+    def __init__(self, ell, types, n_species, tables):
+        self.ell, self.types, self.n_species, self.tables = ell, types, n_species, tables
+
+    def _eval(self, xyz, **kw):
+        return sw_multi_eval(self.ell, xyz, self.types, self.n_species, self.tables, **kw)
 
 
 # ----------------------------------------------------------------------------- Ewald reciprocal-space sum (K21)

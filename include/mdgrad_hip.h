@@ -1378,6 +1378,32 @@ int mdg_sw_multi_eval(const float* pos, int n_atoms, const MdgCell* cell /*host*
                       float out_scale, int accumulate, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * K29  Steinhardt bond-orientational order: per-atom moments over the per-atom (ELL) list and their gradient
+ *      (mdgrad_amd/observable.py bond_order; no counterpart in the reference; csrc/bond_order.hip)
+ *   pos [n_frames * n_atoms, 3]; col / cnt: the ELL list of K1 over those rows (frames = groups of n_atoms, col holds row
+ *   indices; it must be symmetric, as the builders make it); the cell must be diagonal.  For every row i and every entry j of
+ *   its list row: u = x_j - x_i re-imaged like the list builder, r = |u|, s = u / r,
+ *     w(r) = 1 (r <= r_in), 1/2 [1 + cos(pi (r - r_in) / (cutoff - r_in))] (r_in < r < cutoff), 0 (r >= cutoff);  0 < r_in < cutoff
+ *     A_lm(i) = sum_j w(r_ij) Y_lm(s_ij),  n_i = sum_j w(r_ij),   Y_lm the real orthonormal spherical harmonics
+ *   ls: HOST int32 [n_l], 1 <= n_l <= 4 distinct values in [1, 12]; K = sum (2l+1) = mdg_bond_order_components(ls, n_l)
+ *   (0 for a refused ls).  Component k of an l's block of 2l+1: k = l - m the sine component of order m, k = l the m = 0 one,
+ *   k = l + m the cosine one; the blocks follow the order of ls.
+ *   fwd: A [K, n_frames * n_atoms] COMPONENT-MAJOR (a wave stores 256 contiguous bytes per component) and n [n_frames * n_atoms].
+ *   bwd: given gA [n_frames * n_atoms, K] ROW-MAJOR (the gather of a neighbour's 2l+1 entries stays inside one or two cache
+ *        lines) and gn [n_frames * n_atoms], the cotangents of A and n, writes g_xyz [n_frames * n_atoms, 3].
+ *   One thread per row, one l at a time, fixed-order sums, no atomics, no workspace: bitwise reproducible.  A row whose own
+ *   position is not finite gets NaN outputs; cnt is clamped to [0, max_nbr] and a column outside the row's frame is skipped.
+ *   A refused ls or n_l is MDG_EINVAL before anything else is looked at.
+ */
+int mdg_bond_order_components(const int32_t* ls /*host*/, int n_l);
+int mdg_bond_order_fwd(const float* pos, int n_frames, int n_atoms, const MdgCell* cell /*host*/, float cutoff, float r_in,
+                       const int32_t* col, const int32_t* cnt, int max_nbr, const int32_t* ls /*host*/, int n_l, float* A, float* n,
+                       void* stream);
+int mdg_bond_order_bwd(const float* pos, int n_frames, int n_atoms, const MdgCell* cell /*host*/, float cutoff, float r_in,
+                       const int32_t* col, const int32_t* cnt, int max_nbr, const int32_t* ls /*host*/, int n_l, const float* gA,
+                       const float* gn, float* g_xyz, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * f4  bonded terms over a static topology table (csrc/bonded.hip).
  * Replaces torchmd/interface.py:447-455 (BondPotentials.forward: harmonic in the SQUARED bond length,
  * 1/2 k (|b|^2 - ro)^2) and :496-508 (AnglePotentials.forward: 1/2 k (theta - theta0)^2 over triples (i, j, k) centred on

@@ -267,6 +267,11 @@ _SIGNATURES = {
                               C.c_int, P, P, P]),
     "mdg_adf_bwd": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), C.c_float, P, P, C.c_int, P, C.c_float, C.c_float,
                               C.c_int, P, P, P]),
+    "mdg_bond_order_components": (C.c_int, [P, C.c_int]),
+    "mdg_bond_order_fwd": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), C.c_float, C.c_float, P, P, C.c_int, P, C.c_int, P, P,
+                                     P]),
+    "mdg_bond_order_bwd": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), C.c_float, C.c_float, P, P, C.c_int, P, C.c_int, P, P,
+                                     P, P]),
     "mdg_virial_workspace": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "mdg_virial_fwd": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), C.POINTER(MdgTerms), P, P, P, P]),
     "mdg_virial_bwd": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), C.POINTER(MdgTerms), P, P, P, P, P, P]),

@@ -26,6 +26,7 @@
 //   tersoff_multi_eval  K26  interface.py TersoffMulti      -> mdg_tersoff_multi_eval
 //   sw_multi_eval    K28  interface.py StillingerWeberMulti -> mdg_sw_multi_eval
 //   eam_table_eval   K27  interface.py EAM                  -> mdg_eam_table_eval
+//   bond_order_fwd/_bwd  K29  observable.py bond_order      -> mdg_bond_order_fwd / mdg_bond_order_bwd
 //   dihedral_phi_fwd/_bwd, dihedral_hist_fwd/_bwd  K19  observable.py Dihedrals / dihedral_distribution -> mdg_dihedral_phi_* / _hist_*
 //   edge_geom(+_bwd) schnet.py:142                          -> mdg_edge_geom / mdg_edge_geom_bwd
 //   cfconv_fwd/_bwd  K9+K10 modules.py:531-571              -> mdg_cfconv_fwd(_bf16) / mdg_cfconv_bwd(_bf16)
@@ -302,6 +303,39 @@ Tensor adf_bwd(const Tensor& pos, int64_t n_frames, int64_t n_atoms, at::ArrayRe
     Tensor g = at::empty_like(pos);
     ok(mdg_adf_bwd(fptr(pos), (int)n_frames, (int)n_atoms, &c, (float)cutoff, col.data_ptr<int32_t>(), cnt.data_ptr<int32_t>(), M,
                    fptr(mu), (float)spacing, (float)coeff, B, fptr(g_raw), mptr(g), stream_of(pos)));
+    return g;
+}
+
+// ------------------------------------------------------------------------------------------------ K29
+// (A [K, rows] component-major, n [rows]) and g_xyz [rows, 3] from gA [rows, K] row-major, gn [rows]; rows = n_frames * n_atoms
+std::vector<int32_t> bond_order_ls(at::ArrayRef<int64_t> ls) {
+    std::vector<int32_t> v(ls.begin(), ls.end());
+    TORCH_CHECK(mdg_bond_order_components(v.data(), (int)v.size()) > 0, "mdgrad: ", mdg_last_error());
+    return v;
+}
+std::tuple<Tensor, Tensor> bond_order_fwd(const Tensor& pos, int64_t n_frames, int64_t n_atoms, at::ArrayRef<double> cell, double cutoff,
+                                          double r_in, const Tensor& col, const Tensor& cnt, at::ArrayRef<int64_t> ls) {
+    adf_check(pos, n_frames, n_atoms, col, cnt, pos);
+    const std::vector<int32_t> v = bond_order_ls(ls);
+    const MdgCell c = make_cell(cell);
+    const int64_t K = mdg_bond_order_components(v.data(), (int)v.size()), rows = n_frames * n_atoms;
+    Tensor A = at::empty({K, rows}, pos.options()), n = at::empty({rows}, pos.options());
+    ok(mdg_bond_order_fwd(fptr(pos), (int)n_frames, (int)n_atoms, &c, (float)cutoff, (float)r_in, col.data_ptr<int32_t>(),
+                          cnt.data_ptr<int32_t>(), (int)col.size(1), v.data(), (int)v.size(), mptr(A), mptr(n), stream_of(pos)));
+    return std::make_tuple(A, n);
+}
+Tensor bond_order_bwd(const Tensor& pos, int64_t n_frames, int64_t n_atoms, at::ArrayRef<double> cell, double cutoff, double r_in,
+                      const Tensor& col, const Tensor& cnt, at::ArrayRef<int64_t> ls, const Tensor& gA, const Tensor& gn) {
+    adf_check(pos, n_frames, n_atoms, col, cnt, pos);
+    check_f32(gA, "gA"); check_f32(gn, "gn"); same_device(pos, gA, "gA"); same_device(pos, gn, "gn");
+    const std::vector<int32_t> v = bond_order_ls(ls);
+    const MdgCell c = make_cell(cell);
+    const int64_t K = mdg_bond_order_components(v.data(), (int)v.size()), rows = n_frames * n_atoms;
+    TORCH_CHECK(gA.numel() == rows * K && gn.numel() == rows, "mdgrad: gA must be [n_frames * n_atoms, K] and gn [n_frames * n_atoms]");
+    Tensor g = at::empty_like(pos);
+    ok(mdg_bond_order_bwd(fptr(pos), (int)n_frames, (int)n_atoms, &c, (float)cutoff, (float)r_in, col.data_ptr<int32_t>(),
+                          cnt.data_ptr<int32_t>(), (int)col.size(1), v.data(), (int)v.size(), fptr(gA), fptr(gn), mptr(g),
+                          stream_of(pos)));
     return g;
 }
 
@@ -1095,6 +1129,10 @@ TORCH_LIBRARY(mdgrad, m) {
           "float spacing, float coeff) -> Tensor");
     m.def("adf_bwd(Tensor pos, int n_frames, int n_atoms, float[] cell, float cutoff, Tensor col, Tensor cnt, Tensor mu, "
           "float spacing, float coeff, Tensor g_raw) -> Tensor");
+    m.def("bond_order_fwd(Tensor pos, int n_frames, int n_atoms, float[] cell, float cutoff, float r_in, Tensor col, Tensor cnt, "
+          "int[] ls) -> (Tensor, Tensor)");
+    m.def("bond_order_bwd(Tensor pos, int n_frames, int n_atoms, float[] cell, float cutoff, float r_in, Tensor col, Tensor cnt, "
+          "int[] ls, Tensor gA, Tensor gn) -> Tensor");
     m.def("virial_fwd(Tensor pos, float[] cell, int[] terms_i, float[] terms_f, Tensor?[] masks, Tensor? theta) -> Tensor");
     m.def("virial_bwd(Tensor pos, float[] cell, int[] terms_i, float[] terms_f, Tensor?[] masks, Tensor? theta, Tensor gW) -> "
           "(Tensor, Tensor)");
@@ -1157,6 +1195,8 @@ TORCH_LIBRARY_IMPL(mdgrad, CUDA, m) {      // (the HIP backend registers under t
     m.impl("rdf_bwd", rdf_bwd);
     m.impl("adf_fwd", adf_fwd);
     m.impl("adf_bwd", adf_bwd);
+    m.impl("bond_order_fwd", bond_order_fwd);
+    m.impl("bond_order_bwd", bond_order_bwd);
     m.impl("virial_fwd", virial_fwd);
     m.impl("virial_bwd", virial_bwd);
     m.impl("sk_fwd", sk_fwd);

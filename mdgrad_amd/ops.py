@@ -9,6 +9,7 @@ torch.autograd.Function wrappers that own the differentiation contract
     SkFn                                                        static structure factor of every frame
     MsdFn                                                       mean-squared displacement over all lags (+ fourth moment)
     IsfFn                                                       intermediate scattering functions F(k,t), F_s(k,t)
+    BondOrderFn                                                 Steinhardt moments A_lm(i), n_i over the per-atom list
     TermEnergyFn -> TermGradFn                                  every other term with parameters, order <= 2 in x, 1 in the
                                                                 parameters; what differs per kernel family is a small `term` object:
       DihedralTerm                                              torsion term, parameters: its coefficients
@@ -2063,6 +2064,89 @@ class AdfRawFn(torch.autograd.Function):
                                   ell.max_nbr, ptr(muc), float(spacing), float(coeff), B, ptr(gr), ptr(gx[f0:f1]),
                                   stream_ptr(x3.device)), "mdg_adf_bwd")
         return gx.reshape(shape), None, None, None, None, None, None
+
+
+# ----------------------------------------------------------------------------- bond-orientational order
+BOND_ORDER_CHUNK_FRAMES = None      # when set: frames per chunk of BondOrderFn (tests force several chunks with it)
+
+
+def _bond_order_chunk_frames(F, N, cell_struct, cutoff):
+    if BOND_ORDER_CHUNK_FRAMES is not None:
+        return max(1, min(F, int(BOND_ORDER_CHUNK_FRAMES)))
+    return _adf_chunk_frames(F, N, cell_struct, cutoff)
+
+
+class BondOrderFn(torch.autograd.Function):
+    """(A [F, N, K], n [F, N]): the Steinhardt moments A_lm(i) = sum_j w(r_ij) Y_lm(s_ij) and n_i = sum_j w(r_ij) of every atom
+    of xyz [F, N, 3] over its row of the neighbour list at `cutoff` (csrc/bond_order.hip, K29): the kernel side of
+    observable.bond_order.  ls: 1..4 distinct l in 1..12, K = sum (2l+1).  The kernel writes A component-major; the returned A
+    is the [F, N, K] view of that buffer.  The lists are built in chunks of frames like AdfRawFn's; the backward pass reuses
+    the forward's list when there was one chunk and rebuilds the chunks one at a time otherwise.  The torch.ops layer serves
+    the launches when it is loaded (_torch_ops.get()), the ctypes bindings otherwise: the same kernels either way.
+    Differentiable once with respect to the positions."""
+
+    @staticmethod
+    def forward(ctx, xyz, ls, cutoff, r_in, cell_struct, mask):
+        require_gpu(xyz, "xyz")
+        x3 = xyz.detach()
+        x3 = x3 if x3.is_contiguous() else x3.contiguous()
+        F, N = x3.shape[0], x3.shape[1]
+        ls = tuple(int(l) for l in ls)
+        K = sum(2 * l + 1 for l in ls)
+        dev = x3.device
+        tops = _torch_ops.get()
+        lib = _lib.load()
+        ls_c = (C.c_int32 * len(ls))(*ls)
+        fc = _bond_order_chunk_frames(F, N, cell_struct, cutoff)
+        A, n, keep = None, torch.empty(F, N, device=dev), None
+        for f0 in range(0, F, fc):
+            f1 = min(F, f0 + fc)
+            flat = x3[f0:f1].reshape(-1, 3)
+            ell = build_ell(flat, cell_struct, cutoff, mask, group=N)
+            if tops is not None:
+                part, n_part = tops.bond_order_fwd(flat, f1 - f0, N, _torch_ops.cell_args(cell_struct), float(cutoff), float(r_in),
+                                                   ell.col, ell.cnt, list(ls))
+                n[f0:f1] = n_part.view(f1 - f0, N)
+            else:
+                part = torch.empty(K, (f1 - f0) * N, device=dev)
+                check(lib.mdg_bond_order_fwd(ptr(flat), f1 - f0, N, C.byref(cell_struct), float(cutoff), float(r_in), ptr(ell.col),
+                                             ptr(ell.cnt), ell.max_nbr, ls_c, len(ls), ptr(part), ptr(n[f0:f1]), stream_ptr(dev)),
+                      "mdg_bond_order_fwd")
+            if f0 == 0 and f1 == F:
+                A, keep = part.view(K, F, N), ell
+            else:
+                A = torch.empty(K, F, N, device=dev) if A is None else A
+                A[:, f0:f1] = part.view(K, f1 - f0, N)
+            del ell
+        ctx.ell = keep
+        ctx.args = (ls, float(cutoff), float(r_in), cell_struct, mask, fc, xyz.shape)
+        ctx.save_for_backward(x3)
+        return A.permute(1, 2, 0), n
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gA, gn):
+        (x3,) = ctx.saved_tensors
+        ls, cutoff, r_in, cell_struct, mask, fc, shape = ctx.args
+        F, N = x3.shape[0], x3.shape[1]
+        tops = _torch_ops.get()
+        lib = _lib.load()
+        ls_c = (C.c_int32 * len(ls))(*ls)
+        gA, gn = gA.detach().to(torch.float32), gn.detach().to(torch.float32)
+        gx = torch.empty_like(x3)
+        for f0 in range(0, F, fc):
+            f1 = min(F, f0 + fc)
+            flat = x3[f0:f1].reshape(-1, 3)
+            ell = ctx.ell if ctx.ell is not None else build_ell(flat, cell_struct, cutoff, mask, group=N)
+            ga, gw = gA[f0:f1].contiguous().view((f1 - f0) * N, -1), gn[f0:f1].contiguous().view(-1)        # gA row-major
+            if tops is not None:
+                gx[f0:f1] = tops.bond_order_bwd(flat, f1 - f0, N, _torch_ops.cell_args(cell_struct), cutoff, r_in, ell.col, ell.cnt,
+                                                list(ls), ga, gw).view(f1 - f0, N, 3)
+            else:
+                check(lib.mdg_bond_order_bwd(ptr(flat), f1 - f0, N, C.byref(cell_struct), cutoff, r_in, ptr(ell.col), ptr(ell.cnt),
+                                             ell.max_nbr, ls_c, len(ls), ptr(ga), ptr(gw), ptr(gx[f0:f1]), stream_ptr(x3.device)),
+                      "mdg_bond_order_bwd")
+        return gx.reshape(shape), None, None, None, None, None
 
 
 # ----------------------------------------------------------------------------- pair virial (pressure)

@@ -876,9 +876,42 @@ int mdg_nhv_adj_end(const float* vh, const float* pm, const float* lvh, const fl
                     const float* mass, const float* Q, const float* t, int64_t* idx, int advance, const float* g_v,
                     const float* g_q, const float* g_pv, int n_rep, int n_atoms, int n_chains, float* lv, float* lq,
                     float* lp, float* scratch, void* stream);
+/* Langevin dynamics (BAOAB) on the same generic path (csrc/langevin.hip): one step as two launches around the ONE force
+ * evaluation, one adjoint interval as one launch between two force-vjp evaluations.  State of M = R*n stacked atoms:
+ * v, q, f, lv, lq, w [M, 3]; mass [M]; time-major frames [T, M, 3]; idx as above; gamma, T: device float[1]; rng: device
+ * int64[2] = (seed, step0) -- a captured HIP graph follows changes of all of them.
+ *   h = t[k+1] - t[k], c1 = exp(-gamma h), c2 = sqrt(-expm1(-2 gamma h))
+ *   mdg_lgv_kick      v1 = v + (h/2) f/m, q1 = q + (h/2) v1, v2 = c1 v1 + c2 sqrt(T/m) xi, qn = q1 + (h/2) v2
+ *   mdg_lgv_finish    v = v2 + (h/2) fn/m, q = qn, f = fn ; frame k+1 stored
+ *   mdg_lgv_adj_pre   q <- frame i ;  w = (h/2) lam_v / m                                       (h = t[i] - t[i-1])
+ *   mdg_lgv_adj_step  given f = F(q_i), dwf = H(q_i) w:  lam_q += dwf ; lam_v += (h/2) lam_q ;
+ *                     gpart[workgroup] += sum lam_v h (sqrt(T/m) xi / c2 - v2), v2 = v_i - (h/2) f/m   (want_gamma) ;
+ *                     lam_v = c1 lam_v + (h/2) lam_q ; w = (h/2) lam_v / m ; lam += g[i-1] ;
+ *                     w += (h'/2) lam_v / m, h' = t[i-1] - t[i-2] (i >= 2) ; q <- frame i-1
+ *   mdg_lgv_gamma_sum out[0] = the mdg_lgv_blocks(M) slots of gpart added in slot order (zero gpart before a sweep)
+ *   mdg_lgv_noise     xi [M, 3] of step rng[1] + step_off
+ * xi: Philox4x32-10, key = (seed lo, seed hi), counter = (atom row, step lo, step hi, 0), step = step0 + k (adjoint:
+ * step0 + i - 1); u_j = ((x_j >> 9) + 1/2) 2^-23; xi = (r0 cos 2 pi u1, r0 sin 2 pi u1, r1 cos 2 pi u3), r0 = sqrt(-2 ln u0),
+ * r1 = sqrt(-2 ln u2).  ticket: one zeroed uint32 shared by the launches of one stream (handed back at zero); advance != 0
+ * (mdg_lgv_finish / mdg_lgv_adj_step): idx[0] <- k + 1 resp. i - 1 once every workgroup has read the old value.  Bitwise
+ * reproducible: no floating-point atomics. */
+int mdg_lgv_blocks(int n_total);
+int mdg_lgv_noise(const int64_t* rng, int64_t step_off, int n_total, float* xi, void* stream);
+int mdg_lgv_kick(const float* v, const float* q, const float* f, const float* mass, const float* gamma, const float* T,
+                 const float* t, const int64_t* idx, const int64_t* rng, int n_total, float* v2, float* qn, void* stream);
+int mdg_lgv_finish(float* v, float* q, float* f, const float* v2, const float* qn, const float* fn, const float* mass,
+                   const float* t, int64_t* idx, int advance, int n_total, float* out_v, float* out_q, uint32_t* ticket,
+                   void* stream);
+int mdg_lgv_adj_pre(const float* q_t, const float* lv, const float* mass, const float* t, const int64_t* idx, int n_total,
+                    float* q, float* w, void* stream);
+int mdg_lgv_adj_step(const float* v_t, const float* q_t, const float* f, const float* dwf, const float* mass,
+                     const float* gamma, const float* T, const float* t, int64_t* idx, int advance, const int64_t* rng,
+                     const float* g_v, const float* g_q, int want_gamma, int n_total, float* lv, float* lq, float* q, float* w,
+                     float* gpart, uint32_t* ticket, void* stream);
+int mdg_lgv_gamma_sum(const float* gpart, int n_total, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------
- * K14  bond-angle distribution  (replaces angle_distribution.forward and its autograd backward:
+ * K14 bond-angle distribution  (replaces angle_distribution.forward and its autograd backward:
  *      torchmd/observable.py:120-151, compute_angle :166-179, generate_angle_list torchmd/topology.py:83-122;
  *      csrc/adf.hip)
  *   pos [n_frames * n_atoms, 3]; col / cnt: the ELL list of K1 over those rows (frames = groups of n_atoms, col holds row

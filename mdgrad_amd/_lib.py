@@ -209,6 +209,13 @@ _SIGNATURES = {
     "mdg_nhv_adj_mid": (C.c_int, [P, P, P, P, P, P, P, P, P, P, P, C.c_float, P, P, C.c_int, C.c_int, C.c_int,
                                   P, P, P, P, P, P, P, P, P]),
     "mdg_nhv_adj_end": (C.c_int, [P, P, P, P, P, P, P, P, P, P, C.c_int, P, P, P, C.c_int, C.c_int, C.c_int, P, P, P, P, P]),
+    "mdg_lgv_blocks": (C.c_int, [C.c_int]),
+    "mdg_lgv_noise": (C.c_int, [P, C.c_int64, C.c_int, P, P]),
+    "mdg_lgv_kick": (C.c_int, [P, P, P, P, P, P, P, P, P, C.c_int, P, P, P]),
+    "mdg_lgv_finish": (C.c_int, [P, P, P, P, P, P, P, P, P, C.c_int, C.c_int, P, P, P, P]),
+    "mdg_lgv_adj_pre": (C.c_int, [P, P, P, P, P, C.c_int, P, P, P]),
+    "mdg_lgv_adj_step": (C.c_int, [P, P, P, P, P, P, P, P, P, C.c_int, P, P, P, C.c_int, C.c_int, P, P, P, P, P, P, P]),
+    "mdg_lgv_gamma_sum": (C.c_int, [P, C.c_int, P, P]),
     "mdg_edge_diff": (C.c_int, [P, P, C.c_int64, C.c_int, P, P]),
     "mdg_edge_scatter": (C.c_int, [P, P, P, P, C.c_int, C.c_int, C.c_int, P, P]),
     "mdg_cfconv_agg": (C.c_int, [P, P, P, P, P, C.c_int, C.c_int, C.c_int, P, P]),

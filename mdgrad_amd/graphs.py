@@ -30,6 +30,11 @@ from .tinydiffeq import _flatten
 MAX_EDGES = int(os.environ.get("MDG_GRAPH_MAX_EDGES", str(1 << 18)))
 
 
+def _is_langevin(func):
+    """md.Langevin (BAOAB): its steps and adjoint intervals are not those of an ODE right-hand side."""
+    return getattr(func, "_method", None) == 'baoab'
+
+
 def enabled(func):
     """Graph replay applies to an integrator with the analytic-adjoint protocol, a neighbour rebuild
     at every call and fixed-capacity lists available on every member of its model."""
@@ -38,7 +43,7 @@ def enabled(func):
     if getattr(func, "use_graphs", True) is False:
         return False
     model = getattr(func, "model", None)
-    if model is None or getattr(func, "topology_update_freq", 0) != 1 or not hasattr(func, "rhs_vjp"):
+    if model is None or getattr(func, "topology_update_freq", 0) != 1 or not (hasattr(func, "rhs_vjp") or _is_langevin(func)):
         return False
     if not getattr(func, "supports_rhs_vjp", lambda: False)():
         return False
@@ -239,6 +244,73 @@ class _AdjointGraph:
         return [l.clone() for l in self.lam], self.gth.clone()
 
 
+class _LangevinForwardGraph(_ForwardGraph):
+    """v, q, F <- one BAOAB step (sovlers._lgv_forward's loop body: kick, force, finish); frame k+1 stored."""
+
+    def _step(self):
+        func, (v, q), F, k = self.func, self.state, self.F, self.k
+        w = func.lgv_work(v)
+        qn = w.kick(v, q, F, self.t, k)
+        w.finish(v, q, F, func.force(qn), self.t, k, self.out, advance=True)            # (k <- k + 1 inside)
+
+    def run(self, y0, t, noise):
+        # (seed, step0) are device words the kernels read: a new stream position needs no new graph
+        self.func.lgv_work(self.state[0]).set_rng(*noise)
+        return super().run(y0, t)
+
+
+class _LangevinAdjointGraph(_AdjointGraph):
+    """lam, gth <- one interval of sovlers._analytic_langevin_adjoint: the force-vjp at frame i and the launch of algebra
+    up to the merged w of frame i-1.  The gather of the last frame before the sweep and the force-vjp at frame 0 after it
+    are launched once per pass, outside the graph."""
+
+    def __init__(self, func, ans, n_params):
+        w = func.lgv_work(ans[0][0])
+        w.q.copy_(ans[1][0])                        # a physical state for the warm-up / capture evaluations
+        w.w.zero_()
+        self.want_gamma = bool(getattr(func, "trainable_gamma", False))
+        super().__init__(func, ans, n_params)
+
+    def _interval(self):
+        func, lam, i = self.func, self.lam, self.i
+        w = func.lgv_work(lam[0])
+        func.update_topology(w.q)
+        F, dwf, th = func.model.force_vjp(w.q, w.w)
+        if th:
+            self.gth.add_(_flatten(func.theta_in_parameter_order(th)))
+        w.adj_step(self.ans, lam, F, dwf, self.t, i, self.gout, want_gamma=self.want_gamma, advance=True)   # (i <- i - 1 inside)
+
+    def run(self, t, ans, grad_output, noise):
+        func, T = self.func, ans[0].shape[0]
+        getattr(func.model, "prepare_pass", lambda: None)()
+        for dst, src in zip(self.ans, ans):
+            dst.copy_(src)
+        for dst, src in zip(self.gout, grad_output):
+            dst.copy_(src)
+        self.t.copy_(t)
+        for l, g in zip(self.lam, grad_output):
+            l.copy_(g[-1])
+        self.gth.zero_()
+        self.i.fill_(T - 1)
+        w = func.lgv_work(self.lam[0])
+        w.set_rng(*noise)
+        w.gpart.zero_()
+        w.adj_pre(self.ans, self.lam[0], self.t, self.i)
+        for _ in range(T - 1):
+            self.graph.replay()
+        func.update_topology(w.q)
+        _, dwf, th = func.model.force_vjp(w.q, w.w)
+        if th:
+            self.gth.add_(_flatten(func.theta_in_parameter_order(th)))
+        self.lam[1].add_(dwf)
+        if self.want_gamma:
+            from .sovlers import _gamma_slot
+            slot = _gamma_slot(func)
+            self.gth[slot:slot + 1].add_(w.gamma_bar())
+        func.update_count += T - 1
+        return [l.clone() for l in self.lam], self.gth.clone()
+
+
 def _cache(func):
     c = getattr(func, "_graph_cache", None)
     if c is None:
@@ -282,9 +354,9 @@ def eager_static(func, body, q_last_of):
     return None if overflow else out
 
 
-def forward(func, y0, t):
+def forward(func, y0, t, noise=None):
     """Frames (v_t, q_t, pv_t) of NHVerlet.integrate by graph replay, or None when graphs do not apply or
-    the capacities overflowed (the caller then integrates eagerly)."""
+    the capacities overflowed (the caller then integrates eagerly).  `noise`: (seed, step0) of an md.Langevin pass."""
     cache = _cache(func)
     if not _prepare(func):
         func.model.set_static_topology(False)
@@ -295,12 +367,12 @@ def forward(func, y0, t):
         func.model._reset_topology(y0[1])
         for k_ in [k_ for k_ in cache if k_[0] == "fwd"]:
             del cache[k_]
-        g = cache[key] = _ForwardGraph(func, y0, t.shape[0])
-    out = g.run(y0, t)
+        g = cache[key] = (_LangevinForwardGraph if _is_langevin(func) else _ForwardGraph)(func, y0, t.shape[0])
+    out = g.run(y0, t, noise) if _is_langevin(func) else g.run(y0, t)
     return None if _finish(func, cache, out[1][-1]) else out
 
 
-def adjoint(func, t, ans, grad_output, n_params):
+def adjoint(func, t, ans, grad_output, n_params, noise=None):
     """(lam, gth) of _analytic_nhc_adjoint by graph replay, or None (see forward)."""
     cache = _cache(func)
     if not _prepare(func):
@@ -312,6 +384,6 @@ def adjoint(func, t, ans, grad_output, n_params):
         func.model._reset_topology(ans[1][0])
         for k_ in [k_ for k_ in cache if k_[0] == "adj"]:
             del cache[k_]
-        g = cache[key] = _AdjointGraph(func, ans, n_params)
-    out = g.run(t, ans, grad_output)
+        g = cache[key] = (_LangevinAdjointGraph if _is_langevin(func) else _AdjointGraph)(func, ans, n_params)
+    out = g.run(t, ans, grad_output, noise) if _is_langevin(func) else g.run(t, ans, grad_output)
     return None if _finish(func, cache, ans[1][0]) else out

@@ -3,7 +3,8 @@
 
 `forward(t, state)` is the generic right-hand side (torch ops around the HIP energy ops,
 differentiable twice) that the reference's Python solvers call; `fused_spec(method)` describes
-the same dynamics to the fused HIP trajectory kernels when that is possible.
+the same dynamics to the fused HIP trajectory kernels when that is possible.  `Langevin` (BAOAB, method 'baoab') has no
+counterpart in the reference: it is a splitting scheme with its own step and discrete adjoint, not a right-hand side.
 """
 import numpy as np
 import weakref
@@ -541,4 +542,138 @@ class NoseHooverChain(_EOM):
     def get_inital_states(self, wrap=True):
         baths = [0.0] * self.num_chains if self.n_rep == 1 else np.zeros((self.n_rep, self.num_chains))
         states = [self.system.get_velocities(), self.system.get_positions(wrap=wrap), baths]
+        return [_to_device_f32(var, self.system.device) for var in states]
+
+
+class Langevin(_EOM):
+    """Langevin dynamics at temperature T with friction gamma, integrated with the BAOAB splitting (Leimkuhler and
+    Matthews); the reference has no stochastic thermostat, so the scheme is defined here.  One step of size
+    h = t[k+1] - t[k], with m the atom's mass and T in energy units (the convention of NoseHooverChain.T: an equilibrated
+    system has <m v^2> = T per degree of freedom):
+
+        v <- v + (h/2) F(q)/m            (B)   a proper 1/m, unlike NVE
+        q <- q + (h/2) v                 (A)
+        v <- c1 v + c2 sqrt(T/m) xi_k    (O)   c1 = exp(-gamma h), c2 = sqrt(-expm1(-2 gamma h))
+        q <- q + (h/2) v                 (A)
+        v <- v + (h/2) F(q)/m            (B)   this force is the next step's first force: one evaluation per step
+
+    `gamma` is a scalar in 1/time of the t grid; with `trainable_gamma` it is a parameter of the integrator (gamma > 0:
+    the derivative of c2 is singular at 0).  gamma = 0, not trainable, is velocity Verlet with 1/m.  T is read from a
+    device scalar, so annealing keeps captured graphs.
+
+    Noise: xi_k of atom row a is Philox4x32-10 (Random123) with key = (seed lo, seed hi) and counter = (a, s lo, s hi, 0),
+    s = step0 + k a 64-bit global step number; from the output words x0..x3, u_j = ((x_j >> 9) + 1/2) 2^-23,
+    xi = (r0 cos 2 pi u1, r0 sin 2 pi u1, r1 cos 2 pi u3) with r0 = sqrt(-2 ln u0), r1 = sqrt(-2 ln u2).  Stacked replicas
+    are rows of one state and get independent noise.  `step0` advances by len(t) - 1 per integration, so consecutive epochs
+    continue one stream; a forward pass records the (seed, step0) it used, and its backward regenerates the same xi_k
+    whatever ran in between; `reseed(seed, step0=0)` resets both.
+
+    Adjoint: for a fixed noise sequence the trajectory is a deterministic map of (y0, theta, gamma); its exact discrete
+    adjoint over the saved frames (sovlers._analytic_langevin_adjoint) applies B+, A+, O+, A+, B+ per interval, the two
+    B+ that meet at a frame merged into one `force_vjp` there: T force-vjp evaluations for T - 1 intervals.  No gradient
+    with respect to T or the time grid.
+
+    fp32 contiguous device states with a model that has `force_vjp` run in the mdg_lgv_* kernels (csrc/langevin.hip);
+    CPU tensors, float64 or a model without `force_vjp` run the same step and adjoint in torch ops."""
+    _ensemble, _method = None, 'baoab'
+
+    def __init__(self, potentials, system, T, gamma, seed=0, trainable_gamma=False, adjoint=True, topology_update_freq=1):
+        super().__init__()
+        if topology_update_freq != 1:
+            raise ValueError("Langevin: topology_update_freq must be 1 (got %r): the BAOAB path rebuilds the neighbour "
+                             "lists at every force evaluation" % (topology_update_freq,))
+        gamma = float(gamma)
+        if gamma < 0 or (trainable_gamma and gamma <= 0):
+            raise ValueError("Langevin: gamma must be %s (got %g)" % ("> 0 when it is trainable" if trainable_gamma else ">= 0",
+                                                                      gamma))
+        self.model = potentials
+        self.system = system
+        self.device = system.device
+        self.mass = torch.Tensor(system.get_masses()).to(self.device)
+        self.N_dof = self.mass.shape[0] * system.dim
+        self.dim = system.dim
+        self.adjoint = adjoint
+        self.state_keys = ['velocities', 'positions']
+        self.topology_update_freq = 1
+        self.update_count = 0
+        self.trainable_gamma = bool(trainable_gamma)
+        if trainable_gamma:
+            self.gamma = torch.nn.Parameter(torch.tensor(gamma, device=self.device))
+        else:
+            self.register_buffer("gamma", torch.tensor(gamma, device=self.device), persistent=False)
+        self.T = T
+        self.reseed(seed)
+
+    def reseed(self, seed, step0=0):
+        """Restart the noise stream: key `seed`, global step number `step0`."""
+        self.seed, self.step0 = int(seed), int(step0)
+
+    T = NoseHooverChain.T
+    update_T = NoseHooverChain.update_T
+    _T_device = NoseHooverChain._T_device
+
+    def _gamma_device(self):
+        """gamma as the fp32 device scalar the kernels read (the parameter itself when it is trainable)."""
+        g = self.gamma.detach()
+        return g.reshape(1) if g.dtype == torch.float32 else g.float().reshape(1)
+
+    def fused_spec(self, method):
+        return None                                   # the fused trajectory kernels do not cover Langevin dynamics
+
+    def forward(self, t, state):
+        raise RuntimeError("Langevin: BAOAB is a splitting scheme, not an ODE right-hand side; integrate with method='baoab'")
+
+    def supports_rhs_vjp(self):
+        return getattr(self.model, "supports_force_vjp", lambda: False)()
+
+    def lgv_steps_ok(self, *tensors):
+        """The mdg_lgv_* kernels apply: analytic force / force-vjp from the model, fp32 contiguous device states outside
+        autograd."""
+        if getattr(self, "hip_algebra", True) is False or self.dim != 3 or not self.supports_rhs_vjp():
+            return False
+        if not all(x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.shape == (self.mass.shape[0], 3)
+                   for x in tensors):
+            return False
+        return self.mass.is_cuda and not (torch.is_grad_enabled() and any(x.requires_grad for x in tensors))
+
+    def lgv_work(self, v):
+        w = getattr(self, "_lgv_work", None)
+        if w is None or w.v2.shape != v.shape or w.v2.device != v.device:
+            w = self._lgv_work = ops.LgvWork(self, v)
+        return w
+
+    def noise(self, seed, step, like):
+        """xi of (seed, step) for a state shaped like `like`, in torch ops (the integers are the device's)."""
+        return ops.lgv_noise_torch(seed, step, like.shape[0], dtype=like.dtype, device=like.device)
+
+    def force_graph(self, q):
+        """F(q) that stays in the autograd graph (adjoint = False: plain backpropagation through the steps)."""
+        self.update_topology(q)
+        (g,) = torch.autograd.grad(self.model(q).sum(), q, create_graph=True)
+        return -g
+
+    def force_and_vjp(self, q, w):
+        """(F, H(q) w, [d(w.F)/dtheta per parameter of the INTEGRATOR]) from the model's force_vjp, or by autograd of
+        (w.F) for a model without one."""
+        self.update_topology(q)
+        plist = list(self.model.parameters())
+        if self.supports_rhs_vjp():
+            F, dwf, gth = self.model.force_vjp(q, w)
+        else:
+            with torch.enable_grad():
+                qq = q.detach().requires_grad_(True)
+                (gu,) = torch.autograd.grad(self.model(qq).sum(), qq, create_graph=True)
+                F = -gu
+                got = torch.autograd.grad((F * w.detach()).sum(), [qq] + plist, allow_unused=True)
+            F, dwf = F.detach(), (torch.zeros_like(q) if got[0] is None else got[0])
+            gth = [torch.zeros_like(p) if g is None else g for p, g in zip(plist, got[1:])]
+        by_id = {id(p): g for p, g in zip(plist, gth or [])}
+        return F, dwf, [by_id[id(p)] if id(p) in by_id else torch.zeros_like(p) for p in self.parameters()]
+
+    def theta_in_parameter_order(self, gth):
+        by_id = {id(p): g for p, g in zip(self.model.parameters(), gth)}
+        return [by_id[id(p)] if id(p) in by_id else torch.zeros_like(p) for p in self.parameters()]
+
+    def get_inital_states(self, wrap=True):
+        states = [self.system.get_velocities(), self.system.get_positions(wrap=wrap)]
         return [_to_device_f32(var, self.system.device) for var in states]

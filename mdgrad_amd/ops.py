@@ -2513,6 +2513,125 @@ class NhvWork:
             _touched(i)
 
 
+# ----------------------------------------------------------------------------- Langevin (BAOAB) algebra
+_PHILOX_M0, _PHILOX_M1, _PHILOX_W0, _PHILOX_W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
+_U32 = 0xFFFFFFFF
+
+
+def _mulhilo32(m, x):
+    """(high, low) 32-bit words of m * x for a constant m < 2^32 and an int64 tensor x of values < 2^32, without leaving
+    the positive range of int64: x is split into 16-bit halves."""
+    xl, xh = x & 0xFFFF, x >> 16
+    pl, ph = m * xl, m * xh                                   # < 2^48
+    return (ph + (pl >> 16)) >> 16, (pl + ((ph & 0xFFFF) << 16)) & _U32
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 (Random123) with integer tensor ops: `counter` four and `key` two int64 tensors (or ints) holding
+    32-bit words; returns the four output words as int64 tensors.  The integers are the device's (csrc/langevin.hip)."""
+    c = [torch.as_tensor(x, dtype=torch.int64) for x in counter]
+    dev = next((x.device for x in c if x.dim()), c[0].device)
+    c = [x.to(dev) for x in c]
+    k0, k1 = (torch.as_tensor(x, dtype=torch.int64).to(dev) for x in key)
+    c0, c1, c2, c3 = torch.broadcast_tensors(*c)
+    for _ in range(10):
+        hi0, lo0 = _mulhilo32(_PHILOX_M0, c0)
+        hi1, lo1 = _mulhilo32(_PHILOX_M1, c2)
+        c0, c1, c2, c3 = hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0
+        k0, k1 = (k0 + _PHILOX_W0) & _U32, (k1 + _PHILOX_W1) & _U32
+    return c0, c1, c2, c3
+
+
+def lgv_noise_torch(seed, step, n, dtype=torch.float64, device="cpu"):
+    """xi [n, 3] of (seed, step) in torch ops: the integers of mdg_lgv_noise, the normals in `dtype`."""
+    seed, step = int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF
+    a = torch.arange(n, dtype=torch.int64, device=device)
+    x = philox4x32_10((a, step & _U32, step >> 32, 0), (seed & _U32, seed >> 32))
+    u = [((w >> 9).to(dtype) + 0.5) * 2.0 ** -23 for w in x]
+    r0, r1 = torch.sqrt(-2.0 * torch.log(u[0])), torch.sqrt(-2.0 * torch.log(u[2]))
+    two_pi = 2.0 * math.pi
+    return torch.stack((r0 * torch.cos(two_pi * u[1]), r0 * torch.sin(two_pi * u[1]), r1 * torch.cos(two_pi * u[3])), 1)
+
+
+def _rng_words(seed, step0, device):
+    """(seed, step0) as the device int64[2] the mdg_lgv_* kernels read (two's complement of the unsigned 64-bit values)."""
+    s64 = lambda x: ((int(x) + (1 << 63)) % (1 << 64)) - (1 << 63)
+    return torch.tensor([s64(seed), s64(step0)], dtype=torch.int64).to(device)
+
+
+def lgv_noise(seed, step, n, device):
+    """xi [n, 3] (float32) of (seed, step) from mdg_lgv_noise: the stream of the Langevin kernels, for tests."""
+    lib = _lib.load()
+    rng = _rng_words(seed, step, device)
+    require_gpu(rng, "rng", dtype=torch.int64)
+    xi = torch.empty(int(n), 3, device=rng.device)
+    check(lib.mdg_lgv_noise(ptr(rng), 0, int(n), ptr(xi), stream_ptr(rng.device)), "mdg_lgv_noise")
+    return xi
+
+
+class LgvWork:
+    """Buffers of the Langevin half-step kernels (csrc/langevin.hip: mdg_lgv_*) for one integrator, allocated once (a
+    captured HIP graph needs fixed addresses): the intermediate state of a forward step / an adjoint interval, the
+    device words (seed, step0) of the noise stream, the per-workgroup partial sums of the friction gradient."""
+
+    def __init__(self, integ, like_v):
+        z = lambda: torch.empty_like(like_v)
+        dev = like_v.device
+        self.mass, self.n = integ.mass, int(like_v.shape[0])
+        self.v2, self.qn, self.q, self.w = z(), z(), z(), z()
+        self._T, self._gamma = integ._T_device, integ._gamma_device
+        self.rng = torch.zeros(2, dtype=torch.int64, device=dev)
+        self._rng_val = (0, 0)
+        self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.gpart = torch.zeros(int(_lib.load().mdg_lgv_blocks(self.n)), device=dev)
+        self.gbar = torch.zeros(1, device=dev)
+
+    def set_rng(self, seed, step0):
+        """The noise stream of the next launches (a copy into the device words: captured graphs follow)."""
+        if self._rng_val != (int(seed), int(step0)):
+            self._rng_val = (int(seed), int(step0))
+            self.rng.copy_(_rng_words(seed, step0, "cpu"))
+
+    def kick(self, v, q, f, t, k):
+        check(_lib.load().mdg_lgv_kick(ptr(v), ptr(q), ptr(f), ptr(self.mass), ptr(self._gamma()), ptr(self._T()), ptr(t), ptr(k),
+                                       ptr(self.rng), self.n, ptr(self.v2), ptr(self.qn), stream_ptr(v.device)), "mdg_lgv_kick")
+        _touched(self.qn)
+        return self.qn
+
+    def finish(self, v, q, f, fn, t, k, out, advance=False):
+        """advance: the launch also sets k <- k + 1."""
+        check(_lib.load().mdg_lgv_finish(ptr(v), ptr(q), ptr(f), ptr(self.v2), ptr(self.qn), ptr(fn.contiguous()), ptr(self.mass),
+                                         ptr(t), ptr(k), int(bool(advance)), self.n, ptr(out[0]), ptr(out[1]), ptr(self.ticket),
+                                         stream_ptr(v.device)), "mdg_lgv_finish")
+        _touched(v, q, f, *out)
+        if advance:
+            _touched(k)
+
+    def adj_pre(self, ans, lv, t, i):
+        check(_lib.load().mdg_lgv_adj_pre(ptr(ans[1]), ptr(lv), ptr(self.mass), ptr(t), ptr(i), self.n, ptr(self.q), ptr(self.w),
+                                          stream_ptr(lv.device)), "mdg_lgv_adj_pre")
+        _touched(self.q, self.w)
+        return self.q, self.w
+
+    def adj_step(self, ans, lam, f, dwf, t, i, gout, want_gamma=False, advance=False):
+        """advance: the launch also sets i <- i - 1.  Returns (q_{i-1}, the merged w of the next force-vjp)."""
+        check(_lib.load().mdg_lgv_adj_step(ptr(ans[0]), ptr(ans[1]), ptr(f.contiguous()), ptr(dwf.contiguous()), ptr(self.mass),
+                                           ptr(self._gamma()), ptr(self._T()), ptr(t), ptr(i), int(bool(advance)), ptr(self.rng),
+                                           ptr(gout[0]), ptr(gout[1]), int(bool(want_gamma)), self.n, ptr(lam[0]), ptr(lam[1]),
+                                           ptr(self.q), ptr(self.w), ptr(self.gpart), ptr(self.ticket), stream_ptr(f.device)),
+              "mdg_lgv_adj_step")
+        _touched(lam[0], lam[1], self.q, self.w)
+        if advance:
+            _touched(i)
+        return self.q, self.w
+
+    def gamma_bar(self):
+        """The friction gradient of the sweep since the last `gpart.zero_()`: the slots added in slot order."""
+        check(_lib.load().mdg_lgv_gamma_sum(ptr(self.gpart), self.n, ptr(self.gbar), stream_ptr(self.gbar.device)),
+              "mdg_lgv_gamma_sum")
+        return self.gbar.clone()
+
+
 # ----------------------------------------------------------------------------- graph ops (SchNet)
 class GraphTopo:
     """Edge topology for the message-passing kernels: ELL list + undirected edge ids + the

@@ -181,11 +181,110 @@ class Verlet(FixedGridODESolver):
         return eager()
 
 
-SOLVERS = {'rk4': RK4, 'NH_verlet': NHVerlet, 'verlet': Verlet}
+def baoab_coefficients(gamma, h):
+    """c1 = exp(-gamma h), c2 = sqrt(-expm1(-2 gamma h)) of the O step (md.Langevin)."""
+    return torch.exp(-gamma * h), torch.sqrt(-torch.expm1(-2.0 * gamma * h))
+
+
+def baoab_kick(func, v, q, F, h, xi, gamma):
+    """B, A, O, A of one BAOAB step (md.Langevin) in torch ops: (velocity after O, q_{k+1})."""
+    m = func.mass[:, None].to(v.dtype)
+    hh = 0.5 * h
+    c1, c2 = baoab_coefficients(gamma, h)
+    v1 = v + hh * F / m
+    q1 = q + hh * v1
+    v2 = c1 * v1 + c2 * torch.sqrt(float(func.T) / m) * xi
+    return v2, q1 + hh * v2
+
+
+class BAOAB(FixedGridODESolver):
+    """Langevin dynamics by the BAOAB splitting (md.Langevin documents the scheme): not an ODE right-hand side, so the
+    solver runs the integrator's own loop -- one force evaluation per step, the mdg_lgv_* kernels and HIP-graph replay
+    where they apply, torch ops otherwise."""
+
+    def step_func(self, func, t, dt, y):
+        raise ValueError("'baoab' integrates an md.Langevin integrator only: a generic right-hand side has no BAOAB step")
+
+    def integrate(self, t):
+        func, y0 = self.func, self.y0
+        if getattr(func, "_method", None) != 'baoab':
+            self.step_func(func, None, None, y0)
+        if len(y0) != 2:
+            raise ValueError("'baoab' takes the state (velocities, positions), got %d tensors" % len(y0))
+        if not bool((t[1:] > t[:-1]).all()):
+            raise AssertionError("t must be strictly increasing: Langevin dynamics are not run backwards")
+        t = t.type_as(y0[0]).to(y0[0].device)
+        T = t.shape[0]
+        seed, step0 = func.seed, func.step0
+        func._last_noise = (seed, step0)              # what OdeintAdjointMethod keeps for its backward pass
+        func.step0 = step0 + T - 1                    # the next integration continues the stream
+        v, q = y0
+        if torch.is_grad_enabled():
+            # plain backpropagation through the steps (adjoint = False): every op stays in the autograd graph
+            if not q.requires_grad:
+                q = q.detach().requires_grad_(True)
+            gamma = func.gamma.to(v.dtype)
+            frames = [(v, q)]
+            F = func.force_graph(q)
+            for k in range(T - 1):
+                h = t[k + 1] - t[k]
+                v2, q = baoab_kick(func, v, q, F, h, func.noise(seed, step0 + k, v), gamma)
+                F = func.force_graph(q)
+                v = v2 + 0.5 * h * F / func.mass[:, None].to(v.dtype)
+                frames.append((v, q))
+            return tuple(torch.stack([f[i] for f in frames]) for i in range(2))
+        if func.lgv_steps_ok(v, q):
+            out = None
+            if graphs.enabled(func) and T > 3:
+                out = graphs.forward(func, (v, q), t, noise=(seed, step0))      # HIP-graph replay, one launch per step
+                if out is None:
+                    out = graphs.eager_static(func, lambda: _lgv_forward(func, (v, q), t, seed, step0), lambda o: o[1][-1])
+            return out if out is not None else _lgv_forward(func, (v, q), t, seed, step0)
+        gamma = func.gamma.detach().to(v.dtype)
+        frames = [(v, q)]
+        F = func.force(q)
+        for k in range(T - 1):
+            h = t[k + 1] - t[k]
+            v2, q = baoab_kick(func, v, q, F, h, func.noise(seed, step0 + k, v), gamma)
+            F = func.force(q)
+            v = v2 + 0.5 * h * F / func.mass[:, None].to(v.dtype)
+            frames.append((v, q))
+        return tuple(torch.stack([f[i] for f in frames]) for i in range(2))
+
+
+def _lgv_forward(func, y0, t, seed, step0):
+    """The loop of BAOAB.integrate with each half of a step as ONE launch (csrc/langevin.hip mdg_lgv_kick / mdg_lgv_finish)
+    around the force evaluation."""
+    v, q = (x.clone() for x in y0)
+    T = t.shape[0]
+    out = [torch.empty((T,) + tuple(x.shape), device=x.device, dtype=x.dtype) for x in y0]
+    for o, x in zip(out, y0):
+        o[0].copy_(x)
+    F = func.force(q).contiguous().clone()
+    w = func.lgv_work(v)
+    w.set_rng(seed, step0)
+    k = torch.zeros(1, dtype=torch.int64, device=v.device)
+    t = t.contiguous()
+    for _ in range(T - 1):
+        qn = w.kick(v, q, F, t, k)
+        w.finish(v, q, F, func.force(qn), t, k, out, advance=True)              # (k <- k + 1 inside the launch)
+    return tuple(out)
+
+
+SOLVERS = {'rk4': RK4, 'NH_verlet': NHVerlet, 'verlet': Verlet, 'baoab': BAOAB}
+
+
+def _check_pairing(func, method):
+    """A Langevin integrator runs with 'baoab' and nothing else does."""
+    of_func = getattr(func, "_method", None)
+    if (of_func == 'baoab') != (method == 'baoab'):
+        raise ValueError("method %r does not integrate %s: md.Langevin goes with method='baoab', and 'baoab' with nothing else"
+                         % (method, type(func).__name__))
 
 
 def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None):
     """sovlers.py:171-193 (generic path)."""
+    _check_pairing(func, method)
     tensor_input, func, y0, t = _check_inputs(func, y0, t)
     if options is None:
         options = {}
@@ -238,6 +337,8 @@ class OdeintAdjointMethod(torch.autograd.Function):
         ctx.func, ctx.solver = func, dict(rtol=rtol, atol=atol, method=method, options=options)
         with torch.no_grad():
             frames = odeint(func, tuple(y0), t, **ctx.solver)
+        if method == 'baoab':
+            ctx.noise = func._last_noise               # (seed, step0) of this pass: the backward regenerates its xi_k
         ctx.save_for_backward(t, flat_params, *frames)
         return frames
 
@@ -247,7 +348,12 @@ class OdeintAdjointMethod(torch.autograd.Function):
         frames, n = tuple(saved), len(saved)
         func, solver = ctx.func, ctx.solver
         wants_time = ctx.needs_input_grad[n + 1]
-        closed_form = (not wants_time) and getattr(func, "supports_rhs_vjp", lambda: False)()
+        if solver["method"] == 'baoab':
+            if wants_time:
+                raise RuntimeError("Langevin ('baoab'): no gradient with respect to the time grid (nor to T); pass a `t` "
+                                   "that does not require grad")
+            return _analytic_langevin_adjoint(func, t, frames, cotangents, flat_params, ctx.noise)
+        closed_form =(not wants_time) and getattr(func, "supports_rhs_vjp", lambda: False)()
         if closed_form and solver["method"] == 'NH_verlet' and n == 3:
             return _analytic_nhc_adjoint(func, t, frames, cotangents, flat_params)
         if closed_form and solver["method"] == 'verlet' and n == 2 and getattr(func, "analytic_verlet", True) is not False:
@@ -393,6 +499,105 @@ def _analytic_nve_adjoint(func, t, ans, grad_output, flat_params):
         return (*out[0], None, None, out[1], None, None, None, None, None)
 
 
+def _gamma_slot(func):
+    """Offset of a trainable friction in the flat parameter vector, or None."""
+    off = 0
+    for p in func.parameters():
+        if p is func.gamma:
+            return off
+        off += p.numel()
+    return None
+
+
+def _analytic_langevin_adjoint(func, t, ans, grad_output, flat_params, noise):
+    """Exact discrete adjoint of the BAOAB map (md.Langevin) over the saved frames, for the noise sequence of the forward
+    pass: per interval B+, A+, O+, A+, B+, with the closing B+ of interval i-1 and the opening B+ of interval i -- both at
+    q_{i-1}, both linear in w -- merged into one force-vjp:  T evaluations for T - 1 intervals.
+
+        at frame i:   lam_q += H(q_i) w ,  theta_bar += d(w.F)/dtheta          (w carries the (h/2)/m of both B+)
+        A+:           lam_v += (h/2) lam_q
+        O+:           gamma_bar += lam_v . h (sqrt(T/m) xi / c2 - v2) ,  lam_v *= c1     (v2 = v_i - (h/2) F(q_i)/m)
+        A+:           lam_v += (h/2) lam_q
+        w  = (h/2) lam_v / m ;  lam += dL/dy_{i-1} ;  w += (h'/2) lam_v / m  (h' = t[i-1] - t[i-2], not at frame 0)"""
+    seed, step0 = noise
+    with torch.no_grad():
+        T = ans[0].shape[0]
+        slot = _gamma_slot(func) if getattr(func, "trainable_gamma", False) else None
+        n_flat = sum(p.numel() for p in func.parameters())
+
+        def eager():
+            lam = [g[-1].clone() for g in grad_output]
+            gth = torch.zeros(n_flat, dtype=lam[0].dtype, device=lam[0].device)
+            if T == 1:
+                return lam, gth
+            if func.lgv_steps_ok(*lam):
+                w = func.lgv_work(lam[0])
+                w.set_rng(seed, step0)
+                w.gpart.zero_()
+                frames = [a.contiguous() for a in ans]
+                gout = [g.contiguous() for g in grad_output]
+                tc = t.to(device=lam[0].device, dtype=lam[0].dtype).contiguous()
+                idx = torch.full((1,), T - 1, dtype=torch.int64, device=lam[0].device)
+                q, wv = w.adj_pre(frames, lam[0], tc, idx)
+                for _ in range(T - 1, 0, -1):
+                    func.update_topology(q)
+                    F, dwf, th = func.model.force_vjp(q, wv)
+                    if th:
+                        gth.add_(_flatten(func.theta_in_parameter_order(th)))
+                    q, wv = w.adj_step(frames, lam, F, dwf, tc, idx, gout, want_gamma=slot is not None, advance=True)
+                func.update_topology(q)
+                _, dwf, th = func.model.force_vjp(q, wv)
+                if th:
+                    gth.add_(_flatten(func.theta_in_parameter_order(th)))
+                lam[1].add_(dwf)
+                if slot is not None:
+                    gth[slot:slot + 1].add_(w.gamma_bar())
+                return lam, gth
+            lv, lq = lam
+            tt = t.to(device=lv.device, dtype=lv.dtype)
+            m = func.mass[:, None].to(lv.dtype)
+            gamma = func.gamma.detach().to(lv.dtype)
+            s = torch.sqrt(float(func.T) / m)
+            gbar = torch.zeros((), dtype=lv.dtype, device=lv.device)
+            w = 0.5 * (tt[T - 1] - tt[T - 2]) * lv / m
+            for i in range(T - 1, 0, -1):
+                h = tt[i] - tt[i - 1]
+                hh = 0.5 * h
+                c1, c2 = baoab_coefficients(gamma, h)
+                F, dwf, th = func.force_and_vjp(ans[1][i], w)
+                if th:
+                    gth = gth + _flatten(th)
+                lq = lq + dwf
+                lv = lv + hh * lq
+                if slot is not None:
+                    v2 = ans[0][i] - hh * F / m
+                    gbar = gbar + (lv * (h * (s * func.noise(seed, step0 + i - 1, lv) / c2 - v2))).sum()
+                lv = c1 * lv
+                lv = lv + hh * lq
+                w = hh * lv / m
+                lv = lv + grad_output[0][i - 1]
+                lq = lq + grad_output[1][i - 1]
+                if i >= 2:
+                    w = w + 0.5 * (tt[i - 1] - tt[i - 2]) * lv / m
+            _, dwf, th = func.force_and_vjp(ans[1][0], w)
+            if th:
+                gth = gth + _flatten(th)
+            lq = lq + dwf
+            if slot is not None:
+                gth[slot] = gth[slot] + gbar
+            return [lv, lq], gth
+
+        out = None
+        if T > 3 and func.lgv_steps_ok(grad_output[0][-1].contiguous(), grad_output[1][-1].contiguous()) and graphs.enabled(func):
+            out = graphs.adjoint(func, t, ans, grad_output, n_flat, noise=noise)       # one graph launch per interval
+            if out is None:
+                out = graphs.eager_static(func, eager, lambda o: ans[1][0])
+        if out is None:
+            out = eager()
+        gth = out[1] if flat_params.numel() else torch.zeros_like(flat_params)
+        return (*out[0], None, None, gth, None, None, None, None, None)
+
+
 def _fused_spec_for(func, method):
     get = getattr(func, "fused_spec", None)
     if get is None:
@@ -404,6 +609,7 @@ def odeint_adjoint(func, y0, t, rtol=1e-6, atol=1e-12, method=None, options=None
     """sovlers.py:296-324.  Dispatches to the fused HIP trajectory when `func` allows it."""
     if not isinstance(func, nn.Module):
         raise ValueError('func is required to be an instance of nn.Module.')
+    _check_pairing(func, method)
     spec = _fused_spec_for(func, method) if (isinstance(y0, (tuple, list)) and not options) else None
     if spec is not None:
         flat_params = spec.flat_params()

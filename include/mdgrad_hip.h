@@ -1437,6 +1437,44 @@ int mdg_bond_order_bwd(const float* pos, int n_frames, int n_atoms, const MdgCel
                        const float* gn, float* g_xyz, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * K31  pair potential energy of every frame and its gradient (mdgrad_amd/thermo.py PotentialEnergy; the energy side of
+ *      trajectory reweighting, mdgrad_amd/reweight.py; csrc/energy.hip on the sweeps of csrc/frame_pairs.hpp)
+ *   pos, cell, terms, theta, the pair set and the three kernel shapes: as K15.
+ *   U[f] = sum_terms sum_pairs phi(r), the plain truncated phi (no shift): the value PairPotentials gives for frame f.
+ *   fwd: U[n_frames], every unordered pair once.
+ *   bwd: given gU[n_frames] = dL/dU.  g_pos and g_theta are each nullable (not both):
+ *        g_pos != null   full rows: g_pos [n_frames, n_atoms, 3] = -gU_f sum_j phi'(r) (x_j - x_i) / r, and g_theta (when not
+ *                        null) = sum_f gU_f sum_pairs dphi/dtheta from half of each visit
+ *        g_pos == null   parameters only (the frames are constants, as in reweighting): the forward's once-per-pair sweep
+ *                        accumulating g_theta[n_theta_total] alone -- half the pair visits, no position written
+ *   workspace: mdg_energy_frames_workspace() floats, shared by both calls.  Fixed-order sums, no floating-point atomics:
+ *   bitwise reproducible.  Tabulated terms (MDG_PAIR_TABLE) are refused: their energy is not tabulated.
+ */
+int64_t mdg_energy_frames_workspace(int n_frames, int n_atoms, int n_theta_total);
+int mdg_energy_frames_fwd(const float* pos, int n_frames, int n_atoms, const MdgCell* cell /*host*/, const MdgTerms* terms /*host*/,
+                          const float* theta, float* U, float* workspace, void* stream);
+int mdg_energy_frames_bwd(const float* pos, int n_frames, int n_atoms, const MdgCell* cell /*host*/, const MdgTerms* terms /*host*/,
+                          const float* theta, const float* gU, float* g_pos, float* g_theta, float* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * K32  smeared pair count of every frame and its gradient (mdgrad_amd/observable.py rdf.per_frame; csrc/rdf_frames.hip):
+ *      the rows whose sum over frames K4 returns
+ *   pos [n_frames, n_atoms, 3], n_atoms <= 1024; the cell must be diagonal; mask: nullable [n_atoms, n_atoms] uint8 selection
+ *   (symmetric); mu [nbins] DEVICE: equally spaced ascending centres, spacing = mu[1] - mu[0] > 0; coeff < 0; 2 <= nbins <= 1024.
+ *     raw[f, k] = sum_{i<j, 0 < d^2 < cutoff^2} exp(coeff (d - mu_k)^2)
+ *   over the 2R + 1 centres around the nearest one, R = ceil(5.3 / (s spacing)), s = sqrt(-coeff log2 e): a dropped term is
+ *   <= 2^-28.1 of a peak term.
+ *   fwd: raw [n_frames, nbins].  A frame belongs to one wave (n_atoms <= 128) or workgroup; its contributions are summed as
+ *        fixed-point integers in LDS: bitwise reproducible, no global atomics.
+ *   bwd: given g_raw [n_frames, nbins], writes g_xyz [n_frames, n_atoms, 3] = d(sum_fk g_raw raw)/d pos; atom-centric full
+ *        rows, no atomics.  A frame whose g_raw row is zero gets zeros.
+ */
+int mdg_rdf_frames_fwd(const float* pos, int n_frames, int n_atoms, const MdgCell* cell /*host*/, float cutoff, const uint8_t* mask,
+                       const float* mu, float spacing, float coeff, int nbins, float* raw, void* stream);
+int mdg_rdf_frames_bwd(const float* pos, int n_frames, int n_atoms, const MdgCell* cell /*host*/, float cutoff, const uint8_t* mask,
+                       const float* mu, float spacing, float coeff, int nbins, const float* g_raw, float* g_xyz, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * f4  bonded terms over a static topology table (csrc/bonded.hip).
  * Replaces torchmd/interface.py:447-455 (BondPotentials.forward: harmonic in the SQUARED bond length,
  * 1/2 k (|b|^2 - ro)^2) and :496-508 (AnglePotentials.forward: 1/2 k (theta - theta0)^2 over triples (i, j, k) centred on

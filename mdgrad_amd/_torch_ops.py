@@ -8,7 +8,8 @@ import torch
 from . import _lib
 
 PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libmdgrad_torch.so")
-OPS = ("nbr_build", "pair_force", "pair_hvp", "nhc_vv_forward", "nhc_vv_adjoint", "rdf_fwd", "rdf_bwd", "adf_fwd", "adf_bwd", "virial_fwd", "virial_bwd", "sk_fwd", "sk_bwd", "msd_fwd", "msd_bwd", "isf_fwd", "isf_bwd", "bond_order_fwd", "bond_order_bwd", "edge_geom",
+OPS = ("nbr_build", "pair_force", "pair_hvp", "nhc_vv_forward", "nhc_vv_adjoint", "rdf_fwd", "rdf_bwd", "adf_fwd", "adf_bwd", "virial_fwd", "virial_bwd",
+       "energy_frames_fwd", "energy_frames_bwd", "rdf_frames_fwd", "rdf_frames_bwd", "sk_fwd", "sk_bwd", "msd_fwd", "msd_bwd", "isf_fwd", "isf_bwd", "bond_order_fwd", "bond_order_bwd", "edge_geom",
        "dihedral_eval", "dihedral_phi_fwd", "dihedral_phi_bwd", "dihedral_hist_fwd", "dihedral_hist_bwd",
        "coulomb_eval", "coulomb_charge_reduce", "ewald_eval", "ewald_excl_eval", "sw_eval", "eam_eval", "tersoff_eval",
        "tersoff_multi_eval", "eam_table_eval", "sw_multi_eval",

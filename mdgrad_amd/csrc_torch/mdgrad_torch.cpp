@@ -27,6 +27,8 @@
 //   sw_multi_eval    K28  interface.py StillingerWeberMulti -> mdg_sw_multi_eval
 //   eam_table_eval   K27  interface.py EAM                  -> mdg_eam_table_eval
 //   bond_order_fwd/_bwd  K29  observable.py bond_order      -> mdg_bond_order_fwd / mdg_bond_order_bwd
+//   energy_frames_fwd/_bwd  K31  thermo.py PotentialEnergy  -> mdg_energy_frames_fwd / mdg_energy_frames_bwd
+//   rdf_frames_fwd/_bwd  K32  observable.py rdf.per_frame   -> mdg_rdf_frames_fwd / mdg_rdf_frames_bwd
 //   dihedral_phi_fwd/_bwd, dihedral_hist_fwd/_bwd  K19  observable.py Dihedrals / dihedral_distribution -> mdg_dihedral_phi_* / _hist_*
 //   edge_geom(+_bwd) schnet.py:142                          -> mdg_edge_geom / mdg_edge_geom_bwd
 //   cfconv_fwd/_bwd  K9+K10 modules.py:531-571              -> mdg_cfconv_fwd(_bf16) / mdg_cfconv_bwd(_bf16)
@@ -387,6 +389,67 @@ std::tuple<Tensor, Tensor> virial_bwd(const Tensor& pos, at::ArrayRef<double> ce
     ok(mdg_virial_bwd(fptr(pos), F, N, &c, &ts, fptr(theta, "theta"), fptr(gW), mptr(g), K ? mptr(gth) : nullptr, mptr(ws),
                       stream_of(pos)));
     return {g, gth};
+}
+
+// ------------------------------------------------------------------------------------------------ K31
+// arguments as K15; U [F]
+Tensor energy_frames_fwd(const Tensor& pos, at::ArrayRef<double> cell, at::ArrayRef<int64_t> terms_i, at::ArrayRef<double> terms_f,
+                         const c10::List<c10::optional<Tensor>>& masks, const OptTensor& theta) {
+    const MdgTerms ts = virial_terms(pos, terms_i, terms_f, masks, theta);
+    const MdgCell c = make_cell(cell);
+    const int F = (int)pos.size(0), N = (int)pos.size(1);
+    Tensor U = at::empty({F}, pos.options()), ws = at::empty({mdg_energy_frames_workspace(F, N, ts.n_theta_total)}, pos.options());
+    ok(mdg_energy_frames_fwd(fptr(pos), F, N, &c, &ts, fptr(theta, "theta"), mptr(U), mptr(ws), stream_of(pos)));
+    return U;
+}
+// (g_pos [F,N,3], g_theta [K]); want_pos = false: the parameters-only sweep, g_pos comes back empty
+std::tuple<Tensor, Tensor> energy_frames_bwd(const Tensor& pos, at::ArrayRef<double> cell, at::ArrayRef<int64_t> terms_i,
+                                             at::ArrayRef<double> terms_f, const c10::List<c10::optional<Tensor>>& masks,
+                                             const OptTensor& theta, const Tensor& gU, bool want_pos) {
+    const MdgTerms ts = virial_terms(pos, terms_i, terms_f, masks, theta);
+    check_f32(gU, "gU"); same_device(pos, gU, "gU");
+    TORCH_CHECK(gU.numel() == pos.size(0), "mdgrad: gU must have one entry per frame");
+    const MdgCell c = make_cell(cell);
+    const int F = (int)pos.size(0), N = (int)pos.size(1), K = ts.n_theta_total;
+    TORCH_CHECK(want_pos || K > 0, "mdgrad: nothing to compute (no position gradient wanted and the terms hold no parameters)");
+    Tensor g = want_pos ? at::empty_like(pos) : at::empty({0}, pos.options()), gth = at::empty({K}, pos.options());
+    Tensor ws = at::empty({mdg_energy_frames_workspace(F, N, K)}, pos.options());
+    ok(mdg_energy_frames_bwd(fptr(pos), F, N, &c, &ts, fptr(theta, "theta"), fptr(gU), want_pos ? mptr(g) : nullptr,
+                             K ? mptr(gth) : nullptr, mptr(ws), stream_of(pos)));
+    return {g, gth};
+}
+
+// ------------------------------------------------------------------------------------------------ K32
+const uint8_t* rdf_frames_check(const Tensor& xyz, const OptTensor& mask, const Tensor& mu) {
+    check_f32(xyz, "xyz"); check_f32(mu, "mu"); same_device(xyz, mu, "mu");
+    TORCH_CHECK(xyz.dim() == 3 && xyz.size(2) == 3, "mdgrad: xyz must be [F,N,3]");
+    if (!(mask.has_value() && mask->defined())) return nullptr;
+    same_device(xyz, *mask, "mask");
+    TORCH_CHECK(mask->scalar_type() == at::kByte && mask->is_contiguous() && mask->numel() == xyz.size(1) * xyz.size(1),
+                "mdgrad: mask must be a contiguous uint8 [N,N] tensor");
+    return mask->data_ptr<uint8_t>();
+}
+Tensor rdf_frames_fwd(const Tensor& xyz, at::ArrayRef<double> cell, double cutoff, const OptTensor& mask, const Tensor& mu,
+                      double spacing, double coeff) {
+    const uint8_t* mk = rdf_frames_check(xyz, mask, mu);
+    const MdgCell c = make_cell(cell);
+    const int F = (int)xyz.size(0), N = (int)xyz.size(1), B = (int)mu.numel();
+    Tensor raw = at::empty({F, B}, xyz.options());
+    ok(mdg_rdf_frames_fwd(fptr(xyz), F, N, &c, (float)cutoff, mk, fptr(mu), (float)spacing, (float)coeff, B, mptr(raw),
+                          stream_of(xyz)));
+    return raw;
+}
+Tensor rdf_frames_bwd(const Tensor& xyz, at::ArrayRef<double> cell, double cutoff, const OptTensor& mask, const Tensor& mu,
+                      double spacing, double coeff, const Tensor& g_raw) {
+    const uint8_t* mk = rdf_frames_check(xyz, mask, mu);
+    check_f32(g_raw, "g_raw"); same_device(xyz, g_raw, "g_raw");
+    const MdgCell c = make_cell(cell);
+    const int F = (int)xyz.size(0), N = (int)xyz.size(1), B = (int)mu.numel();
+    TORCH_CHECK(g_raw.numel() == (int64_t)F * B, "mdgrad: g_raw must be [F, nbins]");
+    Tensor g = at::empty_like(xyz);
+    ok(mdg_rdf_frames_bwd(fptr(xyz), F, N, &c, (float)cutoff, mk, fptr(mu), (float)spacing, (float)coeff, B, fptr(g_raw), mptr(g),
+                          stream_of(xyz)));
+    return g;
 }
 
 // ------------------------------------------------------------------------------------------------ K16
@@ -1136,6 +1199,12 @@ TORCH_LIBRARY(mdgrad, m) {
     m.def("virial_fwd(Tensor pos, float[] cell, int[] terms_i, float[] terms_f, Tensor?[] masks, Tensor? theta) -> Tensor");
     m.def("virial_bwd(Tensor pos, float[] cell, int[] terms_i, float[] terms_f, Tensor?[] masks, Tensor? theta, Tensor gW) -> "
           "(Tensor, Tensor)");
+    m.def("energy_frames_fwd(Tensor pos, float[] cell, int[] terms_i, float[] terms_f, Tensor?[] masks, Tensor? theta) -> Tensor");
+    m.def("energy_frames_bwd(Tensor pos, float[] cell, int[] terms_i, float[] terms_f, Tensor?[] masks, Tensor? theta, Tensor gU, "
+          "bool want_pos) -> (Tensor, Tensor)");
+    m.def("rdf_frames_fwd(Tensor xyz, float[] cell, float cutoff, Tensor? mask, Tensor mu, float spacing, float coeff) -> Tensor");
+    m.def("rdf_frames_bwd(Tensor xyz, float[] cell, float cutoff, Tensor? mask, Tensor mu, float spacing, float coeff, "
+          "Tensor g_raw) -> Tensor");
     m.def("sk_fwd(Tensor pos, float[] cell, Tensor? weights, float norm, Tensor kvec, Tensor seg, int[] seg_host) -> Tensor");
     m.def("sk_bwd(Tensor pos, float[] cell, Tensor? weights, float norm, Tensor kvec, Tensor seg, int[] seg_host, Tensor gS) -> "
           "Tensor");
@@ -1199,6 +1268,10 @@ TORCH_LIBRARY_IMPL(mdgrad, CUDA, m) {      // (the HIP backend registers under t
     m.impl("bond_order_bwd", bond_order_bwd);
     m.impl("virial_fwd", virial_fwd);
     m.impl("virial_bwd", virial_bwd);
+    m.impl("energy_frames_fwd", energy_frames_fwd);
+    m.impl("energy_frames_bwd", energy_frames_bwd);
+    m.impl("rdf_frames_fwd", rdf_frames_fwd);
+    m.impl("rdf_frames_bwd", rdf_frames_bwd);
     m.impl("sk_fwd", sk_fwd);
     m.impl("sk_bwd", sk_bwd);
     m.impl("msd_fwd", msd_fwd);

@@ -1,6 +1,7 @@
 """Observables with the reference's interface (torchmd/observable.py): generate_vol_bins
 :10-21, Observable :24-31, rdf :33-76, vacf :153-163.  The pair search + Gaussian smearing +
-histogram of rdf.forward is one HIP op (ops.RdfRawFn, csrc/rdf.hip); vacf is one fused reduction over the
+histogram of rdf.forward is one HIP op (ops.RdfRawFn, csrc/rdf.hip), and rdf.per_frame keeps the frames' rows of it
+(ops.RdfFramesFn, csrc/rdf_frames.hip; rdf.normalise is forward's tail); vacf is one fused reduction over the
 velocity trajectory (ops.VacfFn, csrc/observe.hip).  angle_distribution :120-151 (with Angles :89-118 and
 compute_angle :166-179): the triplet search + Gaussian smearing + histogram and its gradient are one HIP op
 (ops.AdfRawFn, csrc/adf.hip); the per-triplet angles are torch ops over the device-built angle list.  structure_factor has no
@@ -123,6 +124,63 @@ class rdf(Observable):
         count = count / norm
         rdf = count / (self.vol_bins / self.V)
         return count, self.bins, rdf
+
+    # -- the rows of the sum above: what a weighted average over frames needs (reweight.Reweighting) --------------------
+    PER_FRAME_MAX_ATOMS = ops.RDF_FRAMES_MAX_ATOMS
+    PER_FRAME_MAX_BINS = ops.RDF_FRAMES_MAX_BINS
+
+    def per_frame(self, xyz):
+        """raw[..., k] = sum_{i<j, 0<d<cutoff_boundary} exp(coeff (d - mu_k)^2), the smeared pair count of every frame of xyz
+        ([N, 3], [T, N, 3], [R, T, N, 3] or replica-stacked [..., k N, 3] giving a trailing k before the bins), with the
+        observable's index_tuple selection.  `forward`'s histogram is the sum of these rows; `normalise` turns a row, a sum or
+        a weighted average of rows into an RDF.  float32 device positions run one HIP launch (ops.RdfFramesFn,
+        csrc/rdf_frames.hip); host or float64 positions take the torch restatement with the exact sum.  Differentiable once
+        with respect to xyz.  At most 1024 atoms, a diagonal cell, 2 <= nbins <= 1024."""
+        n = xyz.shape[-2] if xyz.dim() >= 2 else 0
+        if n == 0 or xyz.shape[-1] != 3 or n % self.natoms:
+            raise ValueError("rdf.per_frame: xyz must be [..., k * %d, 3], got %s" % (self.natoms, tuple(xyz.shape)))
+        if self.natoms > self.PER_FRAME_MAX_ATOMS:
+            raise ValueError("rdf.per_frame: at most %d atoms per frame, got %d" % (self.PER_FRAME_MAX_ATOMS, self.natoms))
+        if not 2 <= self.nbins <= self.PER_FRAME_MAX_BINS:
+            raise ValueError("rdf.per_frame: nbins must be in [2, %d], got %d" % (self.PER_FRAME_MAX_BINS, self.nbins))
+        if not self._cell_struct.diag:
+            raise ValueError("rdf.per_frame: the cell must be diagonal")
+        k = n // self.natoms
+        lead = tuple(xyz.shape[:-2]) + ((k,) if k > 1 else ())
+        x = xyz.reshape(-1, self.natoms, 3)
+        if x.is_cuda and x.dtype == torch.float32:
+            raw = ops.RdfFramesFn.apply(x, self.offsets, self.spacing, self.coeff, self.cutoff_boundary, self._cell_struct,
+                                        self._mask)
+        else:
+            raw = self._torch_per_frame(x)
+        return raw.reshape(lead + (self.nbins,))
+
+    def _torch_per_frame(self, x, budget=1 << 16):
+        """The same rows by torch ops in x's dtype on x's device: all pairs, every centre (no reach), chunked over frames."""
+        F, N = x.shape[0], x.shape[1]
+        iu = torch.triu_indices(N, N, offset=1, device=x.device)
+        if self._mask is not None:
+            iu = iu[:, self._mask.to(x.device).bool()[iu[0], iu[1]]]
+        L, mu = self.cell.detach().to(x), self.offsets.detach().to(x)
+        out = []
+        step = max(1, budget // max(1, iu.shape[1]))
+        for a in range(0, F, step):
+            xa = x[a:a + step]
+            D = xa[:, iu[1]] - xa[:, iu[0]]
+            s = D.detach() * (1.0 / L)
+            D = D + (-(s > 0.5).to(x) + (s < -0.5).to(x)) * L
+            d2 = D.pow(2).sum(-1)
+            keep = (d2.detach() < self.cutoff_boundary ** 2) & (d2.detach() != 0)
+            fi, pi = torch.nonzero(keep, as_tuple=True)
+            e = torch.exp(self.coeff * (d2[fi, pi].sqrt()[:, None] - mu[None, :]).pow(2))
+            out.append(x.new_zeros(xa.shape[0], self.nbins).index_add(0, fi, e))
+        return torch.cat(out)
+
+    def normalise(self, raw):
+        """(count, bins, g) of a smeared pair count raw[..., k] -- a row of `per_frame`, their sum or a weighted average of
+        them -- by the tail of `forward`: count = raw / raw.sum(-1), g = count / (vol_bins / V)."""
+        count = raw / raw.sum(-1, keepdim=True)
+        return count, self.bins, count / (self.vol_bins.to(raw) / self.V)
 
 
 def compute_angle(xyz, angle_list, cell, N):

@@ -6,6 +6,8 @@ torch.autograd.Function wrappers that own the differentiation contract
     RdfRawFn                                                    soft histogram
     AdfRawFn                                                    soft histogram of bond angles
     VirialFn                                                    pair virial of every frame (pressure)
+    EnergyFramesFn                                              pair potential energy of every frame (reweighting)
+    RdfFramesFn                                                 soft histogram of every frame
     SkFn                                                        static structure factor of every frame
     MsdFn                                                       mean-squared displacement over all lags (+ fourth moment)
     IsfFn                                                       intermediate scattering functions F(k,t), F_s(k,t)
@@ -2187,6 +2189,97 @@ class VirialFn(torch.autograd.Function):
         check(lib.mdg_virial_bwd(ptr(x3), F, N, C.byref(cell_struct), C.byref(terms), ptr(th) if K else None, ptr(g), ptr(gx),
                                  ptr(gth), ptr(ws), stream_ptr(x3.device)), "mdg_virial_bwd")
         return gx.reshape(xshape), (gth.reshape(tshape) if K else None), None, None, None
+
+
+# ----------------------------------------------------------------------------- pair energy of every frame (reweighting)
+class EnergyFramesFn(torch.autograd.Function):
+    """U[f] = sum_terms sum_pairs phi(r) of every frame of xyz [F, N, 3] (csrc/energy.hip, K31): the kernel side of
+    thermo.PotentialEnergy.  theta, terms, masks: as VirialFn.  Differentiable once.  The backward pass runs the full-row
+    sweep when the positions need a gradient and the once-per-pair parameters-only sweep otherwise (detached frames: the
+    reweighting case); `EnergyFramesFn.last_route` names the one the last backward pass took ("full" | "theta")."""
+
+    last_route = None
+
+    @staticmethod
+    def forward(ctx, xyz, theta, cell_struct, terms, masks):
+        lib = _lib.load()
+        require_gpu(xyz, "xyz")
+        x3 = xyz.detach()
+        x3 = x3 if x3.is_contiguous() else x3.contiguous()
+        F, N = x3.shape[0], x3.shape[1]
+        th = theta.detach().to(device=x3.device, dtype=torch.float32).contiguous()
+        K = th.numel()
+        ws = torch.empty(int(lib.mdg_energy_frames_workspace(F, N, K)), device=x3.device)
+        U = torch.empty(F, device=x3.device)
+        check(lib.mdg_energy_frames_fwd(ptr(x3), F, N, C.byref(cell_struct), C.byref(terms), ptr(th) if K else None, ptr(U),
+                                        ptr(ws), stream_ptr(x3.device)), "mdg_energy_frames_fwd")
+        ctx.args = (cell_struct, terms, masks, xyz.shape, theta.shape)
+        ctx.save_for_backward(x3, th)
+        return U
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gU):
+        lib = _lib.load()
+        x3, th = ctx.saved_tensors
+        cell_struct, terms, masks, xshape, tshape = ctx.args
+        F, N, K = x3.shape[0], x3.shape[1], th.numel()
+        want_x, want_th = ctx.needs_input_grad[0], ctx.needs_input_grad[1] and K > 0
+        if not want_x and not want_th:
+            return None, None, None, None, None
+        g = gU.detach().to(torch.float32).contiguous()
+        ws = torch.empty(int(lib.mdg_energy_frames_workspace(F, N, K)), device=x3.device)
+        gx = torch.empty_like(x3) if want_x else None
+        gth = torch.empty(K, device=x3.device) if want_th else None
+        check(lib.mdg_energy_frames_bwd(ptr(x3), F, N, C.byref(cell_struct), C.byref(terms), ptr(th) if K else None, ptr(g),
+                                        ptr(gx), ptr(gth), ptr(ws), stream_ptr(x3.device)), "mdg_energy_frames_bwd")
+        EnergyFramesFn.last_route = "full" if want_x else "theta"
+        return (gx.reshape(xshape) if want_x else None), (gth.reshape(tshape) if want_th else None), None, None, None
+
+
+# ----------------------------------------------------------------------------- smeared pair count of every frame
+RDF_FRAMES_MAX_ATOMS, RDF_FRAMES_MAX_BINS = 1024, 1024
+
+
+def rdf_frames_reach(spacing, coeff):
+    """R of csrc/rdf_frames.hip: a pair is summed over the 2R + 1 centres around its nearest one, R = ceil(5.3 / (s spacing)),
+    s = sqrt(-coeff log2 e) -- the float32 arithmetic of the library."""
+    f = np.float32
+    s2 = f(-f(coeff) * f(1.4426950408889634))
+    return int(np.ceil(f(5.3) / f(np.sqrt(s2) * f(spacing))))
+
+
+class RdfFramesFn(torch.autograd.Function):
+    """raw[f, k] = sum_{i<j, 0<d<cutoff} exp(coeff (d - mu_k)^2) of every frame of xyz [F, N, 3] (csrc/rdf_frames.hip, K32):
+    the kernel side of observable.rdf.per_frame.  mu [nbins]: equally spaced centres on the device; mask: [N, N] uint8 or
+    None.  Differentiable once with respect to the positions."""
+
+    @staticmethod
+    def forward(ctx, xyz, mu, spacing, coeff, cutoff, cell_struct, mask):
+        lib = _lib.load()
+        require_gpu(xyz, "xyz")
+        x3 = xyz.detach()
+        x3 = x3 if x3.is_contiguous() else x3.contiguous()
+        F, N, B = x3.shape[0], x3.shape[1], mu.numel()
+        raw = torch.empty(F, B, device=x3.device)
+        check(lib.mdg_rdf_frames_fwd(ptr(x3), F, N, C.byref(cell_struct), float(cutoff), ptr(mask), ptr(mu), float(spacing),
+                                     float(coeff), B, ptr(raw), stream_ptr(x3.device)), "mdg_rdf_frames_fwd")
+        ctx.args = (float(spacing), float(coeff), float(cutoff), cell_struct, mask, xyz.shape)
+        ctx.save_for_backward(x3, mu)
+        return raw
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_raw):
+        lib = _lib.load()
+        x3, mu = ctx.saved_tensors
+        spacing, coeff, cutoff, cell_struct, mask, shape = ctx.args
+        F, N, B = x3.shape[0], x3.shape[1], mu.numel()
+        g = g_raw.detach().to(torch.float32).contiguous()
+        gx = torch.empty_like(x3)
+        check(lib.mdg_rdf_frames_bwd(ptr(x3), F, N, C.byref(cell_struct), cutoff, ptr(mask), ptr(mu), spacing, coeff, B, ptr(g),
+                                     ptr(gx), stream_ptr(x3.device)), "mdg_rdf_frames_bwd")
+        return gx.reshape(shape), None, None, None, None, None, None
 
 
 # ----------------------------------------------------------------------------- static structure factor

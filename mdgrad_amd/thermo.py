@@ -1,5 +1,7 @@
 """torchmd/thermo.py:57-66 (`Temperature`) and `Pressure`: the reference's sketch (torchmd/thermo.py:17-54) uses undefined
-names and does not run, so the definition is this module's -- kinetic part plus pair virial over (d V), see `Pressure`."""
+names and does not run, so the definition is this module's -- kinetic part plus pair virial over (d V), see `Pressure`.
+`PotentialEnergy`, the pair energy of every frame of a trajectory in one call, has no counterpart in the reference: the
+per-frame thermodynamic observable and the energy side of trajectory reweighting (mdgrad_amd/reweight.py)."""
 import torch
 
 from . import ops
@@ -86,3 +88,110 @@ class Pressure(Observable):
         if q.shape != v.shape:
             raise ValueError("Pressure: q %s and v %s must agree in shape" % (tuple(q.shape), tuple(v.shape)))
         return (self.kinetic(v) + self.virial(q)) / (self.dim * self.volume)
+
+
+class PotentialEnergy(Observable):
+    """Pair potential energy of every frame of a trajectory in one call:
+
+        U[f] = sum_terms sum_{i<j} phi(r_ij)
+
+    over the pair set PairPotentials sums the energy over (i < j, strict minimum image on the diagonal cell, 0 < d^2 <
+    cutoff^2, the term's index_tuple / ex_pairs selection, its own cutoff) with the plain truncated phi (no shift): U[f] is the
+    value `model(q[f])` gives.  `model` is a PairPotentials of a built-in form or a Stack of one to four of them, as for
+    `Pressure`; `PotentialEnergy.from_terms` takes the pair modules themselves.  q: [N, 3], [T, N, 3], [R, T, N, 3] or
+    replica-stacked [..., k N, 3] (a trailing k).  float32 device positions run the list-free HIP kernels (ops.EnergyFramesFn,
+    csrc/energy.hip); host or float64 positions take the torch restatement `_torch_energy` (all pairs, chunked over frames,
+    the same pair set).  Differentiable once with respect to q and the terms' parameters; when only the parameters need a
+    gradient (detached frames: `reweight.Reweighting`) the backward pass is one once-per-pair launch.
+
+    Not covered: tabulated or learned pair modules (pairMLP ...: the kernels tabulate their force, not their energy),
+    many-body, bonded, charge and GNN terms, triclinic cells, more than 32 768 atoms.  `reweight.Reweighting` accepts any
+    callable q -> U, so such a model can be reweighted with a function of the user's own."""
+
+    MAX_ATOMS = 32768
+
+    def __init__(self, system, model):
+        from .md import _pair_terms_of
+        mods = _pair_terms_of(model)
+        if mods is None:
+            raise NotImplementedError(self._refusal())
+        self._setup(system, [(m.model, float(m.cutoff), m._mask) for m in mods])
+
+    @classmethod
+    def from_terms(cls, system, terms):
+        """From the pair modules themselves: terms = [(module, cutoff, index_tuple, ex_pairs), ...] (the selections may be
+        None), one to four built-in forms.  Needs no neighbour list, so it also serves a system on the host."""
+        self = cls.__new__(cls)
+        terms = [tuple(t) + (None,) * (4 - len(t)) for t in terms]
+        from .potentials import is_builtin_form
+        if not 1 <= len(terms) <= 4 or not all(is_builtin_form(t[0]) for t in terms):
+            raise NotImplementedError(cls._refusal())
+        n = getattr(system, "group_size", system.get_number_of_atoms())
+        self._setup(system, [(m.to(system.device), float(rc), ops.build_mask(n, it, ex, system.device)) for m, rc, it, ex in terms])
+        return self
+
+    @staticmethod
+    def _refusal():
+        return ("PotentialEnergy: the model must be a PairPotentials of a built-in form (%s) or a Stack of one to four of them; "
+                "GNN, bonded, many-body and tabulated user-module (pairMLP ...) terms have no batched energy kernel (the "
+                "tabulated kernels hold the force, not the energy).  reweight.Reweighting accepts any callable q -> U per "
+                "frame: pass a function of your own for such a model" % _FORMS)
+
+    def _setup(self, system, terms):
+        Observable.__init__(self, system)
+        from . import _lib
+        cs = _lib.make_cell(system.get_cell())
+        if not cs.diag:
+            raise ValueError("PotentialEnergy: the cell must be diagonal (triclinic cells are not supported)")
+        if self.natoms > self.MAX_ATOMS:
+            raise ValueError("PotentialEnergy: at most %d atoms per frame, got %d" % (self.MAX_ATOMS, self.natoms))
+        self._cell_struct = cs
+        self._models = torch.nn.ModuleList([m for m, _, _ in terms])
+        self._cutoffs = [rc for _, rc, _ in terms]
+        self._masks = [mk for _, _, mk in terms]
+        descr, off = [], 0
+        for m, rc, mk in terms:
+            n = sum(p.numel() for p in m.mdg_params())
+            descr.append(ops.make_term(m.mdg_term(), rc, off, n, mk))
+            off += n
+        self._terms = ops.make_terms(descr, off)
+
+    def _frames(self, x, name):
+        n = x.shape[-2] if x.dim() >= 2 else 0
+        if n == 0 or x.shape[-1] != 3 or n % self.natoms:
+            raise ValueError("PotentialEnergy: %s must be [..., k * %d, 3], got %s" % (name, self.natoms, tuple(x.shape)))
+        k = n // self.natoms                             # replica-stacked state [..., k N, 3]: one value per replica
+        lead = tuple(x.shape[:-2]) + ((k,) if k > 1 else ())
+        return x.reshape(-1, self.natoms, 3), lead
+
+    def _torch_energy(self, x, budget=1 << 22):
+        """The same sum by torch ops in x's dtype on x's device: all pairs of every frame, chunked over the frames."""
+        F, N = x.shape[0], x.shape[1]
+        iu = torch.triu_indices(N, N, offset=1, device=x.device)
+        L = self.cell.detach().to(x)
+        out = []
+        step = max(1, budget // max(1, iu.shape[1]))
+        for a in range(0, F, step):
+            xa = x[a:a + step]
+            D = xa[:, iu[1]] - xa[:, iu[0]]
+            s = D.detach() * (1.0 / L)
+            D = D + (-(s > 0.5).to(x) + (s < -0.5).to(x)) * L
+            d2 = D.pow(2).sum(-1)
+            U = x.new_zeros(xa.shape[0])
+            for m, rc, mk in zip(self._models, self._cutoffs, self._masks):
+                keep = (d2.detach() < rc ** 2) & (d2.detach() != 0)
+                if mk is not None:
+                    keep = keep & mk.to(x.device).bool()[iu[0], iu[1]][None, :]
+                fi, pi = torch.nonzero(keep, as_tuple=True)
+                U = U.index_add(0, fi, m(d2[fi, pi].sqrt()).to(x.dtype))
+            out.append(U)
+        return torch.cat(out)
+
+    def forward(self, q):
+        """U of every frame of q."""
+        x, lead = self._frames(q, "q")
+        if not (x.is_cuda and x.dtype == torch.float32):
+            return self._torch_energy(x).reshape(lead)
+        params = [p for m in self._models for p in m.mdg_params()]
+        theta = torch.cat([p.reshape(-1) for p in params]) if params else x.new_zeros(0)
+        return ops.EnergyFramesFn.apply(x, theta, self._cell_struct, self._terms, self._masks).reshape(lead)

@@ -1475,6 +1475,33 @@ int mdg_rdf_frames_bwd(const float* pos, int n_frames, int n_atoms, const MdgCel
                        const float* mu, float spacing, float coeff, int nbins, const float* g_raw, float* g_xyz, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * K33  tabulated pair energy of every frame and its gradient (mdgrad_amd/thermo.py TabulatedEnergy: reweighting of learned pair
+ *      potentials, whose energy K31 refuses; csrc/energy_table.hip)
+ *   pos, cell, mask, the pair set and the three kernel shapes: as K31, for ONE cutoff and ONE nullable mask.
+ *   table [2 n_nodes] DEVICE: the nodes (phi_g, du * dphi/du_g) of phi on the grid u_g = u0 + g du in u = r^2, g = 0 .. n_nodes - 1,
+ *   4 <= n_nodes <= 4096, du > 0, u0 >= 0, and the last node at cutoff^2 (to rounding): the layout and cubic-Hermite
+ *   convention of MDG_PAIR_TABLE, applied to the energy.
+ *     U[f] = sum_{i<j, 0 < d^2 < cutoff^2} phi~(d^2),  phi~ the interpolant; a pair with d^2 < u0 takes the constant first
+ *     node value: no position gradient, its node gradient into entry 0.
+ *   fwd: U[n_frames], every unordered pair once; n_below (one DEVICE int32) = the number of pairs with d^2 < u0.
+ *   bwd: given gU[n_frames] = dL/dU.  g_pos and g_table are each nullable (not both):
+ *        g_pos != null   full rows: g_pos [n_frames, n_atoms, 3] = -gU_f sum_j 2 (dphi~/du) (x_j - x_i), the exact derivative
+ *                        of the interpolant, and g_table (when not null) from half of each visit
+ *        g_pos == null   nodes only (the frames are constants, as in reweighting): the forward's once-per-pair sweep
+ *                        accumulating g_table [2 n_nodes] = sum_f gU_f sum_pairs basis alone
+ *   g_table is summed in fixed point with integer atomics (the scale is taken on the device from max |gU|: no host read) and
+ *   U in a fixed order: bitwise reproducible, no floating-point atomics; both routes give the same g_table bits.
+ *   workspace: mdg_energy_table_workspace() floats, shared by both calls.
+ */
+int64_t mdg_energy_table_workspace(int n_frames, int n_atoms, int n_nodes);
+int mdg_energy_table_fwd(const float* pos, int n_frames, int n_atoms, const MdgCell* cell /*host*/, const float* table, int n_nodes,
+                         float u0, float du, float cutoff, const uint8_t* mask, float* U, int32_t* n_below, float* workspace,
+                         void* stream);
+int mdg_energy_table_bwd(const float* pos, int n_frames, int n_atoms, const MdgCell* cell /*host*/, const float* table, int n_nodes,
+                         float u0, float du, float cutoff, const uint8_t* mask, const float* gU, float* g_pos, float* g_table,
+                         float* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * f4  bonded terms over a static topology table (csrc/bonded.hip).
  * Replaces torchmd/interface.py:447-455 (BondPotentials.forward: harmonic in the SQUARED bond length,
  * 1/2 k (|b|^2 - ro)^2) and :496-508 (AnglePotentials.forward: 1/2 k (theta - theta0)^2 over triples (i, j, k) centred on

@@ -285,6 +285,11 @@ _SIGNATURES = {
     "mdg_energy_frames_workspace": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "mdg_energy_frames_fwd": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), C.POINTER(MdgTerms), P, P, P, P]),
     "mdg_energy_frames_bwd": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), C.POINTER(MdgTerms), P, P, P, P, P, P]),
+    "mdg_energy_table_workspace": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "mdg_energy_table_fwd": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), P, C.c_int, C.c_float, C.c_float, C.c_float, P,
+                                       P, P, P, P]),
+    "mdg_energy_table_bwd": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), P, C.c_int, C.c_float, C.c_float, C.c_float, P,
+                                       P, P, P, P, P]),
     "mdg_rdf_frames_fwd": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), C.c_float, P, P, C.c_float, C.c_float, C.c_int, P,
                                      P]),
     "mdg_rdf_frames_bwd": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), C.c_float, P, P, C.c_float, C.c_float, C.c_int, P,

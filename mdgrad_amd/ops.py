@@ -7,6 +7,7 @@ torch.autograd.Function wrappers that own the differentiation contract
     AdfRawFn                                                    soft histogram of bond angles
     VirialFn                                                    pair virial of every frame (pressure)
     EnergyFramesFn                                              pair potential energy of every frame (reweighting)
+    EnergyTableFn                                               tabulated pair energy of every frame (learned pair modules)
     RdfFramesFn                                                 soft histogram of every frame
     SkFn                                                        static structure factor of every frame
     MsdFn                                                       mean-squared displacement over all lags (+ fourth moment)
@@ -2235,6 +2236,59 @@ class EnergyFramesFn(torch.autograd.Function):
                                         ptr(gx), ptr(gth), ptr(ws), stream_ptr(x3.device)), "mdg_energy_frames_bwd")
         EnergyFramesFn.last_route = "full" if want_x else "theta"
         return (gx.reshape(xshape) if want_x else None), (gth.reshape(tshape) if want_th else None), None, None, None
+
+
+# ----------------------------------------------------------------------------- tabulated pair energy of every frame
+class EnergyTableFn(torch.autograd.Function):
+    """U[f] = sum_pairs phi~(d^2) of every frame of xyz [F, N, 3] (csrc/energy_table.hip, K33): the kernel side of
+    thermo.TabulatedEnergy.  table [2 p]: the nodes (phi_g, du dphi/du_g) on the grid u_g = u0 + g du in u = r^2 whose last node
+    is cutoff^2 (p within EAM_TABLE_NODES); mask: [N, N] uint8 or None.  Differentiable once with respect to the positions and
+    the nodes.  The backward pass runs the full-row sweep when the positions need a gradient and the once-per-pair nodes-only
+    sweep otherwise (detached frames: the reweighting case); `EnergyTableFn.last_route` names the one the last backward pass
+    took ("full" | "nodes").  `EnergyTableFn.last_below` is the device word (int32 [1]) of the last forward pass: the number of
+    pairs below the first node, which take the constant first node value."""
+
+    last_route = None
+    last_below = None
+
+    @staticmethod
+    def forward(ctx, xyz, table, cell_struct, p, u0, du, cutoff, mask):
+        lib = _lib.load()
+        require_gpu(xyz, "xyz")
+        x3 = xyz.detach()
+        x3 = x3 if x3.is_contiguous() else x3.contiguous()
+        F, N = x3.shape[0], x3.shape[1]
+        tb = table.detach().to(device=x3.device, dtype=torch.float32).contiguous()
+        if tb.numel() != 2 * int(p):
+            raise ValueError("EnergyTableFn: the table must hold 2 p = %d floats, got %d" % (2 * int(p), tb.numel()))
+        ws = torch.empty(int(lib.mdg_energy_table_workspace(F, N, int(p))), device=x3.device)
+        U = torch.empty(F, device=x3.device)
+        below = torch.empty(1, dtype=torch.int32, device=x3.device)
+        check(lib.mdg_energy_table_fwd(ptr(x3), F, N, C.byref(cell_struct), ptr(tb), int(p), float(u0), float(du), float(cutoff),
+                                       ptr(mask), ptr(U), ptr(below), ptr(ws), stream_ptr(x3.device)), "mdg_energy_table_fwd")
+        EnergyTableFn.last_below = below
+        ctx.args = (cell_struct, int(p), float(u0), float(du), float(cutoff), mask, xyz.shape, table.shape)
+        ctx.save_for_backward(x3, tb)
+        return U
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gU):
+        lib = _lib.load()
+        x3, tb = ctx.saved_tensors
+        cell_struct, p, u0, du, cutoff, mask, xshape, tshape = ctx.args
+        F, N = x3.shape[0], x3.shape[1]
+        want_x, want_t = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not want_x and not want_t:
+            return (None,) * 8
+        g = gU.detach().to(torch.float32).contiguous()
+        ws = torch.empty(int(lib.mdg_energy_table_workspace(F, N, p)), device=x3.device)
+        gx = torch.empty_like(x3) if want_x else None
+        gt = torch.empty(2 * p, device=x3.device) if want_t else None
+        check(lib.mdg_energy_table_bwd(ptr(x3), F, N, C.byref(cell_struct), ptr(tb), p, u0, du, cutoff, ptr(mask), ptr(g),
+                                       ptr(gx), ptr(gt), ptr(ws), stream_ptr(x3.device)), "mdg_energy_table_bwd")
+        EnergyTableFn.last_route = "full" if want_x else "nodes"
+        return ((gx.reshape(xshape) if want_x else None), (gt.reshape(tshape) if want_t else None)) + (None,) * 6
 
 
 # ----------------------------------------------------------------------------- smeared pair count of every frame

@@ -14,9 +14,11 @@ import torch
 class Reweighting:
     """rw = Reweighting(energy, kT, q_ref)
 
-    energy   callable q -> U per frame with the leading shape of q's frames: a thermo.PotentialEnergy (one batched HIP launch,
-             and ONE parameters-only launch for the whole backward pass), or any torch function of the user's own (learned,
-             tabulated, many-body ... models)
+    energy   callable q -> U per frame with the leading shape of q's frames: a thermo.PotentialEnergy (built-in pair forms: one
+             batched HIP launch, and ONE parameters-only launch for the whole backward pass), a thermo.TabulatedEnergy (learned
+             pair modules, pairMLP ...: their energy tabulated at every call, one launch per table, and ONE nodes-only launch
+             whose node gradient autograd carries into the module), or any torch function of the user's own (many-body ...
+             models)
     kT       temperature in energy units
     q_ref    frames sampled at the current parameters, [..., N, 3]; stored detached, with u_ref = energy(q_ref).detach()
 

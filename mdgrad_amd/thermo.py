@@ -1,7 +1,8 @@
 """torchmd/thermo.py:57-66 (`Temperature`) and `Pressure`: the reference's sketch (torchmd/thermo.py:17-54) uses undefined
 names and does not run, so the definition is this module's -- kinetic part plus pair virial over (d V), see `Pressure`.
 `PotentialEnergy`, the pair energy of every frame of a trajectory in one call, has no counterpart in the reference: the
-per-frame thermodynamic observable and the energy side of trajectory reweighting (mdgrad_amd/reweight.py)."""
+per-frame thermodynamic observable and the energy side of trajectory reweighting (mdgrad_amd/reweight.py); `TabulatedEnergy`
+is the same for learned pair modules (pairMLP ...), whose energy it tabulates."""
 import torch
 
 from . import ops
@@ -106,7 +107,8 @@ class PotentialEnergy(Observable):
 
     Not covered: tabulated or learned pair modules (pairMLP ...: the kernels tabulate their force, not their energy),
     many-body, bonded, charge and GNN terms, triclinic cells, more than 32 768 atoms.  `reweight.Reweighting` accepts any
-    callable q -> U, so such a model can be reweighted with a function of the user's own."""
+    callable q -> U, so such a model can be reweighted with a function of the user's own; for learned PAIR modules that
+    callable exists: `TabulatedEnergy`."""
 
     MAX_ATOMS = 32768
 
@@ -195,3 +197,193 @@ class PotentialEnergy(Observable):
         params = [p for m in self._models for p in m.mdg_params()]
         theta = torch.cat([p.reshape(-1) for p in params]) if params else x.new_zeros(0)
         return ops.EnergyFramesFn.apply(x, theta, self._cell_struct, self._terms, self._masks).reshape(lead)
+
+
+class TabulatedEnergy(Observable):
+    """Pair potential energy of every frame of a trajectory for LEARNED pair potentials (pairMLP or any nn.Module phi(r)), which
+    `PotentialEnergy` refuses: the energy side of trajectory reweighting (`reweight.Reweighting`) for the models it was written
+    for.
+
+        U[f] = sum_{built-in members} sum_{i<j} phi(r_ij)  +  sum_{groups} sum_{i<j} phi~_group(r_ij^2)
+
+    `model` is a PairPotentials or a Stack whose members are all PairPotentials, at least one of them a user module;
+    `TabulatedEnergy.from_terms` takes the pair modules themselves.  Built-in members (the steep prior: LJFamily,
+    ExcludedVolume ...) stay exact: they go through `PotentialEnergy`'s kernels (ops.EnergyFramesFn).  The user modules are
+    grouped by (cutoff, selection mask); every forward call tabulates each group's sum of phi on the uniform grid in u = r^2 from
+    (r_min cutoff)^2 to cutoff^2 -- `nodes` nodes (value, du dphi/du), the slopes by autograd with create_graph=True, as the
+    integrators tabulate the force for the fused kernels; `nodes` and `r_min` default to their `table_nodes` and `table_rmin` --
+    and one launch per group (ops.EnergyTableFn, csrc/energy_table.hip) sums the cubic-Hermite interpolant phi~ over the pair
+    set of `PotentialEnergy` (i < j, strict minimum image on the diagonal cell, 0 < d^2 < cutoff^2, the selection, the plain
+    truncated phi).  The node gradient the kernel returns flows through the tabulation into the module parameters; with
+    detached frames (reweighting) the backward pass is one once-per-pair launch per group.  q: [N, 3], [T, N, 3], [R, T, N, 3] or
+    replica-stacked [..., k N, 3].  float32 device positions run the kernels; host or float64 positions take the torch
+    restatement `_torch_table_energy` (the same table, pair set and below-range rule).  Differentiable once.
+
+    Range: a pair closer than r_min cutoff lies below the first node and takes the constant first node value (no force).  With
+    `check_range=True` such a pair raises a RuntimeError (one host read per call, the rule of the fused tabulated path); with
+    `check_range=False` nothing is read and the count of the last call stays available as `last_below`.
+
+    The dynamics interpolate a table of phi'/r, this class a table of phi: the two differ by interpolation error.  That does not
+    bias the reweighting estimator, whose weights use only energy differences between theta and theta_ref on the SAME table.
+
+    Not covered: the virial of tabulated modules, temperature-dependent modules (TPairPotentials / TpairMLP), many-body, bonded,
+    charge and GNN members, triclinic cells, more than 32 768 atoms."""
+
+    MAX_ATOMS = 32768
+
+    def __init__(self, system, model, nodes=None, r_min=None, check_range=True):
+        from .interface import PairPotentials, Stack, TPairPotentials
+        mods = [model] if isinstance(model, PairPotentials) else (list(model.models.values()) if isinstance(model, Stack) else None)
+        if not mods or not all(isinstance(m, PairPotentials) for m in mods):
+            raise NotImplementedError("TabulatedEnergy: the model must be a PairPotentials or a Stack whose members are all "
+                                      "PairPotentials, at least one of them a user module phi(r) (pairMLP ...); GNN, bonded, "
+                                      "many-body and charge members have no tabulated pair energy")
+        if any(isinstance(m, TPairPotentials) for m in mods):
+            raise NotImplementedError("TabulatedEnergy: temperature-dependent pair modules (TPairPotentials / TpairMLP) are not "
+                                      "covered")
+        self._setup(system, [(m.model, float(m.cutoff), m._mask) for m in mods], nodes, r_min, check_range)
+
+    @classmethod
+    def from_terms(cls, system, terms, nodes=None, r_min=None, check_range=True):
+        """From the pair modules themselves: terms = [(module, cutoff, index_tuple, ex_pairs), ...] (the selections may be
+        None).  Needs no neighbour list, so it also serves a system on the host."""
+        self = cls.__new__(cls)
+        terms = [tuple(t) + (None,) * (4 - len(t)) for t in terms]
+        n = getattr(system, "group_size", system.get_number_of_atoms())
+        self._setup(system, [(m.to(system.device), float(rc), ops.build_mask(n, it, ex, system.device)) for m, rc, it, ex in terms],
+                    nodes, r_min, check_range)
+        return self
+
+    def _setup(self, system, terms, nodes, r_min, check_range):
+        import numpy as np
+        from . import _lib
+        from .md import _EOM
+        from .potentials import is_builtin_form
+        Observable.__init__(self, system)
+        if not all(isinstance(m, torch.nn.Module) for m, _, _ in terms):
+            raise NotImplementedError("TabulatedEnergy: every term must be a pair module phi(r)")
+        user = [t for t in terms if not is_builtin_form(t[0])]
+        exact = [t for t in terms if is_builtin_form(t[0])]
+        if not user:
+            raise NotImplementedError("TabulatedEnergy: the model holds no user module (pairMLP ...); thermo.PotentialEnergy "
+                                      "evaluates built-in pair forms exactly")
+        cs = _lib.make_cell(system.get_cell())
+        if not cs.diag:
+            raise ValueError("TabulatedEnergy: the cell must be diagonal (triclinic cells are not supported)")
+        if self.natoms > self.MAX_ATOMS:
+            raise ValueError("TabulatedEnergy: at most %d atoms per frame, got %d" % (self.MAX_ATOMS, self.natoms))
+        self.nodes = int(_EOM.table_nodes if nodes is None else nodes)
+        self.r_min = float(_EOM.table_rmin if r_min is None else r_min)
+        lo, hi = ops.EAM_TABLE_NODES
+        if not lo <= self.nodes <= hi:
+            raise ValueError("TabulatedEnergy: nodes must lie in [%d, %d], got %d" % (lo, hi, self.nodes))
+        if not 0.0 <= self.r_min < 1.0:
+            raise ValueError("TabulatedEnergy: r_min is a fraction of the cutoff in [0, 1), got %r" % (r_min,))
+        self.check_range = bool(check_range)
+        self.last_below = None
+        self._cell_struct = cs
+        self._exact = None
+        if exact:
+            self._exact = PotentialEnergy.__new__(PotentialEnergy)
+            if len(exact) > 4:
+                raise NotImplementedError("TabulatedEnergy: at most four built-in members beside the user modules")
+            self._exact._setup(system, exact)
+        self._groups = []
+        for m, rc, mk in user:
+            for g in self._groups:
+                if g["cutoff"] == rc and ((mk is None and g["mask"] is None) or
+                                          (mk is not None and g["mask"] is not None and torch.equal(mk, g["mask"]))):
+                    g["mods"].append(m)
+                    break
+            else:
+                # the float32 grid the kernel receives: u_g = u0 + g du, the last node at cutoff^2
+                u0 = np.float32((self.r_min * rc) ** 2)
+                du = np.float32((rc * rc - float(u0)) / (self.nodes - 1))
+                self._groups.append(dict(mods=torch.nn.ModuleList([m]), cutoff=rc, mask=mk, u0=float(u0), du=float(du),
+                                         inv_du=float(np.float32(1.0) / du)))
+        self._user = torch.nn.ModuleList([g["mods"] for g in self._groups])
+
+    def _frames(self, x, name):
+        n = x.shape[-2] if x.dim() >= 2 else 0
+        if n == 0 or x.shape[-1] != 3 or n % self.natoms:
+            raise ValueError("TabulatedEnergy: %s must be [..., k * %d, 3], got %s" % (name, self.natoms, tuple(x.shape)))
+        k = n // self.natoms
+        lead = tuple(x.shape[:-2]) + ((k,) if k > 1 else ())
+        return x.reshape(-1, self.natoms, 3), lead
+
+    def grid(self, group=0):
+        """(u0, du, nodes) of a group's table: float32 values, u_g = u0 + g du"""
+        g = self._groups[group]
+        return g["u0"], g["du"], self.nodes
+
+    def tabulate(self, group=0, device=None):
+        """The [2 nodes] table of a group, (phi_g, du dphi/du_g) on its grid, in the modules' dtype and differentiable with
+        respect to their parameters."""
+        g = self._groups[group]
+        ps = list(g["mods"].parameters())
+        dtype = ps[0].dtype if ps else torch.float32
+        device = (ps[0].device if ps else self.device) if device is None else device
+        with torch.enable_grad():
+            u32 = g["u0"] + g["du"] * torch.arange(self.nodes, device=device, dtype=torch.float32)
+            u = u32.to(dtype).requires_grad_(True)
+            r = u.sqrt()[:, None]
+            phi = sum(m(r).reshape(-1) for m in g["mods"])
+            (dphi,) = torch.autograd.grad(phi.sum(), u, create_graph=True)
+            return torch.stack((phi, g["du"] * dphi), 1).reshape(-1)
+
+    def _torch_table_energy(self, x, table, g, budget=1 << 22):
+        """(U [F], pairs below the first node) of one group by torch ops in x's dtype: all pairs of every frame, chunked over
+        the frames; the kernel's grid arithmetic, pair set and below-range rule."""
+        F, N, p = x.shape[0], x.shape[1], self.nodes
+        iu = torch.triu_indices(N, N, offset=1, device=x.device)
+        L = self.cell.detach().to(x)
+        nd = table.to(x).reshape(p, 2)
+        rc2, u0, inv_du = g["cutoff"] ** 2, g["u0"], g["inv_du"]
+        sel = None if g["mask"] is None else g["mask"].to(x.device).bool()[iu[0], iu[1]][None, :]
+        out, below = [], torch.zeros((), dtype=torch.int64, device=x.device)
+        step = max(1, budget // max(1, iu.shape[1]))
+        for a in range(0, F, step):
+            xa = x[a:a + step]
+            D = xa[:, iu[1]] - xa[:, iu[0]]
+            s = D.detach() * (1.0 / L)
+            D = D + (-(s > 0.5).to(x) + (s < -0.5).to(x)) * L
+            d2 = D.pow(2).sum(-1)
+            keep = (d2.detach() < rc2) & (d2.detach() != 0)
+            if sel is not None:
+                keep = keep & sel
+            fi, pi = torch.nonzero(keep, as_tuple=True)
+            d2 = d2[fi, pi]
+            below = below + (d2.detach() < u0).sum()
+            t = ((d2 - u0) * inv_du).clamp(0.0, float(p - 1))               # (no gradient below the first node)
+            c = t.detach().floor().long().clamp(max=p - 2)
+            fr = t - c.to(x)
+            om = 1.0 - fr
+            b0, b1, b2, b3 = (1.0 + 2.0 * fr) * om * om, fr * om * om, fr * fr * (3.0 - 2.0 * fr), fr * fr * (fr - 1.0)
+            phi = b0 * nd[c, 0] + b1 * nd[c, 1] + b2 * nd[c + 1, 0] + b3 * nd[c + 1, 1]
+            out.append(x.new_zeros(xa.shape[0]).index_add(0, fi, phi))
+        return torch.cat(out), below
+
+    def forward(self, q):
+        """U of every frame of q."""
+        x, lead = self._frames(q, "q")
+        kernels = x.is_cuda and x.dtype == torch.float32
+        U = None if self._exact is None else self._exact(x)
+        below = []
+        for k, g in enumerate(self._groups):
+            table = self.tabulate(k, x.device)
+            if kernels:
+                Ug = ops.EnergyTableFn.apply(x, table, self._cell_struct, self.nodes, g["u0"], g["du"], g["cutoff"], g["mask"])
+                below.append(ops.EnergyTableFn.last_below.to(torch.int64).reshape(()))
+            else:
+                Ug, nb = self._torch_table_energy(x, table, g)
+                below.append(nb)
+            U = Ug if U is None else U + Ug
+        self.last_below = below[0] if len(below) == 1 else torch.stack(below).sum()
+        if self.check_range:
+            n = int(self.last_below)
+            if n:
+                raise RuntimeError("TabulatedEnergy: %d pair(s) came closer than r_min * cutoff = %.4g, below the first node of "
+                                   "the tabulated pair energy; lower `r_min` (now %g) or pass check_range=False to let them "
+                                   "take the first node's value" % (n, self.r_min * min(g["cutoff"] for g in self._groups),
+                                                                    self.r_min))
+        return U.reshape(lead)

@@ -20,15 +20,15 @@ using namespace frame_pairs;
 struct EnergyVisit {
     static constexpr int FWD_LEVEL = 0, BWD_LEVEL = 1;
     static constexpr float SIGN = 1.f;
-    static __device__ __forceinline__ float value(const PairOut& o, float) { return o.u; }
+    static __device__ __forceinline__ float value(const PairOut& o, float, float acc) { return acc + o.u; }
     static __device__ __forceinline__ float radial(const PairOut& o, float, float ir) { return -o.du * ir; }
-    static __device__ __forceinline__ float dtheta(const PairOut& o, float, int k) { return o.du_dth[k]; }
+    static __device__ __forceinline__ float dtheta(const PairOut& o, float, int k, float acc) { return acc + o.du_dth[k]; }
 };
 
 }  // namespace
 
 extern "C" int64_t mdg_energy_frames_workspace(int n_frames, int n_atoms, int n_theta_total) {
-    return frame_pairs::workspace(n_frames, n_atoms, n_theta_total);
+    return frame_pairs::workspace(n_frames, n_atoms, n_theta_total, FP_THETA);
 }
 
 extern "C" int mdg_energy_frames_fwd(const float* pos, int n_frames, int n_atoms, const MdgCell* cell, const MdgTerms* terms,
@@ -51,5 +51,6 @@ extern "C" int mdg_energy_frames_bwd(const float* pos, int n_frames, int n_atoms
     MDG_CHECK_ARG(g_pos || g_theta, "energy_frames_bwd: g_pos and g_theta are both null (nothing to compute)");
     MDG_CHECK_ARG(g_pos || A.K > 0, "energy_frames_bwd: g_theta without parameters (the terms hold none)");
     A.g = gU; A.g_pos = g_pos; A.partial = workspace;
-    return launch_grad<EnergyVisit>("energy_frames_bwd", A, g_theta, (hipStream_t)stream);
+    return g_pos ? launch_grad<EnergyVisit, FP_ROWS>("energy_frames_bwd", A, g_theta, (hipStream_t)stream)
+                 : launch_grad<EnergyVisit, FP_THETA>("energy_frames_bwd", A, g_theta, (hipStream_t)stream);
 }

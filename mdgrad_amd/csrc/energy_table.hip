@@ -11,7 +11,8 @@
 //
 // Pair set, the three shapes by frame size (a wave per frame up to 128 atoms, a workgroup per frame up to 1 024, tiles of
 // 256 x 256 atoms up to 32 768) and the fixed-order sums of U are those of csrc/frame_pairs.hpp; positions AND the table are
-// staged in LDS (the lookups are random gathers).  Three sweeps:
+// staged in LDS (the lookups are random gathers).  The sweeps themselves are written out here, not put on that header's
+// pair walk (says why).  Three sweeps:
 //   ET_VALUE    U[f], every unordered pair once
 //   ET_NODES    (frames detached: the reweighting case) gT[2 p] = sum_f gU[f] sum_pairs basis, once per pair, no position written
 //   ET_ROWS     full rows: dL/dx_i = -gU[f] sum_j 2 (dphi~/du) D (D = x_j - x_i), the exact derivative of the interpolant; the
@@ -311,11 +312,9 @@ inline int64_t words_floats(int p) { return ET_HEAD + 4 * (int64_t)p; }      // 
 
 inline int make_tab_args(const char* who, TabArgs& A, const float* pos, int n_frames, int n_atoms, const MdgCell* cell,
                          const float* table, int p, float u0, float du, float cutoff, const uint8_t* mask) {
-    MDG_CHECK_ARG(pos && cell && table, "%s: null argument", who);
-    MDG_CHECK_ARG(n_frames > 0 && n_atoms > 0, "%s: empty trajectory", who);
-    MDG_CHECK_ARG(n_atoms <= FP_MAX_ATOMS, "%s: at most %d atoms per frame, got %d", who, FP_MAX_ATOMS, n_atoms);
-    MDG_CHECK_ARG(n_frames < (1 << 24), "%s: fewer than 2^24 frames in one call (chunk the frames)", who);
-    MDG_CHECK_ARG(cell->diag, "%s: the cell must be diagonal (triclinic cells are not supported)", who);
+    int rc = check_frames(who, pos, cell, table, n_frames, n_atoms, FP_MAX_ATOMS);
+    if (rc == MDG_OK) rc = check_frame_count(who, n_frames);
+    if (rc != MDG_OK) return rc;
     MDG_CHECK_ARG(p >= ET_MIN_NODES && p <= ET_MAX_NODES, "%s: the table needs %d..%d nodes, got %d", who, ET_MIN_NODES,
                   ET_MAX_NODES, p);
     MDG_CHECK_ARG(du > 0.f && cutoff > 0.f && u0 >= 0.f, "%s: the grid needs du > 0, u0 >= 0 and a positive cutoff", who);

@@ -1,6 +1,8 @@
 // List-free all-pairs sweeps over every frame of a trajectory, parameterised by what a visit accumulates: the scaffolding of
-// the per-frame pair observables (csrc/energy.hip is its first user; csrc/virial.hip predates it and states the same sweeps
-// by hand).
+// the per-frame pair observables.  csrc/virial.hip (K15) and csrc/energy.hip (K31) are a visit policy on its kernels.
+// csrc/rdf_frames.hip (K32), whose visit scatters into an integer histogram, has kernels of its own on the pair walk
+// (stage_frame, once_partners, walk_row) and the frame checks; csrc/energy_table.hip (K33) takes the pair test, the tile
+// staging, the second-stage sums and the frame checks, and writes its sweeps out.
 //
 // Pair set of a term = the one PairPotentials sums the energy over (torchmd/topology.py:30-73, interface.py:298-300):
 // pairs i < j, D = x_j - x_i re-imaged with the reference's strict +-1/2 minimum image on the diagonal cell,
@@ -10,9 +12,9 @@
 // A visit policy V names what is summed:
 //   V::FWD_LEVEL, V::BWD_LEVEL          pair_eval levels of the value and of its gradient
 //   V::SIGN                             out[f] = SIGN * sum_pairs V::value
-//   V::value(o, r)                      the summand of a pair
+//   V::value(o, r, acc)                 acc + the summand of a pair (the policy states the arithmetic: a sum or an fma)
 //   V::radial(o, r, ir)                 c of  d(sum)/dx_i = sum_j c D          (D = x_j - x_i)
-//   V::dtheta(o, r, k)                  d(summand)/dtheta_k
+//   V::dtheta(o, r, k, acc)             acc + d(summand)/dtheta_k
 // Three shapes by frame size, positions staged in LDS in all of them:
 //   N <= 128     a wave per frame, four frames per workgroup
 //   N <= 1024    a workgroup per frame
@@ -88,14 +90,14 @@ __device__ __forceinline__ void visit(const TermConst& tc, float dx, float dy, f
     float r, ir;
     pair_eval<MODE == FP_VALUE ? V::FWD_LEVEL : V::BWD_LEVEL, KIND>(tc, d2, r, ir, o);
     if (MODE == FP_VALUE) {
-        a.w += V::value(o, r);
+        a.w = V::value(o, r, a.w);
     } else {
         if (MODE == FP_ROWS) {
             const float c = V::radial(o, r, ir);
             a.gx = fmaf(c, dx, a.gx); a.gy = fmaf(c, dy, a.gy); a.gz = fmaf(c, dz, a.gz);
         }
 #pragma unroll
-        for (int t = 0; t < form_ntheta(KIND); ++t) a.th[t] += V::dtheta(o, r, t);
+        for (int t = 0; t < form_ntheta(KIND); ++t) a.th[t] = V::dtheta(o, r, t, a.th[t]);
     }
 }
 
@@ -105,45 +107,53 @@ __device__ __forceinline__ void put_grad(float* g, const FpAcc& a, float gw, boo
     else { g[0] = fmaf(gw, a.gx, g[0]); g[1] = fmaf(gw, a.gy, g[1]); g[2] = fmaf(gw, a.gz, g[2]); }
 }
 
+// ---------------------------------------------------------------------------------- the pair walk
+// What the sweeps of every user share and what knows nothing of the sums: a visit is the callable fn(dx, dy, dz, d2), called
+// for the pairs of the set above with D = x_j - x_i already re-imaged.
+//
+// the frame p [N, 3] into sf = x [CAP] | y [CAP] | z [CAP], by the TPF threads that share it (t = 0 .. TPF - 1)
+template <int TPF, int CAP>
+__device__ __forceinline__ void stage_frame(float* sf, const float* p, int N, int t) {
+    for (int e = t; e < 3 * N; e += TPF) sf[(e % 3) * CAP + e / 3] = p[e];
+}
+
+// partners of row i in the once-per-pair sweep: k = 1 .. (N - 1) / 2, for even N also k = N / 2 on the first half of the rows
+__device__ __forceinline__ int once_partners(int N, int i) { return ((N - 1) >> 1) + ((!(N & 1) && i < (N >> 1)) ? 1 : 0); }
+
+// atom i of a staged frame against its partners (i + k) mod N, k = 1 .. kmax (once_partners, or N - 1 for the full row)
+template <int CAP, class Fn>
+__device__ __forceinline__ void walk_row(const MdgCell& cell, float rc2, const uint8_t* mask, const float* sf, int N, int i,
+                                         int kmax, Fn&& fn) {
+    const float *sx = sf, *sy = sf + CAP, *sz = sf + 2 * CAP;
+    const float xi = sx[i], yi = sy[i], zi = sz[i];
+    for (int k = 1; k <= kmax; ++k) {
+        int j = i + k;
+        if (j >= N) j -= N;
+        if (mask && !mask[(size_t)i * N + j]) continue;
+        float dx = sx[j] - xi, dy = sy[j] - yi, dz = sz[j] - zi, d2;
+        if (!pair_in(cell, rc2, dx, dy, dz, d2)) continue;
+        fn(dx, dy, dz, d2);
+    }
+}
+
+// thread-owned atom i (mrow = its mask row) against the staged atoms [jlo, nj) of the tile that starts at atom j0
+template <class Fn>
+__device__ __forceinline__ void walk_tile(const MdgCell& cell, float rc2, const uint8_t* mrow, const float* sj, int j0, int jlo,
+                                          int nj, float xi, float yi, float zi, Fn&& fn) {
+    for (int jj = jlo; jj < nj; ++jj) {
+        if (mrow && !mrow[j0 + jj]) continue;
+        float dx = sj[jj] - xi, dy = sj[FP_TILE + jj] - yi, dz = sj[2 * FP_TILE + jj] - zi, d2;
+        if (!pair_in(cell, rc2, dx, dy, dz, d2)) continue;
+        fn(dx, dy, dz, d2);
+    }
+}
+
+__device__ __forceinline__ void stage_tile(float* sj, const float* p, int j0, int nj) {
+    for (int e = threadIdx.x; e < 3 * nj; e += FP_BLOCK) sj[(e % 3) * FP_TILE + e / 3] = p[3 * (size_t)j0 + e];
+}
+
 // ---------------------------------------------------------------------------------- whole frame in LDS (N <= 1024)
-// TPF threads share a frame: lane t of them owns the atoms t, t + TPF, ...; sx / sy / sz = the frame, one array per component
-template <class V, int KIND, int TPF, int MODE>
-__device__ __forceinline__ void frame_once(const FpArgs& A, const TermConst& tc, const uint8_t* mask, const float* sx,
-                                           const float* sy, const float* sz, int t, FpAcc& a) {
-    const int N = A.N, half = (N - 1) >> 1;
-    for (int i = t; i < N; i += TPF) {
-        const float xi = sx[i], yi = sy[i], zi = sz[i];
-        const int kmax = half + ((!(N & 1) && i < (N >> 1)) ? 1 : 0);
-        for (int k = 1; k <= kmax; ++k) {
-            int j = i + k;
-            if (j >= N) j -= N;
-            if (mask && !mask[(size_t)i * N + j]) continue;
-            float dx = sx[j] - xi, dy = sy[j] - yi, dz = sz[j] - zi, d2;
-            if (!pair_in(A.cell, tc.rc2, dx, dy, dz, d2)) continue;
-            visit<V, KIND, MODE>(tc, dx, dy, dz, d2, a);
-        }
-    }
-}
-
-template <class V, int KIND, int TPF>
-__device__ __forceinline__ void frame_rows(const FpArgs& A, const TermConst& tc, const uint8_t* mask, const float* sx,
-                                           const float* sy, const float* sz, int t, long long f, float gw, bool first, FpAcc& a) {
-    const int N = A.N;
-    for (int i = t; i < N; i += TPF) {
-        const float xi = sx[i], yi = sy[i], zi = sz[i];
-        a.gx = a.gy = a.gz = 0.f;
-        for (int k = 1; k < N; ++k) {
-            int j = i + k;
-            if (j >= N) j -= N;
-            if (mask && !mask[(size_t)i * N + j]) continue;
-            float dx = sx[j] - xi, dy = sy[j] - yi, dz = sz[j] - zi, d2;
-            if (!pair_in(A.cell, tc.rc2, dx, dy, dz, d2)) continue;
-            visit<V, KIND, FP_ROWS>(tc, dx, dy, dz, d2, a);
-        }
-        put_grad(A.g_pos + ((size_t)f * N + i) * 3, a, gw, first);
-    }
-}
-
+// TPF threads share a frame: lane t of them owns the atoms t, t + TPF, ...
 template <class V, int TPF, int MODE>
 __global__ __launch_bounds__(FP_BLOCK) void fp_frame_kernel(const FpArgs A) {
     constexpr int CAP = TPF == MDG_WAVE ? FP_WAVE_ATOMS : FP_GROUP_ATOMS, FPB = FP_BLOCK / TPF;
@@ -153,25 +163,25 @@ __global__ __launch_bounds__(FP_BLOCK) void fp_frame_kernel(const FpArgs A) {
     const int t = threadIdx.x % TPF, g = threadIdx.x / TPF, N = A.N;
     const long long f = (long long)blockIdx.x * FPB + g;
     const bool live = f < A.F;
-    float* sx = sp + g * 3 * CAP;
-    float* sy = sx + CAP;
-    float* sz = sy + CAP;
-    if (live) {
-        const float* p = A.pos + (size_t)f * N * 3;
-        for (int e = t; e < 3 * N; e += TPF) sp[g * 3 * CAP + (e % 3) * CAP + e / 3] = p[e];
-    }
+    float* sf = sp + g * 3 * CAP;
+    if (live) stage_frame<TPF, CAP>(sf, A.pos + (size_t)f * N * 3, N, t);
     __syncthreads();
     const float gw = (MODE != FP_VALUE && live) ? A.g[f] : 0.f;
     float w = 0.f;
     for (int m = 0; m < A.terms.n_terms; ++m) {
         const MdgPairTerm& term = A.terms.t[m];
         const TermConst tc = term_prepare(term, A.theta);
+        const uint8_t* mask = term.mask;
         with_form(tc, [&](auto form) {
             constexpr int KIND = decltype(form)::value;
             FpAcc a{};
             if (live) {
-                if (MODE == FP_ROWS) frame_rows<V, KIND, TPF>(A, tc, term.mask, sx, sy, sz, t, f, gw, m == 0, a);
-                else frame_once<V, KIND, TPF, MODE>(A, tc, term.mask, sx, sy, sz, t, a);
+                for (int i = t; i < N; i += TPF) {
+                    if (MODE == FP_ROWS) a.gx = a.gy = a.gz = 0.f;
+                    walk_row<CAP>(A.cell, tc.rc2, mask, sf, N, i, MODE == FP_ROWS ? N - 1 : once_partners(N, i),
+                                  [&](float dx, float dy, float dz, float d2) { visit<V, KIND, MODE>(tc, dx, dy, dz, d2, a); });
+                    if (MODE == FP_ROWS) put_grad(A.g_pos + ((size_t)f * N + i) * 3, a, gw, m == 0);
+                }
             }
             w += a.w;
             if constexpr (MODE != FP_VALUE && form_ntheta(KIND) > 0) {
@@ -197,22 +207,6 @@ __global__ __launch_bounds__(FP_BLOCK) void fp_frame_kernel(const FpArgs A) {
 }
 
 // ---------------------------------------------------------------------------------- tiles (N > 1024)
-// thread-owned atom i against the staged atoms [jlo, nj) of the tile that starts at atom j0 (sj: one array per component)
-template <class V, int KIND, int MODE>
-__device__ __forceinline__ void tile_rows(const MdgCell& cell, const TermConst& tc, const uint8_t* mrow, const float* sj, int j0,
-                                          int jlo, int nj, float xi, float yi, float zi, FpAcc& a) {
-    for (int jj = jlo; jj < nj; ++jj) {
-        if (mrow && !mrow[j0 + jj]) continue;
-        float dx = sj[jj] - xi, dy = sj[FP_TILE + jj] - yi, dz = sj[2 * FP_TILE + jj] - zi, d2;
-        if (!pair_in(cell, tc.rc2, dx, dy, dz, d2)) continue;
-        visit<V, KIND, MODE>(tc, dx, dy, dz, d2, a);
-    }
-}
-
-__device__ __forceinline__ void stage_tile(float* sj, const float* p, int j0, int nj) {
-    for (int e = threadIdx.x; e < 3 * nj; e += FP_BLOCK) sj[(e % 3) * FP_TILE + e / 3] = p[3 * (size_t)j0 + e];
-}
-
 // grid (F, nb * (nb / 2 + 1)): tile id = ib + nb * k pairs the i-block ib with the j-block (ib + k) mod nb; k = 0 is the
 // diagonal tile (j > i), and for even nb the shell k = nb / 2 belongs to the first half of the i-blocks (the other tiles of
 // that shell write zeros).  MODE = FP_VALUE or FP_THETA.
@@ -239,7 +233,9 @@ __global__ __launch_bounds__(FP_BLOCK) void fp_tile_once_kernel(const FpArgs A, 
         with_form(tc, [&](auto form) {
             constexpr int KIND = decltype(form)::value;
             FpAcc a{};
-            if (live) tile_rows<V, KIND, MODE>(A.cell, tc, mrow, sj, j0, k == 0 ? t + 1 : 0, nj, xi, yi, zi, a);
+            if (live)
+                walk_tile(A.cell, tc.rc2, mrow, sj, j0, k == 0 ? t + 1 : 0, nj, xi, yi, zi,
+                          [&](float dx, float dy, float dz, float d2) { visit<V, KIND, MODE>(tc, dx, dy, dz, d2, a); });
             w += a.w;
             if constexpr (MODE == FP_THETA && form_ntheta(KIND) > 0) {
                 block_sum_n<MDG_MAX_THETA>(a.th, red);
@@ -280,7 +276,9 @@ __global__ __launch_bounds__(FP_BLOCK) void fp_tile_rows_kernel(const FpArgs A, 
                 __syncthreads();                       // the previous tile has been read
                 stage_tile(sj, p, j0, nj);
                 __syncthreads();
-                if (live) tile_rows<V, KIND, FP_ROWS>(A.cell, tc, mrow, sj, j0, 0, nj, xi, yi, zi, a);
+                if (live)
+                    walk_tile(A.cell, tc.rc2, mrow, sj, j0, 0, nj, xi, yi, zi,
+                              [&](float dx, float dy, float dz, float d2) { visit<V, KIND, FP_ROWS>(tc, dx, dy, dz, d2, a); });
             }
             if (live) put_grad(A.g_pos + ((size_t)f * N + i) * 3, a, gw, m == 0);
             if constexpr (form_ntheta(KIND) > 0) {
@@ -327,22 +325,39 @@ inline long long theta_rows(int n_frames, int n_atoms, int mode) {
     return (long long)n_frames * (mode == FP_ROWS ? tile_blocks(n_atoms) : tile_count(n_atoms));
 }
 
-inline int64_t workspace(int n_frames, int n_atoms, int n_theta_total) {
+// floats of the workspace: the forward's tile partials or the parameter partials of the widest backward sweep the caller has
+// (bwd_mode = FP_THETA when it has the parameters-only route, FP_ROWS otherwise)
+inline int64_t workspace(int n_frames, int n_atoms, int n_theta_total, int bwd_mode) {
     if (n_frames <= 0 || n_atoms <= 0) return 1;
     const long long fwd = n_atoms > FP_GROUP_ATOMS ? (long long)n_frames * tile_count(n_atoms) : 0;
-    const long long bwd = theta_rows(n_frames, n_atoms, FP_THETA) * (n_theta_total > 0 ? n_theta_total : 0);   // (>= FP_ROWS')
+    const long long bwd = theta_rows(n_frames, n_atoms, bwd_mode) * (n_theta_total > 0 ? n_theta_total : 0);
     const long long n = fwd > bwd ? fwd : bwd;
     return n > 0 ? n : 1;
 }
 
-// the checks every entry point shares (`who` names it in the messages), and the argument block
+// the checks on the frames that every entry point of a per-frame family states (`who` names it in the messages; `model` = the
+// family's own input beside the positions and the cell: terms, table or centres)
+inline int check_frames(const char* who, const float* pos, const MdgCell* cell, const void* model, int n_frames, int n_atoms,
+                        int max_atoms) {
+    MDG_CHECK_ARG(pos && cell && model, "%s: null argument", who);
+    MDG_CHECK_ARG(n_frames > 0 && n_atoms > 0, "%s: empty trajectory", who);
+    MDG_CHECK_ARG(n_atoms <= max_atoms, "%s: at most %d atoms per frame, got %d", who, max_atoms, n_atoms);
+    MDG_CHECK_ARG(cell->diag, "%s: the cell must be diagonal (triclinic cells are not supported)", who);
+    return MDG_OK;
+}
+
+// the limit on the frames of one call of K15, K31 and K33
+inline int check_frame_count(const char* who, int n_frames) {
+    MDG_CHECK_ARG(n_frames < (1 << 24), "%s: fewer than 2^24 frames in one call (chunk the frames)", who);
+    return MDG_OK;
+}
+
+// the checks of the built-in pair terms, and the argument block
 inline int make_args(const char* who, FpArgs& A, const float* pos, int n_frames, int n_atoms, const MdgCell* cell,
                      const MdgTerms* terms, const float* theta) {
-    MDG_CHECK_ARG(pos && cell && terms, "%s: null argument", who);
-    MDG_CHECK_ARG(n_frames > 0 && n_atoms > 0, "%s: empty trajectory", who);
-    MDG_CHECK_ARG(n_atoms <= FP_MAX_ATOMS, "%s: at most %d atoms per frame, got %d", who, FP_MAX_ATOMS, n_atoms);
-    MDG_CHECK_ARG(n_frames < (1 << 24), "%s: fewer than 2^24 frames in one call (chunk the frames)", who);
-    MDG_CHECK_ARG(cell->diag, "%s: the cell must be diagonal (triclinic cells are not supported)", who);
+    int rc = check_frames(who, pos, cell, terms, n_frames, n_atoms, FP_MAX_ATOMS);
+    if (rc == MDG_OK) rc = check_frame_count(who, n_frames);
+    if (rc != MDG_OK) return rc;
     MDG_CHECK_ARG(terms->n_terms >= 1 && terms->n_terms <= MDG_MAX_TERMS, "%s: 1..%d pair terms, got %d", who, MDG_MAX_TERMS,
                   terms->n_terms);
     int off = 0;
@@ -383,28 +398,25 @@ inline int launch_value(const char* who, const FpArgs& A, hipStream_t st) {
     return MDG_OK;
 }
 
-// the gradient of sum_f g[f] out[f]: full rows when A.g_pos is set, the once-per-pair parameter sweep otherwise
+// the gradient of sum_f g[f] out[f] by the sweep MODE: FP_ROWS (A.g_pos set) or the once-per-pair parameter sweep FP_THETA
 // (A.g and A.partial set; g_theta [K], null when K == 0 or not wanted)
-template <class V>
+template <class V, int MODE>
 inline int launch_grad(const char* who, const FpArgs& A, float* g_theta, hipStream_t st) {
-    const int mode = A.g_pos ? FP_ROWS : FP_THETA;
-    if (mode == FP_THETA && (A.K == 0 || !g_theta)) return MDG_OK;          // nothing to compute
+    static_assert(MODE == FP_ROWS || MODE == FP_THETA, "a gradient sweep");
+    if (MODE == FP_THETA && (A.K == 0 || !g_theta)) return MDG_OK;          // nothing to compute
     if (A.N <= FP_WAVE_ATOMS) {
         constexpr int FPB = FP_BLOCK / MDG_WAVE;
-        const dim3 grid((A.F + FPB - 1) / FPB);
-        if (mode == FP_ROWS) hipLaunchKernelGGL((fp_frame_kernel<V, MDG_WAVE, FP_ROWS>), grid, dim3(FP_BLOCK), 0, st, A);
-        else hipLaunchKernelGGL((fp_frame_kernel<V, MDG_WAVE, FP_THETA>), grid, dim3(FP_BLOCK), 0, st, A);
+        hipLaunchKernelGGL((fp_frame_kernel<V, MDG_WAVE, MODE>), dim3((A.F + FPB - 1) / FPB), dim3(FP_BLOCK), 0, st, A);
     } else if (A.N <= FP_GROUP_ATOMS) {
-        if (mode == FP_ROWS) hipLaunchKernelGGL((fp_frame_kernel<V, FP_BLOCK, FP_ROWS>), dim3(A.F), dim3(FP_BLOCK), 0, st, A);
-        else hipLaunchKernelGGL((fp_frame_kernel<V, FP_BLOCK, FP_THETA>), dim3(A.F), dim3(FP_BLOCK), 0, st, A);
+        hipLaunchKernelGGL((fp_frame_kernel<V, FP_BLOCK, MODE>), dim3(A.F), dim3(FP_BLOCK), 0, st, A);
     } else {
         const int nb = tile_blocks(A.N);
-        if (mode == FP_ROWS) hipLaunchKernelGGL((fp_tile_rows_kernel<V>), dim3(A.F, nb), dim3(FP_BLOCK), 0, st, A, nb);
+        if constexpr (MODE == FP_ROWS) hipLaunchKernelGGL((fp_tile_rows_kernel<V>), dim3(A.F, nb), dim3(FP_BLOCK), 0, st, A, nb);
         else hipLaunchKernelGGL((fp_tile_once_kernel<V, FP_THETA>), dim3(A.F, tile_count(A.N)), dim3(FP_BLOCK), 0, st, A, nb);
     }
     MDG_CHECK_LAUNCH(who);
     if (A.K > 0 && g_theta) {
-        hipLaunchKernelGGL(fp_col_sum_kernel, dim3(A.K), dim3(FP_BLOCK), 0, st, A.partial, theta_rows(A.F, A.N, mode), A.K, g_theta);
+        hipLaunchKernelGGL(fp_col_sum_kernel, dim3(A.K), dim3(FP_BLOCK), 0, st, A.partial, theta_rows(A.F, A.N, MODE), A.K, g_theta);
         MDG_CHECK_LAUNCH(who);
     }
     return MDG_OK;

@@ -3,9 +3,10 @@
 //
 //   raw[f, k] = sum_{i<j, 0<d<cutoff} exp(coeff (d - mu_k)^2)        mu_k = mu_0 + k h  (linspace centres, h = spacing)
 //
-// Pairs: D = x_j - x_i with the strict +-1/2 minimum image on the diagonal cell, 0 < d^2 < cutoff^2 with the un-contracted d^2
-// (common.hpp), the observable's [N, N] selection mask.  One frame per wave (N <= 128, four frames per workgroup) or per
-// workgroup (N <= 1024), the frame staged in LDS.
+// Pair set (strict +-1/2 minimum image on the diagonal cell, 0 < d^2 < cutoff^2 with the un-contracted d^2, the observable's
+// [N, N] selection mask), the staging of a frame in LDS and the walk over a row's partners are those of csrc/frame_pairs.hpp, in
+// its two whole-frame shapes: one frame per wave (N <= 128, four frames per workgroup) or per workgroup (N <= 1024).  This file
+// holds what a visit does with d = sqrt(d^2): the window, the exp2f terms and the fixed-point histogram.
 //
 // Reach: only the 2R + 1 centres around the nearest one, kc = rint((d - mu_0) / h), are summed, R = ceil(5.3 / (s h)) with
 // s = sqrt(-coeff log2 e), so exp(coeff x^2) = exp2(-(s x)^2): a dropped term is <= exp2(-5.3^2) = 2^-28.1 of a peak term (the
@@ -20,13 +21,12 @@
 //   dL/dd = sum_k g_raw[f, k] 2 coeff (d - mu_k) e_k  over the window,      g_x_i = -sum_j (dL/dd) D / d
 // summed per thread in a fixed order, no atomics.  A frame whose upstream row is all zero gets exact zeros.
 #include <math.h>
-#include "common.hpp"
+#include "frame_pairs.hpp"
 
 namespace {
 
-constexpr int RF_BLOCK = 256;
-constexpr int RF_WAVE_ATOMS = 128;
-constexpr int RF_MAX_ATOMS = 1024;
+using namespace frame_pairs;
+
 constexpr int RF_MAX_BINS = 1024;
 constexpr float RF_REACH = 5.3f;
 
@@ -45,13 +45,6 @@ struct RfArgs {
     MdgCell cell;
 };
 
-__device__ __forceinline__ bool rf_pair(const RfArgs& A, float& dx, float& dy, float& dz, float& d) {
-    min_image<true>(A.cell, dx, dy, dz);
-    const float d2 = norm2_ref(dx, dy, dz);
-    d = sqrtf(d2);
-    return (d2 < A.rc2) && (d2 != 0.f);
-}
-
 // the window [lo, hi] of centres summed for a pair at distance d (empty when lo > hi)
 __device__ __forceinline__ void rf_window(const RfArgs& A, float mu0, float d, int& lo, int& hi) {
     const float t = fminf(fmaxf((d - mu0) * A.inv_h, -1.0e9f), 1.0e9f);
@@ -61,17 +54,8 @@ __device__ __forceinline__ void rf_window(const RfArgs& A, float mu0, float d, i
 }
 
 template <int TPF>
-__device__ __forceinline__ void rf_stage(const RfArgs& A, float* sp, int g, int t, long long f, bool live) {
-    constexpr int CAP = TPF == MDG_WAVE ? RF_WAVE_ATOMS : RF_MAX_ATOMS;
-    if (live) {
-        const float* p = A.pos + (size_t)f * A.N * 3;
-        for (int e = t; e < 3 * A.N; e += TPF) sp[g * 3 * CAP + (e % 3) * CAP + e / 3] = p[e];
-    }
-}
-
-template <int TPF>
-__global__ __launch_bounds__(RF_BLOCK) void rdf_frames_fwd_kernel(const RfArgs A) {
-    constexpr int CAP = TPF == MDG_WAVE ? RF_WAVE_ATOMS : RF_MAX_ATOMS, FPB = RF_BLOCK / TPF;
+__global__ __launch_bounds__(FP_BLOCK) void rdf_frames_fwd_kernel(const RfArgs A) {
+    constexpr int CAP = TPF == MDG_WAVE ? FP_WAVE_ATOMS : FP_GROUP_ATOMS, FPB = FP_BLOCK / TPF;
     __shared__ float sp[FPB * 3 * CAP];
     extern __shared__ __attribute__((aligned(16))) unsigned long long rf_dyn[];       // [FPB, nbins] words, then mu [nbins]
     float* mu_s = reinterpret_cast<float*>(rf_dyn + (size_t)FPB * A.nbins);
@@ -79,34 +63,24 @@ __global__ __launch_bounds__(RF_BLOCK) void rdf_frames_fwd_kernel(const RfArgs A
     const long long f = (long long)blockIdx.x * FPB + g;
     const bool live = f < A.F;
     unsigned long long* hist = rf_dyn + (size_t)g * B;
-    for (int b = threadIdx.x; b < FPB * B; b += RF_BLOCK) rf_dyn[b] = 0ull;
-    for (int b = threadIdx.x; b < B; b += RF_BLOCK) mu_s[b] = A.mu[b];
-    rf_stage<TPF>(A, sp, g, t, f, live);
+    for (int b = threadIdx.x; b < FPB * B; b += FP_BLOCK) rf_dyn[b] = 0ull;
+    for (int b = threadIdx.x; b < B; b += FP_BLOCK) mu_s[b] = A.mu[b];
+    float* sf = sp + g * 3 * CAP;
+    if (live) stage_frame<TPF, CAP>(sf, A.pos + (size_t)f * N * 3, N, t);
     __syncthreads();
     if (live) {
-        const float* sx = sp + g * 3 * CAP;
-        const float* sy = sx + CAP;
-        const float* sz = sy + CAP;
         const float mu0 = mu_s[0];
-        const int half = (N - 1) >> 1;
-        // every unordered pair once: row i takes the partners (i + k) mod N (csrc/frame_pairs.hpp)
-        for (int i = t; i < N; i += TPF) {
-            const float xi = sx[i], yi = sy[i], zi = sz[i];
-            const int kmax = half + ((!(N & 1) && i < (N >> 1)) ? 1 : 0);
-            for (int k = 1; k <= kmax; ++k) {
-                int j = i + k;
-                if (j >= N) j -= N;
-                if (A.mask && !A.mask[(size_t)i * N + j]) continue;
-                float dx = sx[j] - xi, dy = sy[j] - yi, dz = sz[j] - zi, d;
-                if (!rf_pair(A, dx, dy, dz, d)) continue;
+        // every unordered pair once
+        for (int i = t; i < N; i += TPF)
+            walk_row<CAP>(A.cell, A.rc2, A.mask, sf, N, i, once_partners(N, i), [&](float, float, float, float d2) {
+                const float d = sqrtf(d2);
                 int lo, hi;
                 rf_window(A, mu0, d, lo, hi);
                 for (int b = lo; b <= hi; ++b) {
                     const float x = d - mu_s[b];
                     atomicAdd(&hist[b], fx64(A.scale * exp2f(-A.s2 * x * x)));
                 }
-            }
-        }
+            });
     }
     __syncthreads();
     if (live)
@@ -114,8 +88,8 @@ __global__ __launch_bounds__(RF_BLOCK) void rdf_frames_fwd_kernel(const RfArgs A
 }
 
 template <int TPF>
-__global__ __launch_bounds__(RF_BLOCK) void rdf_frames_bwd_kernel(const RfArgs A) {
-    constexpr int CAP = TPF == MDG_WAVE ? RF_WAVE_ATOMS : RF_MAX_ATOMS, FPB = RF_BLOCK / TPF;
+__global__ __launch_bounds__(FP_BLOCK) void rdf_frames_bwd_kernel(const RfArgs A) {
+    constexpr int CAP = TPF == MDG_WAVE ? FP_WAVE_ATOMS : FP_GROUP_ATOMS, FPB = FP_BLOCK / TPF;
     __shared__ float sp[FPB * 3 * CAP];
     extern __shared__ __attribute__((aligned(16))) float rf_dynf[];                   // g_raw rows [FPB, nbins], then mu [nbins]
     float* mu_s = rf_dynf + (size_t)FPB * A.nbins;
@@ -123,25 +97,18 @@ __global__ __launch_bounds__(RF_BLOCK) void rdf_frames_bwd_kernel(const RfArgs A
     const long long f = (long long)blockIdx.x * FPB + g;
     const bool live = f < A.F;
     float* g_s = rf_dynf + (size_t)g * B;
-    for (int b = threadIdx.x; b < B; b += RF_BLOCK) mu_s[b] = A.mu[b];
+    for (int b = threadIdx.x; b < B; b += FP_BLOCK) mu_s[b] = A.mu[b];
     if (live)
         for (int b = t; b < B; b += TPF) g_s[b] = A.g_raw[(size_t)f * B + b];
-    rf_stage<TPF>(A, sp, g, t, f, live);
+    float* sf = sp + g * 3 * CAP;
+    if (live) stage_frame<TPF, CAP>(sf, A.pos + (size_t)f * N * 3, N, t);
     __syncthreads();
     if (!live) return;
-    const float* sx = sp + g * 3 * CAP;
-    const float* sy = sx + CAP;
-    const float* sz = sy + CAP;
     const float mu0 = mu_s[0];
     for (int i = t; i < N; i += TPF) {
-        const float xi = sx[i], yi = sy[i], zi = sz[i];
         float gx = 0.f, gy = 0.f, gz = 0.f;
-        for (int k = 1; k < N; ++k) {
-            int j = i + k;
-            if (j >= N) j -= N;
-            if (A.mask && !A.mask[(size_t)i * N + j]) continue;
-            float dx = sx[j] - xi, dy = sy[j] - yi, dz = sz[j] - zi, d;
-            if (!rf_pair(A, dx, dy, dz, d)) continue;
+        walk_row<CAP>(A.cell, A.rc2, A.mask, sf, N, i, N - 1, [&](float dx, float dy, float dz, float d2) {
+            const float d = sqrtf(d2);
             int lo, hi;
             rf_window(A, mu0, d, lo, hi);
             float acc = 0.f;
@@ -151,7 +118,7 @@ __global__ __launch_bounds__(RF_BLOCK) void rdf_frames_bwd_kernel(const RfArgs A
             }
             const float c = -(A.coeff2 * acc) / d;                  // -(dL/dd) / d
             gx = fmaf(c, dx, gx); gy = fmaf(c, dy, gy); gz = fmaf(c, dz, gz);
-        }
+        });
         float* o = A.g_xyz + ((size_t)f * N + i) * 3;
         o[0] = gx; o[1] = gy; o[2] = gz;
     }
@@ -159,10 +126,8 @@ __global__ __launch_bounds__(RF_BLOCK) void rdf_frames_bwd_kernel(const RfArgs A
 
 int rf_args(RfArgs& A, const float* pos, int n_frames, int n_atoms, const MdgCell* cell, float cutoff, const uint8_t* mask,
             const float* mu, float spacing, float coeff, int nbins) {
-    MDG_CHECK_ARG(pos && cell && mu, "rdf_frames: null argument");
-    MDG_CHECK_ARG(n_frames > 0 && n_atoms > 0, "rdf_frames: empty trajectory");
-    MDG_CHECK_ARG(n_atoms <= RF_MAX_ATOMS, "rdf_frames: at most %d atoms per frame, got %d", RF_MAX_ATOMS, n_atoms);
-    MDG_CHECK_ARG(cell->diag, "rdf_frames: the cell must be diagonal (triclinic cells are not supported)");
+    const int rc = check_frames("rdf_frames", pos, cell, mu, n_frames, n_atoms, FP_GROUP_ATOMS);    // (no tiles)
+    if (rc != MDG_OK) return rc;
     MDG_CHECK_ARG(cutoff > 0.f && isfinite(cutoff), "rdf_frames: cutoff must be positive");
     MDG_CHECK_ARG(nbins >= 2 && nbins <= RF_MAX_BINS, "rdf_frames: nbins must be in [2, %d], got %d", RF_MAX_BINS, nbins);
     MDG_CHECK_ARG(coeff < 0.f && isfinite(coeff), "rdf_frames: coeff must be finite and negative (width > 0), got %g", (double)coeff);
@@ -184,11 +149,11 @@ int rf_args(RfArgs& A, const float* pos, int n_frames, int n_atoms, const MdgCel
 
 template <class K64, class K256>
 int rf_launch(const char* name, const RfArgs& A, size_t word, K64 k64, K256 k256, hipStream_t st) {
-    if (A.N <= RF_WAVE_ATOMS) {
-        constexpr int FPB = RF_BLOCK / MDG_WAVE;
-        hipLaunchKernelGGL(k64, dim3((A.F + FPB - 1) / FPB), dim3(RF_BLOCK), (size_t)A.nbins * (FPB * word + sizeof(float)), st, A);
+    if (A.N <= FP_WAVE_ATOMS) {
+        constexpr int FPB = FP_BLOCK / MDG_WAVE;
+        hipLaunchKernelGGL(k64, dim3((A.F + FPB - 1) / FPB), dim3(FP_BLOCK), (size_t)A.nbins * (FPB * word + sizeof(float)), st, A);
     } else {
-        hipLaunchKernelGGL(k256, dim3(A.F), dim3(RF_BLOCK), (size_t)A.nbins * (word + sizeof(float)), st, A);
+        hipLaunchKernelGGL(k256, dim3(A.F), dim3(FP_BLOCK), (size_t)A.nbins * (word + sizeof(float)), st, A);
     }
     MDG_CHECK_LAUNCH(name);
     return MDG_OK;
@@ -205,7 +170,7 @@ extern "C" int mdg_rdf_frames_fwd(const float* pos, int n_frames, int n_atoms, c
     MDG_CHECK_ARG(raw, "rdf_frames_fwd: null output");
     A.raw = raw;
     return rf_launch("rdf_frames_fwd_kernel", A, sizeof(unsigned long long), rdf_frames_fwd_kernel<MDG_WAVE>,
-                     rdf_frames_fwd_kernel<RF_BLOCK>, (hipStream_t)stream);
+                     rdf_frames_fwd_kernel<FP_BLOCK>, (hipStream_t)stream);
 }
 
 extern "C" int mdg_rdf_frames_bwd(const float* pos, int n_frames, int n_atoms, const MdgCell* cell, float cutoff,
@@ -216,6 +181,6 @@ extern "C" int mdg_rdf_frames_bwd(const float* pos, int n_frames, int n_atoms, c
     if (rc != MDG_OK) return rc;
     MDG_CHECK_ARG(g_raw && g_xyz, "rdf_frames_bwd: null g_raw or g_xyz");
     A.g_raw = g_raw; A.g_xyz = g_xyz;
-    return rf_launch("rdf_frames_bwd_kernel", A, sizeof(float), rdf_frames_bwd_kernel<MDG_WAVE>, rdf_frames_bwd_kernel<RF_BLOCK>,
+    return rf_launch("rdf_frames_bwd_kernel", A, sizeof(float), rdf_frames_bwd_kernel<MDG_WAVE>, rdf_frames_bwd_kernel<FP_BLOCK>,
                      (hipStream_t)stream);
 }

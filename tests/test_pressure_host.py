@@ -125,17 +125,21 @@ def _kernels(tmp_path):
 def test_virial_kernels_use_no_scratch_and_the_wave_kernels_keep_four_waves(tmp_path):
     ks = _kernels(tmp_path)
     names = sorted(ks)
-    for stem in ("virial_frame_kernelILi64ELb0E", "virial_frame_kernelILi64ELb1E", "virial_frame_kernelILi256ELb0E",
-                 "virial_frame_kernelILi256ELb1E", "virial_tile_fwd_kernel", "virial_tile_bwd_kernel", "virial_row_sum_kernel",
-                 "virial_col_sum_kernel"):
+    # the instantiations of csrc/frame_pairs.hpp for VirialVisit: value (0) and full rows (2), a wave / a workgroup per frame
+    wave = [n for n in names if "fp_frame_kernel" in n and "VirialVisitELi64E" in n]
+    assert len(wave) == 2, names
+    for stem in ("VirialVisitELi64ELi0E", "VirialVisitELi64ELi2E", "VirialVisitELi256ELi0E", "VirialVisitELi256ELi2E",
+                 "fp_tile_once_kernel", "fp_tile_rows_kernel", "fp_row_sum_kernel", "fp_col_sum_kernel"):
         assert any(stem in n for n in names), "kernel %s is missing from virial.hip.o: %s" % (stem, names)
     for n, (vgprs, scratch) in ks.items():
+        print("%-110s %3d VGPRs, %d B scratch" % (n, vgprs, scratch))
         assert scratch == 0, "%s uses %d B of scratch per lane" % (n, scratch)
-        if "virial_frame_kernelILi64E" in n:
+        if n in wave:
             assert vgprs <= WAVE_VGPRS, "%s: %d VGPRs" % (n, vgprs)
 
 
 def test_virial_source_has_no_floating_point_atomics():
-    src = open(SRC).read()
-    code = "\n".join(line.split("//")[0] for line in src.splitlines())
-    assert "unsafeAtomicAdd" not in code and "atomicAdd" not in code and "atomic" not in code.lower()
+    for path in (SRC, os.path.join(os.path.dirname(SRC), "frame_pairs.hpp")):        # the policy, and the sweeps it runs on
+        src = open(path).read()
+        code = "\n".join(line.split("//")[0] for line in src.splitlines())
+        assert "unsafeAtomicAdd" not in code and "atomicAdd" not in code and "atomic" not in code.lower(), path

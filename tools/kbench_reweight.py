@@ -1,11 +1,13 @@
 """Times the kernels behind trajectory reweighting on the headline's frames (R replicas x T frames x 108 atoms, LJ 12-6, cutoff
 2.5): thermo.PotentialEnergy forward, its parameters-only and full backward passes (csrc/energy.hip), rdf.per_frame forward and
-backward (csrc/rdf_frames.hip), and -- the yardstick -- Pressure.virial forward and backward (csrc/virial.hip) on the same
-frames.  HIP events after warm-up; the variants alternate inside every repetition and min / median / max over the repetitions
+backward (csrc/rdf_frames.hip), Pressure.virial forward and backward (csrc/virial.hip), and the kernels of
+thermo.TabulatedEnergy (csrc/energy_table.hip through ops.EnergyTableFn: forward, backward to the nodes only, backward with
+positions) for a small pairMLP tabulated once on 2 048 nodes -- all four per-frame families on the same frames.  HIP events
+after warm-up; the variants alternate inside every repetition and min / median / max over the repetitions
 are printed, so the run-to-run spread stands next to every difference.  Then one outer step of examples/fit_rdf_reweight.py
-(with and without a resample) next to one of examples/fit_rdf_lj.py at equal replicas and steps.
+(with and without a resample) next to one of examples/fit_rdf_lj.py at equal replicas and steps (--no-fits leaves that out).
 
-    python tools/kbench_reweight.py [--replicas 16384] [--frames 50] [--reps 7] [--fit-replicas 4096]"""
+    python tools/kbench_reweight.py [--replicas 16384] [--frames 50] [--reps 7] [--fit-replicas 4096] [--no-fits]"""
 import argparse
 import importlib.util
 import os
@@ -16,12 +18,12 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from mdgrad_amd import potentials  # noqa: E402
+from mdgrad_amd import _lib, ops, potentials  # noqa: E402
 from mdgrad_amd.interface import PairPotentials  # noqa: E402
 from mdgrad_amd.observable import rdf  # noqa: E402
 from mdgrad_amd.reweight import Reweighting  # noqa: E402
 from mdgrad_amd.system import System, FaceCenteredCubic  # noqa: E402
-from mdgrad_amd.thermo import PotentialEnergy, Pressure  # noqa: E402
+from mdgrad_amd.thermo import PotentialEnergy, Pressure, TabulatedEnergy  # noqa: E402
 
 DEV = "cuda:0"
 
@@ -47,17 +49,26 @@ def kernels(R, T, reps, warmup):
     gU = torch.rand(F, device=DEV, generator=g) + 0.5
     gR = torch.randn(F, 100, device=DEV, generator=g)
     ps = [mdl.sigma, mdl.epsilon]
+    # the tabulated family: the table of a small pairMLP, made once (the tabulation is torch autograd, not a kernel)
+    mlp = potentials.pairMLP(n_gauss=8, r_start=0.5, r_end=2.5, n_layers=1, n_width=8, nonlinear="ELU").to(DEV)
+    tab = TabulatedEnergy.from_terms(system, [(mlp, 2.5)], nodes=2048, check_range=False)
+    table = tab.tabulate(0).detach().requires_grad_(True)
+    u0, du, nodes = tab.grid(0)
+    cell = _lib.make_cell(system.get_cell())
+
+    def tabulated(x):
+        return ops.EnergyTableFn.apply(x, table, cell, nodes, u0, du, 2.5, None)
 
     def graph(fn, positions):
         qq = q.detach().requires_grad_(positions)
         return qq, fn(qq)
 
-    def bwd_of(fn, up, positions, params=True):
+    def bwd_of(fn, up, positions, leaves=ps):
         """a closure that times ONLY the backward pass: the forward runs outside the events"""
         def run():
             qq, out = graph(fn, positions)
             torch.cuda.synchronize()
-            return event_ms(lambda: torch.autograd.grad((out * up).sum(), ([qq] if positions else []) + (ps if params else [])))
+            return event_ms(lambda: torch.autograd.grad((out * up).sum(), ([qq] if positions else []) + leaves))
         return run
 
     def fwd_of(fn):
@@ -66,11 +77,14 @@ def kernels(R, T, reps, warmup):
                 return event_ms(lambda: fn(q))
         return run
 
-    variants = [("energy forward", fwd_of(energy)), ("virial forward (yardstick)", fwd_of(press.virial)),
+    variants = [("energy forward", fwd_of(energy)), ("virial forward", fwd_of(press.virial)),
                 ("energy backward, parameters only", bwd_of(energy, gU, False)),
                 ("energy backward, full rows", bwd_of(energy, gU, True)),
-                ("virial backward (yardstick)", bwd_of(press.virial, gU, True)),
-                ("rdf.per_frame forward", fwd_of(obs.per_frame)), ("rdf.per_frame backward", bwd_of(obs.per_frame, gR, True, False))]
+                ("virial backward", bwd_of(press.virial, gU, True)),
+                ("rdf.per_frame forward", fwd_of(obs.per_frame)), ("rdf.per_frame backward", bwd_of(obs.per_frame, gR, True, [])),
+                ("tabulated energy forward", fwd_of(tabulated)),
+                ("tabulated energy backward, nodes only", bwd_of(tabulated, gU, False, [table])),
+                ("tabulated energy backward, full rows", bwd_of(tabulated, gU, True, [table]))]
     ms = {name: [] for name, _ in variants}
     for rep in range(warmup + reps):
         for name, run in variants:                       # alternating: every repetition times every variant once
@@ -170,9 +184,11 @@ if __name__ == "__main__":
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--fit-replicas", type=int, default=4096)
     ap.add_argument("--fit-frames", type=int, default=60)
+    ap.add_argument("--no-fits", action="store_true", help="time the kernels only, not the outer steps of the examples")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("kbench_reweight: no HIP device -- timings are taken on the GPU only")
     print("device:", torch.cuda.get_device_name(0), flush=True)
     kernels(args.replicas, args.frames, args.reps, args.warmup)
-    fits(args.fit_replicas, args.fit_frames, max(3, args.reps // 2), 1)
+    if not args.no_fits:
+        fits(args.fit_replicas, args.fit_frames, max(3, args.reps // 2), 1)

@@ -931,6 +931,23 @@ int mdg_adf_bwd(const float* pos, int n_frames, int n_atoms, const MdgCell* cell
                 const int32_t* cnt, int max_nbr, const float* mu, float spacing, float coeff, int nbins,
                 const float* g_raw, float* g_xyz, void* stream);
 
+/* K35  the bond-angle histogram of every frame on its own (mdgrad_amd/observable.py angle_distribution.per_frame; csrc/adf.hip):
+ *      the rows whose sum over the frames K14 returns -- same list, triplets, re-imaging, atan2 angle, weight 2, reach and
+ *      recurrence.
+ *   fwd: raw [n_frames, nbins].  A workgroup per frame; its contributions are summed as fixed-point integers in LDS and written
+ *        straight to raw[f, :]: bitwise reproducible, no global atomics, no scratch.  The scale comes from the triplet bound of
+ *        one frame, n_atoms max_nbr (max_nbr - 1) / 2.  A non-finite angle makes the row of its frame NaN and no other.
+ *   bwd: given g_raw [n_frames, nbins], writes g_xyz [n_frames * n_atoms, 3] = d(sum_fb g_raw raw)/d pos; atom-centric, every
+ *        thread reads the g_raw row of its own frame, the degenerate-triplet rule of K14, no atomics.  A frame whose g_raw row
+ *        is zero gets zeros.
+ */
+int mdg_adf_frames_fwd(const float* pos, int n_frames, int n_atoms, const MdgCell* cell /*host*/, float cutoff, const int32_t* col,
+                       const int32_t* cnt, int max_nbr, const float* mu, float spacing, float coeff, int nbins, float* raw,
+                       void* stream);
+int mdg_adf_frames_bwd(const float* pos, int n_frames, int n_atoms, const MdgCell* cell /*host*/, float cutoff, const int32_t* col,
+                       const int32_t* cnt, int max_nbr, const float* mu, float spacing, float coeff, int nbins,
+                       const float* g_raw, float* g_xyz, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * K15  pair virial of every frame and its gradient: the configurational part of the pressure
  *      P = (sum_i m_i |v_i|^2 + W) / (dim V)  (mdgrad_amd/thermo.py Pressure; the reference's sketch, torchmd/thermo.py:17-54,
@@ -1500,6 +1517,29 @@ int mdg_energy_table_fwd(const float* pos, int n_frames, int n_atoms, const MdgC
 int mdg_energy_table_bwd(const float* pos, int n_frames, int n_atoms, const MdgCell* cell /*host*/, const float* table, int n_nodes,
                          float u0, float du, float cutoff, const uint8_t* mask, const float* gU, float* g_pos, float* g_table,
                          float* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * K34  Stillinger-Weber energy of every frame, list-free (mdgrad_amd/thermo.py StillingerWeberEnergy: reweighting of the
+ *      one-species three-body model of K23; csrc/sw_frames.hip)
+ *   pos [n_frames, n_atoms, 3], n_atoms <= 1024; the cell must be diagonal; consts: the fixed constants of MdgSWConsts (its host
+ *   copies of epsilon, sigma, lam are not read); theta: DEVICE float[3] = (epsilon, sigma, lam), required.
+ *     U[f] = 1/2 sum_i sum_j phi2(r_ij) + sum_i sum_{j<k} phi3(j, i, k)          K23's definition and per-edge formulas
+ *   over the atoms j, k of frame f with D = x_j - x_i re-imaged by the strict minimum image (as K31) and 0 < r < a sigma,
+ *   r = sqrtf(d2), with the live device sigma: U[f] is the value StillingerWeber gives for frame f.  No list and no host read:
+ *   every atom finds its neighbours in the frame staged in LDS and keeps their indices in a compact row there.
+ *   dU_dtheta nullable [n_frames, 3] = dU[f]/d(epsilon, sigma, lam) from the same pass; the value part of U does not depend on
+ *   whether it is asked for, bit for bit.
+ *   Row cap: mdg_sw_frames_row_cap() = 64 neighbours inside a sigma (silicon, mW water: 4 - 30).  A frame in which an atom
+ *   has more comes out NaN (U and dU_dtheta), alone: rows are never truncated.
+ *   Fixed-order sums, no floating-point atomics: bitwise reproducible, and permuting the frames permutes the outputs bit for
+ *   bit.  Needs no workspace.
+ *   mdg_sw_frames_theta_bwd: g_theta[3] = sum_f gU[f] dU_dtheta[f, :] in a fixed order -- the whole parameter backward pass of
+ *   K34 (no second walk over the frames).
+ */
+int mdg_sw_frames_row_cap(void);
+int mdg_sw_frames_fwd(const float* pos, int n_frames, int n_atoms, const MdgCell* cell /*host*/, const MdgSWConsts* consts /*host*/,
+                      const float* theta, float* U, float* dU_dtheta, void* stream);
+int mdg_sw_frames_theta_bwd(const float* gU, const float* dU_dtheta, int n_frames, float* g_theta, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * f4  bonded terms over a static topology table (csrc/bonded.hip).

@@ -274,6 +274,10 @@ _SIGNATURES = {
                               C.c_int, P, P, P]),
     "mdg_adf_bwd": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), C.c_float, P, P, C.c_int, P, C.c_float, C.c_float,
                               C.c_int, P, P, P]),
+    "mdg_adf_frames_fwd": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), C.c_float, P, P, C.c_int, P, C.c_float, C.c_float,
+                                     C.c_int, P, P]),
+    "mdg_adf_frames_bwd": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), C.c_float, P, P, C.c_int, P, C.c_float, C.c_float,
+                                     C.c_int, P, P, P]),
     "mdg_bond_order_components": (C.c_int, [P, C.c_int]),
     "mdg_bond_order_fwd": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), C.c_float, C.c_float, P, P, C.c_int, P, C.c_int, P, P,
                                      P]),
@@ -328,6 +332,9 @@ _SIGNATURES = {
     "mdg_sw_partial_size": (C.c_int64, [C.c_int]),
     "mdg_sw_eval": (C.c_int, [P, C.c_int, C.POINTER(MdgCell), P, P, P, C.c_int, C.POINTER(MdgSWConsts), P, P,
                               P, P, P, P, P, P, C.c_float, C.c_int, P]),
+    "mdg_sw_frames_row_cap": (C.c_int, []),
+    "mdg_sw_frames_fwd": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), C.POINTER(MdgSWConsts), P, P, P, P]),
+    "mdg_sw_frames_theta_bwd": (C.c_int, [P, P, C.c_int, P, P]),
     "mdg_eam_partial_size": (C.c_int64, [C.c_int]),
     "mdg_eam_eval": (C.c_int, [P, C.c_int, C.POINTER(MdgCell), P, P, P, C.c_int, C.POINTER(MdgEAMConsts), P, P,
                                P, P, P, P, P, P, P, C.c_float, C.c_int, P]),

@@ -89,7 +89,12 @@ __device__ __forceinline__ bool window(const AdfArgs& A, const float* mu_s, floa
     return true;
 }
 
-__global__ __launch_bounds__(ADF_BLOCK) void adf_fwd_kernel(AdfArgs A, float scale, unsigned long long* __restrict__ words) {
+// FRAMES = false: a persistent grid over all list rows, one LDS histogram per workgroup flushed into the global words (K14).
+// FRAMES = true (K35): workgroup f walks the n_atoms rows of frame f alone and writes its LDS histogram straight to
+// raw[f, :] -- no global atomics; a non-finite angle makes that row NaN and no other.
+template <bool FRAMES>
+__global__ __launch_bounds__(ADF_BLOCK) void adf_fwd_kernel(AdfArgs A, float scale, unsigned long long* __restrict__ words,
+                                                            int n_atoms, double inv_scale, float* __restrict__ raw) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long hist[];
     float* mu_s = reinterpret_cast<float*>(hist + A.nbins);
     __shared__ int bad;
@@ -100,7 +105,10 @@ __global__ __launch_bounds__(ADF_BLOCK) void adf_fwd_kernel(AdfArgs A, float sca
     if (threadIdx.x == 0) bad = 0;
     __syncthreads();
     const float w2 = 2.f * scale;                                  // weight 2: both orders of the unordered pair
-    for (long long j = (long long)blockIdx.x * ADF_BLOCK + threadIdx.x; j < A.n_total; j += (long long)gridDim.x * ADF_BLOCK) {
+    const long long j_lo = FRAMES ? (long long)blockIdx.x * n_atoms : (long long)blockIdx.x * ADF_BLOCK;
+    const long long j_hi = FRAMES ? j_lo + n_atoms : A.n_total;
+    const long long j_step = FRAMES ? ADF_BLOCK : (long long)gridDim.x * ADF_BLOCK;
+    for (long long j = j_lo + threadIdx.x; j < j_hi; j += j_step) {
         const int n = A.cnt[j];
         const int32_t* row = A.col + j * A.max_nbr;
         const float3 xc = make_float3(A.pos[3 * j], A.pos[3 * j + 1], A.pos[3 * j + 2]);
@@ -132,6 +140,13 @@ __global__ __launch_bounds__(ADF_BLOCK) void adf_fwd_kernel(AdfArgs A, float sca
         }
     }
     __syncthreads();
+    if (FRAMES) {
+        const bool nan = bad != 0;
+        float* out = raw + (size_t)blockIdx.x * A.nbins;
+        for (int b = threadIdx.x; b < A.nbins; b += ADF_BLOCK)
+            out[b] = nan ? __int_as_float(0x7fc00000) : (float)((double)(long long)hist[b] * inv_scale);
+        return;
+    }
     for (int b = threadIdx.x; b < A.nbins; b += ADF_BLOCK)
         if (hist[b]) atomicAdd(&words[b], hist[b]);
     if (threadIdx.x == 0 && bad) atomicOr(reinterpret_cast<unsigned int*>(words + A.nbins), 1u);
@@ -168,17 +183,22 @@ __device__ __forceinline__ float dl_dtheta(const AdfArgs& A, const float* mu_s, 
     return -4.f * 0.69314718055994531f * A.s2 * acc;
 }
 
-__global__ __launch_bounds__(ADF_BLOCK) void adf_bwd_kernel(AdfArgs A, const float* __restrict__ g_raw, float* __restrict__ g_xyz) {
+// FRAMES = false: one g_raw [nbins] for every row (K14), grid = blocks of rows.
+// FRAMES = true (K35): grid (frames, blocks of the atoms of a frame); a thread reads the g_raw row of its own frame.
+template <bool FRAMES>
+__global__ __launch_bounds__(ADF_BLOCK) void adf_bwd_kernel(AdfArgs A, const float* __restrict__ g_raw, float* __restrict__ g_xyz,
+                                                            int n_atoms) {
     extern __shared__ __attribute__((aligned(16))) float smb[];
     float* mu_s = smb;
     float* g_s = smb + A.nbins;
     for (int b = threadIdx.x; b < A.nbins; b += ADF_BLOCK) {
         mu_s[b] = A.mu[b];
-        g_s[b] = g_raw[b];
+        g_s[b] = g_raw[(FRAMES ? (size_t)blockIdx.x * A.nbins : (size_t)0) + b];
     }
     __syncthreads();
-    const long long a = (long long)blockIdx.x * ADF_BLOCK + threadIdx.x;
-    if (a >= A.n_total) return;
+    const int a_in = blockIdx.y * ADF_BLOCK + threadIdx.x;           // FRAMES: the atom inside its frame
+    const long long a = FRAMES ? (long long)blockIdx.x * n_atoms + a_in : (long long)blockIdx.x * ADF_BLOCK + threadIdx.x;
+    if (FRAMES ? a_in >= n_atoms : a >= A.n_total) return;
     const int n = A.cnt[a];
     const int32_t* row = A.col + a * A.max_nbr;
     const float3 xa = make_float3(A.pos[3 * a], A.pos[3 * a + 1], A.pos[3 * a + 2]);
@@ -277,8 +297,8 @@ extern "C" int mdg_adf_fwd(const float* pos, int n_frames, int n_atoms, const Md
     const long long blocks = (A.n_total + ADF_BLOCK - 1) / ADF_BLOCK;
     const int grid = (int)(blocks < ADF_MAX_BLOCKS ? blocks : ADF_MAX_BLOCKS);
     const size_t lds = (size_t)nbins * (sizeof(unsigned long long) + sizeof(float));
-    hipLaunchKernelGGL(adf_fwd_kernel, dim3(grid), dim3(ADF_BLOCK), lds, st, A, scale,
-                       reinterpret_cast<unsigned long long*>(scratch));
+    hipLaunchKernelGGL(adf_fwd_kernel<false>, dim3(grid), dim3(ADF_BLOCK), lds, st, A, scale,
+                       reinterpret_cast<unsigned long long*>(scratch), n_atoms, 0.0, (float*)nullptr);
     MDG_CHECK_LAUNCH("adf_fwd_kernel");
     hipLaunchKernelGGL(adf_finish_kernel, dim3((nbins + 255) / 256), dim3(256), 0, st,
                        reinterpret_cast<const unsigned long long*>(scratch), nbins, 1.0 / (double)scale, raw);
@@ -294,8 +314,41 @@ extern "C" int mdg_adf_bwd(const float* pos, int n_frames, int n_atoms, const Md
     if (rc != MDG_OK) return rc;
     MDG_CHECK_ARG(g_raw && g_xyz, "adf_bwd: null g_raw or g_xyz");
     const long long blocks = (A.n_total + ADF_BLOCK - 1) / ADF_BLOCK;
-    hipLaunchKernelGGL(adf_bwd_kernel, dim3((unsigned)blocks), dim3(ADF_BLOCK), (size_t)nbins * 2 * sizeof(float),
-                       (hipStream_t)stream, A, g_raw, g_xyz);
+    hipLaunchKernelGGL(adf_bwd_kernel<false>, dim3((unsigned)blocks), dim3(ADF_BLOCK), (size_t)nbins * 2 * sizeof(float),
+                       (hipStream_t)stream, A, g_raw, g_xyz, n_atoms);
     MDG_CHECK_LAUNCH("adf_bwd_kernel");
+    return MDG_OK;
+}
+
+// ---------------------------------------------------------------------------------- K35: the rows of the sum above
+// raw [n_frames, nbins]: the histogram of every frame on its own.  The fixed-point scale comes from the triplet bound of ONE
+// frame, n_atoms max_nbr (max_nbr - 1) / 2, so no word of a frame's LDS histogram can leave int64.
+extern "C" int mdg_adf_frames_fwd(const float* pos, int n_frames, int n_atoms, const MdgCell* cell, float cutoff, const int32_t* col,
+                                  const int32_t* cnt, int max_nbr, const float* mu, float spacing, float coeff, int nbins,
+                                  float* raw, void* stream) {
+    AdfArgs A;
+    const int rc = adf_args(A, pos, n_frames, n_atoms, cell, cutoff, col, cnt, max_nbr, mu, spacing, coeff, nbins);
+    if (rc != MDG_OK) return rc;
+    MDG_CHECK_ARG(raw, "adf_frames_fwd: null output");
+    const double n_contrib = (double)n_atoms * (double)max_nbr * (double)(max_nbr - 1) * 0.5;
+    const float scale = 0.5f * fx64_limit(n_contrib);
+    const size_t lds = (size_t)nbins * (sizeof(unsigned long long) + sizeof(float));
+    hipLaunchKernelGGL(adf_fwd_kernel<true>, dim3(n_frames), dim3(ADF_BLOCK), lds, (hipStream_t)stream, A, scale,
+                       (unsigned long long*)nullptr, n_atoms, 1.0 / (double)scale, raw);
+    MDG_CHECK_LAUNCH("adf_frames_fwd_kernel");
+    return MDG_OK;
+}
+
+// g_xyz [n_frames * n_atoms, 3] = d(sum_fb g_raw[f, b] raw[f, b]) / d pos, g_raw [n_frames, nbins]
+extern "C" int mdg_adf_frames_bwd(const float* pos, int n_frames, int n_atoms, const MdgCell* cell, float cutoff, const int32_t* col,
+                                  const int32_t* cnt, int max_nbr, const float* mu, float spacing, float coeff, int nbins,
+                                  const float* g_raw, float* g_xyz, void* stream) {
+    AdfArgs A;
+    const int rc = adf_args(A, pos, n_frames, n_atoms, cell, cutoff, col, cnt, max_nbr, mu, spacing, coeff, nbins);
+    if (rc != MDG_OK) return rc;
+    MDG_CHECK_ARG(g_raw && g_xyz, "adf_frames_bwd: null g_raw or g_xyz");
+    hipLaunchKernelGGL(adf_bwd_kernel<true>, dim3(n_frames, (n_atoms + ADF_BLOCK - 1) / ADF_BLOCK), dim3(ADF_BLOCK),
+                       (size_t)nbins * 2 * sizeof(float), (hipStream_t)stream, A, g_raw, g_xyz, n_atoms);
+    MDG_CHECK_LAUNCH("adf_frames_bwd_kernel");
     return MDG_OK;
 }

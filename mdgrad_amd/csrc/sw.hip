@@ -24,7 +24,7 @@
 // No fused multiply-adds are formed by the compiler in this file: the float and the Dual instantiation then round the value
 // parts identically, so dU/dx of a LEVEL 1 launch equals that of a LEVEL 2 launch bit for bit.
 #pragma clang fp contract(off)
-#include "dual.hpp"
+#include "sw_core.hpp"          // SwK, sw_pow, SwEdge, sw_edge: shared with csrc/sw_frames.hip (K34)
 #include "manybody.hpp"
 
 namespace {
@@ -42,35 +42,6 @@ struct SwArgs {
     float* grad; float* hw; float* pth; float* pthw; float* partial;
     float oscale; int oacc;
 };
-
-struct SwK {                                   // per-thread constants
-    float eps, sigma, lam, le, rc, gs, gamma, cos0, A, B, fp, fq; int p, q;
-};
-
-template <class T> __device__ __forceinline__ T sw_pow(T x, int n) {
-    T r = mk<T>(1.f, 0.f);
-    while (n > 0) { if (n & 1) r = r * x; x = x * x; n >>= 1; }
-    return r;
-}
-
-// one list entry seen from its centre: unit vector centre -> end, r, 1/r, 1/(r - rc), g
-template <class T> struct SwEdge { T ex, ey, ez, r, ir, inv, g; };
-
-// (dx, dy, dz) = end - centre with the stored image applied, (ax, ay, az) = w_end - w_centre.  False outside the support.
-template <class T>
-__device__ __forceinline__ bool sw_edge(const SwK& K, float dx, float dy, float dz, float ax, float ay, float az, SwEdge<T>& e) {
-    const T x = mk<T>(dx, ax), y = mk<T>(dy, ay), z = mk<T>(dz, az);
-    const T one = mk<T>(1.f, 0.f);
-    const T d2 = x * x + y * y + z * z;
-    const float rv = sqrtf(val(d2));
-    if (!(rv > 0.f && rv < K.rc)) return false;              // the support test, on the r that r - rc is formed from
-    e.r = fsqrt_(d2);
-    e.ir = one / e.r;
-    e.ex = x * e.ir; e.ey = y * e.ir; e.ez = z * e.ir;
-    e.inv = one / (e.r - K.rc);
-    e.g = fexp_(K.gs * e.inv);
-    return true;
-}
 
 template <class T, int LEVEL>
 __device__ __forceinline__ void sw_atom(const SwArgs& A, const SwK& K, int i, int sub, float (&out)[14]) {

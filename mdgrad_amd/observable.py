@@ -266,6 +266,77 @@ class angle_distribution(Angles):
             angles = self._angle_cos(frames).acos()
         return self.bins, count, angles
 
+    # -- the rows of the sum above: what a weighted average over frames needs (reweight.Reweighting) --------------------
+    def per_frame(self, xyz):
+        """raw[..., b] = sum over the ordered triplets of ONE frame of exp(coeff (theta - mu_b)^2): the un-normalised histogram
+        of every frame of xyz ([N, 3], [T, N, 3], [R, T, N, 3] or replica-stacked [..., k N, 3] giving a trailing k before the
+        bins), with the observable's cutoff and index_tuple selection.  `forward`'s histogram before its normalisation is the
+        sum of these rows; `normalise` turns a row, a sum or a weighted average of rows into the distribution.  float32
+        device positions run the HIP kernels of `forward` frame by frame (ops.AdfFramesFn, csrc/adf.hip: a workgroup per
+        frame, no global atomics); host or float64 positions take the torch restatement `_torch_per_frame` with the exact
+        sum.  In the kernels a non-finite angle makes the row of its frame NaN and no other (an atom with a non-finite
+        coordinate has no listed neighbour, as in `forward`).  Differentiable once with respect to xyz."""
+        n = xyz.shape[-2] if xyz.dim() >= 2 else 0
+        if n == 0 or xyz.shape[-1] != 3 or n % self.natoms:
+            raise ValueError("angle_distribution.per_frame: xyz must be [..., k * %d, 3], got %s" % (self.natoms, tuple(xyz.shape)))
+        k = n // self.natoms
+        lead = tuple(xyz.shape[:-2]) + ((k,) if k > 1 else ())
+        x = xyz.reshape(-1, self.natoms, 3)
+        if x.is_cuda and x.dtype == torch.float32:
+            raw = ops.AdfFramesFn.apply(x, self.smear.offsets, self.coeff, self.cutoff, self._cell_struct, self._mask, self.spacing)
+        else:
+            raw = self._torch_per_frame(x)
+        return raw.reshape(lead + (self.nbins,))
+
+    def _torch_per_frame(self, x, budget=1 << 18):
+        """The same rows by torch ops in x's dtype on x's device: all pairs of a frame (the neighbour test of the list
+        builders: strict minimum image, 0 < d^2 < cutoff^2, the selection), every unordered pair of neighbours of every
+        centre with weight 2, bond vectors re-imaged with topology.get_offsets, theta = atan2(|u x v|, u.v), every centre (no
+        reach); chunked over frames.  A triplet with |u x v| <= 2^-20 |u| |v| has no gradient, as in the kernels."""
+        F, N = x.shape[0], x.shape[1]
+        L, mu = self.cell.detach().to(x), self.smear.offsets.detach().to(x)
+        sel = None if self._mask is None else self._mask.to(x.device).bool()
+        eps2 = (2.0 ** -20) ** 2
+        out = []
+        for f in range(F):
+            xf = x[f]
+            with torch.no_grad():
+                D = xf[None, :, :] - xf[:, None, :]
+                s = D * (1.0 / L)
+                D = D + (-(s > 0.5).to(x) + (s < -0.5).to(x)) * L
+                d2 = D.pow(2).sum(-1)
+                adj = (d2 < self.cutoff ** 2) & (d2 != 0)
+                if sel is not None:
+                    adj = adj & sel
+                c, e = torch.nonzero(adj, as_tuple=True)                     # (centre, end), sorted by centre then end
+                cnt = torch.bincount(c, minlength=N)
+                start = torch.cumsum(cnt, 0) - cnt
+                # every unordered pair (p < q) of entries of one centre's row
+                K = int(cnt.max()) if c.numel() else 0
+                tp, tq = torch.triu_indices(K, K, offset=1, device=x.device) if K > 1 else (c[:0], c[:0])
+                ok = tq[None, :] < cnt[:, None]
+                ci, ti = torch.nonzero(ok, as_tuple=True)
+                ia, ib = e[start[ci] + tp[ti]], e[start[ci] + tq[ti]]
+            row = x.new_zeros(self.nbins)
+            for a in range(0, ci.numel(), budget):
+                cc, aa, bb = ci[a:a + budget], ia[a:a + budget], ib[a:a + budget]
+                u, v = xf[aa] - xf[cc], xf[bb] - xf[cc]
+                u = u + get_offsets(u.detach(), L, x.device).to(x) * L
+                v = v + get_offsets(v.detach(), L, x.device).to(x) * L
+                w = torch.cross(u, v, dim=-1)
+                w2, dot = w.pow(2).sum(-1), (u * v).sum(-1)
+                deg = w2.detach() <= eps2 * (u.pow(2).sum(-1) * v.pow(2).sum(-1)).detach()
+                th = torch.where(deg, torch.atan2(torch.zeros_like(dot), dot).detach(),
+                                 torch.atan2(torch.where(deg, torch.ones_like(w2), w2).sqrt(), dot))
+                row = row + 2.0 * torch.exp(self.coeff * (th[:, None] - mu[None, :]).pow(2)).sum(0)
+            out.append(row)
+        return torch.stack(out)
+
+    def normalise(self, raw):
+        """The distribution of an un-normalised histogram raw[..., b] -- a row of `per_frame`, their sum or a weighted average
+        of them -- by the tail of `forward`: raw / raw.sum(-1)."""
+        return raw / raw.sum(-1, keepdim=True)
+
 
 def compute_dihe(xyz, dihes):
     """torchmd/observable.py:181-197: cos of the dihedral angle of every row (i, j, k, l) of `dihes` in every frame of xyz

@@ -5,9 +5,11 @@ torch.autograd.Function wrappers that own the differentiation contract
     FusedTrajFn                                                 whole NH-Verlet/Verlet trajectory + adjoint
     RdfRawFn                                                    soft histogram
     AdfRawFn                                                    soft histogram of bond angles
+    AdfFramesFn                                                 soft histogram of bond angles of every frame
     VirialFn                                                    pair virial of every frame (pressure)
     EnergyFramesFn                                              pair potential energy of every frame (reweighting)
     EnergyTableFn                                               tabulated pair energy of every frame (learned pair modules)
+    SWFramesFn                                                  Stillinger-Weber energy of every frame (reweighting)
     RdfFramesFn                                                 soft histogram of every frame
     SkFn                                                        static structure factor of every frame
     MsdFn                                                       mean-squared displacement over all lags (+ fourth moment)
@@ -2069,6 +2071,58 @@ class AdfRawFn(torch.autograd.Function):
         return gx.reshape(shape), None, None, None, None, None, None
 
 
+class AdfFramesFn(torch.autograd.Function):
+    """raw[f, b] = the histogram of AdfRawFn for frame f alone (csrc/adf.hip, K35): the kernel side of
+    observable.angle_distribution.per_frame; AdfRawFn's histogram is the sum of these rows.  xyz: [F, N, 3] frames.  The lists
+    are built in the frame chunks of AdfRawFn (`_adf_chunk_frames`), kept for the backward pass when there was one chunk and
+    rebuilt one at a time otherwise.  A frame's row depends on the frame and on the width of the list alone (the fixed-point
+    scale is n_atoms max_nbr (max_nbr - 1) / 2 deep), and that width is `estimate_max_nbr`'s unless a row outgrows it, so a
+    chunked run gives the bits of the single-chunk run.  Differentiable once with respect to the positions."""
+
+    @staticmethod
+    def forward(ctx, xyz, mu, coeff, cutoff, cell_struct, mask, spacing):
+        lib = _lib.load()
+        require_gpu(xyz, "xyz")
+        x3 = xyz.detach()
+        x3 = x3 if x3.is_contiguous() else x3.contiguous()
+        F, N, B = x3.shape[0], x3.shape[1], mu.shape[0]
+        dev = x3.device
+        muc = mu.detach().to(device=dev, dtype=torch.float32).contiguous()
+        fc = _adf_chunk_frames(F, N, cell_struct, cutoff)
+        raw, keep = torch.empty(F, B, device=dev), None
+        for f0 in range(0, F, fc):
+            f1 = min(F, f0 + fc)
+            flat = x3[f0:f1].reshape(-1, 3)
+            ell = build_ell(flat, cell_struct, cutoff, mask, group=N)
+            check(lib.mdg_adf_frames_fwd(ptr(flat), f1 - f0, N, C.byref(cell_struct), float(cutoff), ptr(ell.col), ptr(ell.cnt),
+                                         ell.max_nbr, ptr(muc), float(spacing), float(coeff), B, ptr(raw[f0:f1]),
+                                         stream_ptr(dev)), "mdg_adf_frames_fwd")
+            keep = ell if (f0 == 0 and f1 == F) else None
+            del ell
+        ctx.ell = keep
+        ctx.args = (float(coeff), float(cutoff), cell_struct, mask, float(spacing), fc, xyz.shape)
+        ctx.save_for_backward(x3, muc)
+        return raw
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_raw):
+        lib = _lib.load()
+        x3, muc = ctx.saved_tensors
+        coeff, cutoff, cell_struct, mask, spacing, fc, shape = ctx.args
+        F, N, B = x3.shape[0], x3.shape[1], muc.shape[0]
+        gr = g_raw.detach().to(torch.float32).contiguous()
+        gx = torch.empty_like(x3)
+        for f0 in range(0, F, fc):
+            f1 = min(F, f0 + fc)
+            flat = x3[f0:f1].reshape(-1, 3)
+            ell = ctx.ell if ctx.ell is not None else build_ell(flat, cell_struct, cutoff, mask, group=N)
+            check(lib.mdg_adf_frames_bwd(ptr(flat), f1 - f0, N, C.byref(cell_struct), float(cutoff), ptr(ell.col), ptr(ell.cnt),
+                                         ell.max_nbr, ptr(muc), float(spacing), float(coeff), B, ptr(gr[f0:f1]), ptr(gx[f0:f1]),
+                                         stream_ptr(x3.device)), "mdg_adf_frames_bwd")
+        return gx.reshape(shape), None, None, None, None, None, None
+
+
 # ----------------------------------------------------------------------------- bond-orientational order
 BOND_ORDER_CHUNK_FRAMES = None      # when set: frames per chunk of BondOrderFn (tests force several chunks with it)
 
@@ -2289,6 +2343,79 @@ class EnergyTableFn(torch.autograd.Function):
                                        ptr(gx), ptr(gt), ptr(ws), stream_ptr(x3.device)), "mdg_energy_table_bwd")
         EnergyTableFn.last_route = "full" if want_x else "nodes"
         return ((gx.reshape(xshape) if want_x else None), (gt.reshape(tshape) if want_t else None)) + (None,) * 6
+
+
+# ----------------------------------------------------------------------------- Stillinger-Weber energy of every frame
+SW_FRAMES_MAX_ATOMS = 1024
+
+
+def sw_frames_row_cap():
+    """Neighbours inside a sigma that csrc/sw_frames.hip keeps per atom; a frame with a longer row comes out NaN."""
+    return int(_lib.load().mdg_sw_frames_row_cap())
+
+
+class SWFramesFn(torch.autograd.Function):
+    """U[f] = the Stillinger-Weber energy of every frame of xyz [F, N, 3] (csrc/sw_frames.hip, K34): the kernel side of
+    thermo.StillingerWeberEnergy.  epsilon, sigma, lam: the module's parameters (or buffers), through which the gradient flows;
+    theta: the device float [3] = (epsilon, sigma, lam) the kernel reads; consts: MdgSWConsts; list_scale: the position
+    gradient's list is searched at list_scale a sigma.  Differentiable once.
+
+    When a parameter requires grad the forward launch also emits dU_dtheta [F, 3], and the parameter part of the backward pass
+    is the fixed-order sum_f gU[f] dU_dtheta[f] (mdg_sw_frames_theta_bwd): no pair or triplet is visited again.  The position
+    gradient, off the reweighting path, goes through the list kernel of K23 (mdg_sw_eval): the frames stacked as groups of N
+    behind a list searched at list_scale a sigma (sigma of the forward call, read on the host there: one read per backward
+    pass, none on the parameters-only route), in the frame chunks of AdfRawFn, every frame's rows scaled by gU[f].
+    `SWFramesFn.last_route` names what the last backward pass ran: "theta" (the sum alone: detached frames, the reweighting
+    case) or "full" (the list kernel as well)."""
+
+    last_route = None
+
+    @staticmethod
+    def forward(ctx, xyz, epsilon, sigma, lam, theta, cell_struct, consts, list_scale):
+        lib = _lib.load()
+        require_gpu(xyz, "xyz")
+        _check_theta(theta)
+        x3 = xyz.detach()
+        x3 = x3 if x3.is_contiguous() else x3.contiguous()
+        F, N = x3.shape[0], x3.shape[1]
+        want_th = any(ctx.needs_input_grad[1:4])
+        U = torch.empty(F, device=x3.device)
+        dU = torch.empty(F, 3, device=x3.device) if want_th else None
+        check(lib.mdg_sw_frames_fwd(ptr(x3), F, N, C.byref(cell_struct), C.byref(consts), ptr(theta), ptr(U), ptr(dU),
+                                    stream_ptr(x3.device)), "mdg_sw_frames_fwd")
+        ctx.args = (cell_struct, consts, float(list_scale), xyz.shape, [p.shape for p in (epsilon, sigma, lam)])
+        ctx.save_for_backward(x3, theta.detach() if ctx.needs_input_grad[0] else None, dU)
+        return U
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gU):
+        lib = _lib.load()
+        x3, th, dU = ctx.saved_tensors
+        cell_struct, consts, list_scale, xshape, pshapes = ctx.args
+        F, N = x3.shape[0], x3.shape[1]
+        want_x = ctx.needs_input_grad[0]
+        g = gU.detach().to(torch.float32).contiguous()
+        gth = [None, None, None]
+        if dU is not None:
+            out = torch.empty(3, device=x3.device)
+            check(lib.mdg_sw_frames_theta_bwd(ptr(g), ptr(dU), F, ptr(out), stream_ptr(x3.device)), "mdg_sw_frames_theta_bwd")
+            gth = [out[k:k + 1].reshape(pshapes[k]) if ctx.needs_input_grad[1 + k] else None for k in range(3)]
+        gx = None
+        if want_x:
+            gx = torch.empty_like(x3)
+            list_cutoff = list_scale * consts.a * float(th[1])
+            fc = _adf_chunk_frames(F, N, cell_struct, list_cutoff)
+            for f0 in range(0, F, fc):
+                f1 = min(F, f0 + fc)
+                flat = x3[f0:f1].reshape(-1, 3)
+                ell = build_ell(flat, cell_struct, list_cutoff, None, group=N)
+                o = sw_eval(ell, flat, consts, th, energy=False, grad=True)
+                torch.mul(o["grad"].view(f1 - f0, N, 3), g[f0:f1, None, None], out=gx[f0:f1])
+                del ell
+            gx = gx.reshape(xshape)
+        SWFramesFn.last_route = "full" if want_x else "theta"
+        return (gx,) + tuple(gth) + (None, None, None, None)
 
 
 # ----------------------------------------------------------------------------- smeared pair count of every frame

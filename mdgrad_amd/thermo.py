@@ -2,7 +2,8 @@
 names and does not run, so the definition is this module's -- kinetic part plus pair virial over (d V), see `Pressure`.
 `PotentialEnergy`, the pair energy of every frame of a trajectory in one call, has no counterpart in the reference: the
 per-frame thermodynamic observable and the energy side of trajectory reweighting (mdgrad_amd/reweight.py); `TabulatedEnergy`
-is the same for learned pair modules (pairMLP ...), whose energy it tabulates."""
+is the same for learned pair modules (pairMLP ...), whose energy it tabulates, and `StillingerWeberEnergy` for the one-species
+three-body model (silicon, mW water)."""
 import torch
 
 from . import ops
@@ -387,3 +388,104 @@ class TabulatedEnergy(Observable):
                                    "take the first node's value" % (n, self.r_min * min(g["cutoff"] for g in self._groups),
                                                                     self.r_min))
         return U.reshape(lead)
+
+
+class StillingerWeberEnergy(Observable):
+    """Stillinger-Weber energy of every frame of a trajectory in one call, which `PotentialEnergy` refuses: the energy side of
+    trajectory reweighting (`reweight.Reweighting`) for the three-body models fitted to structure that a pair term cannot express
+    (silicon, mW water).
+
+        U[f] = sum_{i<j} phi2(r_ij) + sum_i sum_{j<k in row(i)} phi3(r_ij, r_ik, cos theta_jik)
+
+    with the definition, pair set (strict minimum image on the diagonal cell, 0 < r < a sigma) and formulas of
+    `interface.StillingerWeber`: U[f] is the value `model(q[f])` gives.  `model` is a StillingerWeber (one species); its
+    parameters are read where they are, so the optimiser that steps them steps this energy.  q: [N, 3], [T, N, 3],
+    [R, T, N, 3] or replica-stacked [..., k N, 3] (a trailing k).
+
+    float32 device positions run ONE list-free launch (ops.SWFramesFn, csrc/sw_frames.hip): every atom finds its neighbours in
+    its frame with the live device sigma, so a step of the trainable sigma costs nothing -- no neighbour list is searched and
+    nothing is read on the host (sigma is read once per change of its version counter for the half-cell check below, never
+    inside a HIP-graph capture).  The kernel reads (epsilon, sigma, lam) packed on the device at every call, so it follows the
+    parameters however they were stepped.  When epsilon, sigma or lam requires grad the same launch emits dU[f]/d(epsilon, sigma, lam), and the parameter
+    part of the backward pass is their fixed-order weighted sum: with detached frames (reweighting) the backward pass visits no
+    pair or triplet at all.  A position gradient, off that path, goes through the model's list kernel (mdg_sw_eval) on the
+    frames stacked behind a list searched at 1.02 a sigma (one host read of sigma per such backward pass).  Host or float64 positions take the model's torch restatement
+    `_torch_energy`, frame by frame.  Differentiable once.
+
+    An atom may hold at most `ops.sw_frames_row_cap()` = 64 neighbours inside a sigma (silicon and mW water hold 4 - 30); a
+    frame with a longer row comes out NaN rather than truncated.  a sigma may not exceed half the shortest cell length
+    (ValueError).
+
+    Not covered: StillingerWeberMulti, Tersoff and EAM frame energies, a StillingerWeber stacked with pair terms (add a
+    `PotentialEnergy` of the pair terms: Reweighting takes any callable), the virial, more than 1024 atoms per frame,
+    triclinic cells."""
+
+    MAX_ATOMS = ops.SW_FRAMES_MAX_ATOMS
+
+    def __init__(self, system, model):
+        from . import _lib
+        from .interface import StillingerWeber
+        if not isinstance(model, StillingerWeber):
+            raise NotImplementedError("StillingerWeberEnergy: the model must be an interface.StillingerWeber (one species); got "
+                                      "%s.  StillingerWeberMulti, Tersoff, EAM, pair terms and Stacks have no batched "
+                                      "Stillinger-Weber frame energy (built-in pair forms: thermo.PotentialEnergy; learned pair "
+                                      "modules: thermo.TabulatedEnergy)" % type(model).__name__)
+        super().__init__(system)
+        cs = _lib.make_cell(system.get_cell())
+        if not cs.diag:
+            raise ValueError("StillingerWeberEnergy: the cell must be diagonal (triclinic cells are not supported)")
+        if self.natoms > self.MAX_ATOMS:
+            raise ValueError("StillingerWeberEnergy: at most %d atoms per frame, got %d" % (self.MAX_ATOMS, self.natoms))
+        if self.natoms != model._group:
+            raise ValueError("StillingerWeberEnergy: the model was built for %d atoms per replica, the system holds %d"
+                             % (model._group, self.natoms))
+        self.model = model
+        self._cell_struct = cs
+        self._half_cell = 0.5 * min(cs.h[0], cs.h[4], cs.h[8])
+        self._sig_key = None
+        self._sync_cutoff()
+
+    def _sync_cutoff(self):
+        """The half-cell check on a sigma; sigma is read on the host only when its version counter moved, and never inside a
+        HIP-graph capture (StillingerWeber._sync_cutoff)."""
+        s = self.model.sigma
+        if s.is_cuda and torch.cuda.is_current_stream_capturing():
+            return
+        key = (s.data_ptr(), s._version)
+        if key == self._sig_key:
+            return
+        rc = self.model.a * float(s.detach())                  # (one host read per change of sigma)
+        if not rc > 0.0:
+            raise ValueError("StillingerWeberEnergy: sigma must stay positive (got %g)" % (rc / self.model.a))
+        if rc > self._half_cell:
+            raise ValueError("StillingerWeberEnergy: a * sigma = %g exceeds half the shortest cell length (%g): the minimum "
+                             "image no longer holds every neighbour" % (rc, self._half_cell))
+        self._sig_key = key
+
+    def _frames(self, x, name):
+        n = x.shape[-2] if x.dim() >= 2 else 0
+        if n == 0 or x.shape[-1] != 3 or n % self.natoms:
+            raise ValueError("StillingerWeberEnergy: %s must be [..., k * %d, 3], got %s" % (name, self.natoms, tuple(x.shape)))
+        k = n // self.natoms                             # replica-stacked state [..., k N, 3]: one value per replica
+        lead = tuple(x.shape[:-2]) + ((k,) if k > 1 else ())
+        return x.reshape(-1, self.natoms, 3), lead
+
+    def _torch_energy(self, x):
+        """The model's torch restatement, one frame at a time (each frame is one replica to it)."""
+        m = self.model
+        n_rep, m._n_rep = m._n_rep, 1
+        try:
+            return torch.stack([m._torch_energy(xf).reshape(()) for xf in x])
+        finally:
+            m._n_rep = n_rep
+
+    def forward(self, q):
+        """U of every frame of q."""
+        x, lead = self._frames(q, "q")
+        self._sync_cutoff()
+        if not (x.is_cuda and x.dtype == torch.float32):
+            return self._torch_energy(x).reshape(lead)
+        m = self.model
+        theta = torch.cat([p.detach().reshape(-1) for p in (m.epsilon, m.sigma, m.lam)]).to(device=x.device, dtype=torch.float32)
+        return ops.SWFramesFn.apply(x, m.epsilon, m.sigma, m.lam, theta, self._cell_struct, m._consts,
+                                    m.cutoff_reset).reshape(lead)

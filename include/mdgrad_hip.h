@@ -1542,6 +1542,53 @@ int mdg_sw_frames_fwd(const float* pos, int n_frames, int n_atoms, const MdgCell
 int mdg_sw_frames_theta_bwd(const float* gU, const float* dU_dtheta, int n_frames, float* g_theta, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * K36  tabulated embedded-atom energy of every frame, list-free (mdgrad_amd/thermo.py EAMEnergy: reweighting of the "eam/alloy"
+ *      term of K27; csrc/eam_frames.hip)
+ *   pos [n_frames, n_atoms, 3], n_atoms <= 1024, n_frames < 2^24; the cell must be diagonal; types: device int32 [n_atoms], the
+ *   species of the atoms of ONE frame (values clamped into [0, S)); consts, tables: the grids and the flat node image of K27.
+ *     U[f] = sum_i [ 1/2 sum_j phi_ab(r_ij) + F_a(rho_i) ],   rho_i = sum_j f_b(r_ij)          K27's definition and lookups
+ *   over the atoms j of frame f with D = x_j - x_i re-imaged by the strict minimum image (as K31) and 0 < r < rc, r = sqrtf(d2):
+ *   U[f] is the value the EAM term gives for frame f (linear continuation outside the grids; an atom without a neighbour gets
+ *   F_a(0)).  Every atom walks its frame, staged in LDS, once: one bracketing cell per pair serves phi_ab and f_b, and F_a is
+ *   applied when the walk ends.  No list, no row cap, no workspace.
+ *   table_mode: where the pair and density tables are read from: 1 = a workgroup copy in LDS (at most
+ *   mdg_eam_table_frames_lds_floats() floats of them, else MDG_EINVAL), 0 = global memory through the caches, -1 = the copy when
+ *   the tables fit it and n_atoms <= 128 (four frames share it), global memory otherwise.
+ *   The bits of U do not depend on it.
+ *   rho nullable [n_frames, n_atoms] = rho_i of every atom, the input of the node gradient; the value part of U does not depend
+ *   on whether it is asked for, bit for bit.
+ *   mdg_eam_table_frames_nodes_bwd: g_tables [mdg_eam_table_size()] = sum_f gU[f] dU[f]/dtables in the layout of `tables`, from
+ *   the frames, the saved rho and the tables: the forward walk once more, adding 1/2 gU_f basis(r_ij) to phi_ab and
+ *   gU_f F_a'(rho_i) basis(r_ij) to f_b per visit, gU_f basis(rho_i) to F_a per atom, as fixed-point numbers with integer
+ *   atomics (one int64 word per entry in `fx`, mdg_eam_table_fx_size() words; a table set of at most 6144 words is summed per
+ *   workgroup in LDS first).  The power-of-two scale of each table family is taken on the device from bounds -- max |gU|,
+ *   max |F'| and max |basis(rho)| over the saved rho, max(1, r_min / h_r) for basis(r), and n_frames n_atoms (n_atoms - 1)
+ *   resp. n_frames n_atoms contributions -- so that no sum can leave 2^62: no flag, no host read (a captured graph can hold the
+ *   call).  With pin_cutoff the last node of every phi and f table comes back as exactly 0.
+ *   Fixed-order float sums and integer atomics only: bitwise reproducible; permuting the frames permutes U bit for bit and
+ *   leaves g_tables unchanged bit for bit.  MDG_EINVAL: a null buffer, n_atoms > 1024, a non-diagonal cell, and the grid limits
+ *   of K27 (n_species outside [1, 4], n_r or n_rho outside [4, 4096], h_r <= 0 or h_rho <= 0, rc <= r_min, r_min < 0).
+ *
+ * K37  Sutton-Chen energy of every frame, list-free (EAMEnergy for the one-species term of K24; csrc/eam_frames.hip)
+ *   The skeleton of K36 with the closed-form S_n, S_m of K24 (csrc/eam_core.hpp); consts: rc, n, m, shift of MdgEAMConsts (its
+ *   host copies of epsilon, a, c are not read); theta: DEVICE float[3] = (epsilon, a, c), required.  An atom without a neighbour
+ *   has an embedding energy of exactly 0.
+ *   dU_dtheta nullable [n_frames, 3] = dU[f]/d(epsilon, a, c) from the same pass (K24's pth formulas); the value part of U does
+ *   not depend on whether it is asked for, bit for bit.  The parameter backward pass is mdg_sw_frames_theta_bwd (K34): the
+ *   fixed-order weighted sum over the frames, no second walk.
+ *   MDG_EINVAL: a null buffer, n_atoms > 1024, a non-diagonal cell, rc <= 0, exponents outside 1 <= m < n <= 16, shift not 0 / 1.
+ */
+int mdg_eam_table_frames_lds_floats(void);
+int mdg_eam_table_frames_fwd(const float* pos, int n_frames, int n_atoms, const MdgCell* cell /*host*/, const int32_t* types,
+                             const MdgEAMTableConsts* consts /*host*/, const float* tables /*device*/, int table_mode, float* U,
+                             float* rho, void* stream);
+int mdg_eam_table_frames_nodes_bwd(const float* pos, int n_frames, int n_atoms, const MdgCell* cell /*host*/, const int32_t* types,
+                                   const MdgEAMTableConsts* consts /*host*/, const float* tables /*device*/, const float* gU,
+                                   const float* rho, float* g_tables, int64_t* fx, void* stream);
+int mdg_eam_frames_fwd(const float* pos, int n_frames, int n_atoms, const MdgCell* cell /*host*/, const MdgEAMConsts* consts /*host*/,
+                       const float* theta, float* U, float* dU_dtheta, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * f4  bonded terms over a static topology table (csrc/bonded.hip).
  * Replaces torchmd/interface.py:447-455 (BondPotentials.forward: harmonic in the SQUARED bond length,
  * 1/2 k (|b|^2 - ro)^2) and :496-508 (AnglePotentials.forward: 1/2 k (theta - theta0)^2 over triples (i, j, k) centred on

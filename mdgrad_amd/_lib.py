@@ -356,6 +356,12 @@ _SIGNATURES = {
     "mdg_eam_table_fx_size": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "mdg_eam_table_eval": (C.c_int, [P, C.c_int, C.POINTER(MdgCell), P, P, P, C.c_int, P, C.POINTER(MdgEAMTableConsts), P, P,
                                      P, P, P, P, P, P, P, P, C.c_float, C.c_int, P]),
+    "mdg_eam_table_frames_lds_floats": (C.c_int, []),
+    "mdg_eam_table_frames_fwd": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), P, C.POINTER(MdgEAMTableConsts), P, C.c_int,
+                                           P, P, P]),
+    "mdg_eam_table_frames_nodes_bwd": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), P, C.POINTER(MdgEAMTableConsts), P, P,
+                                                 P, P, P, P]),
+    "mdg_eam_frames_fwd": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), C.POINTER(MdgEAMConsts), P, P, P, P]),
     "mdg_ewald_workspace": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "mdg_ewald_eval": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), P, P, P, C.c_int, P, P, P, P, P, P, P, C.c_float,
                                  C.c_int, P]),

@@ -23,9 +23,9 @@
 // LEVEL 2 runs the same code on Dual numbers seeded with w: x + t w gives dU/dx + t H w, and the per-atom parameter terms carry
 // d(w . grad)(d u_i / d theta) in their dual parts.  No fused multiply-adds are formed by the compiler in this file: the float
 // and the Dual instantiation round the value parts identically, so dU/dx of a LEVEL 1 launch equals that of a LEVEL 2 launch bit
-// for bit.
-#pragma clang fp contract(off)
-#include "dual.hpp"
+// for bit.  The per-thread constants, the integer power, the edge and S_k / S_k' live in csrc/eam_core.hpp, shared with the
+// list-free frame energy (csrc/eam_frames.hip, K37).
+#include "eam_core.hpp"
 #include "manybody.hpp"
 
 namespace {
@@ -45,56 +45,10 @@ struct EamArgs {
     float oscale; int oacc;
 };
 
-struct EamK {                                  // per-thread constants
-    float eps, a, c, rc, fn, fm;
-    float qn, qm;                              // (a/rc)^k of the shifted form, 0 as published
-    float ln, lm;                              // k (a/rc)^k / rc, 0 as published
-    int n, m;
-};
-
-template <class T> __device__ __forceinline__ T eam_pow(T x, int n) {
-    T r = mk<T>(1.f, 0.f);
-    while (n > 0) { if (n & 1) r = r * x; x = x * x; n >>= 1; }
-    return r;
-}
-
+// the per-thread constants (csrc/eam_core.hpp) from the device theta, or from the host values when there is none
 __device__ __forceinline__ EamK eam_constants(const EamArgs& A) {
-    EamK K;
-    K.eps = A.theta ? A.theta[0] : A.eps;
-    K.a = A.theta ? A.theta[1] : A.a;
-    K.c = A.theta ? A.theta[2] : A.c;
-    K.rc = A.rc; K.n = A.n; K.m = A.m; K.fn = (float)A.n; K.fm = (float)A.m;
-    K.qn = K.qm = K.ln = K.lm = 0.f;
-    if (A.shifted) {
-        const float s = K.a / K.rc;
-        K.qn = eam_pow<float>(s, K.n); K.qm = eam_pow<float>(s, K.m);
-        K.ln = K.fn * K.qn / K.rc; K.lm = K.fm * K.qm / K.rc;
-    }
-    return K;
-}
-
-// one list entry seen from its centre: unit vector centre -> end, r, 1/r
-template <class T> struct EamEdge { T ex, ey, ez, r, ir; };
-
-// (dx, dy, dz) = end - centre with the stored image applied, (ax, ay, az) = w_end - w_centre.  False outside the support.
-template <class T>
-__device__ __forceinline__ bool eam_edge(const EamK& K, float dx, float dy, float dz, float ax, float ay, float az, EamEdge<T>& e) {
-    const T x = mk<T>(dx, ax), y = mk<T>(dy, ay), z = mk<T>(dz, az);
-    const T d2 = x * x + y * y + z * z;
-    const float rv = sqrtf(val(d2));
-    if (!(rv > 0.f && rv < K.rc)) return false;              // the support test, on the r that r - rc is formed from
-    e.r = fsqrt_(d2);
-    e.ir = mk<T>(1.f, 0.f) / e.r;
-    e.ex = x * e.ir; e.ey = y * e.ir; e.ez = z * e.ir;
-    return true;
-}
-
-// S_k(r) and S_k'(r) from s = a / r:  S = s^k - q + l (r - rc),  S' = l - k s^k / r   (q = l = 0 as published)
-template <class T>
-__device__ __forceinline__ void eam_shape(const EamEdge<T>& e, T s, int k, float fk, float q, float l, float rc, T& S, T& dS) {
-    const T sk = eam_pow(s, k);
-    S = (sk - q) + l * (e.r - rc);
-    dS = l - fk * (sk * e.ir);
+    return eam_constants(A.theta ? A.theta[0] : A.eps, A.theta ? A.theta[1] : A.a, A.theta ? A.theta[2] : A.c, A.rc, A.n, A.m,
+                         A.shifted);
 }
 
 // the entry in slot s of row(i) as an edge i -> j; returns j, or -1 when there is nothing to add

@@ -28,9 +28,10 @@
 // no flag, no host read, no re-run.  A finish kernel turns the words into floats.
 //
 // No fused multiply-adds are formed by the compiler in this file: the float and the Dual instantiation round the value parts
-// identically, so dU/dx of a LEVEL 1 launch equals that of a LEVEL 2 launch bit for bit.
-#pragma clang fp contract(off)
-#include "dual.hpp"
+// identically, so dU/dx of a LEVEL 1 launch equals that of a LEVEL 2 launch bit for bit.  The layout of the flat image, the
+// bracketing cell with its weights, the fixed-order dot product and the power-of-two scale live in csrc/eam_table_core.hpp,
+// shared with the list-free frame energy (csrc/eam_frames.hip, K36).
+#include "eam_table_core.hpp"
 #include "manybody.hpp"
 
 namespace {
@@ -38,7 +39,6 @@ namespace {
 constexpr int EAM_LPA = 16;                   // lanes per atom, as in csrc/eam.hip
 constexpr int EAM_BLOCK = 256;
 constexpr int ET_LDS_WORDS = 6144;            // 48 KiB of int64 words: the largest table set that gets a workgroup copy in LDS
-constexpr int ET_BOUNDS = 8;                  // int64 words in front of the fixed-point words; the first five uint32 hold the bounds
 enum { ET_BV = 0, ET_BD, ET_FP, ET_FPP, ET_EM };   // max |basis|, |d basis|, |F'|, |F'' d rho|, |embed weight| as float bits
 
 struct EtArgs {
@@ -55,53 +55,10 @@ struct EtArgs {
     float oscale; int oacc;
 };
 
-__device__ __forceinline__ int et_npair(int S) { return S * (S + 1) / 2; }
 __device__ __forceinline__ int et_type(const EtArgs& A, int i) { return min(max(A.types[i], 0), A.S - 1); }
-__device__ __forceinline__ int et_pair(int a, int b) { const int lo = min(a, b), hi = max(a, b); return hi * (hi + 1) / 2 + lo; }
-__device__ __forceinline__ const float* et_pair_tab(const EtArgs& A, int p) { return A.tab + 2 * (size_t)p * A.nr; }
-__device__ __forceinline__ const float* et_dens_tab(const EtArgs& A, int b) { return A.tab + 2 * (size_t)(et_npair(A.S) + b) * A.nr; }
-__device__ __forceinline__ size_t et_embed_off(const EtArgs& A, int a) {
-    return 2 * ((size_t)(et_npair(A.S) + A.S) * A.nr + (size_t)a * A.nrho);
-}
-
-// the bracketing cell of x on the grid x0 + g / inv_h, g = 0 .. n - 1, and the weights of its four node entries
-// (v_g, d_g, v_{g+1}, d_{g+1}) in the value (b) and in the derivative with respect to t = (x - x_g) inv_h (d)
-template <class T> struct EtBasis { int g; T b[4]; T d[4]; };
-
-template <class T>
-__device__ __forceinline__ void et_basis(T x, float x0, float inv_h, int n, EtBasis<T>& B) {
-    const T one = mk<T>(1.f, 0.f), zero = mk<T>(0.f, 0.f);
-    const T u = inv_h * (x - x0);
-    const float uv = val(u);
-    if (uv < 0.f) {                                          // below the grid: v_0 + t d_0
-        B.g = 0;
-        B.b[0] = one; B.b[1] = u; B.b[2] = zero; B.b[3] = zero;
-        B.d[0] = zero; B.d[1] = one; B.d[2] = zero; B.d[3] = zero;
-        return;
-    }
-    B.g = (int)fminf(uv, (float)(n - 2));                    // (a NaN lands in the last cell: no index leaves the table)
-    const T t = u - (float)B.g;
-    if (val(t) > 1.f) {                                      // above the grid: v_{n-1} + (t - 1) d_{n-1}
-        B.b[0] = zero; B.b[1] = zero; B.b[2] = one; B.b[3] = t - 1.f;
-        B.d[0] = zero; B.d[1] = zero; B.d[2] = zero; B.d[3] = one;
-        return;
-    }
-    const T s = 1.f - t, ss = s * s, tt = t * t, ts = t * s;
-    B.b[0] = (2.f * t + 1.f) * ss;
-    B.b[1] = t * ss;
-    B.b[2] = tt * (3.f - 2.f * t);
-    B.b[3] = zero - tt * s;
-    B.d[0] = -6.f * ts;
-    B.d[1] = s * (1.f - 3.f * t);
-    B.d[2] = 6.f * ts;
-    B.d[3] = t * (3.f * t - 2.f);
-}
-
-// sum_k c_k node_k over the four entries at `nd`, in a fixed order
-template <class T>
-__device__ __forceinline__ T et_dot(const T (&c)[4], const float* __restrict__ nd) {
-    return ((nd[0] * c[0] + nd[1] * c[1]) + nd[2] * c[2]) + nd[3] * c[3];
-}
+__device__ __forceinline__ const float* et_pair_tab(const EtArgs& A, int p) { return A.tab + et_pair_off(p, A.nr); }
+__device__ __forceinline__ const float* et_dens_tab(const EtArgs& A, int b) { return A.tab + et_dens_off(A.S, b, A.nr); }
+__device__ __forceinline__ size_t et_embed_off(const EtArgs& A, int a) { return et_embed_off(A.S, a, A.nr, A.nrho); }
 
 // one list entry seen from its centre: unit vector centre -> end, r
 template <class T> struct EtEdge { T ex, ey, ez, r; };
@@ -126,23 +83,10 @@ __device__ __forceinline__ int et_entry(const EtArgs& A, size_t row, int s, floa
     return j;
 }
 
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 template <class T> __device__ __forceinline__ float et_max_abs4(float m, const T (&c)[4], bool dual) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) m = fmaxf(m, fabsf(dual ? dual_part(c[k]) : val(c[k])));
     return m;
-}
-
-// the power of two that takes a contribution of at most `bound` to at most lim / 2 (1 when there is nothing to scale)
-__device__ __forceinline__ float et_pow2(float bound, float lim) {
-    if (!(bound > 0.f) || !(bound <= 3.0e38f)) return 1.f;
-    const int k = ilogbf(lim) - ilogbf(bound) - 2;
-    return ldexpf(1.f, min(max(k, -120), 120));
 }
 
 // the scales of the pair, density and embedding words of a launch at `level`, from the bounds of the density pass

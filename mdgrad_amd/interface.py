@@ -1614,10 +1614,11 @@ class SuttonChen(_ManyBodyTerm):
         q = (a / self.cutoff) ** k
         return s - q + k * (r - self.cutoff) * q / self.cutoff
 
-    def _torch_energy(self, xyz):
+    def _torch_energy(self, xyz, thetas=None):
         """The same energy in torch ops, in the dtype and on the device of xyz (differentiable by autograd in xyz and in
-        epsilon, a, c)."""
-        eps, a, c = (p.to(xyz).reshape(()) for p in (self.epsilon, self.a, self.c))
+        epsilon, a, c).  `thetas`: (epsilon, a, c) as the caller holds them (thermo.EAMEnergy casts them once for all its
+        frames, so that their gradient is summed over the frames in the dtype of xyz)."""
+        eps, a, c = (p.to(xyz).reshape(()) for p in (thetas or (self.epsilon, self.a, self.c)))
         i, j, off = self._all_pairs(xyz, self.cutoff)
         cell = self.cell.detach().to(xyz)
         cell = torch.diag(cell) if cell.dim() == 1 else cell
@@ -1969,10 +1970,11 @@ class EAM(_ManyBodyTerm):
         return self._work
 
     # -- energy ----------------------------------------------------------------------------------------------------
-    def _torch_energy(self, xyz):
+    def _torch_energy(self, xyz, nodes=None):
         """The same energy in torch ops, in the dtype and on the device of xyz (differentiable by autograd in xyz and in the
-        three node tensors)."""
-        pn, dn, en = (v.to(xyz) for v in self._nodes())
+        three node tensors).  `nodes`: the three node tensors as the caller holds them (thermo.EAMEnergy casts them once for
+        all its frames, so that their gradient is summed over the frames in the dtype of xyz)."""
+        pn, dn, en = (v.to(xyz) for v in (nodes or self._nodes()))
         if self.pin_cutoff:                                   # the last node of phi and f is held at (0, 0): no gradient reaches it
             keep = torch.ones(self.n_r, 1, dtype=xyz.dtype, device=xyz.device)
             keep[-1] = 0.0

@@ -10,6 +10,7 @@ torch.autograd.Function wrappers that own the differentiation contract
     EnergyFramesFn                                              pair potential energy of every frame (reweighting)
     EnergyTableFn                                               tabulated pair energy of every frame (learned pair modules)
     SWFramesFn                                                  Stillinger-Weber energy of every frame (reweighting)
+    EAMTableFramesFn, EAMFramesFn                               embedded-atom energy of every frame (reweighting)
     RdfFramesFn                                                 soft histogram of every frame
     SkFn                                                        static structure factor of every frame
     MsdFn                                                       mean-squared displacement over all lags (+ fourth moment)
@@ -2416,6 +2417,157 @@ class SWFramesFn(torch.autograd.Function):
             gx = gx.reshape(xshape)
         SWFramesFn.last_route = "full" if want_x else "theta"
         return (gx,) + tuple(gth) + (None, None, None, None)
+
+
+# ----------------------------------------------------------------------------- embedded-atom energy of every frame
+EAM_FRAMES_MAX_ATOMS = 1024
+
+
+def eam_table_frames_lds_floats():
+    """The largest pair-and-density table set (in floats) that csrc/eam_frames.hip reads from a workgroup copy in LDS."""
+    return int(_lib.load().mdg_eam_table_frames_lds_floats())
+
+
+def _frames_list_grad(x3, g, cell_struct, cutoff, evaluate):
+    """gx[f] = g[f] * dU/dx of frame f through a term's list kernel: the frames stacked as groups of N behind a list searched
+    at `cutoff`, in the frame chunks of AdfRawFn; evaluate(ell, flat, n_frames) -> the [n_frames N, 3] gradient."""
+    F, N = x3.shape[0], x3.shape[1]
+    gx = torch.empty_like(x3)
+    fc = _adf_chunk_frames(F, N, cell_struct, cutoff)
+    for f0 in range(0, F, fc):
+        f1 = min(F, f0 + fc)
+        flat = x3[f0:f1].reshape(-1, 3)
+        ell = build_ell(flat, cell_struct, cutoff, None, group=N)
+        torch.mul(evaluate(ell, flat, f1 - f0).view(f1 - f0, N, 3), g[f0:f1, None, None], out=gx[f0:f1])
+        del ell
+    return gx
+
+
+class EAMTableFramesFn(torch.autograd.Function):
+    """U[f] = the tabulated embedded-atom energy of every frame of xyz [F, N, 3] (csrc/eam_frames.hip, K36): the kernel side of
+    thermo.EAMEnergy for interface.EAM.  pair_nodes, density_nodes, embed_nodes: the module's node tensors, through which the
+    gradient flows; tables: the flat float32 device image the kernel reads; types: device int32 [N], one frame's species;
+    consts: MdgEAMTableConsts.  Differentiable once.
+
+    When a node tensor requires grad the forward launch also keeps rho [F, N], and the node part of the backward pass is
+    mdg_eam_table_frames_nodes_bwd: one more walk over the frames with a fixed-point scatter, no list and no host read.  The
+    position gradient, off the reweighting path, goes through the list kernel of K27 (mdg_eam_table_eval) on the frames stacked
+    as groups of N, every frame's rows scaled by gU[f]; with both wanted each takes its own route.
+    `EAMTableFramesFn.last_route` names what the last backward pass ran: "nodes" (detached frames, the reweighting case),
+    "positions" or "full" (both).  `table_mode` (class attribute): -1 = the entry point chooses where the r-tables are read from
+    (a workgroup copy in LDS for small sets in the wave-per-frame shape, global memory otherwise), 0 = global memory, 1 = LDS."""
+
+    last_route = None
+    table_mode = -1
+
+    @staticmethod
+    def forward(ctx, xyz, pair_nodes, density_nodes, embed_nodes, tables, types, cell_struct, consts):
+        lib = _lib.load()
+        require_gpu(xyz, "xyz")
+        require_gpu(tables, "tables")
+        require_gpu(types, "types", dtype=torch.int32)
+        x3 = xyz.detach()
+        x3 = x3 if x3.is_contiguous() else x3.contiguous()
+        F, N = x3.shape[0], x3.shape[1]
+        if tables.numel() != eam_table_size(consts) or types.numel() != N:
+            raise ValueError("EAMTableFramesFn: tables must hold %d floats and types %d entries (got %d, %d)"
+                             % (eam_table_size(consts), N, tables.numel(), types.numel()))
+        want_nodes = any(ctx.needs_input_grad[1:4])
+        tb = tables.detach()
+        if want_nodes or ctx.needs_input_grad[0]:
+            tb = tb.clone()                                   # (the module's mirror is rewritten when the nodes are stepped)
+        U = torch.empty(F, device=x3.device)
+        rho = torch.empty(F, N, device=x3.device) if want_nodes else None
+        check(lib.mdg_eam_table_frames_fwd(ptr(x3), F, N, C.byref(cell_struct), ptr(types), C.byref(consts), ptr(tb),
+                                           int(EAMTableFramesFn.table_mode), ptr(U), ptr(rho), stream_ptr(x3.device)),
+              "mdg_eam_table_frames_fwd")
+        ctx.args = (cell_struct, consts, xyz.shape, [p.shape for p in (pair_nodes, density_nodes, embed_nodes)],
+                    [p.dtype for p in (pair_nodes, density_nodes, embed_nodes)])
+        ctx.save_for_backward(x3, tb, types, rho)
+        return U
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gU):
+        lib = _lib.load()
+        x3, tb, types, rho = ctx.saved_tensors
+        cell_struct, consts, xshape, pshapes, pdtypes = ctx.args
+        F, N = x3.shape[0], x3.shape[1]
+        want_x = ctx.needs_input_grad[0]
+        g = gU.detach().to(torch.float32).contiguous()
+        gn = [None, None, None]
+        if rho is not None:
+            out = torch.empty(eam_table_size(consts), device=x3.device)
+            fx = torch.empty(eam_table_fx_size(consts), dtype=torch.int64, device=x3.device)
+            check(lib.mdg_eam_table_frames_nodes_bwd(ptr(x3), F, N, C.byref(cell_struct), ptr(types), C.byref(consts), ptr(tb),
+                                                     ptr(g), ptr(rho), ptr(out), ptr(fx), stream_ptr(x3.device)),
+                  "mdg_eam_table_frames_nodes_bwd")
+            pos = 0
+            for k in range(3):
+                n = int(np.prod(pshapes[k]))
+                if ctx.needs_input_grad[1 + k]:
+                    gn[k] = out[pos:pos + n].reshape(pshapes[k]).to(pdtypes[k])
+                pos += n
+        gx = None
+        if want_x:
+            def evaluate(ell, flat, nf):
+                return eam_table_eval(ell, flat, types.repeat(nf), consts, tb, energy=False, grad=True)["grad"]
+            gx = _frames_list_grad(x3, g, cell_struct, float(consts.rc), evaluate).reshape(xshape)
+        EAMTableFramesFn.last_route = ("full" if rho is not None else "positions") if want_x else "nodes"
+        return (gx,) + tuple(gn) + (None, None, None, None)
+
+
+class EAMFramesFn(torch.autograd.Function):
+    """U[f] = the Sutton-Chen energy of every frame of xyz [F, N, 3] (csrc/eam_frames.hip, K37): the kernel side of
+    thermo.EAMEnergy for interface.SuttonChen.  epsilon, a, c: the module's parameters (or buffers), through which the gradient
+    flows; theta: the device float [3] = (epsilon, a, c) the kernel reads; consts: MdgEAMConsts.  Differentiable once.
+
+    When a parameter requires grad the forward launch also emits dU_dtheta [F, 3], and the parameter part of the backward pass
+    is the fixed-order sum_f gU[f] dU_dtheta[f] (mdg_sw_frames_theta_bwd, the reducer of K34): no pair is visited again.  The
+    position gradient, off the reweighting path, goes through the list kernel of K24 (mdg_eam_eval) on the frames stacked as
+    groups of N, every frame's rows scaled by gU[f].  `EAMFramesFn.last_route` names what the last backward pass ran: "theta"
+    (the sum alone: detached frames, the reweighting case), "positions" or "full" (both)."""
+
+    last_route = None
+
+    @staticmethod
+    def forward(ctx, xyz, epsilon, a, c, theta, cell_struct, consts):
+        lib = _lib.load()
+        require_gpu(xyz, "xyz")
+        _check_theta(theta)
+        x3 = xyz.detach()
+        x3 = x3 if x3.is_contiguous() else x3.contiguous()
+        F, N = x3.shape[0], x3.shape[1]
+        want_th = any(ctx.needs_input_grad[1:4])
+        U = torch.empty(F, device=x3.device)
+        dU = torch.empty(F, 3, device=x3.device) if want_th else None
+        check(lib.mdg_eam_frames_fwd(ptr(x3), F, N, C.byref(cell_struct), C.byref(consts), ptr(theta), ptr(U), ptr(dU),
+                                     stream_ptr(x3.device)), "mdg_eam_frames_fwd")
+        ctx.args = (cell_struct, consts, xyz.shape, [p.shape for p in (epsilon, a, c)])
+        ctx.save_for_backward(x3, theta.detach() if ctx.needs_input_grad[0] else None, dU)
+        return U
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gU):
+        lib = _lib.load()
+        x3, th, dU = ctx.saved_tensors
+        cell_struct, consts, xshape, pshapes = ctx.args
+        F = x3.shape[0]
+        want_x = ctx.needs_input_grad[0]
+        g = gU.detach().to(torch.float32).contiguous()
+        gth = [None, None, None]
+        if dU is not None:
+            out = torch.empty(3, device=x3.device)
+            check(lib.mdg_sw_frames_theta_bwd(ptr(g), ptr(dU), F, ptr(out), stream_ptr(x3.device)), "mdg_sw_frames_theta_bwd")
+            gth = [out[k:k + 1].reshape(pshapes[k]) if ctx.needs_input_grad[1 + k] else None for k in range(3)]
+        gx = None
+        if want_x:
+            def evaluate(ell, flat, nf):
+                return eam_eval(ell, flat, consts, th, energy=False, grad=True)["grad"]
+            gx = _frames_list_grad(x3, g, cell_struct, float(consts.rc), evaluate).reshape(xshape)
+        EAMFramesFn.last_route = ("full" if dU is not None else "positions") if want_x else "theta"
+        return (gx,) + tuple(gth) + (None, None, None)
 
 
 # ----------------------------------------------------------------------------- smeared pair count of every frame

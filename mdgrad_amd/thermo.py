@@ -2,8 +2,8 @@
 names and does not run, so the definition is this module's -- kinetic part plus pair virial over (d V), see `Pressure`.
 `PotentialEnergy`, the pair energy of every frame of a trajectory in one call, has no counterpart in the reference: the
 per-frame thermodynamic observable and the energy side of trajectory reweighting (mdgrad_amd/reweight.py); `TabulatedEnergy`
-is the same for learned pair modules (pairMLP ...), whose energy it tabulates, and `StillingerWeberEnergy` for the one-species
-three-body model (silicon, mW water)."""
+is the same for learned pair modules (pairMLP ...), whose energy it tabulates, `StillingerWeberEnergy` for the one-species
+three-body model (silicon, mW water) and `EAMEnergy` for the embedded-atom models of the metals (Sutton-Chen and tabulated)."""
 import torch
 
 from . import ops
@@ -416,9 +416,9 @@ class StillingerWeberEnergy(Observable):
     frame with a longer row comes out NaN rather than truncated.  a sigma may not exceed half the shortest cell length
     (ValueError).
 
-    Not covered: StillingerWeberMulti, Tersoff and EAM frame energies, a StillingerWeber stacked with pair terms (add a
-    `PotentialEnergy` of the pair terms: Reweighting takes any callable), the virial, more than 1024 atoms per frame,
-    triclinic cells."""
+    Not covered: StillingerWeberMulti and Tersoff frame energies (embedded-atom models: `EAMEnergy`), a StillingerWeber stacked
+    with pair terms (add a `PotentialEnergy` of the pair terms: Reweighting takes any callable), the virial, more than 1024
+    atoms per frame, triclinic cells."""
 
     MAX_ATOMS = ops.SW_FRAMES_MAX_ATOMS
 
@@ -429,7 +429,8 @@ class StillingerWeberEnergy(Observable):
             raise NotImplementedError("StillingerWeberEnergy: the model must be an interface.StillingerWeber (one species); got "
                                       "%s.  StillingerWeberMulti, Tersoff, EAM, pair terms and Stacks have no batched "
                                       "Stillinger-Weber frame energy (built-in pair forms: thermo.PotentialEnergy; learned pair "
-                                      "modules: thermo.TabulatedEnergy)" % type(model).__name__)
+                                      "modules: thermo.TabulatedEnergy; SuttonChen and EAM: thermo.EAMEnergy)"
+                                      % type(model).__name__)
         super().__init__(system)
         cs = _lib.make_cell(system.get_cell())
         if not cs.diag:
@@ -489,3 +490,101 @@ class StillingerWeberEnergy(Observable):
         theta = torch.cat([p.detach().reshape(-1) for p in (m.epsilon, m.sigma, m.lam)]).to(device=x.device, dtype=torch.float32)
         return ops.SWFramesFn.apply(x, m.epsilon, m.sigma, m.lam, theta, self._cell_struct, m._consts,
                                     m.cutoff_reset).reshape(lead)
+
+
+class EAMEnergy(Observable):
+    """Embedded-atom energy of every frame of a trajectory in one call: the energy side of trajectory reweighting
+    (`reweight.Reweighting`) for the metals, whose trainable object is often the shape of tabulated functions -- thousands of
+    node entries, all of whose gradients one weighted scatter gives at once.
+
+        U[f] = sum_i [ 1/2 sum_{j != i} phi_ab(r_ij) + F_a(rho_i) ],   rho_i = sum_{j != i} f_b(r_ij)
+
+    `model` is an `interface.EAM` (tabulated, 1 - 4 species) or an `interface.SuttonChen`; U[f] is the value `model(q[f])`
+    gives, with the model's own conventions: its pair set (strict minimum image on the diagonal cell, 0 < r < cutoff with
+    r = sqrtf(d2)), for EAM the linear continuation outside the grids and F_a(0) for an atom without a neighbour, for SuttonChen
+    an embedding energy of exactly 0 for such an atom and both shifts; per-atom `types` of one replica (one replica is one
+    frame).  q: [N, 3], [T, N, 3], [R, T, N, 3] or replica-stacked [..., k N, 3] (a trailing k).
+
+    float32 device positions run ONE list-free launch (ops.EAMTableFramesFn / ops.EAMFramesFn, csrc/eam_frames.hip): every
+    atom walks its frame once and has 1/2 sum phi and rho_i when the walk ends.  The parameters are read where they live, so the
+    optimiser that steps them steps this energy: SuttonChen's (epsilon, a, c) are packed on the device at every call, EAM's
+    nodes come from the model's float32 device mirror, refreshed as `EAM._tables()` refreshes it.  With detached frames
+    (reweighting) the backward pass of SuttonChen visits no pair (the same launch emitted dU[f]/d(epsilon, a, c); their
+    fixed-order weighted sum remains), and that of EAM is one more walk with an order-independent fixed-point scatter into the
+    nodes.  A position gradient, off that path, goes through the model's list kernel on the stacked frames.  Host or float64
+    positions take the model's torch restatement `_torch_energy`, frame by frame.  Differentiable once.
+
+    The cutoff may not exceed half the shortest cell length (ValueError: the strict minimum image would miss neighbours).
+
+    Not covered: Tersoff, TersoffMulti and StillingerWeberMulti frame energies, an embedded-atom term stacked with pair terms
+    (add a `PotentialEnergy` of the pair terms: Reweighting takes any callable), the virial, more than 1024 atoms per frame,
+    triclinic cells."""
+
+    MAX_ATOMS = ops.EAM_FRAMES_MAX_ATOMS
+
+    def __init__(self, system, model):
+        from . import _lib
+        from .interface import EAM, SuttonChen
+        if not isinstance(model, (EAM, SuttonChen)):
+            raise NotImplementedError("EAMEnergy: the model must be an interface.EAM or an interface.SuttonChen; got %s.  Stacks, "
+                                      "Tersoff and Stillinger-Weber terms have no batched embedded-atom frame energy (one-species "
+                                      "Stillinger-Weber: thermo.StillingerWeberEnergy; built-in pair forms: thermo.PotentialEnergy; "
+                                      "learned pair modules: thermo.TabulatedEnergy)" % type(model).__name__)
+        super().__init__(system)
+        cs = _lib.make_cell(system.get_cell())
+        if not cs.diag:
+            raise ValueError("EAMEnergy: the cell must be diagonal (triclinic cells are not supported)")
+        if self.natoms > self.MAX_ATOMS:
+            raise ValueError("EAMEnergy: at most %d atoms per frame, got %d" % (self.MAX_ATOMS, self.natoms))
+        if self.natoms != model._group:
+            raise ValueError("EAMEnergy: the model was built for %d atoms per replica, the system holds %d"
+                             % (model._group, self.natoms))
+        half = 0.5 * min(cs.h[0], cs.h[4], cs.h[8])
+        if model.cutoff > half:
+            raise ValueError("EAMEnergy: cutoff = %g exceeds half the shortest cell length (%g): the minimum image no longer "
+                             "holds every neighbour" % (model.cutoff, half))
+        self.model = model
+        self.tabulated = isinstance(model, EAM)
+        self._cell_struct = cs
+        self._types = None
+
+    def _frames(self, x, name):
+        n = x.shape[-2] if x.dim() >= 2 else 0
+        if n == 0 or x.shape[-1] != 3 or n % self.natoms:
+            raise ValueError("EAMEnergy: %s must be [..., k * %d, 3], got %s" % (name, self.natoms, tuple(x.shape)))
+        k = n // self.natoms                             # replica-stacked state [..., k N, 3]: one value per replica
+        lead = tuple(x.shape[:-2]) + ((k,) if k > 1 else ())
+        return x.reshape(-1, self.natoms, 3), lead
+
+    def _torch_energy(self, x):
+        """The model's torch restatement, one frame at a time (each frame is one replica to it)."""
+        m = self.model
+        n_rep, m._n_rep = m._n_rep, 1
+        types = m.types if self.tabulated else None
+        if self.tabulated:
+            m.types = types[:self.natoms]                 # (one entry per atom of the stacked system: one replica's)
+        # (cast once: the parameter gradient is summed over the frames in the dtype of x and rounded to the parameters' once)
+        params = tuple(p.to(x) for p in (m._nodes() if self.tabulated else (m.epsilon, m.a, m.c)))
+        try:
+            return torch.stack([m._torch_energy(xf, params).reshape(()) for xf in x])
+        finally:
+            m._n_rep = n_rep
+            if self.tabulated:
+                m.types = types
+
+    def forward(self, q):
+        """U of every frame of q."""
+        x, lead = self._frames(q, "q")
+        if not (x.is_cuda and x.dtype == torch.float32):
+            return self._torch_energy(x).reshape(lead)
+        m = self.model
+        if self.tabulated:
+            if self._types is None or self._types.device != x.device:
+                self._types = m.types[:self.natoms].to(device=x.device, dtype=torch.int32).contiguous()
+            tables = m._tables()
+            if tables.device != x.device:
+                tables = tables.to(x.device)
+            return ops.EAMTableFramesFn.apply(x, m.pair_nodes, m.density_nodes, m.embed_nodes, tables, self._types,
+                                              self._cell_struct, m._consts).reshape(lead)
+        theta = torch.cat([p.detach().reshape(-1) for p in (m.epsilon, m.a, m.c)]).to(device=x.device, dtype=torch.float32)
+        return ops.EAMFramesFn.apply(x, m.epsilon, m.a, m.c, theta, self._cell_struct, m._consts).reshape(lead)

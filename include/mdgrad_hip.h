@@ -88,9 +88,13 @@ int mdg_version(void);
  *
  * mdg_nbr_build_dense: all-pairs minimum image, any (triclinic) cell, O(N^2).
  * mdg_nbr_build_cell : cell list (bin -> sort -> 27-stencil), orthorhombic cells with
- *                      at least 3 bins per side; identical output.
+ *                      at least 3 bins per side; identical output.  A bin is wider than the
+ *                      cutoff by 2^-18 of the box side: nb = floor(L / (cutoff + 2^-18 L)), so a
+ *                      box of exactly n cutoffs has n - 1 bins (mdg_nbr_cell_bins: the counts, and
+ *                      1 when the cell list takes this cell at this cutoff, else 0).
  * `scratch` for the cell build: int32[ 2*N + 2*ncell_max + 8 ] (see mdg_nbr_cell_scratch).
  */
+int mdg_nbr_cell_bins(const MdgCell* cell /*host*/, float cutoff, int32_t* nb /*[3] or NULL*/);
 int mdg_nbr_build_dense(const float* pos, int n_atoms, const MdgCell* cell /*host*/,
                         float cutoff, const uint8_t* mask,
                         int32_t* col, int32_t* shift, int32_t* cnt, int max_nbr,
@@ -449,7 +453,8 @@ int mdg_rdf_fwd_ell(const float* pos, int64_t n_atoms_total, const MdgCell* cell
  * than the histogram): per frame, positions sorted by (bin, atom index); a wave per atom walks the 27-bin stencil and
  * counts every pair once on the fine integer grid (forward), or sums the tabulated pair force of
  * phi(d) = sum_k g_k exp(coeff (d - mu_k)^2) (backward: term/theta = the MDG_PAIR_TABLE built from dL/d raw, as for
- * mdg_pair_eval_ell; g_xyz [F][N][3] = dL/dxyz).  Orthorhombic cells of >= 3 `cutoff` per side, N <= 32 768
+ * mdg_pair_eval_ell; g_xyz [F][N][3] = dL/dxyz).  Orthorhombic cells of >= 3 bins per side, bins counted as
+ * mdg_nbr_cell_bins counts them (wider than `cutoff` by 2^-18 of the side), N <= 32 768
  * (mdg_rdf_cell_supported); cutoff = the list cutoff (>= the reach of the fine grid).  scratch: int32 words of
  * mdg_rdf_cell_scratch(), 16-byte aligned, filled by the forward call and read by the backward call of the same frames.
  * Replaces torchmd/observable.py:62-76 (generate_nbr_list + GaussianSmearing(...).sum(0)) and its autograd transpose. */

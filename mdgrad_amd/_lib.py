@@ -128,8 +128,9 @@ _SIGNATURES = {
     "mdg_nbr_build_dense": (C.c_int, [P, C.c_int, C.POINTER(MdgCell), C.c_float, P, P, P, P, C.c_int, P, P]),
     "mdg_nbr_build_dense_groups": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), C.c_float, P, P, P, P,
                                              C.c_int, P, P]),
+    "mdg_nbr_cell_bins": (C.c_int, [C.POINTER(MdgCell), C.c_float, C.POINTER(C.c_int32)]),
     "mdg_nbr_cell_scratch": (C.c_int64, [C.c_int, C.POINTER(MdgCell), C.c_float]),
-    "mdg_nbr_build_cell": (C.c_int, [P, C.c_int, C.POINTER(MdgCell), C.c_float, P, P, P, P, C.c_int, P, P, P]),
+    "mdg_nbr_build_cell":(C.c_int, [P, C.c_int, C.POINTER(MdgCell), C.c_float, P, P, P, P, C.c_int, P, P, P]),
     "mdg_nbr_cell_scratch_groups": (C.c_int64, [C.c_int, C.c_int, C.POINTER(MdgCell), C.c_float]),
     "mdg_nbr_build_cell_groups": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), C.c_float, P, P, P, P, C.c_int,
                                             P, P, P]),

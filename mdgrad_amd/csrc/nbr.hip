@@ -9,7 +9,9 @@
 //   cell  : bin atoms (wrapped fractional coordinates) -> counting sort -> one wave per
 //           atom walks the 27-bin stencil, then rank-sorts its row in LDS.  The pair test is
 //           the SAME arithmetic as the dense path (reference minimum image + un-contracted
-//           d^2), so both produce identical lists.
+//           d^2), so both produce identical lists -- provided the stencil holds every pair
+//           the test accepts: bins wider than the cutoff by a margin (make_bins), atoms at
+//           most one cell outside the box.  Pinned by tests/test_gpu_nbr_ref.py.
 #include <stdarg.h>
 #include <string.h>
 #include "common.hpp"
@@ -82,10 +84,20 @@ __global__ void nbr_dense_kernel(const float* __restrict__ pos, int N, int group
 // ---------------------------------------------------------------------------- cell list
 struct Bins { int nb[3]; int ncell; };
 
+// A bin must be WIDER than the cutoff by BIN_MARGIN of the box, not merely as wide: the 27-bin stencil holds every pair
+// the pair test accepts only while two atoms two bins apart are farther apart than the cutoff, and both sides of that
+// are float32 arithmetic.  bin_coord places an atom within L 2^-21.5 of its true bin (the rounded 1 / L times a
+// coordinate of up to two cells, the rounded fraction, the rounded product with nb), the pair test sees a distance within
+// L 1.5 * 2^-20 of the true one (tests/nbr_ref.py: delta): together under L 2.2 * 2^-20.  With floor(L / cutoff) bins a box
+// of a whole number of cutoffs per side has bins of exactly the cutoff and the cell list missed pairs the dense builder
+// lists (tests/golden/nbr_bin_edge.npz).  Every other box keeps its bin count, and its list bit for bit.
+constexpr double BIN_MARGIN = 1.0 / 262144.0;    // 2^-18
+
 __host__ __device__ inline Bins make_bins(const MdgCell& c, float cutoff) {
     Bins b;
     for (int d = 0; d < 3; ++d) {
-        int n = (int)floorf(c.h[4 * d] / cutoff);
+        const double L = (double)c.h[4 * d];
+        int n = (int)floor(L / ((double)cutoff + BIN_MARGIN * L));
         b.nb[d] = n < 1 ? 1 : n;
     }
     b.ncell = b.nb[0] * b.nb[1] * b.nb[2];
@@ -458,6 +470,13 @@ extern "C" int mdg_nbr_build_dense_groups(const float* pos, int n_atoms, int gro
                            shift, cnt, max_nbr, overflow);
     MDG_CHECK_LAUNCH("nbr_dense_kernel");
     return MDG_OK;
+}
+
+extern "C" int mdg_nbr_cell_bins(const MdgCell* cell, float cutoff, int32_t* nb) {
+    if (!cell || !(cutoff > 0.f)) return 0;
+    const Bins b = make_bins(*cell, cutoff);
+    if (nb) { nb[0] = b.nb[0]; nb[1] = b.nb[1]; nb[2] = b.nb[2]; }
+    return cell->diag && b.nb[0] >= 3 && b.nb[1] >= 3 && b.nb[2] >= 3;
 }
 
 extern "C" int64_t mdg_nbr_cell_scratch_groups(int n_atoms, int group, const MdgCell* cell, float cutoff) {

@@ -50,7 +50,10 @@ bool zfine_enabled() {
 CellGrid make_grid(const MdgCell& c, float cutoff) {
     CellGrid g;
     for (int d = 0; d < 3; ++d) {
-        int n = (int)floorf(c.h[4 * d] / cutoff);
+        // (a bin is wider than the cutoff by 2^-18 of the box, as in csrc/nbr.hip make_bins: with bins of exactly the cutoff
+        //  the float32 binning puts pairs the pair test accepts two bins apart, tests/golden/nbr_bin_edge.npz)
+        const double L = (double)c.h[4 * d];
+        int n = (int)floor(L / ((double)cutoff + L / 262144.0));
         g.nb[d] = n > 16 ? 16 : n;                       // (bins wider than the cutoff are fine; 16^3 = RC_MAX_CELLS)
     }
     g.zw = 1;

@@ -116,6 +116,10 @@ struct LargeArgs {
 // compacted neighbour buffer by index, which restores the ascending-j order of the all-atom scan: same sums, same bits.)
 constexpr int LG_MAX_CELLS = 4096;
 
+// The binning arithmetic of csrc/nbr.hip (bin_coord) with bins of floor(L / (cutoff + skin)) per side, NOT yet the margin
+// nbr.hip's make_bins adds: while lists are kept the skin is that margin (the exact cutoff is re-tested per pair), but a run
+// that searches at every evaluation (skin 0) in a box of a whole number of cutoffs per side has bins of exactly the cutoff,
+// where the 3 x 3 x 3 stencil can miss a pair at the cutoff (tests/test_nbr_ref_host.py shows the construction).
 __device__ __forceinline__ int bin_coord_l(float x, float inv, int nb) {
     float fr = x * inv;
     fr -= floorf(fr);

@@ -127,9 +127,11 @@ class EllList:
 
 
 def _use_cell_list(n_atoms, cs, cutoff):
+    """The cell list pays from 512 atoms, in an orthorhombic box of at least three bins per side -- bins as the
+    builder counts them (csrc/nbr.hip make_bins: wider than the cutoff by a margin)."""
     if not cs.diag or n_atoms < 512:
         return False
-    return all(cs.h[4 * d] / cutoff >= 3.0 for d in range(3))
+    return bool(_lib.load().mdg_nbr_cell_bins(C.byref(cs), float(cutoff), None))
 
 
 def build_ell(xyz, cell_struct, cutoff, mask=None, max_nbr=None, method="auto", group=None, need=None):

@@ -157,3 +157,68 @@ def test_rdf_variant_against_float64(name):
     if "coincident" in name:                   # (the pair at d = 0 is rejected: _check found the reference's finite gradient)
         x = case.frames()[0]
         assert (x[:, 17] == x[:, 3]).all() and np.isfinite(grads[0]).all() and np.abs(grads[0][:, 17]).max() > 0
+
+
+# ------------------------------------------------------------------ the cell sweep in a box of a whole number of cutoffs
+def _bin_edge_inputs(k):
+    """Construction k of tests/golden/nbr_bin_edge.npz (tests/nbr_ref.py case F: a pair at the cutoff across one bin, four
+    filler atoms) as one frame for the C entry points of csrc/rdf_cell.hip: 20 centres over the last length unit below the
+    cutoff, sigma = two spacings, and an upstream gradient on the centre one sigma below the cutoff, where a pair at the
+    cutoff pulls hardest (|dL/dd| = exp(-1/2) / sigma, about 5.8)."""
+    import nbr_ref
+    c = nbr_ref.cases()["F construction %d" % k]
+    rc = float(np.float32(c.cutoff))
+    mu = torch.linspace(rc - 1.0, rc, 20).numpy().copy()
+    dmu = float(mu[1] - mu[0])
+    g = np.zeros(20, np.float32)
+    g[17] = 1.0
+    return c, mu, dmu, -0.5 / (2.0 * dmu) ** 2, g
+
+
+@pytest.mark.parametrize("k", range(6))
+def test_cell_sweep_gradient_in_a_box_of_a_whole_number_of_cutoffs(k):
+    """mdg_rdf_fwd_cell + mdg_rdf_bwd_cell, called directly (ops.RdfRawFn takes this route from 512 atoms only, and puts the
+    list cutoff 5.3 widths beyond the last centre, where a pair at the cutoff weighs 2^-28): the gradient on the two atoms of
+    a pair that sits at the cutoff, two x- or y-bins apart when bins are exactly one cutoff wide, against the float64
+    reference -- measure and allowance as above (u-space pair table).  make_grid's x and y bins had no margin over the cutoff;
+    the sweep then never met these pairs (z is binned finer, with a margin of its own).  The forward histogram is not judged:
+    its fine grid ends at the cutoff by design, so a pair within float32 rounding of it is outside.
+    On an MI355X: floor 6.0e-8 (1.1e-7 for construction 5), allowed 6.0e-7 (1.1e-6), kernel 2.6e-8 .. 1.2e-7; with
+    floor(L / cutoff) bins along x and y the four constructions along x or y measured 1.0 (no gradient at all), the two
+    along z 2.6e-8 and 1.1e-7."""
+    from mdgrad_amd import _lib, ops
+    from mdgrad_amd._lib import check, ptr, stream_ptr
+    import ctypes as C
+    lib = _lib.load()
+    c, mu, dmu, coeff, g = _bin_edge_inputs(k)
+    n, cutoff = len(c.pos), float(np.float32(c.cutoff))
+    cs = _lib.make_cell(c.cell)
+    assert lib.mdg_rdf_cell_supported(n, C.byref(cs), cutoff) == 1 and lib.mdg_rdf_ell_supported(dmu, coeff, 20) == 1
+    frames = c.pos[None]
+    kw = dict(g_raw=g[None], dtype=np.float64)
+    ref = R.rdf_reference(frames, c.cell, mu, coeff, cutoff, **kw)
+    m64 = R.rdf_reference(frames, c.cell, mu, coeff, cutoff, model=("utable", 4096), **kw)
+    m32 = R.rdf_reference(frames, c.cell, mu, coeff, cutoff, g_raw=g[None], dtype=np.float32, model=("utable", 4096))
+    assert ref.A[0][0, 0] > 5.0 and ref.A[0][0, 1] > 5.0, "the pair must pull visibly"
+    a_min = R.scale_floor(g, coeff)
+    scale = (ref.A[0] + a_min)[..., None]
+    floor = max(float((np.abs(m32.g_xyz[0].astype(np.float64) - m64.g_xyz[0]) / scale).max()), R.ULP)
+    gap = float((np.abs(m64.g_xyz[0] - ref.g_xyz[0]) / scale).max())
+    allowed = MARGIN * floor + gap
+    x, muc = T(c.pos, DEV), T(mu, DEV)
+    raw = torch.empty(20, device=DEV)
+    scratch = torch.empty(int(lib.mdg_rdf_cell_scratch(1, n, C.byref(cs), cutoff)) + 4, dtype=torch.int32, device=DEV)
+    check(lib.mdg_rdf_fwd_cell(ptr(x), 1, n, C.byref(cs), cutoff, ptr(muc), dmu, coeff, 20, ptr(raw), ptr(scratch),
+                               stream_ptr(x.device)), "mdg_rdf_fwd_cell")
+    table, u0, du = ops._rdf_pair_table(T(g, DEV), muc, coeff, cutoff, 4096)
+    term = ops.make_term(dict(kind=ops.MDG_PAIR_TABLE, p=4096, a=u0, phi=du, c=1.0), cutoff, 0, 2 * 4096, None)
+    gx = torch.full_like(x, float("nan"))
+    check(lib.mdg_rdf_bwd_cell(1, n, C.byref(cs), cutoff, C.byref(term), ptr(table), ptr(scratch), ptr(gx), stream_ptr(x.device)),
+          "mdg_rdf_bwd_cell")
+    torch.cuda.synchronize()
+    got = gx.cpu().numpy()[None]
+    v = R.backward_error(got, ref, 0, a_min)
+    _report("cell sweep, bin-edge construction %d  floor %.3e  model_gap %.3e  allowed %.3e  kernel %.3e%s" % (
+        k, floor, gap, allowed, v, "" if v <= allowed else "   <-- FAILS"))
+    assert np.isfinite(raw.cpu().numpy()).all()
+    assert v <= allowed, (k, v, allowed, got[0, :2], ref.g_xyz[0][0, :2])

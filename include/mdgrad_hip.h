@@ -1594,6 +1594,40 @@ int mdg_eam_frames_fwd(const float* pos, int n_frames, int n_atoms, const MdgCel
                        const float* theta, float* U, float* dU_dtheta, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * K38  Tersoff energy of every frame, list-free (mdgrad_amd/thermo.py TersoffEnergy: reweighting of the bond-order models of
+ *      K25 and K26; csrc/tersoff_frames.hip)
+ *   pos [n_frames, n_atoms, 3], n_atoms <= 1024; the cell must be diagonal.
+ *     U[f] = 1/2 sum_i sum_{j in row(i)} fc_ab(r_ij) [A_ab exp(-lam1_ab r_ij) - b_ij B_ab exp(-lam2_ab r_ij)]
+ *   with K25 / K26's definition and formulas (csrc/tersoff_core.hpp) over the neighbours an atom finds in its own frame:
+ *   D = x_j - x_i under the strict minimum image, 0 < r < R_ab + D_ab on r = sqrtf(d2) with the entry of the directed pair
+ *   (centre species, end species); a bond with zeta = 0 has b = 1 and zero derivatives.  Only the bond pass runs: no list, no
+ *   bond_work, no workspace.
+ *   mdg_tersoff_frames_fwd        one species: consts = the constants of MdgTersoffConsts (its host copies of A, B, h are not
+ *                                 read); theta: DEVICE float[3] = (A, B, h), required.  dU_dtheta nullable [n_frames, 3].
+ *   mdg_tersoff_multi_frames_fwd  1 <= n_species <= 4: types DEVICE int32 [n_atoms] = one frame's species, shared by all frames
+ *                                 (clamped into the table); tables: DEVICE float [mdg_tersoff_multi_table_size(n_species)], the
+ *                                 image of K26.  dU_dtheta nullable [n_frames, 2 S^2 + S] in the order (A.flat, B.flat, h) of
+ *                                 K26's pth.
+ *   dU_dtheta comes from the same pass; the value part of U does not depend on whether it is asked for, bit for bit.
+ *   Row cap: mdg_tersoff_frames_row_cap() = 32 neighbours inside R + D (silicon, carbon, germanium and their alloys: 3 - 10).
+ *   A frame in which an atom has more comes out NaN (U and its dU_dtheta row), alone: rows are never truncated.
+ *   Fixed-order sums, no floating-point atomics: bitwise reproducible, and permuting the frames permutes the outputs bit for
+ *   bit.
+ *   mdg_frames_theta_bwd: g_theta[n_params] = sum_f gU[f] dU_dtheta[f, :] in double and in a fixed order, a workgroup per
+ *   parameter -- the whole parameter backward pass of K38 (no second walk over the frames).
+ *   MDG_EINVAL: a null buffer, n_atoms > 1024, a non-diagonal cell, n_species outside [1, 4], and for the one-species entry the
+ *   conditions of mdg_tersoff_eval on the constants (lam1, lam2 > 0; D > 0; R > D; m = 1 or 3; n > 0; beta >= 0; d != 0).
+ */
+int mdg_tersoff_frames_row_cap(void);
+int mdg_tersoff_frames_fwd(const float* pos, int n_frames, int n_atoms, const MdgCell* cell /*host*/,
+                           const MdgTersoffConsts* consts /*host*/, const float* theta /*device [3], required*/, float* U,
+                           float* dU_dtheta /*[F, 3] or null*/, void* stream);
+int mdg_tersoff_multi_frames_fwd(const float* pos, int n_frames, int n_atoms, const MdgCell* cell /*host*/,
+                                 const int32_t* types /*device [n_atoms]*/, int n_species, const float* tables /*device*/,
+                                 float* U, float* dU_dtheta /*[F, 2 S^2 + S] or null*/, void* stream);
+int mdg_frames_theta_bwd(const float* gU, const float* dU_dtheta, int n_frames, int n_params, float* g_theta, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * f4  bonded terms over a static topology table (csrc/bonded.hip).
  * Replaces torchmd/interface.py:447-455 (BondPotentials.forward: harmonic in the SQUARED bond length,
  * 1/2 k (|b|^2 - ro)^2) and :496-508 (AnglePotentials.forward: 1/2 k (theta - theta0)^2 over triples (i, j, k) centred on

@@ -363,6 +363,10 @@ _SIGNATURES = {
     "mdg_eam_table_frames_nodes_bwd": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), P, C.POINTER(MdgEAMTableConsts), P, P,
                                                  P, P, P, P]),
     "mdg_eam_frames_fwd": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), C.POINTER(MdgEAMConsts), P, P, P, P]),
+    "mdg_tersoff_frames_row_cap": (C.c_int, []),
+    "mdg_tersoff_frames_fwd": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), C.POINTER(MdgTersoffConsts), P, P, P, P]),
+    "mdg_tersoff_multi_frames_fwd": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), P, C.c_int, P, P, P, P]),
+    "mdg_frames_theta_bwd": (C.c_int, [P, P, C.c_int, C.c_int, P, P]),
     "mdg_ewald_workspace": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "mdg_ewald_eval": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(MdgCell), P, P, P, C.c_int, P, P, P, P, P, P, P, C.c_float,
                                  C.c_int, P]),

@@ -121,13 +121,14 @@ class _DeviceMirror:
     `numel`: the size of that image when it is not the summed size of the sources.  get() refreshes the buffer when a source
     changed (address or version counter); inside a HIP-graph capture it returns the buffer as it is -- the replaying pass
     refreshes it once before its first replay (`prepare_pass`), so the captured steps carry no torch op for it -- or, when
-    there is no buffer yet, a freshly packed tensor."""
+    there is no buffer yet, a freshly packed tensor.  get(fresh=True) rewrites the buffer whatever the version counters say
+    (an edit through `p.data` moves none)."""
 
     def __init__(self, sources, pack=_cat_f32, numel=None):
         self.sources, self.pack, self.numel = sources, pack, numel
         self.buf, self.key = None, None
 
-    def get(self):
+    def get(self, fresh=False):
         ps = self.sources()
         n = sum(p.numel() for p in ps) if self.numel is None else self.numel
         capturing = ps[0].is_cuda and torch.cuda.is_current_stream_capturing()
@@ -140,7 +141,7 @@ class _DeviceMirror:
         if capturing:
             return buf
         key = tuple((p.data_ptr(), p._version) for p in ps)
-        if self.key != key:
+        if fresh or self.key != key:
             self.pack(ps, out=buf)
             self.key = key
         return buf
@@ -2109,12 +2110,13 @@ class Tersoff(_ManyBodyTerm):
             self._scratch()
 
     # -- energy ----------------------------------------------------------------------------------------------------
-    def _torch_energy(self, xyz):
+    def _torch_energy(self, xyz, params=None):
         """The same energy in torch ops, in the dtype and on the device of xyz (differentiable by autograd in xyz and in
         A, B, h), with g in its published form: every pair as two directed bonds, grouped by centre into a padded [N, K]
-        table, zeta as a sum over the [N, K, K] pairs of entries of one row."""
+        table, zeta as a sum over the [N, K, K] pairs of entries of one row.  params: (A, B, h) to take instead of the
+        module's (a caller that evaluates many frames casts them once)."""
         k = self._consts
-        A, B, h = (p.to(xyz).reshape(()) for p in (self.A, self.B, self.h))
+        A, B, h = (p.to(xyz).reshape(()) for p in (params if params is not None else (self.A, self.B, self.h)))
         i, j, off = self._all_pairs(xyz, self.cutoff)
         if i.numel() == 0:
             return xyz.sum() * 0.0
@@ -2318,12 +2320,13 @@ class TersoffMulti(_ManyBodyTerm):
             self._scratch()
 
     # -- energy ----------------------------------------------------------------------------------------------------
-    def _torch_energy(self, xyz):
+    def _torch_energy(self, xyz, params=None):
         """The same energy in torch ops, in the dtype and on the device of xyz (differentiable by autograd in xyz and in
         A, B, h), with g in its published form: every pair as two directed bonds with the constants of (centre species, end
-        species), grouped by centre into a padded [N, K] table, zeta as a sum over the [N, K, K] pairs of entries of a row."""
+        species), grouped by centre into a padded [N, K] table, zeta as a sum over the [N, K, K] pairs of entries of a row.
+        params: (A, B, h) to take instead of the module's (a caller that evaluates many frames casts them once)."""
         const = lambda v: torch.as_tensor(v, dtype=xyz.dtype, device=xyz.device)
-        A, B, h = (p.to(xyz) for p in (self.A, self.B, self.h))
+        A, B, h = (p.to(xyz) for p in (params if params is not None else (self.A, self.B, self.h)))
         i, j, off = self._all_pairs(xyz, self.cutoff)
         if i.numel() == 0:
             return xyz.sum() * 0.0

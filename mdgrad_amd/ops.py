@@ -2572,6 +2572,136 @@ class EAMFramesFn(torch.autograd.Function):
         return (gx,) + tuple(gth) + (None, None, None)
 
 
+# ----------------------------------------------------------------------------- Tersoff energy of every frame
+TERSOFF_FRAMES_MAX_ATOMS = 1024
+
+
+def tersoff_frames_row_cap():
+    """Neighbours inside R + D that csrc/tersoff_frames.hip keeps per atom; a frame with a longer row comes out NaN."""
+    return int(_lib.load().mdg_tersoff_frames_row_cap())
+
+
+def _frames_theta_bwd(ctx, g, dU, shapes):
+    """The parameter part of a frame energy's backward pass: sum_f g[f] dU[f, :] (mdg_frames_theta_bwd), cut into the
+    parameters of `shapes` (inputs 1, 2, ... of the autograd function) where they require grad."""
+    lib = _lib.load()
+    F, n = dU.shape
+    out = torch.empty(n, device=dU.device)
+    check(lib.mdg_frames_theta_bwd(ptr(g), ptr(dU), F, n, ptr(out), stream_ptr(dU.device)), "mdg_frames_theta_bwd")
+    gth, pos = [], 0
+    for k, shape in enumerate(shapes):
+        m = int(np.prod(shape))
+        gth.append(out[pos:pos + m].reshape(shape) if ctx.needs_input_grad[1 + k] else None)
+        pos += m
+    return gth
+
+
+class TersoffFramesFn(torch.autograd.Function):
+    """U[f] = the Tersoff energy of every frame of xyz [F, N, 3] (csrc/tersoff_frames.hip, K38): the kernel side of
+    thermo.TersoffEnergy for interface.Tersoff.  A, B, h: the module's parameters (or buffers), through which the gradient
+    flows; theta: the device float [3] = (A, B, h) the kernel reads; consts: MdgTersoffConsts.  Differentiable once.
+
+    When a parameter requires grad the forward launch also emits dU_dtheta [F, 3], and the parameter part of the backward pass
+    is the fixed-order sum_f gU[f] dU_dtheta[f] (mdg_frames_theta_bwd): no bond is visited again.  The position gradient, off
+    the reweighting path, goes through the list kernels of K25 (mdg_tersoff_eval) on the frames stacked as groups of N behind
+    a list searched at R + D, bond_work sized per chunk, every frame's rows scaled by gU[f].  `TersoffFramesFn.last_route`
+    names what the last backward pass ran: "theta" (the sum alone: detached frames, the reweighting case) or "full" (the list
+    kernels as well)."""
+
+    last_route = None
+
+    @staticmethod
+    def forward(ctx, xyz, A, B, h, theta, cell_struct, consts):
+        lib = _lib.load()
+        require_gpu(xyz, "xyz")
+        _check_theta(theta)
+        x3 = xyz.detach()
+        x3 = x3 if x3.is_contiguous() else x3.contiguous()
+        F, N = x3.shape[0], x3.shape[1]
+        want_th = any(ctx.needs_input_grad[1:4])
+        th = theta.detach()
+        if ctx.needs_input_grad[0]:
+            th = th.clone()                                   # (the module's mirror is rewritten when the parameters are stepped)
+        U = torch.empty(F, device=x3.device)
+        dU = torch.empty(F, 3, device=x3.device) if want_th else None
+        check(lib.mdg_tersoff_frames_fwd(ptr(x3), F, N, C.byref(cell_struct), C.byref(consts), ptr(th), ptr(U), ptr(dU),
+                                         stream_ptr(x3.device)), "mdg_tersoff_frames_fwd")
+        ctx.args = (cell_struct, consts, xyz.shape, [p.shape for p in (A, B, h)])
+        ctx.save_for_backward(x3, th if ctx.needs_input_grad[0] else None, dU)
+        return U
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gU):
+        x3, th, dU = ctx.saved_tensors
+        cell_struct, consts, xshape, pshapes = ctx.args
+        want_x = ctx.needs_input_grad[0]
+        g = gU.detach().to(torch.float32).contiguous()
+        gth = _frames_theta_bwd(ctx, g, dU, pshapes) if dU is not None else [None, None, None]
+        gx = None
+        if want_x:
+            def evaluate(ell, flat, nf):
+                return tersoff_eval(ell, flat, consts, th, energy=False, grad=True)["grad"]
+            gx = _frames_list_grad(x3, g, cell_struct, float(consts.R + consts.D), evaluate).reshape(xshape)
+        TersoffFramesFn.last_route = "full" if want_x else "theta"
+        return (gx,) + tuple(gth) + (None, None, None)
+
+
+class TersoffMultiFramesFn(torch.autograd.Function):
+    """U[f] = the multi-species Tersoff energy of every frame of xyz [F, N, 3] (csrc/tersoff_frames.hip, K38): the kernel side
+    of thermo.TersoffEnergy for interface.TersoffMulti.  A [S, S], B [S, S], h [S]: the module's parameters (or buffers), through
+    which the gradient flows; tables: the device table image the kernel reads (TersoffMulti._tables()); types: device int32
+    [N], one frame's species; cutoff: max (R + D), where the position gradient's list is searched.  Differentiable once.
+
+    The routes are TersoffFramesFn's: dU_dtheta [F, 2 S^2 + S] from the forward launch in the order (A.flat, B.flat, h), the
+    parameter part of the backward pass by mdg_frames_theta_bwd, the position gradient through the list kernels of K26
+    (mdg_tersoff_multi_eval) with `types` tiled per chunk.  `TersoffMultiFramesFn.last_route`: "theta" or "full"."""
+
+    last_route = None
+
+    @staticmethod
+    def forward(ctx, xyz, A, B, h, tables, types, n_species, cell_struct, cutoff):
+        lib = _lib.load()
+        require_gpu(xyz, "xyz")
+        require_gpu(tables, "tables")
+        require_gpu(types, "types", dtype=torch.int32)
+        x3 = xyz.detach()
+        x3 = x3 if x3.is_contiguous() else x3.contiguous()
+        F, N, S = x3.shape[0], x3.shape[1], int(n_species)
+        if not 1 <= S <= TERSOFF_MULTI_MAX_SPECIES:
+            raise ValueError("mdgrad_amd: n_species must lie in [1, %d] (got %r)" % (TERSOFF_MULTI_MAX_SPECIES, n_species))
+        if tables.numel() != 8 * S * (S + 1) or not tables.is_contiguous() or types.numel() != N or not types.is_contiguous():
+            raise ValueError("TersoffMultiFramesFn: tables must hold %d floats and types %d entries (got %d, %d)"
+                             % (8 * S * (S + 1), N, tables.numel(), types.numel()))
+        want_th = any(ctx.needs_input_grad[1:4])
+        tb = tables.detach()
+        if ctx.needs_input_grad[0]:
+            tb = tb.clone()                                   # (the module's mirror is rewritten when the parameters are stepped)
+        U = torch.empty(F, device=x3.device)
+        dU = torch.empty(F, 2 * S * S + S, device=x3.device) if want_th else None
+        check(lib.mdg_tersoff_multi_frames_fwd(ptr(x3), F, N, C.byref(cell_struct), ptr(types), S, ptr(tb), ptr(U), ptr(dU),
+                                               stream_ptr(x3.device)), "mdg_tersoff_multi_frames_fwd")
+        ctx.args = (cell_struct, S, float(cutoff), xyz.shape, [p.shape for p in (A, B, h)])
+        ctx.save_for_backward(x3, tb if ctx.needs_input_grad[0] else None, types if ctx.needs_input_grad[0] else None, dU)
+        return U
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gU):
+        x3, tb, types, dU = ctx.saved_tensors
+        cell_struct, S, cutoff, xshape, pshapes = ctx.args
+        want_x = ctx.needs_input_grad[0]
+        g = gU.detach().to(torch.float32).contiguous()
+        gth = _frames_theta_bwd(ctx, g, dU, pshapes) if dU is not None else [None, None, None]
+        gx = None
+        if want_x:
+            def evaluate(ell, flat, nf):
+                return tersoff_multi_eval(ell, flat, types.repeat(nf), S, tb, energy=False, grad=True)["grad"]
+            gx = _frames_list_grad(x3, g, cell_struct, cutoff, evaluate).reshape(xshape)
+        TersoffMultiFramesFn.last_route = "full" if want_x else "theta"
+        return (gx,) + tuple(gth) + (None, None, None, None, None)
+
+
 # ----------------------------------------------------------------------------- smeared pair count of every frame
 RDF_FRAMES_MAX_ATOMS, RDF_FRAMES_MAX_BINS = 1024, 1024
 

@@ -3,7 +3,8 @@ names and does not run, so the definition is this module's -- kinetic part plus 
 `PotentialEnergy`, the pair energy of every frame of a trajectory in one call, has no counterpart in the reference: the
 per-frame thermodynamic observable and the energy side of trajectory reweighting (mdgrad_amd/reweight.py); `TabulatedEnergy`
 is the same for learned pair modules (pairMLP ...), whose energy it tabulates, `StillingerWeberEnergy` for the one-species
-three-body model (silicon, mW water) and `EAMEnergy` for the embedded-atom models of the metals (Sutton-Chen and tabulated)."""
+three-body model (silicon, mW water), `EAMEnergy` for the embedded-atom models of the metals (Sutton-Chen and tabulated) and
+`TersoffEnergy` for the bond-order models (Tersoff, TersoffMulti)."""
 import torch
 
 from . import ops
@@ -416,9 +417,9 @@ class StillingerWeberEnergy(Observable):
     frame with a longer row comes out NaN rather than truncated.  a sigma may not exceed half the shortest cell length
     (ValueError).
 
-    Not covered: StillingerWeberMulti and Tersoff frame energies (embedded-atom models: `EAMEnergy`), a StillingerWeber stacked
-    with pair terms (add a `PotentialEnergy` of the pair terms: Reweighting takes any callable), the virial, more than 1024
-    atoms per frame, triclinic cells."""
+    Not covered: StillingerWeberMulti frame energies (embedded-atom models: `EAMEnergy`; Tersoff and TersoffMulti:
+    `TersoffEnergy`), a StillingerWeber stacked with pair terms (add a `PotentialEnergy` of the pair terms: Reweighting takes
+    any callable), the virial, more than 1024 atoms per frame, triclinic cells."""
 
     MAX_ATOMS = ops.SW_FRAMES_MAX_ATOMS
 
@@ -429,7 +430,8 @@ class StillingerWeberEnergy(Observable):
             raise NotImplementedError("StillingerWeberEnergy: the model must be an interface.StillingerWeber (one species); got "
                                       "%s.  StillingerWeberMulti, Tersoff, EAM, pair terms and Stacks have no batched "
                                       "Stillinger-Weber frame energy (built-in pair forms: thermo.PotentialEnergy; learned pair "
-                                      "modules: thermo.TabulatedEnergy; SuttonChen and EAM: thermo.EAMEnergy)"
+                                      "modules: thermo.TabulatedEnergy; SuttonChen and EAM: thermo.EAMEnergy; Tersoff and "
+                                      "TersoffMulti: thermo.TersoffEnergy)"
                                       % type(model).__name__)
         super().__init__(system)
         cs = _lib.make_cell(system.get_cell())
@@ -516,9 +518,9 @@ class EAMEnergy(Observable):
 
     The cutoff may not exceed half the shortest cell length (ValueError: the strict minimum image would miss neighbours).
 
-    Not covered: Tersoff, TersoffMulti and StillingerWeberMulti frame energies, an embedded-atom term stacked with pair terms
-    (add a `PotentialEnergy` of the pair terms: Reweighting takes any callable), the virial, more than 1024 atoms per frame,
-    triclinic cells."""
+    Not covered: StillingerWeberMulti frame energies (Tersoff and TersoffMulti: `TersoffEnergy`), an embedded-atom term
+    stacked with pair terms (add a `PotentialEnergy` of the pair terms: Reweighting takes any callable), the virial, more than
+    1024 atoms per frame, triclinic cells."""
 
     MAX_ATOMS = ops.EAM_FRAMES_MAX_ATOMS
 
@@ -528,8 +530,9 @@ class EAMEnergy(Observable):
         if not isinstance(model, (EAM, SuttonChen)):
             raise NotImplementedError("EAMEnergy: the model must be an interface.EAM or an interface.SuttonChen; got %s.  Stacks, "
                                       "Tersoff and Stillinger-Weber terms have no batched embedded-atom frame energy (one-species "
-                                      "Stillinger-Weber: thermo.StillingerWeberEnergy; built-in pair forms: thermo.PotentialEnergy; "
-                                      "learned pair modules: thermo.TabulatedEnergy)" % type(model).__name__)
+                                      "Stillinger-Weber: thermo.StillingerWeberEnergy; Tersoff and TersoffMulti: "
+                                      "thermo.TersoffEnergy; built-in pair forms: thermo.PotentialEnergy; learned pair modules: "
+                                      "thermo.TabulatedEnergy)" % type(model).__name__)
         super().__init__(system)
         cs = _lib.make_cell(system.get_cell())
         if not cs.diag:
@@ -588,3 +591,109 @@ class EAMEnergy(Observable):
                                               self._cell_struct, m._consts).reshape(lead)
         theta = torch.cat([p.detach().reshape(-1) for p in (m.epsilon, m.a, m.c)]).to(device=x.device, dtype=torch.float32)
         return ops.EAMFramesFn.apply(x, m.epsilon, m.a, m.c, theta, self._cell_struct, m._consts).reshape(lead)
+
+
+class TersoffEnergy(Observable):
+    """Tersoff bond-order energy of every frame of a trajectory in one call: the energy side of trajectory reweighting
+    (`reweight.Reweighting`) for silicon, carbon, germanium and their alloys, whose trainable A, B and h are what a fit to an
+    angle distribution or an RDF carries.
+
+        U[f] = 1/2 sum_i sum_{j != i} fc_ab(r_ij) [ A_ab exp(-lam1_ab r_ij) - b_ij B_ab exp(-lam2_ab r_ij) ]
+
+    `model` is an `interface.Tersoff` (one species) or an `interface.TersoffMulti` (1 - 4 species); U[f] is the value
+    `model(q[f])` gives, with the model's own conventions: the strict minimum image on the diagonal cell, the support
+    0 < r < R_ab + D_ab of the directed pair (centre species, end species) on r = sqrtf(d2), b = 1 with zero derivatives where
+    zeta = 0, per-atom `types` of one replica (one replica is one frame).  q: [N, 3], [T, N, 3], [R, T, N, 3] or
+    replica-stacked [..., k N, 3] (a trailing k).
+
+    float32 device positions run ONE list-free launch (ops.TersoffFramesFn / ops.TersoffMultiFramesFn,
+    csrc/tersoff_frames.hip): every atom finds its neighbours in its frame and runs the bond pass over them; no list is
+    searched and nothing is read on the host.  The kernel reads (A, B, h) from the model's device mirror (`Tersoff._theta()`,
+    `TersoffMulti._tables()`), rewritten here at every call, so it follows the parameters however they were stepped.  When A,
+    B or h requires grad the same launch emits dU[f]/d(A, B, h), and the parameter part of the backward pass is their
+    fixed-order weighted sum: with detached frames (reweighting) the backward pass visits no bond at all.  A position
+    gradient, off that path, goes through the model's list kernels on the stacked frames behind a list searched at the
+    model's cutoff.  Host or float64 positions take the model's torch restatement `_torch_energy`, frame by frame.
+    Differentiable once.
+
+    An atom may hold at most `ops.tersoff_frames_row_cap()` = 32 neighbours inside R + D (the covalent networks hold 3 - 10);
+    a frame with a longer row comes out NaN rather than truncated.  The cutoff max (R + D) is absolute and may not exceed half
+    the shortest cell length (ValueError at construction).
+
+    Not covered: StillingerWeberMulti frame energies, the virial of the term, a Tersoff term stacked with pair terms in one
+    launch (add a `PotentialEnergy` of the pair terms: Reweighting takes any callable), triclinic cells, more than 1024 atoms
+    per frame, evaluation inside the fused trajectory launches."""
+
+    MAX_ATOMS = ops.TERSOFF_FRAMES_MAX_ATOMS
+
+    def __init__(self, system, model):
+        from . import _lib
+        from .interface import Tersoff, TersoffMulti
+        if not isinstance(model, (Tersoff, TersoffMulti)):
+            raise NotImplementedError("TersoffEnergy: the model must be an interface.Tersoff or an interface.TersoffMulti; got "
+                                      "%s.  Stacks, Stillinger-Weber and embedded-atom terms have no batched Tersoff frame "
+                                      "energy (one-species Stillinger-Weber: thermo.StillingerWeberEnergy; SuttonChen and EAM: "
+                                      "thermo.EAMEnergy; built-in pair forms: thermo.PotentialEnergy; learned pair modules: "
+                                      "thermo.TabulatedEnergy)" % type(model).__name__)
+        super().__init__(system)
+        cs = _lib.make_cell(system.get_cell())
+        if not cs.diag:
+            raise ValueError("TersoffEnergy: the cell must be diagonal (triclinic cells are not supported)")
+        if self.natoms > self.MAX_ATOMS:
+            raise ValueError("TersoffEnergy: at most %d atoms per frame, got %d" % (self.MAX_ATOMS, self.natoms))
+        if self.natoms != model._group:
+            raise ValueError("TersoffEnergy: the model was built for %d atoms per replica, the system holds %d"
+                             % (model._group, self.natoms))
+        half = 0.5 * min(cs.h[0], cs.h[4], cs.h[8])
+        if model.cutoff > half:
+            raise ValueError("TersoffEnergy: cutoff = %g exceeds half the shortest cell length (%g): the minimum image no longer "
+                             "holds every neighbour" % (model.cutoff, half))
+        self.model = model
+        self.multi = isinstance(model, TersoffMulti)
+        self._cell_struct = cs
+        self._types = None
+
+    def _frames(self, x, name):
+        n = x.shape[-2] if x.dim() >= 2 else 0
+        if n == 0 or x.shape[-1] != 3 or n % self.natoms:
+            raise ValueError("TersoffEnergy: %s must be [..., k * %d, 3], got %s" % (name, self.natoms, tuple(x.shape)))
+        k = n // self.natoms                             # replica-stacked state [..., k N, 3]: one value per replica
+        lead = tuple(x.shape[:-2]) + ((k,) if k > 1 else ())
+        return x.reshape(-1, self.natoms, 3), lead
+
+    def _torch_energy(self, x):
+        """The model's torch restatement, one frame at a time (each frame is one replica to it)."""
+        m = self.model
+        n_rep, m._n_rep = m._n_rep, 1
+        types = m.types if self.multi else None
+        if self.multi:
+            m.types = types[:self.natoms]                 # (one entry per atom of the stacked system: one replica's)
+        # (cast once: the parameter gradient is summed over the frames in the dtype of x and rounded to the parameters' once)
+        params = tuple(p.to(x) for p in (m.A, m.B, m.h))
+        try:
+            return torch.stack([m._torch_energy(xf, params).reshape(()) for xf in x])
+        finally:
+            m._n_rep = n_rep
+            if self.multi:
+                m.types = types
+
+    def _mirror(self, mirror, device):
+        """The model's device image of (A, B, h), rewritten now (an edit through `.data` moves no version counter, so the
+        mirror's own test would miss it); inside a HIP-graph capture it comes as it is."""
+        buf = mirror.get(fresh=True)
+        return buf if buf.device == device else buf.to(device)
+
+    def forward(self, q):
+        """U of every frame of q."""
+        x, lead = self._frames(q, "q")
+        if not (x.is_cuda and x.dtype == torch.float32):
+            return self._torch_energy(x).reshape(lead)
+        m = self.model
+        if self.multi:
+            if self._types is None or self._types.device != x.device:
+                self._types = m.types[:self.natoms].to(device=x.device, dtype=torch.int32).contiguous()
+            tables = self._mirror(m._table_mirror, x.device)
+            return ops.TersoffMultiFramesFn.apply(x, m.A, m.B, m.h, tables, self._types, m.n_species, self._cell_struct,
+                                                  m.cutoff).reshape(lead)
+        theta = self._mirror(m._theta_mirror, x.device)
+        return ops.TersoffFramesFn.apply(x, m.A, m.B, m.h, theta, self._cell_struct, m._consts).reshape(lead)

@@ -1539,7 +1539,8 @@ int mdg_energy_table_bwd(const float* pos, int n_frames, int n_atoms, const MdgC
  *   Fixed-order sums, no floating-point atomics: bitwise reproducible, and permuting the frames permutes the outputs bit for
  *   bit.  Needs no workspace.
  *   mdg_sw_frames_theta_bwd: g_theta[3] = sum_f gU[f] dU_dtheta[f, :] in a fixed order -- the whole parameter backward pass of
- *   K34 (no second walk over the frames).
+ *   K34 (no second walk over the frames).  It is mdg_frames_theta_bwd (below) with n_params = 3: the same kernel
+ *   (csrc/frames_reduce.hip), the same bits.
  */
 int mdg_sw_frames_row_cap(void);
 int mdg_sw_frames_fwd(const float* pos, int n_frames, int n_atoms, const MdgCell* cell /*host*/, const MdgSWConsts* consts /*host*/,
@@ -1579,7 +1580,7 @@ int mdg_sw_frames_theta_bwd(const float* gU, const float* dU_dtheta, int n_frame
  *   host copies of epsilon, a, c are not read); theta: DEVICE float[3] = (epsilon, a, c), required.  An atom without a neighbour
  *   has an embedding energy of exactly 0.
  *   dU_dtheta nullable [n_frames, 3] = dU[f]/d(epsilon, a, c) from the same pass (K24's pth formulas); the value part of U does
- *   not depend on whether it is asked for, bit for bit.  The parameter backward pass is mdg_sw_frames_theta_bwd (K34): the
+ *   not depend on whether it is asked for, bit for bit.  The parameter backward pass is mdg_frames_theta_bwd (below): the
  *   fixed-order weighted sum over the frames, no second walk.
  *   MDG_EINVAL: a null buffer, n_atoms > 1024, a non-diagonal cell, rc <= 0, exponents outside 1 <= m < n <= 16, shift not 0 / 1.
  */
@@ -1614,7 +1615,8 @@ int mdg_eam_frames_fwd(const float* pos, int n_frames, int n_atoms, const MdgCel
  *   Fixed-order sums, no floating-point atomics: bitwise reproducible, and permuting the frames permutes the outputs bit for
  *   bit.
  *   mdg_frames_theta_bwd: g_theta[n_params] = sum_f gU[f] dU_dtheta[f, :] in double and in a fixed order, a workgroup per
- *   parameter -- the whole parameter backward pass of K38 (no second walk over the frames).
+ *   parameter -- the whole parameter backward pass of K34, K37 and K38 (no second walk over the frames;
+ *   csrc/frames_reduce.hip).
  *   MDG_EINVAL: a null buffer, n_atoms > 1024, a non-diagonal cell, n_species outside [1, 4], and for the one-species entry the
  *   conditions of mdg_tersoff_eval on the constants (lam1, lam2 > 0; D > 0; R > D; m = 1 or 3; n > 0; beta >= 0; d != 0).
  */

@@ -8,9 +8,10 @@
 // (csrc/frame_pairs.hpp), r = sqrtf(d2) with the un-contracted d2, 0 < r < rc.  Nothing is searched and no list exists; the
 // value is the one the model gives for the frame.
 //
-// Shape: the frame's positions are staged in LDS (a wave per frame up to 128 atoms, four frames per workgroup; a workgroup per
-// frame up to 1024 atoms); every thread owns the atoms t, t + TPF, ... and walks the whole frame once for each: when the walk
-// ends it holds both 1/2 sum phi and rho_i and applies F on the spot.  No rows, no row cap, no second pass.
+// Shape: the scaffold of csrc/frame_atoms.hpp.  Every thread walks the whole frame once for each of its atoms: when the walk
+// ends it holds both 1/2 sum phi and rho_i and applies F on the spot.  No rows, no row cap, no second pass.  K37 walks with
+// walk_all; the two K36 kernels write the same loop out (ETF_WALK): through the callable their table offsets compile to other
+// instructions, measured 1 - 2 % slower on an MI355X at 4 096 frames, with the same bits.
 //
 // K36 (tabulated): one bracket (g, t) per pair serves the phi_ab and the f_b lookup (csrc/eam_table_core.hpp).  The r-tables
 // (pair and density) are read from a workgroup copy in LDS when they hold at most EF_LDS_TABLE_FLOATS floats and four frames
@@ -31,7 +32,7 @@
 // does not depend on whether rho or dU_dtheta is asked for (no fused multiply-add is formed in this file).
 #include "eam_table_core.hpp"
 #include "eam_core.hpp"
-#include "frame_pairs.hpp"
+#include "frame_atoms.hpp"
 
 namespace {
 
@@ -40,6 +41,14 @@ using namespace frame_pairs;
 constexpr int EF_LDS_TABLE_FLOATS = 8192;     // forward: r-tables of at most 32 KiB get a workgroup copy in LDS
 constexpr int EF_LDS_WORDS = 6144;            // node gradient: a table set of at most 48 KiB of int64 words is summed in LDS first
 enum { EF_GU = 0, EF_FP, EF_EM, EF_NB };      // max |gU|, |F'(rho)|, |basis(rho)| as float bits in the first words of fx
+
+// walk_all of csrc/frame_atoms.hpp written out for K36: atom i (at xi, yi, zi) of the frame `fr` against j = 0 .. N - 1 in
+// index order, the body run with r = sqrtf(d2) for the atoms inside K27's support 0 < r < rc
+#define ETF_WALK(fr, A, i, j, r)                                                                           \
+    for (int j = 0; j < (fr).N; ++j)                                                                       \
+        if (float dx_ = (fr).sx[j] - xi, dy_ = (fr).sy[j] - yi, dz_ = (fr).sz[j] - zi, d2_;                \
+            j != i && pair_in((A).cell, __int_as_float(0x7f800000), dx_, dy_, dz_, d2_))                   \
+            if (const float r = sqrtf(d2_); r > 0.f && r < (A).rc)
 
 struct EtfArgs {
     const float* pos; const int32_t* types; const float* tab;
@@ -61,36 +70,24 @@ __device__ __forceinline__ void etf_stage_types(uint8_t* sty, const EtfArgs& A) 
 // ---------------------------------------------------------------------------------- K36 forward
 template <int TPF, bool LDS_TAB>
 __global__ __launch_bounds__(FP_BLOCK) void etf_fwd_kernel(const EtfArgs A) {
-    constexpr int CAP = TPF == MDG_WAVE ? FP_WAVE_ATOMS : FP_GROUP_ATOMS, FPB = FP_BLOCK / TPF;
-    static_assert(TPF == MDG_WAVE || TPF == FP_BLOCK, "a wave or the whole workgroup per frame");
-    __shared__ float sp[FPB * 3 * CAP];
-    __shared__ uint8_t sty[CAP];
+    using C = FrameCtx<TPF>;
+    __shared__ float sp[C::FPB * 3 * C::CAP];
+    __shared__ uint8_t sty[C::CAP];
     __shared__ float red[17];
     extern __shared__ float etf_tab[];                        // LDS_TAB: [r_floats], the pair and density tables
-    const int t = threadIdx.x % TPF, g = threadIdx.x / TPF, N = A.N;
-    const long long f = (long long)blockIdx.x * FPB + g;
-    const bool live = f < A.F;
-    float* sf = sp + g * 3 * CAP;
     etf_stage_types(sty, A);
     if (LDS_TAB) {
         for (int e = threadIdx.x; e < A.r_floats; e += FP_BLOCK) etf_tab[e] = A.tab[e];
     }
-    if (live) stage_frame<TPF, CAP>(sf, A.pos + (size_t)f * N * 3, N, t);
-    __syncthreads();
+    const C fr = open_frame<TPF>(sp, A.pos, A.F, A.N);
     const float* rt = LDS_TAB ? etf_tab : A.tab;
-    const float *sx = sf, *sy = sf + CAP, *sz = sf + 2 * CAP;
-    const float inf = __int_as_float(0x7f800000);
     float en = 0.f;
-    if (live) {
-        for (int i = t; i < N; i += TPF) {
-            const float xi = sx[i], yi = sy[i], zi = sz[i];
+    if (fr.live) {
+        for (int i = fr.t; i < fr.N; i += TPF) {
+            const float xi = fr.sx[i], yi = fr.sy[i], zi = fr.sz[i];
             const int a = sty[i];
             float SP = 0.f, R = 0.f;
-            for (int j = 0; j < N; ++j) {
-                float dx = sx[j] - xi, dy = sy[j] - yi, dz = sz[j] - zi, d2;
-                if (j == i || !pair_in(A.cell, inf, dx, dy, dz, d2)) continue;
-                const float r = sqrtf(d2);
-                if (!(r > 0.f && r < A.rc)) continue;         // K27's support test
+            ETF_WALK(fr, A, i, j, r) {
                 const int b = sty[j];
                 EtBasis<float> B;
                 et_basis<float>(r, A.rmin, A.inv_hr, A.nr, B);
@@ -101,11 +98,11 @@ __global__ __launch_bounds__(FP_BLOCK) void etf_fwd_kernel(const EtfArgs A) {
             et_basis<float>(R, A.rhomin, A.inv_hrho, A.nrho, B);
             const float Fe = et_dot<float>(B.b, A.tab + et_embed_off(A.S, a, A.nr, A.nrho) + 2 * B.g);
             en = en + (0.5f * SP + Fe);                       // u_i = 1/2 sum_j phi + F_a(rho_i)
-            if (A.rho) A.rho[(size_t)f * N + i] = R;
+            if (A.rho) A.rho[(size_t)fr.f * fr.N + i] = R;
         }
     }
     en = TPF == MDG_WAVE ? wave_sum(en) : block_sum(en, red);
-    if (live && t == 0) A.U[f] = en;
+    if (fr.live && fr.t == 0) A.U[fr.f] = en;
 }
 
 // ---------------------------------------------------------------------------------- K36b node gradient
@@ -161,47 +158,35 @@ __device__ __forceinline__ void etf_scales(const unsigned long long* fx, float b
 
 template <int TPF>
 __global__ __launch_bounds__(FP_BLOCK) void etf_nodes_kernel(const EtfArgs A) {
-    constexpr int CAP = TPF == MDG_WAVE ? FP_WAVE_ATOMS : FP_GROUP_ATOMS, FPB = FP_BLOCK / TPF;
-    static_assert(TPF == MDG_WAVE || TPF == FP_BLOCK, "a wave or the whole workgroup per frame");
-    __shared__ float sp[FPB * 3 * CAP];
-    __shared__ uint8_t sty[CAP];
+    using C = FrameCtx<TPF>;
+    __shared__ float sp[C::FPB * 3 * C::CAP];
+    __shared__ uint8_t sty[C::CAP];
     extern __shared__ unsigned long long etf_acc[];           // [lds_words]: this workgroup's share of the words
-    const int t = threadIdx.x % TPF, g = threadIdx.x / TPF, N = A.N;
-    const long long f = (long long)blockIdx.x * FPB + g;
-    const bool live = f < A.F;
-    float* sf = sp + g * 3 * CAP;
     unsigned long long* fxw = A.fx + ET_BOUNDS;
     const bool lds = A.lds_words > 0;                         // (grid-uniform)
     etf_stage_types(sty, A);
     if (lds) {
         for (int k = threadIdx.x; k < A.lds_words; k += FP_BLOCK) etf_acc[k] = 0ull;
     }
-    if (live) stage_frame<TPF, CAP>(sf, A.pos + (size_t)f * N * 3, N, t);
-    __syncthreads();
+    const C fr = open_frame<TPF>(sp, A.pos, A.F, A.N);
     auto add = [&](size_t word, float v) {
         if (v == 0.f) return;
         if (lds) atomicAdd(etf_acc + word, fx64(v)); else atomicAdd(fxw + word, fx64(v));
     };
-    const float *sx = sf, *sy = sf + CAP, *sz = sf + 2 * CAP;
-    const float inf = __int_as_float(0x7f800000);
-    const float gw = live ? A.gU[f] : 0.f;
-    if (live && gw != 0.f) {                                  // (a frame of weight zero adds nothing)
+    const float gw = fr.live ? A.gU[fr.f] : 0.f;
+    if (fr.live && gw != 0.f) {                                  // (a frame of weight zero adds nothing)
         float sc[3];
         etf_scales(A.fx, A.bv, A.lim_edge, A.lim_atom, sc);
-        for (int i = t; i < N; i += TPF) {
-            const float xi = sx[i], yi = sy[i], zi = sz[i];
+        for (int i = fr.t; i < fr.N; i += TPF) {
+            const float xi = fr.sx[i], yi = fr.sy[i], zi = fr.sz[i];
             const int a = sty[i];
             EtBasis<float> E;
             size_t eoff;
-            const float FpI = etf_embed(A, A.rho_in[(size_t)f * N + i], a, E, eoff);
+            const float FpI = etf_embed(A, A.rho_in[(size_t)fr.f * fr.N + i], a, E, eoff);
 #pragma unroll
             for (int k = 0; k < 4; ++k) add(eoff + k, (gw * E.b[k]) * sc[2]);
             const float cp = 0.5f * gw, cd = gw * FpI;
-            for (int j = 0; j < N; ++j) {
-                float dx = sx[j] - xi, dy = sy[j] - yi, dz = sz[j] - zi, d2;
-                if (j == i || !pair_in(A.cell, inf, dx, dy, dz, d2)) continue;
-                const float r = sqrtf(d2);
-                if (!(r > 0.f && r < A.rc)) continue;
+            ETF_WALK(fr, A, i, j, r) {
                 const int b = sty[j];
                 EtBasis<float> B;
                 et_basis<float>(r, A.rmin, A.inv_hr, A.nr, B);
@@ -247,37 +232,26 @@ struct EsfArgs {
 
 template <int TPF, bool DTH>
 __global__ __launch_bounds__(FP_BLOCK) void eam_frames_kernel(const EsfArgs A) {
-    constexpr int CAP = TPF == MDG_WAVE ? FP_WAVE_ATOMS : FP_GROUP_ATOMS, FPB = FP_BLOCK / TPF;
-    static_assert(TPF == MDG_WAVE || TPF == FP_BLOCK, "a wave or the whole workgroup per frame");
+    using C = FrameCtx<TPF>;
     constexpr int NV = 4;                                     // U, dU/d(eps, a, c)
-    __shared__ float sp[FPB * 3 * CAP];
+    __shared__ float sp[C::FPB * 3 * C::CAP];
     __shared__ float red[(FP_BLOCK / MDG_WAVE) * NV];
-    const int t = threadIdx.x % TPF, g = threadIdx.x / TPF, N = A.N;
-    const long long f = (long long)blockIdx.x * FPB + g;
-    const bool live = f < A.F;
-    float* sf = sp + g * 3 * CAP;
-    if (live) stage_frame<TPF, CAP>(sf, A.pos + (size_t)f * N * 3, N, t);
-    __syncthreads();
+    const C fr = open_frame<TPF>(sp, A.pos, A.F, A.N);
     const EamK K = eam_constants(A.theta[0], A.theta[1], A.theta[2], A.rc, A.n, A.m, A.shifted);
-    const float *sx = sf, *sy = sf + CAP, *sz = sf + 2 * CAP;
-    const float inf = __int_as_float(0x7f800000);
     float v[NV] = {0.f, 0.f, 0.f, 0.f};
-    if (live) {
-        for (int i = t; i < N; i += TPF) {
-            const float xi = sx[i], yi = sy[i], zi = sz[i];
+    if (fr.live) {
+        for (int i = fr.t; i < fr.N; i += TPF) {
             float SP = 0.f, R = 0.f;
-            for (int j = 0; j < N; ++j) {
-                float dx = sx[j] - xi, dy = sy[j] - yi, dz = sz[j] - zi, d2;
-                if (j == i || !pair_in(A.cell, inf, dx, dy, dz, d2)) continue;
+            walk_all<C::CAP>(A.cell, fr.sf, fr.N, i, [&](int, float dx, float dy, float dz, float) {
                 EamEdge<float> e;
-                if (!eam_edge<float>(K, dx, dy, dz, 0.f, 0.f, 0.f, e)) continue;      // K24's support test
+                if (!eam_edge<float>(K, dx, dy, dz, 0.f, 0.f, 0.f, e)) return;        // K24's support test
                 const float sr = K.a * e.ir;
                 float Sn, dSn, Sm, dSm;
                 eam_shape<float>(e, sr, K.n, K.fn, K.qn, K.ln, K.rc, Sn, dSn);
                 eam_shape<float>(e, sr, K.m, K.fm, K.qm, K.lm, K.rc, Sm, dSm);
                 SP = SP + Sn;
                 R = R + Sm;
-            }
+            });
             // u_i = eps (1/2 sum_j S_n - c sqrt(rho_i)) and its parameter derivatives (eam_force_kernel's pe, pa, pc);
             // rho_i <= 0 (no neighbour): embedding energy and F' exactly 0
             const bool dense = R > 0.f;
@@ -293,17 +267,11 @@ __global__ __launch_bounds__(FP_BLOCK) void eam_frames_kernel(const EsfArgs A) {
             }
         }
     }
-    if constexpr (TPF == MDG_WAVE) {
-#pragma unroll
-        for (int k = 0; k < NV; ++k) v[k] = wave_sum(v[k]);
-    } else {
-        block_sum_n<NV>(v, red);
-    }
-    if (live && t == 0) {
-        A.U[f] = v[0];
+    if (frame_sums(fr, v, red)) {
+        A.U[fr.f] = v[0];
         if (DTH) {
 #pragma unroll
-            for (int k = 0; k < 3; ++k) A.dU[3 * f + k] = v[1 + k];
+            for (int k = 0; k < 3; ++k) A.dU[3 * fr.f + k] = v[1 + k];
         }
     }
 }
@@ -350,16 +318,10 @@ extern "C" int mdg_eam_table_frames_fwd(const float* pos, int n_frames, int n_at
     // by size: the copy pays where four frames share it (measured: docs/KERNELS.md K36); a workgroup per frame reads global memory
     const bool lds = table_mode == 1 || (table_mode == -1 && a.r_floats <= EF_LDS_TABLE_FLOATS && n_atoms <= FP_WAVE_ATOMS);
     const size_t dyn = lds ? (size_t)a.r_floats * sizeof(float) : 0;
-    hipStream_t st = (hipStream_t)stream;
-    if (n_atoms <= FP_WAVE_ATOMS) {
-        constexpr int FPB = FP_BLOCK / MDG_WAVE;
-        const dim3 grid((n_frames + FPB - 1) / FPB);
-        if (lds) hipLaunchKernelGGL((etf_fwd_kernel<MDG_WAVE, true>), grid, dim3(FP_BLOCK), dyn, st, a);
-        else hipLaunchKernelGGL((etf_fwd_kernel<MDG_WAVE, false>), grid, dim3(FP_BLOCK), 0, st, a);
-    } else {
-        if (lds) hipLaunchKernelGGL((etf_fwd_kernel<FP_BLOCK, true>), dim3(n_frames), dim3(FP_BLOCK), dyn, st, a);
-        else hipLaunchKernelGGL((etf_fwd_kernel<FP_BLOCK, false>), dim3(n_frames), dim3(FP_BLOCK), 0, st, a);
-    }
+    launch_frames(n_frames, n_atoms, lds, [&](auto tpf, auto tab, dim3 grid) {
+        hipLaunchKernelGGL((etf_fwd_kernel<decltype(tpf)::value, decltype(tab)::value>), grid, dim3(FP_BLOCK), dyn,
+                           (hipStream_t)stream, a);
+    });
     MDG_CHECK_LAUNCH("etf_fwd_kernel");
     return MDG_OK;
 }
@@ -386,12 +348,9 @@ extern "C" int mdg_eam_table_frames_nodes_bwd(const float* pos, int n_frames, in
     const long long total = (long long)n_frames * n_atoms;
     hipLaunchKernelGGL(etf_bounds_kernel, dim3((unsigned)((total + FP_BLOCK - 1) / FP_BLOCK)), dim3(FP_BLOCK), 0, st, a);
     const size_t dyn = (size_t)a.lds_words * sizeof(unsigned long long);
-    if (n_atoms <= FP_WAVE_ATOMS) {
-        constexpr int FPB = FP_BLOCK / MDG_WAVE;
-        hipLaunchKernelGGL((etf_nodes_kernel<MDG_WAVE>), dim3((n_frames + FPB - 1) / FPB), dim3(FP_BLOCK), dyn, st, a);
-    } else {
-        hipLaunchKernelGGL((etf_nodes_kernel<FP_BLOCK>), dim3(n_frames), dim3(FP_BLOCK), dyn, st, a);
-    }
+    launch_frames(n_frames, n_atoms, [&](auto tpf, dim3 grid) {
+        hipLaunchKernelGGL((etf_nodes_kernel<decltype(tpf)::value>), grid, dim3(FP_BLOCK), dyn, st, a);
+    });
     hipLaunchKernelGGL(etf_finish_kernel, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, st, a.fx, n_words, a.bv,
                        a.lim_edge, a.lim_atom, a.S, a.nr, (int)k->pin_cutoff, g_tables);
     MDG_CHECK_LAUNCH("etf_nodes_kernel");
@@ -408,16 +367,10 @@ extern "C" int mdg_eam_frames_fwd(const float* pos, int n_frames, int n_atoms, c
     MDG_CHECK_ARG(k->m >= 1 && k->m < k->n && k->n <= 16, "eam_frames_fwd: exponents need 1 <= m < n <= 16");
     MDG_CHECK_ARG(k->shift == 0 || k->shift == 1, "eam_frames_fwd: shift must be 0 (as published) or 1 (shifted force)");
     EsfArgs A{pos, theta, U, dU_dtheta, n_frames, n_atoms, *cell, (float)k->rc, (int)k->n, (int)k->m, (int)k->shift};
-    hipStream_t st = (hipStream_t)stream;
-    if (n_atoms <= FP_WAVE_ATOMS) {
-        constexpr int FPB = FP_BLOCK / MDG_WAVE;
-        const dim3 grid((n_frames + FPB - 1) / FPB);
-        if (dU_dtheta) hipLaunchKernelGGL((eam_frames_kernel<MDG_WAVE, true>), grid, dim3(FP_BLOCK), 0, st, A);
-        else hipLaunchKernelGGL((eam_frames_kernel<MDG_WAVE, false>), grid, dim3(FP_BLOCK), 0, st, A);
-    } else {
-        if (dU_dtheta) hipLaunchKernelGGL((eam_frames_kernel<FP_BLOCK, true>), dim3(n_frames), dim3(FP_BLOCK), 0, st, A);
-        else hipLaunchKernelGGL((eam_frames_kernel<FP_BLOCK, false>), dim3(n_frames), dim3(FP_BLOCK), 0, st, A);
-    }
+    launch_frames(n_frames, n_atoms, dU_dtheta != nullptr, [&](auto tpf, auto dth, dim3 grid) {
+        hipLaunchKernelGGL((eam_frames_kernel<decltype(tpf)::value, decltype(dth)::value>), grid, dim3(FP_BLOCK), 0,
+                           (hipStream_t)stream, A);
+    });
     MDG_CHECK_LAUNCH("eam_frames_kernel");
     return MDG_OK;
 }

@@ -1,9 +1,13 @@
 // List-free all-pairs sweeps over every frame of a trajectory, parameterised by what a visit accumulates: the scaffolding of
-// the per-frame pair observables.  csrc/virial.hip (K15) and csrc/energy.hip (K31) are a visit policy on its kernels.
-// csrc/rdf_frames.hip (K32), whose visit scatters into an integer histogram, has kernels of its own on the pair walk
-// (stage_frame, once_partners, walk_row) and the frame checks; csrc/energy_table.hip (K33) takes the pair test, the tile
-// staging, the second-stage sums and the frame checks, and writes its sweeps out; csrc/sw_frames.hip (K34), whose atoms keep
-// the neighbours they find for the triplets, takes stage_frame, pair_in and the frame checks.
+// the per-frame pair observables.  Who takes what:
+//   csrc/virial.hip (K15), csrc/energy.hip (K31)   a visit policy on the kernels of this file
+//   csrc/rdf_frames.hip (K32)                      kernels of its own (its visit scatters into an integer histogram) on the
+//                                                  pair walk (stage_frame, once_partners, walk_row) and the frame checks
+//   csrc/energy_table.hip (K33)                    the pair test, the tile staging, the second-stage sums and the frame
+//                                                  checks; it writes its sweeps out
+//   csrc/frame_atoms.hpp                           stage_frame and pair_in, for the many-body frame energies (K34, K36 - K38:
+//                                                  csrc/sw_frames.hip, eam_frames.hip, tersoff_frames.hip), whose atoms walk
+//                                                  the whole frame in index order; those take the frame checks from here
 //
 // Pair set of a term = the one PairPotentials sums the energy over (torchmd/topology.py:30-73, interface.py:298-300):
 // pairs i < j, D = x_j - x_i re-imaged with the reference's strict +-1/2 minimum image on the diagonal cell,

@@ -9,22 +9,18 @@
 // searched on the host and no list exists: a step of sigma costs nothing, and the value is the one StillingerWeber gives
 // for the frame.
 //
-// Shape: the frame's positions are staged in LDS (a wave per frame up to 128 atoms, four frames per workgroup; a workgroup
-// per frame up to 1024 atoms); every thread owns the atoms t, t + TPF, ... and, for each of them,
-//   1. walks the frame once and writes the indices of the atoms inside the support into ITS OWN compact row in LDS (uint16,
-//      slot-major: lane-consecutive, no bank conflict) -- every lane does the same N - 1 tests;
+// Shape: the scaffold of csrc/frame_atoms.hpp.  Every thread, for each of its atoms,
+//   1. builds the row of the atoms inside the support (build_row) -- every lane does the same N - 1 tests;
 //   2. walks that row: the pair (i, j) for every slot, the triplet (j, i, k) for every later slot, edges by sw_edge().
-// The row belongs to one thread from the first step to the second, so no barrier separates them.
 // Row cap: SWF_ROW_CAP = 64 entries (32 KB of LDS for the 256 rows of a workgroup; silicon and mW water hold 4 - 30
-// neighbours inside a sigma).  A row is never truncated silently: a frame in which any atom has more neighbours comes out NaN
-// in U and dU_dtheta, alone.
+// neighbours inside a sigma); a frame in which any atom has more neighbours comes out NaN in U and dU_dtheta, alone.
 //
 // Every sum runs in a fixed order: per atom in slot order, per thread in atom order, then the shuffle / LDS trees of
 // common.hpp.  No floating-point atomics; a frame's arithmetic does not depend on where it stands in the batch, so permuting
 // the frames permutes the outputs bit for bit, and the value part does not depend on whether dU_dtheta is asked for (no
 // fused multiply-add is formed in this file).
 #include "sw_core.hpp"
-#include "frame_pairs.hpp"
+#include "frame_atoms.hpp"
 
 namespace {
 
@@ -42,41 +38,28 @@ struct SwfArgs {
 
 template <int TPF, bool DTH>
 __global__ __launch_bounds__(FP_BLOCK) void sw_frames_kernel(const SwfArgs A) {
-    constexpr int CAP = TPF == MDG_WAVE ? FP_WAVE_ATOMS : FP_GROUP_ATOMS, FPB = FP_BLOCK / TPF;
-    static_assert(TPF == MDG_WAVE || TPF == FP_BLOCK, "a wave or the whole workgroup per frame");
+    using C = FrameCtx<TPF>;
     constexpr int NV = 5;                                     // U, dU/d(eps, sigma, lam), overflowing rows
-    __shared__ float sp[FPB * 3 * CAP];
+    __shared__ float sp[C::FPB * 3 * C::CAP];
     __shared__ uint16_t rows[SWF_ROW_CAP * FP_BLOCK];
     __shared__ float red[(FP_BLOCK / MDG_WAVE) * NV];
-    const int t = threadIdx.x % TPF, g = threadIdx.x / TPF, N = A.N;
-    const long long f = (long long)blockIdx.x * FPB + g;
-    const bool live = f < A.F;
-    float* sf = sp + g * 3 * CAP;
-    if (live) stage_frame<TPF, CAP>(sf, A.pos + (size_t)f * N * 3, N, t);
-    __syncthreads();
+    const C fr = open_frame<TPF>(sp, A.pos, A.F, A.N);
     const SwK K = sw_constants(A.theta[0], A.theta[1], A.theta[2], A.a, A.gamma, A.cos0, A.A, A.B, A.p, A.q);
-    const float *sx = sf, *sy = sf + CAP, *sz = sf + 2 * CAP;
-    uint16_t* row = rows + threadIdx.x;                       // slot s of this thread's row: row[s * FP_BLOCK]
-    const float inf = __int_as_float(0x7f800000);
+    const float *sx = fr.sx, *sy = fr.sy, *sz = fr.sz;
+    uint16_t* row = rows + threadIdx.x;
     float v[NV] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    if (live) {
-        for (int i = t; i < N; i += TPF) {
+    if (fr.live) {
+        for (int i = fr.t; i < fr.N; i += TPF) {
             const float xi = sx[i], yi = sy[i], zi = sz[i];
-            // ---- 1. the row of atom i
-            int n = 0, over = 0;
-            for (int j = 0; j < N; ++j) {
-                float dx = sx[j] - xi, dy = sy[j] - yi, dz = sz[j] - zi, d2;
-                if (j == i || !pair_in(A.cell, inf, dx, dy, dz, d2)) continue;
-                const float rv = sqrtf(d2);
-                if (!(rv > 0.f && rv < K.rc)) continue;       // sw_edge's support test
-                if (n < SWF_ROW_CAP) row[(n++) * FP_BLOCK] = (uint16_t)j;
-                else over = 1;
-            }
+            // ---- 1. the row of atom i (sw_edge's support test)
+            int over;
+            const int n = build_row<SWF_ROW_CAP, C::CAP>(row, A.cell, fr.sf, fr.N, i, over,
+                                                         [&](int, float rv) { return rv < K.rc; });
             if (over) { v[4] += 1.f; continue; }
             // ---- 2. pairs and triplets of the row
             float S2 = 0.f, S2s = 0.f, S3 = 0.f, S3s = 0.f;
             for (int s = 0; s < n; ++s) {
-                const int j = row[s * FP_BLOCK];
+                const int j = row_at(row, s);
                 float dx = sx[j] - xi, dy = sy[j] - yi, dz = sz[j] - zi;
                 min_image<true>(A.cell, dx, dy, dz);
                 SwEdge<float> ej;
@@ -86,7 +69,7 @@ __global__ __launch_bounds__(FP_BLOCK) void sw_frames_kernel(const SwfArgs A) {
                 if (DTH) S2s = S2s + sw_pair_dsigma<float>(K, ej, pr);
                 const float q1 = ej.inv * ej.inv;
                 for (int u = s + 1; u < n; ++u) {
-                    const int k = row[u * FP_BLOCK];
+                    const int k = row_at(row, u);
                     float bx = sx[k] - xi, by = sy[k] - yi, bz = sz[k] - zi;
                     min_image<true>(A.cell, bx, by, bz);
                     SwEdge<float> ek;
@@ -109,38 +92,14 @@ __global__ __launch_bounds__(FP_BLOCK) void sw_frames_kernel(const SwfArgs A) {
             }
         }
     }
-    if constexpr (TPF == MDG_WAVE) {
-#pragma unroll
-        for (int k = 0; k < NV; ++k) v[k] = wave_sum(v[k]);
-    } else {
-        block_sum_n<NV>(v, red);
-    }
-    if (live && t == 0) {
-        const float nan = __int_as_float(0x7fc00000);
+    if (frame_sums(fr, v, red)) {
         const bool bad = v[4] > 0.f;
-        A.U[f] = bad ? nan : v[0];
+        A.U[fr.f] = nan_if(bad, v[0]);
         if (DTH) {
 #pragma unroll
-            for (int k = 0; k < 3; ++k) A.dU[3 * f + k] = bad ? nan : v[1 + k];
+            for (int k = 0; k < 3; ++k) A.dU[3 * fr.f + k] = nan_if(bad, v[1 + k]);
         }
     }
-}
-
-// g_theta[k] = sum_f gU[f] dU[f, k]: a workgroup per parameter, fixed order.  The products of a reweighting gradient cancel
-// (gU sums to zero over the frames), so the sum runs in double: 3 F multiply-adds in all.
-__global__ __launch_bounds__(FP_BLOCK) void sw_frames_reduce_kernel(const float* __restrict__ gU, const float* __restrict__ dU,
-                                                                    long long F, float* __restrict__ g_theta) {
-    __shared__ double red[FP_BLOCK];
-    const int k = blockIdx.x;
-    double s = 0.0;
-    for (long long f = threadIdx.x; f < F; f += FP_BLOCK) s = s + (double)gU[f] * (double)dU[3 * f + k];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = FP_BLOCK / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) g_theta[k] = (float)red[0];
 }
 
 }  // namespace
@@ -157,25 +116,10 @@ extern "C" int mdg_sw_frames_fwd(const float* pos, int n_frames, int n_atoms, co
     MDG_CHECK_ARG(k->q >= 0 && k->q < k->p && k->p <= 12, "sw_frames_fwd: exponents need 0 <= q < p <= 12");
     SwfArgs A{pos, theta, U, dU_dtheta, n_frames, n_atoms, *cell,
               (float)k->a, (float)k->gamma, (float)k->cos0, (float)k->A, (float)k->B, (int)k->p, (int)k->q};
-    hipStream_t st = (hipStream_t)stream;
-    if (n_atoms <= FP_WAVE_ATOMS) {
-        constexpr int FPB = FP_BLOCK / MDG_WAVE;
-        const dim3 grid((n_frames + FPB - 1) / FPB);
-        if (dU_dtheta) hipLaunchKernelGGL((sw_frames_kernel<MDG_WAVE, true>), grid, dim3(FP_BLOCK), 0, st, A);
-        else hipLaunchKernelGGL((sw_frames_kernel<MDG_WAVE, false>), grid, dim3(FP_BLOCK), 0, st, A);
-    } else {
-        if (dU_dtheta) hipLaunchKernelGGL((sw_frames_kernel<FP_BLOCK, true>), dim3(n_frames), dim3(FP_BLOCK), 0, st, A);
-        else hipLaunchKernelGGL((sw_frames_kernel<FP_BLOCK, false>), dim3(n_frames), dim3(FP_BLOCK), 0, st, A);
-    }
+    launch_frames(n_frames, n_atoms, dU_dtheta != nullptr, [&](auto tpf, auto dth, dim3 grid) {
+        hipLaunchKernelGGL((sw_frames_kernel<decltype(tpf)::value, decltype(dth)::value>), grid, dim3(FP_BLOCK), 0,
+                           (hipStream_t)stream, A);
+    });
     MDG_CHECK_LAUNCH("sw_frames_kernel");
-    return MDG_OK;
-}
-
-extern "C" int mdg_sw_frames_theta_bwd(const float* gU, const float* dU_dtheta, int n_frames, float* g_theta, void* stream) {
-    MDG_CHECK_ARG(gU && dU_dtheta && g_theta, "sw_frames_theta_bwd: null argument");
-    MDG_CHECK_ARG(n_frames > 0, "sw_frames_theta_bwd: empty trajectory");
-    hipLaunchKernelGGL(sw_frames_reduce_kernel, dim3(3), dim3(FP_BLOCK), 0, (hipStream_t)stream, gU, dU_dtheta,
-                       (long long)n_frames, g_theta);
-    MDG_CHECK_LAUNCH("sw_frames_reduce_kernel");
     return MDG_OK;
 }

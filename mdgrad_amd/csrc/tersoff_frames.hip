@@ -17,25 +17,21 @@
 //                        atom, clamped into the table), both staged into LDS once per workgroup; P = 2 S^2 + S in the order
 //                        (A.flat, B.flat, h) of K26's pth
 //
-// Shape (that of csrc/sw_frames.hip, K34): the frame's positions are staged in LDS (a wave per frame up to 128 atoms, four
-// frames per workgroup; a workgroup per frame up to 1024 atoms); every thread owns the atoms t, t + TPF, ... and, for each,
-//   1. walks the frame once and writes the indices of the atoms inside the support of (t_i, t_j) into ITS OWN compact row in
-//      LDS (uint16, slot-major: lane-consecutive, no bank conflict);
+// Shape: the scaffold of csrc/frame_atoms.hpp.  Every thread, for each of its atoms,
+//   1. builds the row of the atoms inside the support of (t_i, t_j) (build_row);
 //   2. for every slot s forms zeta_is by a loop over the row, then b and b', the bond's half energy and
 //      d u_i / d(A[a, .], B[a, .], h[a]);
 //   3. adds them into per-thread sums (constant indices and predicated adds: nothing is indexed by a run-time species).
-// The row belongs to one thread from the first step to the second, so no barrier separates them.  The zeta loop rebuilds the
-// edge of k for every j, as the list kernel does.
+// The zeta loop rebuilds the edge of k for every j, as the list kernel does.
 // Row cap: TF_ROW_CAP = 32 entries (16 KB of LDS for the 256 rows of a workgroup; silicon, carbon, germanium and their alloys
-// hold 3 - 10 neighbours inside R + D).  A row is never truncated: a frame in which any atom has more neighbours comes out
-// NaN in U and dU_dtheta, alone.
+// hold 3 - 10 neighbours inside R + D); a frame in which any atom has more neighbours comes out NaN in U and dU_dtheta, alone.
 //
 // Every sum runs in a fixed order: per atom in slot order, per thread in atom order, then the shuffle / LDS trees of
 // common.hpp.  No floating-point atomics; a frame's arithmetic does not depend on where it stands in the batch, and the value
 // part does not depend on whether dU_dtheta is asked for (no fused multiply-add is formed in this file).
 #pragma clang fp contract(off)
 #include "tersoff_core.hpp"
-#include "frame_pairs.hpp"
+#include "frame_atoms.hpp"
 
 namespace {
 
@@ -120,43 +116,32 @@ __device__ __forceinline__ bool tf_edge(const MdgCell& cell, const TersEntry& pp
 
 template <class P, int TPF, bool DTH>
 __global__ __launch_bounds__(FP_BLOCK) void tersoff_frames_kernel(const TfArgs A, const typename P::Args V) {
-    constexpr int CAP = TPF == MDG_WAVE ? FP_WAVE_ATOMS : FP_GROUP_ATOMS, FPB = FP_BLOCK / TPF, SMAX = P::SMAX;
-    static_assert(TPF == MDG_WAVE || TPF == FP_BLOCK, "a wave or the whole workgroup per frame");
+    using C = FrameCtx<TPF>;
+    constexpr int SMAX = P::SMAX;
     // per-thread sums: U, overflowing rows, then dU/d(A[a, b], B[a, b], h[a]) at the register stride SMAX
     constexpr int NTH = DTH ? 2 * SMAX * SMAX + SMAX : 0, NV = 2 + NTH;
     constexpr int OA = 2, OB = 2 + SMAX * SMAX, OH = 2 + 2 * SMAX * SMAX;
-    __shared__ float sp[FPB * 3 * CAP];
+    __shared__ float sp[C::FPB * 3 * C::CAP];
     __shared__ uint16_t rows[TF_ROW_CAP * FP_BLOCK];
     __shared__ float red[(FP_BLOCK / MDG_WAVE) * NV];
     __shared__ float stab[P::LDS_FLOATS];
     __shared__ uint8_t sty[P::LDS_TYPES];
-    const int t = threadIdx.x % TPF, g = threadIdx.x / TPF, N = A.N;
-    const long long f = (long long)blockIdx.x * FPB + g;
-    const bool live = f < A.F;
-    float* sf = sp + g * 3 * CAP;
-    if (live) stage_frame<TPF, CAP>(sf, A.pos + (size_t)f * N * 3, N, t);
-    const P p(V, N, stab, sty);
-    __syncthreads();
-    const float *sx = sf, *sy = sf + CAP, *sz = sf + 2 * CAP;
-    uint16_t* row = rows + threadIdx.x;                       // slot s of this thread's row: row[s * FP_BLOCK]
-    const float inf = __int_as_float(0x7f800000);
+    const P p(V, A.N, stab, sty);
+    const C fr = open_frame<TPF>(sp, A.pos, A.F, A.N);
+    const float *sx = fr.sx, *sy = fr.sy, *sz = fr.sz;
+    uint16_t* row = rows + threadIdx.x;
     float v[NV];
 #pragma unroll
     for (int k = 0; k < NV; ++k) v[k] = 0.f;
-    if (live) {
-        for (int i = t; i < N; i += TPF) {
+    if (fr.live) {
+        for (int i = fr.t; i < fr.N; i += TPF) {
             const float xi = sx[i], yi = sy[i], zi = sz[i];
             const int ti = p.species(i);
-            // ---- 1. the row of atom i: the atoms inside the support of (t_i, t_j)
-            int n = 0, over = 0;
-            for (int j = 0; j < N; ++j) {
-                float dx = sx[j] - xi, dy = sy[j] - yi, dz = sz[j] - zi, d2;
-                if (j == i || !pair_in(A.cell, inf, dx, dy, dz, d2)) continue;
-                const float rv = sqrtf(d2);
-                if (!(rv > 0.f && rv < p.pair(ti, p.species(j))[PA_RC])) continue;          // ters_geom's support test
-                if (n < TF_ROW_CAP) row[(n++) * FP_BLOCK] = (uint16_t)j;
-                else over = 1;
-            }
+            // ---- 1. the row of atom i: the atoms inside the support of (t_i, t_j) (ters_geom's support test)
+            int over;
+            const int n = build_row<TF_ROW_CAP, C::CAP>(row, A.cell, fr.sf, fr.N, i, over, [&](int j, float rv) {
+                return rv < p.pair(ti, p.species(j))[PA_RC];
+            });
             if (over) { v[1] += 1.f; continue; }
             // ---- 2. the bonds i -> j of the row (ters_bonds without bond_work)
             const TersEntry& cc = p.centre(ti);
@@ -164,7 +149,7 @@ __global__ __launch_bounds__(FP_BLOCK) void tersoff_frames_kernel(const TfArgs A
 #pragma unroll
             for (int q = 0; q < SMAX; ++q) { pa[q] = 0.f; pb[q] = 0.f; }
             for (int s = 0; s < n; ++s) {
-                const int j = row[s * FP_BLOCK];
+                const int j = row_at(row, s);
                 const int tj = p.species(j);
                 const TersEntry& pp = p.pair(ti, tj);
                 TersEdge<float> ej;
@@ -172,7 +157,7 @@ __global__ __launch_bounds__(FP_BLOCK) void tersoff_frames_kernel(const TfArgs A
                 float zeta = 0.f, zh = 0.f;
                 for (int u = 0; u < n; ++u) {
                     if (u == s) continue;
-                    const int k = row[u * FP_BLOCK];
+                    const int k = row_at(row, u);
                     TersEdge<float> ek;
                     if (!tf_edge(A.cell, p.pair(ti, p.species(k)), sx, sy, sz, k, xi, yi, zi, ek)) continue;
                     const TersTerm<float> tt = ters_term<float>(p, cc, ej, ek);
@@ -218,64 +203,35 @@ __global__ __launch_bounds__(FP_BLOCK) void tersoff_frames_kernel(const TfArgs A
             }
         }
     }
-    if constexpr (TPF == MDG_WAVE) {
-#pragma unroll
-        for (int k = 0; k < NV; ++k) v[k] = wave_sum(v[k]);
-    } else {
-        block_sum_n<NV>(v, red);
-    }
-    if (live && t == 0) {
-        const float nan = __int_as_float(0x7fc00000);
+    if (frame_sums(fr, v, red)) {
         const bool bad = v[1] > 0.f;
-        A.U[f] = bad ? nan : v[0];
+        A.U[fr.f] = nan_if(bad, v[0]);
         if constexpr (DTH) {
             const int S = p.S, S2 = S * S;
-            float* d = A.dU + (size_t)f * (2 * S2 + S);
+            float* d = A.dU + (size_t)fr.f * (2 * S2 + S);
 #pragma unroll
             for (int a = 0; a < SMAX; ++a) {
                 if (a < S) {
 #pragma unroll
                     for (int q = 0; q < SMAX; ++q) {
                         if (q < S) {
-                            d[a * S + q] = bad ? nan : v[OA + a * SMAX + q];
-                            d[S2 + a * S + q] = bad ? nan : v[OB + a * SMAX + q];
+                            d[a * S + q] = nan_if(bad, v[OA + a * SMAX + q]);
+                            d[S2 + a * S + q] = nan_if(bad, v[OB + a * SMAX + q]);
                         }
                     }
-                    d[2 * S2 + a] = bad ? nan : v[OH + a];
+                    d[2 * S2 + a] = nan_if(bad, v[OH + a]);
                 }
             }
         }
     }
 }
 
-// g_theta[k] = sum_f gU[f] dU[f, k]: a workgroup per parameter, fixed order.  The products of a reweighting gradient cancel
-// (gU sums to zero over the frames), so the sum runs in double.
-__global__ __launch_bounds__(FP_BLOCK) void frames_theta_reduce_kernel(const float* __restrict__ gU, const float* __restrict__ dU,
-                                                                       long long F, int P, float* __restrict__ g_theta) {
-    __shared__ double red[FP_BLOCK];
-    const int k = blockIdx.x;
-    double s = 0.0;
-    for (long long f = threadIdx.x; f < F; f += FP_BLOCK) s = s + (double)gU[f] * (double)dU[(size_t)f * P + k];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = FP_BLOCK / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) g_theta[k] = (float)red[0];
-}
-
 template <class P>
 inline void tersoff_frames_launch(const TfArgs& a, const typename P::Args& v, hipStream_t st) {
-    if (a.N <= FP_WAVE_ATOMS) {
-        constexpr int FPB = FP_BLOCK / MDG_WAVE;
-        const dim3 grid((a.F + FPB - 1) / FPB);
-        if (a.dU) hipLaunchKernelGGL((tersoff_frames_kernel<P, MDG_WAVE, true>), grid, dim3(FP_BLOCK), 0, st, a, v);
-        else hipLaunchKernelGGL((tersoff_frames_kernel<P, MDG_WAVE, false>), grid, dim3(FP_BLOCK), 0, st, a, v);
-    } else {
-        if (a.dU) hipLaunchKernelGGL((tersoff_frames_kernel<P, FP_BLOCK, true>), dim3(a.F), dim3(FP_BLOCK), 0, st, a, v);
-        else hipLaunchKernelGGL((tersoff_frames_kernel<P, FP_BLOCK, false>), dim3(a.F), dim3(FP_BLOCK), 0, st, a, v);
-    }
+    launch_frames(a.F, a.N, a.dU != nullptr, [&](auto tpf, auto dth, dim3 grid) {
+        hipLaunchKernelGGL((tersoff_frames_kernel<P, decltype(tpf)::value, decltype(dth)::value>), grid, dim3(FP_BLOCK), 0, st,
+                           a, v);
+    });
 }
 
 }  // namespace
@@ -313,16 +269,5 @@ extern "C" int mdg_tersoff_multi_frames_fwd(const float* pos, int n_frames, int 
     const TfTableArgs v{types, n_species, tables};
     tersoff_frames_launch<TersFrameTableView>(a, v, (hipStream_t)stream);
     MDG_CHECK_LAUNCH("tersoff_multi_frames_kernel");
-    return MDG_OK;
-}
-
-extern "C" int mdg_frames_theta_bwd(const float* gU, const float* dU_dtheta, int n_frames, int n_params, float* g_theta,
-                                    void* stream) {
-    MDG_CHECK_ARG(gU && dU_dtheta && g_theta, "frames_theta_bwd: null argument");
-    MDG_CHECK_ARG(n_frames > 0, "frames_theta_bwd: empty trajectory");
-    MDG_CHECK_ARG(n_params > 0, "frames_theta_bwd: n_params must be positive (got %d)", n_params);
-    hipLaunchKernelGGL(frames_theta_reduce_kernel, dim3(n_params), dim3(FP_BLOCK), 0, (hipStream_t)stream, gU, dU_dtheta,
-                       (long long)n_frames, n_params, g_theta);
-    MDG_CHECK_LAUNCH("frames_theta_reduce_kernel");
     return MDG_OK;
 }

@@ -2348,6 +2348,62 @@ class EnergyTableFn(torch.autograd.Function):
         return ((gx.reshape(xshape) if want_x else None), (gt.reshape(tshape) if want_t else None)) + (None,) * 6
 
 
+# ----------------------------------------------------------------------------- many-body energies of every frame: the scaffold
+def _frames_begin(ctx, xyz):
+    """The start of a frame energy's forward pass: (x3, U, side) = the detached contiguous frames [F, N, 3], the output [F]
+    and side(cols) -> the [F, cols] buffer the launch fills for the backward pass (dU_dtheta, or rho) when one of the inputs
+    1 .. 3 (the model's parameters) requires grad, else None."""
+    require_gpu(xyz, "xyz")
+    x3 = xyz.detach()
+    x3 = x3 if x3.is_contiguous() else x3.contiguous()
+    want = any(ctx.needs_input_grad[1:4])
+    return x3, torch.empty(x3.shape[0], device=x3.device), lambda cols: x3.new_empty(x3.shape[0], cols) if want else None
+
+
+def _frames_list_grad(x3, g, cell_struct, cutoff, evaluate):
+    """gx[f] = g[f] * dU/dx of frame f through a term's list kernel: the frames stacked as groups of N behind a list searched
+    at `cutoff`, in the frame chunks of AdfRawFn; evaluate(ell, flat, n_frames) -> the [n_frames N, 3] gradient."""
+    F, N = x3.shape[0], x3.shape[1]
+    gx = torch.empty_like(x3)
+    fc = _adf_chunk_frames(F, N, cell_struct, cutoff)
+    for f0 in range(0, F, fc):
+        f1 = min(F, f0 + fc)
+        flat = x3[f0:f1].reshape(-1, 3)
+        ell = build_ell(flat, cell_struct, cutoff, None, group=N)
+        torch.mul(evaluate(ell, flat, f1 - f0).view(f1 - f0, N, 3), g[f0:f1, None, None], out=gx[f0:f1])
+        del ell
+    return gx
+
+
+def _frames_theta_bwd(ctx, g, dU, shapes):
+    """The parameter part of a frame energy's backward pass: sum_f g[f] dU[f, :] (mdg_frames_theta_bwd), cut into the
+    parameters of `shapes` (inputs 1, 2, ... of the autograd function) where they require grad."""
+    lib = _lib.load()
+    F, n = dU.shape
+    out = torch.empty(n, device=dU.device)
+    check(lib.mdg_frames_theta_bwd(ptr(g), ptr(dU), F, n, ptr(out), stream_ptr(dU.device)), "mdg_frames_theta_bwd")
+    gth, pos = [], 0
+    for k, shape in enumerate(shapes):
+        m = int(np.prod(shape))
+        gth.append(out[pos:pos + m].reshape(shape) if ctx.needs_input_grad[1 + k] else None)
+        pos += m
+    return gth
+
+
+def _frames_backward(ctx, fn, gU, x3, xshape, cell_struct, side, params, cutoff, evaluate, routes):
+    """The backward pass of a frame energy `fn`: (gx, gp) = the position gradient through the term's list kernel
+    (_frames_list_grad at cutoff(), called on that route only) where xyz requires grad, and the three parameter gradients
+    params(g) where the forward pass kept `side` (it is None when no parameter requires grad).  fn.last_route <- routes[0]
+    (parameters alone), routes[1] (positions alone) or routes[2] (both)."""
+    g = gU.detach().to(torch.float32).contiguous()
+    gp = params(g) if side is not None else [None, None, None]
+    gx = None
+    if ctx.needs_input_grad[0]:
+        gx = _frames_list_grad(x3, g, cell_struct, float(cutoff()), evaluate).reshape(xshape)
+    fn.last_route = (routes[2] if side is not None else routes[1]) if gx is not None else routes[0]
+    return gx, gp
+
+
 # ----------------------------------------------------------------------------- Stillinger-Weber energy of every frame
 SW_FRAMES_MAX_ATOMS = 1024
 
@@ -2364,7 +2420,7 @@ class SWFramesFn(torch.autograd.Function):
     gradient's list is searched at list_scale a sigma.  Differentiable once.
 
     When a parameter requires grad the forward launch also emits dU_dtheta [F, 3], and the parameter part of the backward pass
-    is the fixed-order sum_f gU[f] dU_dtheta[f] (mdg_sw_frames_theta_bwd): no pair or triplet is visited again.  The position
+    is the fixed-order sum_f gU[f] dU_dtheta[f] (mdg_frames_theta_bwd): no pair or triplet is visited again.  The position
     gradient, off the reweighting path, goes through the list kernel of K23 (mdg_sw_eval): the frames stacked as groups of N
     behind a list searched at list_scale a sigma (sigma of the forward call, read on the host there: one read per backward
     pass, none on the parameters-only route), in the frame chunks of AdfRawFn, every frame's rows scaled by gU[f].
@@ -2376,14 +2432,9 @@ class SWFramesFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, epsilon, sigma, lam, theta, cell_struct, consts, list_scale):
         lib = _lib.load()
-        require_gpu(xyz, "xyz")
+        x3, U, side = _frames_begin(ctx, xyz)
         _check_theta(theta)
-        x3 = xyz.detach()
-        x3 = x3 if x3.is_contiguous() else x3.contiguous()
-        F, N = x3.shape[0], x3.shape[1]
-        want_th = any(ctx.needs_input_grad[1:4])
-        U = torch.empty(F, device=x3.device)
-        dU = torch.empty(F, 3, device=x3.device) if want_th else None
+        F, N, dU = x3.shape[0], x3.shape[1], side(3)
         check(lib.mdg_sw_frames_fwd(ptr(x3), F, N, C.byref(cell_struct), C.byref(consts), ptr(theta), ptr(U), ptr(dU),
                                     stream_ptr(x3.device)), "mdg_sw_frames_fwd")
         ctx.args = (cell_struct, consts, float(list_scale), xyz.shape, [p.shape for p in (epsilon, sigma, lam)])
@@ -2393,31 +2444,14 @@ class SWFramesFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gU):
-        lib = _lib.load()
         x3, th, dU = ctx.saved_tensors
         cell_struct, consts, list_scale, xshape, pshapes = ctx.args
-        F, N = x3.shape[0], x3.shape[1]
-        want_x = ctx.needs_input_grad[0]
-        g = gU.detach().to(torch.float32).contiguous()
-        gth = [None, None, None]
-        if dU is not None:
-            out = torch.empty(3, device=x3.device)
-            check(lib.mdg_sw_frames_theta_bwd(ptr(g), ptr(dU), F, ptr(out), stream_ptr(x3.device)), "mdg_sw_frames_theta_bwd")
-            gth = [out[k:k + 1].reshape(pshapes[k]) if ctx.needs_input_grad[1 + k] else None for k in range(3)]
-        gx = None
-        if want_x:
-            gx = torch.empty_like(x3)
-            list_cutoff = list_scale * consts.a * float(th[1])
-            fc = _adf_chunk_frames(F, N, cell_struct, list_cutoff)
-            for f0 in range(0, F, fc):
-                f1 = min(F, f0 + fc)
-                flat = x3[f0:f1].reshape(-1, 3)
-                ell = build_ell(flat, cell_struct, list_cutoff, None, group=N)
-                o = sw_eval(ell, flat, consts, th, energy=False, grad=True)
-                torch.mul(o["grad"].view(f1 - f0, N, 3), g[f0:f1, None, None], out=gx[f0:f1])
-                del ell
-            gx = gx.reshape(xshape)
-        SWFramesFn.last_route = "full" if want_x else "theta"
+
+        def evaluate(ell, flat, nf):
+            return sw_eval(ell, flat, consts, th, energy=False, grad=True)["grad"]
+        gx, gth = _frames_backward(ctx, SWFramesFn, gU, x3, xshape, cell_struct, dU,
+                                   lambda g: _frames_theta_bwd(ctx, g, dU, pshapes), lambda: list_scale * consts.a * float(th[1]), evaluate,
+                                   ("theta", "full", "full"))
         return (gx,) + tuple(gth) + (None, None, None, None)
 
 
@@ -2428,21 +2462,6 @@ EAM_FRAMES_MAX_ATOMS = 1024
 def eam_table_frames_lds_floats():
     """The largest pair-and-density table set (in floats) that csrc/eam_frames.hip reads from a workgroup copy in LDS."""
     return int(_lib.load().mdg_eam_table_frames_lds_floats())
-
-
-def _frames_list_grad(x3, g, cell_struct, cutoff, evaluate):
-    """gx[f] = g[f] * dU/dx of frame f through a term's list kernel: the frames stacked as groups of N behind a list searched
-    at `cutoff`, in the frame chunks of AdfRawFn; evaluate(ell, flat, n_frames) -> the [n_frames N, 3] gradient."""
-    F, N = x3.shape[0], x3.shape[1]
-    gx = torch.empty_like(x3)
-    fc = _adf_chunk_frames(F, N, cell_struct, cutoff)
-    for f0 in range(0, F, fc):
-        f1 = min(F, f0 + fc)
-        flat = x3[f0:f1].reshape(-1, 3)
-        ell = build_ell(flat, cell_struct, cutoff, None, group=N)
-        torch.mul(evaluate(ell, flat, f1 - f0).view(f1 - f0, N, 3), g[f0:f1, None, None], out=gx[f0:f1])
-        del ell
-    return gx
 
 
 class EAMTableFramesFn(torch.autograd.Function):
@@ -2465,21 +2484,17 @@ class EAMTableFramesFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, pair_nodes, density_nodes, embed_nodes, tables, types, cell_struct, consts):
         lib = _lib.load()
-        require_gpu(xyz, "xyz")
+        x3, U, side = _frames_begin(ctx, xyz)
         require_gpu(tables, "tables")
         require_gpu(types, "types", dtype=torch.int32)
-        x3 = xyz.detach()
-        x3 = x3 if x3.is_contiguous() else x3.contiguous()
         F, N = x3.shape[0], x3.shape[1]
         if tables.numel() != eam_table_size(consts) or types.numel() != N:
             raise ValueError("EAMTableFramesFn: tables must hold %d floats and types %d entries (got %d, %d)"
                              % (eam_table_size(consts), N, tables.numel(), types.numel()))
-        want_nodes = any(ctx.needs_input_grad[1:4])
+        rho = side(N)
         tb = tables.detach()
-        if want_nodes or ctx.needs_input_grad[0]:
+        if rho is not None or ctx.needs_input_grad[0]:
             tb = tb.clone()                                   # (the module's mirror is rewritten when the nodes are stepped)
-        U = torch.empty(F, device=x3.device)
-        rho = torch.empty(F, N, device=x3.device) if want_nodes else None
         check(lib.mdg_eam_table_frames_fwd(ptr(x3), F, N, C.byref(cell_struct), ptr(types), C.byref(consts), ptr(tb),
                                            int(EAMTableFramesFn.table_mode), ptr(U), ptr(rho), stream_ptr(x3.device)),
               "mdg_eam_table_frames_fwd")
@@ -2495,27 +2510,25 @@ class EAMTableFramesFn(torch.autograd.Function):
         x3, tb, types, rho = ctx.saved_tensors
         cell_struct, consts, xshape, pshapes, pdtypes = ctx.args
         F, N = x3.shape[0], x3.shape[1]
-        want_x = ctx.needs_input_grad[0]
-        g = gU.detach().to(torch.float32).contiguous()
-        gn = [None, None, None]
-        if rho is not None:
+
+        def nodes(g):
             out = torch.empty(eam_table_size(consts), device=x3.device)
             fx = torch.empty(eam_table_fx_size(consts), dtype=torch.int64, device=x3.device)
             check(lib.mdg_eam_table_frames_nodes_bwd(ptr(x3), F, N, C.byref(cell_struct), ptr(types), C.byref(consts), ptr(tb),
                                                      ptr(g), ptr(rho), ptr(out), ptr(fx), stream_ptr(x3.device)),
                   "mdg_eam_table_frames_nodes_bwd")
-            pos = 0
+            gn, pos = [None, None, None], 0
             for k in range(3):
                 n = int(np.prod(pshapes[k]))
                 if ctx.needs_input_grad[1 + k]:
                     gn[k] = out[pos:pos + n].reshape(pshapes[k]).to(pdtypes[k])
                 pos += n
-        gx = None
-        if want_x:
-            def evaluate(ell, flat, nf):
-                return eam_table_eval(ell, flat, types.repeat(nf), consts, tb, energy=False, grad=True)["grad"]
-            gx = _frames_list_grad(x3, g, cell_struct, float(consts.rc), evaluate).reshape(xshape)
-        EAMTableFramesFn.last_route = ("full" if rho is not None else "positions") if want_x else "nodes"
+            return gn
+
+        def evaluate(ell, flat, nf):
+            return eam_table_eval(ell, flat, types.repeat(nf), consts, tb, energy=False, grad=True)["grad"]
+        gx, gn = _frames_backward(ctx, EAMTableFramesFn, gU, x3, xshape, cell_struct, rho, nodes, lambda: consts.rc, evaluate,
+                                  ("nodes", "positions", "full"))
         return (gx,) + tuple(gn) + (None, None, None, None)
 
 
@@ -2525,7 +2538,7 @@ class EAMFramesFn(torch.autograd.Function):
     flows; theta: the device float [3] = (epsilon, a, c) the kernel reads; consts: MdgEAMConsts.  Differentiable once.
 
     When a parameter requires grad the forward launch also emits dU_dtheta [F, 3], and the parameter part of the backward pass
-    is the fixed-order sum_f gU[f] dU_dtheta[f] (mdg_sw_frames_theta_bwd, the reducer of K34): no pair is visited again.  The
+    is the fixed-order sum_f gU[f] dU_dtheta[f] (mdg_frames_theta_bwd): no pair is visited again.  The
     position gradient, off the reweighting path, goes through the list kernel of K24 (mdg_eam_eval) on the frames stacked as
     groups of N, every frame's rows scaled by gU[f].  `EAMFramesFn.last_route` names what the last backward pass ran: "theta"
     (the sum alone: detached frames, the reweighting case), "positions" or "full" (both)."""
@@ -2535,14 +2548,9 @@ class EAMFramesFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, epsilon, a, c, theta, cell_struct, consts):
         lib = _lib.load()
-        require_gpu(xyz, "xyz")
+        x3, U, side = _frames_begin(ctx, xyz)
         _check_theta(theta)
-        x3 = xyz.detach()
-        x3 = x3 if x3.is_contiguous() else x3.contiguous()
-        F, N = x3.shape[0], x3.shape[1]
-        want_th = any(ctx.needs_input_grad[1:4])
-        U = torch.empty(F, device=x3.device)
-        dU = torch.empty(F, 3, device=x3.device) if want_th else None
+        F, N, dU = x3.shape[0], x3.shape[1], side(3)
         check(lib.mdg_eam_frames_fwd(ptr(x3), F, N, C.byref(cell_struct), C.byref(consts), ptr(theta), ptr(U), ptr(dU),
                                      stream_ptr(x3.device)), "mdg_eam_frames_fwd")
         ctx.args = (cell_struct, consts, xyz.shape, [p.shape for p in (epsilon, a, c)])
@@ -2552,23 +2560,14 @@ class EAMFramesFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gU):
-        lib = _lib.load()
         x3, th, dU = ctx.saved_tensors
         cell_struct, consts, xshape, pshapes = ctx.args
-        F = x3.shape[0]
-        want_x = ctx.needs_input_grad[0]
-        g = gU.detach().to(torch.float32).contiguous()
-        gth = [None, None, None]
-        if dU is not None:
-            out = torch.empty(3, device=x3.device)
-            check(lib.mdg_sw_frames_theta_bwd(ptr(g), ptr(dU), F, ptr(out), stream_ptr(x3.device)), "mdg_sw_frames_theta_bwd")
-            gth = [out[k:k + 1].reshape(pshapes[k]) if ctx.needs_input_grad[1 + k] else None for k in range(3)]
-        gx = None
-        if want_x:
-            def evaluate(ell, flat, nf):
-                return eam_eval(ell, flat, consts, th, energy=False, grad=True)["grad"]
-            gx = _frames_list_grad(x3, g, cell_struct, float(consts.rc), evaluate).reshape(xshape)
-        EAMFramesFn.last_route = ("full" if dU is not None else "positions") if want_x else "theta"
+
+        def evaluate(ell, flat, nf):
+            return eam_eval(ell, flat, consts, th, energy=False, grad=True)["grad"]
+        gx, gth = _frames_backward(ctx, EAMFramesFn, gU, x3, xshape, cell_struct, dU,
+                                   lambda g: _frames_theta_bwd(ctx, g, dU, pshapes), lambda: consts.rc, evaluate,
+                                   ("theta", "positions", "full"))
         return (gx,) + tuple(gth) + (None, None, None)
 
 
@@ -2579,21 +2578,6 @@ TERSOFF_FRAMES_MAX_ATOMS = 1024
 def tersoff_frames_row_cap():
     """Neighbours inside R + D that csrc/tersoff_frames.hip keeps per atom; a frame with a longer row comes out NaN."""
     return int(_lib.load().mdg_tersoff_frames_row_cap())
-
-
-def _frames_theta_bwd(ctx, g, dU, shapes):
-    """The parameter part of a frame energy's backward pass: sum_f g[f] dU[f, :] (mdg_frames_theta_bwd), cut into the
-    parameters of `shapes` (inputs 1, 2, ... of the autograd function) where they require grad."""
-    lib = _lib.load()
-    F, n = dU.shape
-    out = torch.empty(n, device=dU.device)
-    check(lib.mdg_frames_theta_bwd(ptr(g), ptr(dU), F, n, ptr(out), stream_ptr(dU.device)), "mdg_frames_theta_bwd")
-    gth, pos = [], 0
-    for k, shape in enumerate(shapes):
-        m = int(np.prod(shape))
-        gth.append(out[pos:pos + m].reshape(shape) if ctx.needs_input_grad[1 + k] else None)
-        pos += m
-    return gth
 
 
 class TersoffFramesFn(torch.autograd.Function):
@@ -2613,17 +2597,12 @@ class TersoffFramesFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, A, B, h, theta, cell_struct, consts):
         lib = _lib.load()
-        require_gpu(xyz, "xyz")
+        x3, U, side = _frames_begin(ctx, xyz)
         _check_theta(theta)
-        x3 = xyz.detach()
-        x3 = x3 if x3.is_contiguous() else x3.contiguous()
-        F, N = x3.shape[0], x3.shape[1]
-        want_th = any(ctx.needs_input_grad[1:4])
+        F, N, dU = x3.shape[0], x3.shape[1], side(3)
         th = theta.detach()
         if ctx.needs_input_grad[0]:
             th = th.clone()                                   # (the module's mirror is rewritten when the parameters are stepped)
-        U = torch.empty(F, device=x3.device)
-        dU = torch.empty(F, 3, device=x3.device) if want_th else None
         check(lib.mdg_tersoff_frames_fwd(ptr(x3), F, N, C.byref(cell_struct), C.byref(consts), ptr(th), ptr(U), ptr(dU),
                                          stream_ptr(x3.device)), "mdg_tersoff_frames_fwd")
         ctx.args = (cell_struct, consts, xyz.shape, [p.shape for p in (A, B, h)])
@@ -2635,15 +2614,12 @@ class TersoffFramesFn(torch.autograd.Function):
     def backward(ctx, gU):
         x3, th, dU = ctx.saved_tensors
         cell_struct, consts, xshape, pshapes = ctx.args
-        want_x = ctx.needs_input_grad[0]
-        g = gU.detach().to(torch.float32).contiguous()
-        gth = _frames_theta_bwd(ctx, g, dU, pshapes) if dU is not None else [None, None, None]
-        gx = None
-        if want_x:
-            def evaluate(ell, flat, nf):
-                return tersoff_eval(ell, flat, consts, th, energy=False, grad=True)["grad"]
-            gx = _frames_list_grad(x3, g, cell_struct, float(consts.R + consts.D), evaluate).reshape(xshape)
-        TersoffFramesFn.last_route = "full" if want_x else "theta"
+
+        def evaluate(ell, flat, nf):
+            return tersoff_eval(ell, flat, consts, th, energy=False, grad=True)["grad"]
+        gx, gth = _frames_backward(ctx, TersoffFramesFn, gU, x3, xshape, cell_struct, dU,
+                                   lambda g: _frames_theta_bwd(ctx, g, dU, pshapes), lambda: consts.R + consts.D, evaluate,
+                                   ("theta", "full", "full"))
         return (gx,) + tuple(gth) + (None, None, None)
 
 
@@ -2662,23 +2638,19 @@ class TersoffMultiFramesFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, A, B, h, tables, types, n_species, cell_struct, cutoff):
         lib = _lib.load()
-        require_gpu(xyz, "xyz")
+        x3, U, side = _frames_begin(ctx, xyz)
         require_gpu(tables, "tables")
         require_gpu(types, "types", dtype=torch.int32)
-        x3 = xyz.detach()
-        x3 = x3 if x3.is_contiguous() else x3.contiguous()
         F, N, S = x3.shape[0], x3.shape[1], int(n_species)
         if not 1 <= S <= TERSOFF_MULTI_MAX_SPECIES:
             raise ValueError("mdgrad_amd: n_species must lie in [1, %d] (got %r)" % (TERSOFF_MULTI_MAX_SPECIES, n_species))
         if tables.numel() != 8 * S * (S + 1) or not tables.is_contiguous() or types.numel() != N or not types.is_contiguous():
             raise ValueError("TersoffMultiFramesFn: tables must hold %d floats and types %d entries (got %d, %d)"
                              % (8 * S * (S + 1), N, tables.numel(), types.numel()))
-        want_th = any(ctx.needs_input_grad[1:4])
+        dU = side(2 * S * S + S)
         tb = tables.detach()
         if ctx.needs_input_grad[0]:
             tb = tb.clone()                                   # (the module's mirror is rewritten when the parameters are stepped)
-        U = torch.empty(F, device=x3.device)
-        dU = torch.empty(F, 2 * S * S + S, device=x3.device) if want_th else None
         check(lib.mdg_tersoff_multi_frames_fwd(ptr(x3), F, N, C.byref(cell_struct), ptr(types), S, ptr(tb), ptr(U), ptr(dU),
                                                stream_ptr(x3.device)), "mdg_tersoff_multi_frames_fwd")
         ctx.args = (cell_struct, S, float(cutoff), xyz.shape, [p.shape for p in (A, B, h)])
@@ -2690,15 +2662,12 @@ class TersoffMultiFramesFn(torch.autograd.Function):
     def backward(ctx, gU):
         x3, tb, types, dU = ctx.saved_tensors
         cell_struct, S, cutoff, xshape, pshapes = ctx.args
-        want_x = ctx.needs_input_grad[0]
-        g = gU.detach().to(torch.float32).contiguous()
-        gth = _frames_theta_bwd(ctx, g, dU, pshapes) if dU is not None else [None, None, None]
-        gx = None
-        if want_x:
-            def evaluate(ell, flat, nf):
-                return tersoff_multi_eval(ell, flat, types.repeat(nf), S, tb, energy=False, grad=True)["grad"]
-            gx = _frames_list_grad(x3, g, cell_struct, cutoff, evaluate).reshape(xshape)
-        TersoffMultiFramesFn.last_route = "full" if want_x else "theta"
+
+        def evaluate(ell, flat, nf):
+            return tersoff_multi_eval(ell, flat, types.repeat(nf), S, tb, energy=False, grad=True)["grad"]
+        gx, gth = _frames_backward(ctx, TersoffMultiFramesFn, gU, x3, xshape, cell_struct, dU,
+                                   lambda g: _frames_theta_bwd(ctx, g, dU, pshapes), lambda: cutoff, evaluate,
+                                   ("theta", "full", "full"))
         return (gx,) + tuple(gth) + (None, None, None, None, None)
 
 

@@ -13,6 +13,17 @@ from .observable import Observable
 _FORMS = "LJFamily / LennardJones / LennardJones69, ExcludedVolume, ModifiedMorse, Buck, Yukawa"
 
 
+def _frames(self, x, name):
+    """x [..., k N, 3] as frames [F, N, 3] and the shape of the per-frame result (the method `_frames` of the per-frame
+    observables below)."""
+    n = x.shape[-2] if x.dim() >= 2 else 0
+    if n == 0 or x.shape[-1] != 3 or n % self.natoms:
+        raise ValueError("%s: %s must be [..., k * %d, 3], got %s" % (type(self).__name__, name, self.natoms, tuple(x.shape)))
+    k = n // self.natoms                             # replica-stacked state [..., k N, 3]: one value per replica
+    lead = tuple(x.shape[:-2]) + ((k,) if k > 1 else ())
+    return x.reshape(-1, self.natoms, 3), lead
+
+
 class Temperature(Observable):
     def __init__(self, system):
         super().__init__(system)
@@ -67,13 +78,7 @@ class Pressure(Observable):
         self._terms = ops.make_terms(terms, off)
         self._masks = [m._mask for m in mods]
 
-    def _frames(self, x, name):
-        n = x.shape[-2] if x.dim() >= 2 else 0
-        if n == 0 or x.shape[-1] != 3 or n % self.natoms:
-            raise ValueError("Pressure: %s must be [..., k * %d, 3], got %s" % (name, self.natoms, tuple(x.shape)))
-        k = n // self.natoms                             # replica-stacked state [..., k N, 3]: one value per replica
-        lead = tuple(x.shape[:-2]) + ((k,) if k > 1 else ())
-        return x.reshape(-1, self.natoms, 3), lead
+    _frames = _frames
 
     def virial(self, q):
         """W of every frame of q ([N, 3], [T, N, 3], [R, T, N, 3] or replica-stacked [..., k N, 3])."""
@@ -160,13 +165,7 @@ class PotentialEnergy(Observable):
             off += n
         self._terms = ops.make_terms(descr, off)
 
-    def _frames(self, x, name):
-        n = x.shape[-2] if x.dim() >= 2 else 0
-        if n == 0 or x.shape[-1] != 3 or n % self.natoms:
-            raise ValueError("PotentialEnergy: %s must be [..., k * %d, 3], got %s" % (name, self.natoms, tuple(x.shape)))
-        k = n // self.natoms                             # replica-stacked state [..., k N, 3]: one value per replica
-        lead = tuple(x.shape[:-2]) + ((k,) if k > 1 else ())
-        return x.reshape(-1, self.natoms, 3), lead
+    _frames = _frames
 
     def _torch_energy(self, x, budget=1 << 22):
         """The same sum by torch ops in x's dtype on x's device: all pairs of every frame, chunked over the frames."""
@@ -305,13 +304,7 @@ class TabulatedEnergy(Observable):
                                          inv_du=float(np.float32(1.0) / du)))
         self._user = torch.nn.ModuleList([g["mods"] for g in self._groups])
 
-    def _frames(self, x, name):
-        n = x.shape[-2] if x.dim() >= 2 else 0
-        if n == 0 or x.shape[-1] != 3 or n % self.natoms:
-            raise ValueError("TabulatedEnergy: %s must be [..., k * %d, 3], got %s" % (name, self.natoms, tuple(x.shape)))
-        k = n // self.natoms
-        lead = tuple(x.shape[:-2]) + ((k,) if k > 1 else ())
-        return x.reshape(-1, self.natoms, 3), lead
+    _frames = _frames
 
     def grid(self, group=0):
         """(u0, du, nodes) of a group's table: float32 values, u_g = u0 + g du"""
@@ -391,7 +384,70 @@ class TabulatedEnergy(Observable):
         return U.reshape(lead)
 
 
-class StillingerWeberEnergy(Observable):
+class _ManyBodyEnergy(Observable):
+    """What StillingerWeberEnergy, EAMEnergy and TersoffEnergy share: the checks of the constructor, the frame-by-frame torch
+    restatement and the device copy of one replica's species.  A subclass names its models (`_model_types`), its refusal
+    (`_REFUSAL`, with one %s for the model's class) and the arguments of its model's `_torch_energy` (`_torch_args`);
+    `_typed` says whether the model carries per-atom `types`."""
+
+    MAX_ATOMS = 1024
+    _REFUSAL = None
+    _typed = False
+    _frames = _frames
+
+    def __init__(self, system, model):
+        from . import _lib
+        name = type(self).__name__
+        if not isinstance(model, self._model_types()):
+            raise NotImplementedError(self._REFUSAL % type(model).__name__)
+        super().__init__(system)
+        cs = _lib.make_cell(system.get_cell())
+        if not cs.diag:
+            raise ValueError("%s: the cell must be diagonal (triclinic cells are not supported)" % name)
+        if self.natoms > self.MAX_ATOMS:
+            raise ValueError("%s: at most %d atoms per frame, got %d" % (name, self.MAX_ATOMS, self.natoms))
+        if self.natoms != model._group:
+            raise ValueError("%s: the model was built for %d atoms per replica, the system holds %d"
+                             % (name, model._group, self.natoms))
+        self.model = model
+        self._cell_struct = cs
+        self._half_cell = 0.5 * min(cs.h[0], cs.h[4], cs.h[8])
+        self._types = None
+        self._check_cutoff()
+
+    def _check_cutoff(self):
+        """The half-cell check on the model's fixed cutoff."""
+        if self.model.cutoff > self._half_cell:
+            raise ValueError("%s: cutoff = %g exceeds half the shortest cell length (%g): the minimum image no longer "
+                             "holds every neighbour" % (type(self).__name__, self.model.cutoff, self._half_cell))
+
+    def _torch_args(self, x):
+        """What the model's `_torch_energy` takes after the frame."""
+        return ()
+
+    def _torch_energy(self, x):
+        """The model's torch restatement, one frame at a time (each frame is one replica to it)."""
+        m = self.model
+        n_rep, m._n_rep = m._n_rep, 1
+        types = m.types if self._typed else None
+        if self._typed:
+            m.types = types[:self.natoms]                 # (one entry per atom of the stacked system: one replica's)
+        args = self._torch_args(x)
+        try:
+            return torch.stack([m._torch_energy(xf, *args).reshape(()) for xf in x])
+        finally:
+            m._n_rep = n_rep
+            if self._typed:
+                m.types = types
+
+    def _device_types(self, device):
+        """One replica's species as device int32 [N], copied once per device."""
+        if self._types is None or self._types.device != device:
+            self._types = self.model.types[:self.natoms].to(device=device, dtype=torch.int32).contiguous()
+        return self._types
+
+
+class StillingerWeberEnergy(_ManyBodyEnergy):
     """Stillinger-Weber energy of every frame of a trajectory in one call, which `PotentialEnergy` refuses: the energy side of
     trajectory reweighting (`reweight.Reweighting`) for the three-body models fitted to structure that a pair term cannot express
     (silicon, mW water).
@@ -422,29 +478,19 @@ class StillingerWeberEnergy(Observable):
     any callable), the virial, more than 1024 atoms per frame, triclinic cells."""
 
     MAX_ATOMS = ops.SW_FRAMES_MAX_ATOMS
+    _REFUSAL = ("StillingerWeberEnergy: the model must be an interface.StillingerWeber (one species); got "
+                "%s.  StillingerWeberMulti, Tersoff, EAM, pair terms and Stacks have no batched "
+                "Stillinger-Weber frame energy (built-in pair forms: thermo.PotentialEnergy; learned pair "
+                "modules: thermo.TabulatedEnergy; SuttonChen and EAM: thermo.EAMEnergy; Tersoff and "
+                "TersoffMulti: thermo.TersoffEnergy)")
 
-    def __init__(self, system, model):
-        from . import _lib
+    @staticmethod
+    def _model_types():
         from .interface import StillingerWeber
-        if not isinstance(model, StillingerWeber):
-            raise NotImplementedError("StillingerWeberEnergy: the model must be an interface.StillingerWeber (one species); got "
-                                      "%s.  StillingerWeberMulti, Tersoff, EAM, pair terms and Stacks have no batched "
-                                      "Stillinger-Weber frame energy (built-in pair forms: thermo.PotentialEnergy; learned pair "
-                                      "modules: thermo.TabulatedEnergy; SuttonChen and EAM: thermo.EAMEnergy; Tersoff and "
-                                      "TersoffMulti: thermo.TersoffEnergy)"
-                                      % type(model).__name__)
-        super().__init__(system)
-        cs = _lib.make_cell(system.get_cell())
-        if not cs.diag:
-            raise ValueError("StillingerWeberEnergy: the cell must be diagonal (triclinic cells are not supported)")
-        if self.natoms > self.MAX_ATOMS:
-            raise ValueError("StillingerWeberEnergy: at most %d atoms per frame, got %d" % (self.MAX_ATOMS, self.natoms))
-        if self.natoms != model._group:
-            raise ValueError("StillingerWeberEnergy: the model was built for %d atoms per replica, the system holds %d"
-                             % (model._group, self.natoms))
-        self.model = model
-        self._cell_struct = cs
-        self._half_cell = 0.5 * min(cs.h[0], cs.h[4], cs.h[8])
+        return StillingerWeber
+
+    def _check_cutoff(self):
+        """a sigma moves with the trainable sigma: the check is `_sync_cutoff`, repeated at every call."""
         self._sig_key = None
         self._sync_cutoff()
 
@@ -465,23 +511,6 @@ class StillingerWeberEnergy(Observable):
                              "image no longer holds every neighbour" % (rc, self._half_cell))
         self._sig_key = key
 
-    def _frames(self, x, name):
-        n = x.shape[-2] if x.dim() >= 2 else 0
-        if n == 0 or x.shape[-1] != 3 or n % self.natoms:
-            raise ValueError("StillingerWeberEnergy: %s must be [..., k * %d, 3], got %s" % (name, self.natoms, tuple(x.shape)))
-        k = n // self.natoms                             # replica-stacked state [..., k N, 3]: one value per replica
-        lead = tuple(x.shape[:-2]) + ((k,) if k > 1 else ())
-        return x.reshape(-1, self.natoms, 3), lead
-
-    def _torch_energy(self, x):
-        """The model's torch restatement, one frame at a time (each frame is one replica to it)."""
-        m = self.model
-        n_rep, m._n_rep = m._n_rep, 1
-        try:
-            return torch.stack([m._torch_energy(xf).reshape(()) for xf in x])
-        finally:
-            m._n_rep = n_rep
-
     def forward(self, q):
         """U of every frame of q."""
         x, lead = self._frames(q, "q")
@@ -494,7 +523,7 @@ class StillingerWeberEnergy(Observable):
                                     m.cutoff_reset).reshape(lead)
 
 
-class EAMEnergy(Observable):
+class EAMEnergy(_ManyBodyEnergy):
     """Embedded-atom energy of every frame of a trajectory in one call: the energy side of trajectory reweighting
     (`reweight.Reweighting`) for the metals, whose trainable object is often the shape of tabulated functions -- thousands of
     node entries, all of whose gradients one weighted scatter gives at once.
@@ -523,57 +552,25 @@ class EAMEnergy(Observable):
     1024 atoms per frame, triclinic cells."""
 
     MAX_ATOMS = ops.EAM_FRAMES_MAX_ATOMS
+    _REFUSAL = ("EAMEnergy: the model must be an interface.EAM or an interface.SuttonChen; got %s.  Stacks, "
+                "Tersoff and Stillinger-Weber terms have no batched embedded-atom frame energy (one-species "
+                "Stillinger-Weber: thermo.StillingerWeberEnergy; Tersoff and TersoffMulti: "
+                "thermo.TersoffEnergy; built-in pair forms: thermo.PotentialEnergy; learned pair modules: "
+                "thermo.TabulatedEnergy)")
+
+    @staticmethod
+    def _model_types():
+        from .interface import EAM, SuttonChen
+        return EAM, SuttonChen
 
     def __init__(self, system, model):
-        from . import _lib
-        from .interface import EAM, SuttonChen
-        if not isinstance(model, (EAM, SuttonChen)):
-            raise NotImplementedError("EAMEnergy: the model must be an interface.EAM or an interface.SuttonChen; got %s.  Stacks, "
-                                      "Tersoff and Stillinger-Weber terms have no batched embedded-atom frame energy (one-species "
-                                      "Stillinger-Weber: thermo.StillingerWeberEnergy; Tersoff and TersoffMulti: "
-                                      "thermo.TersoffEnergy; built-in pair forms: thermo.PotentialEnergy; learned pair modules: "
-                                      "thermo.TabulatedEnergy)" % type(model).__name__)
-        super().__init__(system)
-        cs = _lib.make_cell(system.get_cell())
-        if not cs.diag:
-            raise ValueError("EAMEnergy: the cell must be diagonal (triclinic cells are not supported)")
-        if self.natoms > self.MAX_ATOMS:
-            raise ValueError("EAMEnergy: at most %d atoms per frame, got %d" % (self.MAX_ATOMS, self.natoms))
-        if self.natoms != model._group:
-            raise ValueError("EAMEnergy: the model was built for %d atoms per replica, the system holds %d"
-                             % (model._group, self.natoms))
-        half = 0.5 * min(cs.h[0], cs.h[4], cs.h[8])
-        if model.cutoff > half:
-            raise ValueError("EAMEnergy: cutoff = %g exceeds half the shortest cell length (%g): the minimum image no longer "
-                             "holds every neighbour" % (model.cutoff, half))
-        self.model = model
-        self.tabulated = isinstance(model, EAM)
-        self._cell_struct = cs
-        self._types = None
+        super().__init__(system, model)
+        self.tabulated = self._typed = isinstance(model, self._model_types()[0])
 
-    def _frames(self, x, name):
-        n = x.shape[-2] if x.dim() >= 2 else 0
-        if n == 0 or x.shape[-1] != 3 or n % self.natoms:
-            raise ValueError("EAMEnergy: %s must be [..., k * %d, 3], got %s" % (name, self.natoms, tuple(x.shape)))
-        k = n // self.natoms                             # replica-stacked state [..., k N, 3]: one value per replica
-        lead = tuple(x.shape[:-2]) + ((k,) if k > 1 else ())
-        return x.reshape(-1, self.natoms, 3), lead
-
-    def _torch_energy(self, x):
-        """The model's torch restatement, one frame at a time (each frame is one replica to it)."""
-        m = self.model
-        n_rep, m._n_rep = m._n_rep, 1
-        types = m.types if self.tabulated else None
-        if self.tabulated:
-            m.types = types[:self.natoms]                 # (one entry per atom of the stacked system: one replica's)
+    def _torch_args(self, x):
         # (cast once: the parameter gradient is summed over the frames in the dtype of x and rounded to the parameters' once)
-        params = tuple(p.to(x) for p in (m._nodes() if self.tabulated else (m.epsilon, m.a, m.c)))
-        try:
-            return torch.stack([m._torch_energy(xf, params).reshape(()) for xf in x])
-        finally:
-            m._n_rep = n_rep
-            if self.tabulated:
-                m.types = types
+        m = self.model
+        return (tuple(p.to(x) for p in (m._nodes() if self.tabulated else (m.epsilon, m.a, m.c))),)
 
     def forward(self, q):
         """U of every frame of q."""
@@ -582,18 +579,16 @@ class EAMEnergy(Observable):
             return self._torch_energy(x).reshape(lead)
         m = self.model
         if self.tabulated:
-            if self._types is None or self._types.device != x.device:
-                self._types = m.types[:self.natoms].to(device=x.device, dtype=torch.int32).contiguous()
             tables = m._tables()
             if tables.device != x.device:
                 tables = tables.to(x.device)
-            return ops.EAMTableFramesFn.apply(x, m.pair_nodes, m.density_nodes, m.embed_nodes, tables, self._types,
-                                              self._cell_struct, m._consts).reshape(lead)
+            return ops.EAMTableFramesFn.apply(x, m.pair_nodes, m.density_nodes, m.embed_nodes, tables,
+                                              self._device_types(x.device), self._cell_struct, m._consts).reshape(lead)
         theta = torch.cat([p.detach().reshape(-1) for p in (m.epsilon, m.a, m.c)]).to(device=x.device, dtype=torch.float32)
         return ops.EAMFramesFn.apply(x, m.epsilon, m.a, m.c, theta, self._cell_struct, m._consts).reshape(lead)
 
 
-class TersoffEnergy(Observable):
+class TersoffEnergy(_ManyBodyEnergy):
     """Tersoff bond-order energy of every frame of a trajectory in one call: the energy side of trajectory reweighting
     (`reweight.Reweighting`) for silicon, carbon, germanium and their alloys, whose trainable A, B and h are what a fit to an
     angle distribution or an RDF carries.
@@ -625,57 +620,25 @@ class TersoffEnergy(Observable):
     per frame, evaluation inside the fused trajectory launches."""
 
     MAX_ATOMS = ops.TERSOFF_FRAMES_MAX_ATOMS
+    _REFUSAL = ("TersoffEnergy: the model must be an interface.Tersoff or an interface.TersoffMulti; got "
+                "%s.  Stacks, Stillinger-Weber and embedded-atom terms have no batched Tersoff frame "
+                "energy (one-species Stillinger-Weber: thermo.StillingerWeberEnergy; SuttonChen and EAM: "
+                "thermo.EAMEnergy; built-in pair forms: thermo.PotentialEnergy; learned pair modules: "
+                "thermo.TabulatedEnergy)")
+
+    @staticmethod
+    def _model_types():
+        from .interface import Tersoff, TersoffMulti
+        return Tersoff, TersoffMulti
 
     def __init__(self, system, model):
-        from . import _lib
-        from .interface import Tersoff, TersoffMulti
-        if not isinstance(model, (Tersoff, TersoffMulti)):
-            raise NotImplementedError("TersoffEnergy: the model must be an interface.Tersoff or an interface.TersoffMulti; got "
-                                      "%s.  Stacks, Stillinger-Weber and embedded-atom terms have no batched Tersoff frame "
-                                      "energy (one-species Stillinger-Weber: thermo.StillingerWeberEnergy; SuttonChen and EAM: "
-                                      "thermo.EAMEnergy; built-in pair forms: thermo.PotentialEnergy; learned pair modules: "
-                                      "thermo.TabulatedEnergy)" % type(model).__name__)
-        super().__init__(system)
-        cs = _lib.make_cell(system.get_cell())
-        if not cs.diag:
-            raise ValueError("TersoffEnergy: the cell must be diagonal (triclinic cells are not supported)")
-        if self.natoms > self.MAX_ATOMS:
-            raise ValueError("TersoffEnergy: at most %d atoms per frame, got %d" % (self.MAX_ATOMS, self.natoms))
-        if self.natoms != model._group:
-            raise ValueError("TersoffEnergy: the model was built for %d atoms per replica, the system holds %d"
-                             % (model._group, self.natoms))
-        half = 0.5 * min(cs.h[0], cs.h[4], cs.h[8])
-        if model.cutoff > half:
-            raise ValueError("TersoffEnergy: cutoff = %g exceeds half the shortest cell length (%g): the minimum image no longer "
-                             "holds every neighbour" % (model.cutoff, half))
-        self.model = model
-        self.multi = isinstance(model, TersoffMulti)
-        self._cell_struct = cs
-        self._types = None
+        super().__init__(system, model)
+        self.multi = self._typed = isinstance(model, self._model_types()[1])
 
-    def _frames(self, x, name):
-        n = x.shape[-2] if x.dim() >= 2 else 0
-        if n == 0 or x.shape[-1] != 3 or n % self.natoms:
-            raise ValueError("TersoffEnergy: %s must be [..., k * %d, 3], got %s" % (name, self.natoms, tuple(x.shape)))
-        k = n // self.natoms                             # replica-stacked state [..., k N, 3]: one value per replica
-        lead = tuple(x.shape[:-2]) + ((k,) if k > 1 else ())
-        return x.reshape(-1, self.natoms, 3), lead
-
-    def _torch_energy(self, x):
-        """The model's torch restatement, one frame at a time (each frame is one replica to it)."""
-        m = self.model
-        n_rep, m._n_rep = m._n_rep, 1
-        types = m.types if self.multi else None
-        if self.multi:
-            m.types = types[:self.natoms]                 # (one entry per atom of the stacked system: one replica's)
+    def _torch_args(self, x):
         # (cast once: the parameter gradient is summed over the frames in the dtype of x and rounded to the parameters' once)
-        params = tuple(p.to(x) for p in (m.A, m.B, m.h))
-        try:
-            return torch.stack([m._torch_energy(xf, params).reshape(()) for xf in x])
-        finally:
-            m._n_rep = n_rep
-            if self.multi:
-                m.types = types
+        m = self.model
+        return (tuple(p.to(x) for p in (m.A, m.B, m.h)),)
 
     def _mirror(self, mirror, device):
         """The model's device image of (A, B, h), rewritten now (an edit through `.data` moves no version counter, so the
@@ -690,10 +653,8 @@ class TersoffEnergy(Observable):
             return self._torch_energy(x).reshape(lead)
         m = self.model
         if self.multi:
-            if self._types is None or self._types.device != x.device:
-                self._types = m.types[:self.natoms].to(device=x.device, dtype=torch.int32).contiguous()
             tables = self._mirror(m._table_mirror, x.device)
-            return ops.TersoffMultiFramesFn.apply(x, m.A, m.B, m.h, tables, self._types, m.n_species, self._cell_struct,
-                                                  m.cutoff).reshape(lead)
+            return ops.TersoffMultiFramesFn.apply(x, m.A, m.B, m.h, tables, self._device_types(x.device), m.n_species,
+                                                  self._cell_struct, m.cutoff).reshape(lead)
         theta = self._mirror(m._theta_mirror, x.device)
         return ops.TersoffFramesFn.apply(x, m.A, m.B, m.h, theta, self._cell_struct, m._consts).reshape(lead)

@@ -310,3 +310,21 @@ def test_a_row_beyond_the_cap_gives_nan_for_its_frame_alone():
         p.requires_grad_(True)
     U = energy(case.q())
     assert bool(torch.isnan(U[1])) and bool(torch.isfinite(U[0])) and torch.equal(U[0].detach(), U[2].detach())
+
+
+@pytest.mark.parametrize("F", [1, 257])
+def test_sw_theta_bwd_is_the_shared_reducer_with_three_columns(F):
+    """mdg_sw_frames_theta_bwd(gU, dU, F) and mdg_frames_theta_bwd(gU, dU, F, 3) give the same bits (one kernel,
+    csrc/frames_reduce.hip): one frame, and 257 = one more than a workgroup's stride, so both the strided loop and the tree
+    run."""
+    from mdgrad_amd import _lib
+    lib = _lib.load()
+    gen = torch.Generator(device="cpu").manual_seed(41 + F)
+    gU = torch.randn(F, generator=gen).to(DEV)
+    dU = torch.randn(F, 3, generator=gen).to(DEV)
+    a, b = torch.full((3,), float("nan"), device=DEV), torch.full((3,), float("nan"), device=DEV)
+    _lib.check(lib.mdg_sw_frames_theta_bwd(_lib.ptr(gU), _lib.ptr(dU), F, _lib.ptr(a), _lib.stream_ptr(gU.device)),
+               "mdg_sw_frames_theta_bwd")
+    _lib.check(lib.mdg_frames_theta_bwd(_lib.ptr(gU), _lib.ptr(dU), F, 3, _lib.ptr(b), _lib.stream_ptr(gU.device)),
+               "mdg_frames_theta_bwd")
+    assert bool(torch.isfinite(a).all()) and torch.equal(a, b)

@@ -13,7 +13,7 @@
 //   2. force pass:    dU/dx_i = -sum_j [phi'(r_ij) + (F'_i + F'_j) f'(r_ij)] e_ij   (e_ij = the unit vector i -> j), an
 //                     atom-centric gather with one writer per output word; u_i and its parameter terms; the energy through a
 //                     fixed-order block partial and a finish kernel.
-// Both are laid out like sw_ell_kernel (csrc/sw.hip): LPA lanes walk one atom's row, wave shuffles combine the per-atom sums.  No
+// Both are laid out like sw_kernel (csrc/sw_core.hpp): LPA lanes walk one atom's row, wave shuffles combine the per-atom sums.  No
 // float atomics => bitwise reproducible.  Rows are read from global memory, nothing is staged, so there is no row cap.  The
 // support test is applied on r = sqrtf(d2) against rc; a list searched with a larger radius (a skin) is exact.
 //

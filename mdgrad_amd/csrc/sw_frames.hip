@@ -11,7 +11,8 @@
 //
 // Shape: the scaffold of csrc/frame_atoms.hpp.  Every thread, for each of its atoms,
 //   1. builds the row of the atoms inside the support (build_row) -- every lane does the same N - 1 tests;
-//   2. walks that row: the pair (i, j) for every slot, the triplet (j, i, k) for every later slot, edges by sw_edge().
+//   2. walks that row: the pair (i, j) for every slot, the triplet (j, i, k) for every later slot, edges by sw_edge() and pair
+//      terms by sw_pair() of csrc/sw_core.hpp on one pair entry (eps, sigma, a sigma, gamma sigma, ...) built from theta.
 // Row cap: SWF_ROW_CAP = 64 entries (32 KB of LDS for the 256 rows of a workgroup; silicon and mW water hold 4 - 30
 // neighbours inside a sigma); a frame in which any atom has more neighbours comes out NaN in U and dU_dtheta, alone.
 //
@@ -44,7 +45,9 @@ __global__ __launch_bounds__(FP_BLOCK) void sw_frames_kernel(const SwfArgs A) {
     __shared__ uint16_t rows[SWF_ROW_CAP * FP_BLOCK];
     __shared__ float red[(FP_BLOCK / MDG_WAVE) * NV];
     const C fr = open_frame<TPF>(sp, A.pos, A.F, A.N);
-    const SwK K = sw_constants(A.theta[0], A.theta[1], A.theta[2], A.a, A.gamma, A.cos0, A.A, A.B, A.p, A.q);
+    // the one pair entry, from the live (eps, sigma, lam) as csrc/sw.hip derives it
+    const float eps = A.theta[0], sigma = A.theta[1], lam = A.theta[2];
+    const SwPairE P{eps, sigma, A.a * sigma, A.gamma * sigma, A.gamma, A.A, A.B, (float)A.p, (float)A.q, A.a, eps * A.A, 0.f};
     const float *sx = fr.sx, *sy = fr.sy, *sz = fr.sz;
     uint16_t* row = rows + threadIdx.x;
     float v[NV] = {0.f, 0.f, 0.f, 0.f, 0.f};
@@ -54,7 +57,7 @@ __global__ __launch_bounds__(FP_BLOCK) void sw_frames_kernel(const SwfArgs A) {
             // ---- 1. the row of atom i (sw_edge's support test)
             int over;
             const int n = build_row<SWF_ROW_CAP, C::CAP>(row, A.cell, fr.sf, fr.N, i, over,
-                                                         [&](int, float rv) { return rv < K.rc; });
+                                                         [&](int, float rv) { return rv < P.rc; });
             if (over) { v[4] += 1.f; continue; }
             // ---- 2. pairs and triplets of the row
             float S2 = 0.f, S2s = 0.f, S3 = 0.f, S3s = 0.f;
@@ -63,32 +66,33 @@ __global__ __launch_bounds__(FP_BLOCK) void sw_frames_kernel(const SwfArgs A) {
                 float dx = sx[j] - xi, dy = sy[j] - yi, dz = sz[j] - zi;
                 min_image<true>(A.cell, dx, dy, dz);
                 SwEdge<float> ej;
-                if (!sw_edge<float>(K, dx, dy, dz, 0.f, 0.f, 0.f, ej)) continue;
-                const SwPair<float> pr = sw_pair<float>(K, ej);
-                S2 = S2 + pr.e2;
-                if (DTH) S2s = S2s + sw_pair_dsigma<float>(K, ej, pr);
+                if (!sw_edge<float>(P, dx, dy, dz, 0.f, 0.f, 0.f, ej)) continue;
+                float e2, e2s = 0.f, du = 0.f;                           // (du: the force, not needed here)
+                sw_pair<float, DTH ? 1 : 0>(P, A.p, A.q, ej, e2, e2s, du);
+                S2 = S2 + e2;
+                if (DTH) S2s = S2s + e2s;
                 const float q1 = ej.inv * ej.inv;
                 for (int u = s + 1; u < n; ++u) {
                     const int k = row_at(row, u);
                     float bx = sx[k] - xi, by = sy[k] - yi, bz = sz[k] - zi;
                     min_image<true>(A.cell, bx, by, bz);
                     SwEdge<float> ek;
-                    if (!sw_edge<float>(K, bx, by, bz, 0.f, 0.f, 0.f, ek)) continue;
+                    if (!sw_edge<float>(P, bx, by, bz, 0.f, 0.f, 0.f, ek)) continue;
                     const float c = ej.ex * ek.ex + ej.ey * ek.ey + ej.ez * ek.ez;
-                    const float dc = c - K.cos0;
+                    const float dc = c - A.cos0;
                     const float gg = ej.g * ek.g;
                     const float t3 = dc * dc * gg;
                     S3 = S3 + t3;
-                    if (DTH) S3s = S3s + K.gamma * (t3 * (ej.r * q1 + ek.r * (ek.inv * ek.inv)));
+                    if (DTH) S3s = S3s + P.gamma * (t3 * (ej.r * q1 + ek.r * (ek.inv * ek.inv)));
                 }
             }
-            // u_i = eps (S2 / 2 + lam S3) and its parameter derivatives (sw_atom's pe, psg, pl)
-            const float pe = 0.5f * S2 + K.lam * S3;
-            v[0] += K.eps * pe;
+            // u_i = eps (S2 / 2 + lam S3) and its parameter derivatives (this kernel's own sum: K23 / K28 add u_i term by term)
+            const float pe = 0.5f * S2 + lam * S3;
+            v[0] += eps * pe;
             if (DTH) {
                 v[1] += pe;
-                v[2] += K.eps * (0.5f * S2s + K.lam * S3s);
-                v[3] += K.eps * S3;
+                v[2] += eps * (0.5f * S2s + lam * S3s);
+                v[3] += eps * S3;
             }
         }
     }

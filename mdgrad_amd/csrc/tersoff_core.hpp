@@ -20,7 +20,7 @@
 //                   - P_ij dzeta_ij/dx_i                                       (a loop over row(i)),
 //                   - P_ji dzeta_ji/dx_i, i being the end of the bond j -> i,  (one loop over row(j) ...
 //                   - P_jk dzeta_jk/dx_i for every other k of row(j), i being the third atom       ... for both).
-// Both are laid out like sw_ell_kernel (csrc/sw.hip): LPA lanes walk one atom's row, wave shuffles combine the per-atom sums,
+// Both are laid out like sw_kernel (csrc/sw_core.hpp): LPA lanes walk one atom's row, wave shuffles combine the per-atom sums,
 // the energy goes through a fixed-order block partial and a finish kernel.  No float atomics => bitwise reproducible.  Rows
 // are read from global memory where they are needed, nothing is staged, so there is no row cap; the cost is O(n^2) per atom.
 // The support test 0 < r < R + D of an entry is applied on r = sqrtf(d2) with that entry's own pair constants, so the list may
@@ -74,7 +74,7 @@
 
 namespace {
 
-constexpr int TERS_LPA = 16;                  // lanes per atom: taken over from sw.hip (covalent rows hold 4 - 16 entries);
+constexpr int TERS_LPA = 16;                  // lanes per atom: taken over from sw_core.hpp (covalent rows hold 4 - 16 entries);
                                               // the choice has not been measured for these kernels
 constexpr int TERS_BLOCK = 256;
 

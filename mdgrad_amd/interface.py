@@ -1009,7 +1009,67 @@ class CoulombPotentials(_ChargeTerm, _ListTerm):
         return k.conversion * (pair - k.self_s * q.pow(2).sum())
 
 
-class StillingerWeber(_ManyBodyTerm):
+class _MovingCutoff:
+    """Mixin of a list term whose support radius moves with a trainable `sigma` (StillingerWeber, StillingerWeberMulti).  The
+    kernel applies every entry's own support test with the live sigma, so any list searched with a radius at or above the
+    support radius is exact; the module only keeps its list sufficient: it is searched with `self.cutoff`, which is kept while
+    rc <= cutoff <= `cutoff_keep` rc and otherwise reset to `cutoff_reset` rc, and `static_version()` changes with it, so
+    captured graphs are rebuilt.  A class supplies `_support_radius()`: rc of the current sigma by ONE host read, raising the
+    class's errors; it is called only outside a HIP-graph capture and only when sigma's version counter moved."""
+
+    cutoff_reset = 1.02          # a reset list is searched with this multiple of the support radius ...
+    cutoff_keep = 1.05           # ... and kept while radius <= cutoff <= this multiple of the radius (design constants)
+
+    def _init_cutoff(self, system):
+        """The state of the protocol, and half the shortest height of the cell, which no support radius may exceed."""
+        h = np.asarray(system.get_cell(), dtype=np.float64)
+        h = np.diag(h) if h.ndim == 1 else h
+        vol = abs(float(np.linalg.det(h)))
+        self._half_height = 0.5 * min(vol / float(np.linalg.norm(np.cross(h[(d + 1) % 3], h[(d + 2) % 3]))) for d in range(3))
+        self.cutoff, self._cut_ver, self._list_ver, self._sig_key = None, 0, -1, None
+
+    def _support_radius(self):
+        raise NotImplementedError
+
+    def _sync_cutoff(self):
+        """Apply the cutoff rule to the current sigma; True when the cutoff was reset.  Inside a capture, or while sigma's
+        version counter has not moved, nothing is read."""
+        s = self.sigma
+        if s.is_cuda and torch.cuda.is_current_stream_capturing():
+            return False
+        key = (s.data_ptr(), s._version)
+        if key == self._sig_key:
+            return False
+        self._sig_key = key
+        rc = self._support_radius()
+        if self.cutoff is not None and rc <= self.cutoff <= self.cutoff_keep * rc:
+            return False
+        self.cutoff = self.cutoff_reset * rc
+        self._cut_ver += 1
+        return True
+
+    def static_version(self):
+        return (super().static_version(), self._cut_ver)
+
+    def _reset_topology(self, xyz, _cache=None):
+        self._sync_cutoff()
+        super()._reset_topology(xyz, _cache)         # (a Stack member's Verlet list serves: the support test is per entry)
+        self._list_ver = self._cut_ver
+
+    def set_static_topology(self, on=True):
+        self._sync_cutoff()
+        super().set_static_topology(on)
+
+    def _current_list(self, xyz):
+        """The list to evaluate on: rebuilt here when sigma has moved the cutoff since the last search (never inside a
+        capture, where sigma is not read)."""
+        self._sync_cutoff()
+        if self._list_ver != self._cut_ver:
+            self._reset_topology(xyz.detach())
+        return self._ell
+
+
+class StillingerWeber(_MovingCutoff, _ManyBodyTerm):
     """Stillinger-Weber potential for one species (Stillinger and Weber 1985): a short-ranged pair term plus a three-body
     term that prefers the angle cos0 between the bonds of every atom to its near neighbours -- tetrahedral silicon
     (`silicon`) and monatomic coarse-grained water (`mW`, Molinero and Moore 2009).  With rc = a sigma:
@@ -1037,8 +1097,6 @@ class StillingerWeber(_ManyBodyTerm):
     d(w.F)/d(epsilon, sigma, lam) comes from the same launch plus a fixed-order reduction.  float64 or host positions take
     the torch restatement `_torch_energy`."""
 
-    cutoff_reset = 1.02          # a reset list is searched with this multiple of a sigma ...
-    cutoff_keep = 1.05           # ... and kept while a sigma <= cutoff <= this multiple of a sigma (design constants)
     # 1 kcal/mol in eV: 4184 J/mol over (1.602176634e-19 J/eV * 6.02214076e23 /mol), the exact SI values of 2019
     KCAL_PER_MOL = 4184.0 / (1.602176634e-19 * 6.02214076e23)
 
@@ -1050,10 +1108,7 @@ class StillingerWeber(_ManyBodyTerm):
         self._consts = ops.sw_consts(epsilon, sigma, lam, a, gamma, cos0, A, B, p, q)
         k = self._consts
         self.a, self.gamma, self.cos0, self.A, self.B, self.p, self.q = k.a, k.gamma, k.cos0, k.A, k.B, int(k.p), int(k.q)
-        h = np.asarray(system.get_cell(), dtype=np.float64)
-        h = np.diag(h) if h.ndim == 1 else h
-        vol = abs(float(np.linalg.det(h)))
-        self._half_height = 0.5 * min(vol / float(np.linalg.norm(np.cross(h[(d + 1) % 3], h[(d + 2) % 3]))) for d in range(3))
+        self._init_cutoff(system)
         if k.a * k.sigma > self._half_height:
             raise ValueError("StillingerWeber: a * sigma = %g exceeds half the shortest cell height (%g)"
                              % (k.a * k.sigma, self._half_height))
@@ -1067,7 +1122,6 @@ class StillingerWeber(_ManyBodyTerm):
         self._n_rep = system.get_number_of_atoms() // self._group
         self._ell = None
         self._theta_mirror = _DeviceMirror(self._thetas)
-        self.cutoff, self._cut_ver, self._list_ver, self._sig_key = None, 0, -1, None
         self._sync_cutoff()
         if torch.device(self.device).type == "cuda":
             self._reset_topology(torch.Tensor(system.get_positions()).to(system.device))
@@ -1085,38 +1139,12 @@ class StillingerWeber(_ManyBodyTerm):
         kw.setdefault("lam", 23.15)
         return cls(system, 6.189 * cls.KCAL_PER_MOL, 2.3925, **kw)
 
-    # -- the cutoff the list is searched with ---------------------------------------------------------------------
-    def _sync_cutoff(self):
-        """Apply the cutoff rule to the current sigma; True when the cutoff was reset.  Inside a capture, or while sigma's
-        version counter has not moved, nothing is read."""
-        s = self.sigma
-        if s.is_cuda and torch.cuda.is_current_stream_capturing():
-            return False
-        key = (s.data_ptr(), s._version)
-        if key == self._sig_key:
-            return False
-        self._sig_key = key
-        rc = self.a * float(s.detach())                       # (one host read per change of sigma)
+    # -- the cutoff the list is searched with: _MovingCutoff on a sigma -----------------------------------------------
+    def _support_radius(self):
+        rc = self.a * float(self.sigma.detach())              # (one host read per change of sigma)
         if not rc > 0.0:
             raise ValueError("StillingerWeber: sigma must stay positive (got %g)" % (rc / self.a))
-        if self.cutoff is not None and rc <= self.cutoff <= self.cutoff_keep * rc:
-            return False
-        self.cutoff = self.cutoff_reset * rc
-        self._cut_ver += 1
-        return True
-
-    def static_version(self):
-        return (super().static_version(), self._cut_ver)
-
-    # -- topology: the lists of PairPotentials ---------------------------------------------------------------------
-    def _reset_topology(self, xyz, _cache=None):
-        self._sync_cutoff()
-        super()._reset_topology(xyz, _cache)         # (a Stack member's Verlet list serves: the support test is per pair)
-        self._list_ver = self._cut_ver
-
-    def set_static_topology(self, on=True):
-        self._sync_cutoff()
-        super().set_static_topology(on)
+        return rc
 
     # -- the device copy of (epsilon, sigma, lam) the kernel reads -------------------------------------------------
     def _thetas(self):
@@ -1130,14 +1158,6 @@ class StillingerWeber(_ManyBodyTerm):
         self._sync_cutoff()
         if self._hip_ok():
             self._theta()
-
-    def _current_list(self, xyz):
-        """The list to evaluate on: rebuilt here when sigma has moved the cutoff since the last search (never inside a
-        capture, where sigma is not read)."""
-        self._sync_cutoff()
-        if self._list_ver != self._cut_ver:
-            self._reset_topology(xyz.detach())
-        return self._ell
 
     # -- energy ----------------------------------------------------------------------------------------------------
     def _torch_energy(self, xyz):
@@ -1176,7 +1196,7 @@ class StillingerWeber(_ManyBodyTerm):
         return ops.SWTerm(self._current_list(xyz), self._consts, self._theta())
 
 
-class StillingerWeberMulti(_ManyBodyTerm):
+class StillingerWeberMulti(_MovingCutoff, _ManyBodyTerm):
     """Stillinger-Weber potential for 1 <= S <= 4 species in the convention of LAMMPS `pair_style sw`: compounds and mixtures
     (CdTe, GaN, SiGe, mW water with a solute) from tables per ordered pair and per triplet of species.  Atom i has the species
     t_i = `types`[i]; with a = t_i (the centre), b = t_j, c = t_k
@@ -1213,12 +1233,11 @@ class StillingerWeberMulti(_ManyBodyTerm):
     the pressure of the term, the fused trajectory kernels (a Stack holding the term stays on force / force_vjp).
 
     forward(xyz) is differentiable twice in xyz and once in (epsilon, sigma, lam) on the HIP kernel (ops.SWMultiTerm,
-    csrc/sw_multi.hip: csrc/sw.hip with every constant looked up by species in a device table); force / force_vjp serve the
+    csrc/sw_multi.hip: the kernel of csrc/sw_core.hpp with every constant looked up by species in a device table); force / force_vjp serve the
     analytic adjoint and HIP-graph replay, also while the parameters require grad.  float64 or host positions take the torch
     restatement `_torch_energy`."""
 
     MAX_SPECIES = ops.SW_MULTI_MAX_SPECIES
-    cutoff_reset, cutoff_keep = StillingerWeber.cutoff_reset, StillingerWeber.cutoff_keep
     DEFAULTS = dict(a=1.80, gamma=1.20, cos0=-1.0 / 3.0, A=7.049556277, B=0.6022245584, p=4, q=0)   # StillingerWeber's
     PUBLISHED = dict(silicon=dict(epsilon=2.1683, sigma=2.0951, lam=21.0),
                      mW=dict(epsilon=6.189 * StillingerWeber.KCAL_PER_MOL, sigma=2.3925, lam=23.15))
@@ -1342,10 +1361,7 @@ class StillingerWeberMulti(_ManyBodyTerm):
                              % (self._group, ty.shape[0]))
         if not np.issubdtype(ty.dtype, np.integer) or ty.min() < 0 or ty.max() >= S:
             raise ValueError("StillingerWeberMulti: types must be integers in [0, %d)" % S)
-        cell = np.asarray(system.get_cell(), dtype=np.float64)
-        cell = np.diag(cell) if cell.ndim == 1 else cell
-        vol = abs(float(np.linalg.det(cell)))
-        self._half_height = 0.5 * min(vol / float(np.linalg.norm(np.cross(cell[(d + 1) % 3], cell[(d + 2) % 3]))) for d in range(3))
+        self._init_cutoff(system)
         rc = float((self._pair["a"] * self._pair["sigma"]).max())
         if rc > self._half_height:
             raise ValueError("StillingerWeberMulti: max a * sigma = %g exceeds half the shortest cell height (%g)"
@@ -1364,55 +1380,21 @@ class StillingerWeberMulti(_ManyBodyTerm):
         self._a32 = torch.tensor(self._pair["a"], dtype=torch.float32, device=self.device)
         self._e3 = torch.tensor(self._triplet["epsilon3"], dtype=torch.float32, device=self.device)
         self._table_mirror = _DeviceMirror(self._thetas, pack=self._pack_tables, numel=int(self._image.shape[0]))
-        self.cutoff, self._cut_ver, self._list_ver, self._sig_key = None, 0, -1, None
         self._sync_cutoff()
         if torch.device(self.device).type == "cuda":
             self._reset_topology(torch.Tensor(system.get_positions()).to(system.device))
             self._tables()
 
-    # -- the cutoff the list is searched with: StillingerWeber's rule on max_ab a_ab sigma_ab ------------------------
-    def _sync_cutoff(self):
-        """Apply the cutoff rule to the current sigma; True when the cutoff was reset.  Inside a capture, or while sigma's
-        version counter has not moved, nothing is read."""
-        s = self.sigma
-        if s.is_cuda and torch.cuda.is_current_stream_capturing():
-            return False
-        key = (s.data_ptr(), s._version)
-        if key == self._sig_key:
-            return False
-        self._sig_key = key
-        sd = s.detach()
+    # -- the cutoff the list is searched with: _MovingCutoff on max_ab a_ab sigma_ab -----------------------------------
+    def _support_radius(self):
+        sd = self.sigma.detach()
         rc, smin = torch.stack([(self._a32.to(sd.device) * sd).max(), sd.min()]).tolist()   # (one host read per change of sigma)
         if not smin > 0.0:
             raise ValueError("StillingerWeberMulti: every sigma must stay positive (got %g)" % smin)
         if rc > self._half_height:
             raise ValueError("StillingerWeberMulti: max a * sigma = %g exceeds half the shortest cell height (%g)"
                              % (rc, self._half_height))
-        if self.cutoff is not None and rc <= self.cutoff <= self.cutoff_keep * rc:
-            return False
-        self.cutoff = self.cutoff_reset * rc
-        self._cut_ver += 1
-        return True
-
-    def static_version(self):
-        return (super().static_version(), self._cut_ver)
-
-    def _reset_topology(self, xyz, _cache=None):
-        self._sync_cutoff()
-        super()._reset_topology(xyz, _cache)         # (a Stack member's Verlet list serves: the support test is per entry)
-        self._list_ver = self._cut_ver
-
-    def set_static_topology(self, on=True):
-        self._sync_cutoff()
-        super().set_static_topology(on)
-
-    def _current_list(self, xyz):
-        """The list to evaluate on: rebuilt here when sigma has moved the cutoff since the last search (never inside a
-        capture, where sigma is not read)."""
-        self._sync_cutoff()
-        if self._list_ver != self._cut_ver:
-            self._reset_topology(xyz.detach())
-        return self._ell
+        return rc
 
     # -- the device table the kernel reads: the constants plus what follows from the current (epsilon, sigma, lam) -----
     def _thetas(self):

@@ -1,4 +1,4 @@
-"""K23: the Stillinger-Weber term (StillingerWeber, mdg_sw_eval, csrc/sw.hip) against the float64 definition of tests/sw_ref.py
+"""K23: the Stillinger-Weber term (StillingerWeber, mdg_sw_eval, csrc/sw.hip on csrc/sw_core.hpp) against the float64 definition of tests/sw_ref.py
 (pinned to an independent loop and to the diamond ground state by tests/test_sw_host.py) and, in a trajectory, against the CPU
 oracle's adjoint.
 
@@ -7,7 +7,9 @@ pair and triplet contributions to that component (sw_ref.evaluate): a few ulp pe
 conditioning of gamma sigma / (r - a sigma) near the cutoff, plus a few dozen sequential float32 additions per lane.  `within`
 prints the largest observed err / (2^-24 A); on an MI355X the largest over all cases of this file were U 5.51 (perfect lattice),
 dU/dx 40.53, H.w 40.27 (both on the isolated dimer of the 37-atom set), dU/dtheta 21.80 (Si-64), d(w.dU/dx)/dtheta 4.34, the
-sum of the forces 2.10; Si-64 alone: 1.99, 12.20, 12.68, 21.80, 1.51, 0.30.
+sum of the forces 2.10; Si-64 alone: 1.99, 12.20, 12.68, 21.80, 1.51, 0.30.  With the gather of csrc/sw_core.hpp (the same terms,
+the additions in the order of the multi-species kernel) the maxima are the same five figures and the sum of the forces 0.56;
+Si-64 alone: 1.99, 13.19, 11.58, 21.80, 1.63, 0.30.
 
 Why some exceed 16, and why K stays 64: phi2' = eps A E [-(p B s^p - q s^q) / r - (B s^p - s^q) sigma / (r - a sigma)^2] is the
 sum of two product-rule terms of opposite sign that cancel at the minimum of phi2 (r = 2.35 A for silicon).  A counts the net

@@ -13,8 +13,8 @@ gas37, which holds an isolated dimer at 2.30 A like the gas case of tests/test_g
 the sum of the forces 0.30; ab64 alone: 0.25, 20.67, 14.81, 20.91, 12.00, 0.30; asym64: 1.04, 20.58, 14.56, 20.91, 10.59, 0.25;
 s3_64: 2.92, 14.90, 13.77, 20.96, 17.89, 0.22; the perfect zincblende lattice: U 1.84, dU/dx 5.70 on its own scale; the list
 searched with a skin against float64: dU/dx 16.50, H.w 14.17.  No case exceeds 64.  S = 1 and S = 2 identical silicon sets against
-the one-species float64 reference: U 1.99, dU/dx 13.19, H.w 11.80, folded dU/dtheta 22.96, folded d(w.dU/dx)/dtheta 7.28; the
-bit-identity to ops.sw_eval is printed, not asserted (this kernel adds the same terms in another order).
+the one-species float64 reference: U 1.99, dU/dx 13.19, H.w 11.80, folded dU/dtheta 22.96, folded d(w.dU/dx)/dtheta 7.28; on
+the same list the energy, dU/dx and H.w equal those of ops.sw_eval bit for bit, which is asserted (one kernel text, csrc/sw_core.hpp).
 
 Every configuration meets the input conditions of tests/test_sw_multi_host.py; one of them (sw_multi_ref.cutoff_rounding) keeps
 out atoms whose only terms lie a few tenths of an Angstrom inside a cutoff: there the rounding of the cutoff to float32 alone
@@ -173,13 +173,19 @@ def test_identical_silicon_sets_equal_the_one_species_reference(S):
     mod = StillingerWeberMulti(system, types, [StillingerWeberMulti.PUBLISHED["silicon"]] * S)
     one = StillingerWeber.silicon(system)
     th = [float(p.detach()) for p in (one.epsilon, one.sigma, one.lam)]
+    # the precondition of the bit comparison below: both modules hold the same float32 parameters
+    for name, got, want in (("epsilon", mod.epsilon, one.epsilon), ("sigma", mod.sigma, one.sigma), ("lam", mod.lam, one.lam),
+                            ("lam epsilon3", mod.lam * mod._e3, one.lam * one.epsilon)):
+        got, want = got.detach().cpu().reshape(-1), want.detach().cpu().reshape(-1)
+        assert got.dtype == torch.float32 and torch.equal(got, want.expand_as(got)), "float32 %s of the table module" % name
+    ell = one._ell                                                          # (both kernels on the same list)
     w32 = np.random.default_rng(5).normal(0, 1, x32.shape).astype(F32)
     k = R1.consts()
     lst = R1.pairs_and_triplets(x32, cell32, k["a"] * th[1])
     ref = R1.evaluate(x32, th, lst, cell32, k, w=w32)
     x, w = T(x32, DEV), T(w32, DEV)
-    o1 = _eval(mod, x, energy=True, grad=True, want_theta=True)
-    o2 = _eval(mod, x, w=w, energy=False, grad=True, want_theta=True)
+    o1 = _eval(mod, x, ell=ell, energy=True, grad=True, want_theta=True)
+    o2 = _eval(mod, x, ell=ell, w=w, energy=False, grad=True, want_theta=True)
     within(o1["energy"], ref["U"].reshape(1), ref["A_U"].reshape(1), "S = %d identical sets: U" % S)
     within(o1["grad"], ref["grad"], ref["A_grad"], "S = %d identical sets: dU/dx" % S)
     within(o2["hw"], ref["hw"], ref["A_hw"], "S = %d identical sets: H.w" % S)
@@ -190,9 +196,13 @@ def test_identical_silicon_sets_equal_the_one_species_reference(S):
         ge, gs, gl = g[:S * S].sum(), g[S * S:2 * S * S].sum(), g[2 * S * S:].sum()
         fold = torch.stack([ge + lam * gl / eps, gs, gl])
         within(fold, ref[rk], ref["A_" + rk], "S = %d identical sets: folded %s" % (S, rk))
-    b = ops.sw_eval(one._ell, x, one._consts, one._theta(), energy=True, grad=True)
-    print("S = %d: bit-identical to ops.sw_eval: U %s, dU/dx %s" % (S, bool(torch.equal(b["energy"], o1["energy"])),
-                                                                     bool(torch.equal(b["grad"], o1["grad"]))))
+    # one text (csrc/sw_core.hpp): on the same list the table kernel and the one-species kernel run the same operations in the
+    # same order on the same float32 constants, so the energy, dU/dx and H.w agree bit for bit.  (The parameter rows keep the
+    # tolerance comparison above: their epsilon column means something else in the two classes.)
+    b1 = ops.sw_eval(ell, x, one._consts, one._theta(), energy=True, grad=True)
+    b2 = ops.sw_eval(ell, x, one._consts, one._theta(), w=w, energy=False, grad=True)
+    assert torch.equal(b1["energy"], o1["energy"]) and torch.equal(b1["grad"], o1["grad"]), "LEVEL 1: U and dU/dx of ops.sw_eval"
+    assert torch.equal(b2["grad"], o2["grad"]) and torch.equal(b2["hw"], o2["hw"]), "LEVEL 2: dU/dx and H.w of ops.sw_eval"
 
 
 # ------------------------------------------------------------------------------------------------ 4: relabelling
